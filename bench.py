@@ -6,19 +6,23 @@ A "step" is one pass of the hot path over one batch: the full 200-candidate path
 src/path.cpp:37, then Algorithm::fit to PDAS convergence + train_loss + ic per candidate) on data that is already resident
 in HBM (upload + normalisation are untimed and reported separately).
 
-OUTPUT.  Rank 0 prints ONE line of strict JSON as the LAST line of stdout, at most 6 KB: the contract keys, `roofline`
-(HIP-event timing of the kernel that streams X; covariance form: both roofs per launch width, the binding one on top),
-`cpu_baseline`, the streaming leg's flat keys `roofline.streaming_*`, and a few figures per other config.  The full record
-(every leg, segments of the CPU timing, histograms, the k-path report) goes to gpurun_out/bench_detail.json
-(BESSX_BENCH_DETAIL_STDOUT=1: also as an EARLIER stdout line).
+OUTPUT.  Rank 0 prints ONE line of strict JSON as the LAST line of stdout, at most 6 KB: the contract keys (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...); with --full also
+`roofline` (HIP-event timing of the kernel that streams X; covariance form: both roofs per launch width, the binding one
+on top), `cpu_baseline`, the streaming leg's flat keys `roofline.streaming_*`, and a few figures per other config.  The
+full record (every leg, segments of the CPU timing, histograms, the k-path report) goes to the side file DETAIL_PATH
+(BESSX_BENCH_DETAIL_PATH overrides it; BESSX_BENCH_DETAIL_STDOUT=1: also as an EARLIER stdout line).
 
-Two evaluations of the score pass are timed with the same --steps / --warmup at N = 1: the headline is the covariance
-form (cached Gram columns; `config.headline_mode`), and the STREAMING formulation north_star prescribes -- every PDAS
-iteration reads X once -- is in `roofline.streaming_*` (candidates/s, ms per step, k_xtv against the HBM roof, the whole
-step against the HBM roof) and in `streaming_score_pass`.
+A plain run sets up, warms up, times the --steps steps and prints the line; everything else it can measure or check is
+behind --full.  --dump-outputs DIR writes what the last timed step returned (bench.dump_outputs) as DIR/<name>.npy.
+
+With --full, two evaluations of the score pass are timed with the same --steps / --warmup at N = 1: the headline is
+the covariance form (cached Gram columns; `config.headline_mode`), and the STREAMING formulation north_star prescribes --
+every PDAS iteration reads X once -- is in `roofline.streaming_*` (candidates/s, ms per step, k_xtv against the HBM roof,
+the whole step against the HBM roof) and in `streaming_score_pass`.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload lm-seq|lm-cv-gs] [--shard kpath|replica]
-                  [--n N --p P --kmax KMAX] [--no-cpu-baseline]
+                  [--n N --p P --kmax KMAX] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
 
 --gpus N > 1 without a launcher (WORLD_SIZE unset): this process starts N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU)
@@ -28,8 +32,9 @@ WORLD_SIZE must equal --gpus.
 N > 1, default (--shard kpath): STRONG scaling of the ONE configs[1] problem, partitioned as north_star says.  X is
 replicated; s.list = 1..200 is cut into N contiguous chunks, each chunk one warm-start chain (bess_amd/dist.py
 partition), stitched into the single chain (dist.StitchedKPath); NO data-path collective: RCCL carries the IC curve
-(8 B per candidate) and the chunks' last models (a few KB per stitch round).  After the timed region rank 0 runs the
-single chain and the line reports for how many k the supports agree (all of them, by construction of the stitch).
+(8 B per candidate) and the chunks' last models (a few KB per stitch round).  With --full, after the timed region
+rank 0 runs the single chain and the line reports for how many k the supports agree (all of them, by construction of
+the stitch).
 --coop-variant (opt-in): the same steps once more with the cooperative prefill / pilot policy (Gram column blocks
 all-gathered between the ranks -- a data-path collective north_star does not have), as a second figure
 `cooperative_prefill_variant` in the same line; --prefill / --pilot make that variant the timed one.
@@ -44,12 +49,13 @@ chain and, in the final sweep, (fold x s) pairs dealt to the ranks (bess_amd.dis
 BESSX_BENCH_ONE_DEVICE=1 rehearses the N-rank path on a box with ONE GPU (ranks share device 0, collectives over
 gloo) -- never what the driver runs.
 
-At N = 1 with the default sizes the record also carries `other_configs`: one timed path each of BASELINE configs[2]
-(logistic n=100k p=5k k<=100), configs[3] (LM gs_path + 5-fold CV) and configs[4] (Cox n=200k p=20k k<=150) with the
-kernel that streams X against the HBM roof and the time per IRLS / Newton step (--no-other-configs skips them; they
-add about two minutes, most of it generating and uploading the 32 GB Cox design).
+With --full at N = 1 and the default sizes the record also carries `other_configs`: one timed path each of BASELINE
+configs[2] (logistic n=100k p=5k k<=100), configs[3] (LM gs_path + 5-fold CV) and configs[4] (Cox n=200k p=20k k<=150)
+with the kernel that streams X against the HBM roof and the time per IRLS / Newton step (--no-other-configs skips them;
+they add about two minutes, most of it generating and uploading the 32 GB Cox design).
 """
 import argparse
+import datetime
 import json
 import os
 import socket
@@ -131,6 +137,14 @@ def parse_args(argv=None):
                     help="skip the extra (untimed-by-contract) measurement of the streaming score pass at N=1")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the N=1 measurements of BASELINE configs[2], [3], [4] (other_configs in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline figure: the figures from the HIP-event timing of the "
+                         "kernel that streams X in the timed steps (roofline, whole_step, group_XTX), the device's copy "
+                         "bandwidth, the single-chain comparisons, the streaming leg, the CPU baseline and the other "
+                         "configs; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64; the inputs are seeded, so two builds can be compared output for output)")
     args = ap.parse_args(argv)
     args.chunk_start_option = args.chunk_start
     dn, dp, dk, dt = (200000, 20000, 150, 75) if args.workload == "cox-seq" else (50000, 10000, 200, 100)
@@ -654,6 +668,33 @@ def _round(v, nd=6):
     return v
 
 
+DUMP_LIMIT = 64 << 20  # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(dirpath, res):
+    """--dump-outputs: every numeric entry of a path result (arrays, scalars, ragged per-candidate lists padded with NaN)
+    as `dirpath/<name>.npy` in float64.  Left out: device_seconds (a timing) and the trace (a record of the run)."""
+    arrays = {}
+    for name, v in res.items():
+        if name in ("device_seconds", "trace") or v is None or isinstance(v, dict):
+            continue
+        if isinstance(v, (list, tuple)) and v and all(np.ndim(x) == 1 for x in v):
+            a = np.full((len(v), max(len(x) for x in v)), np.nan)
+            for i, x in enumerate(v):
+                a[i, :len(x)] = x
+        else:
+            a = np.asarray(v)
+            if a.dtype.kind not in "biuf":
+                continue
+        arrays[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
 
@@ -668,9 +709,10 @@ def compact_line(full):
     cfg = full.get("config", {})
     line["config"] = _pick(cfg, ["workload", "candidates_per_step", "score_pass", "headline_mode", "units_sharded",
                                  "collective", "communicator", "ranks_with_work", "streaming_mode"])
-    roof = dict(full.get("roofline", {}))
-    roof.pop("traffic_source", None)
-    line["roofline"] = roof
+    if full.get("roofline"):
+        roof = dict(full["roofline"])
+        roof.pop("traffic_source", None)
+        line["roofline"] = roof
     cb = full.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = _pick(cb, ["value", "unit", "cores", "kind", "sample", "cpu_model", "host_cores",
@@ -782,6 +824,13 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
+        if world > 1:
+            # every rank says so before any of them exits: the launcher stops the other ranks when the first one ends
+            print("bench.py needs a GPU: libbessx has no CPU path", file=sys.stderr, flush=True)
+            dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=120))
+            dist.barrier()
+            dist.destroy_process_group()
+            sys.exit(1)
         raise SystemExit("bench.py needs a GPU: libbessx has no CPU path")
     one_dev = os.environ.get("BESSX_BENCH_ONE_DEVICE") == "1"
     if one_dev:
@@ -924,6 +973,8 @@ def main():
                                    coarse_lead=coarse_lead, comm=own_comm) if kpath else None
     for _ in range(args.warmup):
         out = stitched.step() if kpath else sess.sequential_path(seq, ic_type=3)
+    # event pairs around every launch of the kernel that streams X, with or without --full: the timed steps stay the ones
+    # the headline has always been measured on; only --full reads them (roofline, whole_step, group_XTX)
     sess.enable_kernel_timing(True)
     sess.score_pass_stats(reset=True)
     barrier()
@@ -942,9 +993,17 @@ def main():
             ic_curves = bdist.gather_rows(out["cand_ic"], world, device=comm_dev)
     barrier()
     dt = max_over_ranks(time.time() - t0)
-    k1 = sess.score_pass_stats()
-    cw = sess.counters()  # (panel launches by width, device time of the last group_XTX pass: read before any reset)
+    if args.full:
+        k1 = sess.score_pass_stats()
+        cw = sess.counters()  # (panel launches by width, device time of the last group_XTX pass: read before any reset)
     sess.enable_kernel_timing(False)
+    if args.dump_outputs and rank == 0:
+        if kpath:  # the stitched path's IC curve and choice, and this rank's chunk of the candidates
+            res = {"chunk_" + k: v for k, v in (stitch["chunk"] or {}).items()}
+            res.update({"ic_curve": stitch["ic_curve"], "best_k": stitch["best_k"]})
+        else:
+            res = dict(out, ic_curves=ic_curves) if ic_curves is not None else out
+        dump_outputs(args.dump_outputs, res)
 
     coop_variant = None
     if kpath and args.coop_variant and covariance and not cox:
@@ -973,7 +1032,7 @@ def main():
             coop_variant = {"value": None, "what": "the measured policy asks for no prefill at this N / size"}
 
     chunk_report = None
-    if kpath:
+    if kpath and args.full:
         # compare the chunked chains with the single warm-start chain, after the timed region
         bounds = stitch["bounds"]  # (of the last timed step: the boundaries move when --rebalance is on)
         lo, hi = bounds[rank], bounds[rank + 1]
@@ -1094,16 +1153,7 @@ def main():
     if rank == 0:
         n_cand = args.kmax * args.steps * (1 if (kpath or not distributed) else world)
         value = n_cand / dt
-        roof = roofline_of(k1, covariance, widths_of(cw))
-        roof["passes_over_X_timed"] = float(k1["launches"])
-        try:  # the spec peak next to a ceiling measured on this very device (read + write of a D2D copy)
-            roof["measured_stream_copy_GBps"] = capi.op_stream_copy_gbps(1 << 30, 10)
-        except Exception:
-            roof["measured_stream_copy_GBps"] = None
         step_s = dt / args.steps
-        x_seconds = k1["seconds"] / args.steps
-        # passes over X per step: the timed launches of the kernel that streams X + (LM) the group_XTX pass of every path
-        x_passes = k1["launches"] / float(args.steps) + (0.0 if cox else 1.0)
         line = {
             "metric": ("candidate subsets solved/sec (Cox n=%dk,p=%dk,k<=%d)" % (args.n // 1000, args.p // 1000, args.kmax)
                        if cox else "candidate subsets solved/sec (n=50k,p=10k,k<=200 LM)"), "value": value,
@@ -1133,28 +1183,39 @@ def main():
                        # k-path chunks: every rank owns a chunk of at least one candidate as long as N <= kmax
                        "ranks_with_work": min(world, args.kmax) if kpath else world,
                        "chunk_start": (args.chunk_start_option if kpath else None)},
-            "roofline": roof,
-            # the WHOLE step against the HBM roof: bytes the step streams from X / step time, and where the time goes
-            "whole_step": {"bytes_streamed_from_X": x_passes * 8.0 * args.n * args.p,
-                           "achieved_GBps": x_passes * 8.0 * args.n * args.p / step_s / 1e9,
-                           "frac_of_hbm_peak": x_passes * 8.0 * args.n * args.p / step_s / 1e9 / HBM_PEAK_GBPS,
-                           # (passes over X never overlap each other: one chain at a time holds the fill right -- staged
-                           # fills run beside other chains' selection / solve kernels, not beside another pass -- so the
-                           # summed launch time of the kernel that streams X is a true share of the step)
-                           "time": {"wall_ms": 1e3 * step_s, "summed_kernel_ms_streaming_X": 1e3 * x_seconds,
-                                    "kernel_streaming_X_share": min(1.0, x_seconds / step_s),
-                                    "candidate_chain_and_host_share (selection, k x k solve, p x k GEMV, publish)":
-                                    max(0.0, 1.0 - x_seconds / step_s)}},
-            "passes_over_X_per_candidate": x_passes / float(max(len(seq), 1)),
             "pdas_iterations_per_candidate": pdas_iters / float(max(len(seq), 1) * args.steps),
             # I_k of SURVEY 8d: PDAS iterations Algorithm::fit took per candidate (identical to the reference's,
             # tests/test_fullsize_gpu.py), as a histogram {iterations: candidates}
             "pdas_iterations_histogram": {str(int(k)): int(v) for k, v in
                                           zip(*np.unique(out["cand_iters"], return_counts=True))},
             "upload_and_normalise_seconds": upload_s,
-            "selected_k": int(out["best_T0"]) if not kpath else chunk_report["best_k_chunked"],
+            "selected_k": int(out["best_T0"]) if not kpath else int(stitch["best_k"]),
             "selected_ic": float(out["ic"]) if not kpath else float(np.min(ic_curves[0])),
         }
+        if args.full:
+            roof = roofline_of(k1, covariance, widths_of(cw))
+            roof["passes_over_X_timed"] = float(k1["launches"])
+            try:  # the spec peak next to a ceiling measured on this very device (read + write of a D2D copy)
+                roof["measured_stream_copy_GBps"] = capi.op_stream_copy_gbps(1 << 30, 10)
+            except Exception:
+                roof["measured_stream_copy_GBps"] = None
+            x_seconds = k1["seconds"] / args.steps
+            # passes over X per step: the timed launches of the kernel that streams X + (LM) the group_XTX pass of every path
+            x_passes = k1["launches"] / float(args.steps) + (0.0 if cox else 1.0)
+            line["roofline"] = roof
+            # the WHOLE step against the HBM roof: bytes the step streams from X / step time, and where the time goes
+            line["whole_step"] = {
+                "bytes_streamed_from_X": x_passes * 8.0 * args.n * args.p,
+                "achieved_GBps": x_passes * 8.0 * args.n * args.p / step_s / 1e9,
+                "frac_of_hbm_peak": x_passes * 8.0 * args.n * args.p / step_s / 1e9 / HBM_PEAK_GBPS,
+                # (passes over X never overlap each other: one chain at a time holds the fill right -- staged fills run
+                # beside other chains' selection / solve kernels, not beside another pass -- so the summed launch time
+                # of the kernel that streams X is a true share of the step)
+                "time": {"wall_ms": 1e3 * step_s, "summed_kernel_ms_streaming_X": 1e3 * x_seconds,
+                         "kernel_streaming_X_share": min(1.0, x_seconds / step_s),
+                         "candidate_chain_and_host_share (selection, k x k solve, p x k GEMV, publish)":
+                         max(0.0, 1.0 - x_seconds / step_s)}}
+            line["passes_over_X_per_candidate"] = x_passes / float(max(len(seq), 1))
         if chunk_report:
             line["kpath_chunks_vs_single_chain"] = chunk_report
             # Amdahl's arithmetic of the partition north_star names (X replicated, contiguous chunks of s.list, no data-path
@@ -1168,9 +1229,9 @@ def main():
                          "repeated on every rank (DESIGN.md section 6)"}
         if coop_variant:
             line["cooperative_prefill_variant"] = coop_variant
-        norm = sess.normalization() if world == 1 else None
-        cnt = sess.counters() if world == 1 else {}
-        if not cox:
+        norm = sess.normalization() if (world == 1 and args.full) else None
+        cnt = sess.counters() if (world == 1 and args.full) else {}
+        if args.full and not cox:
             # the reference forms X^T y / diag(X^T X) inside every sequential_path call (group_XTX, src/path.cpp:37) and so
             # does every path call here (bessx_paths.cpp run_path): that pass over X IS in the step.  Its device time (HIP
             # events, last path) and the step without it as side keys (rounds 1-5 had it at session creation):
@@ -1204,7 +1265,7 @@ def main():
                 "what": "a coarse warm-start chain over the chunk boundaries fills the cache and starts every chunk; the "
                         "chunks run side by side on fit contexts of their own (a stream and a host thread each), fills "
                         "of the shared cache while every other chain stands still; stitched like the multi-GPU k-path"}
-        if covariance and world == 1 and not args.no_streaming_leg and not cox:
+        if args.full and covariance and world == 1 and not args.no_streaming_leg and not cox:
             # the other evaluation of the same path (every PDAS iteration reads X once), for comparison
             sess.close()
             s2 = capi.Session(X, y, data_type=1, is_normal=True, model_type=1, max_iter=20, is_warm_start=True,
@@ -1298,13 +1359,14 @@ def main():
         if ic_curves is not None and not kpath:
             line["ic_curves_gathered"] = int(ic_curves.shape[0])
             line["best_k_per_problem"] = [int(bdist.select_best(c)) + 1 for c in ic_curves]
-        if not args.no_cpu_baseline and world == 1 and not cox:
+        if args.full and not args.no_cpu_baseline and world == 1 and not cox:
             try:
                 line["cpu_baseline"] = cpu_baseline(X, y, out, norm, args.kmax, args.cpu_budget)
             except Exception as e:  # the checker is optional for the measurement itself
                 line["cpu_baseline"] = {"value": None, "unit": "candidates/s", "cores": 1, "kind": "port",
                                         "sample": "failed: %r" % (e,)}
-        if world == 1 and not cox and not args.no_other_configs and (args.n, args.p, args.kmax) == (50000, 10000, 200):
+        if (args.full and world == 1 and not cox and not args.no_other_configs and
+                (args.n, args.p, args.kmax) == (50000, 10000, 200)):
             sess.close()
             try:
                 line["other_configs"] = measure_other_configs(local_rank, X, y,
@@ -1343,6 +1405,8 @@ def bench_cv(args, world, rank, local_rank, comm_dev, barrier, max_over_ranks):
         out = bdist.FoldShardedCV(sess, 5, world, rank, device=cdev).gs_path(1, args.kmax)
     barrier()
     dt = max_over_ranks(time.time() - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
         emit({
             "metric": "candidate subsets solved/sec (n=50k,p=10k, LM gs_path + 5-fold CV)",

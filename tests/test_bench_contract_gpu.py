@@ -1,10 +1,12 @@
-"""bench.py's output contract on a small problem (the driver parses this line): one JSON object with the metric,
-the roofline of the kernel that streams X (HIP-event timing), and the CPU baseline."""
+"""bench.py's output contract on a small problem (the driver parses this line): one JSON object with the metric and,
+with --full, the roofline of the kernel that streams X (HIP-event timing) and the CPU baseline; a plain run's line and
+the outputs it dumps."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,8 +22,8 @@ def test_bench_line(gpu):
     if os.path.exists(detail):
         os.unlink(detail)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "3000", "--p", "800", "--kmax", "30",
-                          "--k-true", "10", "--steps", "2", "--warmup", "1"], cwd=ROOT, capture_output=True, text=True,
-                         timeout=600)
+                          "--k-true", "10", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, capture_output=True,
+                         text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     # the driver parses the LAST line of stdout out of an 8 KB tail: one strict-JSON object, small
@@ -68,3 +70,29 @@ def test_bench_line(gpu):
     assert sum(full["pdas_iterations_histogram"].values()) == 30
     assert full["whole_step"]["time"]["wall_ms"] > 0
     assert abs(full["value"] - d["value"]) < 1e-4 * d["value"]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """Without --full: the contract keys and nothing measured beside the steps; --dump-outputs writes the last timed
+    step's result, the same as the path run here on the same seeded problem."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "3000", "--p", "800", "--kmax", "30",
+                          "--k-true", "10", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.splitlines()[-1], parse_constant=_reject_constant)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "candidates/s" and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] - 30 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-4 * d["value"]
+    for k in ("roofline", "whole_step", "cpu_baseline", "streaming_score_pass", "chunk_chains", "other_configs",
+              "group_XTX_ms_inside_step"):
+        assert k not in d, k
+    from bess_amd import synth
+    X, y, _, _ = synth.make_lm(3000, 800, 10)
+    with gpu.Session(X, y, data_type=1, is_normal=True, model_type=1, max_iter=20, is_warm_start=True) as s:
+        want = s.sequential_path(np.arange(1, 31), ic_type=3)
+    for k in ("beta", "cand_T0", "cand_iters", "cand_support", "cand_beta", "cand_ic", "cand_train_loss", "best_T0", "ic"):
+        got = np.load(os.path.join(str(tmp_path), k + ".npy"))
+        assert got.dtype == np.float64, k
+        np.testing.assert_allclose(got, np.asarray(want[k], dtype=np.float64), rtol=1e-9, atol=0, err_msg=k)
+    assert not os.path.exists(os.path.join(str(tmp_path), "device_seconds.npy"))

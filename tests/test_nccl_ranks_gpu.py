@@ -33,7 +33,7 @@ def _bench_nccl(extra, timeout=900):
         env["BESSX_BENCH_ERRDIR"] = errdir
         env["BESSX_BENCH_DETAIL_PATH"] = os.path.join(errdir, "detail.json")
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "3000", "--p", "800", "--kmax", "30",
-                              "--k-true", "10", "--steps", "2", "--warmup", "1", "--gpus", "2"] + extra, cwd=ROOT,
+                              "--k-true", "10", "--steps", "2", "--warmup", "1", "--gpus", "2", "--full"] + extra, cwd=ROOT,
                              capture_output=True, text=True, timeout=timeout, env=env)
         errs = []
         for f in sorted(glob.glob(os.path.join(errdir, "*.err"))):

@@ -33,8 +33,8 @@ def _run_bench(extra, env=None, timeout=900):
         e["BESSX_BENCH_ERRDIR"] = errdir
         e["BESSX_BENCH_DETAIL_PATH"] = os.path.join(errdir, "detail.json")
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "3000", "--p", "800", "--kmax", "30",
-                              "--k-true", "10", "--steps", "2", "--warmup", "1"] + extra, cwd=ROOT, capture_output=True,
-                             text=True, timeout=timeout, env=e)
+                              "--k-true", "10", "--steps", "2", "--warmup", "1", "--full"] + extra, cwd=ROOT,
+                             capture_output=True, text=True, timeout=timeout, env=e)
         assert out.returncode == 0, "bench.py %s -> rc %d\n%s\n==== [rank ..] lines on stdout\n%s\n==== stderr (tail)\n%s" % (
             " ".join(extra), out.returncode, _rank_errors(errdir),
             "\n".join(ln for ln in out.stdout.splitlines() if ln.startswith("[rank")), out.stderr[-1500:])
