@@ -33,7 +33,7 @@ SYMBOLS = [
     "bessx_session_cov_prefill_export", "bessx_session_cov_prefill_import", "bessx_session_cov_prefill_end",
     "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
-    "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench",
+    "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -112,6 +112,8 @@ def lib():
         L.bessx_session_set_cv.argtypes = [_vp, _i, _I, ctypes.c_uint]
         L.bessx_session_get_cv_folds.argtypes = [_vp, _I]
         L.bessx_session_sequential_path.argtypes = [_vp, _I, _i, _D, _i, _i, _i, ctypes.POINTER(PathResult)]
+        L.bessx_session_set_responses.argtypes = [_vp, _D, _i, _i]
+        L.bessx_session_sequential_path_multi.argtypes = [_vp, _I, _i, _D, _i, _i, _i, ctypes.POINTER(PathResult)]
         L.bessx_session_gs_path.argtypes = [_vp, _i, _i, _i, _i, ctypes.POINTER(PathResult)]
         L.bessx_session_pgs_path.argtypes = [_vp, _i, _i, _d, _d, _i, _i, _i, _i, ctypes.POINTER(PathResult)]
         L.bessx_session_trace_enable.argtypes = [_vp, _i]
@@ -307,7 +309,8 @@ class Session:
                  23: "kpath_chunks_us", 24: "kpath_stitch_us", 25: "panel_launches_one_group",
                  26: "panel_ns_one_group", 27: "panel_launches_two_groups", 28: "panel_ns_two_groups",
                  29: "shared_pass_launches", 30: "shared_pass_chain_slots", 31: "shared_pass_partial_batches",
-                 32: "own_queue_streams_created_by_the_process"}  # (4-6: mechanisms removed in round 3)
+                 32: "own_queue_streams_created_by_the_process", 33: "multi_responses_batched",
+                 34: "multi_responses_host", 35: "multi_union_fills"}  # (4-6: mechanisms removed in round 3)
         return {n: int(lib().bessx_session_counter(self._h, i)) for i, n in names.items()}
 
     def screening(self):
@@ -374,7 +377,8 @@ class Session:
         _check(lib().bessx_session_get_normalization(self._h, _dp(xm), _dp(xn), ctypes.byref(ym)))
         return xm, xn, ym.value
 
-    def _run(self, call, capacity, max_T0):
+    def _result(self, res, capacity, max_T0):
+        """Caller-allocated arrays of one bessx_path_result, bound into res."""
         beta = np.zeros(self.p)
         arr = {
             "cand_T0": np.zeros(capacity, dtype=np.int32), "cand_lambda": np.zeros(capacity),
@@ -382,20 +386,27 @@ class Session:
             "cand_ic": np.zeros(capacity), "cand_coef0": np.zeros(capacity),
             "cand_support": np.full((capacity, max_T0), -1, dtype=np.int32), "cand_beta": np.zeros((capacity, max_T0)),
         }
-        res = PathResult()
         res.beta = _dp(beta)
         res.capacity = capacity
         res.max_T0 = max_T0
         for k, v in arr.items():
             setattr(res, k, _ip(v) if v.dtype == np.int32 else _dp(v))
+        return beta, arr
+
+    def _run(self, call, capacity, max_T0):
+        res = PathResult()
+        beta, arr = self._result(res, capacity, max_T0)
         _check(call(ctypes.byref(res)))
+        return self._collect(res, beta, arr, capacity)
+
+    def _collect(self, res, beta, arr, capacity, trace=None):
         nc = min(res.n_candidates, capacity)
         out = {"beta": beta, "coef0": res.coef0, "train_loss": res.train_loss, "ic": res.ic, "lambda": res.lambda_,
                "best_T0": res.best_T0, "best_iters": res.best_iters, "n_candidates": res.n_candidates,
                "device_seconds": res.device_seconds, "n_fits": res.n_fits, "n_pdas_iters": res.n_pdas_iters}
         for k, v in arr.items():
             out[k] = v[:nc]
-        out["trace"] = self._trace()
+        out["trace"] = self._trace() if trace is None else trace
         return out
 
     def sequential_path(self, sequence, lambda_seq=(0.0,), ic_type=4, is_cv=False):
@@ -405,6 +416,40 @@ class Session:
         return self._run(lambda r: L.bessx_session_sequential_path(self._h, _ip(seq), seq.size, _dp(lam), lam.size,
                                                                    ic_type, int(is_cv), r),
                          seq.size * lam.size, min(self.p, (int(seq.max()) if seq.size else 1) * self._gsize_max))
+
+    def set_responses(self, Y):
+        """R extra responses for this session's design (bessx_session_set_responses): Y is n x R; every column is
+        prepared like the session's own y.  Replaces an earlier set; the session's own y stays."""
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y.reshape(-1, 1)
+        if Y.ndim != 2 or Y.shape[0] != self.n:
+            raise ValueError("Y must have shape (n, R) with n = %d rows" % self.n)
+        if np.isnan(Y).any():
+            raise ValueError("Y contains NaN")
+        Yc = np.asfortranarray(Y)
+        _check(lib().bessx_session_set_responses(self._h, _dp(Yc), Yc.shape[1], 1))
+        self._n_responses = Yc.shape[1]
+
+    def sequential_path_multi(self, sequence, lambda_seq=(0.0,), ic_type=4):
+        """sequential_path once per response of set_responses (bessx_session_sequential_path_multi): a list with what
+        sequential_path returns, one entry per column of Y."""
+        R = getattr(self, "_n_responses", 0)
+        if R < 1:
+            raise ValueError("call set_responses first")
+        seq, lam = _i32(sequence), _f64(lambda_seq)
+        capacity = seq.size * lam.size
+        max_T0 = min(self.p, (int(seq.max()) if seq.size else 1) * self._gsize_max)
+        results = (PathResult * R)()
+        bufs = [self._result(results[r], capacity, max_T0) for r in range(R)]
+        _check(lib().bessx_session_sequential_path_multi(self._h, _ip(seq), seq.size, _dp(lam), lam.size, ic_type, 0,
+                                                         results))
+        trace = self._trace()
+        out = []
+        for r in range(R):
+            o = self._collect(results[r], bufs[r][0], bufs[r][1], capacity, trace)
+            out.append(o)
+        return out
 
     def sequential_path_chain(self, sequence, lambda_seq=(0.0,), ic_type=4, is_cv=False, init_idx=(), init_val=(),
                               init_coef0=0.0, keep_caches=False, stop_support=None, stop_beta=None, stop_rtol=1e-9,

@@ -49,6 +49,9 @@ struct GramTask {
 };
 
 hipError_t launch_transpose_in(const double *src, int rows, int p, double *X, long ld, long r0, hipStream_t st);
+// k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
+hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
+                                  int add_weight, double *y_mean, double *yy, hipStream_t st);
 hipError_t launch_normalize(double *X, long ld, int n, int p, double *y, const double *w, int data_type,
                             int is_normal, int add_weight, double *x_mean, double *x_norm, double *y_mean,
                             hipStream_t st);
@@ -267,6 +270,8 @@ hipError_t launch_mc_status(const McChain *chains, int nchains, unsigned char *h
 hipError_t launch_mc_resume(const McChain *chains, int chain, hipStream_t st);
 // stop a chain where it stands (the host takes it over)
 hipError_t launch_mc_stop(const McChain *chains, int chain, hipStream_t st);
+// launch_mc_resume for the chains chain[0..n) (device list) in one launch
+hipError_t launch_mc_resume_list(const McChain *chains, const int *chain, int n, hipStream_t st);
 
 hipError_t launch_chol_big(double *Gt, int m, int mt, double ridge, int ridge_skip0, const double *rhs,
                            const int *rhs_gather, double *sol, int *info, double *rdiag, double *z,
@@ -433,6 +438,11 @@ struct CovUnion {
   const int *list[8];  // the column sets that have to be cached when the fill is done
   int len[8];
   int on_restart[8];   // 1: this set is already cached -- it is listed only if the cache is started over
+  // more sets than the 8 above (the merged run of many responses): dn of them, device arrays of their lists and
+  // lengths, listed after the fixed ones (on_restart 0)
+  int dn;
+  const int *const *dlist;
+  const int *dlen;
 };
 // restart: 0 keep the cache, 1 start it over, 2 decide on the device -- start over iff the columns the due lists miss
 // (counted per list: an upper bound) do not fit the C-column cache; fill_ctrl->cov_nmiss tells which it was

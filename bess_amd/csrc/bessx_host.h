@@ -287,6 +287,15 @@ struct bessx_session {
   int *kch_slot_w = nullptr;            // (owner) the writer's slot map of staged fills, p ints
   hipStream_t kch_fill_st = nullptr;    // (owner) the stream the chains' staged fills run on (some compute units left out)
   hipEvent_t kch_ev = nullptr;          // (chain context) orders its fill list in front of the fill on kch_fill_st
+  // extra responses of the design (bessx_session_set_responses, bessx_multi.cpp): R prepared columns (ld each), their
+  // means, y.y and null losses; the session's own response while one of them is installed; counters 33-35
+  int resp_R = 0;
+  double *resp_y = nullptr, *resp_xty = nullptr, *resp_part = nullptr, *own_xty = nullptr;
+  std::vector<double> resp_mean, resp_yy, resp_null;
+  double *own_y = nullptr;
+  double own_yy = 0.0, own_mean = 0.0, own_null = 0.0;
+  long long multi_batched = 0, multi_host = 0, multi_fills = 0;
+  bool fcols_wide = false;  // cov_fcols holds every column (+ 4 COV_R): the union fill of many responses' lists
   long long kch_merged = 0, kch_takeovers = 0;  // chunk phases run as merged launches; chains the host had to finish
   long long kch_paths = 0, kch_refits = 0, kch_chunk_fills = 0;  // paths run chunked, stitch refits, fills in the chunk phase
   int kch_last_chains = 0;              // chains of the last chunked path
@@ -477,10 +486,34 @@ bool shared_pass_applies(const bessx_session *c);  // chain context whose passes
 int shared_pass_submit(bessx_session *c, const double *v, const double *v2, double *part, double *part2,
                        const CoxBufs *cox, const FitCtrl *ctrl, int slot);
 void kchains_free(bessx_session *s);
+// merged launches over chains on the session's stream (bessx_kchunks.cpp): a chain is a chunk of one response's path or
+// the whole path of one response (bessx_multi.cpp)
+struct McJob {
+  bessx_session *c = nullptr;           // the chain's fit context (mc_contexts)
+  int lo = 0, ncand = 0;                // its levels: seq[lo .. lo + ncand)
+  int rec0 = 0;                         // its first row of the records
+  const std::vector<int> *init_idx = nullptr;  // the model its first candidate starts from (normalised; may be NULL)
+  const std::vector<double> *init_val = nullptr;
+  double init_coef0 = 0.0;
+  const double *xty = nullptr;          // X^T y of its response (device); NULL: the context's own
+};
+struct McRecords {  // per candidate row: MC_REC_I ints, MC_REC_D doubles, width support entries and coefficients
+  std::vector<int> i, A;
+  std::vector<double> d, b;
+};
+bool mc_engine_applies(const bessx_session *s);
+// |y - X beta|^2 of a model by a pass over its columns, on the context's y (the loss when the solve's terms cancel)
+int mc_sse_by_residual(bessx_session *c, hipStream_t st, const int *idx, const double *val, int T0, double coef0, double *out);
+int mc_contexts(bessx_session *s, int n);           // at least n merged-run contexts in s->kch (apart from the chunk chains')
+void kchains_contexts(const bessx_session *s, std::vector<bessx_session *> *out);  // every chain context of s
+bessx_session *mc_context(bessx_session *s, int i);
+int mc_engine(bessx_session *s, const int *seq, int ns, std::vector<McJob> &jobs, int nrec, double lambda, int width,
+              McRecords &rec, std::vector<int> &takeover, long long *fills);
 void kchains_quiesce(bessx_session *s);
 int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm = false);
 hipError_t cox_alloc(bessx_session *s);                        // bessx_session.cpp
-int chain_ctx_create(bessx_session *ps, bessx_session **out);  // bessx_session.cpp
+// (own_queue = false: an ordinary stream -- the contexts of a merged run of many responses queue nothing on theirs)
+int chain_ctx_create(bessx_session *ps, bessx_session **out, bool own_queue = true);  // bessx_session.cpp
 void chain_ctx_free(bessx_session *c);
 int prefill_begin(bessx_session *s, const int *cols, int ncols, int append);  // bessx_paths.cpp
 int glm_geometry(bessx_session *s, int T0, int *mt, int *mp, int *ntask, int *ntiles, int *rps, int *nslab);

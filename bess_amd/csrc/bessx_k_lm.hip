@@ -94,6 +94,37 @@ __global__ void __launch_bounds__(256) k_y_prepare(double *__restrict__ y, int n
   }
 }
 
+// k_y_prepare for R responses at once (bessx_session_set_responses): block r prepares column r of Y (ld-strided, rows
+// n..ld zero) exactly as k_y_prepare prepares a session's y, then forms y.y with k_dot's loop and tree -- the bits of
+// prepare_rowset's yy for a session created with that column as its response.
+__global__ void __launch_bounds__(256) k_y_prepare_multi(double *__restrict__ Y, int n, long ld,
+                                                         const double *__restrict__ w, int centre, int add_weight,
+                                                         double *__restrict__ y_mean, double *__restrict__ yy) {
+  __shared__ double sm[4];
+  __shared__ double bc;
+  double *__restrict__ y = Y + (size_t)blockIdx.x * ld;
+  double mean = 0.0;
+  if (centre) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += y[i] * w[i];
+    s = block_sum_256(s, sm);
+    if (threadIdx.x == 0) bc = s / (double)n;
+    __syncthreads();
+    mean = bc;
+  }
+  if (threadIdx.x == 0) y_mean[blockIdx.x] = mean;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    double v = y[i] - mean;
+    if (add_weight) v = v * sqrt(w[i]);
+    y[i] = v;
+  }
+  __syncthreads();
+  double s = 0.0;
+  for (long i = threadIdx.x; i < ld; i += 256) s = fma(y[i], y[i], s);
+  s = block_sum_256(s, sm);
+  if (threadIdx.x == 0) yy[blockIdx.x] = s;
+}
+
 // ------------------------------------------------------------------------------------------
 // K1 / K2: streaming X^T v.  The dominant kernel of every PDAS iteration (HBM bound).
 //
@@ -1146,6 +1177,15 @@ hipError_t launch_normalize(double *X, long ld, int n, int p, double *y, const d
   }
   hipLaunchKernelGGL(k_y_prepare, dim3(1), dim3(256), 0, st, y, n, w, (int)(is_normal && data_type == 1), add_weight,
                      y_mean);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
+                                  int add_weight, double *y_mean, double *yy, hipStream_t st) {
+  if (R < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_y_prepare_multi, dim3(R), dim3(256), 0, st, Y, n, ld, w, (int)(is_normal && data_type == 1),
+                     add_weight, y_mean, yy);
   LAUNCH_CHECK();
   return hipSuccess;
 }

@@ -1969,6 +1969,18 @@ __global__ void k_mc_resume(const McChain *__restrict__ chains, int chain) {
   st->resume = 1;
 }
 
+__global__ void k_mc_resume_list(const McChain *__restrict__ chains, const int *__restrict__ list) {
+  const int chain = list[blockIdx.x];
+  McState *st = chains[chain].state;
+  FitCtrl *ctrl = chains[chain].nd.ctrl;
+  if (ctrl->cov_stall) {
+    ctrl->cov_stall = 0;
+    ctrl->l = -1 - ctrl->l;
+  }
+  st->parked = 0;
+  st->resume = 1;
+}
+
 __global__ void k_mc_stop(const McChain *__restrict__ chains, int chain) {
   McState *st = chains[chain].state;
   if (!st->finished) {
@@ -2398,6 +2410,12 @@ hipError_t launch_mc_status(const McChain *chains, int nchains, unsigned char *h
 }
 hipError_t launch_mc_resume(const McChain *chains, int chain, hipStream_t st) {
   hipLaunchKernelGGL(k_mc_resume, dim3(1), dim3(1), 0, st, chains, chain);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+hipError_t launch_mc_resume_list(const McChain *chains, const int *chain, int n, hipStream_t st) {
+  if (n < 1) return hipSuccess;
+  hipLaunchKernelGGL(k_mc_resume_list, dim3(n), dim3(1), 0, st, chains, chain);
   LAUNCH_CHECK();
   return hipSuccess;
 }

@@ -59,6 +59,9 @@ struct SharedPass {
 
 struct KChains {
   std::vector<bessx_session *> ctx;
+  // the chains of merged runs of many responses (mc_contexts): apart from the chunk chains' contexts, whose streams have
+  // hardware queues of their own; these queue nothing on theirs
+  std::vector<bessx_session *> mc_ctx;
   FoldPool pool;
   bool pool_started = false;
   SharedPass sp;
@@ -83,28 +86,45 @@ struct KChains {
   McState *mc_states = nullptr;
   int *mc_seq = nullptr, *mc_rec_i = nullptr, *mc_rec_A = nullptr;
   double *mc_rec_d = nullptr, *mc_rec_b = nullptr;
-  size_t mc_cap_cand = 0, mc_cap_cells = 0;
+  size_t mc_cap_cand = 0, mc_cap_cells = 0, mc_cap_seq = 0;
   unsigned char *mc_status_h = nullptr;
   unsigned long long *mc_flag = nullptr, mc_seq_no = 0;
+  // (per chain, mc_cap_chains of each: the union fill's lists beyond 8 and the resume list -- device, pinned staging)
+  int mc_cap_chains = 0;
+  const int **mc_ulist = nullptr;
+  int *mc_ulen = nullptr, *mc_rlist = nullptr;
+  unsigned char *mc_stage_h = nullptr;
 };
 
-static void mc_free(KChains *k) {
+static void mc_free_chains(KChains *k) {  // what is sized by the number of chains
   if (k->mc_chains) (void)hipFree(k->mc_chains);
   if (k->mc_states) (void)hipFree(k->mc_states);
+  if (k->mc_status_h) (void)hipHostFree(k->mc_status_h);
+  if (k->mc_ulist) (void)hipFree(k->mc_ulist);
+  if (k->mc_ulen) (void)hipFree(k->mc_ulen);
+  if (k->mc_rlist) (void)hipFree(k->mc_rlist);
+  if (k->mc_stage_h) (void)hipHostFree(k->mc_stage_h);
+  k->mc_chains = nullptr;
+  k->mc_states = nullptr;
+  k->mc_status_h = nullptr;
+  k->mc_ulist = nullptr;
+  k->mc_ulen = k->mc_rlist = nullptr;
+  k->mc_stage_h = nullptr;
+  k->mc_cap_chains = 0;
+}
+
+static void mc_free(KChains *k) {
+  mc_free_chains(k);
   if (k->mc_seq) (void)hipFree(k->mc_seq);
   if (k->mc_rec_i) (void)hipFree(k->mc_rec_i);
   if (k->mc_rec_A) (void)hipFree(k->mc_rec_A);
   if (k->mc_rec_d) (void)hipFree(k->mc_rec_d);
   if (k->mc_rec_b) (void)hipFree(k->mc_rec_b);
-  if (k->mc_status_h) (void)hipHostFree(k->mc_status_h);
   if (k->mc_flag) (void)hipHostFree(k->mc_flag);
-  k->mc_chains = nullptr;
-  k->mc_states = nullptr;
   k->mc_seq = k->mc_rec_i = k->mc_rec_A = nullptr;
   k->mc_rec_d = k->mc_rec_b = nullptr;
-  k->mc_status_h = nullptr;
   k->mc_flag = nullptr;
-  k->mc_cap_cand = k->mc_cap_cells = 0;
+  k->mc_cap_cand = k->mc_cap_cells = k->mc_cap_seq = 0;
 }
 
 // between two candidates of a chunk chain: if another chain waits to fill, drain this chain's stream and stand still
@@ -356,6 +376,7 @@ void kchains_free(bessx_session *s) {
   if (s->kch_fill_st) ctx_stream_destroy(s->kch_fill_st);
   s->kch_fill_st = nullptr;
   for (bessx_session *c : k->ctx) chain_ctx_free(c);
+  for (bessx_session *c : k->mc_ctx) chain_ctx_free(c);
   if (!k->pool.broken) delete k;  // (a broken pool's threads may still touch it: leaked on purpose)
   s->kch = nullptr;
 }
@@ -509,6 +530,14 @@ int context_begin(bessx_session *c, bool keep_model = false) {
 void kchains_quiesce(bessx_session *s) {
   if (!s || !s->kch) return;
   for (bessx_session *c : s->kch->ctx) (void)hipStreamSynchronize(c->st);
+  for (bessx_session *c : s->kch->mc_ctx) (void)hipStreamSynchronize(c->st);
+}
+
+void kchains_contexts(const bessx_session *s, std::vector<bessx_session *> *out) {
+  out->clear();
+  if (!s || !s->kch) return;
+  out->insert(out->end(), s->kch->ctx.begin(), s->kch->ctx.end());
+  out->insert(out->end(), s->kch->mc_ctx.begin(), s->kch->mc_ctx.end());
 }
 
 // Contexts and host threads for the path's chains.  Non-zero when they cannot be had (no memory for the contexts, host
@@ -550,11 +579,13 @@ int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm) {
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// The chunk phase as merged launches on ONE stream (bessx_dev.h: McChain).  The chains' own streams and host threads are
-// not used here; the stitch that follows runs as before.  Returns 0 with every chunk's candidates in run[r] (a chain the
-// device could not finish by itself is finished through sequential_path on its context: same candidates), > 0 on a
-// failure, < 0 when the engine does not apply to this path (the caller then runs the chunks on their own streams).
+// Merged launches on ONE stream (bessx_dev.h: McChain): the chunk phase of one path, and the paths of many responses
+// (bessx_multi.cpp).  One core, mc_engine, serves both.
 // ----------------------------------------------------------------------------------------------------------------
+bool mc_engine_applies(const bessx_session *s) {
+  return s->model_type == 1 && s->cov_mode && s->fuse && s->fuse_sel && s->cov_cg && s->cg_by_rows;
+}
+
 namespace {
 
 struct McHostStatus {
@@ -587,6 +618,8 @@ int mc_wait(bessx_session *s, KChains *k, unsigned long long want) {
   return 0;
 }
 
+}  // namespace
+
 // |y - X beta|^2 of a model by one pass over its columns (what algorithm_fit does when the solve's loss terms cancel)
 int mc_sse_by_residual(bessx_session *c, hipStream_t st, const int *idx, const double *val, int T0, double coef0, double *out) {
   int *st_idx = reinterpret_cast<int *>(c->stage_h);
@@ -608,44 +641,59 @@ int mc_sse_by_residual(bessx_session *c, hipStream_t st, const int *idx, const d
   return 0;
 }
 
-int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, const std::vector<int> &bounds,
-                  std::vector<ChunkRun> &run, double lambda, int ic_type, int width) {
-  if (s->model_type != 1 || !s->cov_mode || !s->fuse || !s->fuse_sel || !s->cov_cg || !s->cg_by_rows || C > 8) return -1;
-  if (!mc_applies(s->p, seq[ns - 1])) return -1;
-  // Measured on configs[1] (tools/kchunks_bench.py, profiles/README.md, round 5): NOT faster than the chains on streams
-  // of their own -- 12.4-12.6 ms per path against 12.0 with 4 chains, 12.7 with 8 -- because the merged launches run the
-  // chains in lock-step: every step costs what the chain with the largest systems needs (48 us for selection, record,
-  // selection and a 200-unknown solve) and the chunk phase is (candidates per chain) x that.  Kept behind the test hook
-  // kchunks_merged=1, exercised by tests/test_kchunks_gpu.py; the default is the stream per chain.
-  const char *mc_on = test_hook("kchunks_merged");
-  if (!(mc_on && std::string(mc_on) == "1")) return -1;
+namespace {
+
+}  // namespace
+
+// ---- the merged-launch core (bessx_host.h: McJob): one chain = a chunk of one response's path or the whole path of one
+// response.  Buffers sized by the number of chains, every chain's first fit started, rounds of (score pass, selection +
+// solve) pairs, ONE union fill per round for every parked chain, then every chain's records read back.
+int mc_engine(bessx_session *s, const int *seq, int ns, std::vector<McJob> &jobs, int nrec, double lambda, int width,
+              McRecords &rec, std::vector<int> &takeover, long long *fills) {
+  KChains *k = s->kch;
+  const int C = (int)jobs.size();
+  if (!k || C < 1) return fail(BESSX_ERR_ARG, "merged chains: nothing to run");
   const int p = s->p;
   hipStream_t st = s->st;
   // ---- buffers
-  if (!k->mc_chains) {
-    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_chains), 8 * sizeof(McChain)));
-    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_states), 8 * sizeof(McState)));
-    HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_status_h), 8 * sizeof(McHostStatus)));
-    HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_flag), 128));
-    k->mc_flag[0] = 0ull;
-    k->mc_seq_no = 0;
+  if (C > k->mc_cap_chains) {
+    mc_free_chains(k);
+    const int cap = std::max(C, 8);
+    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_chains), (size_t)cap * sizeof(McChain)));
+    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_states), (size_t)cap * sizeof(McState)));
+    HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_status_h), (size_t)cap * sizeof(McHostStatus)));
+    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_ulist), (size_t)cap * sizeof(const int *)));
+    HIPX(dmalloc(&k->mc_ulen, (size_t)cap));
+    HIPX(dmalloc(&k->mc_rlist, (size_t)cap));
+    HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_stage_h), (size_t)cap * (sizeof(const int *) + 2 * sizeof(int))));
+    if (!k->mc_flag) {
+      HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_flag), 128));
+      k->mc_flag[0] = 0ull;
+      k->mc_seq_no = 0;
+    }
+    k->mc_cap_chains = cap;
   }
-  if ((size_t)ns > k->mc_cap_cand || (size_t)ns * width > k->mc_cap_cells) {
+  if ((size_t)ns > k->mc_cap_seq) {
     if (k->mc_seq) (void)hipFree(k->mc_seq);
+    k->mc_seq = nullptr;
+    k->mc_cap_seq = 0;
+    HIPX(dmalloc(&k->mc_seq, (size_t)ns));
+    k->mc_cap_seq = (size_t)ns;
+  }
+  if ((size_t)nrec > k->mc_cap_cand || (size_t)nrec * width > k->mc_cap_cells) {
     if (k->mc_rec_i) (void)hipFree(k->mc_rec_i);
     if (k->mc_rec_d) (void)hipFree(k->mc_rec_d);
     if (k->mc_rec_A) (void)hipFree(k->mc_rec_A);
     if (k->mc_rec_b) (void)hipFree(k->mc_rec_b);
-    k->mc_seq = k->mc_rec_i = k->mc_rec_A = nullptr;
+    k->mc_rec_i = k->mc_rec_A = nullptr;
     k->mc_rec_d = k->mc_rec_b = nullptr;
     k->mc_cap_cand = k->mc_cap_cells = 0;
-    HIPX(dmalloc(&k->mc_seq, (size_t)ns));
-    HIPX(dmalloc(&k->mc_rec_i, (size_t)ns * MC_REC_I));
-    HIPX(dmalloc(&k->mc_rec_d, (size_t)ns * MC_REC_D));
-    HIPX(dmalloc(&k->mc_rec_A, (size_t)ns * width));
-    HIPX(dmalloc(&k->mc_rec_b, (size_t)ns * width));
-    k->mc_cap_cand = (size_t)ns;
-    k->mc_cap_cells = (size_t)ns * width;
+    HIPX(dmalloc(&k->mc_rec_i, (size_t)nrec * MC_REC_I));
+    HIPX(dmalloc(&k->mc_rec_d, (size_t)nrec * MC_REC_D));
+    HIPX(dmalloc(&k->mc_rec_A, (size_t)nrec * width));
+    HIPX(dmalloc(&k->mc_rec_b, (size_t)nrec * width));
+    k->mc_cap_cand = (size_t)nrec;
+    k->mc_cap_cells = (size_t)nrec * width;
   }
   if (!s->fill_ctrl) {
     HIPX(hipMalloc(reinterpret_cast<void **>(&s->fill_ctrl), sizeof(FitCtrl)));
@@ -653,29 +701,30 @@ int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, c
     HIPX(hipHostMalloc(reinterpret_cast<void **>(&s->fill_ctrl_h), sizeof(FitCtrl)));
   }
   HIPX(hipMemcpyAsync(k->mc_seq, seq, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPX(hipMemsetAsync(k->mc_rec_i, 0, (size_t)ns * MC_REC_I * sizeof(int), st));
+  HIPX(hipMemsetAsync(k->mc_rec_i, 0, (size_t)nrec * MC_REC_I * sizeof(int), st));
   // ---- the chains: their contexts' buffers, the start of their first fit
   std::vector<McChain> hc((size_t)C);
   std::vector<McState> hs((size_t)C);
   for (int r = 0; r < C; r++) {
-    bessx_session *c = k->ctx[r];
-    ChunkRun &q = run[r];
+    McJob &j = jobs[(size_t)r];
+    bessx_session *c = j.c;
     if (int rc = context_begin(c)) return rc;
     c->timing = s->timing;
-    const int lo = q.lo, ncand = q.hi - q.lo, k_init = (int)q.init_idx.size();
-    if (ncand < 1 || k_init > c->cap) return fail(BESSX_ERR_ARG, "chunk chains: bad chunk");
+    const int lo = j.lo, ncand = j.ncand, k_init = j.init_idx ? (int)j.init_idx->size() : 0;
+    if (ncand < 1 || k_init > c->cap || lo + ncand > ns || j.rec0 + ncand > nrec)
+      return fail(BESSX_ERR_ARG, "merged chains: bad chain");
     bessx_session::CovCache &cv = c->cov[0];
     int *st_idx = reinterpret_cast<int *>(c->stage_h);
     double *st_val = reinterpret_cast<double *>(c->stage_h + (size_t)c->capA * sizeof(int));
     for (int i = 0; i < k_init; i++) {
-      st_idx[i] = q.init_idx[i];
-      st_val[i] = q.init_val[i];
+      st_idx[i] = (*j.init_idx)[(size_t)i];
+      st_val[i] = (*j.init_val)[(size_t)i];
     }
     if (k_init) {
       HIPX(hipMemcpyAsync(c->init_idx_d, st_idx, k_init * sizeof(int), hipMemcpyHostToDevice, st));
       HIPX(hipMemcpyAsync(c->init_val_d, st_val, k_init * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    HIPX(launch_fit_begin(c->ctrl, seq[lo], k_init, c->init_idx_d, c->init_val_d, q.init_coef0, c->A_cur, c->b_cur,
+    HIPX(launch_fit_begin(c->ctrl, seq[lo], k_init, c->init_idx_d, c->init_val_d, j.init_coef0, c->A_cur, c->b_cur,
                           c->beta_dense, p, c->hist, st, c->inA));
     McChain &m = hc[(size_t)r];
     m = McChain();
@@ -685,7 +734,7 @@ int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, c
     m.max_iter = c->max_iter;
     m.p = p;
     m.G = cv.G;
-    m.xty = c->xty[0];
+    m.xty = j.xty ? j.xty : c->xty[0];
     m.xtx = c->xtx[0];
     m.n_t = (double)c->n_train[0];
     m.lambda = lambda;
@@ -714,10 +763,10 @@ int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, c
     m.sol = c->sol;
     m.tol = c->cg_tol;
     m.maxit = 64;
-    m.rec_i = k->mc_rec_i + (size_t)lo * MC_REC_I;
-    m.rec_d = k->mc_rec_d + (size_t)lo * MC_REC_D;
-    m.rec_A = k->mc_rec_A + (size_t)lo * width;
-    m.rec_b = k->mc_rec_b + (size_t)lo * width;
+    m.rec_i = k->mc_rec_i + (size_t)j.rec0 * MC_REC_I;
+    m.rec_d = k->mc_rec_d + (size_t)j.rec0 * MC_REC_D;
+    m.rec_A = k->mc_rec_A + (size_t)j.rec0 * width;
+    m.rec_b = k->mc_rec_b + (size_t)j.rec0 * width;
     McState &z = hs[(size_t)r];
     z = McState();
     z.ncand = ncand;
@@ -729,15 +778,18 @@ int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, c
   HIPX(hipStreamSynchronize(st));  // (hc / hs / the staging buffers are the host's again)
   // ---- rounds: a batch of (score pass, selection + solve) pairs, then every chain's state
   int longest = 0;
-  for (int r = 0; r < C; r++) longest = std::max(longest, run[r].hi - run[r].lo);
+  for (const McJob &j : jobs) longest = std::max(longest, j.ncand);
   // Batches of 8 pairs: a chain that parks on a missing column waits for the end of its batch before the host sees it
   // (queueing the whole chunk ahead -- about one pair per candidate -- left a parked chain idle for up to 2.6 ms on
   // configs[1]); the read-back between two batches costs the device ~25 us of 500.
   int batch = 8;
   const McHostStatus *hstat = reinterpret_cast<const McHostStatus *>(k->mc_status_h);
-  std::vector<int> takeover((size_t)C, 0);
+  takeover.assign((size_t)C, 0);
+  const int **stage_lists = reinterpret_cast<const int **>(k->mc_stage_h);
+  int *stage_len = reinterpret_cast<int *>(k->mc_stage_h + (size_t)k->mc_cap_chains * sizeof(const int *));
+  int *stage_resume = stage_len + k->mc_cap_chains;
   for (int round = 0;; round++) {
-    if (round > 64 + longest) return fail(BESSX_ERR_NUMERIC, "chunk chains (merged launches): the chains do not end");
+    if (round > 64 + longest) return fail(BESSX_ERR_NUMERIC, "merged chains: the chains do not end");
     for (int b = 0; b < batch; b++) {
       HIPX(launch_mc_cov_d(k->mc_chains, C, p, st));
       HIPX(launch_mc_sel_cgr(k->mc_chains, C, p, st));
@@ -770,11 +822,22 @@ int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, c
       bessx_session *spec_src = nullptr;
       int ub = 0;
       for (int r : parked) {
-        bessx_session *c = k->ctx[r];
-        u.list[u.nf] = c->A_new;
-        u.len[u.nf++] = hstat[r].ctrl.T0;
+        bessx_session *c = jobs[(size_t)r].c;
+        if (u.nf < 8) {
+          u.list[u.nf] = c->A_new;
+          u.len[u.nf++] = hstat[r].ctrl.T0;
+        } else {  // (beyond 8 sets: device arrays of lists, listed after the fixed ones)
+          stage_lists[u.dn] = c->A_new;
+          stage_len[u.dn++] = hstat[r].ctrl.T0;
+        }
         ub += hstat[r].ctrl.cov_nmiss;
         if (!spec_src && cov_speculates(c)) spec_src = c;
+      }
+      if (u.dn > 0) {
+        HIPX(hipMemcpyAsync(k->mc_ulist, stage_lists, (size_t)u.dn * sizeof(const int *), hipMemcpyHostToDevice, st));
+        HIPX(hipMemcpyAsync(k->mc_ulen, stage_len, (size_t)u.dn * sizeof(int), hipMemcpyHostToDevice, st));
+        u.dlist = k->mc_ulist;
+        u.dlen = k->mc_ulen;
       }
       if (spec_src)
         HIPX(launch_topk(spec_src->bd2, p, s->cov_spec, spec_src->cov_extras, spec_src->cand, nullptr, 0, st));
@@ -787,25 +850,89 @@ int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, c
       s->fill_groups_seen = s->fill_ctrl_h->cov_groups;
       const int ngroups = s->fill_ctrl_h->cov_nfill / COV_R;
       if (ngroups > (ub + s->cov_spec + 2 * COV_R - 1) / COV_R)
-        return fail(BESSX_ERR_NUMERIC, "internal error: union fill list longer than its bound (chunk chains)");
+        return fail(BESSX_ERR_NUMERIC, "internal error: union fill list longer than its bound (merged chains)");
       if (int rc = enqueue_cov_fill(s, 0, ngroups, 1, s->fill_ctrl)) return rc;
       if (s->timing) {
         HIPX(hipStreamSynchronize(st));
         if (int rc = cov_collect(s, s->fill_ctrl_h->cov_nfill)) return rc;
       }
-      for (int r : parked) HIPX(launch_mc_resume(k->mc_chains, r, st));
-      s->kch_chunk_fills++;
+      for (size_t i = 0; i < parked.size(); i++) stage_resume[i] = parked[i];
+      HIPX(hipMemcpyAsync(k->mc_rlist, stage_resume, parked.size() * sizeof(int), hipMemcpyHostToDevice, st));
+      HIPX(launch_mc_resume_list(k->mc_chains, k->mc_rlist, (int)parked.size(), st));
+      if (fills) (*fills)++;
     }
     if (all) break;
   }
   // ---- the records
-  std::vector<int> rec_i((size_t)ns * MC_REC_I), rec_A((size_t)ns * width);
-  std::vector<double> rec_d((size_t)ns * MC_REC_D), rec_b((size_t)ns * width);
-  HIPX(hipMemcpyAsync(rec_i.data(), k->mc_rec_i, rec_i.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPX(hipMemcpyAsync(rec_d.data(), k->mc_rec_d, rec_d.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPX(hipMemcpyAsync(rec_A.data(), k->mc_rec_A, rec_A.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPX(hipMemcpyAsync(rec_b.data(), k->mc_rec_b, rec_b.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  rec.i.assign((size_t)nrec * MC_REC_I, 0);
+  rec.A.assign((size_t)nrec * width, 0);
+  rec.d.assign((size_t)nrec * MC_REC_D, 0.0);
+  rec.b.assign((size_t)nrec * width, 0.0);
+  HIPX(hipMemcpyAsync(rec.i.data(), k->mc_rec_i, rec.i.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPX(hipMemcpyAsync(rec.d.data(), k->mc_rec_d, rec.d.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipMemcpyAsync(rec.A.data(), k->mc_rec_A, rec.A.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPX(hipMemcpyAsync(rec.b.data(), k->mc_rec_b, rec.b.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPX(hipStreamSynchronize(st));
+  for (const McJob &j : jobs) {
+    for (auto &cc : j.c->cache) cc.valid = cc.model_only = false;  // (the device state of the context is the engine's, not a fit's of its own)
+    j.c->dev_state_rs = -1;
+  }
+  return 0;
+}
+
+int mc_contexts(bessx_session *s, int n) {
+  if (hipSetDevice(s->device) != hipSuccess) return fail(BESSX_ERR_HIP, "merged chains: device");
+  if (!s->kch) s->kch = new KChains();
+  KChains *k = s->kch;
+  while ((int)k->mc_ctx.size() < n) {
+    bessx_session *c = nullptr;
+    // (ordinary streams: the merged run queues everything on the session's own)
+    if (int rc = chain_ctx_create(s, &c, false)) {
+      (void)hipGetLastError();
+      return rc;
+    }
+    c->kch_index = -1;
+    k->mc_ctx.push_back(c);
+  }
+  return 0;
+}
+
+bessx_session *mc_context(bessx_session *s, int i) { return s->kch->mc_ctx[(size_t)i]; }
+
+namespace {
+
+// The chunk phase as merged launches (mc_engine) -- the chains' own streams and host threads are not used here; the
+// stitch that follows runs as before.  Returns 0 with every chunk's candidates in run[r] (a chain the device could not
+// finish by itself is finished through sequential_path on its context: same candidates), > 0 on a failure, < 0 when
+// the engine does not apply to this path (the caller then runs the chunks on their own streams).
+int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, const std::vector<int> &bounds,
+                  std::vector<ChunkRun> &run, double lambda, int ic_type, int width) {
+  if (!mc_engine_applies(s) || C > 8) return -1;
+  if (!mc_applies(s->p, seq[ns - 1])) return -1;
+  // Measured on configs[1] (tools/kchunks_bench.py, profiles/README.md, round 5): NOT faster than the chains on streams
+  // of their own -- 12.4-12.6 ms per path against 12.0 with 4 chains, 12.7 with 8 -- because the merged launches run the
+  // chains in lock-step: every step costs what the chain with the largest systems needs (48 us for selection, record,
+  // selection and a 200-unknown solve) and the chunk phase is (candidates per chain) x that.  Kept behind the test hook
+  // kchunks_merged=1, exercised by tests/test_kchunks_gpu.py; the default is the stream per chain.
+  const char *mc_on = test_hook("kchunks_merged");
+  if (!(mc_on && std::string(mc_on) == "1")) return -1;
+  std::vector<McJob> jobs((size_t)C);
+  for (int r = 0; r < C; r++) {
+    McJob &j = jobs[(size_t)r];
+    j.c = k->ctx[r];
+    j.lo = j.rec0 = run[r].lo;
+    j.ncand = run[r].hi - run[r].lo;
+    j.init_idx = &run[r].init_idx;
+    j.init_val = &run[r].init_val;
+    j.init_coef0 = run[r].init_coef0;
+  }
+  McRecords recs;
+  std::vector<int> takeover;
+  if (int rc = mc_engine(s, seq, ns, jobs, ns, lambda, width, recs, takeover, &s->kch_chunk_fills)) return rc;
+  const std::vector<int> &rec_i = recs.i, &rec_A = recs.A;
+  const std::vector<double> &rec_d = recs.d, &rec_b = recs.b;
+  const McHostStatus *hstat = reinterpret_cast<const McHostStatus *>(k->mc_status_h);
+  const hipStream_t st = s->st;
   for (int r = 0; r < C; r++) {
     bessx_session *c = k->ctx[r];
     ChunkRun &q = run[r];

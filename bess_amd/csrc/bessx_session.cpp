@@ -72,6 +72,10 @@ void session_free(bessx_session *s) {
   F(s->x_mean);
   F(s->x_norm);
   F(s->y_mean_d);
+  F(s->resp_y);
+  F(s->resp_xty);
+  F(s->resp_part);
+  F(s->own_xty);
   F(s->always);
   for (auto q : s->mask) F(q);
   for (auto q : s->xtx) F(q);
@@ -1396,7 +1400,7 @@ static void drop_folds(bessx_session *s) {
 // Context of row set rs for the fold chains that run side by side (see bessx_session::fold_ctx): a copy of the parent
 // that borrows its data and caches and owns the state a fit writes.  Same capacities as the parent, so every enqueue
 // function of the covariance form works on it unchanged.
-static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out) {
+static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out, bool own_queue_ok = true) {
   bessx_session *c = new bessx_session(*ps);
   c->parent = ps;
   c->fold_pool = nullptr;
@@ -1448,7 +1452,7 @@ static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out) {
     // device, so it restricts nothing.  BESSX_TEST_HOOKS=ctx_streams=pool: ordinary streams, round 4's form.
     // (The chains share one priority level: spread over the levels, which have their own pools of hardware queues,
     // the chains on the lower levels ran 2-8 x slower per kernel and the path no faster.)
-    const bool own_queue = ctx_stream_create(ps->device, &c->st);
+    const bool own_queue = own_queue_ok && ctx_stream_create(ps->device, &c->st);
     if (!own_queue) {
       int lo = 0, hi = 0;
       e = hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -1511,9 +1515,9 @@ static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out) {
 // vectors a fit of row set 0 writes (d, the residual, the work vector of the loss fallback).
 }  // extern "C"
 namespace bessx {
-int chain_ctx_create(bessx_session *ps, bessx_session **out) {
+int chain_ctx_create(bessx_session *ps, bessx_session **out, bool own_queue) {
   bessx_session *c = nullptr;
-  if (int rc = fold_ctx_create(ps, 0, &c)) return rc;
+  if (int rc = fold_ctx_create(ps, 0, &c, own_queue)) return rc;
   c->kch_owner = ps;
   c->kch = nullptr;
   c->kch_index = -1;
@@ -1973,6 +1977,9 @@ long long bessx_session_counter(const bessx_session *s, int which) {
     case 30: return s->sp_chain_slots;
     case 31: return s->sp_partial;
     case 32: return ctx_streams_created();
+    case 33: return s->multi_batched;
+    case 34: return s->multi_host;
+    case 35: return s->multi_fills;
     case 10: {  // times the Gram column cache of the all-rows row set was started over since the last path started
       if (s->cov.empty()) return 0;
       int m[8] = {0, 0, 0, 0, 0, 0, 0, 0};

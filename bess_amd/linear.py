@@ -76,6 +76,12 @@ class bess_base:
             raise ValueError("There is NAN value in y")
         n, p = X.shape
         self.p = p
+        Y = None
+        if self.model_type_int == 1 and y.ndim == 2 and y.shape[1] >= 2:
+            # several responses against one design: every column is fitted (beta (p, R); coef0, train_loss, ic (R,))
+            if y.shape[0] != n:
+                raise ValueError("X.shape(0) should be equal to y.shape(0) (y has one column per response)")
+            Y, y = y, y[:, 0]
         g_index = self._group_starts(group, p) if self.algorithm_type_int == 2 else range(p)
         if self.model_type_int == 4:
             # Cox: rows by ascending time, response becomes the status column (linear.py:257-263)
@@ -124,6 +130,9 @@ class bess_base:
         if min(p, top * gsz) > capi.MAX_SPARSITY:
             raise ValueError("bess_amd: sparsity levels up to %d active columns are supported, this path asks for %d "
                              "(shorten `sequence` / lower `s_max`)" % (capi.MAX_SPARSITY, min(p, top * gsz)))
+        if Y is not None:
+            self._fit_responses(X, Y, weight, is_normal, g_index, state, p, top, gsz)
+            return
         result = capi.pywrap_bess(X, y, self.data_type, weight, is_normal, self.algorithm_type_int,
                                   self.model_type_int, self.max_iter, self.exchange_num, self.path_type_int,
                                   self.is_warm_start, self.ic_type_int, self.is_cv, self.K, g_index, state,
@@ -133,10 +142,44 @@ class bess_base:
                                   1, 1, p)
         self.beta, self.coef0, self.train_loss, self.ic = result[0], result[1], result[2], result[3]
 
+    def _fit_responses(self, X, Y, weight, is_normal, g_index, state, p, top, gsz):
+        """fit() of the Lm classes for a 2-D y: the sequential path without CV or screening runs every response on ONE
+        session (capi.Session.sequential_path_multi: one design upload, one shared Gram column cache); everything else
+        fits the columns one after another through pywrap_bess.  Same results as fitting each column alone."""
+        R = Y.shape[1]
+        beta, coef0, loss, ic = np.zeros((p, R)), np.zeros(R), np.zeros(R), np.zeros(R)
+        if self.path_type_int == 1 and not self.is_cv and not self.is_screening:
+            ses = capi.Session(X, Y[:, 0], weight=weight, data_type=self.data_type, is_normal=is_normal,
+                               model_type=self.model_type_int, algorithm_type=self.algorithm_type_int,
+                               max_iter=self.max_iter, is_warm_start=self.is_warm_start,
+                               always_select=self.always_select, g_index=list(g_index),
+                               max_sparsity=min(top * gsz, p, capi.MAX_SPARSITY))
+            try:
+                ses.set_responses(Y)
+                res = ses.sequential_path_multi(self.sequence, self.lambda_sequence, self.ic_type_int)
+            finally:
+                ses.close()
+            for r, o in enumerate(res):
+                beta[:, r], coef0[r], loss[r], ic[r] = o["beta"], o["coef0"], o["train_loss"], o["ic"]
+        else:
+            for r in range(R):
+                out = capi.pywrap_bess(X, np.ascontiguousarray(Y[:, r]), self.data_type, weight, is_normal,
+                                       self.algorithm_type_int, self.model_type_int, self.max_iter, self.exchange_num,
+                                       self.path_type_int, self.is_warm_start, self.ic_type_int, self.is_cv, self.K,
+                                       g_index, state, self.sequence, self.lambda_sequence, self.s_min, self.s_max,
+                                       self.K_max, self.epsilon, self.lambda_min, self.lambda_max, self.n_lambda,
+                                       self.is_screening, self.screening_size, self.powell_path, self.always_select,
+                                       self.tao, p, 1, 1, 1, 1, 1, 1, p)
+                beta[:, r] = out[0]
+                coef0[r], loss[r], ic[r] = (float(np.ravel(v)[0]) for v in out[1:4])
+        self.beta, self.coef0, self.train_loss, self.ic = beta, coef0, loss, ic
+
     def predict(self, X):
         X = np.asarray(X)
         if X.shape[1] != self.p:
             raise ValueError("X.shape[1] should be " + str(self.p))
+        if self.model_type_int == 1 and np.ndim(self.beta) == 2:  # (one column per response)
+            return np.dot(X, self.beta) + np.asarray(self.coef0)[None, :]
         eta = np.dot(X, self.beta) + np.ones(X.shape[0]) * self.coef0
         if self.model_type_int == 1:
             return eta

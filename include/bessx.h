@@ -176,7 +176,9 @@ int bessx_session_score_mode(const bessx_session *s);
  * reset with bessx_session_score_pass_stats), 29 multi-chain launches of the chunk chains' shared passes over X
  * (fall-through launches included), 30 vector sets those launches served (kernel timing on), 31 batches launched before
  * every chain had arrived (the 50 ms timeout), 32 streams with a hardware queue of their own the PROCESS has created so
- * far (they are recycled across sessions).  -1 for an unknown id. */
+ * far (they are recycled across sessions); bessx_session_sequential_path_multi: 33 responses run through the merged
+ * engine, 34 responses or parts of responses the host finished through the ordinary path (takeovers, and every response
+ * of a path the engine does not apply to), 35 union fills served during merged runs of responses.  -1 for an unknown id. */
 long long bessx_session_counter(const bessx_session *s, int which);
 
 /* Metric::set_cv_train_test_mask + cal_cv_group_XTX (src/Metric.h:49-129).  fold_id[i] in [0,K)
@@ -253,6 +255,28 @@ typedef struct {
 int bessx_session_sequential_path_chain(bessx_session *s, const int *sequence, int sequence_len,
                                         const double *lambda_seq, int lambda_len, int ic_type, int is_cv,
                                         bessx_path_chain *chain, bessx_path_result *res);
+
+/* Many responses against this session's design (LM, model_type 1; bessx_multi.cpp).
+ * bessx_session_set_responses: R extra responses, Y n x R, column-major if col_major else row-major.  Each column is
+ * prepared exactly like the session's y (weights, data_type centring; src/Data.h:79-93, k_y_prepare).  Replaces any
+ * earlier set.  The session's own y is not changed.  BESSX_ERR_ARG for R < 1 or a NaN in Y; BESSX_ERR_UNSUPPORTED
+ * for model_type != 1.
+ * bessx_session_sequential_path_multi: sequential_path (same arguments and meaning) once per response set by
+ * bessx_session_set_responses: res[0..R) in column order, each filled exactly as bessx_session_sequential_path fills its
+ * result for a session created with that column as y.  Where the merged-launch engine applies (covariance score mode
+ * with a cache that holds every column, one lambda, warm start, ascending levels of at most the k_sel_cgr range, singleton
+ * groups) the responses run in batches of up to 256 as chains of ONE merged run that share the Gram column cache and
+ * its fills; a response the device stops (tie, Cholesky handoff, ...) is finished on the host through
+ * bessx_session_sequential_path_chain from its last recorded model.  Elsewhere the responses run one after another
+ * through the ordinary path.  Same results either way.  The session's own response, X^T y and y.y are restored before
+ * the call returns.  BESSX_ERR_UNSUPPORTED for is_cv != 0, model_type != 1 and a screening session; BESSX_ERR_ARG before
+ * bessx_session_set_responses.  A response whose own path fails (e.g. a constant column: the error code its single-
+ * response session returns) fails the whole call with that code; res[] is then incomplete and no response's result may
+ * be used.  Counters 33-35 (bessx_session_counter). */
+int bessx_session_set_responses(bessx_session *s, const double *Y, int R, int col_major);
+int bessx_session_sequential_path_multi(bessx_session *s, const int *sequence, int sequence_len,
+                                        const double *lambda_seq, int lambda_len, int ic_type, int is_cv,
+                                        bessx_path_result *res);
 
 /* gs_path (src/path.cpp:134-389): integer golden section on [s_min, s_max] then exhaustive sweep. */
 int bessx_session_gs_path(bessx_session *s, int s_min, int s_max, int ic_type, int is_cv, bessx_path_result *res);
