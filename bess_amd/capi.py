@@ -34,6 +34,8 @@ SYMBOLS = [
     "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
+    "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
+    "bessx_op_ingest_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -54,6 +56,13 @@ class Problem(ctypes.Structure):
                 ("is_warm_start", _i), ("always_select", _I), ("always_select_len", _i), ("device", _i),
                 ("group_index", _I), ("group_index_len", _i),
                 ("is_screening", _i), ("screening_size", _i), ("score_mode", _i), ("max_sparsity", _i)]
+
+
+class DeviceInput(ctypes.Structure):
+    """bessx_device_input: X (and optionally y, weight) in GPU memory; strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("y_host", _D),
+                ("y_dev", _vp), ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp),
+                ("weight_dtype", _i), ("weight_stride", _ll), ("row_order", _I), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -156,6 +165,15 @@ def lib():
         L.bessx_op_xtv_multi_bench.argtypes = [_i, _i, _i, _i, _i, _D, _D]
         L.bessx_op_topk_bench.argtypes = [_i, _i, _i, _i, _D]
         L.bessx_op_chol_bench.argtypes = [_i, _i, _D]
+        L.bessx_session_create_device.argtypes = [ctypes.POINTER(_vp), ctypes.POINTER(Problem),
+                                                  ctypes.POINTER(DeviceInput)]
+        L.bessx_session_set_responses_device.argtypes = [_vp, _vp, _i, _ll, _ll, _i, _vp]
+        L.bessx_pywrap_bess_device.argtypes = (
+            [ctypes.POINTER(DeviceInput), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _I, _i, _D, _i, _I, _i, _D, _i]
+            + [_i, _i, _i, _d, _d, _d, _i, _i, _i, _i, _I, _i, _d]
+            + [_D, _i, _D, _i, _D, _i, _D, _i, _D, _D, _i, _D, _i, _D, _i, _I, _i, _I, _I])
+        L.bessx_op_ingest.argtypes = [_vp, _i, _ll, _ll, _I, _i, _i, _ll, _vp, _D, _I]
+        L.bessx_op_ingest_bench.argtypes = [_vp, _i, _ll, _ll, _I, _i, _i, _ll, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -186,6 +204,112 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+NAN_IN_X = "There is NAN value in X"
+
+
+def _check_device_route(rc):
+    """_check for the entry points that ingest X on the device: the kernel's NaN flag becomes the estimators' error."""
+    if rc == 1 and last_error() == NAN_IN_X:
+        raise ValueError(NAN_IN_X)
+    _check(rc)
+
+
+def is_device_array(a):
+    """True for an object in GPU memory: anything that exposes __cuda_array_interface__ (torch ROCm tensors do)."""
+    return hasattr(a, "__cuda_array_interface__")
+
+
+class _DeviceArray:
+    """Pointer, element type, shape and ELEMENT strides of a device array, from its __cuda_array_interface__.  Raises
+    ValueError for what the ingest kernel does not take; makes no device call.  Keeps the object alive."""
+
+    def __init__(self, a, what, ndim=None):
+        cai = a.__cuda_array_interface__
+        shape = tuple(int(v) for v in cai["shape"])
+        if ndim is not None and len(shape) != ndim:
+            raise ValueError("%s: a device array must be %d-D, got shape %s" % (what, ndim, shape))
+        if len(shape) < 1 or len(shape) > 2:
+            raise ValueError("%s: a device array must be 1-D or 2-D, got shape %s" % (what, shape))
+        typestr = cai["typestr"]
+        if typestr not in ("<f8", "<f4"):
+            raise ValueError("%s: a device array must be float64 or float32 (typestr '<f8' or '<f4'), got %r"
+                             % (what, typestr))
+        item = 8 if typestr == "<f8" else 4
+        if any(v < 1 for v in shape):
+            raise ValueError("%s: empty device array, shape %s" % (what, shape))
+        strides = cai.get("strides")
+        if strides is None:  # C-contiguous
+            strides, acc = [], item
+            for v in reversed(shape):
+                strides.insert(0, acc)
+                acc *= v
+        strides = tuple(int(v) for v in strides)
+        if len(strides) != len(shape) or any(v < 0 or v % item for v in strides):
+            raise ValueError("%s: byte strides of a device array must be non-negative multiples of the item size %d, "
+                             "got %s" % (what, item, strides))
+        self.obj, self.ptr, self.item = a, int(cai["data"][0]), item
+        self.dtype = 0 if item == 8 else 1  # BESSX_F64 / BESSX_F32
+        self.shape, self.strides = shape, tuple(v // item for v in strides)
+        if not self.ptr:
+            raise ValueError("%s: null device pointer" % what)
+
+    @property
+    def size(self):
+        return int(np.prod(self.shape))
+
+    def as_vector(self, what):
+        """(ptr, dtype, stride) of a 1-D array or of a 2-D one with a single row or column."""
+        if len(self.shape) == 1:
+            return self.strides[0]
+        if self.shape[1] == 1:
+            return self.strides[0]
+        if self.shape[0] == 1:
+            return self.strides[1]
+        raise ValueError("%s: expected a vector, got shape %s" % (what, self.shape))
+
+
+def _device_input(x, y, weight, row_order, stream):
+    """(DeviceInput, n, p, objects to keep alive) for x on the device; every check that needs no device is made here."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    keep = [dx]
+    din = DeviceInput()
+    din.x, din.x_dtype, din.x_row_stride, din.x_col_stride = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1]
+    if is_device_array(y):
+        dy = _DeviceArray(y, "y")
+        if dy.size != n:
+            raise ValueError("X.shape(0) should be equal to y.size")
+        din.y_dev, din.y_dtype, din.y_stride = dy.ptr, dy.dtype, dy.as_vector("y")
+        keep.append(dy)
+    else:
+        yh = _f64(y).reshape(-1)
+        if yh.size != n:
+            raise ValueError("X.shape(0) should be equal to y.size")
+        din.y_host = _dp(yh)
+        keep.append(yh)
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            din.weight_dev, din.weight_dtype, din.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+            keep.append(dw)
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            din.weight_host = _dp(wh)
+            keep.append(wh)
+    if row_order is not None:
+        ro = _i32(row_order).reshape(-1)
+        if ro.size != n or (np.sort(ro) != np.arange(n)).any():
+            raise ValueError("row_order must be a permutation of 0..n-1")
+        din.row_order = _ip(ro)
+        keep.append(ro)
+    din.stream = int(stream) if stream else None
+    return din, n, p, keep
+
+
 def device_info():
     buf = ctypes.create_string_buffer(512)
     _check(lib().bessx_device_info(buf, 512))
@@ -196,14 +320,21 @@ def pywrap_bess(x, y, data_type, weight, is_normal, algorithm_type, model_type, 
                 is_warm_start, ic_type, is_cv, K, g_index, state, sequence, lambda_sequence, s_min, s_max, K_max,
                 epsilon, lambda_min, lambda_max, n_lambda, is_screening, screening_size, powell_path, always_select,
                 tao, beta_out_len, coef0_out_len=1, train_loss_out_len=1, ic_out_len=1, aic_out_len=1,
-                bic_out_len=1, gic_out_len=1, A_out_len=None):
+                bic_out_len=1, gic_out_len=1, A_out_len=None, row_order=None, stream=0):
     """Same 38 positional arguments and 10-tuple result as the reference's SWIG wrapper
     (python/src/bess.i:17-30, called at python/bess/linear.py:360-375):
-    (beta, coef0, train_loss, ic, nullloss, aic, bic, gic, A_out, l_out)."""
-    x = _f64(x)
-    n, p = x.shape
-    y = _f64(y).reshape(-1)
-    weight = _f64(weight)
+    (beta, coef0, train_loss, ic, nullloss, aic, bic, gic, A_out, l_out).
+    An x in GPU memory (is_device_array) is read where it lies (bessx_pywrap_bess_device): y and weight may then be
+    device arrays too, row_order (a permutation: row i of the problem is row row_order[i] of x; x only) and stream
+    (raw handle of the stream x was produced on) apply; ValueError("There is NAN value in X") for a NaN in x."""
+    din = None
+    if is_device_array(x):
+        din, n, p, _keep = _device_input(x, y, weight, row_order, stream)
+    else:
+        x = _f64(x)
+        n, p = x.shape
+        y = _f64(y).reshape(-1)
+        weight = _f64(weight)
     state = _f64(state)
     g_index = _i32(g_index)
     sequence = _i32(sequence)
@@ -216,6 +347,20 @@ def pywrap_bess(x, y, data_type, weight, is_normal, algorithm_type, model_type, 
     aic, bic, gic = np.zeros(aic_out_len), np.zeros(bic_out_len), np.zeros(gic_out_len)
     a_out = np.zeros(A_out_len, dtype=np.int32)
     l_out = np.zeros(1, dtype=np.int32)
+    if din is not None:
+        x_nan = np.zeros(1, dtype=np.int32)
+        rc = lib().bessx_pywrap_bess_device(
+            ctypes.byref(din), n, p, data_type, int(is_normal), algorithm_type, model_type,
+            max_iter, exchange_num, path_type, int(is_warm_start), ic_type, int(is_cv), K, _ip(g_index), g_index.size,
+            _dp(state), state.size, _ip(sequence), sequence.size, _dp(lambda_sequence), lambda_sequence.size, s_min,
+            s_max, K_max, epsilon, lambda_min, lambda_max, n_lambda, int(is_screening), screening_size, powell_path,
+            _ip(always_select), always_select.size, tao, _dp(beta), beta.size, _dp(coef0), coef0.size, _dp(loss),
+            loss.size, _dp(ic), ic.size, _dp(nullloss), _dp(aic), aic.size, _dp(bic), bic.size, _dp(gic), gic.size,
+            _ip(a_out), a_out.size, _ip(l_out), _ip(x_nan))
+        if x_nan[0]:
+            raise ValueError(NAN_IN_X)
+        _check(rc)
+        return beta, coef0, loss, ic, float(nullloss[0]), aic, bic, gic, a_out, int(l_out[0])
     _check(lib().bessx_pywrap_bess(
         _dp(x), n, p, _dp(y), y.size, data_type, _dp(weight), weight.size, int(is_normal), algorithm_type, model_type,
         max_iter, exchange_num, path_type, int(is_warm_start), ic_type, int(is_cv), K, _ip(g_index), g_index.size,
@@ -267,17 +412,28 @@ def bessCpp(x, y, data_type, weight, is_normal, algorithm_type, model_type, max_
 
 
 class Session:
-    """The state bessCpp builds (Data + Algorithm + Metric, src/bess.cpp:61-165), resident in HBM."""
+    """The state bessCpp builds (Data + Algorithm + Metric, src/bess.cpp:61-165), resident in HBM.
+
+    x in GPU memory (anything with __cuda_array_interface__: 2-D, float64 or float32, any non-negative strides) is read
+    where it lies (bessx_session_create_device) and never crosses the bus; y and weight may then be device arrays or
+    anything NumPy accepts.  stream: raw handle of the stream the data was produced on (0 = the null stream); row_order:
+    a permutation, session row i is row row_order[i] of x (x only; y and weight are in session order).  The caller's
+    arrays are free again when the constructor returns.  x_col_major is ignored for a device x (its strides say it)."""
 
     def __init__(self, x, y, weight=None, data_type=1, is_normal=True, model_type=1, algorithm_type=1, max_iter=20,
                  is_warm_start=True, always_select=(), x_col_major=False, device=-1, g_index=None,
-                 is_screening=False, screening_size=0, score_mode=0, max_sparsity=0):
-        x = np.asfortranarray(x, dtype=np.float64) if x_col_major else _f64(x)
-        self.n, self.p = x.shape
-        y = _f64(y).reshape(-1)
-        if y.size != self.n:
-            raise ValueError("X.shape(0) should be equal to y.size")
-        w = None if weight is None else _f64(weight)
+                 is_screening=False, screening_size=0, score_mode=0, max_sparsity=0, stream=0, row_order=None):
+        din = None
+        if is_device_array(x):
+            din, self.n, self.p, _keep = _device_input(x, y, weight, row_order, stream)
+            x = y = w = None
+        else:
+            x = np.asfortranarray(x, dtype=np.float64) if x_col_major else _f64(x)
+            self.n, self.p = x.shape
+            y = _f64(y).reshape(-1)
+            if y.size != self.n:
+                raise ValueError("X.shape(0) should be equal to y.size")
+            w = None if weight is None else _f64(weight)
         al = _i32(always_select)
         gi = None if g_index is None else _i32(g_index)
         self._gsize_max = 1
@@ -288,7 +444,10 @@ class Session:
                      0 if gi is None else gi.size, int(is_screening), int(screening_size), int(score_mode),
                      int(max_sparsity))
         h = _vp()
-        _check(lib().bessx_session_create(ctypes.byref(h), ctypes.byref(pb)))
+        if din is not None:
+            _check_device_route(lib().bessx_session_create_device(ctypes.byref(h), ctypes.byref(pb), ctypes.byref(din)))
+        else:
+            _check(lib().bessx_session_create(ctypes.byref(h), ctypes.byref(pb)))
         self._h = h
         self.K = 0
         self.is_warm_start = bool(is_warm_start)
@@ -310,7 +469,8 @@ class Session:
                  26: "panel_ns_one_group", 27: "panel_launches_two_groups", 28: "panel_ns_two_groups",
                  29: "shared_pass_launches", 30: "shared_pass_chain_slots", 31: "shared_pass_partial_batches",
                  32: "own_queue_streams_created_by_the_process", 33: "multi_responses_batched",
-                 34: "multi_responses_host", 35: "multi_union_fills"}  # (4-6: mechanisms removed in round 3)
+                 34: "multi_responses_host", 35: "multi_union_fills", 36: "x_bytes_uploaded_from_host",
+                 37: "x_bytes_ingested_on_device"}  # (4-6: mechanisms removed in round 3)
         return {n: int(lib().bessx_session_counter(self._h, i)) for i, n in names.items()}
 
     def screening(self):
@@ -417,9 +577,23 @@ class Session:
                                                                    ic_type, int(is_cv), r),
                          seq.size * lam.size, min(self.p, (int(seq.max()) if seq.size else 1) * self._gsize_max))
 
-    def set_responses(self, Y):
+    def set_responses(self, Y, stream=0):
         """R extra responses for this session's design (bessx_session_set_responses): Y is n x R; every column is
-        prepared like the session's own y.  Replaces an earlier set; the session's own y stays."""
+        prepared like the session's own y.  Replaces an earlier set; the session's own y stays.  Y may be a device
+        array (float64 / float32, any strides; stream: the stream it was produced on)."""
+        if is_device_array(Y):
+            dY = _DeviceArray(Y, "Y")
+            shape = dY.shape if len(dY.shape) == 2 else (dY.shape[0], 1)
+            strides = dY.strides if len(dY.shape) == 2 else (dY.strides[0], 0)
+            if shape[0] != self.n:
+                raise ValueError("Y must have shape (n, R) with n = %d rows" % self.n)
+            rc = lib().bessx_session_set_responses_device(self._h, dY.ptr, dY.dtype, strides[0], strides[1], shape[1],
+                                                          int(stream) if stream else None)
+            if rc == 1 and "NaN" in last_error():
+                raise ValueError("Y contains NaN")
+            _check(rc)
+            self._n_responses = shape[1]
+            return
         Y = np.asarray(Y, dtype=np.float64)
         if Y.ndim == 1:
             Y = Y.reshape(-1, 1)
@@ -711,6 +885,53 @@ def op_stream_copy_gbps(nbytes=1 << 30, repeats=10):
     g = _d(0)
     _check(lib().bessx_op_stream_copy_gbps(nbytes, repeats, ctypes.byref(g)))
     return g.value
+
+
+def _ingest_args(x, row_order):
+    dx = _DeviceArray(x, "x")
+    shape = dx.shape if len(dx.shape) == 2 else (dx.shape[0], 1)
+    strides = dx.strides if len(dx.shape) == 2 else (dx.strides[0], 0)
+    ro = None
+    if row_order is not None:
+        ro = _i32(row_order).reshape(-1)
+        if ro.size != shape[0]:
+            raise ValueError("row_order must have one entry per row")
+    return dx, shape, strides, ro
+
+
+def padded_rows(n):
+    """Leading dimension of a session's matrix for n rows (bessx_session_create: row blocks of 128 * U)."""
+    rb = 128 * (8 if n >= 4096 else (4 if n >= 2048 else (2 if n >= 1024 else 1)))
+    return (n + rb - 1) // rb * rb
+
+
+def op_ingest(x, row_order=None, ld=None, stream=0):
+    """The ingest kernel alone on a device array x (n x p): (the zero-padded column-major fp64 image as an (ld, p)
+    Fortran-ordered host array, NaN flag)."""
+    dx, (n, p), (rs, cs), ro = _ingest_args(x, row_order)
+    ld = padded_rows(n) if ld is None else int(ld)
+    out = np.empty((ld, p), order="F")
+    flag = np.zeros(1, dtype=np.int32)
+    _check(lib().bessx_op_ingest(dx.ptr, dx.dtype, rs, cs, _ip(ro), n, p, ld, int(stream) if stream else None, _dp(out),
+                                 _ip(flag)))
+    return out, bool(flag[0])
+
+
+def device_to_host(a, stream=0):
+    """A device array (1-D or 2-D, float64 / float32) as a float64 host array of the same shape, through the ingest
+    kernel -- for the n-value vectors (y, weight) of the estimators; no torch needed."""
+    shape = _DeviceArray(a, "array").shape
+    out, _ = op_ingest(a, ld=(shape[0] + 127) // 128 * 128, stream=stream)
+    return np.ascontiguousarray(out[:shape[0]]).reshape(shape)
+
+
+def op_ingest_bench(x, row_order=None, repeats=20):
+    """(ms per launch, GB/s of bytes read + written) of the ingest kernel on the device array x, device events."""
+    dx, (n, p), (rs, cs), ro = _ingest_args(x, row_order)
+    ms, g = _d(0), _d(0)
+    _check(lib().bessx_op_ingest_bench(dx.ptr, dx.dtype, rs, cs, _ip(ro), n, p, padded_rows(n), repeats,
+                                       ctypes.byref(ms), ctypes.byref(g)))
+    return ms.value, g.value
 
 
 def op_chol_bench(m, repeats=200):

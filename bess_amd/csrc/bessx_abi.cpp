@@ -6,7 +6,9 @@ extern "C" {
 // ----------------------------------------------------------------------------------------------
 // pywrap_bess drop-in (src/bess.cpp:218-281 -> bessCpp :37-214)
 // ----------------------------------------------------------------------------------------------
-int bessx_pywrap_bess(double *x, int x_row, int x_col, double *y, int y_len, int data_type, double *weight,
+// the body of bessx_pywrap_bess and bessx_pywrap_bess_device: din null = x, y, weight on the host; else the data of din
+static int pywrap_impl(const bessx_device_input *din, double *x, int x_row, int x_col, double *y, int y_len,
+                       int data_type, double *weight,
                       int weight_len, int is_normal, int algorithm_type, int model_type, int max_iter,
                       int exchange_num, int path_type, int is_warm_start, int ic_type, int is_cv, int K, int *gindex,
                       int gindex_len, double *state, int state_len, int *sequence, int sequence_len,
@@ -20,8 +22,8 @@ int bessx_pywrap_bess(double *x, int x_row, int x_col, double *y, int y_len, int
   (void)exchange_num; (void)state; (void)state_len; (void)K_max; (void)epsilon;
   (void)tao;  // dead on the live reference paths
   (void)coef0_out_len; (void)train_loss_out_len; (void)ic_out_len;
-  if (!x || !y || !beta_out || !coef0_out || !train_loss_out || !ic_out) return fail(BESSX_ERR_ARG, "null argument");
-  if (y_len != x_row || (weight && weight_len != x_row)) return fail(BESSX_ERR_ARG, "length of y / weight != rows of x");
+  if ((!din && (!x || !y)) || !beta_out || !coef0_out || !train_loss_out || !ic_out) return fail(BESSX_ERR_ARG, "null argument");
+  if (!din && (y_len != x_row || (weight && weight_len != x_row))) return fail(BESSX_ERR_ARG, "length of y / weight != rows of x");
   if (beta_out_len < x_col) return fail(BESSX_ERR_ARG, "beta_out too short");
   if (!gindex || gindex_len < 1 || gindex_len > x_col) return fail(BESSX_ERR_ARG, "bad group index");
   bessx_problem pb;
@@ -56,7 +58,7 @@ int bessx_pywrap_bess(double *x, int x_row, int x_col, double *y, int y_len, int
     pb.max_sparsity = (int)std::min<long>(std::min<long>(top * gmax, x_col), T0_HARD);
   }
   bessx_session *s = nullptr;
-  if (int rc = bessx_session_create(&s, &pb)) return rc;
+  if (int rc = din ? bessx_session_create_device(&s, &pb, din) : bessx_session_create(&s, &pb)) return rc;
   int rc = 0;
   if (is_cv) rc = bessx_session_set_cv(s, K, nullptr, 123u);
   bessx_path_result res;
@@ -90,6 +92,51 @@ int bessx_pywrap_bess(double *x, int x_row, int x_col, double *y, int y_len, int
   std::string keep = g_err;
   bessx_session_destroy(s);
   g_err = keep;
+  return rc;
+}
+
+int bessx_pywrap_bess(double *x, int x_row, int x_col, double *y, int y_len, int data_type, double *weight,
+                      int weight_len, int is_normal, int algorithm_type, int model_type, int max_iter,
+                      int exchange_num, int path_type, int is_warm_start, int ic_type, int is_cv, int K, int *gindex,
+                      int gindex_len, double *state, int state_len, int *sequence, int sequence_len,
+                      double *lambda_sequence, int lambda_sequence_len, int s_min, int s_max, int K_max,
+                      double epsilon, double lambda_min, double lambda_max, int n_lambda, int is_screening,
+                      int screening_size, int powell_path, int *always_select, int always_select_len, double tao,
+                      double *beta_out, int beta_out_len, double *coef0_out, int coef0_out_len,
+                      double *train_loss_out, int train_loss_out_len, double *ic_out, int ic_out_len,
+                      double *nullloss_out, double *aic_out, int aic_out_len, double *bic_out, int bic_out_len,
+                      double *gic_out, int gic_out_len, int *A_out, int A_out_len, int *l_out) {
+  return pywrap_impl(nullptr, x, x_row, x_col, y, y_len, data_type, weight, weight_len, is_normal, algorithm_type,
+                     model_type, max_iter, exchange_num, path_type, is_warm_start, ic_type, is_cv, K, gindex, gindex_len,
+                     state, state_len, sequence, sequence_len, lambda_sequence, lambda_sequence_len, s_min, s_max, K_max,
+                     epsilon, lambda_min, lambda_max, n_lambda, is_screening, screening_size, powell_path, always_select,
+                     always_select_len, tao, beta_out, beta_out_len, coef0_out, coef0_out_len, train_loss_out,
+                     train_loss_out_len, ic_out, ic_out_len, nullloss_out, aic_out, aic_out_len, bic_out, bic_out_len,
+                     gic_out, gic_out_len, A_out, A_out_len, l_out);
+}
+
+int bessx_pywrap_bess_device(const bessx_device_input *in, int x_row, int x_col, int data_type, int is_normal,
+                             int algorithm_type, int model_type, int max_iter, int exchange_num, int path_type,
+                             int is_warm_start, int ic_type, int is_cv, int K, int *gindex, int gindex_len,
+                             double *state, int state_len, int *sequence, int sequence_len, double *lambda_sequence,
+                             int lambda_sequence_len, int s_min, int s_max, int K_max, double epsilon,
+                             double lambda_min, double lambda_max, int n_lambda, int is_screening, int screening_size,
+                             int powell_path, int *always_select, int always_select_len, double tao, double *beta_out,
+                             int beta_out_len, double *coef0_out, int coef0_out_len, double *train_loss_out,
+                             int train_loss_out_len, double *ic_out, int ic_out_len, double *nullloss_out,
+                             double *aic_out, int aic_out_len, double *bic_out, int bic_out_len, double *gic_out,
+                             int gic_out_len, int *A_out, int A_out_len, int *l_out, int *x_nan_out) {
+  if (x_nan_out) *x_nan_out = 0;
+  if (!in) return fail(BESSX_ERR_ARG, "null argument");
+  const int rc = pywrap_impl(in, nullptr, x_row, x_col, nullptr, x_row, data_type, nullptr, x_row, is_normal,
+                             algorithm_type, model_type, max_iter, exchange_num, path_type, is_warm_start, ic_type, is_cv,
+                             K, gindex, gindex_len, state, state_len, sequence, sequence_len, lambda_sequence,
+                             lambda_sequence_len, s_min, s_max, K_max, epsilon, lambda_min, lambda_max, n_lambda,
+                             is_screening, screening_size, powell_path, always_select, always_select_len, tao, beta_out,
+                             beta_out_len, coef0_out, coef0_out_len, train_loss_out, train_loss_out_len, ic_out,
+                             ic_out_len, nullloss_out, aic_out, aic_out_len, bic_out, bic_out_len, gic_out, gic_out_len,
+                             A_out, A_out_len, l_out);
+  if (rc == BESSX_ERR_ARG && x_nan_out && g_err == "There is NAN value in X") *x_nan_out = 1;
   return rc;
 }
 
@@ -658,5 +705,78 @@ int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps) {
   return BESSX_OK;
 }
 
+// the ingest kernel alone on a caller's device matrix (tests/test_device_input_gpu.py)
+static int op_ingest_prepare(const void *x, int dtype, long long rs, long long cs, const int *row_order, int n, int p,
+                             long long ld, Scratch &sc, double **dst, unsigned **flag, int **order_d) {
+  if (int rc = need_device()) return rc;
+  if (ld < n || ld % 128 != 0) return fail(BESSX_ERR_ARG, "op_ingest: ld must be a multiple of 128, at least n");
+  int dev = -1;
+  if (int rc = check_device_matrix("op_ingest: x", x, dtype, rs, cs, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  *order_d = nullptr;
+  if (row_order) {
+    for (int i = 0; i < n; i++)
+      if (row_order[i] < 0 || row_order[i] >= n) return fail(BESSX_ERR_ARG, "op_ingest: row_order entry out of range");
+    HIPX(sc.alloc(order_d, (size_t)n));
+    HIPX(hipMemcpy(*order_d, row_order, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  }
+  HIPX(sc.alloc(dst, (size_t)ld * p));
+  HIPX(sc.alloc(flag, 1));
+  return 0;
+}
+
+int bessx_op_ingest(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order, int n,
+                    int p, long long ld, void *stream, double *out, int *nan_flag) {
+  if (!out || !nan_flag) return fail(BESSX_ERR_ARG, "op_ingest: null argument");
+  Scratch sc;
+  double *dst = nullptr;
+  unsigned *flag = nullptr;
+  int *od = nullptr;
+  if (int rc = op_ingest_prepare(x, dtype, row_stride, col_stride, row_order, n, p, ld, sc, &dst, &flag, &od)) return rc;
+  HIPX(hipMemset(dst, 0xff, (size_t)ld * p * sizeof(double)));  // the kernel itself must write every padding row
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc = ingest_enqueue(x, dtype == BESSX_F32, row_stride, col_stride, od, n, p, dst, ld, flag,
+                          static_cast<hipStream_t>(stream), st);
+  unsigned h = 0;
+  if (rc == 0) {
+    hipError_t e = hipMemcpyAsync(out, dst, (size_t)ld * p * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, flag, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(BESSX_ERR_HIP, std::string("op_ingest: ") + hipGetErrorString(e));
+  }
+  (void)hipStreamDestroy(st);
+  *nan_flag = h ? 1 : 0;
+  return rc;
+}
+
+int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order,
+                          int n, int p, long long ld, int repeats, double *avg_ms, double *gbps) {
+  if (repeats < 1 || !avg_ms || !gbps) return fail(BESSX_ERR_ARG, "op_ingest_bench: bad arguments");
+  Scratch sc;
+  double *dst = nullptr;
+  unsigned *flag = nullptr;
+  int *od = nullptr;
+  if (int rc = op_ingest_prepare(x, dtype, row_stride, col_stride, row_order, n, p, ld, sc, &dst, &flag, &od)) return rc;
+  HIPX(hipMemset(flag, 0, sizeof(unsigned)));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(hipEventCreate(&e0));
+  HIPX(hipEventCreate(&e1));
+  const int f32 = dtype == BESSX_F32;
+  HIPX(launch_ingest(x, f32, row_stride, col_stride, od, n, p, dst, ld, flag, nullptr));
+  HIPX(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < repeats; i++) HIPX(launch_ingest(x, f32, row_stride, col_stride, od, n, p, dst, ld, flag, nullptr));
+  HIPX(hipEventRecord(e1, nullptr));
+  HIPX(hipEventSynchronize(e1));
+  float ms = 0.f;
+  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  const double bytes = (double)n * (double)p * (f32 ? 4.0 : 8.0) + (double)ld * (double)p * 8.0;
+  *avg_ms = ms / repeats;
+  *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;
+  return BESSX_OK;
+}
 
 }  // extern "C"

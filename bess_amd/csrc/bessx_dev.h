@@ -49,6 +49,10 @@ struct GramTask {
 };
 
 hipError_t launch_transpose_in(const double *src, int rows, int p, double *X, long ld, long r0, hipStream_t st);
+// device ingest (bessx_k_ingest.hip): X (ld x p, ld a multiple of 128, rows n..ld zero) <- a device matrix of fp64 / fp32
+// elements, element (i, j) at src[order[i] * rs + j * cs] (order: device, may be null); *nan_flag is set on a NaN
+hipError_t launch_ingest(const void *src, int f32, long long rs, long long cs, const int *order, long long n,
+                         long long p, double *X, long long ld, unsigned *nan_flag, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

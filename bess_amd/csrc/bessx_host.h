@@ -295,6 +295,7 @@ struct bessx_session {
   double *own_y = nullptr;
   double own_yy = 0.0, own_mean = 0.0, own_null = 0.0;
   long long multi_batched = 0, multi_host = 0, multi_fills = 0;
+  long long x_host_bytes = 0, x_dev_bytes = 0;  // bytes of X uploaded from host memory / ingested from device memory
   bool fcols_wide = false;  // cov_fcols holds every column (+ 4 COV_R): the union fill of many responses' lists
   long long kch_merged = 0, kch_takeovers = 0;  // chunk phases run as merged launches; chains the host had to finish
   long long kch_paths = 0, kch_refits = 0, kch_chunk_fills = 0;  // paths run chunked, stitch refits, fills in the chunk phase
@@ -456,6 +457,23 @@ int gram_tasks_for(bessx_session *s, int mt, const GramTask **tasks, int *ntask)
 void gram_geometry(const bessx_session *s, int ntask, int *rows_per_slab, int *nslab, int ntiles = 0,
                           bool allow_lds = true);
 int upload_x(bessx_session *s, const double *x, int col_major);
+// a caller's matrix in DEVICE memory (bessx_device_input): element (i, j) at data[order_d[i] * rs + j * cs]
+struct DevX {
+  const void *data = nullptr;
+  int f32 = 0;
+  long long rs = 0, cs = 0;
+  const int *order_d = nullptr;  // device copy of the row order, or null
+  hipStream_t stream = nullptr;  // the caller's stream: reads are ordered after the work queued on it so far
+};
+// fill s->X (s->ld x s->p) from dx on the session's stream and wait for it; BESSX_ERR_ARG "There is NAN value in X"
+int ingest_x(bessx_session *s, const DevX &dx);
+// dst (device, ld x p) <- a caller's device matrix, ordered after `caller`, on `st` (not waited for)
+int ingest_enqueue(const void *src, int f32, long long rs, long long cs, const int *order_d, long long n, long long p,
+                   double *dst, long long ld, unsigned *nan_flag, hipStream_t caller, hipStream_t st);
+// BESSX_ERR_ARG unless data .. data + extent of the (n, p, rs, cs) view is device memory; *device_out: its device
+int check_device_matrix(const char *what, const void *data, int dtype, long long rs, long long cs, long long n,
+                        long long p, int *device_out);
+int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX *dx);
 int prepare_rowset(bessx_session *s, int rs, bool keep_yy = false);
 int cov_C_dev(const bessx_session *s);
 bool cov_speculates(const bessx_session *s);

@@ -2,6 +2,7 @@
 // time stamps and counters live in __device__ variables of bessx_kdev.hpp, which every separately compiled unit would
 // own a copy of.  Never part of the product library.
 #include "bessx_k_lm.hip"
+#include "bessx_k_ingest.hip"
 #include "bessx_k_solve.hip"
 #include "bessx_k_glm.hip"
 #include "bessx_k_cox.hip"

@@ -305,6 +305,35 @@ int bessx_session_set_responses(bessx_session *s, const double *Y, int R, int co
   return BESSX_OK;
 }
 
+int bessx_session_set_responses_device(bessx_session *s, const void *Y, int dtype, long long row_stride,
+                                       long long col_stride, int R, void *stream) {
+  if (!s || !Y) return fail(BESSX_ERR_ARG, "set_responses: null session or Y");
+  if (R < 1) return fail(BESSX_ERR_ARG, "set_responses: R must be at least 1");
+  if (s->model_type != 1)
+    return fail(BESSX_ERR_UNSUPPORTED, "set_responses: several responses exist for the linear model (model_type 1) only");
+  int dev = -1;
+  if (int rc = check_device_matrix("set_responses: device Y", Y, dtype, row_stride, col_stride, s->n, R, &dev)) return rc;
+  if (dev != s->device) return fail(BESSX_ERR_ARG, "set_responses: device Y: memory of another device than the session's");
+  HIPX(hipSetDevice(s->device));
+  if (int rc = settle_device_chain(s)) return rc;
+  // Y is n x R values: the ingest kernel makes them fp64 column-major, the host copy goes through the host entry
+  const int n = s->n;
+  const long long ld = ((long long)n + 127) / 128 * 128;
+  Scratch sc;
+  double *d = nullptr;
+  unsigned *flag = nullptr;
+  HIPX(sc.alloc(&d, (size_t)ld * R));
+  HIPX(sc.alloc(&flag, 1));
+  std::vector<double> host((size_t)n * R);
+  if (int rc = ingest_enqueue(Y, dtype == BESSX_F32, row_stride, col_stride, nullptr, n, R, d, ld, flag,
+                              static_cast<hipStream_t>(stream), s->st))
+    return rc;
+  HIPX(hipMemcpy2DAsync(host.data(), (size_t)n * sizeof(double), d, (size_t)ld * sizeof(double),
+                        (size_t)n * sizeof(double), (size_t)R, hipMemcpyDeviceToHost, s->st));
+  HIPX(hipStreamSynchronize(s->st));
+  return bessx_session_set_responses(s, host.data(), R, 1);
+}
+
 int bessx_session_sequential_path_multi(bessx_session *s, const int *sequence, int sequence_len,
                                         const double *lambda_seq, int lambda_len, int ic_type, int is_cv,
                                         bessx_path_result *res) {

@@ -503,6 +503,7 @@ void gram_geometry(const bessx_session *s, int ntask, int *rows_per_slab, int *n
 // upload x (row- or column-major host memory) into the padded column-major device matrix
 int upload_x(bessx_session *s, const double *x, int col_major) {
   const int n = s->n, p = s->p;
+  s->x_host_bytes += (long long)n * p * (long long)sizeof(double);
   HIPX(hipMemsetAsync(s->X, 0, (size_t)s->ld * p * sizeof(double), s->st));
   if (col_major) {
     HIPX(hipMemcpy2DAsync(s->X, (size_t)s->ld * sizeof(double), x, (size_t)n * sizeof(double),
@@ -527,6 +528,69 @@ int upload_x(bessx_session *s, const double *x, int col_major) {
     }
   }
   HIPX(hipFree(stage));
+  return 0;
+}
+
+// ---- X already in device memory (bessx_session_create_device) ----
+int check_device_matrix(const char *what, const void *data, int dtype, long long rs, long long cs, long long n,
+                        long long p, int *device_out) {
+  const std::string w(what);
+  if (!data) return fail(BESSX_ERR_ARG, w + ": null device pointer");
+  if (dtype != BESSX_F64 && dtype != BESSX_F32) return fail(BESSX_ERR_ARG, w + ": dtype must be BESSX_F64 or BESSX_F32");
+  if (rs < 0 || cs < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (n < 1 || p < 1) return fail(BESSX_ERR_ARG, w + ": empty matrix");
+  const size_t item = dtype == BESSX_F32 ? 4 : 8;
+  if ((reinterpret_cast<uintptr_t>(data) % item) != 0) return fail(BESSX_ERR_ARG, w + ": pointer not aligned to its element size");
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, data) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BESSX_ERR_ARG, w + ": not a device pointer (hipPointerGetAttributes does not know it)");
+  }
+  if (at.type != hipMemoryTypeDevice) return fail(BESSX_ERR_ARG, w + ": not device memory (host or managed memory)");
+  // the whole view must lie inside the allocation that holds its first element
+  void *base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t *>(&base), &size, const_cast<void *>(data)) == hipSuccess) {
+    const unsigned __int128 last = (unsigned __int128)(n - 1) * (unsigned __int128)rs + (unsigned __int128)(p - 1) * (unsigned __int128)cs;
+    const unsigned __int128 end = (unsigned __int128)(reinterpret_cast<uintptr_t>(data) - reinterpret_cast<uintptr_t>(base)) +
+                                  (last + 1) * item;
+    if (end > (unsigned __int128)size) return fail(BESSX_ERR_ARG, w + ": the view reaches past the end of its device allocation");
+  } else {
+    (void)hipGetLastError();
+  }
+  if (device_out) *device_out = at.device;
+  return 0;
+}
+
+int ingest_enqueue(const void *src, int f32, long long rs, long long cs, const int *order_d, long long n, long long p,
+                   double *dst, long long ld, unsigned *nan_flag, hipStream_t caller, hipStream_t st) {
+  // reads come after everything the caller has queued on its stream so far
+  hipEvent_t ev = nullptr;
+  HIPX(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, caller);
+  if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+  (void)hipEventDestroy(ev);  // (released once the record has completed)
+  if (e == hipSuccess) e = hipMemsetAsync(nan_flag, 0, sizeof(unsigned), st);
+  if (e == hipSuccess) e = launch_ingest(src, f32, rs, cs, order_d, n, p, dst, ld, nan_flag, st);
+  if (e != hipSuccess) return fail(BESSX_ERR_HIP, std::string("ingest: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int ingest_x(bessx_session *s, const DevX &dx) {
+  unsigned *flag = nullptr;
+  HIPX(dmalloc(&flag, 1));
+  unsigned h = 0;
+  int rc = ingest_enqueue(dx.data, dx.f32, dx.rs, dx.cs, dx.order_d, s->n, s->p, s->X, s->ld, flag, dx.stream, s->st);
+  if (rc == 0) {
+    hipError_t e = hipMemcpyAsync(&h, flag, sizeof(unsigned), hipMemcpyDeviceToHost, s->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->st);
+    if (e != hipSuccess) rc = fail(BESSX_ERR_HIP, std::string("ingest_x: ") + hipGetErrorString(e));
+  }
+  (void)hipFree(flag);
+  if (rc) return rc;
+  s->x_dev_bytes += (long long)s->n * s->p * (dx.f32 ? 4 : 8);
+  if (h) return fail(BESSX_ERR_ARG, "There is NAN value in X");
   return 0;
 }
 
@@ -673,6 +737,16 @@ int bessx_device_info(char *buf, int buf_len) {
 
 int bessx_session_create(bessx_session **out, const bessx_problem *pb) {
   if (!out || !pb || !pb->x || !pb->y) return fail(BESSX_ERR_ARG, "null argument");
+  return session_create_impl(out, pb, nullptr);
+}
+
+}  // extern "C"
+
+namespace bessx {
+
+// bessx_session_create; dx: X in device memory (pb->x, pb->x_col_major unused), or null: X at pb->x on the host
+int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX *dx) {
+  if (!out || !pb || (!dx && !pb->x) || !pb->y) return fail(BESSX_ERR_ARG, "null argument");
   if (pb->n < 1 || pb->p < 1) return fail(BESSX_ERR_ARG, "n and p must be positive");
   if (pb->model_type < 1 || pb->model_type > 4) return fail(BESSX_ERR_ARG, "model_type must be 1..4");
   if (pb->algorithm_type != 1 && pb->algorithm_type != 5 && pb->algorithm_type != 2 && pb->algorithm_type != 3)
@@ -783,7 +857,7 @@ int bessx_session_create(bessx_session **out, const bessx_problem *pb) {
     HIPS(dmalloc(&Xraw, (size_t)ld * pf));
     s->X = Xraw;
     {
-      int rc = upload_x(s, pb->x, pb->x_col_major);
+      int rc = dx ? ingest_x(s, *dx) : upload_x(s, pb->x, pb->x_col_major);
       if (rc) {
         drop();
         return bail(rc);
@@ -873,8 +947,12 @@ int bessx_session_create(bessx_session **out, const bessx_problem *pb) {
                                "undefined behaviour in the reference (logit_fit returns n coefficients, "
                                "src/logistic.cpp:62-110, of which screening() reads the last g_size, src/screening.cpp:60)"));
             }
-            std::vector<double> xs((size_t)n * gs);
-            if (pb->x_col_major) {
+            std::vector<double> xs(dx ? 0 : (size_t)n * gs);
+            DevX subx;
+            if (dx) {  // the group's columns as a column-offset view of the caller's matrix
+              subx = *dx;
+              subx.data = static_cast<const char *>(dx->data) + (size_t)g_lo[g] * (size_t)dx->cs * (dx->f32 ? 4 : 8);
+            } else if (pb->x_col_major) {
               std::memcpy(xs.data(), pb->x + (size_t)g_lo[g] * n, xs.size() * sizeof(double));
             } else {
               for (int i = 0; i < n; i++)
@@ -896,7 +974,7 @@ int bessx_session_create(bessx_session **out, const bessx_problem *pb) {
             q.device = s->device;
             bessx_session *sub = nullptr;
             g_marginal_fit_variant = logit ? 1 : 2;
-            int rc = bessx_session_create(&sub, &q);
+            int rc = session_create_impl(&sub, &q, dx ? &subx : nullptr);
             g_marginal_fit_variant = 0;
             std::vector<int> sup((size_t)gs);
             std::vector<double> bq((size_t)gs);
@@ -1135,7 +1213,7 @@ int bessx_session_create(bessx_session **out, const bessx_problem *pb) {
   }
   static_assert(sizeof(FitCtrl) <= 128, "FitCtrl must fit its slot of the result block");
   // data
-  if (!x_ready) TRY(upload_x(s, pb->x, pb->x_col_major));
+  if (!x_ready) TRY(dx ? ingest_x(s, *dx) : upload_x(s, pb->x, pb->x_col_major));
   {
     std::vector<double> tmp((size_t)ld, 0.0);
     std::copy(pb->y, pb->y + n, tmp.begin());
@@ -1344,6 +1422,87 @@ int bessx_session_create(bessx_session **out, const bessx_problem *pb) {
 #undef HIPT
   *out = s;
   return BESSX_OK;
+}
+
+// n values of a caller's device vector as fp64 on the host (through the ingest kernel: one column)
+static int fetch_device_vector(const char *what, const void *data, int dtype, long long stride, int n, int device,
+                               hipStream_t caller, std::vector<double> &host) {
+  int dev = -1;
+  if (int rc = check_device_matrix(what, data, dtype, stride, 0, n, 1, &dev)) return rc;
+  if (dev != device) return fail(BESSX_ERR_ARG, std::string(what) + ": memory of another device than the session's");
+  const long long ld = ((long long)n + 127) / 128 * 128;
+  Scratch sc;
+  double *d = nullptr;
+  unsigned *flag = nullptr;
+  HIPX(sc.alloc(&d, (size_t)ld));
+  HIPX(sc.alloc(&flag, 1));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  host.assign((size_t)n, 0.0);
+  int rc = ingest_enqueue(data, dtype == BESSX_F32, stride, 0, nullptr, n, 1, d, ld, flag, caller, st);
+  if (rc == 0) {
+    hipError_t e = hipMemcpyAsync(host.data(), d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(BESSX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+}  // namespace bessx
+
+extern "C" {
+
+int bessx_session_create_device(bessx_session **out, const bessx_problem *pb, const bessx_device_input *in) {
+  if (!out || !pb || !in) return fail(BESSX_ERR_ARG, "null argument");
+  if (pb->n < 1 || pb->p < 1) return fail(BESSX_ERR_ARG, "n and p must be positive");
+  if (!in->y_host && !in->y_dev) return fail(BESSX_ERR_ARG, "device input: y_host or y_dev must be given");
+  if (in->y_host && in->y_dev) return fail(BESSX_ERR_ARG, "device input: give y_host or y_dev, not both");
+  if (in->weight_host && in->weight_dev) return fail(BESSX_ERR_ARG, "device input: give weight_host or weight_dev, not both");
+  if (int rc = need_device()) return rc;
+  const int n = pb->n;
+  int xdev = -1;
+  if (int rc = check_device_matrix("device input x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, n, pb->p, &xdev))
+    return rc;
+  if (pb->device >= 0 && pb->device != xdev)
+    return fail(BESSX_ERR_ARG, "device input x: memory of another device than bessx_problem.device");
+  if (in->row_order) {
+    std::vector<unsigned char> seen((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+      const int r = in->row_order[i];
+      if (r < 0 || r >= n || seen[(size_t)r]) return fail(BESSX_ERR_ARG, "device input: row_order must be a permutation of 0..n-1");
+      seen[(size_t)r] = 1;
+    }
+  }
+  HIPX(hipSetDevice(xdev));
+  hipStream_t caller = static_cast<hipStream_t>(in->stream);
+  std::vector<double> yh, wh;
+  if (in->y_dev)
+    if (int rc = fetch_device_vector("device input y", in->y_dev, in->y_dtype, in->y_stride, n, xdev, caller, yh)) return rc;
+  if (in->weight_dev)
+    if (int rc = fetch_device_vector("device input weight", in->weight_dev, in->weight_dtype, in->weight_stride, n, xdev,
+                                     caller, wh))
+      return rc;
+  bessx_problem q = *pb;
+  q.x = nullptr;
+  q.x_col_major = 0;
+  q.y = in->y_dev ? yh.data() : in->y_host;
+  q.weight = in->weight_dev ? wh.data() : in->weight_host;
+  q.device = xdev;
+  DevX dx;
+  dx.data = in->x;
+  dx.f32 = in->x_dtype == BESSX_F32;
+  dx.rs = in->x_row_stride;
+  dx.cs = in->x_col_stride;
+  dx.stream = caller;
+  Scratch sc;
+  if (in->row_order) {
+    int *od = nullptr;
+    HIPX(sc.alloc(&od, (size_t)n));
+    HIPX(hipMemcpy(od, in->row_order, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    dx.order_d = od;
+  }
+  return session_create_impl(out, &q, &dx);
 }
 
 void bessx_session_destroy(bessx_session *s) { session_free(s); }
@@ -1980,6 +2139,8 @@ long long bessx_session_counter(const bessx_session *s, int which) {
     case 33: return s->multi_batched;
     case 34: return s->multi_host;
     case 35: return s->multi_fills;
+    case 36: return s->x_host_bytes;
+    case 37: return s->x_dev_bytes;
     case 10: {  // times the Gram column cache of the all-rows row set was started over since the last path started
       if (s->cov.empty()) return 0;
       int m[8] = {0, 0, 0, 0, 0, 0, 0, 0};

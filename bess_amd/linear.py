@@ -5,6 +5,7 @@ pywrap_bess (python/bess/linear.py:204-387) is restated here; all numerical work
 the HIP library through bess_amd.capi.pywrap_bess -- there is no NumPy solver in this file.
 """
 import math
+import sys
 
 import numpy as np
 
@@ -17,6 +18,15 @@ _IC_CODE = {"aic": 1, "bic": 2, "gic": 3, "ebic": 4}               # linear.py:1
 _DATA_TYPE = {"Lm": 1, "Logistic": 2, "Poisson": 2, "Cox": 3}      # linear.py:475,517,559,597
 
 
+def _current_stream(a):
+    """Raw handle of torch's current stream for a's device when a is a torch tensor (torch is looked up, never
+    imported), else 0 (the null stream)."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(a, torch.Tensor) and a.is_cuda:
+        return int(torch.cuda.current_stream(a.device).cuda_stream)
+    return 0
+
+
 class bess_base:
     """Base estimator.  Parameters follow python/bess/linear.py:87-91:
 
@@ -25,6 +35,10 @@ class bess_base:
     is_screening=False, screening_size=None, powell_path=1, always_select=[], tao=0.
 
     Attributes after fit(): beta, coef0, train_loss, ic.
+
+    fit(X, y) also takes an X in GPU memory (a torch ROCm tensor, or anything with __cuda_array_interface__: float64
+    or float32, any strides): the library reads it where it lies, on torch's current stream, and X never crosses the
+    bus.  y and weight may be device arrays too (n values: they are copied to the host).  predict() takes host arrays.
     """
 
     def __init__(self, algorithm_type, model_type, path_type, max_iter=20, exchange_num=0, is_warm_start=True,
@@ -69,12 +83,31 @@ class bess_base:
         return [int(np.argmax(group == g)) for g in sorted(set(group.tolist()))]
 
     def fit(self, X, y, is_weight=False, is_normal=True, weight=None, state=None, group=None):
-        X, y = np.asarray(X), np.asarray(y)
-        if np.isnan(X).any():
-            raise ValueError("There is NAN value in X")
+        try:
+            self._fit(X, y, is_weight, is_normal, weight, state, group)
+        finally:
+            self._Y_device = None  # (no reference to the caller's device array outlives the call)
+
+    def _fit(self, X, y, is_weight, is_normal, weight, state, group):
+        on_device = capi.is_device_array(X)
+        self._stream, self._row_order, self._Y_device = (_current_stream(X) if on_device else 0), None, None
+        if on_device:
+            # X stays where it is: its NaN verdict comes from the ingest kernel's flag (capi raises the same message)
+            n, p = capi._DeviceArray(X, "X", 2).shape
+            if capi.is_device_array(y):
+                if len(y.__cuda_array_interface__["shape"]) == 2 and self.model_type_int == 1:
+                    self._Y_device = y
+                y = capi.device_to_host(y, _current_stream(y))
+            if weight is not None and capi.is_device_array(weight):
+                weight = capi.device_to_host(weight, _current_stream(weight))
+            y = np.asarray(y)
+        else:
+            X, y = np.asarray(X), np.asarray(y)
+            if np.isnan(X).any():
+                raise ValueError("There is NAN value in X")
+            n, p = X.shape
         if np.isnan(y).any():
             raise ValueError("There is NAN value in y")
-        n, p = X.shape
         self.p = p
         Y = None
         if self.model_type_int == 1 and y.ndim == 2 and y.shape[1] >= 2:
@@ -86,7 +119,11 @@ class bess_base:
         if self.model_type_int == 4:
             # Cox: rows by ascending time, response becomes the status column (linear.py:257-263)
             order = y[:, 0].argsort()
-            X, y = X[order], y[order][:, 1].reshape(-1)
+            if on_device:
+                self._row_order = order  # the ingest kernel reads the rows in this order: no sorted copy of X
+            else:
+                X = X[order]
+            y = y[order][:, 1].reshape(-1)
         if n != y.size:
             raise ValueError("X.shape(0) should be equal to y.size")
         if is_weight:
@@ -139,7 +176,7 @@ class bess_base:
                                   self.sequence, self.lambda_sequence, self.s_min, self.s_max, self.K_max,
                                   self.epsilon, self.lambda_min, self.lambda_max, self.n_lambda, self.is_screening,
                                   self.screening_size, self.powell_path, self.always_select, self.tao, p, 1, 1, 1, 1,
-                                  1, 1, p)
+                                  1, 1, p, row_order=self._row_order, stream=self._stream)
         self.beta, self.coef0, self.train_loss, self.ic = result[0], result[1], result[2], result[3]
 
     def _fit_responses(self, X, Y, weight, is_normal, g_index, state, p, top, gsz):
@@ -153,9 +190,12 @@ class bess_base:
                                model_type=self.model_type_int, algorithm_type=self.algorithm_type_int,
                                max_iter=self.max_iter, is_warm_start=self.is_warm_start,
                                always_select=self.always_select, g_index=list(g_index),
-                               max_sparsity=min(top * gsz, p, capi.MAX_SPARSITY))
+                               max_sparsity=min(top * gsz, p, capi.MAX_SPARSITY), stream=self._stream)
             try:
-                ses.set_responses(Y)
+                if self._Y_device is not None:
+                    ses.set_responses(self._Y_device, stream=_current_stream(self._Y_device))
+                else:
+                    ses.set_responses(Y)
                 res = ses.sequential_path_multi(self.sequence, self.lambda_sequence, self.ic_type_int)
             finally:
                 ses.close()
@@ -169,7 +209,7 @@ class bess_base:
                                        g_index, state, self.sequence, self.lambda_sequence, self.s_min, self.s_max,
                                        self.K_max, self.epsilon, self.lambda_min, self.lambda_max, self.n_lambda,
                                        self.is_screening, self.screening_size, self.powell_path, self.always_select,
-                                       self.tao, p, 1, 1, 1, 1, 1, 1, p)
+                                       self.tao, p, 1, 1, 1, 1, 1, 1, p, stream=self._stream)
                 beta[:, r] = out[0]
                 coef0[r], loss[r], ic[r] = (float(np.ravel(v)[0]) for v in out[1:4])
         self.beta, self.coef0, self.train_loss, self.ic = beta, coef0, loss, ic

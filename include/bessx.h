@@ -147,6 +147,62 @@ typedef struct {
 
 int bessx_session_create(bessx_session **out, const bessx_problem *prob);
 void bessx_session_destroy(bessx_session *s);
+
+/* ---------------------------------------------------------------------------------------
+ * 2b. X already in GPU memory.  The design matrix is read where it lies -- it never crosses the bus -- by one
+ *     ingest kernel (bessx_k_ingest.hip) that leaves in the session exactly (bit for bit) the matrix that
+ *     bessx_session_create uploads for the same values; everything after it is the same code.
+ *     A matrix is (data, dtype, row_stride, col_stride): element (i, j) at data[i * row_stride + j * col_stride],
+ *     strides in ELEMENTS, non-negative; dtype BESSX_F64 or BESSX_F32 (widened exactly).  Column-contiguous
+ *     (row_stride 1) and row-contiguous (col_stride 1, a C-contiguous torch tensor) sources run at streaming rate;
+ *     any other view is correct, not fast.
+ *     row_order (host, n entries, a permutation of 0..n-1; NULL = identity): session row i is row row_order[i] of x.
+ *     It applies to x ONLY: y and weight are given in the session's row order.  (The Cox estimators sort rows by
+ *     time this way without a second copy of X.)
+ *     y and weight are n values each: a host pointer (*_host) or a device vector (*_dev, *_dtype, *_stride); give one
+ *     of the two for y; weight may be all NULL (= ones).  They are copied to the host once.
+ *     stream: the HIP stream (hipStream_t) on which the caller produced the data, NULL = the null stream.  The library
+ *     orders its reads after the work queued on that stream so far (event + stream wait) and has finished reading
+ *     the caller's memory when the call returns: the caller's buffers are never written, never referenced afterwards,
+ *     and may be freed or overwritten at once.  Peak device memory is therefore the caller's X plus the session's own
+ *     padded fp64 copy (with screening: plus the kept columns).
+ *     Every device pointer must be device memory (hipPointerGetAttributes) of the session's device and hold the
+ *     whole view: otherwise BESSX_ERR_ARG, not a fault.  A NaN in x: BESSX_ERR_ARG, message "There is NAN value in X"
+ *     (the kernel raises a device flag; X is not read back).
+ * ------------------------------------------------------------------------------------- */
+enum { BESSX_F64 = 0, BESSX_F32 = 1 };
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_stride;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  const int *row_order;
+  void *stream;
+} bessx_device_input;
+/* bessx_session_create with the data of `in`: prob->x / y / weight / x_col_major are ignored; prob->device == -1
+ * means the device that owns in->x.  Screening works (wide-group marginal fits run on column-offset views of in->x). */
+int bessx_session_create_device(bessx_session **out, const bessx_problem *prob, const bessx_device_input *in);
+/* bessx_pywrap_bess for data in GPU memory (section 2b): the x, x_row, x_col triple becomes the descriptor plus the
+ * shape; y and weight come from the descriptor.  Everything after session creation is shared with bessx_pywrap_bess.
+ * *x_nan_out (may be NULL) is set to 1 when the call fails because x holds a NaN, else 0. */
+int bessx_pywrap_bess_device(const bessx_device_input *in, int x_row, int x_col, int data_type, int is_normal,
+                             int algorithm_type, int model_type, int max_iter, int exchange_num, int path_type,
+                             int is_warm_start, int ic_type, int is_cv, int K, int *gindex, int gindex_len,
+                             double *state, int state_len, int *sequence, int sequence_len, double *lambda_sequence,
+                             int lambda_sequence_len, int s_min, int s_max, int K_max, double epsilon,
+                             double lambda_min, double lambda_max, int n_lambda, int is_screening, int screening_size,
+                             int powell_path, int *always_select, int always_select_len, double tao, double *beta_out,
+                             int beta_out_len, double *coef0_out, int coef0_out_len, double *train_loss_out,
+                             int train_loss_out_len, double *ic_out, int ic_out_len, double *nullloss_out,
+                             double *aic_out, int aic_out_len, double *bic_out, int bic_out_len, double *gic_out,
+                             int gic_out_len, int *A_out, int A_out_len, int *l_out, int *x_nan_out);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -178,7 +234,9 @@ int bessx_session_score_mode(const bessx_session *s);
  * every chain had arrived (the 50 ms timeout), 32 streams with a hardware queue of their own the PROCESS has created so
  * far (they are recycled across sessions); bessx_session_sequential_path_multi: 33 responses run through the merged
  * engine, 34 responses or parts of responses the host finished through the ordinary path (takeovers, and every response
- * of a path the engine does not apply to), 35 union fills served during merged runs of responses.  -1 for an unknown id. */
+ * of a path the engine does not apply to), 35 union fills served during merged runs of responses; 36 bytes of X
+ * uploaded from host memory, 37 bytes of X ingested from device memory (source bytes, n * p * element size; a
+ * session of bessx_session_create_device reports 0 for 36).  -1 for an unknown id. */
 long long bessx_session_counter(const bessx_session *s, int which);
 
 /* Metric::set_cv_train_test_mask + cal_cv_group_XTX (src/Metric.h:49-129).  fold_id[i] in [0,K)
@@ -274,6 +332,10 @@ int bessx_session_sequential_path_chain(bessx_session *s, const int *sequence, i
  * response session returns) fails the whole call with that code; res[] is then incomplete and no response's result may
  * be used.  Counters 33-35 (bessx_session_counter). */
 int bessx_session_set_responses(bessx_session *s, const double *Y, int R, int col_major);
+/* The same for Y (n x R) in device memory, described like X in bessx_device_input (dtype, element strides, the
+ * caller's stream; same ordering and lifetime rules).  Same preparation and results as bessx_session_set_responses. */
+int bessx_session_set_responses_device(bessx_session *s, const void *Y, int dtype, long long row_stride,
+                                       long long col_stride, int R, void *stream);
 int bessx_session_sequential_path_multi(bessx_session *s, const int *sequence, int sequence_len,
                                         const double *lambda_seq, int lambda_len, int ic_type, int is_cv,
                                         bessx_path_result *res);
@@ -430,6 +492,15 @@ int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbp
 /* Device-to-device streaming copy rate in GB/s (read+write bytes / time): the measured HBM ceiling
  * quoted next to the spec peak in bench.py. */
 int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps);
+/* The ingest kernel alone (section 2b): x is a DEVICE matrix (dtype, element strides), row_order a host permutation or
+ * NULL, ld a multiple of 128 >= n.  out (host, ld * p doubles) receives the padded column-major image, *nan_flag 1 if
+ * the kernel met a NaN, else 0. */
+int bessx_op_ingest(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order, int n,
+                    int p, long long ld, void *stream, double *out, int *nan_flag);
+/* The same launch timed with device events: one warm-up, then `repeats` launches; *avg_ms per launch and *gbps of
+ * bytes read (n * p * element size) plus bytes written (ld * p * 8). */
+int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order,
+                          int n, int p, long long ld, int repeats, double *avg_ms, double *gbps);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
