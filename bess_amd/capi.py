@@ -470,7 +470,8 @@ class Session:
                  29: "shared_pass_launches", 30: "shared_pass_chain_slots", 31: "shared_pass_partial_batches",
                  32: "own_queue_streams_created_by_the_process", 33: "multi_responses_batched",
                  34: "multi_responses_host", 35: "multi_union_fills", 36: "x_bytes_uploaded_from_host",
-                 37: "x_bytes_ingested_on_device"}  # (4-6: mechanisms removed in round 3)
+                 37: "x_bytes_ingested_on_device", 38: "live_device_bytes_of_the_process",
+                 39: "live_pinned_bytes_of_the_process", 40: "allocation_requests_of_the_process"}  # (4-6: mechanisms removed in round 3)
         return {n: int(lib().bessx_session_counter(self._h, i)) for i, n in names.items()}
 
     def screening(self):

@@ -260,7 +260,7 @@ int bessx_op_xtv(const double *x, int n, int p, int ld, const double *v, const d
                  double *out2) {
   if (int rc = need_device()) return rc;
   if (!x || !v || !out || n < 1 || p < 1 || ld < n) return fail(BESSX_ERR_ARG, "op_xtv: bad arguments");
-  Scratch sc;
+  Owner sc;
   const int U = n >= 4096 ? 8 : (n >= 2048 ? 4 : (n >= 1024 ? 2 : 1));
   double *dX, *dv, *dv2 = nullptr, *part, *part2 = nullptr, *dout;
   long ldd;
@@ -289,7 +289,7 @@ int bessx_op_xtv_multi(const double *x, int n, int p, int ld, const double *v, c
   if (int rc = need_device()) return rc;
   if (!x || !v || !out || n < 1 || p < 1 || ld < n || nc < 1 || nc > XTV_MC_MAX || (v2 && !out2))
     return fail(BESSX_ERR_ARG, "op_xtv_multi: bad arguments");
-  Scratch sc;
+  Owner sc;
   const int U = n >= 4096 ? 8 : (n >= 2048 ? 4 : (n >= 1024 ? 2 : 1));
   double *dX, *dout;
   long ldd;
@@ -329,7 +329,7 @@ int bessx_op_topk(const double *score, int len, int k, int *out_idx) {
   if (!score || !out_idx || len < 1 || k < 0 || k > len) return fail(BESSX_ERR_ARG, "op_topk: bad arguments");
   if (k == 0) return BESSX_OK;
   if (!topk_supported(len, k)) return fail(BESSX_ERR_UNSUPPORTED, "op_topk: len / k combination needs a third level");
-  Scratch sc;
+  Owner sc;
   double *ds;
   int *dout, *dcand;
   HIPX(sc.alloc(&ds, (size_t)len));
@@ -349,7 +349,7 @@ int bessx_op_topk_bench(int len, int k, int variant, int repeats, double *avg_us
   if (int rc = need_device()) return rc;
   if (len < 1 || k < 1 || k > len || repeats < 1 || !avg_us) return fail(BESSX_ERR_ARG, "op_topk_bench: bad arguments");
   if (!topk_supported(len, k)) return fail(BESSX_ERR_UNSUPPORTED, "op_topk_bench: len / k combination needs a third level");
-  Scratch sc;
+  Owner sc;
   double *ds;
   int *dout, *dcand;
   HIPX(sc.alloc(&ds, (size_t)len));
@@ -365,8 +365,8 @@ int bessx_op_topk_bench(int len, int k, int variant, int repeats, double *avg_us
   HIPX(hipMemcpy(ds, h.data(), (size_t)len * sizeof(double), hipMemcpyHostToDevice));
   topk_set_variant(variant);
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   hipError_t e = launch_topk(ds, len, k, dout, dcand, nullptr, 0, nullptr);
   if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
   for (int i = 0; i < repeats && e == hipSuccess; i++) e = launch_topk(ds, len, k, dout, dcand, nullptr, 0, nullptr);
@@ -375,8 +375,6 @@ int bessx_op_topk_bench(int len, int k, int variant, int repeats, double *avg_us
   topk_set_variant(1);
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   HIPX(e);
   *avg_us = 1e3 * (double)ms / repeats;
   return BESSX_OK;
@@ -387,7 +385,7 @@ int bessx_op_gram(const double *x, int n, int p, int ld, const int *cols, int m,
   if (!x || !cols || !out || n < 1 || p < 1 || ld < n || m < 1 || m > T0_CAP) return fail(BESSX_ERR_ARG, "op_gram: bad arguments");
   for (int i = 0; i < m; i++)
     if (cols[i] < 0 || cols[i] >= p) return fail(BESSX_ERR_ARG, "op_gram: column index out of range");
-  Scratch sc;
+  Owner sc;
   const int U = 1;
   HIPX(gram_lds_prepare());
   double *dX, *dw = nullptr, *daux, *gpart, *Gt;
@@ -437,7 +435,7 @@ int bessx_op_gram(const double *x, int n, int p, int ld, const int *cols, int m,
 int bessx_op_chol_solve(const double *a, int m, const double *b, double *sol) {
   if (int rc = need_device()) return rc;
   if (!a || !b || !sol || m < 1 || m > T0_CAP) return fail(BESSX_ERR_ARG, "op_chol_solve: need 1 <= m <= 2046");
-  Scratch sc;
+  Owner sc;
   const int mt = (m + 1 + 15) / 16, ntiles = mt * (mt + 1) / 2;
   std::vector<double> ht((size_t)ntiles * 256, 0.0);
   for (int I = 0; I < mt; I++)
@@ -481,7 +479,7 @@ int bessx_op_chol_solve(const double *a, int m, const double *b, double *sol) {
 int bessx_op_chol_bench(int m, int repeats, double *avg_us) {
   if (int rc = need_device()) return rc;
   if (m < 1 || m > T0_FAST || repeats < 1 || !avg_us) return fail(BESSX_ERR_ARG, "op_chol_bench: need 1 <= m <= 254");
-  Scratch sc;
+  Owner sc;
   const int mt = (m + 1 + 15) / 16, ntiles = mt * (mt + 1) / 2;
   // a well conditioned matrix: 4 I + small symmetric off-diagonal entries
   std::vector<double> ht((size_t)ntiles * 256, 0.0);
@@ -505,8 +503,8 @@ int bessx_op_chol_bench(int m, int repeats, double *avg_us) {
   HIPX(hipMemcpy(Gt, ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(launch_fill(drhs, m, 1.0, nullptr));
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   hipError_t e = launch_chol(Gt, m, mt, 0.0, 0, drhs, nullptr, dsol, dinfo, nullptr, 0, 0, nullptr);
   if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
   for (int i = 0; i < repeats && e == hipSuccess; i++)
@@ -515,8 +513,6 @@ int bessx_op_chol_bench(int m, int repeats, double *avg_us) {
   if (e == hipSuccess) e = hipEventSynchronize(e1);
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   HIPX(e);
   *avg_us = 1e3 * (double)ms / repeats;
   return BESSX_OK;
@@ -526,7 +522,7 @@ int bessx_op_normalize(double *x, int n, int p, double *y, const double *weight,
                        int add_weight, double *x_mean, double *x_norm, double *y_mean) {
   if (int rc = need_device()) return rc;
   if (!x || !y || !weight || n < 1 || p < 1) return fail(BESSX_ERR_ARG, "op_normalize: bad arguments");
-  Scratch sc;
+  Owner sc;
   double *dX, *dy, *dw, *dm, *dn, *dym;
   long ldd;
   if (int rc = upload_padded(sc, x, n, p, n, 1, &dX, &ldd)) return rc;
@@ -550,7 +546,7 @@ int bessx_op_normalize(double *x, int n, int p, double *y, const double *weight,
 int bessx_op_xtv_bench(int n, int p, int variant, int repeats, double *gbps, double *avg_ms) {
   if (int rc = need_device()) return rc;
   if (n < 1 || p < 1 || repeats < 1 || !gbps) return fail(BESSX_ERR_ARG, "op_xtv_bench: bad arguments");
-  Scratch sc;
+  Owner sc;
   const long ld = ((long)n + 1023) / 1024 * 1024;  // valid for every variant (multiple of 128*U)
   double *dX, *dv, *part;
   HIPX(sc.alloc(&dX, (size_t)ld * p));
@@ -559,8 +555,8 @@ int bessx_op_xtv_bench(int n, int p, int variant, int repeats, double *gbps, dou
   HIPX(launch_fill(dX, ld * (long)p, 1.0, nullptr));
   HIPX(launch_fill(dv, ld, 0.5, nullptr));
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   HIPX(launch_xtv_variant(variant, dX, ld, p, dv, part, nullptr));
   HIPX(hipEventRecord(e0, nullptr));
   for (int i = 0; i < repeats; i++) HIPX(launch_xtv_variant(variant, dX, ld, p, dv, part, nullptr));
@@ -568,8 +564,6 @@ int bessx_op_xtv_bench(int n, int p, int variant, int repeats, double *gbps, dou
   HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPX(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *gbps = 8.0 * (double)n * (double)p * repeats / ((double)ms * 1e-3) / 1e9;
   if (avg_ms) *avg_ms = ms / repeats;
   return BESSX_OK;
@@ -578,7 +572,7 @@ int bessx_op_xtv_bench(int n, int p, int variant, int repeats, double *gbps, dou
 int bessx_op_xtv_multi_bench(int n, int p, int nc, int two, int repeats, double *gbps, double *avg_ms) {
   if (int rc = need_device()) return rc;
   if (n < 1 || p < 1 || repeats < 1 || !gbps || nc < 1 || nc > XTV_MC_MAX) return fail(BESSX_ERR_ARG, "op_xtv_multi_bench: bad arguments");
-  Scratch sc;
+  Owner sc;
   const long ld = ((long)n + 1023) / 1024 * 1024;
   double *dX, *dv, *part;
   HIPX(sc.alloc(&dX, (size_t)ld * p));
@@ -595,8 +589,8 @@ int bessx_op_xtv_multi_bench(int n, int p, int nc, int two, int repeats, double 
     a.part2[c] = part + (size_t)(2 * c + 1) * (ld / 1024) * p;
   }
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   HIPX(launch_xtv_mc(dX, ld, p, 8, a, two != 0, nullptr));
   HIPX(hipEventRecord(e0, nullptr));
   for (int i = 0; i < repeats; i++) HIPX(launch_xtv_mc(dX, ld, p, 8, a, two != 0, nullptr));
@@ -604,8 +598,6 @@ int bessx_op_xtv_multi_bench(int n, int p, int nc, int two, int repeats, double 
   HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPX(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *gbps = 8.0 * (double)n * (double)p * repeats / ((double)ms * 1e-3) / 1e9;
   if (avg_ms) *avg_ms = ms / repeats;
   return BESSX_OK;
@@ -614,7 +606,7 @@ int bessx_op_xtv_multi_bench(int n, int p, int nc, int two, int repeats, double 
 int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbps, double *avg_ms) {
   if (int rc = need_device()) return rc;
   if (n < 1 || p < 1 || repeats < 1 || !gbps) return fail(BESSX_ERR_ARG, "op_cox_score_bench: bad arguments");
-  Scratch sc;
+  Owner sc;
   const long ld = ((long)n + 1023) / 1024 * 1024;
   const int nrb = (int)(ld / 1024);
   double *dX, *vec, *out;
@@ -624,8 +616,8 @@ int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbp
   HIPX(launch_fill(dX, ld * (long)p, 1.0, nullptr));
   HIPX(launch_fill(vec, ld * 4, 0.5, nullptr));
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   // variant 1 (what the solver runs): consecutive waves take consecutive column groups of one row block; 0 (round 3):
   // the row blocks of one column group
   // variant 10 + nc: the multi-chain kernel (k_cox_score1p_mc) with nc chains' vector sets per launch
@@ -652,8 +644,6 @@ int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbp
     HIPX(hipEventSynchronize(e1));
     float ms = 0.f;
     HIPX(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *gbps = 8.0 * (double)n * (double)p * repeats / ((double)ms * 1e-3) / 1e9;
     if (avg_ms) *avg_ms = ms / repeats;
     return BESSX_OK;
@@ -672,8 +662,6 @@ int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbp
   HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPX(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *gbps = 8.0 * (double)n * (double)p * repeats / ((double)ms * 1e-3) / 1e9;
   if (avg_ms) *avg_ms = ms / repeats;
   cox_score_set_variant(1);
@@ -683,15 +671,15 @@ int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbp
 int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps) {
   if (int rc = need_device()) return rc;
   if (bytes < (1 << 20) || repeats < 1 || !gbps) return fail(BESSX_ERR_ARG, "op_stream_copy: bad arguments");
-  Scratch sc;
+  Owner sc;
   double *a, *b;
   size_t n = (size_t)bytes / 16 * 2;
   HIPX(sc.alloc(&a, n));
   HIPX(sc.alloc(&b, n));
   HIPX(hipMemset(a, 1, n * sizeof(double)));
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   HIPX(launch_copy(a, b, (long)n, nullptr));
   HIPX(hipEventRecord(e0, nullptr));
   for (int i = 0; i < repeats; i++) HIPX(launch_copy(a, b, (long)n, nullptr));
@@ -699,15 +687,13 @@ int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps) {
   HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPX(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *gbps = 2.0 * (double)n * 8.0 * repeats / ((double)ms * 1e-3) / 1e9;
   return BESSX_OK;
 }
 
 // the ingest kernel alone on a caller's device matrix (tests/test_device_input_gpu.py)
 static int op_ingest_prepare(const void *x, int dtype, long long rs, long long cs, const int *row_order, int n, int p,
-                             long long ld, Scratch &sc, double **dst, unsigned **flag, int **order_d) {
+                             long long ld, Owner &sc, double **dst, unsigned **flag, int **order_d) {
   if (int rc = need_device()) return rc;
   if (ld < n || ld % 128 != 0) return fail(BESSX_ERR_ARG, "op_ingest: ld must be a multiple of 128, at least n");
   int dev = -1;
@@ -728,7 +714,7 @@ static int op_ingest_prepare(const void *x, int dtype, long long rs, long long c
 int bessx_op_ingest(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order, int n,
                     int p, long long ld, void *stream, double *out, int *nan_flag) {
   if (!out || !nan_flag) return fail(BESSX_ERR_ARG, "op_ingest: null argument");
-  Scratch sc;
+  Owner sc;
   double *dst = nullptr;
   unsigned *flag = nullptr;
   int *od = nullptr;
@@ -753,7 +739,7 @@ int bessx_op_ingest(const void *x, int dtype, long long row_stride, long long co
 int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order,
                           int n, int p, long long ld, int repeats, double *avg_ms, double *gbps) {
   if (repeats < 1 || !avg_ms || !gbps) return fail(BESSX_ERR_ARG, "op_ingest_bench: bad arguments");
-  Scratch sc;
+  Owner sc;
   double *dst = nullptr;
   unsigned *flag = nullptr;
   int *od = nullptr;
@@ -761,8 +747,8 @@ int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long l
   HIPX(hipMemset(flag, 0, sizeof(unsigned)));
   HIPX(hipDeviceSynchronize());
   hipEvent_t e0, e1;
-  HIPX(hipEventCreate(&e0));
-  HIPX(hipEventCreate(&e1));
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
   const int f32 = dtype == BESSX_F32;
   HIPX(launch_ingest(x, f32, row_stride, col_stride, od, n, p, dst, ld, flag, nullptr));
   HIPX(hipEventRecord(e0, nullptr));
@@ -771,8 +757,6 @@ int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long l
   HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPX(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   const double bytes = (double)n * (double)p * (f32 ? 4.0 : 8.0) + (double)ld * (double)p * 8.0;
   *avg_ms = ms / repeats;
   *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;

@@ -234,9 +234,8 @@ int cgb_reserve(bessx_session *s) {
   bessx_session *owner = s->parent ? s->parent : s;
   if (!owner->cgb_work) {
     const int kcap = std::min(owner->cap, CGB_MAX_K);
-    if (dmalloc(&owner->cgb_work, cgb_work_doubles(kcap)) != hipSuccess) {
+    if (owner->own.alloc(&owner->cgb_work, cgb_work_doubles(kcap)) != hipSuccess) {
       (void)hipGetLastError();
-      owner->cgb_work = nullptr;
       return 1;  // (no memory: the blocked Cholesky does it)
     }
     owner->cgb_cap = kcap;
@@ -484,9 +483,8 @@ int cov_unpark(bessx_session *s, const FitCtrl *hc, int T0, double lambda, int r
   // kernels): the list first, on this chain's stream
   hipStream_t own_st = s->st;
   hipStream_t fill_st = staged ? s->kch_owner->kch_fill_st : nullptr;
-  if (fill_st && !s->kch_ev && hipEventCreateWithFlags(&s->kch_ev, hipEventDisableTiming) != hipSuccess) {
+  if (fill_st && !s->kch_ev && s->own.event(&s->kch_ev, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
-    s->kch_ev = nullptr;
     fill_st = nullptr;
   }
   if (fill_st) {
@@ -618,22 +616,10 @@ int cox_reserve(bessx_session *s, int T0) {
   size_t cols = std::min<size_t>((size_t)s->capA, std::max(need, 2 * s->cox_M_cols));
   CoxBufs &c = s->cox;
   HIPX(hipStreamSynchronize(s->st));
-  auto regrow = [&](double **ptr, size_t count) -> hipError_t {
-    for (auto &q : s->cox_allocs)
-      if (q == *ptr) {
-        (void)hipFree(*ptr);
-        *ptr = nullptr;
-        hipError_t e = dmalloc(ptr, count);
-        q = *ptr;
-        if (e == hipSuccess) e = hipMemset(*ptr, 0, count * sizeof(double));
-        return e;
-      }
-    return hipErrorInvalidValue;
-  };
   const size_t mt = cols / 16;
-  HIPX(regrow(&c.M, (size_t)s->ld * cols));
-  HIPX(regrow(&c.Gt2, mt * (mt + 1) / 2 * 256));
-  HIPX(regrow(&c.SCR, cox_scan_scratch_doubles(s->ld, (int)cols)));
+  HIPX(s->own.regrow(&c.M, (size_t)s->ld * cols, true));
+  HIPX(s->own.regrow(&c.Gt2, mt * (mt + 1) / 2 * 256, true));
+  HIPX(s->own.regrow(&c.SCR, cox_scan_scratch_doubles(s->ld, (int)cols), true));
   s->cox_M_cols = cols;
   return 0;
 }
@@ -806,9 +792,12 @@ static int group_eig_ensure(bessx_session *s, int rs, double lambda) {
     s->geig_valid.resize((size_t)rs + 1, 0);
   }
   if (!s->geig_v_rs[rs]) {
-    if (dmalloc(&s->geig_v_rs[rs], (size_t)s->goff_h[s->N]) != hipSuccess ||
-        dmalloc(&s->geig_l_rs[rs], (size_t)s->p) != hipSuccess) {
+    Owner &own = rowset_owner(s, rs);
+    if (own.alloc(&s->geig_v_rs[rs], (size_t)s->goff_h[s->N]) != hipSuccess ||
+        own.alloc(&s->geig_l_rs[rs], (size_t)s->p) != hipSuccess) {
       (void)hipGetLastError();
+      own.release_one(s->geig_v_rs[rs]);  // (not one without the other: the next fit asks again)
+      s->geig_v_rs[rs] = nullptr;
       return 1;  // (no memory: diagonalise at every iteration as before)
     }
   }

@@ -103,6 +103,143 @@ static constexpr int T0_FAST = 254;  // fast path: m + 1 <= 256 lives in the reg
 static constexpr int T0_CAP = 2046;   // default capacity of a session (bessx_problem.max_sparsity = 0): m + 2 <= 2048
 static constexpr int T0_HARD = 16382;  // largest capacity a session can be created with: m + 2 <= 16384
 
+// Device memory comes back with whatever it last held: on a fresh box mostly zeros, in a long-lived process the bytes of
+// earlier sessions.  BESSX_TEST_HOOKS=poison=1 fills every allocation with 0xFF bytes (a NaN for a double, -1 for an int),
+// so that a kernel that reads a buffer nobody wrote shows up in the tests instead of on somebody's machine.
+inline bool poison_allocations() {  // (read at every allocation: allocations are rare, and a test switches it per session)
+  const char *v = test_hook("poison");
+  return v && std::string(v) == "1";
+}
+
+// What the owners of the process have handed out and not taken back yet (bessx_session_counter 38 / 39), and how many
+// requests they were asked for.
+struct Ledger {
+  static inline std::atomic<long long> device_bytes{0}, pinned_bytes{0}, requests{0};
+};
+
+// BESSX_TEST_HOOKS=alloc_fail=N: the N-th request (device memory, pinned memory or event) that the owners of the process
+// receive after the hook was last read as a NEW value fails with hipErrorOutOfMemory WITHOUT calling the runtime -- a
+// host-side error return that walks the clean-up paths of session creation, set_cv and the chain contexts
+// (tests/test_ownership_gpu.py).  Unset, or 0: no request fails.
+inline bool alloc_request_fails() {
+  static std::mutex mu;
+  static long long fail_at = 0, since = 0;  // the hook's value as last read; Ledger::requests when it was first read so
+  const char *v = test_hook("alloc_fail");
+  const long long want = v ? std::atoll(v) : 0;
+  std::lock_guard<std::mutex> lk(mu);
+  const long long now = ++Ledger::requests;
+  if (want != fail_at) {
+    fail_at = want;
+    since = now - 1;
+  }
+  return fail_at > 0 && now - since == fail_at;
+}
+
+// The one owner of GPU-side resources: device memory, pinned host memory and events.  It keeps what it handed out and
+// gives all of it back in release() and in its destructor.  A COPY OF AN OWNER IS EMPTY: a fit context is a copy of its
+// parent session (new bessx_session(*ps)) that borrows every pointer of the parent and owns what it allocates itself.
+// Streams are not held here: ctx_stream_create / ctx_stream_destroy pool them per process.
+struct Owner {
+  enum Kind : char { DEVICE, PINNED, EVENT };
+  struct Item {
+    void *ptr;
+    size_t bytes;
+    Kind kind;
+  };
+  std::vector<Item> items;
+  Owner() = default;
+  Owner(const Owner &) {}
+  Owner &operator=(const Owner &) = delete;
+  ~Owner() { release(); }
+
+  // device memory: at least one element, the poison fill of the test hook
+  template <class T>
+  hipError_t alloc(T **out, size_t count) {
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    *out = nullptr;
+    if (alloc_request_fails()) return hipErrorOutOfMemory;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(out), bytes);
+    if (e != hipSuccess) {
+      *out = nullptr;
+      return e;
+    }
+    items.push_back({*out, bytes, DEVICE});
+    Ledger::device_bytes += (long long)bytes;
+    return poison_allocations() ? hipMemset(*out, 0xff, bytes) : hipSuccess;
+  }
+  template <class T>
+  hipError_t zeros(T **out, size_t count) {
+    hipError_t e = alloc(out, count);
+    return e == hipSuccess ? hipMemset(*out, 0, std::max<size_t>(count, 1) * sizeof(T)) : e;
+  }
+  template <class T>
+  hipError_t copy_of(T **out, size_t count, const T *src) {  // (src: device memory)
+    hipError_t e = alloc(out, count);
+    return e == hipSuccess ? hipMemcpy(*out, src, count * sizeof(T), hipMemcpyDeviceToDevice) : e;
+  }
+  template <class T>
+  hipError_t pinned(T **out, size_t count) {
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    *out = nullptr;
+    if (alloc_request_fails()) return hipErrorOutOfMemory;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(out), bytes);
+    if (e != hipSuccess) {
+      *out = nullptr;
+      return e;
+    }
+    items.push_back({*out, bytes, PINNED});
+    Ledger::pinned_bytes += (long long)bytes;
+    return hipSuccess;
+  }
+  hipError_t event(hipEvent_t *out, unsigned flags = hipEventDefault) {
+    *out = nullptr;
+    if (alloc_request_fails()) return hipErrorOutOfMemory;
+    hipError_t e = hipEventCreateWithFlags(out, flags);
+    if (e != hipSuccess) {
+      *out = nullptr;
+      return e;
+    }
+    items.push_back({*out, 0, EVENT});
+    return hipSuccess;
+  }
+  // a buffer that grows: the old one goes, a new one of `count` elements takes its place (contents are not kept)
+  template <class T>
+  hipError_t regrow(T **ptr, size_t count, bool zero = false) {
+    release_one(*ptr);
+    return zero ? zeros(ptr, count) : alloc(ptr, count);
+  }
+  void release_one(void *ptr) {
+    if (!ptr) return;
+    for (size_t i = items.size(); i-- > 0;)
+      if (items[i].ptr == ptr) {
+        give_back(items[i]);
+        items.erase(items.begin() + (long)i);
+        return;
+      }
+  }
+  void release() {
+    for (size_t i = items.size(); i-- > 0;) give_back(items[i]);
+    items.clear();
+  }
+
+ private:
+  static void give_back(const Item &it) {
+    hipError_t e = hipSuccess;
+    if (it.kind == DEVICE) {
+      e = hipFree(it.ptr);
+      Ledger::device_bytes -= (long long)it.bytes;
+    } else if (it.kind == PINNED) {
+      e = hipHostFree(it.ptr);
+      Ledger::pinned_bytes -= (long long)it.bytes;
+    } else {
+      e = hipEventDestroy(static_cast<hipEvent_t>(it.ptr));
+    }
+    if (e != hipSuccess && std::getenv("BESSX_DEBUG"))
+      std::fprintf(stderr, "[bessx] releasing %p (%zu bytes, kind %d): %s\n", it.ptr, it.bytes, (int)it.kind,
+                   hipGetErrorString(e));
+  }
+};
+
 }  // namespace bessx
 
 using namespace bessx;
@@ -121,6 +258,10 @@ struct bessx_session {
   int data_type = 1, is_normal = 1, model_type = 1, algorithm_type = 1, max_iter = 20, warm_start = 1;
   int device = 0;
   hipStream_t st = nullptr;
+  // Every device buffer, pinned buffer and event below belongs to the owner of the session (or context) that allocated
+  // it; a context's copy of a pointer it did not allocate is borrowed.  cv_own: what bessx_session_set_cv creates (row
+  // sets 1..K, the fold-major copy, the union fills' control block and events), released when the folds change.
+  Owner own, cv_own;
   // device data
   double *X = nullptr, *y = nullptr, *w = nullptr, *aux = nullptr;
   double *x_mean = nullptr, *x_norm = nullptr, *y_mean_d = nullptr;
@@ -152,7 +293,6 @@ struct bessx_session {
   int cox_state_rs = -1;
   int dev_state_rs = -1;                // row set of the fit whose final coefficients sit in A_cur/b_cur/beta_dense
   CoxBufs cox = {};                     // Cox work space (model_type 4 only)
-  std::vector<void *> cox_allocs;
   int *idcols = nullptr;
   struct RsCache {
     bool valid = false;  // part_rs / r_rs belong to exactly (beta, coef0) below
@@ -273,7 +413,6 @@ struct bessx_session {
   // (stream, control block, scores, solve work space) that READS the one cache of the all-rows row set; a chain that
   // needs a column the cache lacks fills it while every other chain stands still (KChains: safe points between
   // candidates); the chunks are stitched into the single chain exactly as bess_amd.dist.StitchedKPath does it.
-  std::vector<void *> ctx_allocs;       // chain context: device buffers it owns beyond a fold context's
   bessx::KChains *kch = nullptr;        // parent: contexts, host threads, the fill rendezvous (created at first use)
   bessx_session *kch_owner = nullptr;   // chain context: the session whose cache it reads
   int kpath_chains = 0;                 // 0 = automatic, 1 = one chain (off), C >= 2 = that many chunk chains
@@ -398,35 +537,8 @@ static constexpr int COV_R = 32;        // columns per panel group (matches the 
 static constexpr int COV_SLOT_GROUPS = 2;  // groups an ordinary PDAS slot launches
 static constexpr int COV_CS = 512;         // side of the slot-indexed Gram of the cached columns (2 MiB)
 
-// Device memory comes back with whatever it last held: on a fresh box mostly zeros, in a long-lived process the bytes of
-// earlier sessions.  BESSX_TEST_HOOKS=poison=1 fills every allocation with 0xFF bytes (a NaN for a double, -1 for an int),
-// so that a kernel that reads a buffer nobody wrote shows up in the tests instead of on somebody's machine.
-inline bool poison_allocations() {  // (read at every allocation: allocations are rare, and a test switches it per session)
-  const char *v = test_hook("poison");
-  return v && std::string(v) == "1";
-}
-
-template <class T>
-hipError_t dmalloc(T **ptr, size_t count) {
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(ptr), bytes);
-  if (e == hipSuccess && poison_allocations()) e = hipMemset(*ptr, 0xff, bytes);
-  return e;
-}
-
-struct Scratch {
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *q : ptrs) (void)hipFree(q);
-  }
-  template <class T>
-  hipError_t alloc(T **out, size_t count) {
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(out), std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess && poison_allocations()) e = hipMemset(*out, 0xff, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(*out);
-    return e;
-  }
-};
+// the owner of what belongs to row set rs (0: all rows; 1..K: the CV folds)
+inline Owner &rowset_owner(bessx_session *s, int rs) { return rs == 0 ? s->own : s->cv_own; }
 
 inline int caller_col(const bessx_session *s, int j) { return s->screen_map.empty() ? j : s->screen_map[j]; }
 
@@ -441,7 +553,7 @@ struct Candidate {  // one (s, lambda) of a path: the full-data fit's model (nor
 struct PgsArgs;
 
 // ---- bessx_session.cpp / bessx_fit.cpp / bessx_cv.cpp / bessx_paths.cpp: what they call across files
-void fold_ctx_free(bessx_session *c);
+void ctx_free(bessx_session *c);  // a fold context or a chunk chain's
 void drop_fold_contexts(bessx_session *s);
 void session_free(bessx_session *s);
 size_t part_elems(const bessx_session *s);
@@ -532,7 +644,6 @@ int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm = false)
 hipError_t cox_alloc(bessx_session *s);                        // bessx_session.cpp
 // (own_queue = false: an ordinary stream -- the contexts of a merged run of many responses queue nothing on theirs)
 int chain_ctx_create(bessx_session *ps, bessx_session **out, bool own_queue = true);  // bessx_session.cpp
-void chain_ctx_free(bessx_session *c);
 int prefill_begin(bessx_session *s, const int *cols, int ncols, int append);  // bessx_paths.cpp
 int glm_geometry(bessx_session *s, int T0, int *mt, int *mp, int *ntask, int *ntiles, int *rps, int *nslab);
 int enqueue_glm_head(bessx_session *s, int slot, int T0, double lambda, int rs, bool skip_k1,
@@ -584,8 +695,8 @@ int run_path(bessx_session *s, bool gs, const int *seq, int ns, const double *la
                     int s_max, int ic_type, int is_cv, bessx_path_result *res, const PgsArgs *pgs = nullptr,
                     bessx_path_chain *chain = nullptr);
 int need_device();
-int upload_padded(Scratch &sc, const double *x, int n, int p, int ld_in, int U, double **dX, long *ld_out);
-int upload_vec_padded(Scratch &sc, const double *v, int n, long ld, double **dv);
+int upload_padded(Owner &sc, const double *x, int n, int p, int ld_in, int U, double **dX, long *ld_out);
+int upload_vec_padded(Owner &sc, const double *v, int n, long ld, double **dv);
 
 }  // namespace bessx
 

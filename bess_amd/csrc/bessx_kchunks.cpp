@@ -55,6 +55,7 @@ struct SharedPass {
   int *ran = nullptr;  // device, RAN_CAP ints
   static constexpr int RAN_CAP = 8192;
   int launches = 0;
+  Owner own;  // the events and `ran`
 };
 
 struct KChains {
@@ -94,38 +95,8 @@ struct KChains {
   const int **mc_ulist = nullptr;
   int *mc_ulen = nullptr, *mc_rlist = nullptr;
   unsigned char *mc_stage_h = nullptr;
+  Owner chains_own, own;  // what is sized by the number of chains (released when that grows); the rest, kch_slot_w included
 };
-
-static void mc_free_chains(KChains *k) {  // what is sized by the number of chains
-  if (k->mc_chains) (void)hipFree(k->mc_chains);
-  if (k->mc_states) (void)hipFree(k->mc_states);
-  if (k->mc_status_h) (void)hipHostFree(k->mc_status_h);
-  if (k->mc_ulist) (void)hipFree(k->mc_ulist);
-  if (k->mc_ulen) (void)hipFree(k->mc_ulen);
-  if (k->mc_rlist) (void)hipFree(k->mc_rlist);
-  if (k->mc_stage_h) (void)hipHostFree(k->mc_stage_h);
-  k->mc_chains = nullptr;
-  k->mc_states = nullptr;
-  k->mc_status_h = nullptr;
-  k->mc_ulist = nullptr;
-  k->mc_ulen = k->mc_rlist = nullptr;
-  k->mc_stage_h = nullptr;
-  k->mc_cap_chains = 0;
-}
-
-static void mc_free(KChains *k) {
-  mc_free_chains(k);
-  if (k->mc_seq) (void)hipFree(k->mc_seq);
-  if (k->mc_rec_i) (void)hipFree(k->mc_rec_i);
-  if (k->mc_rec_A) (void)hipFree(k->mc_rec_A);
-  if (k->mc_rec_d) (void)hipFree(k->mc_rec_d);
-  if (k->mc_rec_b) (void)hipFree(k->mc_rec_b);
-  if (k->mc_flag) (void)hipHostFree(k->mc_flag);
-  k->mc_seq = k->mc_rec_i = k->mc_rec_A = nullptr;
-  k->mc_rec_d = k->mc_rec_b = nullptr;
-  k->mc_flag = nullptr;
-  k->mc_cap_cand = k->mc_cap_cells = k->mc_cap_seq = 0;
-}
 
 // between two candidates of a chunk chain: if another chain waits to fill, drain this chain's stream and stand still
 void kchains_safe_point(bessx_session *c) {
@@ -176,14 +147,7 @@ static void kchains_round(KChains *k, int chains, bool staged = false) { k->rdv.
 // ---- shared passes -------------------------------------------------------------------------------------------------
 static void sp_free(SharedPass &sp) {
   if (sp.st) ctx_stream_destroy(sp.st);
-  for (auto &grp : sp.ev_in)
-    for (auto &e : grp)
-      if (e) (void)hipEventDestroy(e);
-  for (auto &grp : sp.ev_out)
-    for (auto &e : grp)
-      if (e) (void)hipEventDestroy(e);
-  for (auto &e : sp.tev) (void)hipEventDestroy(e);
-  if (sp.ran) (void)hipFree(sp.ran);
+  sp.own.release();
   sp.st = nullptr;
   sp.ran = nullptr;
   sp.tev.clear();
@@ -207,10 +171,10 @@ static bool sp_prepare(bessx_session *s, SharedPass &sp) {
   }
   bool ok = true;
   for (auto &grp : sp.ev_in)
-    for (auto &e : grp) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    for (auto &e : grp) ok = ok && sp.own.event(&e, hipEventDisableTiming) == hipSuccess;
   for (auto &grp : sp.ev_out)
-    for (auto &e : grp) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void **>(&sp.ran), SharedPass::RAN_CAP * sizeof(int)) == hipSuccess;
+    for (auto &e : grp) ok = ok && sp.own.event(&e, hipEventDisableTiming) == hipSuccess;
+  ok = ok && sp.own.alloc(&sp.ran, SharedPass::RAN_CAP) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     sp_free(sp);
@@ -229,7 +193,7 @@ static void sp_launch(bessx_session *o, SharedPass &sp, int grp, int n, unsigned
   if (sp.timing && sp.launches < SharedPass::RAN_CAP) {
     while (sp.tev.size() < sp.tused + 2) {
       hipEvent_t ev = nullptr;
-      if (hipEventCreate(&ev) != hipSuccess) break;
+      if (sp.own.event(&ev) != hipSuccess) break;
       sp.tev.push_back(ev);
     }
     if (sp.tev.size() >= sp.tused + 2) {
@@ -369,16 +333,17 @@ void kchains_free(bessx_session *s) {
   if (!s || !s->kch) return;
   KChains *k = s->kch;
   if (k->pool_started) k->pool.stop();
-  mc_free(k);
-  sp_free(k->sp);
-  if (s->kch_slot_w) (void)hipFree(s->kch_slot_w);
-  s->kch_slot_w = nullptr;
   if (s->kch_fill_st) ctx_stream_destroy(s->kch_fill_st);
   s->kch_fill_st = nullptr;
-  for (bessx_session *c : k->ctx) chain_ctx_free(c);
-  for (bessx_session *c : k->mc_ctx) chain_ctx_free(c);
-  if (!k->pool.broken) delete k;  // (a broken pool's threads may still touch it: leaked on purpose)
+  for (bessx_session *c : k->ctx) ctx_free(c);
+  for (bessx_session *c : k->mc_ctx) ctx_free(c);
+  // (a broken pool's threads may still touch it and what its owners hold: leaked on purpose)
+  if (!k->pool.broken) {
+    sp_free(k->sp);
+    delete k;
+  }
   s->kch = nullptr;
+  s->kch_slot_w = nullptr;
 }
 
 // how many chunk chains for this path (1 = the single chain)
@@ -657,48 +622,43 @@ int mc_engine(bessx_session *s, const int *seq, int ns, std::vector<McJob> &jobs
   hipStream_t st = s->st;
   // ---- buffers
   if (C > k->mc_cap_chains) {
-    mc_free_chains(k);
+    k->chains_own.release();
+    k->mc_cap_chains = 0;
     const int cap = std::max(C, 8);
-    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_chains), (size_t)cap * sizeof(McChain)));
-    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_states), (size_t)cap * sizeof(McState)));
-    HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_status_h), (size_t)cap * sizeof(McHostStatus)));
-    HIPX(hipMalloc(reinterpret_cast<void **>(&k->mc_ulist), (size_t)cap * sizeof(const int *)));
-    HIPX(dmalloc(&k->mc_ulen, (size_t)cap));
-    HIPX(dmalloc(&k->mc_rlist, (size_t)cap));
-    HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_stage_h), (size_t)cap * (sizeof(const int *) + 2 * sizeof(int))));
+    HIPX(k->chains_own.alloc(&k->mc_chains, (size_t)cap));
+    HIPX(k->chains_own.alloc(&k->mc_states, (size_t)cap));
+    HIPX(k->chains_own.pinned(&k->mc_status_h, (size_t)cap * sizeof(McHostStatus)));
+    HIPX(k->chains_own.alloc(&k->mc_ulist, (size_t)cap));
+    HIPX(k->chains_own.alloc(&k->mc_ulen, (size_t)cap));
+    HIPX(k->chains_own.alloc(&k->mc_rlist, (size_t)cap));
+    HIPX(k->chains_own.pinned(&k->mc_stage_h, (size_t)cap * (sizeof(const int *) + 2 * sizeof(int))));
     if (!k->mc_flag) {
-      HIPX(hipHostMalloc(reinterpret_cast<void **>(&k->mc_flag), 128));
+      HIPX(k->own.pinned(&k->mc_flag, 128 / sizeof(unsigned long long)));
       k->mc_flag[0] = 0ull;
       k->mc_seq_no = 0;
     }
     k->mc_cap_chains = cap;
   }
   if ((size_t)ns > k->mc_cap_seq) {
-    if (k->mc_seq) (void)hipFree(k->mc_seq);
-    k->mc_seq = nullptr;
     k->mc_cap_seq = 0;
-    HIPX(dmalloc(&k->mc_seq, (size_t)ns));
+    HIPX(k->own.regrow(&k->mc_seq, (size_t)ns));
     k->mc_cap_seq = (size_t)ns;
   }
   if ((size_t)nrec > k->mc_cap_cand || (size_t)nrec * width > k->mc_cap_cells) {
-    if (k->mc_rec_i) (void)hipFree(k->mc_rec_i);
-    if (k->mc_rec_d) (void)hipFree(k->mc_rec_d);
-    if (k->mc_rec_A) (void)hipFree(k->mc_rec_A);
-    if (k->mc_rec_b) (void)hipFree(k->mc_rec_b);
+    k->mc_cap_cand = k->mc_cap_cells = 0;
+    for (void *q : {(void *)k->mc_rec_i, (void *)k->mc_rec_d, (void *)k->mc_rec_A, (void *)k->mc_rec_b}) k->own.release_one(q);
     k->mc_rec_i = k->mc_rec_A = nullptr;
     k->mc_rec_d = k->mc_rec_b = nullptr;
-    k->mc_cap_cand = k->mc_cap_cells = 0;
-    HIPX(dmalloc(&k->mc_rec_i, (size_t)nrec * MC_REC_I));
-    HIPX(dmalloc(&k->mc_rec_d, (size_t)nrec * MC_REC_D));
-    HIPX(dmalloc(&k->mc_rec_A, (size_t)nrec * width));
-    HIPX(dmalloc(&k->mc_rec_b, (size_t)nrec * width));
+    HIPX(k->own.alloc(&k->mc_rec_i, (size_t)nrec * MC_REC_I));
+    HIPX(k->own.alloc(&k->mc_rec_d, (size_t)nrec * MC_REC_D));
+    HIPX(k->own.alloc(&k->mc_rec_A, (size_t)nrec * width));
+    HIPX(k->own.alloc(&k->mc_rec_b, (size_t)nrec * width));
     k->mc_cap_cand = (size_t)nrec;
     k->mc_cap_cells = (size_t)nrec * width;
   }
   if (!s->fill_ctrl) {
-    HIPX(hipMalloc(reinterpret_cast<void **>(&s->fill_ctrl), sizeof(FitCtrl)));
-    HIPX(hipMemset(s->fill_ctrl, 0, sizeof(FitCtrl)));
-    HIPX(hipHostMalloc(reinterpret_cast<void **>(&s->fill_ctrl_h), sizeof(FitCtrl)));
+    HIPX(s->cv_own.zeros(&s->fill_ctrl, 1));
+    HIPX(s->cv_own.pinned(&s->fill_ctrl_h, 1));
   }
   HIPX(hipMemcpyAsync(k->mc_seq, seq, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
   HIPX(hipMemsetAsync(k->mc_rec_i, 0, (size_t)nrec * MC_REC_I * sizeof(int), st));
@@ -1092,9 +1052,8 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     pipeline = ep && std::atoi(ep) != 0 && (int)k->ctx.size() > C && (int)k->pool.th.size() >= C && link == nullptr;
     if (pipeline) staged = true;
   }
-  if (staged && !s->kch_slot_w && dmalloc(&s->kch_slot_w, (size_t)s->p) != hipSuccess) {
+  if (staged && !s->kch_slot_w && k->own.alloc(&s->kch_slot_w, (size_t)s->p) != hipSuccess) {
     (void)hipGetLastError();
-    s->kch_slot_w = nullptr;
     staged = pipeline = false;
   }
   if (staged && !s->kch_fill_st && !s->kch_fill_tried) {

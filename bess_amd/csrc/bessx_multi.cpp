@@ -262,20 +262,16 @@ int bessx_session_set_responses(bessx_session *s, const double *Y, int R, int co
     }
   HIPX(hipSetDevice(s->device));
   if (int rc = settle_device_chain(s)) return rc;
-  auto F = [](double *&q) {
-    if (q) (void)hipFree(q);
-    q = nullptr;
-  };
   if (R != s->resp_R) {
-    F(s->resp_y);
     s->resp_R = 0;
-    HIPX(dmalloc(&s->resp_y, (size_t)ld * R));
+    HIPX(s->own.regrow(&s->resp_y, (size_t)ld * R));
   }
-  if (!s->resp_xty) HIPX(dmalloc(&s->resp_xty, (size_t)MULTI_BATCH * s->p));
-  if (!s->resp_part) HIPX(dmalloc(&s->resp_part, (size_t)XTV_MC_MAX * part_elems(s)));
-  if (!s->own_xty) HIPX(dmalloc(&s->own_xty, (size_t)s->p));
+  if (!s->resp_xty) HIPX(s->own.alloc(&s->resp_xty, (size_t)MULTI_BATCH * s->p));
+  if (!s->resp_part) HIPX(s->own.alloc(&s->resp_part, (size_t)XTV_MC_MAX * part_elems(s)));
+  if (!s->own_xty) HIPX(s->own.alloc(&s->own_xty, (size_t)s->p));
+  Owner tmp;
   double *stats = nullptr;
-  HIPX(dmalloc(&stats, (size_t)2 * R));
+  HIPX(tmp.alloc(&stats, (size_t)2 * R));
   std::vector<double> st2((size_t)2 * R);
   std::vector<double> w((size_t)n);
   hipError_t e = hipMemcpyAsync(s->resp_y, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, s->st);
@@ -286,7 +282,6 @@ int bessx_session_set_responses(bessx_session *s, const double *Y, int R, int co
   if (e == hipSuccess) e = hipMemcpyAsync(st2.data(), stats, st2.size() * sizeof(double), hipMemcpyDeviceToHost, s->st);
   if (e == hipSuccess) e = hipMemcpyAsync(w.data(), s->w, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->st);
   if (e == hipSuccess) e = hipStreamSynchronize(s->st);
-  (void)hipFree(stats);
   if (e != hipSuccess) return fail(BESSX_ERR_HIP, std::string("set_responses: ") + hipGetErrorString(e));
   s->resp_mean.assign(st2.begin(), st2.begin() + R);
   s->resp_yy.assign(st2.begin() + R, st2.end());
@@ -319,7 +314,7 @@ int bessx_session_set_responses_device(bessx_session *s, const void *Y, int dtyp
   // Y is n x R values: the ingest kernel makes them fp64 column-major, the host copy goes through the host entry
   const int n = s->n;
   const long long ld = ((long long)n + 127) / 128 * 128;
-  Scratch sc;
+  Owner sc;
   double *d = nullptr;
   unsigned *flag = nullptr;
   HIPX(sc.alloc(&d, (size_t)ld * R));
@@ -363,11 +358,11 @@ int bessx_session_sequential_path_multi(bessx_session *s, const int *sequence, i
       // the fill list of a union fill: the missing columns of up to 256 supports (every column at most once) and the
       // speculative ones, padded to a group
       int *wide = nullptr;
-      if (dmalloc(&wide, (size_t)(s->p + 31) / 32 * 32 + 4 * COV_R) != hipSuccess) {
+      if (s->own.alloc(&wide, (size_t)(s->p + 31) / 32 * 32 + 4 * COV_R) != hipSuccess) {
         (void)hipGetLastError();
         rc = fail(BESSX_ERR_HIP, "sequential_path_multi: fill list");
       } else {
-        (void)hipFree(s->cov_fcols);
+        s->own.release_one(s->cov_fcols);
         s->cov_fcols = wide;
         s->fcols_wide = true;
       }

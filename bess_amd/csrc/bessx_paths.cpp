@@ -619,9 +619,8 @@ int run_path(bessx_session *s, bool gs, const int *seq, int ns, const double *la
     // pass runs; with the kernel timing on, two events bracket it and counter 19 reads them when asked)
     bool timed = s->timing;
     for (int i = 0; i < 2 && timed; i++)
-      if (!s->xtx_ev[i] && hipEventCreate(&s->xtx_ev[i]) != hipSuccess) {
+      if (!s->xtx_ev[i] && s->own.event(&s->xtx_ev[i]) != hipSuccess) {
         (void)hipGetLastError();
-        s->xtx_ev[i] = nullptr;
         timed = false;
       }
     if (timed) (void)hipEventRecord(s->xtx_ev[0], s->st);
@@ -853,9 +852,8 @@ static int prefill_ready(bessx_session *s) {
   if (s->cv_shared) return fail(BESSX_ERR_UNSUPPORTED, "cov_prefill: not offered on sessions with cross-validation folds");
   HIPX(hipSetDevice(s->device));
   if (!s->fill_ctrl) {
-    HIPX(hipMalloc(reinterpret_cast<void **>(&s->fill_ctrl), sizeof(FitCtrl)));
-    HIPX(hipMemset(s->fill_ctrl, 0, sizeof(FitCtrl)));
-    HIPX(hipHostMalloc(reinterpret_cast<void **>(&s->fill_ctrl_h), sizeof(FitCtrl)));
+    HIPX(s->cv_own.zeros(&s->fill_ctrl, 1));
+    HIPX(s->cv_own.pinned(&s->fill_ctrl_h, 1));
   }
   return 0;
 }

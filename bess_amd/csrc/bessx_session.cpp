@@ -9,18 +9,11 @@ thread_local int g_marginal_fit_variant = 0;
 
 
 
-// A fold context (bessx_session::fold_ctx) owns only what a fit writes; everything else is the parent's.
-void fold_ctx_free(bessx_session *c) {
+// A fold or chunk-chain context: its stream drains before its buffers go; everything it did not allocate is the parent's.
+void ctx_free(bessx_session *c) {
   if (!c) return;
   if (c->st) (void)hipStreamSynchronize(c->st);
-  void *dev[] = {c->resblk, c->bd, c->bd2, c->beta_dense, c->inA, c->cov_bmm, c->sol, c->A_new, c->cand, c->tie_buf,
-                 c->fb_work, c->hist, c->hist_beta, c->hist_coef0, c->Gt, c->init_idx_d, c->init_val_d, c->cov_fcols,
-                 c->cov_extras, c->rdiag, c->zbig};
-  for (void *q : dev)
-    if (q) (void)hipFree(q);
-  if (c->res_buf[0]) (void)hipHostFree(c->res_buf[0]);
-  if (c->pub_flag) (void)hipHostFree(c->pub_flag);
-  if (c->stage_h) (void)hipHostFree(c->stage_h);
+  c->own.release();
   if (c->st) ctx_stream_destroy(c->st);
   delete c;
 }
@@ -31,12 +24,12 @@ void drop_fold_contexts(bessx_session *s) {
     if (!s->fold_pool->broken) delete s->fold_pool;  // (a broken pool's threads may still touch it: leaked on purpose)
     s->fold_pool = nullptr;
   }
-  for (bessx_session *c : s->fold_ctx) fold_ctx_free(c);
+  for (bessx_session *c : s->fold_ctx) ctx_free(c);
   s->fold_ctx.clear();
-  if (s->fill_ctrl) (void)hipFree(s->fill_ctrl);
-  if (s->fill_ctrl_h) (void)hipHostFree(s->fill_ctrl_h);
-  if (s->ev_fill) (void)hipEventDestroy(s->ev_fill);
-  if (s->ev_ctx) (void)hipEventDestroy(s->ev_ctx);
+  s->cv_own.release_one(s->fill_ctrl);
+  s->cv_own.release_one(s->fill_ctrl_h);
+  s->cv_own.release_one(s->ev_fill);
+  s->cv_own.release_one(s->ev_ctx);
   s->fill_ctrl = s->fill_ctrl_h = nullptr;
   s->ev_fill = s->ev_ctx = nullptr;
   s->fill_groups_seen = 0;
@@ -62,107 +55,8 @@ void session_free(bessx_session *s) {
                  s->dbg_waits_ready, s->dbg_enq_s * 1e3);
   (void)hipSetDevice(s->device);
   if (s->st) (void)hipStreamSynchronize(s->st);
-  auto F = [](void *q) {
-    if (q) (void)hipFree(q);
-  };
-  F(s->X);
-  F(s->y);
-  F(s->w);
-  F(s->aux);
-  F(s->x_mean);
-  F(s->x_norm);
-  F(s->y_mean_d);
-  F(s->resp_y);
-  F(s->resp_xty);
-  F(s->resp_part);
-  F(s->own_xty);
-  F(s->always);
-  for (auto q : s->mask) F(q);
-  for (auto q : s->xtx) F(q);
-  for (auto q : s->xty) F(q);
-  for (auto q : s->part_rs) F(q);
-  for (auto q : s->r_rs) F(q);
-  for (auto q : s->part2_rs) F(q);
-  for (auto q : s->h_rs) F(q);
-  F(s->logfact);
-  F(s->Wv);
-  F(s->llpart);
-  F(s->bcur);
-  F(s->bprev);
-  F(s->gidx);
-  F(s->gsz);
-  F(s->goff);
-  F(s->gcols_new);
-  F(s->mblk);
-  F(s->dcol);
-  F(s->mblk2);
-  F(s->mwork);
-  F(s->zwork);
-  F(s->allcols);
-  for (auto q : s->gxtx_rs) F(q);
-  for (auto q : s->geig_v_rs) F(q);
-  for (auto q : s->geig_l_rs) F(q);
-  for (auto q : s->cox_allocs) F(q);
-  F(s->idcols);
-  F(s->part2);
-  F(s->bd);
-  F(s->beta_dense);
-  F(s->sol);
-  F(s->tmpv);
-  F(s->A_new);
-  F(s->cand);
-  F(s->tie_buf);
-  F(s->fb_work);
-  F(s->hist);
-  F(s->gcols);
-  F(s->info);
-  F(s->hist_beta);
-  F(s->hist_coef0);
-  F(s->gtasks);
-  for (auto &bt : s->big_tasks) F(bt.second);
-  F(s->rdiag);
-  F(s->zbig);
-  for (auto &c : s->gcache) {
-    F(c.g0);
-    F(c.g1);
-    F(c.A);
-    F(c.meta);
-  }
-  F(s->Xp);
-  F(s->zp);
-  F(s->cvp_part);
-  for (auto &c : s->cov) {
-    F(c.G);
-    if (!c.shares_map) {
-      F(c.slot_of);
-      F(c.meta);
-    }
-    F(c.GS);
-    F(c.zero);
-  }
-  F(s->cov_part);
-  F(s->cgb_work);
-  F(s->bd2);
-  F(s->inA);
-  F(s->cov_bmm);
-  F(s->cov_fcols);
-  F(s->cov_extras);
-  F(s->Rt);
-  F(s->gsrc);
-  F(s->gpart);
-  F(s->Gt);
-  F(s->init_idx_d);
-  F(s->init_val_d);
-  F(s->resblk);
-  for (auto q : s->res_buf)
-    if (q) (void)hipHostFree(q);
-  if (s->pub_flag) (void)hipHostFree(s->pub_flag);
-  for (auto q : s->snap)
-    if (q) (void)hipFree(q);
-  if (s->stage_h) (void)hipHostFree(s->stage_h);
-  for (auto e : s->ev_pool) (void)hipEventDestroy(e);
-  for (auto &ev : s->xtx_ev)
-    if (ev && !s->parent) (void)hipEventDestroy(ev);
+  s->cv_own.release();
+  s->own.release();
   if (s->st) ctx_stream_destroy(s->st);
   delete s;
 }
@@ -179,7 +73,7 @@ int k1_begin(bessx_session *s, hipEvent_t *a, hipEvent_t *b) {
   if (s->ev_used + 2 > s->ev_pool.size()) {
     for (int i = 0; i < 64; i++) {
       hipEvent_t e;
-      HIPX(hipEventCreate(&e));
+      HIPX(s->own.event(&e));
       s->ev_pool.push_back(e);
     }
   }
@@ -228,51 +122,35 @@ int cov_collect(bessx_session *s, int nfill) {
   return 0;
 }
 
+// (what a failed allocation leaves half-built stays with the row set's owner and goes with it)
 int alloc_gram_cache(bessx_session *s) {
+  Owner &own = rowset_owner(s, (int)s->gcache.size());
   bessx_session::GramCache c;
-  hipError_t e = dmalloc(&c.g0, (size_t)256 * 256);
-  if (e == hipSuccess) e = dmalloc(&c.g1, (size_t)256 * 256);
-  if (e == hipSuccess) e = dmalloc(&c.A, 256);
-  if (e == hipSuccess) e = dmalloc(&c.meta, 2);
-  if (e == hipSuccess) e = hipMemset(c.meta, 0, 2 * sizeof(int));
-  if (e != hipSuccess) {  // nothing half-built is left behind
-    (void)hipFree(c.g0);
-    (void)hipFree(c.g1);
-    (void)hipFree(c.A);
-    (void)hipFree(c.meta);
-    return fail(BESSX_ERR_HIP, std::string("Gram cache: ") + hipGetErrorString(e));
-  }
+  hipError_t e = own.alloc(&c.g0, (size_t)256 * 256);
+  if (e == hipSuccess) e = own.alloc(&c.g1, (size_t)256 * 256);
+  if (e == hipSuccess) e = own.alloc(&c.A, 256);
+  if (e == hipSuccess) e = own.zeros(&c.meta, 2);
+  if (e != hipSuccess) return fail(BESSX_ERR_HIP, std::string("Gram cache: ") + hipGetErrorString(e));
   s->gcache.push_back(c);
   return 0;
 }
 
-
 int alloc_cov_cache(bessx_session *s, bool share_map) {
+  Owner &own = rowset_owner(s, (int)s->cov.size());
   bessx_session::CovCache c;
-  hipError_t e = dmalloc(&c.G, (size_t)s->p * s->cov_C);
+  hipError_t e = own.alloc(&c.G, (size_t)s->p * s->cov_C);
   if (share_map && !s->cov.empty()) {
     c.slot_of = s->cov[0].slot_of;
     c.meta = s->cov[0].meta;
     c.shares_map = true;
   }
-  if (e == hipSuccess && !c.shares_map) e = dmalloc(&c.slot_of, (size_t)s->p);
-  if (e == hipSuccess && !c.shares_map) e = dmalloc(&c.meta, 8);
-  if (e == hipSuccess) e = dmalloc(&c.GS, (size_t)COV_CS * COV_CS);
-  if (e == hipSuccess) e = hipMemset(c.GS, 0, (size_t)COV_CS * COV_CS * sizeof(double));
+  if (e == hipSuccess && !c.shares_map) e = own.alloc(&c.slot_of, (size_t)s->p);
+  if (e == hipSuccess && !c.shares_map) e = own.alloc(&c.meta, 8);
+  if (e == hipSuccess) e = own.zeros(&c.GS, (size_t)COV_CS * COV_CS);
   if (e == hipSuccess && !c.shares_map) e = hipMemset(c.slot_of, 0xff, (size_t)s->p * sizeof(int));
   if (e == hipSuccess && !c.shares_map) e = hipMemset(c.meta, 0, 8 * sizeof(int));
-  if (e == hipSuccess) e = dmalloc(&c.zero, 8);
-  if (e == hipSuccess) e = hipMemset(c.zero, 0, 8 * sizeof(double));
-  if (e != hipSuccess) {
-    (void)hipFree(c.G);
-    if (!c.shares_map) {
-      (void)hipFree(c.slot_of);
-      (void)hipFree(c.meta);
-    }
-    (void)hipFree(c.GS);
-    (void)hipFree(c.zero);
-    return fail(BESSX_ERR_HIP, std::string("Gram column cache: ") + hipGetErrorString(e));
-  }
+  if (e == hipSuccess) e = own.zeros(&c.zero, 8);
+  if (e != hipSuccess) return fail(BESSX_ERR_HIP, std::string("Gram column cache: ") + hipGetErrorString(e));
   s->cov.push_back(c);
   return 0;
 }
@@ -465,7 +343,7 @@ int gram_tasks_for(bessx_session *s, int mt, const GramTask **tasks, int *ntask)
   std::vector<GramTask> t;
   build_gram_tasks(mt, t);
   GramTask *d = nullptr;
-  HIPX(dmalloc(&d, t.size()));
+  HIPX(s->own.alloc(&d, t.size()));
   HIPX(hipMemcpy(d, t.data(), t.size() * sizeof(GramTask), hipMemcpyHostToDevice));
   s->big_tasks.push_back({mt, d});
   s->big_task_cnt.push_back((int)t.size());
@@ -514,20 +392,17 @@ int upload_x(bessx_session *s, const double *x, int col_major) {
   // row-major: stage chunks of rows and transpose on the device
   size_t chunk_rows = std::max<size_t>(64, ((size_t)256 << 20) / ((size_t)p * sizeof(double)));
   chunk_rows = std::min<size_t>(chunk_rows, (size_t)n);
+  Owner tmp;
   double *stage = nullptr;
-  HIPX(dmalloc(&stage, chunk_rows * (size_t)p));
+  HIPX(tmp.alloc(&stage, chunk_rows * (size_t)p));
   for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk_rows) {
     size_t rows = std::min(chunk_rows, (size_t)n - r0);
     hipError_t e = hipMemcpyAsync(stage, x + r0 * (size_t)p, rows * (size_t)p * sizeof(double),
                                   hipMemcpyHostToDevice, s->st);
     if (e == hipSuccess) e = launch_transpose_in(stage, (int)rows, p, s->X, s->ld, (long)r0, s->st);
     if (e == hipSuccess) e = hipStreamSynchronize(s->st);
-    if (e != hipSuccess) {
-      (void)hipFree(stage);
-      return fail(BESSX_ERR_HIP, std::string("upload_x: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(BESSX_ERR_HIP, std::string("upload_x: ") + hipGetErrorString(e));
   }
-  HIPX(hipFree(stage));
   return 0;
 }
 
@@ -566,11 +441,12 @@ int check_device_matrix(const char *what, const void *data, int dtype, long long
 int ingest_enqueue(const void *src, int f32, long long rs, long long cs, const int *order_d, long long n, long long p,
                    double *dst, long long ld, unsigned *nan_flag, hipStream_t caller, hipStream_t st) {
   // reads come after everything the caller has queued on its stream so far
+  Owner tmp;
   hipEvent_t ev = nullptr;
-  HIPX(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  HIPX(tmp.event(&ev, hipEventDisableTiming));
   hipError_t e = hipEventRecord(ev, caller);
   if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
-  (void)hipEventDestroy(ev);  // (released once the record has completed)
+  tmp.release();  // (the event is released once the record has completed)
   if (e == hipSuccess) e = hipMemsetAsync(nan_flag, 0, sizeof(unsigned), st);
   if (e == hipSuccess) e = launch_ingest(src, f32, rs, cs, order_d, n, p, dst, ld, nan_flag, st);
   if (e != hipSuccess) return fail(BESSX_ERR_HIP, std::string("ingest: ") + hipGetErrorString(e));
@@ -578,8 +454,9 @@ int ingest_enqueue(const void *src, int f32, long long rs, long long cs, const i
 }
 
 int ingest_x(bessx_session *s, const DevX &dx) {
+  Owner tmp;
   unsigned *flag = nullptr;
-  HIPX(dmalloc(&flag, 1));
+  HIPX(tmp.alloc(&flag, 1));
   unsigned h = 0;
   int rc = ingest_enqueue(dx.data, dx.f32, dx.rs, dx.cs, dx.order_d, s->n, s->p, s->X, s->ld, flag, dx.stream, s->st);
   if (rc == 0) {
@@ -587,7 +464,6 @@ int ingest_x(bessx_session *s, const DevX &dx) {
     if (e == hipSuccess) e = hipStreamSynchronize(s->st);
     if (e != hipSuccess) rc = fail(BESSX_ERR_HIP, std::string("ingest_x: ") + hipGetErrorString(e));
   }
-  (void)hipFree(flag);
   if (rc) return rc;
   s->x_dev_bytes += (long long)s->n * s->p * (dx.f32 ? 4 : 8);
   if (h) return fail(BESSX_ERR_ARG, "There is NAN value in X");
@@ -633,7 +509,7 @@ int need_device() {
 }
 
 // copy a column-major (n x p, leading dimension ld_in) host matrix into a zero-padded device matrix
-int upload_padded(Scratch &sc, const double *x, int n, int p, int ld_in, int U, double **dX, long *ld_out) {
+int upload_padded(Owner &sc, const double *x, int n, int p, int ld_in, int U, double **dX, long *ld_out) {
   long rb = 128L * U;
   long ld = ((long)n + rb - 1) / rb * rb;
   HIPX(sc.alloc(dX, (size_t)ld * p));
@@ -644,7 +520,7 @@ int upload_padded(Scratch &sc, const double *x, int n, int p, int ld_in, int U, 
   return 0;
 }
 
-int upload_vec_padded(Scratch &sc, const double *v, int n, long ld, double **dv) {
+int upload_vec_padded(Owner &sc, const double *v, int n, long ld, double **dv) {
   std::vector<double> tmp((size_t)ld, 0.0);
   if (v) std::copy(v, v + n, tmp.begin());
   HIPX(sc.alloc(dv, (size_t)ld));
@@ -663,14 +539,7 @@ hipError_t cox_alloc(bessx_session *s) {
   const long ld = s->ld;
   const int n = s->n, capA = s->capA;
   {
-    auto V = [&](double **dst, size_t count) -> hipError_t {
-      hipError_t e = dmalloc(dst, count);
-      if (e == hipSuccess) {
-        s->cox_allocs.push_back(*dst);
-        e = hipMemset(*dst, 0, count * sizeof(double));
-      }
-      return e;
-    };
+    auto V = [&](double **dst, size_t count) { return s->own.zeros(dst, count); };
     CoxBufs &c = s->cox;
     double **vecs[] = {&c.E, &c.TH, &c.ET, &c.S0, &c.RS0, &c.SALL, &c.STEST, &c.EW, &c.WD, &c.ETA0, &c.THF, &c.S0F,
                        &c.RS0F, &c.VG, &c.WG1, &c.UD, &c.TH1, &c.S1};
@@ -838,38 +707,17 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
     double *Xraw = nullptr, *yw = nullptr, *scr = nullptr;
     int *ibuf = nullptr;
     unsigned char *fl_d = nullptr;
-    auto drop = [&]() {
-      (void)hipFree(Xraw);
-      (void)hipFree(yw);
-      (void)hipFree(scr);
-      (void)hipFree(ibuf);
-      (void)hipFree(fl_d);
-      s->X = nullptr;
-    };
-#define HIPS(expr)                                                                            \
-  do {                                                                                        \
-    hipError_t e__ = (expr);                                                                  \
-    if (e__ != hipSuccess) {                                                                  \
-      drop();                                                                                 \
-      return bail(fail(BESSX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)));   \
-    }                                                                                         \
-  } while (0)
-    HIPS(dmalloc(&Xraw, (size_t)ld * pf));
+    Owner tmp;  // the screening's temporaries: gone at the end of this block, whichever way it is left
+    HIPT(tmp.alloc(&Xraw, (size_t)ld * pf));
     s->X = Xraw;
-    {
-      int rc = dx ? ingest_x(s, *dx) : upload_x(s, pb->x, pb->x_col_major);
-      if (rc) {
-        drop();
-        return bail(rc);
-      }
-    }
+    TRY(dx ? ingest_x(s, *dx) : upload_x(s, pb->x, pb->x_col_major));
     // yw: y | weight | ones, padded with zeros;  scr: score | partial sums / per-column solver state
     const size_t scr_len = (size_t)pf * 3 + std::max((size_t)2 * s->nrb * pf, (size_t)5 * pf);
-    HIPS(dmalloc(&yw, (size_t)ld * 3));
-    HIPS(dmalloc(&scr, scr_len));
-    HIPS(dmalloc(&ibuf, (size_t)pf + ss + 32768 + 3 * (size_t)pf + 8));
-    HIPS(dmalloc(&fl_d, (size_t)pf));
-    HIPS(hipMemcpy(fl_d, fl.data(), (size_t)pf, hipMemcpyHostToDevice));
+    HIPT(tmp.alloc(&yw, (size_t)ld * 3));
+    HIPT(tmp.alloc(&scr, scr_len));
+    HIPT(tmp.alloc(&ibuf, (size_t)pf + ss + 32768 + 3 * (size_t)pf + 8));
+    HIPT(tmp.alloc(&fl_d, (size_t)pf));
+    HIPT(hipMemcpy(fl_d, fl.data(), (size_t)pf, hipMemcpyHostToDevice));
     {
       std::vector<double> tmp((size_t)ld * 3, 0.0);
       for (int i = 0; i < n; i++) {
@@ -877,7 +725,7 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
         tmp[(size_t)ld + i] = pb->weight ? pb->weight[i] : 1.0;
         tmp[(size_t)2 * ld + i] = 1.0;
       }
-      HIPS(hipMemcpy(yw, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPT(hipMemcpy(yw, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     double *score = scr, *sxy = scr + pf, *sxx = scr + 2 * (size_t)pf, *work = scr + 3 * (size_t)pf;
     int *done = ibuf, *keep = ibuf + pf, *cand = ibuf + pf + ss;
@@ -895,14 +743,11 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
         g_off[g + 1] = g_off[g] + g_sz[g] * g_sz[g];
         gmax = std::max(gmax, g_sz[g]);
       }
+      Owner gtmp;
       int *gd = nullptr;
       double *gm = nullptr;
-      auto gdrop = [&]() {
-        (void)hipFree(gd);
-        (void)hipFree(gm);
-      };
-      hipError_t e = dmalloc(&gd, (size_t)3 * Ng + 1);
-      if (e == hipSuccess) e = dmalloc(&gm, (size_t)2 * g_off[Ng] + 3 * (size_t)pf);
+      hipError_t e = gtmp.alloc(&gd, (size_t)3 * Ng + 1);
+      if (e == hipSuccess) e = gtmp.alloc(&gm, (size_t)2 * g_off[Ng] + 3 * (size_t)pf);
       if (e == hipSuccess) e = hipMemcpy(gd, g_lo.data(), (size_t)Ng * sizeof(int), hipMemcpyHostToDevice);
       if (e == hipSuccess) e = hipMemcpy(gd + Ng, g_sz.data(), (size_t)Ng * sizeof(int), hipMemcpyHostToDevice);
       if (e == hipSuccess) e = hipMemcpy(gd + 2 * Ng, g_off.data(), ((size_t)Ng + 1) * sizeof(int), hipMemcpyHostToDevice);
@@ -920,11 +765,11 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
       } else {
         // logit_fit on the columns of a group (src/logistic.cpp:60-160): one block per group up to 8 columns
         double *gstate = nullptr;
-        if (e == hipSuccess) e = dmalloc(&gstate, screen_logit_group_state_doubles(Ng));
+        if (e == hipSuccess) e = gtmp.alloc(&gstate, screen_logit_group_state_doubles(Ng));
         if (e == hipSuccess)
           e = launch_screen_logit_group(Xraw, ld, n, Ng, gd, gd + Ng, yw, yw + ld, gstate, done, fl_d, score, s->st);
         if (e == hipSuccess) e = hipStreamSynchronize(s->st);
-        (void)hipFree(gstate);
+        gtmp.release_one(gstate);
       }
       if (e == hipSuccess) e = hipStreamSynchronize(s->st);
       if (e == hipSuccess && pb->model_type != 1) {
@@ -940,13 +785,10 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
           if (gs <= limit) continue;
           double sc = DBL_MAX;
           if (!fl[g]) {
-            if (logit && n <= gs) {
-              gdrop();
-              drop();
+            if (logit && n <= gs)
               return bail(fail(BESSX_ERR_UNSUPPORTED, "logistic screening: a group at least as wide as the sample is "
                                "undefined behaviour in the reference (logit_fit returns n coefficients, "
                                "src/logistic.cpp:62-110, of which screening() reads the last g_size, src/screening.cpp:60)"));
-            }
             std::vector<double> xs(dx ? 0 : (size_t)n * gs);
             DevX subx;
             if (dx) {  // the group's columns as a column-offset view of the caller's matrix
@@ -983,11 +825,7 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
                                      nullptr, nullptr);
             if (sub) bessx_session_destroy(sub);
             (void)hipSetDevice(s->device);
-            if (rc != 0) {
-              gdrop();
-              drop();
-              return bail(rc);
-            }
+            if (rc != 0) return bail(rc);
             double acc = 0.0;
             for (int u = 0; u < gs; u++) acc += bq[u] * bq[u];
             const double v = acc / (double)gs;  // coef_norm, src/screening.cpp:60
@@ -996,32 +834,28 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
           e = hipMemcpy(score + g, &sc, sizeof(double), hipMemcpyHostToDevice);
         }
       }
-      gdrop();
-      if (e != hipSuccess) {
-        drop();
-        return bail(fail(BESSX_ERR_HIP, std::string("group screening: ") + hipGetErrorString(e)));
-      }
+      if (e != hipSuccess) return bail(fail(BESSX_ERR_HIP, std::string("group screening: ") + hipGetErrorString(e)));
     } else if (pb->model_type == 1) {
       // beta_j = x_j.y / x_j.x_j: the closed form of lm_fit on one column (src/screening.cpp:44-47), one score pass
-      HIPS(launch_xtv(Xraw, ld, pf, s->U, yw, yw + 2 * ld, work, work + (size_t)s->nrb * pf, nullptr, 0, s->st));
-      HIPS(launch_part_sum(work, s->nrb, pf, sxy, s->st));
-      HIPS(launch_part_sum(work + (size_t)s->nrb * pf, s->nrb, pf, sxx, s->st));
-      HIPS(launch_screen_score_lm(sxy, sxx, pf, fl_d, score, s->st));
+      HIPT(launch_xtv(Xraw, ld, pf, s->U, yw, yw + 2 * ld, work, work + (size_t)s->nrb * pf, nullptr, 0, s->st));
+      HIPT(launch_part_sum(work, s->nrb, pf, sxy, s->st));
+      HIPT(launch_part_sum(work + (size_t)s->nrb * pf, s->nrb, pf, sxx, s->st));
+      HIPT(launch_screen_score_lm(sxy, sxx, pf, fl_d, score, s->st));
     } else if (pb->model_type == 2) {
-      HIPS(launch_screen_logit(Xraw, ld, n, pf, yw, yw + ld, work, done, fl_d, score, s->st));
+      HIPT(launch_screen_logit(Xraw, ld, n, pf, yw, yw + ld, work, done, fl_d, score, s->st));
     } else {
-      HIPS(launch_screen_cox(Xraw, ld, n, pf, yw, yw + ld, fl_d, score, s->st));
+      HIPT(launch_screen_cox(Xraw, ld, n, pf, yw, yw + ld, fl_d, score, s->st));
     }
     {
       // max_k(coef_norm, screening_size), src/screening.cpp:66: equal marginal scores (duplicated columns) are tied
       int *tflag = ibuf + pf + ss + 32768;
-      HIPS(hipMemsetAsync(tflag, 0, 8 * sizeof(int), s->st));
+      HIPT(hipMemsetAsync(tflag, 0, 8 * sizeof(int), s->st));
       const TopkTie tie = {tflag, tflag + 8};
-      HIPS(launch_topk(score, nunits, ss, keep, cand, nullptr, 0, s->st, nullptr, nullptr, &tie));
+      HIPT(launch_topk(score, nunits, ss, keep, cand, nullptr, 0, s->st, nullptr, nullptr, &tie));
     }
-    HIPS(hipStreamSynchronize(s->st));
+    HIPT(hipStreamSynchronize(s->st));
     s->screen_map.assign((size_t)ss, 0);
-    HIPS(hipMemcpy(s->screen_map.data(), keep, (size_t)ss * sizeof(int), hipMemcpyDeviceToHost));
+    HIPT(hipMemcpy(s->screen_map.data(), keep, (size_t)ss * sizeof(int), hipMemcpyDeviceToHost));
     int pk = ss;  // columns kept
     if (gscr) {
       // kept groups -> their columns (ascending), the group index of the kept data, always_select by kept-group rank
@@ -1033,25 +867,17 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
         for (int u = 0; u < g_sz[g]; u++) s->screen_map.push_back(g_lo[g] + u);
       }
       pk = (int)s->screen_map.size();
-      (void)hipFree(ibuf);
-      ibuf = nullptr;
-      HIPS(dmalloc(&ibuf, (size_t)pk));
+      HIPT(tmp.regrow(&ibuf, (size_t)pk));
       keep = ibuf;
-      HIPS(hipMemcpy(keep, s->screen_map.data(), (size_t)pk * sizeof(int), hipMemcpyHostToDevice));
+      HIPT(hipMemcpy(keep, s->screen_map.data(), (size_t)pk * sizeof(int), hipMemcpyHostToDevice));
     }
     double *X2 = nullptr;
-    HIPS(dmalloc(&X2, (size_t)ld * pk));
+    HIPT(s->own.alloc(&X2, (size_t)ld * pk));
     {
       hipError_t e = launch_gather_cols(Xraw, ld, keep, pk, X2, s->st);
       if (e == hipSuccess) e = hipStreamSynchronize(s->st);
-      if (e != hipSuccess) {
-        (void)hipFree(X2);
-        drop();
-        return bail(fail(BESSX_ERR_HIP, std::string("gather_cols: ") + hipGetErrorString(e)));
-      }
+      if (e != hipSuccess) return bail(fail(BESSX_ERR_HIP, std::string("gather_cols: ") + hipGetErrorString(e)));
     }
-    drop();
-#undef HIPS
     s->X = X2;
     s->p = pk;
     x_ready = true;
@@ -1108,18 +934,18 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
       return bail(fail(BESSX_ERR_UNSUPPORTED, "Cox with groups of size > 1 exists only for algorithm_type 2 / 3 (the "
                                               "group branch of GroupPdasCox::get_A, src/Algorithm.h:1497-1568)"));
   }
-  if (!x_ready) HIPT(dmalloc(&s->X, (size_t)ld * p));
-  HIPT(dmalloc(&s->y, (size_t)ld));
-  HIPT(dmalloc(&s->w, (size_t)ld));
-  HIPT(dmalloc(&s->aux, (size_t)ld * 3));
-  HIPT(dmalloc(&s->x_mean, (size_t)p));
-  HIPT(dmalloc(&s->x_norm, (size_t)p));
-  HIPT(dmalloc(&s->y_mean_d, 1));
-  HIPT(dmalloc(&s->always, (size_t)p));
-  HIPT(dmalloc(&s->tmpv, (size_t)ld));
-  HIPT(dmalloc(&s->part2, (size_t)s->nrb * p));
-  HIPT(dmalloc(&s->bd, (size_t)p));
-  HIPT(dmalloc(&s->beta_dense, (size_t)p));
+  if (!x_ready) HIPT(s->own.alloc(&s->X, (size_t)ld * p));
+  HIPT(s->own.alloc(&s->y, (size_t)ld));
+  HIPT(s->own.alloc(&s->w, (size_t)ld));
+  HIPT(s->own.alloc(&s->aux, (size_t)ld * 3));
+  HIPT(s->own.alloc(&s->x_mean, (size_t)p));
+  HIPT(s->own.alloc(&s->x_norm, (size_t)p));
+  HIPT(s->own.alloc(&s->y_mean_d, 1));
+  HIPT(s->own.alloc(&s->always, (size_t)p));
+  HIPT(s->own.alloc(&s->tmpv, (size_t)ld));
+  HIPT(s->own.alloc(&s->part2, (size_t)s->nrb * p));
+  HIPT(s->own.alloc(&s->bd, (size_t)p));
+  HIPT(s->own.alloc(&s->beta_dense, (size_t)p));
   if (pb->max_sparsity < 0 || pb->max_sparsity > T0_HARD)
     return bail(fail(BESSX_ERR_ARG, "max_sparsity must be in [0, " + std::to_string(T0_HARD) + "]"));
   s->cap = std::min(p, std::max(T0_CAP, pb->max_sparsity));
@@ -1127,27 +953,27 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
   s->capA = std::max(s->capA, 256);
   s->hist_stride = s->capA;
   const int capA = s->capA, mt_max = capA / 16;
-  HIPT(dmalloc(&s->sol, (size_t)capA));
-  HIPT(dmalloc(&s->A_new, (size_t)capA));
-  HIPT(dmalloc(&s->rdiag, (size_t)capA));
-  HIPT(dmalloc(&s->zbig, (size_t)capA));
-  HIPT(dmalloc(&s->cand, 32768));
-  HIPT(dmalloc(&s->fb_work, CHOL_FB_DOUBLES));
-  HIPT(dmalloc(&s->tie_buf, (size_t)3 * p + 8));
+  HIPT(s->own.alloc(&s->sol, (size_t)capA));
+  HIPT(s->own.alloc(&s->A_new, (size_t)capA));
+  HIPT(s->own.alloc(&s->rdiag, (size_t)capA));
+  HIPT(s->own.alloc(&s->zbig, (size_t)capA));
+  HIPT(s->own.alloc(&s->cand, 32768));
+  HIPT(s->own.alloc(&s->fb_work, CHOL_FB_DOUBLES));
+  HIPT(s->own.alloc(&s->tie_buf, (size_t)3 * p + 8));
   HIPT(hipMemset(s->tie_buf, 0, 8 * sizeof(int)));
   s->tie = TopkTie{s->tie_buf, s->tie_buf + 8};
-  HIPT(dmalloc(&s->hist, (size_t)(s->max_iter + 2) * s->hist_stride));
-  HIPT(dmalloc(&s->hist_beta, (size_t)(s->max_iter + 2) * s->hist_stride));
-  HIPT(dmalloc(&s->hist_coef0, (size_t)(s->max_iter + 2)));
-  HIPT(dmalloc(&s->gcols, (size_t)capA + 16));
-  HIPT(dmalloc(&s->Rt, (size_t)16 * 256));
-  HIPT(dmalloc(&s->gsrc, 256));
-  HIPT(dmalloc(&s->init_idx_d, (size_t)capA));
-  HIPT(dmalloc(&s->init_val_d, (size_t)capA));
-  HIPT(dmalloc(&s->Gt, (size_t)mt_max * (mt_max + 1) / 2 * 256));
+  HIPT(s->own.alloc(&s->hist, (size_t)(s->max_iter + 2) * s->hist_stride));
+  HIPT(s->own.alloc(&s->hist_beta, (size_t)(s->max_iter + 2) * s->hist_stride));
+  HIPT(s->own.alloc(&s->hist_coef0, (size_t)(s->max_iter + 2)));
+  HIPT(s->own.alloc(&s->gcols, (size_t)capA + 16));
+  HIPT(s->own.alloc(&s->Rt, (size_t)16 * 256));
+  HIPT(s->own.alloc(&s->gsrc, 256));
+  HIPT(s->own.alloc(&s->init_idx_d, (size_t)capA));
+  HIPT(s->own.alloc(&s->init_val_d, (size_t)capA));
+  HIPT(s->own.alloc(&s->Gt, (size_t)mt_max * (mt_max + 1) / 2 * 256));
   // fp64 partial tiles of the row slabs: 48 MB, or at least 8 slabs of the largest Gram this session can form
   s->gpart_elems = std::max<size_t>((size_t)6 << 20, (size_t)8 * mt_max * (mt_max + 1) / 2 * 256);
-  HIPT(dmalloc(&s->gpart, s->gpart_elems));
+  HIPT(s->own.alloc(&s->gpart, s->gpart_elems));
   // Gram task lists for every tile count
   {
     std::vector<GramTask> all;
@@ -1170,7 +996,7 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
         }
       s->gtask_inc_cnt[mt] = (int)all.size() - s->gtask_inc_off[mt];
     }
-    HIPT(dmalloc(&s->gtasks, all.size()));
+    HIPT(s->own.alloc(&s->gtasks, all.size()));
     HIPT(hipMemcpy(s->gtasks, all.data(), all.size() * sizeof(GramTask), hipMemcpyHostToDevice));
   }
   // result block
@@ -1186,22 +1012,18 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
     size_t o_a = off;
     off += (size_t)capA * sizeof(int);
     s->res_bytes = off;
-    HIPT(hipMalloc(reinterpret_cast<void **>(&s->resblk), off));
-    HIPT(hipMemset(s->resblk, 0, off));
+    HIPT(s->own.zeros(&s->resblk, off));
     s->ctrl = reinterpret_cast<FitCtrl *>(s->resblk + o_ctrl);
     s->sse = reinterpret_cast<double *>(s->resblk + o_sse);
     s->b_cur = reinterpret_cast<double *>(s->resblk + o_b);
     s->A_cur = reinterpret_cast<int *>(s->resblk + o_a);
     for (int b = 0; b < 2; b++) {
-      HIPT(hipHostMalloc(reinterpret_cast<void **>(&s->res_buf[b]), off));
+      HIPT(s->own.pinned(&s->res_buf[b], off));
       std::memset(s->res_buf[b], 0, off);
     }
     s->res_h = s->res_buf[0];
-    for (int b = 0; b < 2; b++) {
-      HIPT(hipMalloc(reinterpret_cast<void **>(&s->snap[b]), off + 64));
-      HIPT(hipMemset(s->snap[b], 0, off + 64));
-    }
-    HIPT(hipHostMalloc(reinterpret_cast<void **>(&s->pub_flag), 128));
+    for (int b = 0; b < 2; b++) HIPT(s->own.zeros(&s->snap[b], off + 64));
+    HIPT(s->own.pinned(&s->pub_flag, 128 / sizeof(unsigned long long)));
     s->pub_flag[0] = 0ull;
     s->pub_flag[8] = 0ull;  // second buffer's flag, its own cache line
     if (const char *ev = test_hook("publish")) s->publish = std::atoi(ev) != 0;
@@ -1209,7 +1031,7 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
     if (const char *ev = test_hook("chain")) s->chain = std::atoi(ev) != 0;
     if (const char *ev = std::getenv("BESSX_KPATH_CHAINS")) s->kpath_chains = std::max(0, std::atoi(ev));
     if (!s->publish) s->chain = false;
-    HIPT(hipHostMalloc(reinterpret_cast<void **>(&s->stage_h), (size_t)capA * (sizeof(int) + sizeof(double))));
+    HIPT(s->own.pinned(&s->stage_h, (size_t)capA * (sizeof(int) + sizeof(double))));
   }
   static_assert(sizeof(FitCtrl) <= 128, "FitCtrl must fit its slot of the result block");
   // data
@@ -1263,9 +1085,9 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
   s->mask.push_back(nullptr);
   s->n_train.push_back(n);
   double *q = nullptr;
-  HIPT(dmalloc(&q, (size_t)p));
+  HIPT(s->own.alloc(&q, (size_t)p));
   s->xtx.push_back(q);
-  HIPT(dmalloc(&q, (size_t)p));
+  HIPT(s->own.alloc(&q, (size_t)p));
   s->xty.push_back(q);
   // Cox: the score pass reads X once and leaves five partial sums per (row block, column) + one per block
   // (k_cox_score1p); the test hook cox_score=2pass keeps the totals / carry / rescan form (two reads of X)
@@ -1274,23 +1096,20 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
     s->cox.one_pass = !(ev && std::string(ev) == "2pass");
     s->cox.need_uv = s->grouped ? 1 : 0;
   }
-  HIPT(dmalloc(&q, part_elems(s)));
+  HIPT(s->own.alloc(&q, part_elems(s)));
   s->part_rs.push_back(q);
-  HIPT(dmalloc(&q, (size_t)ld));
-  HIPT(hipMemset(q, 0, (size_t)ld * sizeof(double)));
+  HIPT(s->own.zeros(&q, (size_t)ld));
   s->r_rs.push_back(q);
-  HIPT(dmalloc(&q, (size_t)s->nrb * p));
+  HIPT(s->own.alloc(&q, (size_t)s->nrb * p));
   s->part2_rs.push_back(q);
-  HIPT(dmalloc(&q, (size_t)ld));
-  HIPT(hipMemset(q, 0, (size_t)ld * sizeof(double)));
+  HIPT(s->own.zeros(&q, (size_t)ld));
   s->h_rs.push_back(q);
-  HIPT(dmalloc(&s->Wv, (size_t)ld));
-  HIPT(hipMemset(s->Wv, 0, (size_t)ld * sizeof(double)));
+  HIPT(s->own.zeros(&s->Wv, (size_t)ld));
   s->llpart_cap = (size_t)std::max(s->n_sse_blk, 1024);  // (also one entry per row slab of k_irls_gram)
-  HIPT(dmalloc(&s->llpart, s->llpart_cap));
-  HIPT(dmalloc(&s->bcur, (size_t)capA + 16));
-  HIPT(dmalloc(&s->bprev, (size_t)capA + 16));
-  HIPT(dmalloc(&s->logfact, (size_t)ld));
+  HIPT(s->own.alloc(&s->llpart, s->llpart_cap));
+  HIPT(s->own.alloc(&s->bcur, (size_t)capA + 16));
+  HIPT(s->own.alloc(&s->bprev, (size_t)capA + 16));
+  HIPT(s->own.alloc(&s->logfact, (size_t)ld));
   {
     // sum_{j=1..y} log j per row, the loop of loglik_poisson (src/poisson.cpp:27-41); only Poisson reads it
     std::vector<double> lf((size_t)ld, 0.0);
@@ -1305,25 +1124,25 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
   }
   s->cache.assign(1, bessx_session::RsCache());
   if (s->grouped) {
-    HIPT(dmalloc(&s->gidx, (size_t)s->N));
-    HIPT(dmalloc(&s->gsz, (size_t)s->N));
-    HIPT(dmalloc(&s->goff, (size_t)s->N + 1));
+    HIPT(s->own.alloc(&s->gidx, (size_t)s->N));
+    HIPT(s->own.alloc(&s->gsz, (size_t)s->N));
+    HIPT(s->own.alloc(&s->goff, (size_t)s->N + 1));
     HIPT(hipMemcpy(s->gidx, s->gidx_h.data(), (size_t)s->N * sizeof(int), hipMemcpyHostToDevice));
     HIPT(hipMemcpy(s->gsz, s->gsz_h.data(), (size_t)s->N * sizeof(int), hipMemcpyHostToDevice));
     HIPT(hipMemcpy(s->goff, s->goff_h.data(), ((size_t)s->N + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIPT(dmalloc(&s->gcols_new, (size_t)s->capA));
-    HIPT(dmalloc(&s->mblk, (size_t)s->goff_h[s->N]));
-    HIPT(dmalloc(&s->dcol, (size_t)p));
+    HIPT(s->own.alloc(&s->gcols_new, (size_t)s->capA));
+    HIPT(s->own.alloc(&s->mblk, (size_t)s->goff_h[s->N]));
+    HIPT(s->own.alloc(&s->dcol, (size_t)p));
     if (s->gmax > 16) {
-      HIPT(dmalloc(&s->mwork, (size_t)s->goff_h[s->N]));
-      HIPT(dmalloc(&s->zwork, (size_t)2 * p));
+      HIPT(s->own.alloc(&s->mwork, (size_t)s->goff_h[s->N]));
+      HIPT(s->own.alloc(&s->zwork, (size_t)2 * p));
     }
     if (s->model_type == 4) {
-      HIPT(dmalloc(&s->mblk2, (size_t)s->goff_h[s->N]));
-      HIPT(dmalloc(&s->allcols, (size_t)p));
+      HIPT(s->own.alloc(&s->mblk2, (size_t)s->goff_h[s->N]));
+      HIPT(s->own.alloc(&s->allcols, (size_t)p));
       HIPT(launch_iota(s->allcols, p, s->st));
     }
-    HIPT(dmalloc(&q, (size_t)s->goff_h[s->N]));
+    HIPT(s->own.alloc(&q, (size_t)s->goff_h[s->N]));
     s->gxtx_rs.push_back(q);
   }
   TRY(alloc_gram_cache(s));
@@ -1388,13 +1207,12 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
         s->cov_panel_blocks = (int)std::min<long>(panel_blocks, 1 << 30);
         s->cov_rps = (int)rps;
         s->cov_nslab = (int)ns;
-        HIPT(dmalloc(&s->cov_part, (size_t)COV_SLOT_GROUPS * ns * njg * cov_streamed_tiles_per_wave() * 2 * 256));
-        HIPT(dmalloc(&s->bd2, (size_t)p));
-        HIPT(dmalloc(&s->inA, (size_t)p));
-        HIPT(hipMemset(s->inA, 0, (size_t)p));
-        HIPT(dmalloc(&s->cov_bmm, (size_t)3 * ((p + 31) / 32)));
-        HIPT(dmalloc(&s->cov_fcols, (size_t)s->capA + 4 * COV_R));
-        HIPT(dmalloc(&s->cov_extras, (size_t)2 * COV_R));
+        HIPT(s->own.alloc(&s->cov_part, (size_t)COV_SLOT_GROUPS * ns * njg * cov_streamed_tiles_per_wave() * 2 * 256));
+        HIPT(s->own.alloc(&s->bd2, (size_t)p));
+        HIPT(s->own.zeros(&s->inA, (size_t)p));
+        HIPT(s->own.alloc(&s->cov_bmm, (size_t)3 * ((p + 31) / 32)));
+        HIPT(s->own.alloc(&s->cov_fcols, (size_t)s->capA + 4 * COV_R));
+        HIPT(s->own.alloc(&s->cov_extras, (size_t)2 * COV_R));
         TRY(alloc_cov_cache(s));
         HIPT(cov_panel_prepare());
         if (const char *ev = test_hook("cov_solver")) s->cov_cg = std::string(ev) != "chol";
@@ -1409,7 +1227,7 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
       }
     }
   }
-  HIPT(dmalloc(&s->idcols, (size_t)capA + 16));
+  HIPT(s->own.alloc(&s->idcols, (size_t)capA + 16));
   if (s->model_type == 4) HIPT(cox_alloc(s));
   if (s->model_type == 1) {
     // group_XTX of the all-rows set (X^T y, diag(X^T X): one pass over X, src/path.cpp:37).  The session needs it for
@@ -1431,7 +1249,7 @@ static int fetch_device_vector(const char *what, const void *data, int dtype, lo
   if (int rc = check_device_matrix(what, data, dtype, stride, 0, n, 1, &dev)) return rc;
   if (dev != device) return fail(BESSX_ERR_ARG, std::string(what) + ": memory of another device than the session's");
   const long long ld = ((long long)n + 127) / 128 * 128;
-  Scratch sc;
+  Owner sc;
   double *d = nullptr;
   unsigned *flag = nullptr;
   HIPX(sc.alloc(&d, (size_t)ld));
@@ -1495,7 +1313,7 @@ int bessx_session_create_device(bessx_session **out, const bessx_problem *pb, co
   dx.rs = in->x_row_stride;
   dx.cs = in->x_col_stride;
   dx.stream = caller;
-  Scratch sc;
+  Owner sc;
   if (in->row_order) {
     int *od = nullptr;
     HIPX(sc.alloc(&od, (size_t)n));
@@ -1507,49 +1325,20 @@ int bessx_session_create_device(bessx_session **out, const bessx_problem *pb, co
 
 void bessx_session_destroy(bessx_session *s) { session_free(s); }
 
-// Free everything bessx_session_set_cv allocated for the folds (row sets 1..K); every vector is walked by its own
-// length, so this is safe on the partly built state an allocation failure leaves behind.
+// Back to the no-CV state: everything bessx_session_set_cv allocated for the folds (row sets 1..K) goes with its owner.
 static void drop_folds(bessx_session *s) {
   drop_fold_contexts(s);
-  auto drop = [](std::vector<double *> &v) {
-    for (size_t i = 1; i < v.size(); i++) (void)hipFree(v[i]);
-    if (!v.empty()) v.resize(1);
-  };
-  drop(s->mask);
-  drop(s->xtx);
-  drop(s->xty);
-  drop(s->part_rs);
-  drop(s->r_rs);
-  drop(s->part2_rs);
-  drop(s->h_rs);
-  drop(s->gxtx_rs);
-  drop(s->geig_v_rs);
-  drop(s->geig_l_rs);
+  s->cv_own.release();
+  for (auto *v : {&s->mask, &s->xtx, &s->xty, &s->part_rs, &s->r_rs, &s->part2_rs, &s->h_rs, &s->gxtx_rs, &s->geig_v_rs,
+                  &s->geig_l_rs})
+    if (v->size() > 1) v->resize(1);
   if (s->geig_valid.size() > 1) s->geig_valid.resize(1);
   if (s->geig_lambda.size() > 1) s->geig_lambda.resize(1);
-  for (size_t i = 1; i < s->gcache.size(); i++) {
-    (void)hipFree(s->gcache[i].g0);
-    (void)hipFree(s->gcache[i].g1);
-    (void)hipFree(s->gcache[i].A);
-    (void)hipFree(s->gcache[i].meta);
-  }
-  if (!s->gcache.empty()) s->gcache.resize(1);
-  (void)hipFree(s->Xp);
-  (void)hipFree(s->zp);
-  (void)hipFree(s->cvp_part);
+  if (s->gcache.size() > 1) s->gcache.resize(1);
+  if (s->cov.size() > 1) s->cov.resize(1);
+  if (s->n_train.size() > 1) s->n_train.resize(1);
   s->Xp = s->zp = s->cvp_part = nullptr;
   s->cv_shared = false;
-  for (size_t i = 1; i < s->cov.size(); i++) {
-    (void)hipFree(s->cov[i].G);
-    if (!s->cov[i].shares_map) {
-      (void)hipFree(s->cov[i].slot_of);
-      (void)hipFree(s->cov[i].meta);
-    }
-    (void)hipFree(s->cov[i].GS);
-    (void)hipFree(s->cov[i].zero);
-  }
-  if (!s->cov.empty()) s->cov.resize(1);
-  if (!s->n_train.empty()) s->n_train.resize(1);
   s->n_test.clear();
   s->cv_init.clear();
   s->cv_fold.clear();
@@ -1560,18 +1349,16 @@ static void drop_folds(bessx_session *s) {
 // that borrows its data and caches and owns the state a fit writes.  Same capacities as the parent, so every enqueue
 // function of the covariance form works on it unchanged.
 static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out, bool own_queue_ok = true) {
-  bessx_session *c = new bessx_session(*ps);
+  bessx_session *c = new bessx_session(*ps);  // (its owners start empty: every pointer copied here is borrowed)
+  // what a context starts over because it is STATE of the parent, not a buffer
   c->parent = ps;
   c->fold_pool = nullptr;
   c->fold_ctx.clear();
-  c->fill_ctrl = c->fill_ctrl_h = nullptr;
-  c->ev_fill = c->ev_ctx = nullptr;
-  c->ev_pool.clear();
+  c->ev_pool.clear();  // (the parent's timing events: a context records into its own)
   c->ev_used = 0;
   c->timing = false;
   c->trace = Trace();
   c->cov_timed.clear();
-  c->cox_allocs.clear();
   c->publish = false;  // results by an asynchronous copy of the block: the driver waits for all chains at once
   c->chain = false;
   c->defer_pub = false;
@@ -1588,19 +1375,8 @@ static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out, bool 
   c->cov_cg_fallbacks = c->cov_tie_rescues = c->cov_panel_groups = 0;
   c->chain_queued = c->chain_hits = c->chain_dead = c->chain_mismatch = 0;
   c->dbg_waits = c->dbg_waits_ready = 0;
-  c->pub_flag = nullptr;  // (allocated below: the chains hand their result blocks over by k_publish)
   c->pub_seq = 0;
-  c->snap[0] = c->snap[1] = nullptr;
-  c->res_buf[0] = c->res_buf[1] = nullptr;
-  c->res_h = nullptr;
-  c->stage_h = nullptr;
   c->st = nullptr;
-  // owned device buffers: cleared first so that a failure half way frees only what this function allocated
-  c->resblk = nullptr;
-  c->bd = c->bd2 = c->beta_dense = c->cov_bmm = c->sol = c->fb_work = c->hist_beta = c->hist_coef0 = c->Gt = nullptr;
-  c->init_val_d = c->rdiag = c->zbig = nullptr;
-  c->inA = nullptr;
-  c->A_new = c->cand = c->tie_buf = c->hist = c->init_idx_d = c->cov_fcols = c->cov_extras = nullptr;
   const int p = ps->p, capA = ps->capA, mt_max = capA / 16;
   hipError_t e = hipSuccess;
   {
@@ -1619,49 +1395,47 @@ static int fold_ctx_create(bessx_session *ps, int rs, bessx_session **out, bool 
     }
     c->own_hw_queue = own_queue;
   }
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->resblk), ps->res_bytes);
-  if (e == hipSuccess) e = hipMemset(c->resblk, 0, ps->res_bytes);
+  Owner &own = c->own;
+  if (e == hipSuccess) e = own.zeros(&c->resblk, ps->res_bytes);
   if (e == hipSuccess) {
     c->ctrl = reinterpret_cast<FitCtrl *>(c->resblk + ((unsigned char *)ps->ctrl - ps->resblk));
     c->sse = reinterpret_cast<double *>(c->resblk + ((unsigned char *)ps->sse - ps->resblk));
     c->b_cur = reinterpret_cast<double *>(c->resblk + ((unsigned char *)ps->b_cur - ps->resblk));
     c->A_cur = reinterpret_cast<int *>(c->resblk + ((unsigned char *)ps->A_cur - ps->resblk));
-    e = hipHostMalloc(reinterpret_cast<void **>(&c->res_buf[0]), ps->res_bytes);
+    e = own.pinned(&c->res_buf[0], ps->res_bytes);
   }
   if (e == hipSuccess) {
     std::memset(c->res_buf[0], 0, ps->res_bytes);
     c->res_h = c->res_buf[0];
-    e = hipHostMalloc(reinterpret_cast<void **>(&c->stage_h), (size_t)capA * (sizeof(int) + sizeof(double)));
+    e = own.pinned(&c->stage_h, (size_t)capA * (sizeof(int) + sizeof(double)));
   }
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->pub_flag), 128);
+  if (e == hipSuccess) e = own.pinned(&c->pub_flag, 128 / sizeof(unsigned long long));
   if (e == hipSuccess) c->pub_flag[0] = c->pub_flag[8] = 0ull;
-  if (e == hipSuccess) e = dmalloc(&c->bd, (size_t)p);
-  if (e == hipSuccess) e = dmalloc(&c->bd2, (size_t)p);
-  if (e == hipSuccess) e = dmalloc(&c->beta_dense, (size_t)p);
-  if (e == hipSuccess) e = hipMemset(c->beta_dense, 0, (size_t)p * sizeof(double));
-  if (e == hipSuccess) e = dmalloc(&c->inA, (size_t)p);
-  if (e == hipSuccess) e = hipMemset(c->inA, 0, (size_t)p);
-  if (e == hipSuccess) e = dmalloc(&c->cov_bmm, (size_t)3 * ((p + 31) / 32));
-  if (e == hipSuccess) e = dmalloc(&c->sol, (size_t)capA);
-  if (e == hipSuccess) e = dmalloc(&c->A_new, (size_t)capA);
-  if (e == hipSuccess) e = dmalloc(&c->rdiag, (size_t)capA);
-  if (e == hipSuccess) e = dmalloc(&c->zbig, (size_t)capA);
-  if (e == hipSuccess) e = dmalloc(&c->cand, 32768);
-  if (e == hipSuccess) e = dmalloc(&c->fb_work, CHOL_FB_DOUBLES);
-  if (e == hipSuccess) e = dmalloc(&c->tie_buf, (size_t)3 * p + 8);
+  if (e == hipSuccess) e = own.alloc(&c->bd, (size_t)p);
+  if (e == hipSuccess) e = own.alloc(&c->bd2, (size_t)p);
+  if (e == hipSuccess) e = own.zeros(&c->beta_dense, (size_t)p);
+  if (e == hipSuccess) e = own.zeros(&c->inA, (size_t)p);
+  if (e == hipSuccess) e = own.alloc(&c->cov_bmm, (size_t)3 * ((p + 31) / 32));
+  if (e == hipSuccess) e = own.alloc(&c->sol, (size_t)capA);
+  if (e == hipSuccess) e = own.alloc(&c->A_new, (size_t)capA);
+  if (e == hipSuccess) e = own.alloc(&c->rdiag, (size_t)capA);
+  if (e == hipSuccess) e = own.alloc(&c->zbig, (size_t)capA);
+  if (e == hipSuccess) e = own.alloc(&c->cand, 32768);
+  if (e == hipSuccess) e = own.alloc(&c->fb_work, CHOL_FB_DOUBLES);
+  if (e == hipSuccess) e = own.alloc(&c->tie_buf, (size_t)3 * p + 8);
   if (e == hipSuccess) e = hipMemset(c->tie_buf, 0, 8 * sizeof(int));
   if (e == hipSuccess) c->tie = TopkTie{c->tie_buf, c->tie_buf + 8};
-  if (e == hipSuccess) e = dmalloc(&c->hist, (size_t)(ps->max_iter + 2) * ps->hist_stride);
-  if (e == hipSuccess) e = dmalloc(&c->hist_beta, (size_t)(ps->max_iter + 2) * ps->hist_stride);
-  if (e == hipSuccess) e = dmalloc(&c->hist_coef0, (size_t)(ps->max_iter + 2));
-  if (e == hipSuccess) e = dmalloc(&c->init_idx_d, (size_t)capA);
-  if (e == hipSuccess) e = dmalloc(&c->init_val_d, (size_t)capA);
-  if (e == hipSuccess) e = dmalloc(&c->Gt, (size_t)mt_max * (mt_max + 1) / 2 * 256);
-  if (e == hipSuccess) e = dmalloc(&c->cov_fcols, (size_t)capA + 4 * COV_R);
-  if (e == hipSuccess) e = dmalloc(&c->cov_extras, (size_t)2 * COV_R);
+  if (e == hipSuccess) e = own.alloc(&c->hist, (size_t)(ps->max_iter + 2) * ps->hist_stride);
+  if (e == hipSuccess) e = own.alloc(&c->hist_beta, (size_t)(ps->max_iter + 2) * ps->hist_stride);
+  if (e == hipSuccess) e = own.alloc(&c->hist_coef0, (size_t)(ps->max_iter + 2));
+  if (e == hipSuccess) e = own.alloc(&c->init_idx_d, (size_t)capA);
+  if (e == hipSuccess) e = own.alloc(&c->init_val_d, (size_t)capA);
+  if (e == hipSuccess) e = own.alloc(&c->Gt, (size_t)mt_max * (mt_max + 1) / 2 * 256);
+  if (e == hipSuccess) e = own.alloc(&c->cov_fcols, (size_t)capA + 4 * COV_R);
+  if (e == hipSuccess) e = own.alloc(&c->cov_extras, (size_t)2 * COV_R);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    fold_ctx_free(c);
+    ctx_free(c);
     return fail(BESSX_ERR_HIP, std::string("fold context: ") + hipGetErrorString(e));
   }
   *out = c;
@@ -1689,89 +1463,49 @@ int chain_ctx_create(bessx_session *ps, bessx_session **out, bool own_queue) {
   c->defer_pub = ps->defer_pub;
   c->cov_no_restart = true;  // (the cache holds every column: never needed; and nobody rewrites the map under the others)
   c->fill_hook = nullptr;
-  c->tmpv = nullptr;
-  c->part_rs[0] = nullptr;
-  c->r_rs[0] = nullptr;
-  hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&c->res_buf[1]), ps->res_bytes);
+  Owner &own = c->own;
+  const size_t ld = (size_t)ps->ld, capA16 = (size_t)ps->capA + 16;
+  hipError_t e = own.pinned(&c->res_buf[1], ps->res_bytes);
   if (e == hipSuccess) std::memset(c->res_buf[1], 0, ps->res_bytes);
-  for (int b = 0; b < 2 && e == hipSuccess; b++) {
-    e = hipMalloc(reinterpret_cast<void **>(&c->snap[b]), ps->res_bytes + 64);
-    if (e == hipSuccess) e = hipMemset(c->snap[b], 0, ps->res_bytes + 64);
-  }
-  if (e == hipSuccess) e = dmalloc(&c->tmpv, (size_t)ps->ld);
-  if (e == hipSuccess) e = dmalloc(&c->part_rs[0], part_elems(ps));
-  if (e == hipSuccess) e = dmalloc(&c->r_rs[0], (size_t)ps->ld);
-  if (e == hipSuccess) e = hipMemset(c->r_rs[0], 0, (size_t)ps->ld * sizeof(double));
+  for (int b = 0; b < 2 && e == hipSuccess; b++) e = own.zeros(&c->snap[b], ps->res_bytes + 64);
+  if (e == hipSuccess) e = own.alloc(&c->tmpv, ld);
+  if (e == hipSuccess) e = own.alloc(&c->part_rs[0], part_elems(ps));
+  if (e == hipSuccess) e = own.zeros(&c->r_rs[0], ld);
   if (e == hipSuccess && ps->model_type == 1 && !ps->cov_mode) {
     // LM in the streaming form of the score pass (round 5): what enqueue_lm_slot writes besides -- the column list and
     // the slab partials of the Gram kernels, the incremental Gram's row buffer and source map, and the Gram cache of
     // the all-rows row set (two 256 x 256 buffers, the cached column list, its meta words)
-    c->ctx_allocs.clear();
-    auto own_d = [&](double **dst, size_t count) -> hipError_t {
-      *dst = nullptr;
-      hipError_t q = dmalloc(dst, count);
-      if (q != hipSuccess) return q;
-      c->ctx_allocs.push_back(*dst);
-      return hipMemset(*dst, 0, count * sizeof(double));
-    };
-    auto own_n = [&](int **dst, size_t count) -> hipError_t {
-      *dst = nullptr;
-      hipError_t q = dmalloc(dst, count);
-      if (q != hipSuccess) return q;
-      c->ctx_allocs.push_back(*dst);
-      return hipMemset(*dst, 0, count * sizeof(int));
-    };
-    e = own_d(&c->gpart, ps->gpart_elems);
-    if (e == hipSuccess) e = own_n(&c->gcols, (size_t)ps->capA + 16);
-    if (e == hipSuccess) e = own_d(&c->Rt, (size_t)16 * 256);
-    if (e == hipSuccess) e = own_n(&c->gsrc, 256);
+    e = own.zeros(&c->gpart, ps->gpart_elems);
+    if (e == hipSuccess) e = own.zeros(&c->gcols, capA16);
+    if (e == hipSuccess) e = own.zeros(&c->Rt, (size_t)16 * 256);
+    if (e == hipSuccess) e = own.zeros(&c->gsrc, 256);
     if (e == hipSuccess && !c->gcache.empty()) {
       bessx_session::GramCache g;
-      e = own_d(&g.g0, (size_t)256 * 256);
-      if (e == hipSuccess) e = own_d(&g.g1, (size_t)256 * 256);
-      if (e == hipSuccess) e = own_n(&g.A, 256);
-      if (e == hipSuccess) e = own_n(&g.meta, 2);
+      e = own.zeros(&g.g0, (size_t)256 * 256);
+      if (e == hipSuccess) e = own.zeros(&g.g1, (size_t)256 * 256);
+      if (e == hipSuccess) e = own.zeros(&g.A, 256);
+      if (e == hipSuccess) e = own.zeros(&g.meta, 2);
       if (e == hipSuccess) c->gcache[0] = g;
     }
   }
   if (e == hipSuccess && ps->model_type != 1) {
     // the IRLS / Newton families: what their fits write besides -- curvature sums and weights, the IRLS vectors, the
     // auxiliary columns (column 2 is the working response), the slab partials and column lists of the Gram kernels
-    c->ctx_allocs.clear();
-    auto own = [&](double **dst, size_t count, const double *copy_of) -> hipError_t {
-      *dst = nullptr;
-      hipError_t q = dmalloc(dst, count);
-      if (q != hipSuccess) return q;
-      c->ctx_allocs.push_back(*dst);
-      return copy_of ? hipMemcpy(*dst, copy_of, count * sizeof(double), hipMemcpyDeviceToDevice)
-                     : hipMemset(*dst, 0, count * sizeof(double));
-    };
-    auto own_i = [&](int **dst, size_t count) -> hipError_t {
-      *dst = nullptr;
-      hipError_t q = dmalloc(dst, count);
-      if (q != hipSuccess) return q;
-      c->ctx_allocs.push_back(*dst);
-      return hipMemset(*dst, 0, count * sizeof(int));
-    };
-    const size_t ld = (size_t)ps->ld;
-    e = own(&c->part2_rs[0], (size_t)ps->nrb * ps->p, nullptr);
-    if (e == hipSuccess) e = own(&c->h_rs[0], ld, nullptr);
-    if (e == hipSuccess) e = own(&c->Wv, ld, nullptr);
-    if (e == hipSuccess) e = own(&c->llpart, ps->llpart_cap, nullptr);
-    if (e == hipSuccess) e = own(&c->bcur, (size_t)ps->capA + 16, nullptr);
-    if (e == hipSuccess) e = own(&c->bprev, (size_t)ps->capA + 16, nullptr);
-    if (e == hipSuccess) e = own(&c->aux, 3 * ld, ps->aux);
-    if (e == hipSuccess) e = own(&c->gpart, ps->gpart_elems, nullptr);
-    if (e == hipSuccess) e = own_i(&c->gcols, (size_t)ps->capA + 16);
-    if (e == hipSuccess) e = own_i(&c->idcols, (size_t)ps->capA + 16);
-    if (e == hipSuccess && ps->idcols)
-      e = hipMemcpy(c->idcols, ps->idcols, ((size_t)ps->capA + 16) * sizeof(int), hipMemcpyDeviceToDevice);
+    e = own.zeros(&c->part2_rs[0], (size_t)ps->nrb * ps->p);
+    if (e == hipSuccess) e = own.zeros(&c->h_rs[0], ld);
+    if (e == hipSuccess) e = own.zeros(&c->Wv, ld);
+    if (e == hipSuccess) e = own.zeros(&c->llpart, ps->llpart_cap);
+    if (e == hipSuccess) e = own.zeros(&c->bcur, capA16);
+    if (e == hipSuccess) e = own.zeros(&c->bprev, capA16);
+    if (e == hipSuccess) e = own.copy_of(&c->aux, 3 * ld, ps->aux);
+    if (e == hipSuccess) e = own.zeros(&c->gpart, ps->gpart_elems);
+    if (e == hipSuccess) e = own.zeros(&c->gcols, capA16);
+    if (e == hipSuccess) e = ps->idcols ? own.copy_of(&c->idcols, capA16, ps->idcols) : own.zeros(&c->idcols, capA16);
     if (e == hipSuccess && ps->model_type == 4) {
       CoxBufs keep = ps->cox;
       c->cox = CoxBufs();
       c->cox.one_pass = keep.one_pass;
       c->cox.need_uv = keep.need_uv;
-      c->cox_allocs.clear();
       e = cox_alloc(c);  // (sets hess_fused / fit_clamp as the session's creation did)
       c->cox.hess_fused = c->cox.hess_fused && keep.hess_fused;
       c->cox.fit_clamp = keep.fit_clamp;
@@ -1780,32 +1514,13 @@ int chain_ctx_create(bessx_session *ps, bessx_session **out, bool own_queue) {
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    chain_ctx_free(c);
+    ctx_free(c);
     return fail(BESSX_ERR_HIP, std::string("chunk chain context: ") + hipGetErrorString(e));
   }
   *out = c;
   return 0;
 }
 
-void chain_ctx_free(bessx_session *c) {
-  if (!c) return;
-  if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->kch_ev) (void)hipEventDestroy(c->kch_ev);
-  c->kch_ev = nullptr;
-  if (c->res_buf[1]) (void)hipHostFree(c->res_buf[1]);
-  for (int b = 0; b < 2; b++)
-    if (c->snap[b]) (void)hipFree(c->snap[b]);
-  if (c->tmpv) (void)hipFree(c->tmpv);
-  if (c->part_rs[0]) (void)hipFree(c->part_rs[0]);
-  if (c->r_rs[0]) (void)hipFree(c->r_rs[0]);
-  for (void *q : c->ctx_allocs) (void)hipFree(q);
-  for (void *q : c->cox_allocs) (void)hipFree(q);
-  c->ctx_allocs.clear();
-  c->cox_allocs.clear();
-  c->res_buf[1] = nullptr;
-  c->snap[0] = c->snap[1] = nullptr;
-  fold_ctx_free(c);
-}
 }  // namespace bessx
 extern "C" {
 
@@ -1856,15 +1571,13 @@ int bessx_session_set_cv(bessx_session *s, int K, const int *fold_id, unsigned s
     sh_ldp = (long)sh_nsl * sh_rps * K;
     const int pt = (p + 15) / 16, njg = (pt + cov_streamed_tiles_per_wave() - 1) / cov_streamed_tiles_per_wave();
     hipError_t e = sh_ldp * 2 > s->ld * 3 ? hipErrorOutOfMemory : hipSuccess;  // more than 1.5 x the rows of X
-    if (e == hipSuccess) e = dmalloc(&s->Xp, (size_t)sh_ldp * p);
-    if (e == hipSuccess) e = dmalloc(&s->zp, (size_t)sh_ldp);
+    if (e == hipSuccess) e = s->cv_own.alloc(&s->Xp, (size_t)sh_ldp * p);
+    if (e == hipSuccess) e = s->cv_own.alloc(&s->zp, (size_t)sh_ldp);
     if (e == hipSuccess)
-      e = dmalloc(&s->cvp_part, (size_t)COV_SLOT_GROUPS * K * sh_nsl * njg * cov_streamed_tiles_per_wave() * 2 * 256);
+      e = s->cv_own.alloc(&s->cvp_part, (size_t)COV_SLOT_GROUPS * K * sh_nsl * njg * cov_streamed_tiles_per_wave() * 2 * 256);
     if (e != hipSuccess) {
       (void)hipGetLastError();  // (an allocation failure is not an error of this call)
-      (void)hipFree(s->Xp);
-      (void)hipFree(s->zp);
-      (void)hipFree(s->cvp_part);
+      for (double *q : {s->Xp, s->zp, s->cvp_part}) s->cv_own.release_one(q);
       s->Xp = s->zp = s->cvp_part = nullptr;
       share = false;
     }
@@ -1884,8 +1597,7 @@ int bessx_session_set_cv(bessx_session *s, int K, const int *fold_id, unsigned s
       drop_folds(s);
       return fail(BESSX_ERR_ARG, "set_cv: empty train or test fold");
     }
-    // every buffer is handed to its vector as soon as it exists: a failure further down leaves nothing unowned, and
-    // drop_folds() (which walks every vector by its own length) returns the session to the no-CV state
+    // a failure further down: drop_folds() returns the session to the no-CV state
 #define CVX(expr)                                                                            \
   do {                                                                                       \
     hipError_t e__ = (expr);                                                                 \
@@ -1896,10 +1608,9 @@ int bessx_session_set_cv(bessx_session *s, int K, const int *fold_id, unsigned s
   } while (0)
     auto grow = [&](std::vector<double *> &v, size_t count, bool zero) -> hipError_t {
       double *q = nullptr;
-      hipError_t e = dmalloc(&q, count);
-      if (e != hipSuccess) return e;
-      v.push_back(q);
-      return zero ? hipMemset(q, 0, count * sizeof(double)) : hipSuccess;
+      hipError_t e = zero ? s->cv_own.zeros(&q, count) : s->cv_own.alloc(&q, count);
+      if (e == hipSuccess) v.push_back(q);
+      return e;
     };
     CVX(grow(s->mask, (size_t)s->ld, false));
     CVX(hipMemcpy(s->mask.back(), m.data(), (size_t)s->ld * sizeof(double), hipMemcpyHostToDevice));
@@ -1929,13 +1640,14 @@ int bessx_session_set_cv(bessx_session *s, int K, const int *fold_id, unsigned s
     const long seg = (long)sh_nsl * sh_rps, ldp = sh_ldp;
     std::vector<int> perm((size_t)ldp, -1), fill((size_t)K, 0);
     for (int i = 0; i < n; i++) perm[(size_t)fold[i] * seg + fill[fold[i]]++] = i;
+    Owner tmp;
     int *dperm = nullptr;
-    hipError_t e = dmalloc(&dperm, (size_t)ldp);
+    hipError_t e = tmp.alloc(&dperm, (size_t)ldp);
     if (e == hipSuccess) e = hipMemcpy(dperm, perm.data(), (size_t)ldp * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemsetAsync(s->zp, 0, (size_t)ldp * sizeof(double), s->st);
     if (e == hipSuccess) e = launch_rows_permute(s->X, s->ld, p, dperm, ldp, s->Xp, s->st);
     if (e == hipSuccess) e = hipStreamSynchronize(s->st);
-    (void)hipFree(dperm);
+    tmp.release();
     if (e != hipSuccess) {
       drop_folds(s);
       return fail(BESSX_ERR_HIP, std::string("set_cv (fold-major copy): ") + hipGetErrorString(e));
@@ -1954,11 +1666,10 @@ int bessx_session_set_cv(bessx_session *s, int K, const int *fold_id, unsigned s
     bool sbs = s->cv_side_by_side && K <= 8 && s->publish && s->fuse && s->cov_cg && s->cg_by_rows && s->fuse_sel;
     if (const char *ev = test_hook("cv_side_by_side")) sbs = sbs && std::string(ev) != "0";
     if (sbs) {
-      hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->fill_ctrl), sizeof(FitCtrl));
-      if (e == hipSuccess) e = hipMemset(s->fill_ctrl, 0, sizeof(FitCtrl));
-      if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s->fill_ctrl_h), sizeof(FitCtrl));
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fill, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_ctx, hipEventDisableTiming);
+      hipError_t e = s->cv_own.zeros(&s->fill_ctrl, 1);
+      if (e == hipSuccess) e = s->cv_own.pinned(&s->fill_ctrl_h, 1);
+      if (e == hipSuccess) e = s->cv_own.event(&s->ev_fill, hipEventDisableTiming);
+      if (e == hipSuccess) e = s->cv_own.event(&s->ev_ctx, hipEventDisableTiming);
       for (int k = 0; k < K && e == hipSuccess; k++) {
         bessx_session *c = nullptr;
         if (fold_ctx_create(s, k + 1, &c) != 0) {
@@ -2141,6 +1852,9 @@ long long bessx_session_counter(const bessx_session *s, int which) {
     case 35: return s->multi_fills;
     case 36: return s->x_host_bytes;
     case 37: return s->x_dev_bytes;
+    case 38: return Ledger::device_bytes.load();  // (38-40: process-wide, like 32)
+    case 39: return Ledger::pinned_bytes.load();
+    case 40: return Ledger::requests.load();  // (what BESSX_TEST_HOOKS=alloc_fail=N counts)
     case 10: {  // times the Gram column cache of the all-rows row set was started over since the last path started
       if (s->cov.empty()) return 0;
       int m[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -236,7 +236,10 @@ int bessx_session_score_mode(const bessx_session *s);
  * engine, 34 responses or parts of responses the host finished through the ordinary path (takeovers, and every response
  * of a path the engine does not apply to), 35 union fills served during merged runs of responses; 36 bytes of X
  * uploaded from host memory, 37 bytes of X ingested from device memory (source bytes, n * p * element size; a
- * session of bessx_session_create_device reports 0 for 36).  -1 for an unknown id. */
+ * session of bessx_session_create_device reports 0 for 36); 38 / 39 bytes of device / pinned host memory the library
+ * holds right now in the whole PROCESS (every session, context and drop-in call: what its allocations handed out and
+ * have not given back -- back at its earlier value once a session is destroyed), 40 allocation requests the library has
+ * made in the process so far (device buffers, pinned buffers, events).  -1 for an unknown id. */
 long long bessx_session_counter(const bessx_session *s, int which);
 
 /* Metric::set_cv_train_test_mask + cal_cv_group_XTX (src/Metric.h:49-129).  fold_id[i] in [0,K)
