@@ -5,6 +5,7 @@ NumPy fallback -- if the library is missing or no GPU is visible the call raises
 """
 import ctypes
 import os
+import sys
 
 import numpy as np
 
@@ -35,7 +36,7 @@ SYMBOLS = [
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
-    "bessx_op_ingest_bench",
+    "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -174,6 +175,8 @@ def lib():
             + [_D, _i, _D, _i, _D, _i, _D, _i, _D, _D, _i, _D, _i, _D, _i, _I, _i, _I, _I])
         L.bessx_op_ingest.argtypes = [_vp, _i, _ll, _ll, _I, _i, _i, _ll, _vp, _D, _I]
         L.bessx_op_ingest_bench.argtypes = [_vp, _i, _ll, _ll, _I, _i, _i, _ll, _i, _D, _D]
+        L.bessx_predict_device.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _D, _D, _i, _i, _vp, _ll, _ll, _vp, _i, _vp]
+        L.bessx_op_predict_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -932,6 +935,95 @@ def op_ingest_bench(x, row_order=None, repeats=20):
     ms, g = _d(0), _d(0)
     _check(lib().bessx_op_ingest_bench(dx.ptr, dx.dtype, rs, cs, _ip(ro), n, p, padded_rows(n), repeats,
                                        ctypes.byref(ms), ctypes.byref(g)))
+    return ms.value, g.value
+
+
+LINKS = {"identity": 0, "logistic": 1, "poisson": 2}  # BESSX_LINK_*
+
+
+def _predict_model(dx, cols, B=None, coef0=None):
+    """(cols int32, B float64 (m, R) or None, coef0 float64 (R,) or None) of a model for the device matrix dx, checked."""
+    p = dx.shape[1]
+    cols = _i32(cols).reshape(-1)
+    if cols.size and (cols.min() < 0 or cols.max() >= p):
+        raise ValueError("cols: column numbers must lie in [0, %d)" % p)
+    if cols.size > 1 and (np.diff(cols) <= 0).any():
+        raise ValueError("cols must be ascending and distinct")
+    if B is None:
+        return cols, None, None
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 1:
+        B = B.reshape(-1, 1)
+    if B.ndim != 2 or B.shape[0] != cols.size or B.shape[1] < 1:
+        raise ValueError("B must have shape (len(cols), R) = (%d, R) with R >= 1, got %s" % (cols.size, B.shape))
+    coef0 = _f64(coef0).reshape(-1)
+    if coef0.size != B.shape[1]:
+        raise ValueError("coef0 must have one entry per response (%d), got %d" % (B.shape[1], coef0.size))
+    return cols, np.ascontiguousarray(B), coef0
+
+
+def predict_device(x, cols, B, coef0, link="identity", out=None, stream=0):
+    """Prediction on a device matrix x (n x p: float64 or float32, any non-negative strides) that is read where it lies
+    (bessx_predict_device): link(x[:, cols] @ B + coef0) from the support columns alone.  cols: ascending distinct column
+    numbers (may be empty); B: (len(cols), R) or (len(cols),); coef0: R values; link: "identity", "logistic" or "poisson".
+    Returns the linear predictor (identity), (pr, labels) (logistic) or exp(eta) (poisson), each of shape (n,) when B is
+    1-D, else (n, R).  out: a float64 device array of that shape to write into (for the logistic link a pair of them with
+    equal strides); out=None allocates a torch tensor on x's device when x is a torch tensor (torch is looked up, never
+    imported), and returns NumPy arrays for any other device object.  stream: raw handle of the stream x was produced
+    on; the results are complete when the call returns."""
+    dx = _DeviceArray(x, "x", 2)
+    n = dx.shape[0]
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    one_d = np.ndim(B) == 1
+    cols, B, coef0 = _predict_model(dx, cols, B, coef0)
+    R = B.shape[1]
+    shape = (n,) if one_d else (n, R)
+    two = link == "logistic"
+    outs = None
+    if out is not None:
+        outs = list(out) if two and isinstance(out, (tuple, list)) else [out]
+        if two and len(outs) != 2:
+            raise ValueError("out: the logistic link writes a pair (pr, labels)")
+        douts = []
+        for o in outs:
+            if not is_device_array(o):
+                raise ValueError("out must be a device array")
+            do = _DeviceArray(o, "out")
+            if do.item != 8:
+                raise ValueError("out: a device array of float64 is needed (typestr '<f8')")
+            if do.shape != shape and not (R == 1 and do.shape in ((n,), (n, 1))):
+                raise ValueError("out must have shape %s, got %s" % (shape, do.shape))
+            douts.append(do)
+        if two and douts[0].strides != douts[1].strides:
+            raise ValueError("out: pr and labels must have equal strides")
+        st = douts[0].strides
+        ors, ocs = st[0], (st[1] if len(st) == 2 else 1)
+        ptrs, on_device, result = [d.ptr for d in douts], 1, outs
+    else:
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(x, torch.Tensor):
+            result = [torch.empty(shape, dtype=torch.float64, device=x.device) for _ in range(2 if two else 1)]
+            ptrs, on_device = [int(t.data_ptr()) for t in result], 1
+        else:
+            result = [np.empty(shape) for _ in range(2 if two else 1)]
+            ptrs, on_device = [int(a.ctypes.data) for a in result], 0
+        ors, ocs = R, 1
+    _check(lib().bessx_predict_device(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, dx.shape[1], _ip(cols),
+                                      cols.size, _dp(B), _dp(coef0), R, LINKS[link], ptrs[0], ors, ocs,
+                                      ptrs[1] if two else None, on_device, int(stream) if stream else None))
+    return tuple(result) if two else result[0]
+
+
+def op_predict_bench(x, cols, R=1, link="identity", repeats=20):
+    """(ms per launch, GB/s of n * m * item bytes read + n * R * 8 written) of the prediction kernel on the device
+    matrix x for the support cols and R responses, device events."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms, g = _d(0), _d(0)
+    _check(lib().bessx_op_predict_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                        _ip(cols), cols.size, int(R), LINKS[link], repeats, ctypes.byref(ms),
+                                        ctypes.byref(g)))
     return ms.value, g.value
 
 

@@ -764,3 +764,159 @@ int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long l
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// prediction on a caller's device matrix (include/bessx.h section 2c)
+// ----------------------------------------------------------------------------------------------
+static_assert((int)BESSX_LINK_IDENTITY == (int)PREDICT_IDENTITY && (int)BESSX_LINK_LOGISTIC == (int)PREDICT_LOGISTIC &&
+                  (int)BESSX_LINK_POISSON == (int)PREDICT_POISSON, "link codes of the launcher");
+
+// everything about a model that needs no device
+static int predict_check_model(const char *who, int n, int p, const int *cols, int m, int R, int link) {
+  const std::string w(who);
+  if (n < 1 || p < 1) return fail(BESSX_ERR_ARG, w + ": empty matrix");
+  if (R < 1) return fail(BESSX_ERR_ARG, w + ": R must be at least 1");
+  if (link != BESSX_LINK_IDENTITY && link != BESSX_LINK_LOGISTIC && link != BESSX_LINK_POISSON)
+    return fail(BESSX_ERR_ARG, w + ": unknown link");
+  if (m < 0 || m > p) return fail(BESSX_ERR_ARG, w + ": m must lie in [0, p]");
+  if (m > 0 && !cols) return fail(BESSX_ERR_ARG, w + ": null argument (cols)");
+  for (int k = 0; k < m; k++) {
+    if (cols[k] < 0 || cols[k] >= p) return fail(BESSX_ERR_ARG, w + ": column number out of range");
+    if (k > 0 && cols[k] <= cols[k - 1]) return fail(BESSX_ERR_ARG, w + ": cols must be ascending and distinct");
+  }
+  return 0;
+}
+
+// the model in one device allocation of `sc`: cols, then B, then coef0 (queued on st; the host arrays must outlive it)
+static int predict_upload_model(Owner &sc, const int *cols, int m, const double *B, const double *coef0, int R,
+                                hipStream_t st, int **cols_d, double **B_d, double **c_d) {
+  HIPX(sc.alloc(B_d, (size_t)m * R + (size_t)R));
+  HIPX(sc.alloc(cols_d, (size_t)m));
+  *c_d = *B_d + (size_t)m * R;
+  if (m > 0) {
+    HIPX(hipMemcpyAsync(*cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(*B_d, B, (size_t)m * R * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  HIPX(hipMemcpyAsync(*c_d, coef0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+static int predict_run(const void *x, int f32, long long rs, long long cs, int n, const int *cols, int m,
+                       const double *B, const double *coef0, int R, int link, double *out, long long ors,
+                       long long ocs, double *out2, int out_on_device, hipStream_t caller, hipStream_t st) {
+  Owner sc;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *stage = nullptr;
+  // reads and writes come after everything the caller has queued on its stream so far
+  hipEvent_t ev = nullptr;
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, caller));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  if (int rc = predict_upload_model(sc, cols, m, B, coef0, R, st, &cols_d, &B_d, &c_d)) return rc;
+  const bool two = link == BESSX_LINK_LOGISTIC;
+  const size_t cnt = (size_t)n * R;
+  if (out_on_device) {
+    HIPX(launch_predict(x, f32, rs, cs, n, cols_d, m, B_d, c_d, R, link, out, ors, ocs, out2, st));
+    HIPX(hipStreamSynchronize(st));
+    return 0;
+  }
+  HIPX(sc.alloc(&stage, cnt * (two ? 2 : 1)));
+  HIPX(launch_predict(x, f32, rs, cs, n, cols_d, m, B_d, c_d, R, link, stage, R, 1, two ? stage + cnt : nullptr, st));
+  const bool dense = ocs == 1 && ors == R;  // (R == 1: any ocs addresses the same elements)
+  std::vector<double> tmp;
+  double *h1 = out, *h2 = out2;
+  if (!(dense || (R == 1 && ors == 1))) {
+    tmp.resize(cnt * (two ? 2 : 1));
+    h1 = tmp.data();
+    h2 = tmp.data() + cnt;
+  }
+  HIPX(hipMemcpyAsync(h1, stage, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (two) HIPX(hipMemcpyAsync(h2, stage + cnt, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  if (!tmp.empty()) {
+    for (long long i = 0; i < n; i++)
+      for (long long r = 0; r < R; r++) {
+        out[i * ors + r * ocs] = h1[i * R + r];
+        if (two) out2[i * ors + r * ocs] = h2[i * R + r];
+      }
+  }
+  return 0;
+}
+
+extern "C" {
+
+int bessx_predict_device(const void *x, int x_dtype, long long x_row_stride, long long x_col_stride, int n, int p,
+                         const int *cols, int m, const double *B, const double *coef0, int R, int link, double *out,
+                         long long out_row_stride, long long out_col_stride, double *out2, int out_on_device,
+                         void *stream) {
+  if (!x || !coef0 || !out) return fail(BESSX_ERR_ARG, "predict_device: null argument");
+  if (x_dtype != BESSX_F64 && x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, "predict_device: x: dtype must be BESSX_F64 or BESSX_F32");
+  if (x_row_stride < 0 || x_col_stride < 0 || out_row_stride < 0 || out_col_stride < 0)
+    return fail(BESSX_ERR_ARG, "predict_device: strides must be non-negative");
+  if (int rc = predict_check_model("predict_device", n, p, cols, m, R, link)) return rc;
+  if (m > 0 && !B) return fail(BESSX_ERR_ARG, "predict_device: null argument (B)");
+  if (link == BESSX_LINK_LOGISTIC && !out2) return fail(BESSX_ERR_ARG, "predict_device: the logistic link needs out2");
+  if ((n > 1 && out_row_stride == 0) || (R > 1 && out_col_stride == 0))
+    return fail(BESSX_ERR_ARG, "predict_device: out: a zero stride along an axis longer than 1");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("predict_device: x", x, x_dtype, x_row_stride, x_col_stride, n, p, &dev)) return rc;
+  if (out_on_device) {
+    int od = -1;
+    if (int rc = check_device_matrix("predict_device: out", out, BESSX_F64, out_row_stride, out_col_stride, n, R, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "predict_device: out is not on the device that owns x");
+    if (link == BESSX_LINK_LOGISTIC) {
+      if (int rc = check_device_matrix("predict_device: out2", out2, BESSX_F64, out_row_stride, out_col_stride, n, R,
+                                       &od))
+        return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "predict_device: out2 is not on the device that owns x");
+    }
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc = predict_run(x, x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, cols, m, B, coef0, R, link, out,
+                       out_row_stride, out_col_stride, out2, out_on_device, static_cast<hipStream_t>(stream), st);
+  if (rc) (void)hipStreamSynchronize(st);  // (nothing queued may outlive the model's buffers)
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                           const int *cols, int m, int R, int link, int repeats, double *avg_ms, double *gbps) {
+  if (!x || repeats < 1 || !avg_ms || !gbps) return fail(BESSX_ERR_ARG, "op_predict_bench: bad arguments");
+  if (int rc = predict_check_model("op_predict_bench", n, p, cols, m, R, link)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_predict_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  std::vector<double> B((size_t)m * R), c0((size_t)R, 0.25);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *out = nullptr;
+  if (int rc = predict_upload_model(sc, cols, m, B.data(), c0.data(), R, nullptr, &cols_d, &B_d, &c_d)) return rc;
+  const size_t cnt = (size_t)n * R;
+  HIPX(sc.alloc(&out, 2 * cnt));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  HIPX(launch_predict(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, out, R, 1, out + cnt, nullptr));
+  HIPX(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < repeats; i++)
+    HIPX(launch_predict(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, out, R, 1, out + cnt, nullptr));
+  HIPX(hipEventRecord(e1, nullptr));
+  HIPX(hipEventSynchronize(e1));
+  float ms = 0.f;
+  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  const double bytes = (double)n * (double)m * (f32 ? 4.0 : 8.0) + (double)cnt * 8.0;
+  *avg_ms = ms / repeats;
+  *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;
+  return BESSX_OK;
+}
+
+}  // extern "C"

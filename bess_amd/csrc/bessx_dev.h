@@ -53,6 +53,13 @@ hipError_t launch_transpose_in(const double *src, int rows, int p, double *X, lo
 // elements, element (i, j) at src[order[i] * rs + j * cs] (order: device, may be null); *nan_flag is set on a NaN
 hipError_t launch_ingest(const void *src, int f32, long long rs, long long cs, const int *order, long long n,
                          long long p, double *X, long long ld, unsigned *nan_flag, hipStream_t st);
+// device prediction (bessx_k_predict.hip): out[i * ors + r * ocs] = link(sum_k src(i, cols[k]) * B[k * R + r] + c[r]) on a
+// device matrix like launch_ingest's; cols (m >= 0, ascending), B (m x R row-major) and c (R) are device arrays.  Only the
+// m support columns are read.  PREDICT_LOGISTIC: out = pr, out2 (same strides) = labels; PREDICT_POISSON: out = exp(eta).
+enum { PREDICT_IDENTITY = 0, PREDICT_LOGISTIC = 1, PREDICT_POISSON = 2 };  // = BESSX_LINK_* of include/bessx.h
+hipError_t launch_predict(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                          const double *B, const double *c, int R, int link, double *out, long long ors, long long ocs,
+                          double *out2, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

@@ -3,6 +3,7 @@
 // own a copy of.  Never part of the product library.
 #include "bessx_k_lm.hip"
 #include "bessx_k_ingest.hip"
+#include "bessx_k_predict.hip"
 #include "bessx_k_solve.hip"
 #include "bessx_k_glm.hip"
 #include "bessx_k_cox.hip"

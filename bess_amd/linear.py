@@ -38,7 +38,8 @@ class bess_base:
 
     fit(X, y) also takes an X in GPU memory (a torch ROCm tensor, or anything with __cuda_array_interface__: float64
     or float32, any strides): the library reads it where it lies, on torch's current stream, and X never crosses the
-    bus.  y and weight may be device arrays too (n values: they are copied to the host).  predict() takes host arrays.
+    bus.  y and weight may be device arrays too (n values: they are copied to the host).  predict(X) takes such an X too: a kernel reads the support's
+    columns of it in place, and the results are torch tensors on X's device when X is one (NumPy arrays otherwise).
     """
 
     def __init__(self, algorithm_type, model_type, path_type, max_iter=20, exchange_num=0, is_warm_start=True,
@@ -214,7 +215,27 @@ class bess_base:
                 coef0[r], loss[r], ic[r] = (float(np.ravel(v)[0]) for v in out[1:4])
         self.beta, self.coef0, self.train_loss, self.ic = beta, coef0, loss, ic
 
+    def _predict_device(self, X):
+        """predict() for an X in GPU memory: only the support's columns of X are read, where they lie."""
+        if capi._DeviceArray(X, "X", 2).shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        if self.model_type_int == 4:
+            return None
+        beta = np.asarray(self.beta, dtype=np.float64)
+        multi = self.model_type_int == 1 and beta.ndim == 2  # (one column per response)
+        cols = np.nonzero(beta.any(axis=1) if multi else beta)[0]  # the union of the supports
+        coef0 = np.asarray(self.coef0, dtype=np.float64).reshape(-1)
+        link = {1: "identity", 2: "logistic", 3: "poisson"}[self.model_type_int]
+        res = capi.predict_device(X, cols, beta[cols], coef0, link=link, stream=_current_stream(X))
+        if self.model_type_int == 2:
+            return {"Y": res[1], "pr": res[0]}
+        if self.model_type_int == 3:
+            return {"lam": res}
+        return res
+
     def predict(self, X):
+        if capi.is_device_array(X):
+            return self._predict_device(X)
         X = np.asarray(X)
         if X.shape[1] != self.p:
             raise ValueError("X.shape[1] should be " + str(self.p))

@@ -203,6 +203,35 @@ int bessx_pywrap_bess_device(const bessx_device_input *in, int x_row, int x_col,
                              int train_loss_out_len, double *ic_out, int ic_out_len, double *nullloss_out,
                              double *aic_out, int aic_out_len, double *bic_out, int bic_out_len, double *gic_out,
                              int gic_out_len, int *A_out, int A_out_len, int *l_out, int *x_nan_out);
+/* ---------------------------------------------------------------------------------------
+ * 2c. Prediction on an X already in GPU memory (bessx_k_predict.hip).  Stateless: a model is (cols, B, coef0), no
+ *     session is needed, and the device is the one that owns x.  For row i and response r
+ *         eta(i, r) = sum_k x(i, cols[k]) * B[k * R + r] + coef0[r]
+ *     is formed from the m support columns alone -- n * m elements of x are read where they lie, not n * p; no fp64 copy
+ *     of x is made, and x is never written.  x is a matrix as in section 2b (dtype, element strides, non-negative).
+ *     cols: m >= 0 column numbers, ascending, distinct, in [0, p) (the union of the supports; m = 0 reads no byte of x
+ *     and every row gets coef0); B: m x R row-major; coef0: R values; all three in HOST memory.  R >= 1.
+ *     link            out                                              out2
+ *     _IDENTITY       eta                                              NULL (ignored)
+ *     _LOGISTIC       e / (e + 1), e = exp(clip(eta, -25, 25))         labels: 1.0 where eta > 0, else 0.0 (required)
+ *     _POISSON        exp(eta)                                         NULL (ignored)
+ *     out (and out2) hold element (i, r) at [i * out_row_stride + r * out_col_stride], strides in elements, non-negative
+ *     and non-zero along every axis longer than 1.  out_on_device != 0: they are device memory of x's device, checked
+ *     like the inputs of section 2b (hipPointerGetAttributes, the whole view inside its allocation): a wrong pointer is
+ *     BESSX_ERR_ARG, not a fault.  Otherwise they are host memory: the library stages the n * R results through a
+ *     device buffer of its own and copies them back.
+ *     stream: as in section 2b.  Reads of x and writes of out are ordered after the work queued on `stream` so far; when
+ *     the call returns the kernel has finished, and x is not referenced afterwards.
+ *     Every sum has a fixed order (no floating-point atomics): the same call gives the same bits.  A NaN in a support
+ *     column of a row reaches that row's outputs and is no error; columns outside the support are not read.
+ *     Argument errors (BESSX_ERR_ARG with a message) are found before any device call; without a GPU a call with valid
+ *     arguments returns BESSX_ERR_HIP.
+ * ------------------------------------------------------------------------------------- */
+enum { BESSX_LINK_IDENTITY = 0, BESSX_LINK_LOGISTIC = 1, BESSX_LINK_POISSON = 2 };
+int bessx_predict_device(const void *x, int x_dtype, long long x_row_stride, long long x_col_stride, int n, int p,
+                         const int *cols, int m, const double *B, const double *coef0, int R, int link, double *out,
+                         long long out_row_stride, long long out_col_stride, double *out2, int out_on_device,
+                         void *stream);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -504,6 +533,12 @@ int bessx_op_ingest(const void *x, int dtype, long long row_stride, long long co
  * bytes read (n * p * element size) plus bytes written (ld * p * 8). */
 int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long long col_stride, const int *row_order,
                           int n, int p, long long ld, int repeats, double *avg_ms, double *gbps);
+/* The prediction kernel of section 2c timed with device events on the device matrix x: one warm-up, then `repeats`
+ * launches for the support cols (host, m ascending distinct columns) and R responses, with coefficients of the library's
+ * own and results in a device buffer of its own.  *avg_ms per launch; *gbps counts the bytes the result needs,
+ * n * m * element size read plus n * R * 8 written (a row-contiguous x moves more than that: whole sectors). */
+int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                           const int *cols, int m, int R, int link, int repeats, double *avg_ms, double *gbps);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
