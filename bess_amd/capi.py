@@ -36,7 +36,7 @@ SYMBOLS = [
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
-    "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench",
+    "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -64,6 +64,14 @@ class DeviceInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("y_host", _D),
                 ("y_dev", _vp), ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp),
                 ("weight_dtype", _i), ("weight_stride", _ll), ("row_order", _I), ("stream", _vp)]
+
+
+class EvalInput(ctypes.Structure):
+    """bessx_eval_input: the model, X in GPU memory, y and weight in host or GPU memory; strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("coef0", _D), ("R", _i), ("link", _i), ("y_host", _D),
+                ("y_dev", _vp), ("y_dtype", _i), ("y_row_stride", _ll), ("y_col_stride", _ll), ("y_cols", _i),
+                ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i), ("weight_stride", _ll), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -177,6 +185,8 @@ def lib():
         L.bessx_op_ingest_bench.argtypes = [_vp, _i, _ll, _ll, _I, _i, _i, _ll, _i, _D, _D]
         L.bessx_predict_device.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _D, _D, _i, _i, _vp, _ll, _ll, _vp, _i, _vp]
         L.bessx_op_predict_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _D, _D]
+        L.bessx_eval_device.argtypes = [ctypes.POINTER(EvalInput), _D, _D, _D]
+        L.bessx_op_eval_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1024,6 +1034,120 @@ def op_predict_bench(x, cols, R=1, link="identity", repeats=20):
     _check(lib().bessx_op_predict_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                         _ip(cols), cols.size, int(R), LINKS[link], repeats, ctypes.byref(ms),
                                         ctypes.byref(g)))
+    return ms.value, g.value
+
+
+def process_counters():
+    """The ledger of the library's GPU resources in this process (bessx_session_counter 38-40, no session needed)."""
+    L = lib()
+    return {"live_device_bytes": int(L.bessx_session_counter(None, 38)),
+            "live_pinned_bytes": int(L.bessx_session_counter(None, 39)),
+            "allocation_requests": int(L.bessx_session_counter(None, 40))}
+
+
+def _eval_y(y, n, R):
+    """y of evaluate_device as (host array or None, _DeviceArray or None, row stride, column stride, y_cols), checked:
+    n values (one column for every model) or an (n, R) array (one column per model)."""
+    if is_device_array(y):
+        dy = _DeviceArray(y, "y")
+        shape, strides, host = dy.shape, dy.strides, None
+    else:
+        host = np.asarray(y, dtype=np.float64)
+        if host.ndim < 1 or host.ndim > 2:
+            raise ValueError("y must be 1-D or 2-D, got shape %s" % (host.shape,))
+        host = np.ascontiguousarray(host)
+        dy, shape, strides = None, host.shape, tuple(v // 8 for v in host.strides)
+    if shape[0] != n:
+        raise ValueError("X.shape(0) should be equal to y.shape(0): %d rows, y has shape %s" % (n, shape))
+    y_cols = shape[1] if len(shape) == 2 else 1
+    if y_cols != 1 and y_cols != R:
+        raise ValueError("y must have 1 column or one per model (%d), got %d" % (R, y_cols))
+    return host, dy, strides[0], (strides[1] if len(shape) == 2 else 0), y_cols
+
+
+def evaluate_device(x, cols, B, coef0, y, link="identity", weight=None, stream=0):
+    """Held-out loss of R models on a device matrix x (n x p: float64 or float32, any non-negative strides) in one pass
+    over the support's columns (bessx_eval_device): with eta = x[:, cols] @ B + coef0,
+        loss[r] = sum_i w_i * f(eta[i, r], y[i, r])
+    f = (y - eta)^2 ("identity"), max(eta, 0) + log1p(exp(-|eta|)) - y * eta ("logistic") or exp(eta) - y * eta
+    ("poisson").  cols, B, coef0 as in predict_device; y: n values shared by the models or (n, R), host or device array;
+    weight: n values, host or device array, None = ones.  Returns {"loss": (R,), "sum_w": float} plus, for the logistic
+    link, "correct": (R,), the weighted count of rows with (eta > 0) == (y > 0.5).  The n x R predictions are never
+    stored, every sum has a fixed order (the same call gives the same bits), and only these numbers cross the bus.
+    stream: raw handle of the stream x (and y, weight) were produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    cols, B, coef0 = _predict_model(dx, cols, B, coef0)
+    R = B.shape[1]
+    yh, dy, yrs, ycs, y_cols = _eval_y(y, n, R)
+    a = EvalInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.B, a.coef0, a.R, a.link = _ip(cols), cols.size, _dp(B), _dp(coef0), R, LINKS[link]
+    a.y_row_stride, a.y_col_stride, a.y_cols = yrs, ycs, y_cols
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [weight]
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_host = _dp(wh)
+            keep.append(wh)
+    a.stream = int(stream) if stream else None
+    loss, aux, sw = np.zeros(R), np.zeros(R), _d(0)
+    _check(lib().bessx_eval_device(ctypes.byref(a), _dp(loss), _dp(aux), ctypes.byref(sw)))
+    out = {"loss": loss, "sum_w": sw.value}
+    if link == "logistic":
+        out["correct"] = aux
+    return out
+
+
+def candidate_models(result):
+    """(cols, B, coef0) of the candidates a path stored (cand_support / cand_beta / cand_coef0 of the dict that
+    Session.sequential_path / gs_path / pgs_path return): the union of their supports, ascending, and the m x R matrix of
+    their de-normalised coefficients (zero where a candidate does not use a column).  They apply to raw X."""
+    sup, beta = np.asarray(result["cand_support"]), np.asarray(result["cand_beta"], dtype=np.float64)
+    coef0 = _f64(result["cand_coef0"]).reshape(-1)
+    R = coef0.size
+    if R < 1 or sup.shape[0] != R or beta.shape != sup.shape:
+        raise ValueError("result holds no stored candidates (cand_support / cand_beta / cand_coef0)")
+    cols = np.unique(sup[sup >= 0]).astype(np.int32)
+    B = np.zeros((cols.size, R))
+    for r in range(R):
+        used = sup[r] >= 0
+        B[np.searchsorted(cols, sup[r][used]), r] = beta[r][used]
+    return cols, B, coef0
+
+
+def evaluate_candidates(result, x, y, link="identity", weight=None, stream=0):
+    """The train / validation split: the loss of every candidate of a path (fitted on the training rows) on held-out rows
+    x, y in GPU memory, in ONE evaluate_device call over the union of the candidates' supports.  Returns (losses (R,),
+    best) with best the index of the smallest loss, the lowest index on a tie (a NaN loss never wins)."""
+    cols, B, coef0 = candidate_models(result)
+    losses = evaluate_device(x, cols, B, coef0, y, link=link, weight=weight, stream=stream)["loss"]
+    finite = np.where(np.isnan(losses), np.inf, losses)
+    return losses, int(np.argmin(finite))
+
+
+def op_eval_bench(x, cols, R=1, link="identity", y_cols=1, repeats=20):
+    """(ms per launch, GB/s of n * m * item + n * 8 * (y_cols + 1) bytes) of the evaluation kernels on the device matrix
+    x for the support cols and R models, device events."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms, g = _d(0), _d(0)
+    _check(lib().bessx_op_eval_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                     _ip(cols), cols.size, int(R), LINKS[link], int(y_cols), repeats, ctypes.byref(ms),
+                                     ctypes.byref(g)))
     return ms.value, g.value
 
 

@@ -920,3 +920,170 @@ int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long 
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// held-out loss on a caller's device matrix (include/bessx.h section 2d)
+// ----------------------------------------------------------------------------------------------
+// everything about the call that needs no device
+static int eval_check_args(const char *who, const bessx_eval_input *in, const double *loss, const double *aux,
+                           const double *sum_w) {
+  const std::string w(who);
+  if (!in || !loss || !sum_w) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->coef0) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0 || in->y_row_stride < 0 || in->y_col_stride < 0 ||
+      in->weight_stride < 0)
+    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, in->R, in->link)) return rc;
+  if (in->m > 0 && !in->B) return fail(BESSX_ERR_ARG, w + ": null argument (B)");
+  if (in->link == BESSX_LINK_LOGISTIC && !aux) return fail(BESSX_ERR_ARG, w + ": the logistic link needs aux");
+  if ((in->y_host != nullptr) == (in->y_dev != nullptr))
+    return fail(BESSX_ERR_ARG, w + ": give y as a host pointer or as a device view (one of the two)");
+  if (in->y_dev && in->y_dtype != BESSX_F64 && in->y_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": y: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->y_cols != 1 && in->y_cols != in->R) return fail(BESSX_ERR_ARG, w + ": y_cols must be 1 or R");
+  if (in->weight_host && in->weight_dev)
+    return fail(BESSX_ERR_ARG, w + ": give weight as a host pointer or as a device vector, not both");
+  if (in->weight_dev && in->weight_dtype != BESSX_F64 && in->weight_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": weight: dtype must be BESSX_F64 or BESSX_F32");
+  return 0;
+}
+
+// y and the weights as the kernel reads them: the caller's device memory where it lies, host data through a buffer of `sc`
+static int eval_stage_data(Owner &sc, const bessx_eval_input *in, hipStream_t st, EvalData *d) {
+  const long long n = in->n;
+  const long long ycs = in->y_cols == 1 ? 0 : in->y_col_stride;
+  *d = EvalData{nullptr, 0, in->y_row_stride, ycs, nullptr, 0, 0};
+  if (in->y_dev) {
+    d->y = in->y_dev;
+    d->y_f32 = in->y_dtype == BESSX_F32;
+  } else {
+    const size_t span = (size_t)((n - 1) * in->y_row_stride + (in->y_cols - 1) * ycs + 1);
+    double *yd = nullptr;
+    HIPX(sc.alloc(&yd, span));
+    HIPX(hipMemcpyAsync(yd, in->y_host, span * sizeof(double), hipMemcpyHostToDevice, st));
+    d->y = yd;
+  }
+  if (in->weight_dev) {
+    d->w = in->weight_dev;
+    d->w_f32 = in->weight_dtype == BESSX_F32;
+    d->ws = in->weight_stride;
+  } else if (in->weight_host) {
+    double *wd = nullptr;
+    HIPX(sc.alloc(&wd, (size_t)n));
+    HIPX(hipMemcpyAsync(wd, in->weight_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    d->w = wd;
+    d->ws = 1;
+  }
+  return 0;
+}
+
+// sc and h belong to the caller: they must outlive everything this function queues on st, also when it fails half way
+static int eval_run(Owner &sc, std::vector<double> &h, const bessx_eval_input *in, double *loss, double *aux,
+                    double *sum_w, hipStream_t st) {
+  // reads come after everything the caller has queued on its stream so far
+  hipEvent_t ev = nullptr;
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *res = nullptr;
+  const int R = in->R, f32 = in->x_dtype == BESSX_F32;
+  if (int rc = predict_upload_model(sc, in->cols, in->m, in->B, in->coef0, R, st, &cols_d, &B_d, &c_d)) return rc;
+  EvalData d;
+  if (int rc = eval_stage_data(sc, in, st, &d)) return rc;
+  const long long nwork =
+      eval_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, in->m, R, in->link, d.w != nullptr);
+  HIPX(sc.alloc(&work, (size_t)nwork));
+  HIPX(sc.alloc(&res, 2 * (size_t)R + 1));
+  HIPX(launch_eval(in->x, f32, in->x_row_stride, in->x_col_stride, in->n, cols_d, in->m, B_d, c_d, R, in->link, d, work,
+                   res, st));
+  h.resize(2 * (size_t)R + 1);
+  HIPX(hipMemcpyAsync(h.data(), res, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  std::copy(h.begin(), h.begin() + R, loss);
+  if (in->link == BESSX_LINK_LOGISTIC) std::copy(h.begin() + R, h.begin() + 2 * R, aux);
+  *sum_w = d.w ? h[2 * (size_t)R] : (double)in->n;
+  return 0;
+}
+
+extern "C" {
+
+int bessx_eval_device(const bessx_eval_input *in, double *loss, double *aux, double *sum_w) {
+  if (int rc = eval_check_args("eval_device", in, loss, aux, sum_w)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("eval_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->y_dev) {
+    if (int rc = check_device_matrix("eval_device: y", in->y_dev, in->y_dtype, in->y_row_stride,
+                                     in->y_cols == 1 ? 0 : in->y_col_stride, in->n, in->y_cols, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "eval_device: y is not on the device that owns x");
+  }
+  if (in->weight_dev) {
+    if (int rc = check_device_matrix("eval_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
+                                     in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "eval_device: weight is not on the device that owns x");
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> h;
+    rc = eval_run(sc, h, in, loss, aux, sum_w, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                        const int *cols, int m, int R, int link, int y_cols, int repeats, double *avg_ms,
+                        double *gbps) {
+  if (!x || repeats < 1 || !avg_ms || !gbps) return fail(BESSX_ERR_ARG, "op_eval_bench: bad arguments");
+  if (int rc = predict_check_model("op_eval_bench", n, p, cols, m, R, link)) return rc;
+  if (y_cols != 1 && y_cols != R) return fail(BESSX_ERR_ARG, "op_eval_bench: y_cols must be 1 or R");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_eval_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  std::vector<double> B((size_t)m * R), c0((size_t)R, 0.25), y((size_t)n * y_cols), wt((size_t)n, 1.0);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (size_t q = 0; q < y.size(); q++) y[q] = (double)(q % 2);
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *y_d = nullptr, *w_d = nullptr, *work = nullptr, *res = nullptr;
+  if (int rc = predict_upload_model(sc, cols, m, B.data(), c0.data(), R, nullptr, &cols_d, &B_d, &c_d)) return rc;
+  HIPX(sc.alloc(&y_d, y.size()));
+  HIPX(sc.alloc(&w_d, wt.size()));
+  HIPX(hipMemcpy(y_d, y.data(), y.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(w_d, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice));
+  const int f32 = dtype == BESSX_F32;
+  const EvalData d{y_d, 0, 1, y_cols == 1 ? 0 : (long long)n, w_d, 0, 1};  // (y column by column)
+  HIPX(sc.alloc(&work, (size_t)eval_workspace(f32, row_stride, col_stride, n, m, R, link, 1)));
+  HIPX(sc.alloc(&res, 2 * (size_t)R + 1));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  HIPX(launch_eval(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, d, work, res, nullptr));
+  HIPX(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < repeats; i++)
+    HIPX(launch_eval(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, d, work, res, nullptr));
+  HIPX(hipEventRecord(e1, nullptr));
+  HIPX(hipEventSynchronize(e1));
+  float ms = 0.f;
+  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  const double bytes = (double)n * (double)m * (f32 ? 4.0 : 8.0) + (double)n * 8.0 * (y_cols + 1.0);
+  *avg_ms = ms / repeats;
+  *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;
+  return BESSX_OK;
+}
+
+}  // extern "C"

@@ -60,6 +60,22 @@ enum { PREDICT_IDENTITY = 0, PREDICT_LOGISTIC = 1, PREDICT_POISSON = 2 };  // = 
 hipError_t launch_predict(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                           const double *B, const double *c, int R, int link, double *out, long long ors, long long ocs,
                           double *out2, hipStream_t st);
+// device evaluation (bessx_k_eval.hip): res[r] = sum_i w_i * f(eta(i, r), y(i, r)) with eta as in launch_predict, in one
+// pass over the support's columns; PREDICT_LOGISTIC also res[R + r] = sum_i w_i * [(eta > 0) == (y > 0.5)]; with weights
+// res[2 * R] = sum_i w_i.  y(i, r) at y[i * yrs + r * ycs] (ycs = 0: one y for every response), w_i at w[i * ws] (w null:
+// ones); fp64 or fp32 device memory.  work: eval_workspace(...) doubles; res: 2 * R + 1 doubles; both device memory.
+struct EvalData {
+  const void *y;
+  int y_f32;
+  long long yrs, ycs;
+  const void *w;
+  int w_f32;
+  long long ws;
+};
+long long eval_workspace(int f32, long long rs, long long cs, long long n, int m, int R, int link, int weighted);
+hipError_t launch_eval(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                       const double *B, const double *c, int R, int link, const EvalData &d, double *work, double *res,
+                       hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

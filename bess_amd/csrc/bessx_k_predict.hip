@@ -1,255 +1,35 @@
 // bessx_k_predict.hip -- prediction on a caller's DEVICE matrix: eta = X[:, cols] B + c for R responses, plus the link
-// (+ launcher).  X is fp64 or fp32 with arbitrary non-negative element strides and is read where it lies, only the m
-// support columns of it: n * m elements instead of n * p.  fp32 is widened in registers (exact).  Two kernels:
-//   k_predict_rows     threads along rows.  A workgroup owns 64 * N rows (N = elements of a 16-byte load); its four
-//                      waves split every chunk of 64 support columns between them and their partial sums are added in
-//                      wave order through LDS.  B is staged in LDS chunk by chunk.  VEC: column-contiguous source with an
-//                      aligned base and column stride, one 16-byte load per column; otherwise element loads at any strides
-//                      (coalesced when row_stride == 1) -- the same arithmetic in the same order.
-//   k_predict_gather   row-contiguous source (col_stride == 1): the support is split across the lanes of a wave (LPR = 64)
-//                      or of a quarter wave (LPR = 16, short supports); a lane keeps its columns' rows of B in registers
-//                      while the wave walks its rows, and the lanes' partial sums are added by a DPP tree (+ three
-//                      additions in lane order for LPR = 64).
-// Both take RT responses per workgroup (blockIdx.y walks the tiles of a wide R) and loop over the support in chunks: no
-// LDS or register array is sized by m or R.  Every sum has a fixed order and there are no atomics: a call repeats bit for
-// bit.  Index arithmetic is in 64 bits.  A NaN in a support column of a row reaches that row's outputs; the other
-// columns are not read.
-#include "bessx_kdev.hpp"
+// (+ launcher).  The loops that form eta are those of bessx_k_xb.hpp (k_xb_rows / k_xb_gather: in-place reads of the m
+// support columns at any strides, fp32 widened in registers, fixed summation order); this file supplies the epilogue
+// that stores link(eta).  A NaN in a support column of a row reaches that row's outputs; the other columns are not read.
+#include "bessx_k_xb.hpp"
 
 namespace bessx {
 
 namespace {
 
-constexpr int PR_CH = 64;  // support columns staged per chunk of k_predict_rows
-constexpr int PR_KPL = 2;  // support columns per lane and chunk of k_predict_gather
-
-template <typename T>
-struct PrVec;
-template <>
-struct PrVec<double> {
-  static constexpr int N = 2;  // elements per 16-byte load
-  typedef d2 type;
-};
-template <>
-struct PrVec<float> {
-  static constexpr int N = 4;
-  typedef float4 type;
-};
-
-__device__ inline void pr_unpack(const d2 &v, double *o) {
-  o[0] = v.x;
-  o[1] = v.y;
-}
-__device__ inline void pr_unpack(const float4 &v, double *o) {
-  o[0] = (double)v.x;
-  o[1] = (double)v.y;
-  o[2] = (double)v.z;
-  o[3] = (double)v.w;
-}
-
 // what bess_base.predict computes from eta on the host: the comparisons keep a NaN a NaN (fmin / fmax would drop it)
-__device__ __forceinline__ void pr_store(double eta, int link, double *__restrict__ out, double *__restrict__ out2,
-                                         long long off) {
-  if (link == PREDICT_LOGISTIC) {
-    const double cl = eta > 25.0 ? 25.0 : (eta < -25.0 ? -25.0 : eta);
-    const double e = exp(cl);
-    out[off] = e / (e + 1.0);
-    out2[off] = eta > 0.0 ? 1.0 : 0.0;
-  } else if (link == PREDICT_POISSON) {
-    out[off] = exp(eta);
-  } else {
-    out[off] = eta;
+struct PrStore {
+  static constexpr bool REDUCE = false, SKIPZ = false;
+  int link;
+  double *__restrict__ out, *__restrict__ out2;
+  long long ors, ocs;
+  __device__ __forceinline__ void store(double eta, long long i, int r) const {
+    const long long off = i * ors + (long long)r * ocs;
+    if (link == PREDICT_LOGISTIC) {
+      const double cl = eta > 25.0 ? 25.0 : (eta < -25.0 ? -25.0 : eta);
+      const double e = exp(cl);
+      out[off] = e / (e + 1.0);
+      out2[off] = eta > 0.0 ? 1.0 : 0.0;
+    } else if (link == PREDICT_POISSON) {
+      out[off] = exp(eta);
+    } else {
+      out[off] = eta;
+    }
   }
-}
-
-// sum over the LPR lanes of a lane group, the same bits in every lane of the group: four symmetric DPP exchanges inside
-// each row of 16 lanes, then (LPR = 64) the four rows in lane order
-template <int LPR>
-__device__ __forceinline__ double pr_group_sum(double v) {
-#pragma unroll
-  for (int st = 0; st < 4; st++) v += dpp_f64(v, st);
-  if (LPR == 64) v = ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
-  return v;
-}
+};
 
 }  // namespace
-
-// ------------------------------------------------------------------------------------------
-// threads along rows: block (row block, response tile).  Lane l of every wave owns rows (blockIdx.x * 64 + l) * N ..
-// + N - 1; wave w takes columns w, w + 4, ... of each chunk, four of them in flight per step.
-// ------------------------------------------------------------------------------------------
-template <typename T, int RT, bool VEC>
-__global__ void __launch_bounds__(256) k_predict_rows(const T *__restrict__ src, long long rs, long long cs, long long n,
-                                                      const int *__restrict__ cols, int m,
-                                                      const double *__restrict__ B, const double *__restrict__ c, int R,
-                                                      int link, double *__restrict__ out, long long ors, long long ocs,
-                                                      double *__restrict__ out2) {
-  constexpr int N = PrVec<T>::N;
-  typedef typename PrVec<T>::type V;
-  __shared__ double Bs[PR_CH * RT];
-  __shared__ int Cs[PR_CH];
-  __shared__ double red[3][N * RT][64];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const long long i0 = ((long long)blockIdx.x * 64 + lane) * N;
-  const int r0 = (int)blockIdx.y * RT;
-  double acc[N][RT];
-#pragma unroll
-  for (int e = 0; e < N; e++)
-#pragma unroll
-    for (int r = 0; r < RT; r++) acc[e][r] = 0.0;
-  for (int k0 = 0; k0 < m; k0 += PR_CH) {
-    const int kc = min(PR_CH, m - k0);
-    __syncthreads();
-    for (int q = t; q < kc * RT; q += 256) {
-      const int j = q / RT, r = q % RT;
-      Bs[q] = (r0 + r < R) ? B[(long long)(k0 + j) * R + r0 + r] : 0.0;
-    }
-    if (t < kc) Cs[t] = cols[k0 + t];
-    __syncthreads();
-    for (int j0 = w; j0 < kc; j0 += 16) {
-      double x[4][N];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int j = j0 + 4 * u;
-#pragma unroll
-        for (int e = 0; e < N; e++) x[u][e] = 0.0;
-        if (j < kc) {  // (wave-uniform; a column past the chunk is not read: its NaN must not reach the sum)
-          const T *cp = src + (long long)Cs[j] * cs;
-          if (VEC && i0 + N <= n) {
-            pr_unpack(*reinterpret_cast<const V *>(cp + i0), x[u]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < N; e++)
-              if (i0 + e < n) x[u][e] = (double)cp[(i0 + e) * rs];
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int j = j0 + 4 * u;
-        if (j < kc) {
-#pragma unroll
-          for (int r = 0; r < RT; r++) {
-            const double b = Bs[j * RT + r];
-#pragma unroll
-            for (int e = 0; e < N; e++) acc[e][r] += x[u][e] * b;
-          }
-        }
-      }
-    }
-  }
-  if (w > 0) {
-#pragma unroll
-    for (int e = 0; e < N; e++)
-#pragma unroll
-      for (int r = 0; r < RT; r++) red[w - 1][e * RT + r][lane] = acc[e][r];
-  }
-  __syncthreads();
-  if (w == 0) {
-#pragma unroll
-    for (int e = 0; e < N; e++) {
-      const long long i = i0 + e;
-#pragma unroll
-      for (int r = 0; r < RT; r++) {
-        if (i < n && r0 + r < R) {
-          const int a = e * RT + r;
-          const double eta = (((acc[e][r] + red[0][a][lane]) + red[1][a][lane]) + red[2][a][lane]) + c[r0 + r];
-          pr_store(eta, link, out, out2, i * ors + (long long)(r0 + r) * ocs);
-        }
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// row-contiguous source: block (row block, response tile), no LDS.  A wave owns 64 / RT rows and works on G = 64 / LPR
-// of them at a time, one per lane group, in S = LPR / RT steps.  Lane lg of a group gathers columns k0 + lg and
-// k0 + LPR + lg of the chunk for its group's row; lane lg of group g keeps the finished sum of row (lg / RT) * G + g,
-// response lg % RT, so the wave's 64 results are one register.
-// ------------------------------------------------------------------------------------------
-template <typename T, int RT, int LPR>
-__global__ void __launch_bounds__(256) k_predict_gather(const T *__restrict__ src, long long rs, long long n,
-                                                        const int *__restrict__ cols, int m,
-                                                        const double *__restrict__ B, const double *__restrict__ c,
-                                                        int R, int link, double *__restrict__ out, long long ors,
-                                                        long long ocs, double *__restrict__ out2) {
-  constexpr int G = 64 / LPR, S = LPR / RT, RPW = 64 / RT;
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63, g = lane / LPR, lg = lane % LPR;
-  const long long row0 = ((long long)blockIdx.x * 4 + w) * RPW;
-  const int r0 = (int)blockIdx.y * RT;
-  double eta = 0.0;
-  for (int k0 = 0; k0 < m; k0 += LPR * PR_KPL) {
-    long long col[PR_KPL];
-    bool ok[PR_KPL];
-    double b[PR_KPL][RT];
-#pragma unroll
-    for (int u = 0; u < PR_KPL; u++) {
-      const int k = k0 + u * LPR + lg;
-      ok[u] = k < m;
-      col[u] = ok[u] ? (long long)cols[k] : 0;
-#pragma unroll
-      for (int r = 0; r < RT; r++) b[u][r] = (ok[u] && r0 + r < R) ? B[(long long)k * R + r0 + r] : 0.0;
-    }
-#pragma unroll 2
-    for (int s = 0; s < S; s++) {
-      const long long i = row0 + s * G + g;
-      double x[PR_KPL];
-#pragma unroll
-      for (int u = 0; u < PR_KPL; u++) x[u] = (ok[u] && i < n) ? (double)src[i * rs + col[u]] : 0.0;
-#pragma unroll
-      for (int r = 0; r < RT; r++) {
-        double part = x[0] * b[0][r];
-#pragma unroll
-        for (int u = 1; u < PR_KPL; u++) part += x[u] * b[u][r];
-        part = pr_group_sum<LPR>(part);
-        if (lg == s * RT + r) eta += part;
-      }
-    }
-  }
-  const long long i = row0 + (lg / RT) * G + g;
-  const int r = r0 + lg % RT;
-  if (i < n && r < R) pr_store(eta + c[r], link, out, out2, i * ors + (long long)r * ocs);
-}
-
-template <typename T, int RT>
-static hipError_t launch_predict_rt(const T *src, long long rs, long long cs, long long n, const int *cols, int m,
-                                    const double *B, const double *c, int R, int link, double *out, long long ors,
-                                    long long ocs, double *out2, hipStream_t st) {
-  const unsigned tiles = (unsigned)((R + RT - 1) / RT);
-  if (tiles > 65535) return hipErrorInvalidValue;
-  if (cs == 1 && rs != 1 && m > 0) {
-    const long long rows_per_block = 4LL * (64 / RT);
-    const dim3 grid((unsigned)((n + rows_per_block - 1) / rows_per_block), tiles);
-    if (m <= 16 * PR_KPL)
-      hipLaunchKernelGGL((k_predict_gather<T, RT, 16>), grid, dim3(256), 0, st, src, rs, n, cols, m, B, c, R, link, out,
-                         ors, ocs, out2);
-    else
-      hipLaunchKernelGGL((k_predict_gather<T, RT, 64>), grid, dim3(256), 0, st, src, rs, n, cols, m, B, c, R, link, out,
-                         ors, ocs, out2);
-  } else {
-    const long long rows_per_block = 64LL * PrVec<T>::N;
-    const dim3 grid((unsigned)((n + rows_per_block - 1) / rows_per_block), tiles);
-    const long long per16 = 16 / (long long)sizeof(T);
-    const bool vec = rs == 1 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && cs % per16 == 0;
-    if (vec)
-      hipLaunchKernelGGL((k_predict_rows<T, RT, true>), grid, dim3(256), 0, st, src, rs, cs, n, cols, m, B, c, R, link,
-                         out, ors, ocs, out2);
-    else
-      hipLaunchKernelGGL((k_predict_rows<T, RT, false>), grid, dim3(256), 0, st, src, rs, cs, n, cols, m, B, c, R, link,
-                         out, ors, ocs, out2);
-  }
-  LAUNCH_CHECK();
-  return hipSuccess;
-}
-
-template <typename T>
-static hipError_t launch_predict_t(const T *src, long long rs, long long cs, long long n, const int *cols, int m,
-                                   const double *B, const double *c, int R, int link, double *out, long long ors,
-                                   long long ocs, double *out2, hipStream_t st) {
-  if (R == 1) return launch_predict_rt<T, 1>(src, rs, cs, n, cols, m, B, c, R, link, out, ors, ocs, out2, st);
-  if (R <= 4) return launch_predict_rt<T, 4>(src, rs, cs, n, cols, m, B, c, R, link, out, ors, ocs, out2, st);
-  return launch_predict_rt<T, 8>(src, rs, cs, n, cols, m, B, c, R, link, out, ors, ocs, out2, st);
-}
 
 // out[i * ors + r * ocs] = link(sum_k src(i, cols[k]) * B[k * R + r] + c[r]) for i < n, r < R; cols (m, ascending, device),
 // B (m x R row-major, device), c (R, device).  PREDICT_LOGISTIC: out = e / (e + 1) with e = exp(clip(eta, -25, 25)) and
@@ -260,9 +40,9 @@ hipError_t launch_predict(const void *src, int f32, long long rs, long long cs, 
   if (!src || !c || !out || n < 1 || n > 0x7fffffffLL || m < 0 || (m > 0 && (!cols || !B)) || R < 1 || rs < 0 || cs < 0 ||
       ors < 0 || ocs < 0 || link < PREDICT_IDENTITY || link > PREDICT_POISSON || (link == PREDICT_LOGISTIC && !out2))
     return hipErrorInvalidValue;
-  if (f32)
-    return launch_predict_t(static_cast<const float *>(src), rs, cs, n, cols, m, B, c, R, link, out, ors, ocs, out2, st);
-  return launch_predict_t(static_cast<const double *>(src), rs, cs, n, cols, m, B, c, R, link, out, ors, ocs, out2, st);
+  const PrStore epi{link, out, out2, ors, ocs};
+  if (f32) return xb_launch(static_cast<const float *>(src), rs, cs, n, cols, m, B, c, R, epi, st);
+  return xb_launch(static_cast<const double *>(src), rs, cs, n, cols, m, B, c, R, epi, st);
 }
 
 }  // namespace bessx

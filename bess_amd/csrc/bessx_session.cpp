@@ -1804,6 +1804,9 @@ int bessx_session_score_pass_stats(bessx_session *s, int reset, double *seconds,
 int bessx_session_score_mode(const bessx_session *s) { return s && s->cov_mode ? 2 : 1; }
 
 long long bessx_session_counter(const bessx_session *s, int which) {
+  if (!s && which >= 38 && which <= 40) {  // (process-wide: readable without a session)
+    return which == 38 ? Ledger::device_bytes.load() : (which == 39 ? Ledger::pinned_bytes.load() : Ledger::requests.load());
+  }
   if (!s) return -1;
   switch (which) {
     case 0: return s->chain_hits;

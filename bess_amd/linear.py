@@ -40,6 +40,8 @@ class bess_base:
     or float32, any strides): the library reads it where it lies, on torch's current stream, and X never crosses the
     bus.  y and weight may be device arrays too (n values: they are copied to the host).  predict(X) takes such an X too: a kernel reads the support's
     columns of it in place, and the results are torch tensors on X's device when X is one (NumPy arrays otherwise).
+    evaluate(X, y) / score(X, y) turn held-out data into loss, R^2, accuracy or deviance: for an X in GPU memory in one
+    fused pass over the support's columns that brings back R numbers.
     """
 
     def __init__(self, algorithm_type, model_type, path_type, max_iter=20, exchange_num=0, is_warm_start=True,
@@ -252,6 +254,102 @@ class bess_base:
         if self.model_type_int == 3:
             return {"lam": np.exp(eta)}
         return None
+
+    # ---- held-out evaluation ------------------------------------------------------------------------------------
+    _LINK = {1: "identity", 2: "logistic", 3: "poisson"}
+
+    def _model_arrays(self):
+        """(beta, cols, coef0 (R,), multi): cols is the union of the supports, multi says that beta has a column per
+        response (Lm fitted to a 2-D y)."""
+        beta = np.asarray(self.beta, dtype=np.float64)
+        multi = self.model_type_int == 1 and beta.ndim == 2
+        cols = np.nonzero(beta.any(axis=1) if multi else beta)[0]
+        return beta, cols, np.asarray(self.coef0, dtype=np.float64).reshape(-1), multi
+
+    @staticmethod
+    def _loss_host(link, eta, Y, w):
+        """(L (R,), A (R,) or None) in fp64 NumPy, the formulas of bessx_eval_device: eta, Y (n, R) or Y (n, 1), w (n,)."""
+        A = None
+        if link == "identity":
+            f = (Y - eta) ** 2
+        elif link == "logistic":
+            f = np.maximum(eta, 0.0) + np.log1p(np.exp(-np.abs(eta))) - Y * eta
+            A = (w[:, None] * ((eta > 0) == (Y > 0.5))).sum(axis=0)
+        else:
+            f = np.exp(eta) - Y * eta
+        return (w[:, None] * f).sum(axis=0), A
+
+    def evaluate(self, X, y, weight=None):
+        """How good the fitted model is on data it was not fitted to: a dict of numbers shaped like coef0.
+        All families: loss = sum_i w_i f(eta_i, y_i) (f as in capi.evaluate_device) and n_eff = sum_i w_i.
+        Lm: mse = loss / n_eff, r2 = 1 - loss / sum_i w_i (y_i - ybar_w)^2 (a 2-D y: per response).
+        Logistic: deviance = 2 loss, accuracy = weighted share of rows with (eta > 0) == (y > 0.5).
+        Poisson: deviance = 2 (loss + sum_i w_i (y_i log y_i - y_i)) with 0 log 0 = 0, d2 = 1 - deviance / null deviance.
+        Cox: None.  An X in GPU memory is read in place on torch's current stream by one fused kernel pass over the
+        support's columns, y and weight may be device arrays as well, and the kernel brings back R numbers (2 R for
+        Logistic).  For Lm and Poisson the terms in y alone (ybar_w, the total sum of squares, y log y, the null
+        deviance) are computed on the host, so a device y and weight are also copied to the host, n values each;
+        Logistic copies neither.  A NumPy X is evaluated in fp64 NumPy with the same formulas."""
+        on_device = capi.is_device_array(X)
+        n, p = capi._DeviceArray(X, "X", 2).shape if on_device else np.asarray(X).shape
+        if p != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        if self.model_type_int == 4:
+            return None
+        beta, cols, coef0, multi = self._model_arrays()
+        R, link = coef0.size, self._LINK[self.model_type_int]
+        # (every shape is checked before anything is copied: a bad call makes no device call)
+        y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
+        if not y_dev:
+            y = np.asarray(y, dtype=np.float64)
+        yshape = capi._DeviceArray(y, "y").shape if y_dev else y.shape
+        if len(yshape) not in (1, 2) or yshape[0] != n or (len(yshape) == 2 and yshape[1] not in (1, R)):
+            raise ValueError("X.shape(0) should be equal to y.shape(0), and y needs 1 column or one per response: "
+                             "%d rows, %d responses, y has shape %s" % (n, R, tuple(yshape)))
+        if weight is not None:
+            if not w_dev:
+                weight = np.asarray(weight, dtype=np.float64).reshape(-1)
+            if (capi._DeviceArray(weight, "weight").size if w_dev else weight.size) != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+        # host copies only where the host uses them: the NumPy route, and the terms in y alone of Lm and Poisson
+        Y = w = None
+        if not on_device or link != "logistic":
+            Y = (capi.device_to_host(y, _current_stream(y)) if y_dev else y).reshape(n, -1)
+            if weight is None:
+                w = np.ones(n)
+            else:
+                w = (capi.device_to_host(weight, _current_stream(weight)) if w_dev else weight).reshape(-1)
+        if on_device:
+            got = capi.evaluate_device(X, cols, beta[cols].reshape(cols.size, R), coef0, y, link=link, weight=weight,
+                                       stream=_current_stream(X))
+            L, A, sw = got["loss"], got.get("correct"), got["sum_w"]
+        else:
+            eta = np.dot(np.asarray(X, dtype=np.float64), beta.reshape(p, R)) + coef0[None, :]
+            L, A = self._loss_host(link, eta, Y, w)
+            sw = float(n) if weight is None else float(w.sum())
+        out = {"loss": L, "n_eff": np.full(R, sw)}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if link == "identity":
+                ybar = (w[:, None] * Y).sum(axis=0) / sw
+                out["mse"] = L / sw
+                out["r2"] = 1.0 - L / (w[:, None] * (Y - ybar[None, :]) ** 2).sum(axis=0)
+            elif link == "logistic":
+                out["deviance"] = 2.0 * L
+                out["accuracy"] = A / sw
+            else:
+                ylogy = np.where(Y > 0, Y * np.log(np.where(Y > 0, Y, 1.0)), 0.0)
+                ybar = (w[:, None] * Y).sum(axis=0) / sw
+                out["deviance"] = 2.0 * (L + (w[:, None] * (ylogy - Y)).sum(axis=0))
+                null = 2.0 * (w[:, None] * (ylogy - Y * np.log(ybar)[None, :] - (Y - ybar[None, :]))).sum(axis=0)
+                out["d2"] = 1.0 - out["deviance"] / null
+        if not multi:
+            out = {k: float(v[0]) for k, v in out.items()}
+        return out
+
+    def score(self, X, y, weight=None):
+        """r2 (Lm), accuracy (Logistic) or d2 (Poisson) of evaluate(X, y, weight); None for Cox."""
+        res = self.evaluate(X, y, weight)
+        return None if res is None else res[{1: "r2", 2: "accuracy", 3: "d2"}[self.model_type_int]]
 
 
 def _make(name, algorithm_type, model_type):

@@ -232,6 +232,60 @@ int bessx_predict_device(const void *x, int x_dtype, long long x_row_stride, lon
                          const int *cols, int m, const double *B, const double *coef0, int R, int link, double *out,
                          long long out_row_stride, long long out_col_stride, double *out2, int out_on_device,
                          void *stream);
+/* ---------------------------------------------------------------------------------------
+ * 2d. Held-out loss on an X already in GPU memory (bessx_k_eval.hip).  Stateless like section 2c, and the same model:
+ *     with eta(i, r) as there,
+ *         loss[r] = sum_i w_i * f(eta(i, r), y(i, r))
+ *     in ONE pass over the m support columns (n * m elements of x read where they lie, x never written, no fp64 copy of
+ *     it; m = 0 reads no byte of x) -- the n x R predictions are never stored.
+ *     link         f(eta, y)                                           aux[r]
+ *     _IDENTITY    (y - eta)^2                                         ignored (may be NULL)
+ *     _LOGISTIC    max(eta, 0) + log1p(exp(-|eta|)) - y * eta          sum_i w_i * [(eta > 0) == (y > 0.5)]: the weighted
+ *                  (negative log-likelihood, overflow-free, no        count of correct labels, label rule of section 2c
+ *                  clamp; any y in [0, 1])                              (required)
+ *     _POISSON     exp(eta) - y * eta  (negative log-likelihood        ignored (may be NULL)
+ *                  without the term in y alone)
+ *     x, n, p, cols, m, B, coef0, R, link: as in section 2c (cols / B / coef0 in HOST memory, same checks).
+ *     y: element (i, r) at [i * y_row_stride + r * y_col_stride], strides in elements, non-negative.  y_cols = 1: one
+ *     column shared by all R models (y_col_stride is ignored); y_cols = R: one column per model.  Give y_host (fp64) or
+ *     y_dev (device memory, y_dtype BESSX_F64 / BESSX_F32), not both.
+ *     weight: n values, weight_host (fp64, contiguous) or weight_dev (weight_dtype, weight_stride), or both NULL = ones.
+ *     stream: as in section 2b.  The reads are ordered after the work queued on `stream` so far; when the call returns
+ *     the caller's buffers are no longer referenced.
+ *     Outputs (host): loss[R]; aux[R] for the logistic link; *sum_w = sum_i w_i (exactly n without weights).
+ *     Every sum is fp64 and has a fixed order -- a workgroup adds its rows in a fixed order and writes one partial per
+ *     response, a second launch adds the partials in a fixed order; no floating-point atomics: the same call gives the same
+ *     bits.  A coefficient that is exactly zero takes nothing from its column, so with B holding the union of several
+ *     supports a NaN or inf in a column reaches exactly the models that use the column, through the rows that hold it; one
+ *     in y or a weight reaches the losses that row belongs to.  None of it is an error; columns outside the support are
+ *     not read.
+ *     Every device pointer is checked as in section 2b (a wrong pointer or a view past its allocation: BESSX_ERR_ARG, not
+ *     a fault).  Argument errors are found before any device call; without a GPU a call with valid arguments returns
+ *     BESSX_ERR_HIP.  The call's device buffers are released before it returns (counters 38 / 39 are back at their
+ *     earlier values; 40 has grown by the call's requests).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  const double *coef0;
+  int R, link;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_row_stride, y_col_stride;
+  int y_cols;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  void *stream;
+} bessx_eval_input;
+int bessx_eval_device(const bessx_eval_input *in, double *loss, double *aux, double *sum_w);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -268,7 +322,8 @@ int bessx_session_score_mode(const bessx_session *s);
  * session of bessx_session_create_device reports 0 for 36); 38 / 39 bytes of device / pinned host memory the library
  * holds right now in the whole PROCESS (every session, context and drop-in call: what its allocations handed out and
  * have not given back -- back at its earlier value once a session is destroyed), 40 allocation requests the library has
- * made in the process so far (device buffers, pinned buffers, events).  -1 for an unknown id. */
+ * made in the process so far (device buffers, pinned buffers, events).  -1 for an unknown id.  s may be NULL for 38-40
+ * (they belong to the process). */
 long long bessx_session_counter(const bessx_session *s, int which);
 
 /* Metric::set_cv_train_test_mask + cal_cv_group_XTX (src/Metric.h:49-129).  fold_id[i] in [0,K)
@@ -539,6 +594,11 @@ int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long l
  * n * m * element size read plus n * R * 8 written (a row-contiguous x moves more than that: whole sectors). */
 int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                            const int *cols, int m, int R, int link, int repeats, double *avg_ms, double *gbps);
+/* The evaluation kernels of section 2d (the fused pass and the addition of its partials) timed the same way: y (n x
+ * y_cols, y_cols = 1 or R, column by column), weights and coefficients of the library's own.  *gbps counts
+ * n * m * element size + n * 8 * (y_cols + 1) bytes. */
+int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                        const int *cols, int m, int R, int link, int y_cols, int repeats, double *avg_ms, double *gbps);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
