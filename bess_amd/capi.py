@@ -477,14 +477,14 @@ class Session:
                  12: "cv_fold_contexts", 13: "shared_wide_fills", 14: "kpath_chunked_paths", 15: "kpath_stitch_refits",
                  16: "kpath_chunk_fills", 17: "kpath_chains_last_path",
                  18: "kpath_stitch_giveups", 19: "group_XTX_ns",
-                 20: "kpath_merged_chunk_phases", 21: "kpath_chains_taken_over", 22: "kpath_coarse_us",
+                 22: "kpath_coarse_us",
                  23: "kpath_chunks_us", 24: "kpath_stitch_us", 25: "panel_launches_one_group",
                  26: "panel_ns_one_group", 27: "panel_launches_two_groups", 28: "panel_ns_two_groups",
                  29: "shared_pass_launches", 30: "shared_pass_chain_slots", 31: "shared_pass_partial_batches",
                  32: "own_queue_streams_created_by_the_process", 33: "multi_responses_batched",
                  34: "multi_responses_host", 35: "multi_union_fills", 36: "x_bytes_uploaded_from_host",
                  37: "x_bytes_ingested_on_device", 38: "live_device_bytes_of_the_process",
-                 39: "live_pinned_bytes_of_the_process", 40: "allocation_requests_of_the_process"}  # (4-6: mechanisms removed in round 3)
+                 39: "live_pinned_bytes_of_the_process", 40: "allocation_requests_of_the_process"}  # (4-6, 20-21: mechanisms removed)
         return {n: int(lib().bessx_session_counter(self._h, i)) for i, n in names.items()}
 
     def screening(self):

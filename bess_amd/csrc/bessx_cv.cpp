@@ -284,7 +284,7 @@ int fold_fits_side_by_side(bessx_session *s, double *out, const std::vector<int>
                                    spec_src ? spec_src->c->bd2 : nullptr, s->cov_spec, spec_min, s->cov[0].slot_of, s->cov[0].meta, p,
                                    s->cov_fcols, s->fill_ctrl, s->st));
         // the list's real length (columns two folds miss are listed once) decides how many groups are formed: the
-        // pair kernel the host would pick for two groups costs 1.8 passes even when the second group is empty
+        // host does not launch passes for groups that are not there
         SBSH(hipMemcpyAsync(s->fill_ctrl_h, s->fill_ctrl, sizeof(FitCtrl), hipMemcpyDeviceToHost, s->st));
         SBSH(hipStreamSynchronize(s->st));
         s->cov_panel_groups += s->fill_ctrl_h->cov_groups - s->fill_groups_seen;

@@ -232,9 +232,10 @@ hipError_t launch_sel_cgr(const double *score, int len, int k, int *A_new, const
                           const TopkNeed *need, double ridge, const double *rhs, double *sol, const CholFuse *fuse,
                           int maxit, hipStream_t st, double tol);
 // ---------------------------------------------------------------------------------------------------------------
-// Merged launches over the chunk chains of one sequential path (round 5, bessx_kchunks.cpp: mc_run_chunks).  The C chains
-// of the chunk phase used to run on a stream and a host thread each; the device runs about 2.5 single-workgroup kernels
-// of different streams at a time (tools/probe/launch_rate.hip), so four chains got 2.4 x one chain's rate.  Here every
+// Merged launches over many chains (round 5, bessx_kchunks.cpp: mc_engine; today the paths of many responses,
+// bessx_multi.cpp -- the chunk chains of ONE path, which it was first built for, run faster on a stream and a host thread
+// each: DESIGN_HISTORY.md).  The device runs about 2.5 single-workgroup kernels of different streams at a time
+// (tools/probe/launch_rate.hip), so four chains on streams of their own get 2.4 x one chain's rate.  Here every
 // chain is a workgroup (or a slice of the grid) of the SAME launch on ONE stream, and the sequencing the host did per
 // chain -- which candidate, which PDAS iteration, is the fit over, open the next one -- lives in device memory:
 //   k_mc_cov_d    (grid: column blocks x chains)  d and the sacrifice scores of every chain whose coefficients changed
@@ -479,7 +480,7 @@ hipError_t launch_cov_fill_union(const CovUnion &u, int restart, const int *extr
 int cov_streamed_tiles_per_wave();
 hipError_t launch_cov_panel(const double *X, const double *aux, long ld, int p, const double *mask, const int *fcols,
                             int g0, int ngroups, int rows_per_slab, int nslab, double *part, const FitCtrl *ctrl,
-                            int parked, hipStream_t st, int variant = 3);
+                            int parked, hipStream_t st);  // k_cov_panel_dp; ngroups 1..2
 hipError_t cov_panel_prepare();
 hipError_t launch_cov_reduce(const double *part, int p, const int *fcols, const int *slot_of, double *G, int g0,
                              int ngroups, int nslab, const FitCtrl *ctrl, int parked, hipStream_t st,

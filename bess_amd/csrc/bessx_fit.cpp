@@ -119,15 +119,8 @@ int enqueue_lm_slot(bessx_session *s, int slot, int T0, double lambda, int rs, b
 // Form the Gram columns of the fill list, 2 groups of 32 columns per launch pair (the slab partials of a launch
 // share one work space).  parked = 1: for a parked fit, 0: start of a fit.  The panel kernel is the one kernel
 // of this mode that reads X: its launches are timed like the streaming score pass (k1_*).
-// Two groups in one launch (a fill of more than 32 columns: cold starts, the chunks of a sharded path): the pair panel
-// kernel forms both in ONE pass over X (1.36 ms against 2 x 0.76 ms); single groups keep the default.
-int panel_variant_for(const bessx_session *s, int ng) {
-  // 3 = k_cov_panel_lds2 (one 32-column group per block), 4 = k_cov_panel_pair (two groups per pass),
-  // 5 = k_cov_panel_dp (round 5: one workgroup per compute unit, two LDS tiles, software-pipelined; one or two groups)
-  if (s->panel_variant == 5) return 5;
-  return ng == 2 ? 4 : 3;
-}
-
+// Two groups in one launch (a fill of more than 32 columns: cold starts, the chunks of a sharded path): the panel
+// kernel forms both in ONE pass over X.
 // gfirst / compact: a cooperative prefill (bessx_session_cov_prefill_*) forms only SOME groups of the list here and
 // fills the slot-indexed Gram GS once every group is in (its own and the ones imported from the other ranks)
 // slot_map: the map the reduction and the compaction place the new columns by (staged fills of chunk chains: the
@@ -146,7 +139,7 @@ int enqueue_cov_fill(bessx_session *s, int rs, int ngroups, int parked, const Fi
       // one unmasked pass over the fold-major copy serves every row set: the columns enter ALL caches (same slots)
       const int nsl_all = s->K * s->cvp_nsl;
       e = launch_cov_panel(s->Xp, s->zp, s->ldp, s->p, nullptr, s->cov_fcols, g0, ng, s->cvp_rps, nsl_all, s->cvp_part,
-                           gc, parked, s->st, panel_variant_for(s, ng));
+                           gc, parked, s->st);
       if (s->timing && e == hipSuccess) {
         e = hipEventRecord(eb, s->st);
         s->cov_timed.push_back({s->ev_used - 2, g0});
@@ -178,7 +171,7 @@ int enqueue_cov_fill(bessx_session *s, int rs, int ngroups, int parked, const Fi
       continue;
     }
     e = launch_cov_panel(s->X, s->aux, s->ld, s->p, s->mask[rs], s->cov_fcols, g0, ng, s->cov_rps,
-                         s->cov_nslab, s->cov_part, gc, parked, s->st, panel_variant_for(s, ng));
+                         s->cov_nslab, s->cov_part, gc, parked, s->st);
     if (s->timing && e == hipSuccess) {
       e = hipEventRecord(eb, s->st);
       s->cov_timed.push_back({s->ev_used - 2, g0});
@@ -813,7 +806,7 @@ static int group_eig_ensure(bessx_session *s, int rs, double lambda) {
 
 // Grouped LM in the covariance form: a fit parked on missing Gram columns (cov_stall = 1).  The fill list is built on the
 // host -- the missing columns, then the uncached columns of the groups this iteration's sacrifices rank highest, whole
-// groups first (a group enters the active set with all its columns), 64 columns in all: one pass of the pair kernel --
+// groups first (a group enters the active set with all its columns), 64 columns in all: one pass of the panel kernel --
 // and takes the next free slots of the cache (prefill_begin, in-fit form).  Then the wake-up; the caller queues the rest
 // of the stalled slot.
 static int grouped_cov_fill(bessx_session *s, const FitCtrl *hc, int T0) {

@@ -347,7 +347,7 @@ struct bessx_session {
   bool cov_mode = false;
   int cov_cs = 512;        // slots covered by the slot-indexed Gram GS (BESSX_COV_CS <= 512: test hook for the mixed gather)
   double cg_tol = 1e-13;   // accepted relative residual of the conjugate-gradient solve (BESSX_CG_TOL)
-  int cov_spec = 32;       // most speculative columns per fill: 64 with the pair panel kernel (variant 4), else 32
+  int cov_spec = 32;       // most speculative columns per fill
   int cov_spec_min = 8;    // a private fill's list is rounded up to the multiple of 32 that leaves room for this many (test hook cov_spec_min)
   bool fuse_sel = true;    // selection + solve of a slot in one launch, k_sel_cgr (test hook fuse_sel=0: two launches)
   bool cg_by_rows = true;  // row-dealt kernel k_cgr for systems of up to 208 unknowns (test hook cg_layout=tiles: k_cg)
@@ -421,7 +421,6 @@ struct bessx_session {
   bool light_confirm = true;            // GLM / Cox: the tail right behind the head of a PDAS iteration >= 2 (bessx_fit.cpp)
   bool kch_fill_tried = false;          // the fill stream of the staged fills was asked for once (there or not)
   bool kch_sp_member = false;           // (chain context) its thread takes part in the owner's shared passes over X
-  int kch_sp_group = 0;                 // ... in this group of chains (the groups alternate on the pass stream)
   long long sp_launches = 0, sp_chain_slots = 0, sp_partial = 0;  // shared passes: launches, open gates in them, batches cut short
   int *kch_slot_w = nullptr;            // (owner) the writer's slot map of staged fills, p ints
   hipStream_t kch_fill_st = nullptr;    // (owner) the stream the chains' staged fills run on (some compute units left out)
@@ -436,11 +435,9 @@ struct bessx_session {
   long long multi_batched = 0, multi_host = 0, multi_fills = 0;
   long long x_host_bytes = 0, x_dev_bytes = 0;  // bytes of X uploaded from host memory / ingested from device memory
   bool fcols_wide = false;  // cov_fcols holds every column (+ 4 COV_R): the union fill of many responses' lists
-  long long kch_merged = 0, kch_takeovers = 0;  // chunk phases run as merged launches; chains the host had to finish
   long long kch_paths = 0, kch_refits = 0, kch_chunk_fills = 0;  // paths run chunked, stitch refits, fills in the chunk phase
   int kch_last_chains = 0;              // chains of the last chunked path
   bool kch_auto_off = false;            // the chunks of a path did not merge with the chain: the automatic choice is one chain
-  int panel_variant = 0;                // 5: k_cov_panel_dp for the fills (default; test hook panel=lds: 0, the round-2 kernels)
   int cov_panel_blocks = 0;             // workgroups of one panel pass with the slab count chosen at creation
   bool own_hw_queue = false;            // (fit contexts) the context's stream has a hardware queue outside the runtime's pool
   long long group_xtx_ns = 0;           // device time of the last all-rows group_XTX pass inside a path call (LM, timing on)
@@ -591,7 +588,6 @@ int cov_C_dev(const bessx_session *s);
 bool cov_speculates(const bessx_session *s);
 int enqueue_lm_slot(bessx_session *s, int slot, int T0, double lambda, int rs, bool skip_k1,
                            std::vector<std::pair<size_t, bool>> &k1_pairs, int part = 0);
-int panel_variant_for(const bessx_session *s, int ng);
 int enqueue_cov_fill(bessx_session *s, int rs, int ngroups, int parked, const FitCtrl *gate = nullptr,
                             int gfirst = 0, bool compact = true, const int *slot_map = nullptr);
 CholFuse cov_fuse_args(bessx_session *s, int rs, int T0, bool force_chol, SlotFuse *sf);

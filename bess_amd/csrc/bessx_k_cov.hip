@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_cov_fill_list(int *__restrict__ fcols, 
   // spec_max = 32: the list is rounded up to the next multiple of 32 that leaves room for >= spec_min speculative columns
   // (round 5: 8, before 16 -- the second group of a two-group launch costs 0.46 ms where a launch of its own costs 0.78,
   // so 50 missing columns are better served by 64 now and 64 at the next miss than by 96 + 32 + 32: DESIGN.md 3a);
-  // spec_max = 64 (pair panel kernel: two groups per pass over X): to the next multiple of 64
+  // spec_max = 64 (two groups per pass over X): to the next multiple of 64
   // spec = 2 (round 5; caches that are never started over): the host selected 64 extras, so that the list is FULL up to
   // its multiple of 32 whatever nm is (with 32 extras a list of 50 missing columns was rounded to 96 with 14 empty
   // places -- columns of a pass over X that computed nothing)
@@ -238,289 +238,35 @@ __global__ void __launch_bounds__(256) k_cov_fill_union(const CovUnion u, int re
   }
 }
 
-// The panel kernel: one BLOCK (4 waves) = 64 streamed columns x 32 right-hand-side columns on one row slab; big = 1:
-// issued by the host for a parked fit (no slot gate), covers groups g0 .. g0+ngroups-1.
-// Global loads are coalesced the way the streaming score pass does it -- a wave instruction reads 512 contiguous
-// bytes of each of two columns (64 rows) -- into registers, then to an LDS tile [column][row] (row stride padded to
-// 66 doubles: conflict-free 16-byte reads in the MFMA operand layout).  Wave w multiplies streamed tile w with both
-// right-hand-side tiles.  (Round 2 measured this design against direct-to-register loads, a double-buffered tile, LDS-DMA
-// staging with 64- and 32-row chunks and a copy of X in the MFMA operand layout: DESIGN.md 3a; only the two kernels
-// that won are kept -- this one, and the pair kernel for launches of two groups.)
-constexpr int CP_RB = 64;            // rows per chunk
-#ifndef CP_PAD
-#define CP_PAD 2
-#endif
-constexpr int CP_LD = CP_RB + CP_PAD;  // padded row stride of a column in LDS (doubles)
-constexpr int CP_COLS = 64 + COV_R;  // columns staged per chunk
-// The loads run TWO chunks ahead (two register stages, one LDS tile, two barriers per chunk): more bytes in flight per
-// CU at the LDS footprint of one tile (2-3 blocks per CU).
-template <bool MASKED>
-__global__ void __launch_bounds__(256) k_cov_panel_lds2(const double *__restrict__ X, const double *__restrict__ aux,
-                                                        long ld, int p, const double *__restrict__ mask,
-                                                        const int *__restrict__ fcols, int g0, int ngroups,
-                                                        int rows_per_slab, int nslab, int njg,
-                                                        double *__restrict__ part, const FitCtrl *__restrict__ ctrl,
-                                                        int big) {
-  KT(5);
-  if (big ? !ctrl->cov_stall : (ctrl->done || ctrl->l != 0)) return;
-  const int nfill = ctrl->cov_nfill;
-  const long per_group = (long)nslab * njg;
-  const int gl = (int)(blockIdx.x / per_group);
-  if (gl >= ngroups || (g0 + gl) * COV_R >= nfill) return;
-  const int rem = (int)(blockIdx.x - (long)gl * per_group);
-  const int slab = rem / njg, jg = rem - slab * njg;
-  PCLK_BEGIN();
-  extern __shared__ double smem[];  // [CP_COLS][CP_LD]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, q = lane >> 4;
-  const int ru = tid & 31, cbase = tid >> 5;
-  const double *src[12];
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    const int cc = i * 8 + cbase;
-    int col;
-    if (cc < 64) {
-      const int j = jg * 64 + cc;
-      col = j < p ? j : -1;
-    } else {
-      col = fcols[(g0 + gl) * COV_R + cc - 64];
-    }
-    src[i] = gram_col(X, aux, ld, col) + 2 * ru;
-  }
-  const long r_begin = (long)slab * rows_per_slab, r_end = min(r_begin + rows_per_slab, ld);
-  const int nchunk = (int)((r_end - r_begin + CP_RB - 1) / CP_RB);
-  d2 stA[12], stB[12], mA, mB;
-#define CP_LOAD(st, ms, r)                                                                                     \
-  do {                                                                                                         \
-    _Pragma("unroll") for (int i = 0; i < 8; i++) st[i] =                                                      \
-        __builtin_nontemporal_load(reinterpret_cast<const d2 *>(src[i] + (r)));                                \
-    _Pragma("unroll") for (int i = 8; i < 12; i++) st[i] = *reinterpret_cast<const d2 *>(src[i] + (r));        \
-    if (MASKED) ms = *reinterpret_cast<const d2 *>(mask + (r) + 2 * ru);                                       \
-  } while (0)
-#define CP_STORE(st, ms)                                                                                       \
-  do {                                                                                                         \
-    double *dst = smem + 2 * ru;                                                                               \
-    _Pragma("unroll") for (int i = 0; i < 12; i++) {                                                           \
-      d2 v = st[i];                                                                                            \
-      if (MASKED && i >= 8) v = v * ms;                                                                        \
-      *reinterpret_cast<d2 *>(dst + (size_t)(i * 8 + cbase) * CP_LD) = v;                                      \
-    }                                                                                                          \
-  } while (0)
-  d4 acc0 = d4{0.0, 0.0, 0.0, 0.0}, acc1 = d4{0.0, 0.0, 0.0, 0.0};
-  const double *pa = smem + (size_t)(wv * 16 + c) * CP_LD + 4 * q;
-  const double *pb0 = smem + (size_t)(64 + c) * CP_LD + 4 * q, *pb1 = smem + (size_t)(80 + c) * CP_LD + 4 * q;
-  auto compute = [&]() {
-#pragma unroll
-    for (int s = 0; s < CP_RB / 16; s++) {
-      const d2 a0 = *reinterpret_cast<const d2 *>(pa + 16 * s), a1 = *reinterpret_cast<const d2 *>(pa + 16 * s + 2);
-      const d2 x0 = *reinterpret_cast<const d2 *>(pb0 + 16 * s), x1 = *reinterpret_cast<const d2 *>(pb0 + 16 * s + 2);
-      const d2 y0 = *reinterpret_cast<const d2 *>(pb1 + 16 * s), y1 = *reinterpret_cast<const d2 *>(pb1 + 16 * s + 2);
-      const double ax = a0.x, ay = a0.y, az = a1.x, aw = a1.y;
-      const double b0x = x0.x, b0y = x0.y, b0z = x1.x, b0w = x1.y;
-      const double b1x = y0.x, b1y = y0.y, b1z = y1.x, b1w = y1.y;
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, b0x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ax, b1x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, b0y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ay, b1y, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(az, b0z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(az, b1z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, b0w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, b1w, acc1, 0, 0, 0);
-    }
-  };
-  // LDS = chunk k, stage A = chunk k+1, stage B = chunk k+2 (in flight)
-  CP_LOAD(stA, mA, r_begin);
-  CP_STORE(stA, mA);
-  if (nchunk > 1) CP_LOAD(stA, mA, r_begin + CP_RB);
-  if (nchunk > 2) CP_LOAD(stB, mB, r_begin + 2 * CP_RB);
-  __syncthreads();
-  for (int k = 0; k < nchunk; k += 2) {
-    compute();
-    __syncthreads();
-    if (k + 1 < nchunk) CP_STORE(stA, mA);
-    __syncthreads();
-    if (k + 3 < nchunk) CP_LOAD(stA, mA, r_begin + (long)(k + 3) * CP_RB);
-    if (k + 1 >= nchunk) break;
-    compute();
-    __syncthreads();
-    if (k + 2 < nchunk) CP_STORE(stB, mB);
-    __syncthreads();
-    if (k + 4 < nchunk) CP_LOAD(stB, mB, r_begin + (long)(k + 4) * CP_RB);
-  }
-#undef CP_LOAD
-#undef CP_STORE
-  const size_t tiles_per_slab = (size_t)njg * COV_NJ * 2;
-  double *out = part + (((size_t)gl * nslab + slab) * tiles_per_slab + (size_t)(jg * COV_NJ + wv) * 2) * 256;
-  *reinterpret_cast<d4 *>(out + lane * 4) = acc0;
-  *reinterpret_cast<d4 *>(out + 256 + lane * 4) = acc1;
-  PCLK_END("lds2");
-}
-
-// The panel kernel for a PAIR of 32-column groups: 64 right-hand-side columns against the same 64 streamed columns,
-// X read ONCE for both groups.  At 32 right-hand-side columns the kernel sits between its two roofs (8 flop per
-// streamed byte: 0.65 of HBM, 0.54 of the fp64 matrix cores, neither saturated because the per-chunk overheads --
-// barriers, staging stores, operand reads -- are paid per 32 KB of X); at 64 the same overheads buy twice the matrix
-// work, the kernel is bound by the fp64 MFMA rate (16 flop per streamed byte) and a path needs about half the passes
-// over X.  Same staging scheme as k_cov_panel_lds2 (coalesced 16-byte loads two chunks ahead, one LDS tile
-// [column][row + pad]); wave w multiplies streamed tile w with the four right-hand-side tiles.  If the second group
-// is beyond the fill list (decided on the device) the block does the work of the 32-column kernel.
-constexpr int CP2_COLS = 64 + 2 * COV_R;  // columns staged per chunk
-// TWO: both groups of the pair are in the fill list (decided on the device, one branch at kernel entry -- inside the
-// loop it would split the matrix-core instruction stream).  The operand reads of row step s + 1 are issued before the
-// MFMAs of step s (two operand register sets): left to the compiler, every step started with its LDS reads and a
-// full wait, exposing the LDS latency eight times per chunk.
-template <bool MASKED, bool TWO>
-__device__ __forceinline__ void cov_pair_body(const double *__restrict__ X, const double *__restrict__ aux, long ld,
-                                              int p, const double *__restrict__ mask, const int *__restrict__ fcols,
-                                              int g0, int rows_per_slab, int nslab, int njg,
-                                              double *__restrict__ part, double *smem) {
-  constexpr int NT = TWO ? 4 : 2;   // right-hand-side tiles
-  constexpr int NL = TWO ? 16 : 12;  // staged columns / 8 = loads per thread and chunk
-  const int slab = blockIdx.x / njg, jg = blockIdx.x - slab * njg;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, q = lane >> 4;
-  const int ru = tid & 31, cbase = tid >> 5;
-  // streamed columns jg * 64 + cbase + 8 i: one pointer and a uniform stride (a column beyond p re-reads the last
-  // existing one of its thread: its products land in rows >= p, which the reduce kernel never stores); right-hand-side
-  // columns: one pointer each
-  const int jc = min(jg * 64 + cbase, p - 1);
-  const double *sx = X + (size_t)jc * ld + 2 * ru;
-  const long sstride = 8 * ld;
-  const int ilim = jg * 64 + cbase < p ? (p - 1 - (jg * 64 + cbase)) / 8 : 0;  // last i whose column exists
-  const double *src[NL - 8];
-#pragma unroll
-  for (int i = 0; i < NL - 8; i++) src[i] = gram_col(X, aux, ld, fcols[g0 * COV_R + i * 8 + cbase]) + 2 * ru;
-  const long r_begin = (long)slab * rows_per_slab, r_end = min(r_begin + rows_per_slab, ld);
-  const int nchunk = (int)((r_end - r_begin + CP_RB - 1) / CP_RB);
-  d2 st[NL], ms;
-  auto load_chunk = [&](long r) {
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-      st[i] = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(sx + min(i, ilim) * sstride + r));
-#pragma unroll
-    for (int i = 8; i < NL; i++) st[i] = *reinterpret_cast<const d2 *>(src[i - 8] + r);
-    if (MASKED) ms = *reinterpret_cast<const d2 *>(mask + r + 2 * ru);
-  };
-  auto store_chunk = [&]() {
-    double *dst = smem + 2 * ru;
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-      d2 v = st[i];
-      if (MASKED && i >= 8) v = v * ms;
-      *reinterpret_cast<d2 *>(dst + (size_t)(i * 8 + cbase) * CP_LD) = v;
-    }
-  };
-  d4 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-  const double *pa = smem + (size_t)(wv * 16 + c) * CP_LD + 4 * q;
-  const double *pb = smem + (size_t)(64 + c) * CP_LD + 4 * q;  // right-hand-side tile t at pb + t * 16 * CP_LD
-  struct Ops {
-    d2 a0, a1, b0[NT], b1[NT];
-  };
-  auto read_ops = [&](int s, Ops &o) {
-    o.a0 = *reinterpret_cast<const d2 *>(pa + 16 * s);
-    o.a1 = *reinterpret_cast<const d2 *>(pa + 16 * s + 2);
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      o.b0[t] = *reinterpret_cast<const d2 *>(pb + (size_t)t * 16 * CP_LD + 16 * s);
-      o.b1[t] = *reinterpret_cast<const d2 *>(pb + (size_t)t * 16 * CP_LD + 16 * s + 2);
-    }
-  };
-  auto mfma_ops = [&](const Ops &o) {
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0.x, o.b0[t].x, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0.y, o.b0[t].y, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1.x, o.b1[t].x, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1.y, o.b1[t].y, acc[t], 0, 0, 0);
-  };
-  auto compute = [&]() {
-    Ops oa, ob;
-    read_ops(0, oa);
-#pragma unroll
-    for (int s = 0; s < CP_RB / 16; s += 2) {
-      read_ops(s + 1, ob);
-      __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise sinks the reads back in front of their use)
-      mfma_ops(oa);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 2 < CP_RB / 16) read_ops(s + 2, oa);
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_ops(ob);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // LDS = chunk k; the registers hold chunk k + 1, loaded while chunk k is multiplied (one stage: the matrix work of
-  // a chunk is twice that of the 32-column kernel, and two 240-register waves per SIMD would not fit)
-  load_chunk(r_begin);
-  store_chunk();
-  if (nchunk > 1) load_chunk(r_begin + CP_RB);
-  __syncthreads();
-#ifndef PAIR_DBG
-#define PAIR_DBG 0
-#endif
-  for (int k = 0; k < nchunk; k++) {
-    compute();
-    if (PAIR_DBG != 2) __syncthreads();
-    if (PAIR_DBG != 1 && PAIR_DBG != 3 && k + 1 < nchunk) store_chunk();
-    if (PAIR_DBG != 2) __syncthreads();
-    if (PAIR_DBG != 1 && k + 2 < nchunk) load_chunk(r_begin + (long)(k + 2) * CP_RB);
-  }
-  // the partial-sum layout of the 32-column kernels: [group][slab][tile pair] -- the reduce kernel is unchanged
-  const size_t tiles_per_slab = (size_t)njg * COV_NJ * 2;
-  double *out = part + ((size_t)slab * tiles_per_slab + (size_t)(jg * COV_NJ + wv) * 2) * 256;
-  *reinterpret_cast<d4 *>(out + lane * 4) = acc[0];
-  *reinterpret_cast<d4 *>(out + 256 + lane * 4) = acc[1];
-  if (TWO) {
-    double *out2 = out + (size_t)nslab * tiles_per_slab * 256;
-    *reinterpret_cast<d4 *>(out2 + lane * 4) = acc[NT - 2];
-    *reinterpret_cast<d4 *>(out2 + 256 + lane * 4) = acc[NT - 1];
-  }
-}
-
-template <bool MASKED>
-__global__ void __launch_bounds__(256) k_cov_panel_pair(const double *__restrict__ X, const double *__restrict__ aux,
-                                                        long ld, int p, const double *__restrict__ mask,
-                                                        const int *__restrict__ fcols, int g0, int rows_per_slab,
-                                                        int nslab, int njg, double *__restrict__ part,
-                                                        const FitCtrl *__restrict__ ctrl, int big) {
-  KT(5);
-  if (big ? !ctrl->cov_stall : (ctrl->done || ctrl->l != 0)) return;
-  const int nfill = ctrl->cov_nfill;
-  if (g0 * COV_R >= nfill) return;
-  extern __shared__ double smem[];  // [CP2_COLS][CP_LD]
-  PCLK_BEGIN();
-  if ((g0 + 1) * COV_R < nfill)     // uniform
-    cov_pair_body<MASKED, true>(X, aux, ld, p, mask, fcols, g0, rows_per_slab, nslab, njg, part, smem);
-  else
-    cov_pair_body<MASKED, false>(X, aux, ld, p, mask, fcols, g0, rows_per_slab, nslab, njg, part, smem);
-  PCLK_END("pair");
-}
-
 // ------------------------------------------------------------------------------------------
-// Round 5: the panel pass as ONE 8-wave workgroup per compute unit over 128 streamed columns, two LDS tiles, one barrier
-// per chunk (k_cov_panel_dp).
+// The panel kernel (k_cov_panel_dp): ONE 8-wave workgroup per compute unit over 128 streamed columns x 32 or 64
+// right-hand-side columns on one row slab, two LDS tiles, one barrier per chunk; big = 1: issued by the host for a
+// parked fit (no slot gate).
 //
-// What the counters and the in-kernel clock said about the two kernels above (profiles/r05_panel_*, README): HBM
-// traffic is the algorithmic 1.03 x, the LDS is 35 % busy, the waves wait to issue 70-76 % of their time -- and the
-// matrix pipe is busy 0.77 / 0.81 of the cycles that REALLY pass: the chip holds its clock at 1.5-2.1 GHz under these
-// kernels (s_memtime against s_memrealtime; the 32-column kernel, which moves more bytes per flop, clocks LOWER than
-// the pair kernel), which is where the distance to the 2.4 GHz peaks comes from.  What a kernel can still change is the
-// data it moves per flop -- every 64-column block stages its own copy of the right-hand-side columns from L2 (half as
-// many bytes again as X itself at 32 columns, as many again at 64) -- and the phases a workgroup stands still in.  Here:
-//   * 128 streamed columns per workgroup: half the right-hand-side traffic (L2 -> LDS) per byte of X;
-//   * 8 waves, wave w multiplies streamed tile w with every right-hand-side tile: two waves per SIMD, as before;
+// Global loads are coalesced the way the streaming score pass does it (16 threads x 2 rows cover a 32-row chunk of one
+// column) into registers, then to an LDS tile [column][row] (row stride padded by DP_PAD doubles: conflict-free
+// 16-byte reads in the MFMA operand layout).  The kernels of rounds 2-4 (one 4-wave block per 64 streamed columns, one
+// LDS tile, two barriers per chunk: DESIGN_HISTORY.md) were measured at HBM traffic 1.03 x the algorithmic, the LDS 35 %
+// busy, the waves waiting to issue 70-76 % of their time and the chip holding its clock at 1.5-2.1 GHz
+// (profiles/r05_panel_*, README).  What a kernel can still change is the data it moves per flop -- every workgroup
+// stages its own copy of the right-hand-side columns from L2 -- and the phases a workgroup stands still in.  Here:
+//   * 128 streamed columns per workgroup: half the right-hand-side traffic (L2 -> LDS) per byte of X of a 64-column block;
+//   * 8 waves, wave w multiplies streamed tile w with every right-hand-side tile: two waves per SIMD;
 //   * 32-row chunks, TWO LDS tiles: while chunk k is multiplied out of one, chunk k + 1 is written into the other --
 //     the stores sit between the matrix instructions of the chunk's first row step, the global loads of chunk k + 3
-//     between those of the second -- and ONE barrier per chunk (the kernels above: multiply | barrier | stage | barrier);
+//     between those of the second -- and ONE barrier per chunk;
 //   * operands of the next row step are read while the current one multiplies; loads run two to three chunks ahead in
 //     two register stages; every staging operation is unconditional (a branch around one costs the compiler its count
 //     of the loads in flight).
-// NT = 2: one 32-column group per pass, NT = 4: a pair.  Same partial-sum layout as the kernels above (k_cov_reduce is
-// unchanged).  104 KB of LDS at NT = 4, 87 KB at NT = 2.
+// NT = 2: one 32-column group per pass, NT = 4: a pair.  Partial sums: [group][slab][64-column group jg][streamed tile
+// 0..COV_NJ-1][right-hand-side tile 0..1][256] (what k_cov_reduce adds over the slabs).  104 KB of LDS at NT = 4, 87 KB
+// at NT = 2.
 // ------------------------------------------------------------------------------------------
+#ifndef DP_PAD
+#define DP_PAD 2
+#endif
 constexpr int DP_RB = 32;            // rows per chunk
-constexpr int DP_LD = DP_RB + CP_PAD;  // padded row stride of a column in LDS (doubles)
+constexpr int DP_LD = DP_RB + DP_PAD;  // padded row stride of a column in LDS (doubles)
 constexpr int DP_SC = 128;           // streamed columns per workgroup
 template <bool MASKED, int NT>
 __device__ __forceinline__ void cov_dp_body(const double *__restrict__ X, const double *__restrict__ aux, long ld,
@@ -644,8 +390,8 @@ __device__ __forceinline__ void cov_dp_body(const double *__restrict__ X, const 
 #undef DP_CHUNK
 #undef DP_LOAD1
 #undef DP_STORE1
-  // streamed tile wv of this workgroup = tile wv & 3 of the 64-column group 2 jb + (wv >> 2) in the layout of the
-  // kernels above; the last workgroup's second half may lie beyond the last group
+  // streamed tile wv of this workgroup = tile wv & 3 of the 64-column group 2 jb + (wv >> 2) in the partial-sum
+  // layout; the last workgroup's second half may lie beyond the last group
   const int jg = 2 * jb + (wv >> 2);
   if (jg < njg) {
     const size_t tiles_per_slab = (size_t)njg * COV_NJ * 2;
@@ -979,60 +725,27 @@ int cov_streamed_tiles_per_wave() { return COV_NJ; }
 
 hipError_t launch_cov_panel(const double *X, const double *aux, long ld, int p, const double *mask, const int *fcols,
                             int g0, int ngroups, int rows_per_slab, int nslab, double *part, const FitCtrl *ctrl,
-                            int parked, hipStream_t st, int variant) {
+                            int parked, hipStream_t st) {
+  if (ngroups < 1 || ngroups > 2) return hipErrorInvalidValue;
   const int pt = (p + 15) / 16, njg = (pt + COV_NJ - 1) / COV_NJ;
-  if (variant == 5 && ngroups <= 2) {
-    // one 8-wave block per (slab, 128-column group): k_cov_panel_dp (one or both groups in one pass over X)
-    const size_t ldsd = (size_t)2 * (DP_SC + 64) * DP_LD * sizeof(double);
-    const long nbd = (long)nslab * ((njg + 1) / 2);
-    if (mask)
-      hipLaunchKernelGGL(k_cov_panel_dp<true>, dim3((unsigned)nbd), dim3(512), ldsd, st, X, aux, ld, p, mask, fcols, g0,
-                         ngroups, rows_per_slab, nslab, njg, part, ctrl, parked);
-    else
-      hipLaunchKernelGGL(k_cov_panel_dp<false>, dim3((unsigned)nbd), dim3(512), ldsd, st, X, aux, ld, p, mask, fcols, g0,
-                         ngroups, rows_per_slab, nslab, njg, part, ctrl, parked);
-    LAUNCH_CHECK();
-    return hipSuccess;
-  }
-  if (variant == 4 && ngroups <= 2) {
-    // one block per (slab, 64-column group) for BOTH groups of the launch: X streamed once
-    const size_t lds2 = (size_t)CP2_COLS * CP_LD * sizeof(double);
-    const long nb2 = (long)nslab * njg;
-    if (mask)
-      hipLaunchKernelGGL(k_cov_panel_pair<true>, dim3((unsigned)nb2), dim3(256), lds2, st, X, aux, ld, p, mask, fcols,
-                         g0, rows_per_slab, nslab, njg, part, ctrl, parked);
-    else
-      hipLaunchKernelGGL(k_cov_panel_pair<false>, dim3((unsigned)nb2), dim3(256), lds2, st, X, aux, ld, p, mask, fcols,
-                         g0, rows_per_slab, nslab, njg, part, ctrl, parked);
-    LAUNCH_CHECK();
-    return hipSuccess;
-  }
-  // one block per (group, slab, 64-column group)
-  const size_t lds = (size_t)CP_COLS * CP_LD * sizeof(double);
-  const long nblk = (long)ngroups * nslab * njg;
+  // one 8-wave block per (slab, 128-column group): one or both groups in one pass over X
+  const size_t ldsd = (size_t)2 * (DP_SC + 64) * DP_LD * sizeof(double);
+  const long nbd = (long)nslab * ((njg + 1) / 2);
   if (mask)
-    hipLaunchKernelGGL(k_cov_panel_lds2<true>, dim3((unsigned)nblk), dim3(256), lds, st, X, aux, ld, p, mask, fcols, g0,
+    hipLaunchKernelGGL(k_cov_panel_dp<true>, dim3((unsigned)nbd), dim3(512), ldsd, st, X, aux, ld, p, mask, fcols, g0,
                        ngroups, rows_per_slab, nslab, njg, part, ctrl, parked);
   else
-    hipLaunchKernelGGL(k_cov_panel_lds2<false>, dim3((unsigned)nblk), dim3(256), lds, st, X, aux, ld, p, mask, fcols,
-                       g0, ngroups, rows_per_slab, nslab, njg, part, ctrl, parked);
+    hipLaunchKernelGGL(k_cov_panel_dp<false>, dim3((unsigned)nbd), dim3(512), ldsd, st, X, aux, ld, p, mask, fcols, g0,
+                       ngroups, rows_per_slab, nslab, njg, part, ctrl, parked);
   LAUNCH_CHECK();
   return hipSuccess;
 }
 
-// one-time opt-in to more than 64 KB of dynamic LDS for the staged panel kernel
+// one-time opt-in to more than 64 KB of dynamic LDS for the panel kernel
 hipError_t cov_panel_prepare() {
-  hipError_t e = hipSuccess;
-  const int lds2 = (int)((size_t)CP2_COLS * CP_LD * sizeof(double));
-  e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_panel_pair<true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_panel_pair<false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-  if (e != hipSuccess) return e;
   const int ldsd = (int)((size_t)2 * (DP_SC + 64) * DP_LD * sizeof(double));
-  e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_panel_dp<true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, ldsd);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_panel_dp<true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, ldsd);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_panel_dp<false>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, ldsd);

@@ -29,24 +29,18 @@ namespace bessx {
 // the launch waits for an event every participant records on its own stream (its vectors are ready), every participant's
 // stream waits for the event recorded behind the launch.  A pass then serves every chain that is at its score pass --
 // the chains fall into step at the passes, and the count of chains is no longer bounded by what a pass per chain costs.
-// Optionally two GROUPS of chains alternate on the pass stream (chain r belongs to group r mod 2; test hook
-// kchunks_pass_groups=2; default 1): while one group's pass runs, the other group's chains do what lies between two passes
-// -- selection, Gram, solve, residual, the IRLS / Newton steps, the host's read-back and the launches of the next slot.
-// Measured slower than the single lock-step (see sequential_path_chunked): kept as a hook.
 struct SharedPass {
-  static constexpr int GROUPS = 2;
-  PassRendezvous rdv[GROUPS];
-  int groups = 1;      // groups of this path
+  PassRendezvous rdv;
   bool on = false;     // this path's chains share their passes
   int kind = 0;        // 0: k_xtv_mc, one vector; 1: k_xtv_mc, two vectors (GLM); 2: k_cox_score1p_mc
   int cap = XTV_MC_MAX;
   hipStream_t st = nullptr;
-  std::mutex launch_mu;  // one group's (waits, launch, records) on the pass stream at a time
-  hipEvent_t ev_in[GROUPS][XTV_MC_MAX] = {};
+  std::mutex launch_mu;  // one batch's (waits, launch, records) on the pass stream at a time
+  hipEvent_t ev_in[XTV_MC_MAX] = {};
   static constexpr int RING = 8;
-  hipEvent_t ev_out[GROUPS][RING] = {};
-  XtvMc xq[GROUPS] = {};
-  CoxMc cq[GROUPS] = {};
+  hipEvent_t ev_out[RING] = {};
+  XtvMc xq = {};
+  CoxMc cq = {};
   int rc = 0;  // first launch error (reported by the path)
   // statistics: HIP events around every launch on the pass stream, and how many gates were open in it
   bool timing = false;
@@ -81,7 +75,7 @@ struct KChains {
     int a, b;
   };
   std::vector<LogRow> log;
-  // merged launches over the chains (mc_run_chunks): device copies of the chains' descriptions and states, the chunk's
+  // merged launches over the chains (mc_engine): device copies of the chains' descriptions and states, the chunk's
   // levels, the per-candidate records; pinned status block and its sequence number
   McChain *mc_chains = nullptr;
   McState *mc_states = nullptr;
@@ -151,10 +145,8 @@ static void sp_free(SharedPass &sp) {
   sp.st = nullptr;
   sp.ran = nullptr;
   sp.tev.clear();
-  for (auto &grp : sp.ev_in)
-    for (auto &e : grp) e = nullptr;
-  for (auto &grp : sp.ev_out)
-    for (auto &e : grp) e = nullptr;
+  for (auto &e : sp.ev_in) e = nullptr;
+  for (auto &e : sp.ev_out) e = nullptr;
 }
 
 // stream, events and the gate counters of the pass stream; false: not to be had (the chains then keep their own passes)
@@ -170,10 +162,8 @@ static bool sp_prepare(bessx_session *s, SharedPass &sp) {
     }
   }
   bool ok = true;
-  for (auto &grp : sp.ev_in)
-    for (auto &e : grp) ok = ok && sp.own.event(&e, hipEventDisableTiming) == hipSuccess;
-  for (auto &grp : sp.ev_out)
-    for (auto &e : grp) ok = ok && sp.own.event(&e, hipEventDisableTiming) == hipSuccess;
+  for (auto &e : sp.ev_in) ok = ok && sp.own.event(&e, hipEventDisableTiming) == hipSuccess;
+  for (auto &e : sp.ev_out) ok = ok && sp.own.event(&e, hipEventDisableTiming) == hipSuccess;
   ok = ok && sp.own.alloc(&sp.ran, SharedPass::RAN_CAP) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -184,10 +174,10 @@ static bool sp_prepare(bessx_session *s, SharedPass &sp) {
 }
 
 // (under the rendezvous' lock) launch the n requests collected as batch g
-static void sp_launch(bessx_session *o, SharedPass &sp, int grp, int n, unsigned long long g) {
+static void sp_launch(bessx_session *o, SharedPass &sp, int n, unsigned long long g) {
   std::lock_guard<std::mutex> lk(sp.launch_mu);
   hipError_t e = hipSuccess;
-  for (int i = 0; i < n && e == hipSuccess; i++) e = hipStreamWaitEvent(sp.st, sp.ev_in[grp][i], 0);
+  for (int i = 0; i < n && e == hipSuccess; i++) e = hipStreamWaitEvent(sp.st, sp.ev_in[i], 0);
   int *ran = nullptr;
   hipEvent_t ea = nullptr, eb = nullptr;
   if (sp.timing && sp.launches < SharedPass::RAN_CAP) {
@@ -206,17 +196,17 @@ static void sp_launch(bessx_session *o, SharedPass &sp, int grp, int n, unsigned
   if (ea && e == hipSuccess) e = hipEventRecord(ea, sp.st);
   if (e == hipSuccess) {
     if (sp.kind == 2) {
-      sp.cq[grp].nc = n;
-      sp.cq[grp].ran = ran;
-      e = launch_cox_score1p_mc(o->X, o->ld, o->p, o->U, o->nrb, sp.cq[grp], sp.st);
+      sp.cq.nc = n;
+      sp.cq.ran = ran;
+      e = launch_cox_score1p_mc(o->X, o->ld, o->p, o->U, o->nrb, sp.cq, sp.st);
     } else {
-      sp.xq[grp].nc = n;
-      sp.xq[grp].ran = ran;
-      e = launch_xtv_mc(o->X, o->ld, o->p, o->U, sp.xq[grp], sp.kind == 1, sp.st);
+      sp.xq.nc = n;
+      sp.xq.ran = ran;
+      e = launch_xtv_mc(o->X, o->ld, o->p, o->U, sp.xq, sp.kind == 1, sp.st);
     }
   }
   if (eb && e == hipSuccess) e = hipEventRecord(eb, sp.st);
-  if (e == hipSuccess) e = hipEventRecord(sp.ev_out[grp][g % SharedPass::RING], sp.st);
+  if (e == hipSuccess) e = hipEventRecord(sp.ev_out[g % SharedPass::RING], sp.st);
   sp.launches++;
   if (e != hipSuccess && sp.rc == 0) {
     sp.rc = (int)e;
@@ -235,12 +225,11 @@ int shared_pass_submit(bessx_session *c, const double *v, const double *v2, doub
                        const CoxBufs *cox, const FitCtrl *ctrl, int slot) {
   bessx_session *o = c->kch_owner;
   SharedPass &sp = o->kch->sp;
-  const int grp = c->kch_sp_group;
   hipError_t e_in = hipSuccess, e_out = hipSuccess;
-  sp.rdv[grp].submit(
+  sp.rdv.submit(
       [&](int i) {
         if (cox) {
-          CoxMc &q = sp.cq[grp];
+          CoxMc &q = sp.cq;
           q.TH[i] = cox->TH;
           q.CU[i] = cox->CU;
           q.CV[i] = cox->CV;
@@ -249,7 +238,7 @@ int shared_pass_submit(bessx_session *c, const double *v, const double *v2, doub
           q.ctrl[i] = ctrl;
           q.slot[i] = slot;
         } else {
-          XtvMc &q = sp.xq[grp];
+          XtvMc &q = sp.xq;
           q.v[i] = v;
           q.v2[i] = v2;
           q.part[i] = part;
@@ -257,10 +246,10 @@ int shared_pass_submit(bessx_session *c, const double *v, const double *v2, doub
           q.ctrl[i] = ctrl;
           q.slot[i] = slot;
         }
-        e_in = hipEventRecord(sp.ev_in[grp][i], c->st);  // everything this chain has queued so far: its vectors are ready
+        e_in = hipEventRecord(sp.ev_in[i], c->st);  // everything this chain has queued so far: its vectors are ready
       },
-      [&](int n, unsigned long long g) { sp_launch(o, sp, grp, n, g); },
-      [&](unsigned long long g) { e_out = hipStreamWaitEvent(c->st, sp.ev_out[grp][g % SharedPass::RING], 0); });
+      [&](int n, unsigned long long g) { sp_launch(o, sp, n, g); },
+      [&](unsigned long long g) { e_out = hipStreamWaitEvent(c->st, sp.ev_out[g % SharedPass::RING], 0); });
   if (e_in != hipSuccess || e_out != hipSuccess || sp.rc != 0)
     return fail(BESSX_ERR_HIP, std::string("shared pass over X: ") +
                                    hipGetErrorString(e_in != hipSuccess ? e_in : (e_out != hipSuccess ? e_out : (hipError_t)sp.rc)));
@@ -274,14 +263,13 @@ static void sp_leave(bessx_session *c) {
   bessx_session *o = c->kch_owner;
   SharedPass &sp = o->kch->sp;
   c->kch_sp_member = false;
-  const int grp = c->kch_sp_group;
-  sp.rdv[grp].leave([&](int n, unsigned long long g) { sp_launch(o, sp, grp, n, g); });
+  sp.rdv.leave([&](int n, unsigned long long g) { sp_launch(o, sp, n, g); });
 }
 
 static void sp_join(bessx_session *c) {
   SharedPass &sp = c->kch_owner->kch->sp;
   if (!sp.on || c->kch_sp_member) return;
-  sp.rdv[c->kch_sp_group].join();
+  sp.rdv.join();
   c->kch_sp_member = true;
 }
 
@@ -290,13 +278,8 @@ static void sp_round(KChains *k, const std::vector<bessx_session *> &who) {
   SharedPass &sp = k->sp;
   for (bessx_session *c : k->ctx) c->kch_sp_member = false;
   if (!sp.on) return;
-  int cnt[SharedPass::GROUPS] = {};
-  for (size_t i = 0; i < who.size(); i++) {
-    who[i]->kch_sp_member = true;
-    who[i]->kch_sp_group = (int)(i % (size_t)sp.groups);
-    cnt[who[i]->kch_sp_group]++;
-  }
-  for (int g = 0; g < SharedPass::GROUPS; g++) sp.rdv[g].reset(cnt[g]);
+  for (bessx_session *c : who) c->kch_sp_member = true;
+  sp.rdv.reset((int)who.size());
 }
 
 // after the path (every chain's stream is idle): the launches' times into the session's score-pass statistics
@@ -318,10 +301,8 @@ static int sp_collect(bessx_session *s, SharedPass &sp) {
     }
   }
   s->sp_launches += sp.launches;
-  for (auto &r : sp.rdv) {
-    s->sp_partial += (long long)r.partial;
-    r.partial = 0;
-  }
+  s->sp_partial += (long long)sp.rdv.partial;
+  sp.rdv.partial = 0;
   sp.tused = 0;
   sp.launches = 0;
   return 0;
@@ -514,12 +495,7 @@ int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm) {
   KChains *k = s->kch;
   if (k->pool.broken) return 1;
   k->rdv.deadline_s = s->wait_deadline_s;
-  // (LM, covariance form, only with the test hook kchunks_pipeline=1: one more context and host thread -- the coarse chain
-  // beside the chunks, see below.  Rounds 4-5 created them for every session: an idle thread woken for every round and
-  // a context's buffers and stream held for nothing)
-  const char *epl = test_hook("kchunks_pipeline");
-  const int extra = (s->model_type == 1 && s->cov_mode && epl && std::atoi(epl) != 0) ? 1 : 0;
-  while ((int)k->ctx.size() < C + extra) {
+  while ((int)k->ctx.size() < C) {
     bessx_session *c = nullptr;
     if (chain_ctx_create(s, &c) != 0) {
       (void)hipGetLastError();
@@ -528,7 +504,7 @@ int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm) {
     c->kch_index = (int)k->ctx.size();
     k->ctx.push_back(c);
   }
-  if (!k->pool_started || (int)k->pool.th.size() < C - 1 + extra) {  // one host thread per chain; the caller is one of them
+  if (!k->pool_started || (int)k->pool.th.size() < C - 1) {  // one host thread per chain; the caller is one of them
     if (k->pool_started) k->pool.stop();
     k->pool.quit = false;  // (a pool started again: no job of the previous threads' numbering is left to run)
     k->pool.ticket = 0;
@@ -536,7 +512,7 @@ int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm) {
     k->pool.job = nullptr;
     {
       const int dev = s->device;
-      k->pool.start(C - 1 + extra, [dev] { (void)hipSetDevice(dev); });
+      k->pool.start(C - 1, [dev] { (void)hipSetDevice(dev); });
     }
     k->pool_started = true;
   }
@@ -544,8 +520,7 @@ int kchunks_prepare(bessx_session *s, int ns, bool link, bool link_warm) {
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// Merged launches on ONE stream (bessx_dev.h: McChain): the chunk phase of one path, and the paths of many responses
-// (bessx_multi.cpp).  One core, mc_engine, serves both.
+// Merged launches on ONE stream (bessx_dev.h: McChain): the paths of many responses (bessx_multi.cpp), run by mc_engine.
 // ----------------------------------------------------------------------------------------------------------------
 bool mc_engine_applies(const bessx_session *s) {
   return s->model_type == 1 && s->cov_mode && s->fuse && s->fuse_sel && s->cov_cg && s->cg_by_rows;
@@ -605,10 +580,6 @@ int mc_sse_by_residual(bessx_session *c, hipStream_t st, const int *idx, const d
   *out = tr;
   return 0;
 }
-
-namespace {
-
-}  // namespace
 
 // ---- the merged-launch core (bessx_host.h: McJob): one chain = a chunk of one response's path or the whole path of one
 // response.  Buffers sized by the number of chains, every chain's first fit started, rounds of (score pass, selection +
@@ -859,145 +830,6 @@ int mc_contexts(bessx_session *s, int n) {
 
 bessx_session *mc_context(bessx_session *s, int i) { return s->kch->mc_ctx[(size_t)i]; }
 
-namespace {
-
-// The chunk phase as merged launches (mc_engine) -- the chains' own streams and host threads are not used here; the
-// stitch that follows runs as before.  Returns 0 with every chunk's candidates in run[r] (a chain the device could not
-// finish by itself is finished through sequential_path on its context: same candidates), > 0 on a failure, < 0 when
-// the engine does not apply to this path (the caller then runs the chunks on their own streams).
-int mc_run_chunks(bessx_session *s, KChains *k, const int *seq, int ns, int C, const std::vector<int> &bounds,
-                  std::vector<ChunkRun> &run, double lambda, int ic_type, int width) {
-  if (!mc_engine_applies(s) || C > 8) return -1;
-  if (!mc_applies(s->p, seq[ns - 1])) return -1;
-  // Measured on configs[1] (tools/kchunks_bench.py, profiles/README.md, round 5): NOT faster than the chains on streams
-  // of their own -- 12.4-12.6 ms per path against 12.0 with 4 chains, 12.7 with 8 -- because the merged launches run the
-  // chains in lock-step: every step costs what the chain with the largest systems needs (48 us for selection, record,
-  // selection and a 200-unknown solve) and the chunk phase is (candidates per chain) x that.  Kept behind the test hook
-  // kchunks_merged=1, exercised by tests/test_kchunks_gpu.py; the default is the stream per chain.
-  const char *mc_on = test_hook("kchunks_merged");
-  if (!(mc_on && std::string(mc_on) == "1")) return -1;
-  std::vector<McJob> jobs((size_t)C);
-  for (int r = 0; r < C; r++) {
-    McJob &j = jobs[(size_t)r];
-    j.c = k->ctx[r];
-    j.lo = j.rec0 = run[r].lo;
-    j.ncand = run[r].hi - run[r].lo;
-    j.init_idx = &run[r].init_idx;
-    j.init_val = &run[r].init_val;
-    j.init_coef0 = run[r].init_coef0;
-  }
-  McRecords recs;
-  std::vector<int> takeover;
-  if (int rc = mc_engine(s, seq, ns, jobs, ns, lambda, width, recs, takeover, &s->kch_chunk_fills)) return rc;
-  const std::vector<int> &rec_i = recs.i, &rec_A = recs.A;
-  const std::vector<double> &rec_d = recs.d, &rec_b = recs.b;
-  const McHostStatus *hstat = reinterpret_cast<const McHostStatus *>(k->mc_status_h);
-  const hipStream_t st = s->st;
-  for (int r = 0; r < C; r++) {
-    bessx_session *c = k->ctx[r];
-    ChunkRun &q = run[r];
-    q.bind(&q.res);
-    const int ncand = q.hi - q.lo;
-    int good = 0;
-    SparseVec last;
-    double last_c0 = q.init_coef0;
-    last.idx = q.init_idx;
-    last.val = q.init_val;
-    for (int i = 0; i < ncand; i++) {
-      const int g = q.lo + i;
-      if (!rec_i[(size_t)g * MC_REC_I + 3]) break;
-      const int T0 = rec_i[(size_t)g * MC_REC_I + 0];
-      if (T0 != seq[g]) return fail(BESSX_ERR_NUMERIC, "internal error: chunk chain record out of order");
-      Candidate cand;
-      cand.T0 = T0;
-      cand.lambda = lambda;
-      cand.beta.idx.assign(rec_A.begin() + (size_t)g * width, rec_A.begin() + (size_t)g * width + T0);
-      cand.beta.val.assign(rec_b.begin() + (size_t)g * width, rec_b.begin() + (size_t)g * width + T0);
-      cand.coef0 = rec_d[(size_t)g * MC_REC_D + 0];
-      cand.iters = rec_i[(size_t)g * MC_REC_I + 1];
-      // the loss from the solved system (algorithm_fit, all rows, covariance form), by a pass over the active columns
-      // where those terms cancel
-      const double yy = c->yy_h[0];
-      double tr = yy - rec_d[(size_t)g * MC_REC_D + 1] - lambda * rec_d[(size_t)g * MC_REC_D + 2];
-      if (!rec_i[(size_t)g * MC_REC_I + 2] || !(tr > 1e-6 * yy))
-        if (int rc = mc_sse_by_residual(c, st, cand.beta.idx.data(), cand.beta.val.data(), T0, cand.coef0, &tr)) return rc;
-      c->sparsity_level = T0;
-      c->lambda_level = lambda;
-      c->beta = cand.beta;
-      c->coef0 = cand.coef0;
-      c->l = cand.iters;
-      c->sse_train = tr;
-      c->sse_test = 0.0;
-      if (int rc = metric_train_loss(c, &cand.loss)) return rc;
-      if (int rc = metric_ic(c, ic_type, 0, &cand.ic)) return rc;
-      store_candidate(c, &q.res, cand, false);
-      last = cand.beta;
-      last_c0 = cand.coef0;
-      good++;
-    }
-    q.fits += good;
-    if (good < ncand) {
-      // the device stopped in this chunk (takeover): the rest through sequential_path on the context, warm from the last
-      // recorded model -- the same chain, by the proven code
-      if (!takeover[(size_t)r] && hstat[r].st.finished != 2)
-        return fail(BESSX_ERR_NUMERIC, "internal error: chunk chain ended short of its candidates");
-      s->kch_takeovers++;
-      ChunkRun rest;
-      rest.shape(q.lo + good, q.hi, width, s->p_full);
-      rest.bind(&rest.res);
-      rest.chain = bessx_path_chain();
-      rest.chain.init_idx = last.idx.data();
-      rest.chain.init_val = last.val.data();
-      rest.chain.init_len = (int)last.idx.size();
-      rest.chain.init_coef0 = last_c0;
-      rest.chain.keep_caches = 1;
-      rest.chain.last_idx = rest.last_idx.data();
-      rest.chain.last_val = rest.last_val.data();
-      rest.chain.last_cap = width;
-      if (int rc = context_begin(c)) return rc;
-      KChains *own = c->kch_owner ? c->kch_owner->kch : nullptr;
-      (void)own;
-      kchains_round(k, 1);  // (one chain runs: a fill of its own finds everybody else standing still)
-      int rc = sequential_path(c, seq + q.lo + good, ncand - good, &lambda, 1, ic_type, 0, &rest.res, &rest.chain);
-      if (rc == 0 && hipStreamSynchronize(c->st) != hipSuccess) rc = fail(BESSX_ERR_HIP, "chunk chain: stream");
-      kchains_leave(k, rc != 0);
-      if (rc) return rc;
-      for (int i = 0; i < ncand - good; i++) {
-        const int gi = good + i;  // (copied field by field into the chunk's arrays: they are already de-normalised)
-        q.T0[gi] = rest.T0[i];
-        q.iters[gi] = rest.iters[i];
-        q.lam[gi] = rest.lam[i];
-        q.loss[gi] = rest.loss[i];
-        q.ic[gi] = rest.ic[i];
-        q.coef0[gi] = rest.coef0[i];
-        std::copy(rest.support.begin() + (size_t)i * width, rest.support.begin() + (size_t)(i + 1) * width,
-                  q.support.begin() + (size_t)gi * width);
-        std::copy(rest.beta.begin() + (size_t)i * width, rest.beta.begin() + (size_t)(i + 1) * width,
-                  q.beta.begin() + (size_t)gi * width);
-      }
-      q.res.n_candidates = ncand;
-      q.fits += c->n_fits;
-      q.last_idx = rest.last_idx;
-      q.last_val = rest.last_val;
-      q.last_len = rest.chain.last_len;
-      q.last_coef0 = rest.chain.last_coef0;
-    } else {
-      q.last_len = (int)last.idx.size();
-      for (int i = 0; i < q.last_len && i < width; i++) {
-        q.last_idx[(size_t)i] = last.idx[(size_t)i];
-        q.last_val[(size_t)i] = last.val[(size_t)i];
-      }
-      q.last_coef0 = last_c0;
-    }
-    for (auto &cc : c->cache) cc.valid = cc.model_only = false;  // (the device state of the context is the engine's, not a fit's of its own)
-    c->dev_state_rs = -1;
-  }
-  s->kch_merged++;
-  return 0;
-}
-
-}  // namespace
-
 int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lambda, int ic_type,
                             bessx_path_result *res, bessx_path_chain *link) {
   const int C = chains_for(s, ns, link != nullptr, link && link->init_len > 0 && link->keep_caches);
@@ -1039,65 +871,33 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
   const bool lm_cov = s->model_type == 1 && s->cov_mode;
   // Staged fills (bessx_sync.h: FillRendezvous, concurrent rounds; test hook kchunks_staged=0/1): a chain's fill writes
   // slots no other chain can see until its last launch publishes them, so nobody stands still for a fill.
-  // The pipeline (test hook kchunks_pipeline=0/1; needs staged fills and the extra context): the coarse chain runs on a
-  // context of its own BESIDE the chunks -- chunk 0 starts with it, chunk r as soon as the coarse fit at its lower
-  // boundary is done -- instead of in front of them.
-  bool staged = false, pipeline = false;
+  bool staged = false;
   if (lm_cov) {
     const char *ev = test_hook("kchunks_staged");
     staged = !ev || std::atoi(ev) != 0;  // (default; 0: round 4's rendezvous -- every chain stands still for a fill)
-    const char *ep = test_hook("kchunks_pipeline");
-    // (not for a link of a longer chain: the columns of the model it starts from are formed by the coarse chain's
-    // first fit, which must then be over before chunk 0 looks them up)
-    pipeline = ep && std::atoi(ep) != 0 && (int)k->ctx.size() > C && (int)k->pool.th.size() >= C && link == nullptr;
-    if (pipeline) staged = true;
   }
   if (staged && !s->kch_slot_w && k->own.alloc(&s->kch_slot_w, (size_t)s->p) != hipSuccess) {
     (void)hipGetLastError();
-    staged = pipeline = false;
+    staged = false;
   }
   if (staged && !s->kch_fill_st && !s->kch_fill_tried) {
     s->kch_fill_tried = true;  // (decided once per session: no unit to leave out, or no such stream to be had)
     // the fills' stream: every compute unit but a few (test hook kchunks_reserve=count[:stride of the mask bits]; 0: the
     // fills run on the filling chain's own stream)
-    int leave = 16, stride = 1;
-    if (s->panel_variant == 5) {
-      // k_cov_panel_dp runs ONE workgroup per compute unit: the units left out must be ones its rounds of workgroups
-      // leave idle anyway (configs[1]: 237 workgroups, one round), or a pass on the fill stream would take a round more
-      hipDeviceProp_t prop;
-      const int cus = hipGetDeviceProperties(&prop, s->device) == hipSuccess ? prop.multiProcessorCount : 0;
-      // (the most units that can go without a round more: rounds = ceil(blocks / units) must stay what it is)
-      const int blocks = s->cov_panel_blocks;
-      const int rounds = (cus > 0 && blocks > 0) ? (blocks + cus - 1) / cus : 0;
-      const int idle = rounds > 0 ? cus - (blocks + rounds - 1) / rounds : 0;
-      leave = idle >= 4 ? std::min(16, idle) : 0;
-    }
+    // k_cov_panel_dp runs ONE workgroup per compute unit: the units left out must be ones its rounds of workgroups
+    // leave idle anyway (configs[1]: 237 workgroups, one round), or a pass on the fill stream would take a round more
+    hipDeviceProp_t prop;
+    const int cus = hipGetDeviceProperties(&prop, s->device) == hipSuccess ? prop.multiProcessorCount : 0;
+    // (the most units that can go without a round more: rounds = ceil(blocks / units) must stay what it is)
+    const int blocks = s->cov_panel_blocks;
+    const int rounds = (cus > 0 && blocks > 0) ? (blocks + cus - 1) / cus : 0;
+    const int idle = rounds > 0 ? cus - (blocks + rounds - 1) / rounds : 0;
+    int leave = idle >= 4 ? std::min(16, idle) : 0, stride = 1;
     if (const char *er = test_hook("kchunks_reserve")) {
       leave = std::max(0, std::atoi(er));
       if (const char *c2 = std::strchr(er, ':')) stride = std::max(1, std::atoi(c2 + 1));
     }
     if (leave > 0 && !ctx_stream_create(s->device, &s->kch_fill_st, leave, stride)) s->kch_fill_st = nullptr;
-  }
-  if (lm_cov && (pipeline || test_hook("kchunks_weights"))) {
-    // chunk lengths by weight (test hook kchunks_weights=w0:w1:...).  Pipeline: chunk r starts when coarse fit r is
-    // done -- the later a chunk starts the shorter it is (default: falling linearly to a third)
-    std::vector<double> w((size_t)C, 1.0);
-    for (int r = 0; r < C && pipeline; r++) w[(size_t)r] = 1.0 - (2.0 / 3.0) * r / std::max(1, C - 1);
-    if (const char *ew = test_hook("kchunks_weights")) {
-      int r = 0;
-      for (const char *q = ew; *q && r < C; r++) {
-        w[(size_t)r] = std::max(0.05, std::atof(q));
-        while (*q && *q != ':') q++;
-        if (*q == ':') q++;
-      }
-    }
-    double tot = 0.0, acc = 0.0;
-    for (double v : w) tot += v;
-    for (int r = 1; r < C; r++) {
-      acc += w[(size_t)r - 1];
-      bounds[(size_t)r] = std::min(std::max((int)std::lround(ns * acc / tot), bounds[(size_t)r - 1] + 1), ns - (C - r));
-    }
-    bounds[(size_t)C] = ns;
   }
   const auto t_begin = now();
   {
@@ -1127,10 +927,10 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
   // In front of the chunks: at most COARSE_MAX coarse fits, at chunk boundaries spread evenly over the path: with more
   // chunks than that a chunk starts from the nearest coarse model below it (or cold, in front of the first one) -- its
   // own first fits bridge the gap side by side with the other chunks, where a coarse fit per chunk (7 for 8 chunks:
-  // + 1.2 ms on configs[1]) would run before any of them.  Beside the chunks (pipeline): one per boundary.
+  // + 1.2 ms on configs[1]) would run before any of them.
   // Starting points only: the stitch makes the path the single chain's.
   constexpr int COARSE_MAX = 3;
-  int M = lm_cov ? (pipeline ? C - 1 : std::min(C - 1, COARSE_MAX)) : 0;  // (no cache to fill otherwise)
+  int M = lm_cov ? std::min(C - 1, COARSE_MAX) : 0;  // (no cache to fill otherwise)
   if (const char *ev = test_hook("kchunks_coarse")) M = std::max(0, std::min(M, std::atoi(ev)));  // (0: every chunk starts cold)
   std::vector<int> coarse_at;  // coarse fit m (1-based) ends at the lower boundary of chunk coarse_at[m - 1]
   {
@@ -1152,8 +952,7 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
   };
   std::vector<CoarseModel> coarse_model(coarse_at.size() + 1);
   long long coarse_fits = 0;
-  auto t_coarse = t_begin;
-  if (!pipeline) {
+  {
     // ---- 1. the coarse chain on the session's own state (the caller has just started the caches over)
     SparseVec init = link_init;
     double c0 = link_c0;
@@ -1166,7 +965,6 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     if (int rc = settle_device_chain(s)) return rc;
     HIPX(hipStreamSynchronize(s->st));  // the cache is complete before any chunk chain reads it
     coarse_fits = s->n_fits;
-    t_coarse = now();
     for (int r = 0; r < C; r++)
       if (start_of[(size_t)r] > 0) {
         const CoarseModel &cm = coarse_model[(size_t)start_of[(size_t)r]];
@@ -1175,8 +973,9 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
         run[(size_t)r].init_coef0 = cm.c0;
       }
   }
+  const auto t_coarse = now();
   // The writer's slot map is a copy of the readers' whenever a round of chains starts (no fill is in flight between two
-  // rounds; what ran in between -- the coarse chain, a chunk phase as merged launches -- filled through the readers' map)
+  // rounds; what ran in between -- the coarse chain -- filled through the readers' map)
   auto writer_map_in_step = [&]() -> int {
     if (!staged) return 0;
     HIPX(hipMemcpyAsync(s->kch_slot_w, s->cov[0].slot_of, (size_t)s->p * sizeof(int), hipMemcpyDeviceToDevice, s->st));
@@ -1186,12 +985,9 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
   if (int rc = writer_map_in_step()) return rc;
   if (lm_cov)
     for (bessx_session *c : k->ctx) c->cov[0].slot_w = staged ? s->kch_slot_w : nullptr;
-  // ---- 2. the chunks side by side: as merged launches on the session's stream where that applies (LM, the fused
-  // selection + solve kernels' range), else on a stream and a host thread each
+  // ---- 2. the chunks side by side, on a stream and a host thread each
   for (int r = 0; r < C; r++) run[r].shape(bounds[r], bounds[r + 1], width, s->p_full);
-  const int merged = pipeline ? -1 : mc_run_chunks(s, k, seq, ns, C, bounds, run, lambda, ic_type, width);
-  if (merged > 0) return merged;
-  kchains_round(k, C + (pipeline ? 1 : 0), staged);
+  kchains_round(k, C, staged);
   {
     // the chains of the streaming forms share their passes over X (SharedPass above; test hook kchunks_shared_pass=0:
     // a pass per chain, as in round 5)
@@ -1199,32 +995,19 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     const char *eh = test_hook("kchunks_shared_pass");
     sp.kind = s->model_type == 1 ? 0 : (s->model_type == 4 ? 2 : 1);
     sp.cap = sp.kind == 2 ? COX_MC_MAX : XTV_MC_MAX;
-    // (one group: two alternating groups -- one group's selection / solve / IRLS steps under the other group's pass --
-    // were built and measured SLOWER, 131 against 91 ms on the streaming configs[1] path with 4 chains, 95 against 84 ms on
-    // logistic with 8: every pass then serves half the chains, and the small kernels run 3-8 x slower beside a pass)
-    sp.groups = 1;
-    if (const char *eg = test_hook("kchunks_pass_groups")) sp.groups = std::max(1, std::min(SharedPass::GROUPS, std::atoi(eg)));
-    sp.on = !lm_cov && C >= 2 && (C + sp.groups - 1) / sp.groups <= sp.cap && (!eh || std::atoi(eh) != 0) &&
+    sp.on = !lm_cov && C >= 2 && C <= sp.cap && (!eh || std::atoi(eh) != 0) &&
             (sp.kind != 2 || s->cox.one_pass) && sp_prepare(s, sp);
     sp.timing = s->timing;
     sp.rc = 0;
-    for (auto &r : sp.rdv) r.timeout_s = std::min(0.05, s->wait_deadline_s);
+    sp.rdv.timeout_s = std::min(0.05, s->wait_deadline_s);
     sp_round(k, std::vector<bessx_session *>(k->ctx.begin(), k->ctx.begin() + C));
   }
-  struct Starts {  // (pipeline) which coarse fits are done
-    std::mutex mu;
-    std::condition_variable cv;
-    int done = 0;
-    bool failed = false;
-  } starts;
-  int coarse_rc = 0;
-  std::string coarse_err;
   // The stitch's first round, early (test hook kchunks_early_stitch=0 switches it off): the thread of chunk r - 1, when its
   // chunk is walked, re-fits the first candidates of chunk r from its own last model on its own (now idle) context while
   // the later chunks are still running -- what round 1 of the stitch below would do after ALL chunks have ended.  It
   // compares with the rows chunk r has stored by then (kchains_progress); a refit that could not see `budget` rows is
   // thrown away and done again in round 1.
-  bool early_on = !pipeline && C <= 9;
+  bool early_on = C <= 9;
   if (const char *ee = test_hook("kchunks_early_stitch")) early_on = early_on && std::atoi(ee) != 0;
   std::vector<ChunkRun> early_st((size_t)C);
   std::vector<char> early_ok((size_t)C, 0);
@@ -1279,63 +1062,11 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     else (void)hipGetLastError();
     kchains_log(c, "early stitch done", t.res.n_candidates, t.chain.stopped_at);
   };
-  auto coarse_job = [&] {
-    bessx_session *w = k->ctx[(size_t)C];
-    int rc = hipSetDevice(s->device) == hipSuccess ? context_begin(w) : fail(BESSX_ERR_HIP, "hipSetDevice");
-    w->timing = s->timing;
-    w->hint.on = false;
-    SparseVec init = link_init;
-    double c0 = link_c0;
-    for (size_t m = 0; m < coarse_at.size() && rc == 0; m++) {
-      rc = run_fit(w, seq[bounds[(size_t)coarse_at[m]] - 1], lambda, init, c0);
-      if (rc) break;
-      init = w->beta;
-      c0 = w->coef0;
-      {
-        std::lock_guard<std::mutex> lk(starts.mu);
-        coarse_model[m + 1] = {init.idx, init.val, c0};
-        starts.done = (int)m + 1;
-      }
-      kchains_log(w, "coarse fit done", seq[bounds[(size_t)coarse_at[m]] - 1], w->l);
-      starts.cv.notify_all();
-    }
-    if (rc == 0) rc = settle_device_chain(w);
-    if (rc == 0 && hipStreamSynchronize(w->st) != hipSuccess) rc = fail(BESSX_ERR_HIP, "coarse chain: stream");
-    if (rc) {
-      coarse_err = g_err;
-      {
-        std::lock_guard<std::mutex> lk(starts.mu);
-        starts.failed = true;
-      }
-      starts.cv.notify_all();
-    }
-    coarse_rc = rc;
-    coarse_fits = w->n_fits;
-    t_coarse = now();
-    kchains_leave(k, rc != 0);
-  };
   auto chunk_job = [&](int r) {
-    if (pipeline && r == C) {
-      coarse_job();
-      return;
-    }
     if (r >= C) return;
     bessx_session *c = k->ctx[r];
     ChunkRun &q = run[r];
     q.rc = 0;
-    if (pipeline && start_of[(size_t)r] > 0) {  // its starting model: the coarse fit at its lower boundary
-      std::unique_lock<std::mutex> lk(starts.mu);
-      const bool ok = bessx_timed_wait(starts.cv, lk, s->wait_deadline_s,
-                                       [&] { return starts.done >= start_of[(size_t)r] || starts.failed; });
-      if (!ok || starts.failed) {
-        q.rc = fail(BESSX_ERR_HIP, "chunk chain: the coarse chain did not deliver its starting model");
-      } else {
-        const CoarseModel &cm = coarse_model[(size_t)start_of[(size_t)r]];
-        q.init_idx = cm.idx;
-        q.init_val = cm.val;
-        q.init_coef0 = cm.c0;
-      }
-    }
     if (q.rc == 0) q.rc = hipSetDevice(s->device) == hipSuccess ? context_begin(c) : fail(BESSX_ERR_HIP, "hipSetDevice");
     c->timing = s->timing;  // (its fills count in the session's score-pass statistics)
     kchains_log(c, "chunk starts", q.lo, q.hi);
@@ -1363,12 +1094,9 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     sp_leave(c);
     kchains_leave(k, q.rc != 0);
   };
-  if (merged < 0) {
-    if (!k->pool.run(chunk_job, s->wait_deadline_s)) return fail(BESSX_ERR_HIP, "chunk chains: a host thread did not come back");
-    if (pipeline && coarse_rc) return fail(coarse_rc, "coarse chain: " + coarse_err);
-    for (int r = 0; r < C; r++)
-      if (run[r].rc) return fail(run[r].rc, "chunk chain: " + run[r].err);
-  }
+  if (!k->pool.run(chunk_job, s->wait_deadline_s)) return fail(BESSX_ERR_HIP, "chunk chains: a host thread did not come back");
+  for (int r = 0; r < C; r++)
+    if (run[r].rc) return fail(run[r].rc, "chunk chain: " + run[r].err);
   const auto t_chunks = now();
   // ---- 3. the stitch, in rounds until no chunk's last model changed (bess_amd.dist.StitchedKPath.step)
   // A chunk whose refit has not met its own chain after `budget` candidates is on another trajectory than the warm
@@ -1383,7 +1111,7 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
   for (int round = 1;; round++) {
     std::vector<ChunkRun> st((size_t)C);
     std::vector<char> have((size_t)C, 0);  // refits of this round that are there already (the early stitch)
-    if (round == 1 && merged < 0)
+    if (round == 1)
       for (int r = 1; r < C; r++)
         if (early_ok[(size_t)r]) {
           st[(size_t)r] = std::move(early_st[(size_t)r]);

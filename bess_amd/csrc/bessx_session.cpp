@@ -1161,8 +1161,8 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
                                       "(at most 16 columns) only"));
     if (eligible && mode != 1) {
       // capacity: every column if p is small, else a few active sets' worth, within 1 GiB per row set
-      // (fills of exactly two groups take the pair panel kernel, one pass for 64 columns; the switches that made every
-      // fill speculate 64 columns, or never paired, measured at parity in rounds 2-3 and are gone)
+      // (fills of two groups form both in one pass of the panel kernel; the switches that made every fill speculate 64
+      // columns, or never paired, measured at parity in rounds 2-3 and are gone)
       s->cov_spec = COV_R;
       if (const char *ev = test_hook("cov_spec_min")) s->cov_spec_min = std::max(1, std::min(COV_R - 1, std::atoi(ev)));  // (16: rounds 2-4)
       // capacity: EVERY column when that fits 2 GiB per row set (p <= ~16000: a path then forms a column at most once and
@@ -1178,23 +1178,17 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
         s->cov_mode = true;
         s->cov_C = (int)C;
         const int pt = (p + 15) / 16, njg = (pt + cov_streamed_tiles_per_wave() - 1) / cov_streamed_tiles_per_wave();
-        // row slabs: two 256-thread blocks of the panel kernel share a CU (50 KB of LDS each), so pick the slab count
-        // whose block count wastes the least of the last round of 512 blocks
-        // the fills' kernel: k_cov_panel_dp (round 5; the default since the chunk chains' coarse phase became a dense
-        // run of passes, where it is 3-4 % faster per pass: DESIGN.md 13); test hook panel=lds: k_cov_panel_lds2 / _pair
-        s->panel_variant = 5;
-        if (const char *ev = test_hook("panel")) s->panel_variant = std::string(ev) == "dp" ? 5 : 0;
+        // row slabs: k_cov_panel_dp runs one 8-wave block per compute unit over 128 streamed columns, so pick the slab
+        // count whose block count wastes the least of the last round of 256 blocks
         long ns = 1, rps = ld;
         long panel_blocks = 0;
         {
-          // (k_cov_panel_dp: one 8-wave block per compute unit, 128 streamed columns per block)
-          const bool dp = s->panel_variant == 5;
-          const long conc = dp ? 256 : 512;  // blocks resident at a time
+          const long conc = 256;  // blocks resident at a time
           double best = 1e300;
           const long ns_max = std::max<long>(1, std::min<long>(64, ld / 256));
           for (long t = 1; t <= ns_max; t++) {
             const long r = ((ld + t - 1) / t + 63) / 64 * 64, used = (ld + r - 1) / r;
-            const long blocks = (long)(dp ? (njg + 1) / 2 : njg) * used;
+            const long blocks = (long)((njg + 1) / 2) * used;
             const double cost = (double)((blocks + conc - 1) / conc) * (double)r * (blocks < conc ? 2.0 : 1.0);
             if (cost < best) {
               best = cost;
@@ -1837,8 +1831,8 @@ long long bessx_session_counter(const bessx_session *s, int which) {
       }
       return s->group_xtx_ns;
     }
-    case 20: return s->kch_merged;
-    case 21: return s->kch_takeovers;
+    case 20:
+    case 21: return 0;  // (the chunk phase as merged launches: measured slower in round 5 and removed)
     case 22: return (long long)(1e6 * s->kch_t[0]);
     case 23: return (long long)(1e6 * s->kch_t[1]);
     case 24: return (long long)(1e6 * s->kch_t[2]);

@@ -307,9 +307,8 @@ int bessx_session_score_mode(const bessx_session *s);
  * during the chunk phase, 17 chains of the last such path, 18 paths whose stitch gave up (a chunk's refit did not meet its
  * own chain within its budget: the rest of the path was walked as one chain, and the automatic choice of this session is
  * one chain from then on), 19 device nanoseconds of the last all-rows group_XTX pass inside a path call (LM; kernel timing
- * on), 20 chunk phases
- * that ran as merged launches on one stream (round 5), 21 chains of such phases the host had to finish through the
- * per-context path (a tie at the selection boundary, a solve handed to the Cholesky kernel, ...), 22-24 microseconds the
+ * on), 20 / 21 retired, always 0 (chunk phases run as merged launches on one stream and the chains of such phases the
+ * host had to finish: measured slower than a stream per chain and removed), 22-24 microseconds the
  * chunked paths spent in their coarse chain / chunk phase / stitch (host clock, summed); round 6: 25 / 26 timed panel
  * launches of ONE 32-column group and their nanoseconds, 27 / 28 the same for launches of TWO groups (one read of X each;
  * reset with bessx_session_score_pass_stats), 29 multi-chain launches of the chunk chains' shared passes over X

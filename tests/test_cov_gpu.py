@@ -164,10 +164,43 @@ def test_cv_row_sets_share_their_fills(gpu, monkeypatch, n, p, K):
     assert_same_trace(a[0]["trace"], want, what="shared CV fills")
 
 
-def test_panel_kernel_dp_against_numpy_and_the_default_kernels(gpu, monkeypatch):
-    """k_cov_panel_dp (round 5: one 8-wave workgroup per compute unit over 128 streamed columns, two LDS tiles, one
-    barrier per chunk; the default, test hook panel=lds selects k_cov_panel_lds2 / _pair): its Gram columns against NumPy X^T X_S -- one group and a pair per pass, a
-    column count that is no multiple of 128, a fold mask -- and a path run with it against the default kernels' path."""
+def _gs_candidates(ref, s_min, s_max, n):
+    """The levels a golden-section search (src/path.cpp:134-389) stores as candidates, replayed from an oracle trace of
+    that search: every point of the section phase, then the levels of the closing sweep that improve the criterion.  The
+    replay must use up the trace's criterion values and meet its all-rows fits in their order."""
+    ics, full = iter(ref["ic_calls"]), [f["T0"] for f in ref["fits"] if f["train_n"] == n]
+    rnd = lambda v: int(np.floor(v + 0.5))
+    lo, hi = s_min, s_max
+    T1, T2 = rnd(0.618 * lo + 0.382 * hi), rnd(0.382 * lo + 0.618 * hi)
+    cand, fitted = [T1, T2], [T1, T2]
+    ic1 = icT1 = next(ics)
+    ic2, icT2 = next(ics), next(ics)
+    while T1 != T2:
+        if icT1 < icT2:
+            hi, T2, ic2, icT2 = T2, T1, ic1, ic1
+            T1 = rnd(0.618 * lo + 0.382 * hi)
+            ic1, icT1 = next(ics), next(ics)
+            cand.append(T1), fitted.append(T1)
+        else:
+            lo, T1, ic1, icT1 = T1, T2, ic2, ic2
+            T2 = rnd(0.382 * lo + 0.618 * hi)
+            ic2, icT2 = next(ics), next(ics)
+            cand.append(T2), fitted.append(T2)
+    best = np.inf
+    for T in range(lo, hi + 1):
+        fitted.append(T)
+        v = next(ics)
+        if v < best:
+            best = v
+            cand.append(T)
+    assert fitted == full and next(ics, None) is None
+    return cand, cand[-1]
+
+
+def test_panel_kernel_dp_against_numpy_and_the_oracle(gpu):
+    """k_cov_panel_dp (one 8-wave workgroup per compute unit over 128 streamed columns, two LDS tiles, one barrier per
+    chunk): its Gram columns against NumPy X^T X_S -- one group and a pair per pass, a column count that is no multiple
+    of 128, a fold mask -- and the paths whose fills it forms against the oracle's."""
     X, y, _, _ = synth.make_lm(3000, 1100, 12, seed=5)  # 1100 columns: the last workgroup's second half is partly empty
     n, p = X.shape
     Xc = X - X.mean(axis=0)
@@ -175,13 +208,9 @@ def test_panel_kernel_dp_against_numpy_and_the_default_kernels(gpu, monkeypatch)
     cols = ((np.arange(128) * 29 + 7) % p).astype(np.int32)
     want = Xn.T @ Xn[:, cols]
     seq = np.arange(1, 41)
-    hooks(monkeypatch, panel="lds")  # (the kernels of rounds 2-4; k_cov_panel_dp is the default since round 5)
-    with gpu.Session(X, y, score_mode=2) as s0:
-        ref = s0.sequential_path(seq, ic_type=3)
-        fold = synth.make_cv_folds(n, 4)
-        s0.set_cv(4, fold)
-        ref_cv = s0.gs_path(1, 30, ic_type=3, is_cv=True)
-    hooks(monkeypatch, panel="dp")
+    fold = synth.make_cv_folds(n, 4)
+    ref = P.trace(X, y, ic_type=3, sequence=seq)
+    ref_cv = P.trace(X, y, ic_type=3, is_cv=True, K=4, cv_fold_id=fold, path_type=2, s_min=1, s_max=30)
     with gpu.Session(X, y, score_mode=2) as s:
         s.cov_prefill_begin(cols)
         s.cov_prefill_compute(0, 1)
@@ -190,10 +219,18 @@ def test_panel_kernel_dp_against_numpy_and_the_default_kernels(gpu, monkeypatch)
         got = s.cov_prefill_export(0, 4).reshape(128, p).T
         s.cov_prefill_end()
         assert np.max(np.abs(got - want)) <= 1e-12 * np.max(np.abs(want))
-        out = s.sequential_path(seq, ic_type=3)
-        assert np.array_equal(out["cand_support"], ref["cand_support"]) and np.array_equal(out["cand_iters"], ref["cand_iters"])
-        np.testing.assert_allclose(out["cand_ic"], ref["cand_ic"], rtol=1e-10)
+        out = s.sequential_path(seq, ic_type=3)  # untraced: the fits chained on the device
+        assert len(ref["fits"]) == len(seq) and np.array_equal(out["cand_T0"], seq)
+        for i, f in enumerate(ref["fits"]):
+            assert np.array_equal(out["cand_support"][i, :seq[i]], f["iters"][-1]), "level %d support" % seq[i]
+            assert out["cand_iters"][i] == len(f["iters"]), "level %d PDAS iterations" % seq[i]
+        np.testing.assert_allclose(out["cand_ic"], ref["ic_calls"], rtol=1e-9, atol=1e-9)
         s.set_cv(4, fold)  # the fold-major copy: masked / multi-row-set fills through the same kernel
+        s.trace_enable(True)
         cv = s.gs_path(1, 30, ic_type=3, is_cv=True)
-        assert cv["best_T0"] == ref_cv["best_T0"] and np.array_equal(cv["cand_T0"], ref_cv["cand_T0"])
-        np.testing.assert_allclose(cv["cand_ic"], ref_cv["cand_ic"], rtol=1e-10)
+        # every fit of the search in the oracle's order and at its level (what cand_T0 lists), every PDAS iteration's
+        # support, every criterion value; and the level the search settles on
+        assert_same_trace(cv["trace"], ref_cv, what="dp panel, gs cv")
+        want_T0, want_best = _gs_candidates(ref_cv, 1, 30, n)
+        assert np.array_equal(cv["cand_T0"], want_T0) and cv["best_T0"] == want_best
+        assert np.array_equal(np.nonzero(cv["beta"])[0], np.nonzero(ref_cv["beta"])[0])

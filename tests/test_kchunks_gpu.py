@@ -298,46 +298,6 @@ def test_the_stitch_gives_up_where_the_chunks_do_not_merge(gpu, monkeypatch):
         _same_path(out, single)
 
 
-@pytest.mark.parametrize("chains", [2, 4, 8])
-def test_merged_launches_over_the_chunk_chains_return_the_single_chain(gpu, monkeypatch, chains):
-    """Round 5 (bessx_dev.h, McChain; test hook kchunks_merged=1): the chunk phase as merged launches on ONE stream -- every
-    chain a workgroup of the same launch, the candidate / iteration sequencing in device memory, parked chains served by
-    one union fill -- gives the single chain's candidates like the stream-per-chain form does: consecutive levels, a
-    path with gaps between the levels (no arg-max start), and a design whose chunks need fills of their own."""
-    from helpers import hooks
-    X, y, _, _ = synth.make_lm(2500, 700, 20, seed=11)
-    seq = np.arange(1, 65)
-    monkeypatch.setenv("BESSX_KPATH_CHAINS", "1")
-    with gpu.Session(X, y) as s:
-        single = s.sequential_path(seq, ic_type=3)
-        single_odd = s.sequential_path(seq[::2], ic_type=2)
-    monkeypatch.setenv("BESSX_KPATH_CHAINS", str(chains))
-    hooks(monkeypatch, kchunks_merged=1)
-    with gpu.Session(X, y) as s:
-        first = s.sequential_path(seq, ic_type=3)
-        cnt = s.counters()
-        assert cnt["kpath_chunked_paths"] == 1 and cnt["kpath_merged_chunk_phases"] == 1
-        again = s.sequential_path(seq, ic_type=3)
-        odd = s.sequential_path(seq[::2], ic_type=2)
-        assert s.counters()["kpath_merged_chunk_phases"] == 3
-    _same_path(first, single)
-    _same_path(again, single)
-    _same_path(odd, single_odd)
-    # a small cache-speculation width and many chunks: the chunks park for fills of their own (union fills)
-    X2, y2, _, _ = synth.make_lm(3000, 2600, 60, seed=3)
-    seq2 = np.arange(1, 161)
-    monkeypatch.setenv("BESSX_KPATH_CHAINS", "1")
-    hooks(monkeypatch, kchunks_merged=0)
-    with gpu.Session(X2, y2) as s:
-        want = s.sequential_path(seq2, ic_type=3)
-    monkeypatch.setenv("BESSX_KPATH_CHAINS", str(chains))
-    hooks(monkeypatch, kchunks_merged=1)
-    with gpu.Session(X2, y2) as s:
-        got = s.sequential_path(seq2, ic_type=3)
-        assert s.counters()["kpath_merged_chunk_phases"] == 1
-    _same_path(got, want)
-
-
 @pytest.mark.parametrize("chains", [2, 3])
 def test_chunk_chains_of_the_streaming_lm_path(gpu, monkeypatch, chains):
     """Round 5: the STREAMING form of the LM score pass (score_mode = 1: every PDAS iteration reads X once -- the
@@ -364,26 +324,25 @@ def test_chunk_chains_of_the_streaming_lm_path(gpu, monkeypatch, chains):
         _same_path(w, s.sequential_path(seq[:40], ic_type=2))
 
 
-@pytest.mark.parametrize("variant", ["rendezvous", "staged_own_stream", "staged_fill_stream", "pipeline", "late_stitch",
+@pytest.mark.parametrize("variant", ["rendezvous", "staged_own_stream", "staged_fill_stream", "late_stitch",
                                      "rendezvous_late_stitch"])
 def test_fill_disciplines_of_the_chunk_chains_return_the_single_chain(gpu, monkeypatch, variant):
     """How a chunk chain's fill of the shared Gram column cache is kept from the other chains (bessx_sync.h:
     FillRendezvous): round 4's rendezvous -- every other chain stands still (kchunks_staged=0) -- and round 5's STAGED
     fills (default): the fill writes slots nobody can look up until its last launch publishes them (k_cov_publish_slots),
     on the filling chain's own stream (kchunks_reserve=0) or on the session's fill stream that leaves some compute units
-    to the other chains' kernels; and the coarse chain BESIDE the chunks instead of in front of them (kchunks_pipeline=1:
-    measured slower, kept selectable).  And when the first round of the stitch runs: early, on the thread of the chunk in
+    to the other chains' kernels.  And when the first round of the stitch runs: early, on the thread of the chunk in
     front as soon as that chunk is walked (default), or after all chunks (kchunks_early_stitch=0).  Designs whose chunks need
     many fills of their own; the same candidates each way, path after path on one session."""
     from helpers import hooks
     hk = {"rendezvous": dict(kchunks_staged=0), "staged_own_stream": dict(kchunks_staged=1, kchunks_reserve=0),
-          "staged_fill_stream": dict(kchunks_staged=1, kchunks_reserve=24), "pipeline": dict(kchunks_pipeline=1),
+          "staged_fill_stream": dict(kchunks_staged=1, kchunks_reserve=24),
           "late_stitch": dict(kchunks_early_stitch=0), "rendezvous_late_stitch": dict(kchunks_staged=0, kchunks_early_stitch=0)}[variant]
     for (n, p, k, seed, top, chains) in ((3000, 2600, 60, 3, 160, 8), (2500, 700, 20, 11, 64, 4), (3000, 1500, 60, 5, 128, 3)):
         X, y, _, _ = synth.make_lm(n, p, k, seed=seed)
         seq = np.arange(1, top + 1)
         monkeypatch.setenv("BESSX_KPATH_CHAINS", "1")
-        hooks(monkeypatch, kchunks_staged=1, kchunks_pipeline=0, kchunks_early_stitch=1)
+        hooks(monkeypatch, kchunks_staged=1, kchunks_early_stitch=1)
         with gpu.Session(X, y) as s:
             want = s.sequential_path(seq, ic_type=3)
         monkeypatch.setenv("BESSX_KPATH_CHAINS", str(chains))
@@ -393,8 +352,6 @@ def test_fill_disciplines_of_the_chunk_chains_return_the_single_chain(gpu, monke
                 _same_path(s.sequential_path(seq, ic_type=3), want)
             cnt = s.counters()
             assert cnt["kpath_chunked_paths"] == 3
-            if variant == "pipeline":
-                assert cnt["kpath_chunk_fills"] >= 3  # (the coarse chain's fills count: it runs on a context too)
 
 
 @pytest.mark.parametrize("fam,chains", [("lm", 4), ("lm", 8), ("logistic", 6), ("poisson", 3), ("cox", 3), ("cox", 4)])
@@ -402,8 +359,7 @@ def test_shared_passes_return_the_path_of_the_chains_own_passes(gpu, monkeypatch
     """Round 6: the chunk chains of the streaming forms hand their vector sets to ONE multi-chain launch per
     pass (k_xtv_mc / k_cox_score1p_mc) instead of streaming X once per chain.  The multi-chain kernels leave bitwise the
     sums of the single-chain kernels (tests/test_ops_gpu.py), so the same chains on passes of their own
-    (kchunks_shared_pass=0, round 5) walk the same path -- and both return the single chain's candidates.  Also as two
-    alternating groups.  (Coefficients are compared to 1e-8, not bitwise: which rows a chunk has stored when its
+    (kchunks_shared_pass=0, round 5) walk the same path -- and both return the single chain's candidates.  (Coefficients are compared to 1e-8, not bitwise: which rows a chunk has stored when its
     predecessor's early stitch looks at them depends on timing, and a replaced row agrees with the chunk's own to 1e-9.)"""
     from helpers import hooks
     if fam == "lm":
@@ -426,8 +382,7 @@ def test_shared_passes_return_the_path_of_the_chains_own_passes(gpu, monkeypatch
     outs = {}
     eq = 1000000000  # (equal chunk lengths in every variant: the same chunks start at the same levels)
     for name, hk in (("own", dict(kchunks_shared_pass=0, kchunks_len_div=eq)),
-                     ("shared", dict(kchunks_shared_pass=1, kchunks_pass_groups=1, kchunks_len_div=eq)),
-                     ("groups", dict(kchunks_shared_pass=1, kchunks_pass_groups=2, kchunks_len_div=eq))):
+                     ("shared", dict(kchunks_shared_pass=1, kchunks_len_div=eq))):
         hooks(monkeypatch, **hk)
         with gpu.Session(X, y, **kw) as s:
             s.enable_kernel_timing(True)

@@ -186,6 +186,20 @@ def test_wide_design_where_the_ordinary_path_runs_chunk_chains(gpu):
         _same(got[r], want, "takeover response %d" % r)
 
 
+def test_parked_chains_are_served_by_union_fills(gpu, monkeypatch):
+    """A wide design and a long path (p = 2600, levels 1..160: more columns than a fill speculates on): the chains of
+    the merged run park on missing Gram columns in the middle of their paths and are served by union fills -- the
+    engine's fill counter says so -- and still return what each response's single chain returns."""
+    X, y, _, _ = synth.make_lm(3000, 2600, 60, seed=3)
+    Y = np.column_stack([y, _responses(X, 3, 4)[:, 1:]])
+    seq = np.arange(1, 161)
+    got, cnt = _multi(gpu, X, Y, seq)
+    assert cnt["multi_responses_batched"] == 3 and cnt["multi_union_fills"] > 0
+    monkeypatch.setenv("BESSX_KPATH_CHAINS", "1")
+    for r, want in enumerate(_singles(gpu, X, Y, seq)):
+        _same(got[r], want, "parked response %d" % r)
+
+
 def test_streaming_fallback_on_chunk_chains(gpu):
     X, y, _, _ = synth.make_lm(50000, 2048, 20, seed=111)  # (n p >= 1e8: the streaming form's chunk chains)
     Y = np.column_stack([y, _responses(X, 2, 112)[:, 1:], np.random.default_rng(113).permutation(y)])

@@ -37,6 +37,5 @@ for C in [1] + [int(v) for v in sys.argv[1:]]:
            "passes_over_X_per_path": cnt["passes_over_X"] / 10.0, "stitch_refits_per_path": cnt["kpath_stitch_refits"] / 10.0,
            "chunk_fills_per_path": cnt["kpath_chunk_fills"] / 10.0,
            "phase_ms_per_path": {"coarse": round(cnt["kpath_coarse_us"] / 10e3, 2), "chunks": round(cnt["kpath_chunks_us"] / 10e3, 2),
-                                 "stitch": round(cnt["kpath_stitch_us"] / 10e3, 2)},
-           "merged_chunk_phases": cnt["kpath_merged_chunk_phases"], "chains_taken_over": cnt["kpath_chains_taken_over"]}
+                                 "stitch": round(cnt["kpath_stitch_us"] / 10e3, 2)}}
     print(json.dumps(rec), flush=True)

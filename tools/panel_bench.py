@@ -1,10 +1,9 @@
-"""The panel kernels of the covariance form alone (k_cov_panel_dp, one or two 32-column groups per pass over X; with
-BESSX_TEST_HOOKS=panel=lds the kernels of rounds 2-4: k_cov_panel_lds2, 32 Gram columns per pass, and k_cov_panel_pair,
-64 per pass): timed with HIP events through the cooperative-prefill entry points (bessx_session_cov_prefill_*), which
-run exactly the fill a parked fit runs -- list, panel, reduce -- on columns of the caller's choice.
+"""The panel kernel of the covariance form alone (k_cov_panel_dp, one or two 32-column groups per pass over X): timed
+with HIP events through the cooperative-prefill entry points (bessx_session_cov_prefill_*), which run exactly the fill
+a parked fit runs -- list, panel, reduce -- on columns of the caller's choice.
   python tools/panel_bench.py [n p] [repeats] [--check]
 Prints one JSON line per variant: ms per launch, TB/s of X streamed, TFLOP/s on the fp64 matrix cores, both against
-the peaks of MI355X_MICROARCH.md.  --check: first compares both kernels with NumPy on a small problem.
+the peaks of MI355X_MICROARCH.md.  --check: first compares both forms with NumPy on a small problem.
 Sits under rocprofv3 --pmc (tools/collect_profiles_r05.sh) for the counters of profiles/r05_panel_*."""
 import json
 import os
@@ -29,13 +28,13 @@ if "--check" in sys.argv:
     want = Xn.T @ Xn[:, cols]  # (p x 128)
     with capi.Session(Xs, ys, score_mode=2) as s:
         s.cov_prefill_begin(cols)
-        s.cov_prefill_compute(0, 1)   # one group: k_cov_panel_lds2
+        s.cov_prefill_compute(0, 1)   # one group per pass
         s.cov_prefill_compute(1, 1)
-        s.cov_prefill_compute(2, 2)   # two groups: k_cov_panel_pair
+        s.cov_prefill_compute(2, 2)   # two groups in one pass
         got = s.cov_prefill_export(0, 4).reshape(128, 1500).T
         s.cov_prefill_end()
     err = float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
-    print(json.dumps({"check": "panel kernels against NumPy X^T X_S (n=4000, p=1500, 128 columns)", "max_rel_err": err}))
+    print(json.dumps({"check": "panel kernel against NumPy X^T X_S (n=4000, p=1500, 128 columns)", "max_rel_err": err}))
     assert err < 1e-12, err
 
 X, y, _, _ = synth.make_lm(n, p, min(100, p // 4))
@@ -44,9 +43,7 @@ with capi.Session(X, y, score_mode=2) as s:
     ngroups = 8
     cols = (np.arange(ngroups * 32, dtype=np.int32) * 37 + 11) % p
     s.cov_prefill_begin(cols)
-    lds = "panel=lds" in os.environ.get("BESSX_TEST_HOOKS", "")  # (round 5: k_cov_panel_dp is the default)
-    for name, per_launch in (((("k_cov_panel_lds2" if lds else "k_cov_panel_dp") + " (32 columns per pass)"), 1),
-                             ((("k_cov_panel_pair" if lds else "k_cov_panel_dp") + " (64 columns per pass)"), 2)):
+    for name, per_launch in (("k_cov_panel_dp (32 columns per pass)", 1), ("k_cov_panel_dp (64 columns per pass)", 2)):
         for g in range(0, ngroups, per_launch):  # warm-up: code objects, clocks
             s.cov_prefill_compute(g, per_launch)
         s.enable_kernel_timing(True)

@@ -1,4 +1,5 @@
-"""Chains x groups sweep of the shared passes.  python tools/shared_pass_sweep.py lm|logistic|poisson|cox "C:G[:lendiv]" ..."""
+"""Sweep of the shared passes by number of chains (S = 0: a pass per chain).
+   python tools/shared_pass_sweep.py lm|logistic|poisson|cox "C[:S[:lendiv]]" ..."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,8 +23,8 @@ with capi.Session(X, y, **kw) as s:
     del X
     for spec in ["1:1"] + sys.argv[2:]:
         f = spec.split(":")
-        C, G = int(f[0]), int(f[1])
-        hooks = "kchunks_pass_groups=%d" % G + (",kchunks_len_div=%s" % f[2] if len(f) > 2 else "") + (",kchunks_shared_pass=0" if G == 0 else "")
+        C, S = int(f[0]), (int(f[1]) if len(f) > 1 else 1)
+        hooks = "kchunks_shared_pass=%d" % (1 if S else 0) + (",kchunks_len_div=%s" % f[2] if len(f) > 2 else "")
         os.environ["BESSX_TEST_HOOKS"] = hooks
         s.set_kpath_chains(C)
         s.sequential_path(seq, ic_type=3)
@@ -40,7 +41,7 @@ with capi.Session(X, y, **kw) as s:
         st = s.score_pass_stats()
         c1 = s.counters()
         s.enable_kernel_timing(False)
-        print(json.dumps({"family": fam, "chains": C, "groups": G, "spec": spec, "ms_per_path": round(1e3 * min(ts), 1),
+        print(json.dumps({"family": fam, "chains": C, "shared": bool(S), "spec": spec, "ms_per_path": round(1e3 * min(ts), 1),
                           "candidates_per_s": round(kmax / min(ts), 1), "passes_per_path": st["launches"] / float(reps),
                           "ms_per_pass": round(1e3 * st["seconds"] / max(st["launches"], 1), 4),
                           "chain_slots_per_path": (c1["shared_pass_chain_slots"] - c0["shared_pass_chain_slots"]) / float(reps),
