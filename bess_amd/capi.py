@@ -37,6 +37,7 @@ SYMBOLS = [
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
+    "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -72,6 +73,13 @@ class EvalInput(ctypes.Structure):
                 ("cols", _I), ("m", _i), ("B", _D), ("coef0", _D), ("R", _i), ("link", _i), ("y_host", _D),
                 ("y_dev", _vp), ("y_dtype", _i), ("y_row_stride", _ll), ("y_col_stride", _ll), ("y_cols", _i),
                 ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i), ("weight_stride", _ll), ("stream", _vp)]
+
+
+class CoxEvalInput(ctypes.Structure):
+    """bessx_cox_eval_input: the model, X in GPU memory, time / status / weight in host memory; strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("R", _i), ("time", _D), ("status", _D), ("weight", _D),
+                ("ties", _i), ("want_pairs", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -187,6 +195,8 @@ def lib():
         L.bessx_op_predict_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _D, _D]
         L.bessx_eval_device.argtypes = [ctypes.POINTER(EvalInput), _D, _D, _D]
         L.bessx_op_eval_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D, _D]
+        L.bessx_eval_cox_device.argtypes = [ctypes.POINTER(CoxEvalInput), _D, ctypes.POINTER(_ll), ctypes.POINTER(_ll)]
+        L.bessx_op_cox_eval_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
         _lib = L
     return _lib
 
@@ -1149,6 +1159,96 @@ def op_eval_bench(x, cols, R=1, link="identity", y_cols=1, repeats=20):
                                      _ip(cols), cols.size, int(R), LINKS[link], int(y_cols), repeats, ctypes.byref(ms),
                                      ctypes.byref(g)))
     return ms.value, g.value
+
+
+TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties
+
+
+def _survival_vector(a, n, what, stream=0, check_only=False):
+    """time, status or weight of the Cox evaluation as n float64 host values; a device array is checked without a device
+    call (check_only) or copied to the host with device_to_host."""
+    if is_device_array(a):
+        if _DeviceArray(a, what).size != n:
+            raise ValueError("X.shape(0) should be equal to %s.size" % what)
+        return None if check_only else np.ascontiguousarray(device_to_host(a, stream).reshape(-1))
+    a = _f64(a).reshape(-1)
+    if a.size != n:
+        raise ValueError("X.shape(0) should be equal to %s.size" % what)
+    return a
+
+
+def evaluate_cox_device(x, cols, B, time, status, weight=None, ties="order", concordance=True, stream=0):
+    """Held-out Cox partial log-likelihood and Harrell's concordance of R models on a device matrix x (n x p: float64 or
+    float32, any non-negative strides), read once where it lies, the support's columns only (bessx_eval_cox_device).
+    With eta = x[:, cols] @ B (no intercept; a zero coefficient takes nothing from its column), the rows in the stable
+    ascending order of time and e = exp(clip(eta, -30, 30)):
+        loglik[r] = sum_k w_k status_k (clip(eta_k) - log S_k),  S_k = sum of e over the rows at or after k in that order
+    (ties="order", the quantity the fit reports as train_loss = -2 loglik) or over every row with time >= time_k
+    (ties="breslow").  A pair k, l is comparable when status_k = 1 and time_k < time_l; it is concordant when eta_k > eta_l,
+    discordant when eta_k < eta_l, tied_risk otherwise; c_index = (concordant + tied_risk / 2) / comparable (NaN without a
+    comparable pair).  cols, B as in predict_device; time, status (0 or 1), weight (None = ones): n values each, host or
+    device arrays (device arrays are copied to the host, n values).  Returns {"loglik": (R,), "comparable": int} plus,
+    with concordance=True, "concordant", "discordant", "tied_risk" ((R,) int64, exact) and "c_index" (R,);
+    concordance=False skips the O(n^2) pair kernel.  Every floating-point sum has a fixed order: the same call gives the
+    same bits.  stream: raw handle of the stream x was produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if ties not in TIES:
+        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
+    B = np.asarray(B, dtype=np.float64)
+    R = B.shape[1] if B.ndim == 2 else 1
+    cols, B, _ = _predict_model(dx, cols, B, np.zeros(R))
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, a in given:  # (every shape is checked before anything is copied)
+        _survival_vector(a, n, what, check_only=True)
+    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    a = CoxEvalInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.B, a.R = _ip(cols), cols.size, _dp(B), R
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    a.ties, a.want_pairs, a.stream = TIES[ties], int(bool(concordance)), int(stream) if stream else None
+    loglik, pairs, comp = np.zeros(R), np.zeros((R, 3), dtype=np.int64), _ll(0)
+    _check(lib().bessx_eval_cox_device(ctypes.byref(a), _dp(loglik), pairs.ctypes.data_as(ctypes.POINTER(_ll)),
+                                       ctypes.byref(comp)))
+    out = {"loglik": loglik, "comparable": int(comp.value)}
+    if concordance:
+        out["concordant"], out["discordant"], out["tied_risk"] = (np.ascontiguousarray(pairs[:, j]) for j in range(3))
+        out["c_index"] = c_index(out["concordant"], out["tied_risk"], out["comparable"])
+    return out
+
+
+def c_index(concordant, tied_risk, comparable):
+    """(concordant + tied_risk / 2) / comparable in fp64; NaN without a comparable pair."""
+    num = np.asarray(concordant, dtype=np.float64) + 0.5 * np.asarray(tied_risk, dtype=np.float64)
+    return num / comparable if comparable > 0 else np.full(np.shape(num), np.nan)
+
+
+def evaluate_cox_candidates(result, x, time, status, weight=None, ties="order", stream=0):
+    """The train / validation split for Cox: the partial log-likelihood of every candidate of a path (fitted on the
+    training rows) on held-out rows x, time, status, in ONE evaluate_cox_device call over the union of the candidates'
+    supports (their coef0 is ignored: Cox has no intercept), without the pair counts.  Returns (loglik (R,), best) with
+    best the index of the largest log-likelihood, the lowest index on a tie (a NaN never wins)."""
+    cols, B, _ = candidate_models(result)
+    ll = evaluate_cox_device(x, cols, B, time, status, weight=weight, ties=ties, concordance=False,
+                             stream=stream)["loglik"]
+    return ll, int(np.argmax(np.where(np.isnan(ll), -np.inf, ll)))
+
+
+def op_cox_eval_bench(x, cols, R=1, ties="order", concordance=True, repeats=20):
+    """Milliseconds per launch of the three stages of the Cox evaluation on the device matrix x for the support cols and
+    R models, device events: (predictor pass, risk-set scan + likelihood reduction, pair counts -- 0.0 without
+    concordance)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms = np.zeros(3)
+    _check(lib().bessx_op_cox_eval_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, int(R), TIES[ties], int(bool(concordance)), repeats,
+                                         _dp(ms)))
+    return tuple(float(v) for v in ms)
 
 
 def op_chol_bench(m, repeats=200):

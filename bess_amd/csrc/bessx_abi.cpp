@@ -1,6 +1,8 @@
 // bessx_abi.cpp -- the drop-in entry points bessx_pywrap_bess / bessx_bessCpp (src/bess.h:20-51) and the single-kernel ops
 #include "bessx_host.h"
 
+#include <climits>
+
 extern "C" {
 
 // ----------------------------------------------------------------------------------------------
@@ -1083,6 +1085,216 @@ int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long lon
   const double bytes = (double)n * (double)m * (f32 ? 4.0 : 8.0) + (double)n * 8.0 * (y_cols + 1.0);
   *avg_ms = ms / repeats;
   *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// held-out Cox partial likelihood and concordance on a caller's device matrix (include/bessx.h section 2e)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the host side of the time order: everything the kernels need about time, status and weight
+struct CoxOrder {
+  std::vector<int> pos, first, kg;  // pos[row] = position; first[k]; kg[k] = first[k] for an event, INT_MAX otherwise
+  std::vector<double> wd;           // w * status in position order
+  long long comparable = 0;
+};
+
+void cox_order(const double *time, const double *status, const double *weight, int n, CoxOrder *o) {
+  std::vector<int> idx((size_t)n);
+  std::iota(idx.begin(), idx.end(), 0);
+  std::stable_sort(idx.begin(), idx.end(), [time](int a, int b) { return time[a] < time[b]; });
+  o->pos.resize((size_t)n);
+  o->first.resize((size_t)n);
+  o->kg.resize((size_t)n);
+  o->wd.resize((size_t)n);
+  for (int k = 0; k < n; k++) {
+    const int i = idx[(size_t)k];
+    o->pos[(size_t)i] = k;
+    o->first[(size_t)k] = (k > 0 && time[idx[(size_t)k - 1]] == time[i]) ? o->first[(size_t)k - 1] : k;
+    o->kg[(size_t)k] = status[i] != 0.0 ? o->first[(size_t)k] : INT_MAX;
+    o->wd[(size_t)k] = (weight ? weight[i] : 1.0) * status[i];
+  }
+  // an event at position k is comparable with every position behind its tie group
+  o->comparable = 0;
+  for (int k = n - 1, end = n; k >= 0; k--) {  // end: first position with a later time than position k
+    if (k < n - 1 && o->first[(size_t)k + 1] != o->first[(size_t)k]) end = k + 1;
+    if (o->kg[(size_t)k] != INT_MAX) o->comparable += n - end;
+  }
+}
+
+int cox_eval_check_args(const char *who, const bessx_cox_eval_input *in, const double *loglik, const long long *pairs,
+                        const long long *comparable) {
+  const std::string w(who);
+  if (!in || !loglik || !comparable) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, in->R, BESSX_LINK_IDENTITY)) return rc;
+  if (in->R > 65535) return fail(BESSX_ERR_ARG, w + ": R must be at most 65535");
+  if (in->m > 0 && !in->B) return fail(BESSX_ERR_ARG, w + ": null argument (B)");
+  if (in->ties != 0 && in->ties != 1) return fail(BESSX_ERR_ARG, w + ": ties must be 0 (order) or 1 (breslow)");
+  if (in->want_pairs && !pairs) return fail(BESSX_ERR_ARG, w + ": want_pairs needs pairs");
+  for (int i = 0; i < in->n; i++) {
+    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
+    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
+  }
+  return 0;
+}
+
+// the device side of one problem: buffers of `sc`, uploads queued on st (the vectors of `o` must outlive them)
+struct CoxDev {
+  int *cols = nullptr, *pos = nullptr, *first = nullptr, *kg = nullptr;
+  double *B = nullptr, *zero = nullptr, *wd = nullptr, *eta = nullptr, *ex = nullptr, *work = nullptr, *res = nullptr;
+  unsigned long long *cnt = nullptr;
+};
+
+int cox_eval_stage(Owner &sc, const CoxOrder &o, const int *cols, int m, const double *B, int R, int n, int need_first,
+                   int want_pairs, hipStream_t st, CoxDev *d) {
+  const size_t N = (size_t)n;
+  HIPX(sc.alloc(&d->B, (size_t)m * R + (size_t)R));
+  HIPX(sc.alloc(&d->cols, (size_t)m));
+  d->zero = d->B + (size_t)m * R;
+  HIPX(hipMemsetAsync(d->zero, 0, (size_t)R * sizeof(double), st));
+  if (m > 0) {
+    HIPX(hipMemcpyAsync(d->cols, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(d->B, B, (size_t)m * R * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  HIPX(sc.alloc(&d->pos, N));
+  HIPX(hipMemcpyAsync(d->pos, o.pos.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPX(sc.alloc(&d->wd, N));
+  HIPX(hipMemcpyAsync(d->wd, o.wd.data(), N * sizeof(double), hipMemcpyHostToDevice, st));
+  if (need_first || want_pairs) {
+    HIPX(sc.alloc(&d->first, N));
+    HIPX(hipMemcpyAsync(d->first, o.first.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (want_pairs) {
+    HIPX(sc.alloc(&d->kg, N));
+    HIPX(hipMemcpyAsync(d->kg, o.kg.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&d->cnt, 2 * (size_t)R));
+  }
+  HIPX(sc.alloc(&d->eta, N * R));
+  HIPX(sc.alloc(&d->ex, N * R));
+  HIPX(sc.alloc(&d->work, (size_t)cox_eval_workspace(n, R)));
+  HIPX(sc.alloc(&d->res, (size_t)R));
+  return 0;
+}
+
+// sc, o, hl and hc belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_eval_run(Owner &sc, const CoxOrder &o, std::vector<double> &hl, std::vector<unsigned long long> &hc,
+                 const bessx_cox_eval_input *in, double *loglik, long long *pairs, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int R = in->R, n = in->n, f32 = in->x_dtype == BESSX_F32;
+  CoxDev d;
+  if (int rc = cox_eval_stage(sc, o, in->cols, in->m, in->B, R, n, in->ties == 1, in->want_pairs, st, &d)) return rc;
+  HIPX(launch_cox_eval_eta(in->x, f32, in->x_row_stride, in->x_col_stride, n, d.cols, in->m, d.B, d.zero, R, d.pos,
+                           d.eta, d.ex, st));
+  HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, in->ties == 1 ? d.first : nullptr, n, R, d.work, d.res, st));
+  hl.resize((size_t)R);
+  HIPX(hipMemcpyAsync(hl.data(), d.res, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (in->want_pairs) {
+    HIPX(launch_cox_eval_pairs(d.eta, d.kg, d.first, n, R, d.cnt, st));
+    hc.resize(2 * (size_t)R);
+    HIPX(hipMemcpyAsync(hc.data(), d.cnt, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  std::copy(hl.begin(), hl.end(), loglik);
+  if (in->want_pairs)
+    for (int r = 0; r < R; r++) {
+      const long long c = (long long)hc[2 * (size_t)r], dd = (long long)hc[2 * (size_t)r + 1];
+      pairs[3 * r] = c;
+      pairs[3 * r + 1] = dd;
+      pairs[3 * r + 2] = o.comparable - c - dd;
+    }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_eval_cox_device(const bessx_cox_eval_input *in, double *loglik, long long *pairs, long long *comparable) {
+  if (int rc = cox_eval_check_args("eval_cox_device", in, loglik, pairs, comparable)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("eval_cox_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> hl;
+    std::vector<unsigned long long> hc;
+    rc = cox_eval_run(sc, o, hl, hc, in, loglik, pairs, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, hl and hc go after this)
+  }
+  (void)hipStreamDestroy(st);
+  if (!rc) *comparable = o.comparable;
+  return rc;
+}
+
+int bessx_op_cox_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int R, int ties, int want_pairs, int repeats, double *stage_ms) {
+  if (!x || repeats < 1 || !stage_ms) return fail(BESSX_ERR_ARG, "op_cox_eval_bench: bad arguments");
+  if (int rc = predict_check_model("op_cox_eval_bench", n, p, cols, m, R, BESSX_LINK_IDENTITY)) return rc;
+  if (R > 65535) return fail(BESSX_ERR_ARG, "op_cox_eval_bench: R must be at most 65535");
+  if (ties != 0 && ties != 1) return fail(BESSX_ERR_ARG, "op_cox_eval_bench: ties must be 0 (order) or 1 (breslow)");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_eval_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m * R), time((size_t)n), status((size_t)n);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int i = 0; i < n; i++) {  // distinct times in an order that is not the rows'
+    time[(size_t)i] = (double)(((long long)i * 7919) % n) + (double)i / (2.0 * n);
+    status[(size_t)i] = (double)(i % 2);
+  }
+  CoxOrder o;
+  cox_order(time.data(), status.data(), nullptr, n, &o);
+  Owner sc;
+  CoxDev d;
+  if (int rc = cox_eval_stage(sc, o, cols, m, B.data(), R, n, ties == 1, want_pairs, nullptr, &d)) return rc;
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  double *keep = nullptr;  // the scan works in place: every timed launch of stage 2 starts from a fresh copy of ex
+  HIPX(sc.alloc(&keep, (size_t)n * R));
+  for (int stage = 0; stage < 3; stage++) {
+    stage_ms[stage] = 0.0;
+    if (stage == 2 && !want_pairs) break;
+    float total = 0.f;
+    for (int i = -1; i < repeats; i++) {  // (i = -1: the warm-up)
+      if (stage == 1)
+        HIPX(hipMemcpyAsync(d.ex, keep, (size_t)n * R * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+      HIPX(hipEventRecord(e0, nullptr));
+      if (stage == 0)
+        HIPX(launch_cox_eval_eta(x, f32, row_stride, col_stride, n, d.cols, m, d.B, d.zero, R, d.pos, d.eta, d.ex, nullptr));
+      else if (stage == 1)
+        HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties == 1 ? d.first : nullptr, n, R, d.work, d.res, nullptr));
+      else
+        HIPX(launch_cox_eval_pairs(d.eta, d.kg, d.first, n, R, d.cnt, nullptr));
+      HIPX(hipEventRecord(e1, nullptr));
+      HIPX(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPX(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 0) total += ms;
+    }
+    stage_ms[stage] = total / repeats;
+    if (stage == 0) HIPX(hipMemcpy(keep, d.ex, (size_t)n * R * sizeof(double), hipMemcpyDeviceToDevice));
+  }
   return BESSX_OK;
 }
 

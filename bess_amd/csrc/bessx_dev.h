@@ -76,6 +76,21 @@ long long eval_workspace(int f32, long long rs, long long cs, long long n, int m
 hipError_t launch_eval(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                        const double *B, const double *c, int R, int link, const EvalData &d, double *work, double *res,
                        hipStream_t st);
+hipError_t launch_eval_finish(const double *part, long long nb, int RS, double *out, hipStream_t st);
+// device evaluation of Cox models (bessx_k_coxeval.hip), in positions k = rank of a row in the stable ascending order of
+// the times.  _eta: eta and exp(clamp(eta, +-30)) of every row at its position pos[i], two R x n position-major arrays
+// (src, cols, B as in launch_predict; zero: R doubles of 0.0).  _loglik: ex becomes the suffix sums S in place, then
+// res[r] = sum_k wd[k] * (clamp(eta) - log S[first ? first[k] : k]); work: cox_eval_workspace(n, R) doubles.  _pairs:
+// cnt[2 r], cnt[2 r + 1] = pairs (k, l) with first[l] > kg[k] and eta_k > eta_l, eta_k < eta_l (kg[k] = first[k] for an
+// event, INT_MAX otherwise).  Everything is device memory.
+long long cox_eval_workspace(long long n, int R);
+hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                               const double *B, const double *zero, int R, const int *pos, double *eta, double *ex,
+                               hipStream_t st);
+hipError_t launch_cox_eval_loglik(const double *eta, double *ex, const double *wd, const int *first, long long n, int R,
+                                  double *work, double *res, hipStream_t st);
+hipError_t launch_cox_eval_pairs(const double *eta, const int *kg, const int *first, long long n, int R,
+                                 unsigned long long *cnt, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

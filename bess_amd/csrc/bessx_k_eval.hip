@@ -85,6 +85,14 @@ __global__ void __launch_bounds__(64) k_eval_finish(const double *__restrict__ p
   if (threadIdx.x == 0) out[q] = s;
 }
 
+// k_eval_finish for other units (bessx_k_coxeval.hip): out[q] = sum_b part[b * RS + q], q < RS
+hipError_t launch_eval_finish(const double *part, long long nb, int RS, double *out, hipStream_t st) {
+  if (!part || !out || nb < 1 || RS < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)RS), dim3(64), 0, st, part, nb, RS, out);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 template <typename T>
 static long long ev_blocks(long long rs, long long cs, long long n, int m, int R) {
   const int rt = xb_tile(R);

@@ -42,6 +42,13 @@ class bess_base:
     columns of it in place, and the results are torch tensors on X's device when X is one (NumPy arrays otherwise).
     evaluate(X, y) / score(X, y) turn held-out data into loss, R^2, accuracy or deviance: for an X in GPU memory in one
     fused pass over the support's columns that brings back R numbers.
+    linear_predictor(X) is X @ beta + coef0 for every family -- for Cox the risk score that predict() does not return --
+    as NumPy for a NumPy X and on X's device for an X in GPU memory.  The Cox classes also have
+    evaluate_survival(X, y, weight=None, ties="order"), with y = (time, status) as in fit: the partial log-likelihood of
+    the fitted model on these rows (ties="order": the rows at or after a row in the stable time order are at risk, the
+    quantity train_loss = -2 loglik reports; ties="breslow": every row with time >= the row's), deviance = -2 loglik,
+    n_events, and Harrell's concordance from exact pair counts (comparable, concordant, discordant, tied_risk, c_index);
+    concordance(X, y) is its c_index.  A device X is read once, in place, by capi.evaluate_cox_device.
     """
 
     def __init__(self, algorithm_type, model_type, path_type, max_iter=20, exchange_num=0, is_warm_start=True,
@@ -350,6 +357,106 @@ class bess_base:
         """r2 (Lm), accuracy (Logistic) or d2 (Poisson) of evaluate(X, y, weight); None for Cox."""
         res = self.evaluate(X, y, weight)
         return None if res is None else res[{1: "r2", 2: "accuracy", 3: "d2"}[self.model_type_int]]
+
+    # ---- Cox: risk score, held-out partial likelihood, concordance -------------------------------------------------
+    def linear_predictor(self, X):
+        """X @ beta + coef0 (a 2-D beta of Lm: one column per response).  A NumPy X gives NumPy; an X in GPU memory is
+        read in place, the support's columns only, and gives a tensor on X's device (capi.predict_device, identity
+        link)."""
+        if capi.is_device_array(X):
+            if capi._DeviceArray(X, "X", 2).shape[1] != self.p:
+                raise ValueError("X.shape[1] should be " + str(self.p))
+            beta, cols, coef0, _ = self._model_arrays()
+            return capi.predict_device(X, cols, beta[cols], coef0, link="identity", stream=_current_stream(X))
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        return X @ self.beta + self.coef0
+
+    @staticmethod
+    def _survival_host(eta, time, status, w, ties, pairs=True):
+        """(loglik, comparable, concordant, discordant) in fp64 NumPy with the definitions of capi.evaluate_cox_device:
+        eta, time, status, w are n-vectors in row order.  pairs=False leaves the O(n^2) counts out (three zeros)."""
+        n = eta.size
+        order = np.argsort(time, kind="stable")
+        eta, t, d = eta[order], time[order], status[order]
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))  # (comparisons: a NaN stays a NaN)
+        S = np.cumsum(np.exp(a)[::-1])[::-1]
+        if ties == "breslow":
+            S = S[first]
+        loglik = float(np.sum((w[order] * d) * (a - np.log(S))))
+        kg = np.where(d != 0, first, np.iinfo(np.int64).max)
+        comparable = concordant = discordant = 0
+        for k0 in range(0, n if pairs else 0, 512):  # (k, l) is comparable when first[l] > kg[k]: l > k follows from it
+            cmp = first[None, k0:] > kg[k0:k0 + 512, None]
+            ek, el = eta[k0:k0 + 512, None], eta[None, k0:]
+            comparable += int(cmp.sum())
+            concordant += int((cmp & (ek > el)).sum())
+            discordant += int((cmp & (ek < el)).sum())
+        return loglik, comparable, concordant, discordant
+
+    def evaluate_survival(self, X, y, weight=None, ties="order"):
+        """Cox only: the fitted model on rows it may not have seen.  y: (n, 2) time and status (0 or 1) as in fit;
+        weight: n values or None.  Returns plain floats and ints: loglik, deviance = -2 loglik, n_events = sum w status,
+        comparable, concordant, discordant, tied_risk, c_index (NaN without a comparable pair); the definitions are those
+        of capi.evaluate_cox_device, which serves an X in GPU memory in one call on torch's current stream (y and weight
+        may be device arrays: n values each are copied to the host).  A NumPy X is evaluated in fp64 NumPy."""
+        if self.model_type_int != 4:
+            raise ValueError("evaluate_survival is for the Cox classes, this is a %s model" % self.model_type)
+        on_device = capi.is_device_array(X)
+        shape = tuple(capi._DeviceArray(X, "X", 2).shape if on_device else np.asarray(X).shape)
+        if len(shape) != 2 or shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        n = shape[0]
+        if ties not in capi.TIES:
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
+        if not y_dev:
+            y = np.asarray(y, dtype=np.float64)
+        yshape = capi._DeviceArray(y, "y").shape if y_dev else y.shape
+        if tuple(yshape) != (n, 2):
+            raise ValueError("y should have shape (X.shape(0), 2) = (%d, 2): time and status, got %s"
+                             % (n, tuple(yshape)))
+        if weight is not None:
+            if not w_dev:
+                weight = np.asarray(weight, dtype=np.float64).reshape(-1)
+            if (capi._DeviceArray(weight, "weight").size if w_dev else weight.size) != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+        if y_dev:
+            y = capi.device_to_host(y, _current_stream(y))
+        w = np.ones(n) if weight is None else (
+            capi.device_to_host(weight, _current_stream(weight)).reshape(-1) if w_dev else weight)
+        time, status = np.ascontiguousarray(y[:, 0]), np.ascontiguousarray(y[:, 1])
+        if np.isnan(time).any():
+            raise ValueError("There is NAN value in y")
+        if not np.isin(status, (0.0, 1.0)).all():
+            raise ValueError("status (y[:, 1]) should be 0 or 1")
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.evaluate_cox_device(X, cols, beta[cols], time, status, weight=None if weight is None else w,
+                                           ties=ties, stream=_current_stream(X))
+            loglik, comparable = float(got["loglik"][0]), got["comparable"]
+            concordant, discordant = int(got["concordant"][0]), int(got["discordant"][0])
+        else:
+            X = np.asarray(X, dtype=np.float64)
+            eta = np.zeros(n)
+            for j in cols:  # (column by column: a row's sum does not depend on where the row lies)
+                eta += X[:, j] * beta[j]
+            loglik, comparable, concordant, discordant = self._survival_host(eta, time, status, w, ties)
+        tied = comparable - concordant - discordant
+        return {"loglik": loglik, "deviance": -2.0 * loglik, "n_events": float(np.sum(w * status)),
+                "comparable": comparable, "concordant": concordant, "discordant": discordant, "tied_risk": tied,
+                "c_index": float(capi.c_index(concordant, tied, comparable))}
+
+    def concordance(self, X, y):
+        """Harrell's c_index of evaluate_survival(X, y) (Cox only)."""
+        if self.model_type_int != 4:
+            raise ValueError("concordance is for the Cox classes, this is a %s model" % self.model_type)
+        return self.evaluate_survival(X, y)["c_index"]
 
 
 def _make(name, algorithm_type, model_type):

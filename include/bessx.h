@@ -286,6 +286,47 @@ typedef struct {
   void *stream;
 } bessx_eval_input;
 int bessx_eval_device(const bessx_eval_input *in, double *loss, double *aux, double *sum_w);
+/* ---------------------------------------------------------------------------------------
+ * 2e. Held-out Cox partial log-likelihood and Harrell's concordance on an X already in GPU memory
+ *     (bessx_k_coxeval.hip).  Stateless like sections 2c / 2d and the same model (cols, B, R), without an intercept:
+ *         eta(i, r) = sum_k x(i, cols[k]) * B[k * R + r]
+ *     (a coefficient that is exactly zero takes nothing from its column).  time, status (0 or 1) and weight (may be NULL =
+ *     ones) are n values each in HOST memory.  The library sorts the rows itself: pi = std::stable_sort of the row
+ *     numbers by time, ascending, equal times in row order; position k holds row pi(k), first(k) is the smallest
+ *     position with the time of position k.  With a(k, r) = clamp(eta(pi(k), r), -30, 30), e = exp(a):
+ *         ties = 0 ("order", the reference's loglik_cox):  S(k, r) = sum_{l >= k} e(l, r)
+ *         ties = 1 ("breslow"):                             S(k, r) = sum_{l >= first(k)} e(l, r)
+ *         loglik[r] = sum_k w_k status_k (a(k, r) - log S(k, r))        (weights on the terms, risk sets unweighted)
+ *     want_pairs != 0: a pair of positions k < l is comparable when status_k = 1 and time_k < time_l strictly;
+ *     *comparable = their number (the data alone decides it), and per model pairs[3 r], pairs[3 r + 1], pairs[3 r + 2] =
+ *     the comparable pairs with eta_k > eta_l (concordant), eta_k < eta_l (discordant), neither (tied_risk: equal or
+ *     NaN), from the unclamped eta, unweighted, exact 64-bit integers.  want_pairs == 0: pairs may be NULL, *comparable
+ *     is still written, and the O(n^2) pair kernel is not launched.
+ *     x is read once, the support's columns only, where it lies; every floating-point sum has a fixed order (the same call
+ *     gives the same bits); the pair counts are added with integer atomics (exact in any order).  A NaN in a support
+ *     column makes the loglik of exactly the models that use the column NaN.  None of it is an error.
+ *     Argument errors (BESSX_ERR_ARG: the messages of section 2d for cols / strides / dtype; a NaN in time; a status
+ *     other than 0 or 1; ties outside {0, 1}) are found before any device call; without a GPU a call with valid arguments
+ *     returns BESSX_ERR_HIP.  Scratch memory (two R x n arrays of doubles and five n-vectors) is released before the call
+ *     returns.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  int R;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  int want_pairs;
+  void *stream;
+} bessx_cox_eval_input;
+int bessx_eval_cox_device(const bessx_cox_eval_input *in, double *loglik, long long *pairs, long long *comparable);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -598,6 +639,11 @@ int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long 
  * n * m * element size + n * 8 * (y_cols + 1) bytes. */
 int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                         const int *cols, int m, int R, int link, int y_cols, int repeats, double *avg_ms, double *gbps);
+/* The three stages of section 2e timed with device events, each in a loop of its own (one warm-up, then `repeats`
+ * launches): stage_ms[0] the predictor pass, [1] the risk-set scan and the likelihood reduction, [2] the pair counts
+ * (0 when want_pairs == 0).  Times (distinct, every second row an event) and coefficients of the library's own. */
+int bessx_op_cox_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int R, int ties, int want_pairs, int repeats, double *stage_ms);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
