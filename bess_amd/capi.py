@@ -34,6 +34,7 @@ SYMBOLS = [
     "bessx_session_cov_prefill_export", "bessx_session_cov_prefill_import", "bessx_session_cov_prefill_end",
     "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
+    "bessx_op_cox_state", "bessx_op_cox_score", "bessx_op_cox_score_multi",
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
@@ -178,6 +179,9 @@ def lib():
         L.bessx_comm_allgather_f64.argtypes = [_vp, _D, _i, _D]
         L.bessx_comm_destroy.argtypes = [_vp]
         L.bessx_comm_destroy.restype = None
+        L.bessx_op_cox_state.argtypes = [_D, _i, _i, _D, _D, _D, _I, _i, _D, _D, _D, _D, _D, _D, _D, _D]
+        L.bessx_op_cox_score.argtypes = [_D, _i, _i, _D, _D, _D, _I, _i, _D, _d, _i, _D]
+        L.bessx_op_cox_score_multi.argtypes = [_D, _i, _i, _D, _D, _D, _I, _i, _D, _i, _d, _D]
         L.bessx_op_xtv_multi.argtypes = [_D, _i, _i, _i, _D, _D, _i, _D, _D]
         L.bessx_op_xtv_multi_bench.argtypes = [_i, _i, _i, _i, _i, _D, _D]
         L.bessx_op_topk_bench.argtypes = [_i, _i, _i, _i, _D]
@@ -867,6 +871,50 @@ def op_xtv_multi(x, vs, v2s=None):
     v2a = None if v2s is None else np.ascontiguousarray(v2s, dtype=np.float64)
     _check(lib().bessx_op_xtv_multi(_dp(x), n, p, n, _dp(vs), _dp(v2a), nc, _dp(out), _dp(out2)))
     return (out, out2) if v2s is not None else out
+
+
+def _cox_op_args(x, status, weight, mask, cols, b):
+    x = np.asfortranarray(x, dtype=np.float64)
+    cols = _i32(cols).reshape(-1)
+    return (x, _f64(status), None if weight is None else _f64(weight), None if mask is None else _f64(mask), cols,
+            _f64(b))
+
+
+def op_cox_state(x, status, cols, b, weight=None, mask=None):
+    """The Cox state pass alone for the model (cols, b) on rows in time order (bessx_op_cox_state): a dict of
+    e, theta, s0, rs0, s_all, s_test (n each; s_test None without a mask) and loss = (all rows, test rows)."""
+    x, st, w, mk, cols, b = _cox_op_args(x, status, weight, mask, cols, b)
+    n, p = x.shape
+    out = {k: np.zeros(n) for k in ("e", "theta", "s0", "rs0", "s_all", "s_test")}
+    loss = np.zeros(2)
+    _check(lib().bessx_op_cox_state(_dp(x), n, p, _dp(st), _dp(w), _dp(mk), _ip(cols), cols.size, _dp(b),
+                                    *[_dp(out[k]) for k in ("e", "theta", "s0", "rs0", "s_all", "s_test")], _dp(loss)))
+    if mk is None:
+        out["s_test"] = None
+    out["loss"] = loss
+    return out
+
+
+def op_cox_score(x, status, cols, b, lam=0.0, form=1, weight=None, mask=None):
+    """Cox sacrifice scores bd (p) of the model (cols, b); form 0 = two passes over X, 1 = one pass."""
+    x, st, w, mk, cols, b = _cox_op_args(x, status, weight, mask, cols, b)
+    n, p = x.shape
+    bd = np.zeros(p)
+    _check(lib().bessx_op_cox_score(_dp(x), n, p, _dp(st), _dp(w), _dp(mk), _ip(cols), cols.size, _dp(b), float(lam),
+                                    int(form), _dp(bd)))
+    return bd
+
+
+def op_cox_score_multi(x, status, cols, bs, lam=0.0, weight=None, mask=None):
+    """... of the nc models (cols, bs[c]) in one pass over X (k_cox_score1p_mc): nc x p."""
+    x, st, w, mk, cols, bs = _cox_op_args(x, status, weight, mask, cols, bs)
+    n, p = x.shape
+    bs = np.ascontiguousarray(np.atleast_2d(bs))
+    nc = bs.shape[0]
+    bd = np.zeros((nc, p))
+    _check(lib().bessx_op_cox_score_multi(_dp(x), n, p, _dp(st), _dp(w), _dp(mk), _ip(cols), cols.size, _dp(bs), nc,
+                                          float(lam), _dp(bd)))
+    return bd
 
 
 def op_topk(score, k):

@@ -670,6 +670,150 @@ int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbp
   return BESSX_OK;
 }
 
+// ---- the Cox solver's state pass and score passes alone (tests/test_cox_ops_gpu.py) ------------------------------
+namespace {
+
+// what a session holds of a Cox problem, for one coefficient vector: X padded to the session's row stride, status,
+// weights (ones without), the row mask, an open FitCtrl (l = 0 = the `when` of the state pass) and the state vectors
+struct CoxOpState {
+  int U = 1, nrb = 0, nsse = 0;
+  long ld = 0;
+  double *X = nullptr, *y = nullptr, *w = nullptr, *mask = nullptr, *b = nullptr, *stats = nullptr;
+  int *cols = nullptr;
+  FitCtrl *ctrl = nullptr;
+  CoxBufs cb = {};
+};
+
+int cox_op_check(const char *who, const double *x, int n, int p, const double *status, const int *cols, int m,
+                 const double *b) {
+  if (!x || !status || n < 1 || p < 1 || m < 0 || m > p || (m > 0 && (!cols || !b)))
+    return fail(BESSX_ERR_ARG, std::string(who) + ": bad arguments");
+  for (int a = 0; a < m; a++)
+    if (cols[a] < 0 || cols[a] >= p) return fail(BESSX_ERR_ARG, std::string(who) + ": column index out of range");
+  return 0;
+}
+
+// uploads the problem (dX given: X is shared with an earlier state of the same call) and runs launch_cox_state
+int cox_op_state(Owner &sc, const double *x, int n, int p, const double *status, const double *weight,
+                 const double *mask, const int *cols, int m, const double *b, int one_pass, double *dX, CoxOpState *o) {
+  o->U = n >= 4096 ? 8 : (n >= 2048 ? 4 : (n >= 1024 ? 2 : 1));  // the session's row stride (bessx_session.cpp)
+  if (dX) {
+    o->X = dX;
+    o->ld = ((long)n + 128L * o->U - 1) / (128L * o->U) * (128L * o->U);
+  } else if (int rc = upload_padded(sc, x, n, p, n, o->U, &o->X, &o->ld)) {
+    return rc;
+  }
+  const long ld = o->ld;
+  o->nrb = (int)(ld / (128L * o->U));
+  o->nsse = (int)((ld + 255) / 256);
+  if (int rc = upload_vec_padded(sc, status, n, ld, &o->y)) return rc;
+  std::vector<double> ones((size_t)n, 1.0);
+  if (int rc = upload_vec_padded(sc, weight ? weight : ones.data(), n, ld, &o->w)) return rc;
+  if (mask)
+    if (int rc = upload_vec_padded(sc, mask, n, ld, &o->mask)) return rc;
+  HIPX(sc.zeros(&o->cols, (size_t)m));
+  HIPX(sc.zeros(&o->b, (size_t)m));
+  if (m > 0) {
+    HIPX(hipMemcpy(o->cols, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+    HIPX(hipMemcpy(o->b, b, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+  }
+  FitCtrl hc = {};
+  hc.k_cur = m;
+  HIPX(sc.alloc(&o->ctrl, 1));
+  HIPX(hipMemcpy(o->ctrl, &hc, sizeof(FitCtrl), hipMemcpyHostToDevice));
+  HIPX(sc.zeros(&o->stats, (size_t)2 * o->nsse));
+  CoxBufs &c = o->cb;
+  double **vec[] = {&c.E, &c.TH, &c.ET, &c.S0, &c.RS0, &c.SALL, &c.STEST, &c.EW, &c.WD, &c.C1, &c.CU, &c.CV, &c.C2};
+  for (double **v : vec) HIPX(sc.zeros(v, (size_t)ld));
+  HIPX(sc.zeros(&c.SCR, cox_scan_scratch_doubles(ld, 0)));
+  c.one_pass = one_pass;
+  HIPX(launch_cox_state(o->X, ld, n, o->y, o->w, o->mask, o->ctrl, 0, o->cols, o->b, c, o->stats, nullptr));
+  return 0;
+}
+
+// bd (p, host) of the state o: launch_cox_score_pass unless the pass has run already (part given), then launch_cox_score
+int cox_op_bd(Owner &sc, const CoxOpState &o, int p, const int *cols, int m, const double *b, double lambda,
+              double *part, double *bd) {
+  double *part2 = nullptr, *beta, *dbd;
+  if (!part) {
+    HIPX(sc.zeros(&part, cox_score_part_doubles(o.nrb, p, o.cb.one_pass)));
+    if (!o.cb.one_pass) HIPX(sc.zeros(&part2, cox_score_part_doubles(o.nrb, p, 0)));
+    HIPX(launch_cox_score_pass(o.X, o.ld, p, o.U, o.nrb, o.cb, part, part2, nullptr, 0, nullptr));
+  }
+  std::vector<double> hb((size_t)p, 0.0);
+  for (int a = 0; a < m; a++) hb[cols[a]] = b[a];
+  HIPX(sc.alloc(&beta, (size_t)p));
+  HIPX(sc.alloc(&dbd, (size_t)p));
+  HIPX(hipMemcpy(beta, hb.data(), (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(launch_cox_score(part, part2, o.nrb, p, beta, lambda, nullptr, dbd, nullptr, 0, nullptr));
+  HIPX(hipMemcpy(bd, dbd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // namespace
+
+int bessx_op_cox_state(const double *x, int n, int p, const double *status, const double *weight, const double *mask,
+                       const int *cols, int m, const double *b, double *e, double *theta, double *s0, double *rs0,
+                       double *s_all, double *s_test, double *loss) {
+  if (int rc = need_device()) return rc;
+  if (int rc = cox_op_check("op_cox_state", x, n, p, status, cols, m, b)) return rc;
+  Owner sc;
+  CoxOpState o;
+  if (int rc = cox_op_state(sc, x, n, p, status, weight, mask, cols, m, b, 0, nullptr, &o)) return rc;
+  const std::pair<double *, const double *> outs[] = {{e, o.cb.E},        {theta, o.cb.TH},    {s0, o.cb.S0},
+                                                      {rs0, o.cb.RS0},    {s_all, o.cb.SALL},  {s_test, mask ? o.cb.STEST : nullptr}};
+  for (const auto &pr : outs)
+    if (pr.first && pr.second) HIPX(hipMemcpy(pr.first, pr.second, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (loss) {  // added over the blocks in block order, as the session does (finish_fit)
+    std::vector<double> part((size_t)2 * o.nsse);
+    HIPX(hipMemcpy(part.data(), o.stats, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double tr = 0.0, te = 0.0;
+    for (int blk = 0; blk < o.nsse; blk++) {
+      tr += part[2 * blk];
+      te += part[2 * blk + 1];
+    }
+    loss[0] = tr;
+    loss[1] = te;
+  }
+  return BESSX_OK;
+}
+
+int bessx_op_cox_score(const double *x, int n, int p, const double *status, const double *weight, const double *mask,
+                       const int *cols, int m, const double *b, double lambda, int form, double *bd) {
+  if (int rc = need_device()) return rc;
+  if (int rc = cox_op_check("op_cox_score", x, n, p, status, cols, m, b)) return rc;
+  if (!bd || (form != 0 && form != 1)) return fail(BESSX_ERR_ARG, "op_cox_score: form 0 (two passes) or 1 (one pass)");
+  Owner sc;
+  CoxOpState o;
+  if (int rc = cox_op_state(sc, x, n, p, status, weight, mask, cols, m, b, form, nullptr, &o)) return rc;
+  return cox_op_bd(sc, o, p, cols, m, b, lambda, nullptr, bd);
+}
+
+int bessx_op_cox_score_multi(const double *x, int n, int p, const double *status, const double *weight,
+                             const double *mask, const int *cols, int m, const double *b, int nc, double lambda,
+                             double *bd) {
+  if (int rc = need_device()) return rc;
+  if (nc < 1 || nc > COX_MC_MAX || !bd) return fail(BESSX_ERR_ARG, "op_cox_score_multi: 1 <= nc <= 6");
+  if (int rc = cox_op_check("op_cox_score_multi", x, n, p, status, cols, m, b)) return rc;  // b: nc x m, row c = chain c
+  Owner sc;
+  std::vector<CoxOpState> o((size_t)nc);
+  CoxMc a = {};
+  a.nc = nc;
+  for (int c = 0; c < nc; c++) {
+    if (int rc = cox_op_state(sc, x, n, p, status, weight, mask, cols, m, m ? b + (size_t)c * m : b, 1, c ? o[0].X : nullptr, &o[c]))
+      return rc;
+    a.TH[c] = o[c].cb.TH;
+    a.CU[c] = o[c].cb.CU;
+    a.CV[c] = o[c].cb.CV;
+    a.C2[c] = o[c].cb.C2;
+    HIPX(sc.zeros(&a.out[c], cox_score_part_doubles(o[c].nrb, p, 1)));
+  }
+  HIPX(launch_cox_score1p_mc(o[0].X, o[0].ld, p, o[0].U, o[0].nrb, a, nullptr));
+  for (int c = 0; c < nc; c++)
+    if (int rc = cox_op_bd(sc, o[c], p, cols, m, m ? b + (size_t)c * m : b, lambda, a.out[c], bd + (size_t)c * p)) return rc;
+  return BESSX_OK;
+}
+
 int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps) {
   if (int rc = need_device()) return rc;
   if (bytes < (1 << 20) || repeats < 1 || !gbps) return fail(BESSX_ERR_ARG, "op_stream_copy: bad arguments");

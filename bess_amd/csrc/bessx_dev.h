@@ -381,6 +381,7 @@ int cox_hess_slab_rows(long ld);
 bool cox_hess_applies(int mt);
 hipError_t cox_hess_prepare();
 size_t cox_scan_scratch_doubles(long ld, int kmax);
+size_t cox_score_part_doubles(int nrb, int p, int one_pass);  // per buffer of launch_cox_score_pass (part; part2: one_pass = 0)
 hipError_t launch_cox_state(const double *X, long ld, int n, const double *y, const double *w, const double *mask,
                             const FitCtrl *ctrl, int when, const int *A_cur, const double *b_cur, CoxBufs cb,
                             double *stats, hipStream_t st);

@@ -24,23 +24,7 @@ __device__ __forceinline__ bool cox_scan_gate_closed(const FitCtrl *ctrl, int ga
   return false;
 }
 
-// exclusive offset of this thread's total among the 256 threads of the block (thread order = scan order)
-__device__ __forceinline__ double block_excl_256(double t, double *sm /*>=4*/, double *btot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double inc = t;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    double tt = __shfl_up(inc, o);
-    if (lane >= o) inc += tt;
-  }
-  if (lane == 63) sm[wave] = inc;
-  __syncthreads();
-  double off = 0.0;
-  for (int w = 0; w < wave; w++) off += sm[w];
-  if (btot != nullptr) *btot = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-  __syncthreads();
-  return off + inc - t;
-}
+// (the exclusive offset of a thread's total inside its block: block_excl_256, bessx_kdev.hpp)
 
 __global__ void __launch_bounds__(SC_T) k_scan3_tot(const double *__restrict__ in0, const double *__restrict__ in1,
                                                     const double *__restrict__ in2, long n, int suffix, int nvec,
@@ -1350,6 +1334,13 @@ hipError_t launch_cox_state(const double *X, long ld, int n, const double *y, co
     LAUNCH_CHECK();
   }
   return hipSuccess;
+}
+
+// doubles in the partial sums of one score pass: the one-pass form leaves five planes of nrb x p and P0 per row block
+// (k_cox_score1p), the two-pass form one plane in each of its two buffers
+size_t cox_score_part_doubles(int nrb, int p, int one_pass) {
+  const size_t plane = (size_t)nrb * (size_t)p;
+  return one_pass ? 5 * plane + (size_t)nrb : plane;
 }
 
 static int g_cox_score_variant = 1;  // the wave -> (column group, row block) map (1 = round 4, 0 = round 3)

@@ -36,28 +36,6 @@ struct CxStore {
   }
 };
 
-// exclusive offset of this thread's total among the 256 threads of the block (thread order = scan order) and the
-// block's total.  Additions only: the offset is the inclusive scan of the lane before (0 in lane 0) plus the totals of
-// the waves before.  (inclusive - own total, the form of block_excl_256 in bessx_k_cox.hip, cancels: behind a thread
-// whose total absorbs what came before it the difference is 0 or rounding noise, and exp(clamp(eta)) spans e^+-30.)
-__device__ __forceinline__ double cxe_block_excl(double t, double *sm /* 4 */, double *btot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double inc = t;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double tt = __shfl_up(inc, o);
-    if (lane >= o) inc += tt;
-  }
-  const double exc = __shfl_up(inc, 1);
-  if (lane == 63) sm[wave] = inc;
-  __syncthreads();
-  double off = 0.0;
-  for (int w = 0; w < wave; w++) off += sm[w];
-  *btot = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-  __syncthreads();
-  return lane ? off + exc : off;
-}
-
 }  // namespace
 
 // scr[r * nb + b] = total of block b (scan order: from the last position down) of model r = blockIdx.y
@@ -71,7 +49,7 @@ __global__ void __launch_bounds__(CXE_T) k_cxe_scan_tot(const double *__restrict
   for (int q = 0; q < CXE_E; q++)
     if (r0 + q < n) s += in[n - 1 - (r0 + q)];
   double bt;
-  (void)cxe_block_excl(s, sm, &bt);
+  (void)block_excl_256(s, sm, &bt);
   if (threadIdx.x == 0) scr[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = bt;
 }
 
@@ -90,7 +68,7 @@ __global__ void __launch_bounds__(CXE_T) k_cxe_scan_apply(double *__restrict__ e
     tt += x[q];
   }
   double bt;
-  double s = carry + cxe_block_excl(tt, sm, &bt);
+  double s = carry + block_excl_256(tt, sm, &bt);
 #pragma unroll
   for (int q = 0; q < CXE_E; q++)
     if (r0 + q < n) {

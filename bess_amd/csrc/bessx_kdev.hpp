@@ -83,6 +83,31 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// Exclusive offset of this thread's total among the 256 threads of the block (thread order = scan order), and the
+// block's total if btot is given.  Additions only: the offset is the inclusive shuffle scan of the lane before (0 in
+// lane 0) plus the totals of the waves before, in wave order.  Every term enters once and none is taken out again, so
+// for non-negative terms the offset is accurate RELATIVE TO ITSELF.  (inclusive - own total cancels: behind a thread
+// whose total absorbs what came before it the difference is 0 or rounding noise, and exp(clamp(eta)) spans e^+-30.)
+// Fixed order, the same for every launch.  The Cox solver's scans (bessx_k_cox.hip) and the held-out evaluation
+// (bessx_k_coxeval.hip) share this copy.
+__device__ __forceinline__ double block_excl_256(double t, double *sm /*>=4*/, double *btot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double inc = t;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double tt = __shfl_up(inc, o);
+    if (lane >= o) inc += tt;
+  }
+  const double exc = __shfl_up(inc, 1);
+  if (lane == 63) sm[wave] = inc;
+  __syncthreads();
+  double off = 0.0;
+  for (int w = 0; w < wave; w++) off += sm[w];
+  if (btot != nullptr) *btot = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+  __syncthreads();
+  return lane ? off + exc : off;
+}
+
 // Wave-wide reductions without LDS permutes: four DPP exchanges inside each row of 16 lanes (mirror, half mirror, the
 // two quad swaps: every lane of a row ends with the row's result), then the four rows through the scalar unit
 // (v_readlane).  A __shfl_xor butterfly costs one LDS round trip per stage and 32-bit word.

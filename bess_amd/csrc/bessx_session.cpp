@@ -63,8 +63,7 @@ void session_free(bessx_session *s) {
 
 // doubles in the score-pass partial sums of one row set
 size_t part_elems(const bessx_session *s) {
-  const size_t plane = (size_t)s->nrb * (size_t)s->p;
-  return (s->model_type == 4 && s->cox.one_pass) ? 5 * plane + (size_t)s->nrb : plane;
+  return cox_score_part_doubles(s->nrb, s->p, s->model_type == 4 && s->cox.one_pass);
 }
 
 // timing of the dominant kernel: event pairs on the session stream, resolved lazily

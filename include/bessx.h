@@ -616,6 +616,26 @@ int bessx_op_xtv_multi_bench(int n, int p, int nc, int two, int repeats, double 
 /* The same for the one-pass Cox score kernel (k_cox_score1p, 8*n*p bytes per launch); variant 1 = the one the solver runs
  * (wave map of round 4), 0 = round 3; 10 + nc (nc = 1..4) = the multi-chain kernel k_cox_score1p_mc with nc vector sets. */
 int bessx_op_cox_score_bench(int n, int p, int variant, int repeats, double *gbps, double *avg_ms);
+/* The Cox solver's state pass alone (k_cox_eta, the risk-set scans k_scan3_tot / k_scan3_apply, k_cox_loss) for the model
+ * (cols[m], b[m]) as a session runs it: x column-major n x p with the rows in time order, padded to the session's row
+ * stride; status n; weight n or NULL (ones); mask n (1 = training row, 0 = test row of a CV fold) or NULL.  Every output is
+ * n doubles and may be NULL: e = exp(clamp(x b, +-30)), theta = weight * e * mask, s0 = suffix sums of theta, rs0 = 1 / s0
+ * (0 where s0 is 0), s_all = suffix sums of e, s_test = suffix sums of e * (1 - mask) (written only with a mask);
+ * loss[0] = sum_i w_i delta_i log(e_i / s_all_i), loss[1] = the same over the test rows with s_test, each added over the
+ * workgroups in workgroup order as the session does. */
+int bessx_op_cox_state(const double *x, int n, int p, const double *status, const double *weight, const double *mask,
+                       const int *cols, int m, const double *b, double *e, double *theta, double *s0, double *rs0,
+                       double *s_all, double *s_test, double *loss);
+/* ... followed by the score pass and the sacrifice scores bd[p] (GroupPdasCox::get_A, src/Algorithm.h:1569-1640) with ridge
+ * lambda.  form 0: two passes over X (block totals, k_cox_carry, k_cox_colscan, k_cox_score); form 1: one pass
+ * (k_cox_score1p, k_cox_score_1p), what a session runs by default. */
+int bessx_op_cox_score(const double *x, int n, int p, const double *status, const double *weight, const double *mask,
+                       const int *cols, int m, const double *b, double lambda, int form, double *bd);
+/* ... and the one-pass form for nc (1..6) coefficient vectors on the same columns in ONE pass over X (k_cox_score1p_mc):
+ * b is nc x m, bd nc x p, row c = chain c.  Bitwise the scores of nc calls of bessx_op_cox_score with form 1. */
+int bessx_op_cox_score_multi(const double *x, int n, int p, const double *status, const double *weight,
+                             const double *mask, const int *cols, int m, const double *b, int nc, double lambda,
+                             double *bd);
 /* Device-to-device streaming copy rate in GB/s (read+write bytes / time): the measured HBM ceiling
  * quoted next to the spec peak in bench.py. */
 int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps);
