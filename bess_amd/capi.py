@@ -39,6 +39,7 @@ SYMBOLS = [
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
+    "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -81,6 +82,20 @@ class CoxEvalInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("B", _D), ("R", _i), ("time", _D), ("status", _D), ("weight", _D),
                 ("ties", _i), ("want_pairs", _i), ("stream", _vp)]
+
+
+class CoxBaselineInput(ctypes.Structure):
+    """bessx_cox_baseline_input: one Cox model, X in GPU memory, time / status / weight in host memory."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("time", _D), ("status", _D), ("weight", _D), ("stream", _vp)]
+
+
+class CoxSurvivalInput(ctypes.Structure):
+    """bessx_cox_survival_input: one Cox model, X in GPU memory, the baseline cumulative hazard at T times in host
+    memory, and how out is laid out; strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("hg", _D), ("T", _i), ("kind", _i), ("out_row_stride", _ll),
+                ("out_col_stride", _ll), ("out_on_device", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -201,6 +216,9 @@ def lib():
         L.bessx_op_eval_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D, _D]
         L.bessx_eval_cox_device.argtypes = [ctypes.POINTER(CoxEvalInput), _D, ctypes.POINTER(_ll), ctypes.POINTER(_ll)]
         L.bessx_op_cox_eval_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
+        L.bessx_cox_baseline_device.argtypes = [ctypes.POINTER(CoxBaselineInput), _I, _D, _D]
+        L.bessx_cox_survival_device.argtypes = [ctypes.POINTER(CoxSurvivalInput), _vp]
+        L.bessx_op_cox_surv_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
         _lib = L
     return _lib
 
@@ -1296,6 +1314,136 @@ def op_cox_eval_bench(x, cols, R=1, ties="order", concordance=True, repeats=20):
     _check(lib().bessx_op_cox_eval_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                          _ip(cols), cols.size, int(R), TIES[ties], int(bool(concordance)), repeats,
                                          _dp(ms)))
+    return tuple(float(v) for v in ms)
+
+
+SURV_KINDS = {"survival": 0, "cumhaz": 1}  # BESSX_SURV_*
+
+
+def _cox_model(dx, cols, B):
+    """(cols int32, B float64 (m,)) of one Cox model for the device matrix dx, checked."""
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 2 and B.shape[1] != 1:
+        raise ValueError("B must hold one model (len(cols) values), got shape %s" % (B.shape,))
+    cols, B, _ = _predict_model(dx, cols, B.reshape(-1), np.zeros(1))
+    return cols, np.ascontiguousarray(B.reshape(-1))
+
+
+def cox_baseline_device(x, cols, B, time, status, weight=None, stream=0):
+    """The Breslow baseline cumulative hazard of one Cox model on the rows it was fitted to, x a device matrix (n x p:
+    float64 or float32, any non-negative strides) read once where it lies, the support's columns only
+    (bessx_cox_baseline_device).  With eta = x[:, cols] @ B, the rows in the stable ascending order of time,
+    e = exp(clip(eta, -30, 30)) and S_k the sum of e over every row with time >= time_k:
+        H0(t) = sum over the rows k with time_k <= t of w_k status_k / S_k.
+    cols, B as in predict_device (one model); time, status (0 or 1), weight (None = ones, else >= 0): n values each, host or
+    device arrays (device arrays are copied to the host).  Returns {"times": (J,) the distinct times that carry an event,
+    ascending, "cumhaz": (J,) H0 at them, "n_events": sum of w * status}; J = 0 when every row is censored.  The prefix
+    sum is fp64, additions only, in a fixed order: the same call gives the same bits."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    cols, B = _cox_model(dx, cols, B)
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, a in given:  # (every shape is checked before anything is copied)
+        _survival_vector(a, n, what, check_only=True)
+    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    if weight is not None and not (host["weight"] >= 0.0).all():
+        raise ValueError("weight should be non-negative")
+    a = CoxBaselineInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.B = _ip(cols), cols.size, _dp(B)
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    a.stream = int(stream) if stream else None
+    J, times, cumhaz = _i(0), np.zeros(n), np.zeros(n)
+    _check(lib().bessx_cox_baseline_device(ctypes.byref(a), ctypes.byref(J), _dp(times), _dp(cumhaz)))
+    w = host.get("weight")
+    return {"times": times[:J.value].copy(), "cumhaz": cumhaz[:J.value].copy(),
+            "n_events": float(np.sum(host["status"] if w is None else w * host["status"]))}
+
+
+def baseline_at(base_times, base_cumhaz, times):
+    """The baseline cumulative hazard as a right-continuous step function, on the host: H0(t) = base_cumhaz at the last
+    base_times <= t, 0 before the first.  base_times ascending; times in any order, repeats allowed; a NaN in times is a
+    ValueError.  Returns an array of the shape of times."""
+    base_times, base_cumhaz = _f64(base_times).reshape(-1), _f64(base_cumhaz).reshape(-1)
+    if base_times.size != base_cumhaz.size:
+        raise ValueError("base_times and base_cumhaz must have the same size, got %d and %d"
+                         % (base_times.size, base_cumhaz.size))
+    times = np.asarray(times, dtype=np.float64)
+    if np.isnan(times).any():
+        raise ValueError("There is NAN value in times")
+    idx = np.searchsorted(base_times, times, side="right")
+    return np.where(idx > 0, np.concatenate([[0.0], base_cumhaz])[idx], 0.0)
+
+
+def cox_survival_device(x, cols, B, base_times, base_cumhaz, times=None, kind="survival", out=None, stream=0):
+    """Survival curves of one Cox model for the rows of a device matrix x (n x p: float64 or float32, any non-negative
+    strides), read once where it lies, the support's columns only (bessx_cox_survival_device): with eta = x[:, cols] @ B,
+    e = exp(clip(eta, -30, 30)) and H0 = baseline_at(base_times, base_cumhaz, times),
+        kind="survival":  S(t_j | x_i) = exp(-(H0(t_j) * e_i)),        kind="cumhaz":  H0(t_j) * e_i,
+    an (n, T) matrix that is written exactly once.  base_times, base_cumhaz: what cox_baseline_device returned;
+    times=None means the baseline's own times.  out: a float64 device array of shape (n, T) to write into, any strides;
+    out=None allocates a torch tensor on x's device when x is a torch tensor (torch is looked up, never imported) and
+    returns a NumPy array for any other device object.  stream: raw handle of the stream x was produced on; the result is
+    complete when the call returns."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if kind not in SURV_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(SURV_KINDS), kind))
+    cols, B = _cox_model(dx, cols, B)
+    grid = base_times if times is None else times
+    if np.ndim(grid) > 1:
+        raise ValueError("times must be 1-D")
+    hg = np.ascontiguousarray(baseline_at(base_times, base_cumhaz, grid).reshape(-1))
+    T = hg.size
+    if T < 1:
+        raise ValueError("times is empty: no curve to compute (a baseline without an event has no times of its own)")
+    if not (hg >= 0.0).all():
+        raise ValueError("base_cumhaz should be non-negative")
+    if out is not None:
+        if not is_device_array(out):
+            raise ValueError("out must be a device array")
+        do = _DeviceArray(out, "out")
+        if do.item != 8:
+            raise ValueError("out: a device array of float64 is needed (typestr '<f8')")
+        if do.shape != (n, T):
+            raise ValueError("out must have shape %s, got %s" % ((n, T), do.shape))
+        ptr, ors, ocs, on_device, result = do.ptr, do.strides[0], do.strides[1], 1, out
+    else:
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(x, torch.Tensor):
+            result = torch.empty((n, T), dtype=torch.float64, device=x.device)
+            ptr, on_device = int(result.data_ptr()), 1
+        else:
+            result = np.empty((n, T))
+            ptr, on_device = int(result.ctypes.data), 0
+        ors, ocs = T, 1
+    a = CoxSurvivalInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.B, a.hg, a.T, a.kind = _ip(cols), cols.size, _dp(B), _dp(hg), T, SURV_KINDS[kind]
+    a.out_row_stride, a.out_col_stride, a.out_on_device = ors, ocs, on_device
+    a.stream = int(stream) if stream else None
+    _check(lib().bessx_cox_survival_device(ctypes.byref(a), ptr))
+    return result
+
+
+def op_cox_surv_bench(x, cols, T=100, kind="survival", out_col_major=False, repeats=20):
+    """Milliseconds per launch of the kernels behind cox_survival_device / cox_baseline_device on the device matrix x for
+    the support cols, device events: (predictor pass that stores exp(clip(eta)) in row order, k_cxs_curves for an (n, T)
+    result laid out row-major or column-major, the baseline's hazard terms + forward scan + gather)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    if kind not in SURV_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(SURV_KINDS), kind))
+    if int(T) < 1:
+        raise ValueError("T must be at least 1")
+    ms = np.zeros(3)
+    _check(lib().bessx_op_cox_surv_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, int(T), SURV_KINDS[kind], int(bool(out_col_major)),
+                                         repeats, _dp(ms)))
     return tuple(float(v) for v in ms)
 
 

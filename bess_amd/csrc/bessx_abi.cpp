@@ -1443,3 +1443,263 @@ int bessx_op_cox_eval_bench(const void *x, int dtype, long long row_stride, long
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// Breslow baseline hazard and survival curves on a caller's device matrix (include/bessx.h section 2f)
+// ----------------------------------------------------------------------------------------------
+static_assert((int)BESSX_SURV_SURVIVAL == 0 && (int)BESSX_SURV_CUMHAZ == 1, "kind codes of launch_cox_surv_curves");
+
+namespace {
+
+const double kCoxZero = 0.0;  // Cox has no intercept: the coef0 of predict_upload_model
+
+// x, cols, m, B of one model (R = 1): everything that needs no device
+int cox_surv_check_model(const char *who, const void *x, int dtype, long long rs, long long cs, int n, int p,
+                         const int *cols, int m, const double *B) {
+  const std::string w(who);
+  if (!x) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (dtype != BESSX_F64 && dtype != BESSX_F32) return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (rs < 0 || cs < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m > 0 && !B) return fail(BESSX_ERR_ARG, w + ": null argument (B)");
+  return 0;
+}
+
+// the tie groups that hold an event: their times (ascending) and last positions
+void cox_event_groups(const CoxOrder &o, const double *time, int n, std::vector<double> *times, std::vector<int> *ends) {
+  std::vector<double> tpos((size_t)n);
+  for (int i = 0; i < n; i++) tpos[(size_t)o.pos[(size_t)i]] = time[i];
+  times->clear();
+  ends->clear();
+  bool event = false;
+  for (int k = 0; k < n; k++) {
+    event = event || o.kg[(size_t)k] != INT_MAX;
+    if (k == n - 1 || o.first[(size_t)k + 1] != o.first[(size_t)k]) {  // (position k ends its group)
+      if (event) {
+        times->push_back(tpos[(size_t)k]);
+        ends->push_back(k);
+      }
+      event = false;
+    }
+  }
+}
+
+// sc, o, ends and hh belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_baseline_run(Owner &sc, const CoxOrder &o, const std::vector<int> &ends, std::vector<double> &hh,
+                     const bessx_cox_baseline_input *in, double *cumhaz, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, J = (int)ends.size(), f32 = in->x_dtype == BESSX_F32;
+  CoxDev d;
+  if (int rc = cox_eval_stage(sc, o, in->cols, in->m, in->B, 1, n, 1, 0, st, &d)) return rc;
+  int *ends_d = nullptr;
+  double *scr = nullptr, *hout = nullptr;
+  HIPX(sc.alloc(&ends_d, (size_t)J));
+  HIPX(sc.alloc(&hout, (size_t)J));
+  HIPX(sc.alloc(&scr, (size_t)cox_surv_workspace(n)));
+  HIPX(hipMemcpyAsync(ends_d, ends.data(), (size_t)J * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPX(launch_cox_eval_eta(in->x, f32, in->x_row_stride, in->x_col_stride, n, d.cols, in->m, d.B, d.zero, 1, d.pos, d.eta,
+                           d.ex, st));
+  HIPX(launch_cox_eval_suffix(d.ex, n, 1, d.work, st));
+  // (eta has served: its n doubles hold h, then H)
+  HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, ends_d, J, d.eta, scr, hout, st));
+  hh.resize((size_t)J);
+  HIPX(hipMemcpyAsync(hh.data(), hout, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  std::copy(hh.begin(), hh.end(), cumhaz);
+  return 0;
+}
+
+// sc and tmp belong to the caller, as above
+int cox_survival_run(Owner &sc, std::vector<double> &tmp, const bessx_cox_survival_input *in, double *out,
+                     hipStream_t st) {
+  hipEvent_t ev = nullptr;
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, T = in->T, f32 = in->x_dtype == BESSX_F32;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *zero_d = nullptr, *ex = nullptr, *hg_d = nullptr, *stage = nullptr;
+  if (int rc = predict_upload_model(sc, in->cols, in->m, in->B, &kCoxZero, 1, st, &cols_d, &B_d, &zero_d)) return rc;
+  HIPX(sc.alloc(&ex, (size_t)n));
+  HIPX(sc.alloc(&hg_d, (size_t)T));
+  HIPX(hipMemcpyAsync(hg_d, in->hg, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(launch_cox_surv_ex(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, in->m, B_d, zero_d, ex, st));
+  if (in->out_on_device) {
+    HIPX(launch_cox_surv_curves(ex, hg_d, n, T, in->kind, out, in->out_row_stride, in->out_col_stride, st));
+    HIPX(hipStreamSynchronize(st));
+    return 0;
+  }
+  const size_t cnt = (size_t)n * (size_t)T;
+  HIPX(sc.alloc(&stage, cnt));
+  HIPX(launch_cox_surv_curves(ex, hg_d, n, T, in->kind, stage, T, 1, st));
+  const long long ors = in->out_row_stride, ocs = in->out_col_stride;
+  const bool dense = (T == 1 || ocs == 1) && (n == 1 || ors == T);
+  double *h = out;
+  if (!dense) {
+    tmp.resize(cnt);
+    h = tmp.data();
+  }
+  HIPX(hipMemcpyAsync(h, stage, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  if (!dense)
+    for (long long i = 0; i < n; i++)
+      for (long long j = 0; j < T; j++) out[i * ors + j * ocs] = h[i * T + j];
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_baseline_device(const bessx_cox_baseline_input *in, int *n_times, double *times, double *cumhaz) {
+  const std::string w("cox_baseline_device");
+  if (!in || !n_times || !times || !cumhaz) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_surv_check_model("cox_baseline_device", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                    in->p, in->cols, in->m, in->B))
+    return rc;
+  if (!in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
+  for (int i = 0; i < in->n; i++) {
+    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
+    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
+    if (in->weight && !(in->weight[i] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": weight must be non-negative");
+  }
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("cox_baseline_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
+                                   in->n, in->p, &dev))
+    return rc;
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  std::vector<double> gt;
+  std::vector<int> ends;
+  cox_event_groups(o, in->time, in->n, &gt, &ends);
+  int rc = 0;
+  if (!ends.empty()) {
+    HIPX(hipSetDevice(dev));
+    hipStream_t st = nullptr;
+    HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    {
+      Owner sc;
+      std::vector<double> hh;
+      rc = cox_baseline_run(sc, o, ends, hh, in, cumhaz, st);
+      if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and hh go after this)
+    }
+    (void)hipStreamDestroy(st);
+  }
+  if (!rc) {
+    *n_times = (int)ends.size();
+    std::copy(gt.begin(), gt.end(), times);
+  }
+  return rc;
+}
+
+int bessx_cox_survival_device(const bessx_cox_survival_input *in, double *out) {
+  const std::string w("cox_survival_device");
+  if (!in || !out) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_surv_check_model("cox_survival_device", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                    in->p, in->cols, in->m, in->B))
+    return rc;
+  if (in->T < 1 || !in->hg) return fail(BESSX_ERR_ARG, w + ": hg needs T >= 1 values");
+  for (int j = 0; j < in->T; j++)
+    if (!(in->hg[j] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": hg must be non-negative");
+  if (in->kind != BESSX_SURV_SURVIVAL && in->kind != BESSX_SURV_CUMHAZ)
+    return fail(BESSX_ERR_ARG, w + ": kind must be BESSX_SURV_SURVIVAL or BESSX_SURV_CUMHAZ");
+  if (in->out_row_stride < 0 || in->out_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if ((in->n > 1 && in->out_row_stride == 0) || (in->T > 1 && in->out_col_stride == 0))
+    return fail(BESSX_ERR_ARG, w + ": out: a zero stride along an axis longer than 1");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("cox_survival_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
+                                   in->n, in->p, &dev))
+    return rc;
+  if (in->out_on_device) {
+    int od = -1;
+    if (int rc = check_device_matrix("cox_survival_device: out", out, BESSX_F64, in->out_row_stride, in->out_col_stride,
+                                     in->n, in->T, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, w + ": out is not on the device that owns x");
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> tmp;
+    rc = cox_survival_run(sc, tmp, in, out, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and tmp go after this)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int T, int kind, int out_col_major, int repeats, double *stage_ms) {
+  if (repeats < 1 || !stage_ms || T < 1 || (kind != BESSX_SURV_SURVIVAL && kind != BESSX_SURV_CUMHAZ))
+    return fail(BESSX_ERR_ARG, "op_cox_surv_bench: bad arguments");
+  if (int rc = cox_surv_check_model("op_cox_surv_bench", x, dtype, row_stride, col_stride, n, p, cols, m, &kCoxZero))
+    return rc;  // (B is the library's own)
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_surv_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m), time((size_t)n), status((size_t)n), hg((size_t)T);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int i = 0; i < n; i++) {  // distinct times in an order that is not the rows'
+    time[(size_t)i] = (double)(((long long)i * 7919) % n) + (double)i / (2.0 * n);
+    status[(size_t)i] = (double)(i % 2);
+  }
+  for (int j = 0; j < T; j++) hg[(size_t)j] = (j + 1.0) / T;
+  CoxOrder o;
+  cox_order(time.data(), status.data(), nullptr, n, &o);
+  std::vector<double> gt;
+  std::vector<int> ends;
+  cox_event_groups(o, time.data(), n, &gt, &ends);
+  const int J = (int)ends.size();
+  Owner sc;
+  CoxDev d;
+  if (int rc = cox_eval_stage(sc, o, cols, m, B.data(), 1, n, 1, 0, nullptr, &d)) return rc;
+  int *ends_d = nullptr;
+  double *scr = nullptr, *hout = nullptr, *ex = nullptr, *hg_d = nullptr, *out = nullptr;
+  HIPX(sc.alloc(&ends_d, (size_t)J));
+  HIPX(sc.alloc(&hout, (size_t)J));
+  HIPX(sc.alloc(&scr, (size_t)cox_surv_workspace(n)));
+  HIPX(sc.alloc(&ex, (size_t)n));
+  HIPX(sc.alloc(&hg_d, (size_t)T));
+  HIPX(sc.alloc(&out, (size_t)n * (size_t)T));
+  HIPX(hipMemcpy(ends_d, ends.data(), (size_t)J * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(hg_d, hg.data(), (size_t)T * sizeof(double), hipMemcpyHostToDevice));
+  const int f32 = dtype == BESSX_F32;
+  // the baseline's own kernels start from S: one predictor pass and suffix scan outside the timed loops
+  HIPX(launch_cox_eval_eta(x, f32, row_stride, col_stride, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, nullptr));
+  HIPX(launch_cox_eval_suffix(d.ex, n, 1, d.work, nullptr));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const long long ors = out_col_major ? 1 : T, ocs = out_col_major ? n : 1;
+  for (int stage = 0; stage < 3; stage++) {
+    float total = 0.f;
+    for (int i = -1; i < repeats; i++) {  // (i = -1: the warm-up)
+      HIPX(hipEventRecord(e0, nullptr));
+      if (stage == 0)
+        HIPX(launch_cox_surv_ex(x, f32, row_stride, col_stride, n, d.cols, m, d.B, d.zero, ex, nullptr));
+      else if (stage == 1)
+        HIPX(launch_cox_surv_curves(ex, hg_d, n, T, kind, out, ors, ocs, nullptr));
+      else
+        HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, ends_d, J, d.eta, scr, hout, nullptr));
+      HIPX(hipEventRecord(e1, nullptr));
+      HIPX(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPX(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 0) total += ms;
+    }
+    stage_ms[stage] = total / repeats;
+  }
+  return BESSX_OK;
+}
+
+}  // extern "C"

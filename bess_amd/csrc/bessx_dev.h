@@ -82,15 +82,29 @@ hipError_t launch_eval_finish(const double *part, long long nb, int RS, double *
 // (src, cols, B as in launch_predict; zero: R doubles of 0.0).  _loglik: ex becomes the suffix sums S in place, then
 // res[r] = sum_k wd[k] * (clamp(eta) - log S[first ? first[k] : k]); work: cox_eval_workspace(n, R) doubles.  _pairs:
 // cnt[2 r], cnt[2 r + 1] = pairs (k, l) with first[l] > kg[k] and eta_k > eta_l, eta_k < eta_l (kg[k] = first[k] for an
-// event, INT_MAX otherwise).  Everything is device memory.
+// event, INT_MAX otherwise).  _suffix is the first half of _loglik: ex becomes S in place (scr: ceil(n / 1024) * R doubles).
+// Everything is device memory.
 long long cox_eval_workspace(long long n, int R);
 hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                                const double *B, const double *zero, int R, const int *pos, double *eta, double *ex,
                                hipStream_t st);
+hipError_t launch_cox_eval_suffix(double *ex, long long n, int R, double *scr, hipStream_t st);
 hipError_t launch_cox_eval_loglik(const double *eta, double *ex, const double *wd, const int *first, long long n, int R,
                                   double *work, double *res, hipStream_t st);
 hipError_t launch_cox_eval_pairs(const double *eta, const int *kg, const int *first, long long n, int R,
                                  unsigned long long *cnt, hipStream_t st);
+// Breslow baseline and survival curves of one Cox model (bessx_k_coxsurv.hip).  _baseline: from S (launch_cox_eval_suffix,
+// R = 1) h(k) = wd[k] / S[first[k]], H = its forward prefix sums in place over h, hout[g] = H[ends[g]] for g < J; scr:
+// cox_surv_workspace(n) doubles.  _surv_ex: ex[i] = exp(clamp(eta_i, +-30)) in ROW order (src, cols, B as in launch_predict,
+// R = 1; zero: a double of 0.0).  _surv_curves: out[i * ors + j * ocs] = exp(-(hg[j] * ex[i])) (kind 0) or hg[j] * ex[i]
+// (kind 1), i < n, j < T.  Everything is device memory.
+long long cox_surv_workspace(long long n);
+hipError_t launch_cox_baseline(const double *S, const double *wd, const int *first, long long n, const int *ends, int J,
+                               double *h, double *scr, double *hout, hipStream_t st);
+hipError_t launch_cox_surv_ex(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                              const double *B, const double *zero, double *ex, hipStream_t st);
+hipError_t launch_cox_surv_curves(const double *ex, const double *hg, long long n, int T, int kind, double *out,
+                                  long long ors, long long ocs, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

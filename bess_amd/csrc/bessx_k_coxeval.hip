@@ -185,6 +185,18 @@ hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long
   return xb_launch(static_cast<const double *>(src), rs, cs, n, cols, m, B, zero, R, epi, st);
 }
 
+// stage 2 alone: ex (R x n, position-major) becomes S in place; scr: ceil(n / 1024) * R doubles (the first half of
+// cox_eval_workspace).  The baseline hazard of bessx_k_coxsurv.hip starts from the same S.
+hipError_t launch_cox_eval_suffix(double *ex, long long n, int R, double *scr, hipStream_t st) {
+  if (!ex || !scr || n < 1 || n > 0x7fffffffLL || R < 1 || R > 65535) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + CXE_B - 1) / CXE_B), (unsigned)R);
+  hipLaunchKernelGGL(k_cxe_scan_tot, grid, dim3(CXE_T), 0, st, ex, n, scr);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_cxe_scan_apply, grid, dim3(CXE_T), 0, st, ex, n, scr);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 // stages 2 and 3: ex becomes S in place; res[r] = loglik of model r.  wd: n doubles (w * delta in position order);
 // first: n ints or null (ties = "order": the identity); work: cox_eval_workspace(n, R) doubles; all device memory.
 hipError_t launch_cox_eval_loglik(const double *eta, double *ex, const double *wd, const int *first, long long n, int R,
@@ -194,10 +206,7 @@ hipError_t launch_cox_eval_loglik(const double *eta, double *ex, const double *w
   const long long nb = (n + CXE_B - 1) / CXE_B;
   const dim3 grid((unsigned)nb, (unsigned)R);
   double *scr = work, *part = work + nb * R;
-  hipLaunchKernelGGL(k_cxe_scan_tot, grid, dim3(CXE_T), 0, st, ex, n, scr);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_cxe_scan_apply, grid, dim3(CXE_T), 0, st, ex, n, scr);
-  LAUNCH_CHECK();
+  if (hipError_t e = launch_cox_eval_suffix(ex, n, R, scr, st)) return e;
   hipLaunchKernelGGL(k_cxe_loglik, grid, dim3(CXE_T), 0, st, eta, ex, wd, first, n, R, part);
   LAUNCH_CHECK();
   return launch_eval_finish(part, nb, R, res, st);

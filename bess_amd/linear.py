@@ -49,6 +49,13 @@ class bess_base:
     quantity train_loss = -2 loglik reports; ties="breslow": every row with time >= the row's), deviance = -2 loglik,
     n_events, and Harrell's concordance from exact pair counts (comparable, concordant, discordant, tied_risk, c_index);
     concordance(X, y) is its c_index.  A device X is read once, in place, by capi.evaluate_cox_device.
+    Predictions in time, Cox classes only: fit_baseline(X, y, weight=None) on the rows the model was fitted to sets
+    baseline_times_ and baseline_cumhaz_ (the Breslow cumulative baseline hazard H0 at the distinct event times) and
+    returns self; predict_survival(X, times=None, kind="survival") then gives the (n, T) matrix
+    S(t | x) = exp(-H0(t) exp(eta)) (kind="cumhaz": H0(t) exp(eta)) at the times given (None: baseline_times_), H0 a
+    right-continuous step function that is 0 before the first event.  For an X in GPU memory both read the support's
+    columns in place (capi.cox_baseline_device / capi.cox_survival_device) and the curves are a tensor on X's device that
+    is written once; a NumPy X is served in fp64 NumPy.  fit() does not call fit_baseline.
     """
 
     def __init__(self, algorithm_type, model_type, path_type, max_iter=20, exchange_num=0, is_warm_start=True,
@@ -398,21 +405,18 @@ class bess_base:
             discordant += int((cmp & (ek < el)).sum())
         return loglik, comparable, concordant, discordant
 
-    def evaluate_survival(self, X, y, weight=None, ties="order"):
-        """Cox only: the fitted model on rows it may not have seen.  y: (n, 2) time and status (0 or 1) as in fit;
-        weight: n values or None.  Returns plain floats and ints: loglik, deviance = -2 loglik, n_events = sum w status,
-        comparable, concordant, discordant, tied_risk, c_index (NaN without a comparable pair); the definitions are those
-        of capi.evaluate_cox_device, which serves an X in GPU memory in one call on torch's current stream (y and weight
-        may be device arrays: n values each are copied to the host).  A NumPy X is evaluated in fp64 NumPy."""
-        if self.model_type_int != 4:
-            raise ValueError("evaluate_survival is for the Cox classes, this is a %s model" % self.model_type)
+    def _survival_x(self, X):
+        """(on_device, n) of an X for the Cox methods, NumPy or in GPU memory; raises the message of predict()."""
         on_device = capi.is_device_array(X)
         shape = tuple(capi._DeviceArray(X, "X", 2).shape if on_device else np.asarray(X).shape)
         if len(shape) != 2 or shape[1] != self.p:
             raise ValueError("X.shape[1] should be " + str(self.p))
-        n = shape[0]
-        if ties not in capi.TIES:
-            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        return on_device, shape[0]
+
+    def _survival_data(self, X, y, weight):
+        """(on_device, n, time, status, w, weight) for the Cox methods: y (n, 2) and weight (n values or None) as host
+        arrays -- device arrays are copied once every shape has been checked -- w = ones without weights."""
+        on_device, n = self._survival_x(X)
         y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
         if not y_dev:
             y = np.asarray(y, dtype=np.float64)
@@ -434,6 +438,20 @@ class bess_base:
             raise ValueError("There is NAN value in y")
         if not np.isin(status, (0.0, 1.0)).all():
             raise ValueError("status (y[:, 1]) should be 0 or 1")
+        return on_device, n, time, status, w, weight
+
+    def evaluate_survival(self, X, y, weight=None, ties="order"):
+        """Cox only: the fitted model on rows it may not have seen.  y: (n, 2) time and status (0 or 1) as in fit;
+        weight: n values or None.  Returns plain floats and ints: loglik, deviance = -2 loglik, n_events = sum w status,
+        comparable, concordant, discordant, tied_risk, c_index (NaN without a comparable pair); the definitions are those
+        of capi.evaluate_cox_device, which serves an X in GPU memory in one call on torch's current stream (y and weight
+        may be device arrays: n values each are copied to the host).  A NumPy X is evaluated in fp64 NumPy."""
+        if self.model_type_int != 4:
+            raise ValueError("evaluate_survival is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
         beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
         cols = np.nonzero(beta)[0]
         if on_device:
@@ -457,6 +475,83 @@ class bess_base:
         if self.model_type_int != 4:
             raise ValueError("concordance is for the Cox classes, this is a %s model" % self.model_type)
         return self.evaluate_survival(X, y)["c_index"]
+
+    # ---- Cox: baseline hazard and survival curves ------------------------------------------------------------------
+    def _support_eta(self, X, cols, beta):
+        """X[:, cols] @ beta[cols] for a NumPy X, column by column: a row's sum does not depend on where the row lies."""
+        X = np.asarray(X, dtype=np.float64)
+        eta = np.zeros(X.shape[0])
+        for j in cols:
+            eta += X[:, j] * beta[j]
+        return eta
+
+    @staticmethod
+    def _baseline_host(eta, time, status, w):
+        """(times, cumhaz) in fp64 NumPy with the definitions of capi.cox_baseline_device: eta, time, status, w are
+        n-vectors in row order."""
+        n = eta.size
+        order = np.argsort(time, kind="stable")
+        eta, t, d, w = eta[order], time[order], status[order], w[order]
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        starts = np.nonzero(new)[0]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))  # (comparisons: a NaN stays a NaN)
+        S = np.cumsum(np.exp(a)[::-1])[::-1][first]
+        H = np.cumsum((w * d) / S)
+        ends = np.append(starts[1:] - 1, n - 1)
+        event = np.maximum.reduceat(d, starts) > 0
+        return t[ends][event], H[ends][event]
+
+    def fit_baseline(self, X, y, weight=None):
+        """Cox only, after fit(): the Breslow baseline cumulative hazard of the fitted model on the rows X, y (the rows
+        it was fitted to), y = (time, status) as in fit, weight n values >= 0 or None.  Sets baseline_times_ (the distinct
+        times that carry an event, ascending) and baseline_cumhaz_ (H0 at them; definitions: capi.cox_baseline_device) and
+        returns self.  An X in GPU memory is read once, in place, on torch's current stream (y and weight may be device
+        arrays: n values each are copied to the host); a NumPy X is served in fp64 NumPy.  fit() does not call this."""
+        if self.model_type_int != 4:
+            raise ValueError("fit_baseline is for the Cox classes, this is a %s model" % self.model_type)
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        if not (w >= 0.0).all():
+            raise ValueError("weight should be non-negative")
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.cox_baseline_device(X, cols, beta[cols], time, status, weight=None if weight is None else w,
+                                           stream=_current_stream(X))
+            self.baseline_times_, self.baseline_cumhaz_ = got["times"], got["cumhaz"]
+        else:
+            self.baseline_times_, self.baseline_cumhaz_ = self._baseline_host(self._support_eta(X, cols, beta), time,
+                                                                              status, w)
+        return self
+
+    def predict_survival(self, X, times=None, kind="survival"):
+        """Cox only, after fit_baseline(): the (n, T) matrix S(t_j | x_i) = exp(-H0(t_j) exp(clip(eta_i, -30, 30)))
+        (kind="survival") or the cumulative hazard H0(t_j) exp(clip(eta_i)) (kind="cumhaz") at the times given (any order,
+        repeats allowed; None = baseline_times_), H0 the right-continuous step function of capi.baseline_at.  An X in GPU
+        memory gives a tensor on X's device, written once by capi.cox_survival_device; a NumPy X gives NumPy."""
+        if self.model_type_int != 4:
+            raise ValueError("predict_survival is for the Cox classes, this is a %s model" % self.model_type)
+        on_device, n = self._survival_x(X)
+        if kind not in capi.SURV_KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (sorted(capi.SURV_KINDS), kind))
+        if getattr(self, "baseline_times_", None) is None:
+            raise ValueError("predict_survival needs the baseline hazard: call fit_baseline(X, y) first")
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            return capi.cox_survival_device(X, cols, beta[cols], self.baseline_times_, self.baseline_cumhaz_, times=times,
+                                            kind=kind, stream=_current_stream(X))
+        grid = self.baseline_times_ if times is None else times
+        if np.ndim(grid) > 1:
+            raise ValueError("times must be 1-D")
+        hg = capi.baseline_at(self.baseline_times_, self.baseline_cumhaz_, grid).reshape(-1)
+        if hg.size < 1:
+            raise ValueError("times is empty: no curve to compute (a baseline without an event has no times of its own)")
+        eta = self._support_eta(X, cols, beta)
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))
+        z = np.exp(a)[:, None] * hg[None, :]
+        return z if kind == "cumhaz" else np.exp(-z)
 
 
 def _make(name, algorithm_type, model_type):

@@ -327,6 +327,73 @@ typedef struct {
   void *stream;
 } bessx_cox_eval_input;
 int bessx_eval_cox_device(const bessx_cox_eval_input *in, double *loglik, long long *pairs, long long *comparable);
+/* ---------------------------------------------------------------------------------------
+ * 2f. Breslow baseline cumulative hazard and survival curves of ONE Cox model (R = 1, no intercept) on an X already in
+ *     GPU memory (bessx_k_coxsurv.hip).  Stateless like sections 2c to 2e.  x is described by dtype, element strides, n and
+ *     p; cols is ascending and distinct, m >= 0, in HOST memory; B holds m values in HOST memory; a coefficient that is
+ *     exactly zero takes nothing from its column; stream is as in section 2b.  eta_i = sum_k x(i, cols[k]) * B[k].
+ *
+ *     bessx_cox_baseline_device: the Breslow estimator on the rows the model was fitted to.  time, status (0 or 1) and
+ *     weight (may be NULL = ones; otherwise every weight >= 0) are n values each in HOST memory.  Positions, pi and
+ *     first(k) are those of section 2e (the host sorts with std::stable_sort).  With a(k) = clamp(eta(pi(k)), -30, 30),
+ *     e = exp(a):
+ *         S(k) = sum_{l >= first(k)} e(l)        (the risk set is unweighted, as in "breslow" of section 2e)
+ *         h(k) = w_k status_k / S(k),            H(k) = sum_{l <= k} h(l)
+ *     Outputs (host): *n_times = J, the number of distinct times that carry at least one row with status = 1 (the data
+ *     alone decide it; J = 0, every row censored, is valid); times[g], those times, ascending; cumhaz[g] = H(last position
+ *     with time times[g]).  The caller sizes times / cumhaz for n entries.  H is an fp64 prefix sum of additions only, in
+ *     a fixed order, every term entering once (no floating-point atomics: the same call gives the same bits).
+ *     Argument errors besides those of section 2e for x / cols / B: a NaN in time; a status other than 0 or 1; a
+ *     negative or NaN weight.
+ *
+ *     bessx_cox_survival_device: with e_i = exp(clamp(eta_i, -30, 30)) and hg (T >= 1 doubles in HOST memory: the
+ *     baseline cumulative hazard at the T requested times -- the caller does the step-function lookup),
+ *         kind = BESSX_SURV_SURVIVAL:  out(i, j) = exp(-(hg[j] * e_i))
+ *         kind = BESSX_SURV_CUMHAZ:    out(i, j) = hg[j] * e_i
+ *     out holds element (i, j) at [i * out_row_stride + j * out_col_stride] and is handled exactly as in section 2c:
+ *     out_on_device != 0: device memory of x's device, checked as there; otherwise host memory, staged through a device
+ *     buffer of the library's own.  The n x T matrix is written exactly once, at streaming rate when out_col_stride == 1
+ *     or out_row_stride == 1 (16-byte stores where the base and the other stride allow); any other strides are correct, not
+ *     fast -- the same arithmetic.  A NaN or negative hg[j] is BESSX_ERR_ARG.  hg[j] = 0 gives exactly 1.0 (_CUMHAZ:
+ *     exactly 0.0) for every row whose support columns are finite.  A NaN in a support column of row i reaches the T
+ *     outputs of row i and nothing else; columns outside the support are not read; x is never written.
+ *
+ *     Every device pointer is checked as in section 2b (a wrong pointer or a view past its allocation: BESSX_ERR_ARG, not
+ *     a fault).  Argument errors are found before any device call; without a GPU a call with valid arguments returns
+ *     BESSX_ERR_HIP.  Scratch memory (baseline: that of section 2e with R = 1 plus 2 J values; curves: n + T doubles, and
+ *     n * T more for a host out) is released before the call returns: counters 38 / 39 are back at their earlier values.
+ * ------------------------------------------------------------------------------------- */
+enum { BESSX_SURV_SURVIVAL = 0, BESSX_SURV_CUMHAZ = 1 };
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  const double *time;
+  const double *status;
+  const double *weight;
+  void *stream;
+} bessx_cox_baseline_input;
+int bessx_cox_baseline_device(const bessx_cox_baseline_input *in, int *n_times, double *times, double *cumhaz);
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  const double *hg;
+  int T;
+  int kind;
+  long long out_row_stride, out_col_stride;
+  int out_on_device;
+  void *stream;
+} bessx_cox_survival_input;
+int bessx_cox_survival_device(const bessx_cox_survival_input *in, double *out);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -664,6 +731,13 @@ int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long lon
  * (0 when want_pairs == 0).  Times (distinct, every second row an event) and coefficients of the library's own. */
 int bessx_op_cox_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int R, int ties, int want_pairs, int repeats, double *stage_ms);
+/* The kernels of section 2f timed the same way for an n x T result of the given kind, row-major (out_col_major == 0) or
+ * column-major, in a device buffer of the library's own: stage_ms[0] the predictor pass that stores exp(clamp(eta)) in row
+ * order, [1] k_cxs_curves, [2] the baseline's own kernels (hazard terms, forward scan, gather) behind a predictor pass and
+ * a risk-set scan that are not timed (they are stages 0 and 1 of bessx_op_cox_eval_bench).  Times, coefficients and hg
+ * of the library's own. */
+int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int T, int kind, int out_col_major, int repeats, double *stage_ms);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
