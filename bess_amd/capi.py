@@ -40,6 +40,7 @@ SYMBOLS = [
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
+    "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -96,6 +97,15 @@ class CoxSurvivalInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("B", _D), ("hg", _D), ("T", _i), ("kind", _i), ("out_row_stride", _ll),
                 ("out_col_stride", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class InfoInput(ctypes.Structure):
+    """bessx_info_input: one model, X in GPU memory, y and weight in host or GPU memory, where info and score go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("coef0", _d), ("link", _i), ("y_host", _D), ("y_dev", _vp),
+                ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
+                ("weight_stride", _ll), ("info", _vp), ("info_ld", _ll), ("score", _vp), ("out_on_device", _i),
+                ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -219,6 +229,9 @@ def lib():
         L.bessx_cox_baseline_device.argtypes = [ctypes.POINTER(CoxBaselineInput), _I, _D, _D]
         L.bessx_cox_survival_device.argtypes = [ctypes.POINTER(CoxSurvivalInput), _vp]
         L.bessx_op_cox_surv_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
+        L.bessx_info_device.argtypes = [ctypes.POINTER(InfoInput), _D, _D]
+        L.bessx_info_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
+        L.bessx_op_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1225,6 +1238,139 @@ def op_eval_bench(x, cols, R=1, link="identity", y_cols=1, repeats=20):
                                      _ip(cols), cols.size, int(R), LINKS[link], int(y_cols), repeats, ctypes.byref(ms),
                                      ctypes.byref(g)))
     return ms.value, g.value
+
+
+INFO_M_MAX = 1024  # the largest m + 1 of information_device (INFO_M_MAX of bessx_dev.h)
+
+
+def info_workspace(n, m, link="identity", weighted=False, dtype=np.float64, row_stride=None, col_stride=1):
+    """(doubles of scratch memory, rows per slab, slabs) of an information_device call on an n-row matrix with a support
+    of m columns (bessx_info_workspace; no device is needed).  The row split depends on (n, m) alone."""
+    nd, rps, sl = _ll(0), _ll(0), _i(0)
+    rs = int(row_stride) if row_stride is not None else max(int(m), 1)
+    _check(lib().bessx_info_workspace(1 if np.dtype(dtype) == np.float32 else 0, rs, int(col_stride), int(n), int(m),
+                                      LINKS[link], int(bool(weighted)), ctypes.byref(nd), ctypes.byref(rps),
+                                      ctypes.byref(sl)))
+    return nd.value, rps.value, sl.value
+
+
+def information_device(x, cols, beta, coef0, y, link="identity", weight=None, stream=0):
+    """Expected information and score of ONE model on a device matrix x (n x p: float64 or float32, any non-negative
+    strides), read where it lies (bessx_info_device): with eta = x[:, cols] @ beta + coef0 and z_i = (1, x[i, cols]),
+        info = sum_i v_i z_i z_i^T  ((m + 1, m + 1), both triangles, exact mirrors),   score = sum_i g_i z_i  (m + 1,)
+    v = w, g = w (y - eta) ("identity"); v = w p (1 - p), g = w (y - p) ("logistic", p = 1 / (1 + exp(-eta)) without
+    overflow or clamp); v = w exp(eta), g = w (y - exp(eta)) ("poisson").  cols: ascending distinct column numbers (may
+    be empty: the intercept-only model reads no element of x); beta: len(cols) finite values; y: n values, weight: n
+    non-negative values or None = ones, each a host or device array, float64 or float32, any stride.  Returns {"info",
+    "score", "loss", "sum_w"}: loss and sum_w are evaluate_device's for the same arguments, bit for bit.  This is the
+    UNPENALISED information on the original scale of x: a model fitted with lambda > 0 has score != 0.  No gathered copy
+    of x[:, cols] is made, every sum has a fixed order (the same call gives the same bits), and a NaN inside the support
+    view propagates (also from a row of weight 0).  len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y,
+    weight) were produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: information_device takes one model per call")
+    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
+    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
+        raise ValueError("beta and coef0 must be finite")
+    yh, dy, yrs, _, y_cols = _eval_y(y, n, 1)
+    a = InfoInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
+    a.y_stride = yrs
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [weight]
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_host = _dp(wh)
+            keep.append(wh)
+    M = cols.size + 1
+    info, score = np.empty((M, M)), np.empty(M)
+    a.info, a.info_ld, a.score, a.out_on_device = info.ctypes.data, M, score.ctypes.data, 0
+    a.stream = int(stream) if stream else None
+    loss, sw = _d(0), _d(0)
+    _check(lib().bessx_info_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw)))
+    return {"info": info, "score": score, "loss": loss.value, "sum_w": sw.value}
+
+
+def op_info_bench(x, cols, repeats=20):
+    """(ms per Gram sweep and finish, TFLOP/s of 2 n (m + 1) (m + 2) operations) of the information kernels on the device
+    matrix x for the support cols, device events."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms, tf = _d(0), _d(0)
+    _check(lib().bessx_op_info_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                     _ip(cols), cols.size, repeats, ctypes.byref(ms), ctypes.byref(tf)))
+    return ms.value, tf.value
+
+
+def wald_table(info, score, coef, link, loss, sum_w):
+    """The coefficient table from an information matrix, on the host in fp64 NumPy.  info (M, M), score (M,), coef (M,)
+    with the intercept first, as information_device orders them; link "identity", "logistic" or "poisson"; loss and
+    sum_w as information_device returns them.  With D = diag(info)^(-1/2) and S = D info D (unit diagonal), S is
+    Cholesky-factored and cov = D S^-1 D; for the identity link cov is multiplied by dispersion = loss / (sum_w - M)
+    (the residual variance; NaN when sum_w - M <= 0), for the other links dispersion = 1.  Returns coef, se =
+    sqrt(diag(cov)), z = coef / se, p_value = erfc(|z| / sqrt(2)) -- two-sided NORMAL, for the identity link too (the
+    normal approximation, not Student's t) -- cov, score, dispersion, dof = sum_w - M, cond = the 2-norm condition number
+    of S, and positive_definite.  When a diagonal entry of info is <= 0 or not finite, or S is not positive definite
+    (duplicated columns, a separated logistic sample), se, z, p_value and cov are NaN and positive_definite is False:
+    data decide that, so nothing is raised.  A score that is not near 0 says that coef is not the unpenalised optimum
+    of its support (lambda > 0), and cov is then not its covariance."""
+    import math
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    info = np.array(info, dtype=np.float64)
+    coef = np.asarray(coef, dtype=np.float64).reshape(-1)
+    score = np.asarray(score, dtype=np.float64).reshape(-1)
+    M = coef.size
+    if info.shape != (M, M) or score.shape != (M,):
+        raise ValueError("info must be (%d, %d) and score (%d,), got %s and %s" % (M, M, M, info.shape, score.shape))
+    dof = float(sum_w) - M
+    if link == "identity":
+        dispersion = float(loss) / dof if dof > 0 else float("nan")
+    else:
+        dispersion = 1.0
+    nan_v, nan_m = np.full(M, np.nan), np.full((M, M), np.nan)
+    out = {"coef": coef, "se": nan_v, "z": nan_v.copy(), "p_value": nan_v.copy(), "cov": nan_m, "score": score,
+           "dispersion": dispersion, "dof": dof, "cond": float("nan"), "positive_definite": False}
+    dg = np.diag(info)
+    if not (np.isfinite(info).all() and (dg > 0).all()):
+        return out
+    d = 1.0 / np.sqrt(dg)
+    S = info * d[:, None] * d[None, :]
+    S = 0.5 * (S + S.T)
+    ev = np.linalg.eigvalsh(S)
+    # (a factor can exist for a matrix that is singular to working precision: the smallest eigenvalue decides as well)
+    if not (ev[0] > M * np.finfo(np.float64).eps * ev[-1]):
+        out["cond"] = float("inf") if ev[0] <= 0 else float(ev[-1] / ev[0])
+        return out
+    try:
+        Lc = np.linalg.cholesky(S)
+    except np.linalg.LinAlgError:
+        out["cond"] = float(ev[-1] / ev[0])
+        return out
+    Li = np.linalg.solve(Lc, np.eye(M))
+    cov = (Li.T @ Li) * d[:, None] * d[None, :] * dispersion
+    se = np.sqrt(np.diag(cov))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = coef / se
+    pv = np.array([math.erfc(abs(v) / math.sqrt(2.0)) if v == v else float("nan") for v in z])
+    out.update(se=se, z=z, p_value=pv, cov=cov, cond=float(ev[-1] / ev[0]), positive_definite=True)
+    return out
 
 
 TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties

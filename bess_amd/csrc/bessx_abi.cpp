@@ -1703,3 +1703,211 @@ int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// expected information and score of one model on a caller's device matrix (include/bessx.h section 2g)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// everything about the call that needs no device
+int info_check_args(const char *who, const bessx_info_input *in, const double *loss, const double *sum_w) {
+  const std::string w(who);
+  if (!in || !loss || !sum_w) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->info || !in->score) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0 || in->y_stride < 0 || in->weight_stride < 0)
+    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, in->link)) return rc;
+  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
+  for (int k = 0; k < in->m; k++)
+    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
+  if (!std::isfinite(in->coef0)) return fail(BESSX_ERR_ARG, w + ": coef0 must be finite");
+  if ((in->y_host != nullptr) == (in->y_dev != nullptr))
+    return fail(BESSX_ERR_ARG, w + ": give y as a host pointer or as a device view (one of the two)");
+  if (in->y_dev && in->y_dtype != BESSX_F64 && in->y_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": y: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->weight_host && in->weight_dev)
+    return fail(BESSX_ERR_ARG, w + ": give weight as a host pointer or as a device vector, not both");
+  if (in->weight_dev && in->weight_dtype != BESSX_F64 && in->weight_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": weight: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->info_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m + 1");
+  if (in->m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  return 0;
+}
+
+// the arguments as section 2d's helpers take them (R = 1, one column of y)
+bessx_eval_input info_as_eval(const bessx_info_input *in) {
+  bessx_eval_input e{};
+  e.x = in->x;
+  e.x_dtype = in->x_dtype;
+  e.x_row_stride = in->x_row_stride;
+  e.x_col_stride = in->x_col_stride;
+  e.n = in->n;
+  e.p = in->p;
+  e.cols = in->cols;
+  e.m = in->m;
+  e.B = in->beta;
+  e.coef0 = &in->coef0;
+  e.R = 1;
+  e.link = in->link;
+  e.y_host = in->y_host;
+  e.y_dev = in->y_dev;
+  e.y_dtype = in->y_dtype;
+  e.y_row_stride = in->y_stride;
+  e.y_cols = 1;
+  e.weight_host = in->weight_host;
+  e.weight_dev = in->weight_dev;
+  e.weight_dtype = in->weight_dtype;
+  e.weight_stride = in->weight_stride;
+  e.stream = in->stream;
+  return e;
+}
+
+// sc and h belong to the caller: they must outlive everything this function queues on st, also when it fails half way
+int info_run(Owner &sc, std::vector<double> &h, const bessx_info_input *in, double *loss, double *sum_w,
+             hipStream_t st) {
+  // reads and writes come after everything the caller has queued on its stream so far
+  hipEvent_t ev = nullptr;
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const bessx_eval_input e = info_as_eval(in);
+  const int f32 = in->x_dtype == BESSX_F32, m = in->m;
+  const size_t M = (size_t)m + 1;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *res = nullptr, *stage = nullptr;
+  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
+  EvalData d;
+  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  HIPX(sc.alloc(&work, (size_t)info_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, m, in->link,
+                                               d.w != nullptr)));
+  HIPX(sc.alloc(&res, 3));
+  double *info_d = in->info, *score_d = in->score;
+  long long ld = in->info_ld;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&stage, M * M + M));
+    info_d = stage;
+    score_d = stage + M * M;
+    ld = (long long)M;
+  }
+  HIPX(launch_info(in->x, f32, in->x_row_stride, in->x_col_stride, in->n, cols_d, m, B_d, c_d, in->link, d, work, res,
+                   info_d, ld, score_d, st));
+  h.resize(3 + (in->out_on_device ? 0 : M * M + M));
+  HIPX(hipMemcpyAsync(h.data(), res, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (!in->out_on_device)
+    HIPX(hipMemcpyAsync(h.data() + 3, stage, (M * M + M) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  *loss = h[0];
+  *sum_w = d.w ? h[2] : (double)in->n;
+  if (!in->out_on_device) {
+    for (size_t j = 0; j < M; j++) std::copy(h.begin() + 3 + j * M, h.begin() + 3 + (j + 1) * M, in->info + j * in->info_ld);
+    std::copy(h.begin() + 3 + M * M, h.end(), in->score);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_info_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int link,
+                         int weighted, long long *doubles, long long *rows_per_slab, int *slabs) {
+  if (!doubles || !rows_per_slab || !slabs) return fail(BESSX_ERR_ARG, "info_workspace: null argument");
+  if (x_dtype != BESSX_F64 && x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, "info_workspace: x: dtype must be BESSX_F64 or BESSX_F32");
+  if (x_row_stride < 0 || x_col_stride < 0) return fail(BESSX_ERR_ARG, "info_workspace: strides must be non-negative");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "info_workspace: empty matrix");
+  if (link != BESSX_LINK_IDENTITY && link != BESSX_LINK_LOGISTIC && link != BESSX_LINK_POISSON)
+    return fail(BESSX_ERR_ARG, "info_workspace: unknown link");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "info_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  *doubles = info_workspace(x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, m, link, weighted != 0);
+  info_split(n, m, rows_per_slab, slabs);
+  return BESSX_OK;
+}
+
+int bessx_info_device(const bessx_info_input *in, double *loss, double *sum_w) {
+  if (int rc = info_check_args("info_device", in, loss, sum_w)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("info_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->y_dev) {
+    if (int rc = check_device_matrix("info_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: y is not on the device that owns x");
+  }
+  if (in->weight_dev) {
+    if (int rc = check_device_matrix("info_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
+                                     in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: weight is not on the device that owns x");
+  }
+  if (in->out_on_device) {
+    if (int rc = check_device_matrix("info_device: info", in->info, BESSX_F64, in->info_ld, 1, in->m + 1, in->m + 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: info is not on the device that owns x");
+    if (int rc = check_device_matrix("info_device: score", in->score, BESSX_F64, 1, 0, in->m + 1, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: score is not on the device that owns x");
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> h;
+    rc = info_run(sc, h, in, loss, sum_w, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                        const int *cols, int m, int repeats, double *avg_ms, double *tflops) {
+  if (!x || repeats < 1 || !avg_ms || !tflops) return fail(BESSX_ERR_ARG, "op_info_bench: bad arguments");
+  if (int rc = predict_check_model("op_info_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_info_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_info_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t M = (size_t)m + 1;
+  std::vector<double> v((size_t)n, 0.25), g((size_t)n);
+  for (size_t i = 0; i < g.size(); i++) g[i] = (i % 2) ? -0.5 : 0.5;
+  int *cols_d = nullptr;
+  double *v_d = nullptr, *g_d = nullptr, *part = nullptr, *out = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&v_d, v.size()));
+  HIPX(sc.alloc(&g_d, g.size()));
+  HIPX(sc.alloc(&part, (size_t)info_gram_workspace(n, m)));
+  HIPX(sc.alloc(&out, M * M + M));
+  if (m > 0) HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(v_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  HIPX(launch_info_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d, g_d, part, out, (long long)M, out + M * M,
+                        nullptr));
+  HIPX(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < repeats; i++)
+    HIPX(launch_info_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d, g_d, part, out, (long long)M, out + M * M,
+                          nullptr));
+  HIPX(hipEventRecord(e1, nullptr));
+  HIPX(hipEventSynchronize(e1));
+  float ms = 0.f;
+  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  *avg_ms = ms / repeats;
+  *tflops = 2.0 * (double)n * (double)M * (double)(M + 1) * repeats / ((double)ms * 1e-3) / 1e12;
+  return BESSX_OK;
+}
+
+}  // extern "C"

@@ -105,6 +105,22 @@ hipError_t launch_cox_surv_ex(const void *src, int f32, long long rs, long long 
                               const double *B, const double *zero, double *ex, hipStream_t st);
 hipError_t launch_cox_surv_curves(const double *ex, const double *hg, long long n, int T, int kind, double *out,
                                   long long ors, long long ocs, hipStream_t st);
+// expected information and score of one model (bessx_k_info.hip): with eta as in launch_predict (R = 1), v_i / g_i the
+// working and score weights of the link and z_i = (1, x(i, cols[0]), ...), info = sum_i v_i z_i z_i^T ((m + 1) x (m + 1),
+// leading dimension ld, both triangles, mirrors of each other) and score = sum_i g_i z_i (m + 1); res: launch_eval's
+// three doubles for R = 1 (the same bits).  m + 1 <= INFO_M_MAX.  work: info_workspace(...) doubles.  launch_info_gram is
+// the Gram sweep and its finish alone, from n-vectors v and g and part = info_gram_workspace(n, m) doubles.  The row
+// split (info_split) is a function of n and m alone.  Everything is device memory.
+constexpr int INFO_M_MAX = 1024;
+void info_split(long long n, int m, long long *rows_per_slab, int *slabs);
+long long info_gram_workspace(long long n, int m);
+long long info_workspace(int f32, long long rs, long long cs, long long n, int m, int link, int weighted);
+hipError_t launch_info_gram(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                            const double *vw, const double *gw, double *part, double *info, long long ld, double *score,
+                            hipStream_t st);
+hipError_t launch_info(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                       const double *B, const double *c, int link, const EvalData &d, double *work, double *res,
+                       double *info, long long ld, double *score, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

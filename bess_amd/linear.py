@@ -56,6 +56,13 @@ class bess_base:
     right-continuous step function that is 0 before the first event.  For an X in GPU memory both read the support's
     columns in place (capi.cox_baseline_device / capi.cox_survival_device) and the curves are a tensor on X's device that
     is written once; a NumPy X is served in fp64 NumPy.  fit() does not call fit_baseline.
+    inference(X, y, weight=None) is the coefficient table of the fitted model on these rows (Lm, Logistic, Poisson; None
+    for Cox; a 2-D beta raises): coef (intercept first), se, z, p_value (two-sided normal), cov, score, dispersion, dof,
+    cond, positive_definite and cols, from the unpenalised expected information sum_i v_i z_i z_i^T of the selected
+    columns (capi.wald_table).  An X in GPU memory is read in place by capi.information_device -- the support's columns
+    go through the fp64 matrix cores, no gathered copy is made and (m + 1)^2 + m + 3 numbers come back; a NumPy X is served
+    in fp64 NumPy with the same definitions.  The table ignores that the columns were selected, and a model fitted with
+    lambda > 0 reports score != 0: its se are those of the unpenalised problem at a point that is not its optimum.
     """
 
     def __init__(self, algorithm_type, model_type, path_type, max_iter=20, exchange_num=0, is_warm_start=True,
@@ -358,6 +365,74 @@ class bess_base:
                 out["d2"] = 1.0 - out["deviance"] / null
         if not multi:
             out = {k: float(v[0]) for k, v in out.items()}
+        return out
+
+    # ---- coefficient table ---------------------------------------------------------------------------------------
+    @staticmethod
+    def _information_host(link, Xs, beta, coef0, y, w):
+        """information_device's quantities in fp64 NumPy: Xs (n, m) the support's columns, beta (m,), y (n,), w (n,)."""
+        n = Xs.shape[0]
+        eta = Xs @ beta + coef0
+        if link == "identity":
+            v, g, f = w.copy(), w * (y - eta), (y - eta) ** 2
+        elif link == "logistic":
+            t = np.exp(-np.abs(eta))
+            p = np.where(eta >= 0, 1.0, t) / (1.0 + t)
+            v, g = w * (t / ((1.0 + t) * (1.0 + t))), w * (y - p)
+            f = np.maximum(eta, 0.0) + np.log1p(t) - y * eta
+        else:
+            e = np.exp(eta)
+            v, g, f = w * e, w * (y - e), e - y * eta
+        Z = np.column_stack([np.ones(n), Xs])
+        info = Z.T @ (v[:, None] * Z)
+        info = np.tril(info) + np.tril(info, -1).T  # (both triangles from the lower one, as the kernel writes them)
+        return {"info": info, "score": Z.T @ g, "loss": float((w * f).sum()), "sum_w": float(w.sum())}
+
+    def inference(self, X, y, weight=None):
+        """Standard errors and Wald tests of the fitted model on the rows (X, y): capi.wald_table's dict -- coef
+        (intercept first), se, z, p_value, cov, score, dispersion, dof, cond, positive_definite -- plus cols, the
+        selected columns in the order of coef[1:].  The information is the unpenalised expected information
+        sum_i v_i z_i z_i^T, z_i = (1, X[i, cols]), on the original scale of X (capi.information_device states v and the
+        score weights g per family); for Lm cov = (loss / (n_eff - m - 1)) (Z^T W Z)^-1 and p_value is the normal
+        approximation.  score = sum_i g_i z_i is 0 up to rounding at the unpenalised optimum of the support: a model
+        fitted with lambda > 0 shows score != 0.  Selection is not corrected for.  An X in GPU memory is read in place on
+        torch's current stream, the support's columns only, and y and weight may be device arrays too; a NumPy X is
+        served in fp64 NumPy with the same definitions.  Cox: None.  A 2-D beta (Lm fitted to several responses) raises
+        ValueError: one model per call."""
+        on_device = capi.is_device_array(X)
+        shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
+        if len(shape) != 2 or shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        n = shape[0]
+        if self.model_type_int == 4:
+            return None
+        beta, cols, coef0, multi = self._model_arrays()
+        if multi:
+            raise ValueError("inference() takes one model: this Lm was fitted to %d responses (a 2-D beta), which is "
+                             "not supported" % beta.shape[1])
+        link = self._LINK[self.model_type_int]
+        y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
+        ysize = capi._DeviceArray(y, "y").size if y_dev else np.size(y)
+        if ysize != n:
+            raise ValueError("X.shape(0) should be equal to y.size")
+        if weight is not None and (capi._DeviceArray(weight, "weight").size if w_dev else np.size(weight)) != n:
+            raise ValueError("X.shape(0) should be equal to weight.size")
+        if on_device:
+            if not y_dev:
+                y = np.asarray(y, dtype=np.float64).reshape(-1)
+            got = capi.information_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight,
+                                          stream=_current_stream(X))
+        else:
+            yh = (capi.device_to_host(y, _current_stream(y)) if y_dev else np.asarray(y, dtype=np.float64)).reshape(-1)
+            if weight is None:
+                w = np.ones(n)
+            else:
+                w = (capi.device_to_host(weight, _current_stream(weight)) if w_dev
+                     else np.asarray(weight, dtype=np.float64)).reshape(-1)
+            got = self._information_host(link, np.asarray(X, dtype=np.float64)[:, cols], beta[cols], coef0[0], yh, w)
+        out = capi.wald_table(got["info"], got["score"], np.concatenate([coef0[:1], beta[cols]]), link, got["loss"],
+                              got["sum_w"])
+        out["cols"] = cols
         return out
 
     def score(self, X, y, weight=None):

@@ -394,6 +394,65 @@ typedef struct {
   void *stream;
 } bessx_cox_survival_input;
 int bessx_cox_survival_device(const bessx_cox_survival_input *in, double *out);
+/* ---------------------------------------------------------------------------------------
+ * 2g. Expected information and score of ONE model on an X already in GPU memory (bessx_k_info.hip): what a coefficient
+ *     table (standard errors, Wald z, p-values) is made of.  Stateless like sections 2c to 2f.  x, n, p, cols, m, link,
+ *     y, weight, stream: as in section 2d with R = 1 and one column of y (beta: m values, coef0: one value, HOST memory,
+ *     all finite).  With eta_i = sum_k x(i, cols[k]) * beta[k] + coef0 -- the loops of sections 2c / 2d, except that a
+ *     zero coefficient is multiplied like any other -- and z_i = (1, x(i, cols[0]), ..., x(i, cols[m - 1])):
+ *         info  = sum_i v_i z_i z_i^T      (m + 1) x (m + 1), entry (j, k) at [j * info_ld + k], info_ld >= m + 1;
+ *                                          both triangles are written and are bit-identical mirrors
+ *         score = sum_i g_i z_i            m + 1 values (intercept first)
+ *     link         v_i                                   g_i
+ *     _IDENTITY    w_i                                   w_i (y_i - eta_i)
+ *     _LOGISTIC    w_i p_i (1 - p_i)                     w_i (y_i - p_i),   p_i = 1 / (1 + exp(-eta_i)), evaluated from
+ *                                                        exp(-|eta_i|): no overflow, no clamp
+ *     _POISSON     w_i exp(eta_i)                        w_i (y_i - exp(eta_i))
+ *     *loss and *sum_w are those of section 2d for the same arguments, bit for bit (for the identity link *loss is the
+ *     weighted residual sum of squares).  This is the UNPENALISED expected information on the original scale of x: a
+ *     model fitted with a ridge penalty lambda > 0 has score != 0, and the inverse of info is then not its covariance.
+ *     The support's columns are read in place -- no gathered copy of x[:, cols] is made -- and accumulated in 16 x 16
+ *     tiles on the fp64 matrix cores, the lower triangle only; the rows are split into slabs whose number depends on
+ *     (n, m) alone, every slab writes one partial per tile and a second launch adds them in slab order: no
+ *     floating-point atomics, the same call gives the same bits.  Rows past n, columns outside the support and the
+ *     padding of the last tile are not read.  A NaN INSIDE the support view is no error and propagates by IEEE rules:
+ *     it makes eta_i NaN, so for the identity link row j and column j of info (its own entry of z) and every entry of
+ *     score are NaN, and for the other links, where v_i depends on eta_i, every entry of info as well -- also when
+ *     w_i = 0, since 0 * NaN is NaN.
+ *     info and score are device memory of x's device when out_on_device != 0 (checked as in section 2c), else host
+ *     memory.  loss and sum_w are host memory.  m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED, with every other
+ *     argument error (BESSX_ERR_ARG, the messages of section 2d; a non-finite beta or coef0) found before any device
+ *     call.  Scratch memory (bessx_info_workspace doubles, the model, host y / weight) is released before the call
+ *     returns: counters 38 / 39 are back at their earlier values.
+ *     bessx_info_workspace needs no device: the doubles of scratch memory of such a call and how its rows are split.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  double coef0;
+  int link;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_stride;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  double *info;
+  long long info_ld;
+  double *score;
+  int out_on_device;
+  void *stream;
+} bessx_info_input;
+int bessx_info_device(const bessx_info_input *in, double *loss, double *sum_w);
+int bessx_info_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int link,
+                         int weighted, long long *doubles, long long *rows_per_slab, int *slabs);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -738,6 +797,11 @@ int bessx_op_cox_eval_bench(const void *x, int dtype, long long row_stride, long
  * of the library's own. */
 int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int T, int kind, int out_col_major, int repeats, double *stage_ms);
+/* The Gram sweep of section 2g and the addition of its partials (k_info_gram, k_info_finish) timed the same way, from
+ * working weights of the library's own (v_i = 1 / 4, g_i alternating in sign): *avg_ms per pair of launches, *tflops =
+ * 2 n (m + 1) (m + 2) useful floating-point operations (both triangles and the score) per second / 1e12. */
+int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                        const int *cols, int m, int repeats, double *avg_ms, double *tflops);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
