@@ -34,7 +34,7 @@ SYMBOLS = [
     "bessx_session_cov_prefill_export", "bessx_session_cov_prefill_import", "bessx_session_cov_prefill_end",
     "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
-    "bessx_op_cox_state", "bessx_op_cox_score", "bessx_op_cox_score_multi",
+    "bessx_op_cox_state", "bessx_op_cox_score", "bessx_op_cox_score_multi", "bessx_op_glm_gh", "bessx_op_glm_irls", "bessx_op_glm_irls_geometry",
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
@@ -207,6 +207,9 @@ def lib():
         L.bessx_op_cox_state.argtypes = [_D, _i, _i, _D, _D, _D, _I, _i, _D, _D, _D, _D, _D, _D, _D, _D]
         L.bessx_op_cox_score.argtypes = [_D, _i, _i, _D, _D, _D, _I, _i, _D, _d, _i, _D]
         L.bessx_op_cox_score_multi.argtypes = [_D, _i, _i, _D, _D, _D, _I, _i, _D, _i, _d, _D]
+        L.bessx_op_glm_gh.argtypes = [_i, _D, _i, _i, _D, _D, _D, _I, _i, _D, _d, _d, _D, _D, _D, _D]
+        L.bessx_op_glm_irls.argtypes = [_i, _i, _i, _i, _d, _i, _D, _i, _i, _D, _D, _D, _I, _i, _D, _D, _D, _D, _D, _D, _I]
+        L.bessx_op_glm_irls_geometry.argtypes = [_i, _i, _I]
         L.bessx_op_xtv_multi.argtypes = [_D, _i, _i, _i, _D, _D, _i, _D, _D]
         L.bessx_op_xtv_multi_bench.argtypes = [_i, _i, _i, _i, _i, _D, _D]
         L.bessx_op_topk_bench.argtypes = [_i, _i, _i, _i, _D]
@@ -946,6 +949,44 @@ def op_cox_score_multi(x, status, cols, bs, lam=0.0, weight=None, mask=None):
     _check(lib().bessx_op_cox_score_multi(_dp(x), n, p, _dp(st), _dp(w), _dp(mk), _ip(cols), cols.size, _dp(bs), nc,
                                           float(lam), _dp(bd)))
     return bd
+
+
+def op_glm_gh(family, x, y, cols, b, coef0=0.0, lam=0.0, weight=None, mask=None, want_bd=True):
+    """The logistic (family 2) / Poisson (3) gradient and curvature pass alone for the model (cols, b, coef0)
+    (bessx_op_glm_gh): a dict of g, h (n each), loss = (all rows, test rows) and, with want_bd, the scores bd (p)."""
+    x, y, w, mk, cols, b = _cox_op_args(x, y, weight, mask, cols, b)
+    n, p = x.shape
+    out = {"g": np.zeros(n), "h": np.zeros(n), "loss": np.zeros(2), "bd": np.zeros(p) if want_bd else None}
+    _check(lib().bessx_op_glm_gh(int(family), _dp(x), n, p, _dp(y), _dp(w), _dp(mk), _ip(cols), cols.size, _dp(b),
+                                 float(coef0), float(lam), _dp(out["g"]), _dp(out["h"]), _dp(out["loss"]), _dp(out["bd"])))
+    return out
+
+
+def op_glm_irls(family, x, y, cols, bcur, route=-1, t=0, wfloor=1, lam=0.0, rows_per_slab=0, weight=None, mask=None,
+                want_bnext=True):
+    """One IRLS step from the iterate bcur (intercept first) on [1, x[:, cols]] (bessx_op_glm_irls): a dict of gram
+    ((T0 + 2)^2, the working response last), ll, bnext (T0 + 1; None without want_bnext: the step's system is not solved),
+    route (the one that ran: 1 fused, 0 five launches) and, from route 0 only, wv and z (n each; None from the fused step)."""
+    x, y, w, mk, cols, bcur = _cox_op_args(x, y, weight, mask, cols, bcur)
+    n, p = x.shape
+    T0 = cols.size
+    assert bcur.size == T0 + 1
+    gram = np.zeros((T0 + 2, T0 + 2), order="F")
+    wv, z, bnext, ll, taken = np.zeros(n), np.zeros(n), (np.zeros(T0 + 1) if want_bnext else None), _d(0), _i(-1)
+    _check(lib().bessx_op_glm_irls(int(family), int(route), int(t), int(wfloor), float(lam), int(rows_per_slab), _dp(x), n,
+                                   p, _dp(y), _dp(w), _dp(mk), _ip(cols), T0, _dp(bcur), _dp(gram), ctypes.byref(ll),
+                                   _dp(wv), _dp(z), _dp(bnext), ctypes.byref(taken)))
+    five = taken.value == 0
+    return {"gram": np.array(gram), "ll": ll.value, "bnext": bnext, "route": taken.value, "wv": wv if five else None,
+            "z": z if five else None}
+
+
+def op_glm_irls_geometry(T0, n):
+    """(padded rows, tile rows, chunks per group of the fused kernel or 0, the solver's rows per slab) of an IRLS step at
+    sparsity level T0 on n rows (bessx_op_glm_irls_geometry; needs no device)."""
+    out = np.zeros(4, dtype=np.int32)
+    _check(lib().bessx_op_glm_irls_geometry(int(T0), int(n), _ip(out)))
+    return tuple(int(v) for v in out)
 
 
 def op_topk(score, k):

@@ -814,6 +814,244 @@ int bessx_op_cox_score_multi(const double *x, int n, int p, const double *status
   return BESSX_OK;
 }
 
+namespace {
+
+// the log-likelihood of an IRLS step from its slab / block terms, added as irls_check_body<NT> adds them: thread i takes
+// the terms i, i + NT, ... in order, wave_sum folds the 64 lanes of a wave (xor 32, 16, ..., 1), the waves follow in order
+double irls_ll_sum(const std::vector<double> &part, int NT) {
+  std::vector<double> th((size_t)NT, 0.0);
+  for (size_t b = 0; b < part.size(); b++) th[b % NT] += part[b];
+  double s = 0.0;
+  for (int wv = 0; wv < NT / 64; wv++) {
+    double *v = th.data() + 64 * wv, nx[64];
+    for (int o = 32; o >= 1; o >>= 1) {
+      for (int l = 0; l < 64; l++) nx[l] = v[l] + v[l ^ o];
+      std::copy(nx, nx + 64, v);
+    }
+    s += v[0];
+  }
+  return s;
+}
+
+int glm_op_check(const char *who, int family, const double *x, int n, int p, const double *y, const int *cols, int m,
+                 const double *b) {
+  if (family != 2 && family != 3) return fail(BESSX_ERR_ARG, std::string(who) + ": family 2 (logistic) or 3 (Poisson)");
+  if (!x || !y || n < 1 || p < 1 || m < 0 || m > p || (m > 0 && (!cols || !b)))
+    return fail(BESSX_ERR_ARG, std::string(who) + ": bad arguments");
+  for (int a = 0; a < m; a++)
+    if (cols[a] < 0 || cols[a] >= p) return fail(BESSX_ERR_ARG, std::string(who) + ": column index out of range");
+  return 0;
+}
+
+// X, y, weights (ones without) and the fold mask (none without) as a session holds them
+struct GlmOpData {
+  int U = 1, nrb = 0, nsse = 0;
+  long ld = 0;
+  double *X = nullptr, *y = nullptr, *w = nullptr, *mask = nullptr;
+};
+
+int glm_op_upload(Owner &sc, const double *x, int n, int p, const double *y, const double *weight, const double *mask,
+                  GlmOpData *o) {
+  o->U = n >= 4096 ? 8 : (n >= 2048 ? 4 : (n >= 1024 ? 2 : 1));  // the session's row stride (bessx_session.cpp)
+  if (int rc = upload_padded(sc, x, n, p, n, o->U, &o->X, &o->ld)) return rc;
+  o->nrb = (int)(o->ld / (128L * o->U));
+  o->nsse = (int)((o->ld + 255) / 256);
+  if (int rc = upload_vec_padded(sc, y, n, o->ld, &o->y)) return rc;
+  std::vector<double> ones((size_t)n, 1.0);
+  if (int rc = upload_vec_padded(sc, weight ? weight : ones.data(), n, o->ld, &o->w)) return rc;
+  if (mask)
+    if (int rc = upload_vec_padded(sc, mask, n, o->ld, &o->mask)) return rc;
+  return 0;
+}
+
+}  // namespace
+
+int bessx_op_glm_gh(int family, const double *x, int n, int p, const double *y, const double *weight, const double *mask,
+                    const int *cols, int m, const double *b, double coef0, double lambda, double *g, double *h,
+                    double *loss, double *bd) {
+  if (int rc = need_device()) return rc;
+  if (int rc = glm_op_check("op_glm_gh", family, x, n, p, y, cols, m, b)) return rc;
+  Owner sc;
+  GlmOpData o;
+  if (int rc = glm_op_upload(sc, x, n, p, y, weight, mask, &o)) return rc;
+  const long ld = o.ld;
+  std::vector<double> lf((size_t)ld, 0.0);
+  if (family == 3) poisson_logfact(y, n, lf.data());
+  double *dlf, *db, *dg, *dh, *stats;
+  int *dcols;
+  FitCtrl *ctrl;
+  HIPX(sc.alloc(&dlf, (size_t)ld));
+  HIPX(hipMemcpy(dlf, lf.data(), (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(sc.zeros(&dcols, (size_t)m));
+  HIPX(sc.zeros(&db, (size_t)m));
+  if (m > 0) {
+    HIPX(hipMemcpy(dcols, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+    HIPX(hipMemcpy(db, b, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+  }
+  FitCtrl hc = {};  // l = 0: the pass at the start of a fit (when = 0), and slot 1 of the score pass behind it
+  hc.k_cur = m;
+  hc.coef0 = coef0;
+  HIPX(sc.alloc(&ctrl, 1));
+  HIPX(hipMemcpy(ctrl, &hc, sizeof(FitCtrl), hipMemcpyHostToDevice));
+  HIPX(sc.zeros(&dg, (size_t)ld));
+  HIPX(sc.zeros(&dh, (size_t)ld));
+  HIPX(sc.zeros(&stats, (size_t)2 * o.nsse));
+  HIPX(launch_glm_eta_gh(family, o.X, ld, n, o.y, o.w, o.mask, dlf, ctrl, 0, dcols, db, dg, dh, stats, nullptr));
+  if (g) HIPX(hipMemcpy(g, dg, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (h) HIPX(hipMemcpy(h, dh, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (loss) {  // added over the blocks in block order, as the session does (finish_fit)
+    std::vector<double> part((size_t)2 * o.nsse);
+    HIPX(hipMemcpy(part.data(), stats, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double tr = 0.0, te = 0.0;
+    for (int blk = 0; blk < o.nsse; blk++) {
+      tr += part[2 * blk];
+      te += part[2 * blk + 1];
+    }
+    loss[0] = tr;
+    loss[1] = te;
+  }
+  if (bd) {  // the score pass on (g, h) and the sacrifice scores, as enqueue_glm_head queues them
+    double *part, *part2, *beta, *dbd;
+    HIPX(sc.alloc(&part, (size_t)o.nrb * p));
+    HIPX(sc.alloc(&part2, (size_t)o.nrb * p));
+    HIPX(sc.alloc(&beta, (size_t)p));
+    HIPX(sc.alloc(&dbd, (size_t)p));
+    std::vector<double> hb((size_t)p, 0.0);
+    for (int a = 0; a < m; a++) hb[cols[a]] = b[a];
+    HIPX(hipMemcpy(beta, hb.data(), (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+    int n_train = n;
+    if (mask) {
+      n_train = 0;
+      for (int i = 0; i < n; i++) n_train += mask[i] != 0.0;
+    }
+    HIPX(launch_xtv(o.X, ld, p, o.U, dg, dh, part, part2, ctrl, 1, nullptr));
+    HIPX(launch_score(part, part2, o.nrb, p, beta, nullptr, (double)n_train, lambda, 1, nullptr, dbd, ctrl, 1, nullptr));
+    HIPX(hipMemcpy(bd, dbd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return BESSX_OK;
+}
+
+int bessx_op_glm_irls_geometry(int T0, int n, int *out) {
+  if (T0 < 1 || T0 > T0_FAST || n < 1 || !out) return fail(BESSX_ERR_ARG, "op_glm_irls_geometry: bad arguments");
+  const int U = n >= 4096 ? 8 : (n >= 2048 ? 4 : (n >= 1024 ? 2 : 1));
+  const long ld = ((long)n + 128L * U - 1) / (128L * U) * (128L * U);
+  const int mt = (T0 + 2 + 15) / 16;
+  out[0] = (int)ld;
+  out[1] = mt;
+  out[2] = irls_gram_chunks(mt);
+  out[3] = irls_gram_slab_rows(mt, ld);
+  return BESSX_OK;
+}
+
+int bessx_op_glm_irls(int family, int route, int t, int wfloor, double lambda, int rows_per_slab, const double *x, int n,
+                      int p, const double *y, const double *weight, const double *mask, const int *cols, int T0,
+                      const double *bcur, double *gram, double *ll, double *wv, double *z, double *bnext,
+                      int *route_taken) {
+  if (int rc = need_device()) return rc;
+  if (int rc = glm_op_check("op_glm_irls", family, x, n, p, y, cols, T0, bcur)) return rc;
+  if (T0 < 1 || T0 > T0_FAST || !bcur || !gram || route < -1 || route > 1 || t < 0 || rows_per_slab < 0 ||
+      rows_per_slab % 64 != 0)
+    return fail(BESSX_ERR_ARG, "op_glm_irls: bad arguments");
+  const int mt = (T0 + 2 + 15) / 16, mp = mt * 16, ntiles = mt * (mt + 1) / 2;  // glm_geometry
+  // route -1: the rule of enqueue_glm_irls_step (the fused step up to 8 tile rows, the five-launch step beyond)
+  const bool fused = route == 1 || (route == -1 && irls_gram_applies(mt));
+  if (fused && !irls_gram_applies(mt)) return fail(BESSX_ERR_UNSUPPORTED, "op_glm_irls: the fused step takes at most 8 tile rows");
+  if (!fused && rows_per_slab != 0) return fail(BESSX_ERR_ARG, "op_glm_irls: rows_per_slab belongs to the fused step");
+  Owner sc;
+  GlmOpData o;
+  if (int rc = glm_op_upload(sc, x, n, p, y, weight, mask, &o)) return rc;
+  const long ld = o.ld;
+  HIPX(gram_lds_prepare());
+  double *aux, *db, *Gt, *gpart, *llpart, *Wv = nullptr, *dfb;
+  int *A_new, *A_cur, *gcols;
+  FitCtrl *ctrl;
+  {  // aux: column 0 zeros, column 1 ones on the data rows, column 2 the working response
+    std::vector<double> ha((size_t)ld * 3, 0.0);
+    std::fill(ha.begin() + ld, ha.begin() + ld + n, 1.0);
+    HIPX(sc.alloc(&aux, ha.size()));
+    HIPX(hipMemcpy(aux, ha.data(), ha.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIPX(sc.alloc(&A_new, (size_t)T0));
+  HIPX(sc.zeros(&A_cur, (size_t)T0));
+  HIPX(sc.alloc(&gcols, (size_t)mp + 16));
+  HIPX(hipMemcpy(A_new, cols, (size_t)T0 * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(sc.zeros(&db, (size_t)mp + 16));
+  HIPX(hipMemcpy(db, bcur, (size_t)(T0 + 1) * sizeof(double), hipMemcpyHostToDevice));
+  FitCtrl hc = {};  // slot 1 of a fit, IRLS step t of its sub-model fit still to do
+  hc.T0 = T0;
+  hc.irls_steps = t;
+  HIPX(sc.alloc(&ctrl, 1));
+  HIPX(hipMemcpy(ctrl, &hc, sizeof(FitCtrl), hipMemcpyHostToDevice));
+  HIPX(sc.alloc(&Gt, (size_t)ntiles * 256));
+  HIPX(sc.alloc(&dfb, CHOL_FB_DOUBLES));
+  const int slot = 1;
+  HIPX(launch_gram_cols(A_new, T0, mp, 1, 1, gcols, ctrl, slot, A_cur, family == 2 ? 1 : 0, nullptr));
+  std::vector<double> hll;
+  if (fused) {
+    const int rows = rows_per_slab ? rows_per_slab : irls_gram_slab_rows(mt, ld);
+    const int ns = (int)((ld + rows - 1) / rows);
+    HIPX(sc.alloc(&gpart, (size_t)ns * ntiles * 256));
+    HIPX(sc.alloc(&llpart, (size_t)ns));
+    HIPX(launch_irls_gram(family, o.X, aux, ld, n, gcols, o.y, o.w, o.mask, ns, mt, gpart, ntiles, ctrl, slot, t, T0, db,
+                          llpart, nullptr, wfloor, rows_per_slab));
+    HIPX(launch_gram_reduce(gpart, ns, ntiles, Gt, ctrl, slot, 1, nullptr));
+    hll.resize((size_t)ns);
+  } else {
+    std::vector<GramTask> tasks;
+    build_gram_tasks(mt, tasks);
+    GramTask *dt;
+    HIPX(sc.alloc(&dt, tasks.size()));
+    HIPX(hipMemcpy(dt, tasks.data(), tasks.size() * sizeof(GramTask), hipMemcpyHostToDevice));
+    bessx_session fake;
+    fake.ld = ld;
+    int rps, nslab;
+    gram_geometry(&fake, (int)tasks.size(), &rps, &nslab, ntiles);
+    HIPX(sc.alloc(&gpart, (size_t)nslab * ntiles * 256));
+    HIPX(sc.alloc(&llpart, (size_t)o.nsse));
+    HIPX(sc.zeros(&Wv, (size_t)ld));
+    HIPX(launch_glm_irls_prep(family, o.X, ld, n, o.y, o.w, o.mask, ctrl, slot, t, A_new, T0, db, Wv, aux + 2 * ld, llpart,
+                              nullptr, wfloor));
+    HIPX(launch_gram(o.X, aux, ld, gcols, Wv, rps, dt, (int)tasks.size(), nslab, gpart, ntiles, Gt, ctrl, slot, 1, nullptr));
+    hll.resize((size_t)o.nsse);
+  }
+  HIPX(hipMemcpy(hll.data(), llpart, hll.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (ll) *ll = irls_ll_sum(hll, fused ? 512 : 256);  // (the test rides in k_chol, 512 threads, or is k_glm_irls_check, 256)
+  if (route_taken) *route_taken = fused ? 1 : 0;
+  if (!fused) {
+    if (wv) HIPX(hipMemcpy(wv, Wv, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (z) HIPX(hipMemcpy(z, aux + 2 * ld, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  {  // rows and columns 0 .. T0 of the tiles are [1, X_A]; the working response is Gram column mp - 1
+    std::vector<double> ht((size_t)ntiles * 256);
+    HIPX(hipMemcpy(ht.data(), Gt, ht.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int M = T0 + 2;
+    auto pos = [&](int rc) { return rc <= T0 ? rc : (rc == mp - 1 ? T0 + 1 : -1); };
+    for (int I = 0; I < mt; I++)
+      for (int J = 0; J <= I; J++) {
+        const int tl = I * (I + 1) / 2 + J;
+        for (int lane = 0; lane < 64; lane++)
+          for (int r = 0; r < 4; r++) {
+            const int row = pos(I * 16 + (lane >> 4) + 4 * r), col = pos(J * 16 + (lane & 15));
+            if (row < 0 || col < 0) continue;
+            const double v = ht[(size_t)tl * 256 + lane * 4 + r];
+            gram[(size_t)col * M + row] = v;
+            if (I != J) gram[(size_t)row * M + col] = v;
+          }
+      }
+  }
+  if (bnext) {  // the solve of the step as the session queues it, without the convergence test at its head
+    CholFuse fbz = {};
+    fbz.fb_work = dfb;
+    HIPX(launch_chol(Gt, T0 + 1, mt, 2.0 * lambda, 1, nullptr, nullptr, db, &ctrl->info, ctrl, slot, 1, nullptr, &fbz));
+    // (a chain whose k_chol stood back carries the pivoted solve behind it: glm_fallback)
+    HIPX(launch_sym_fallback(Gt, T0 + 1, mt, 2.0 * lambda, 1, nullptr, nullptr, db, &ctrl->info, ctrl, slot, nullptr, &fbz));
+    HIPX(hipMemcpy(bnext, db, (size_t)(T0 + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    HIPX(hipMemcpy(&hc, ctrl, sizeof(FitCtrl), hipMemcpyDeviceToHost));
+    if (hc.info) return fail(BESSX_ERR_NUMERIC, "op_glm_irls: the solve of the step gave up (singular system?)");
+  }
+  return BESSX_OK;
+}
+
 int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps) {
   if (int rc = need_device()) return rc;
   if (bytes < (1 << 20) || repeats < 1 || !gbps) return fail(BESSX_ERR_ARG, "op_stream_copy: bad arguments");

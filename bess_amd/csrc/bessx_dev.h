@@ -214,10 +214,11 @@ hipError_t gram_lds_prepare();
 // the IRLS step of the GLM fits in one pass over the active columns (k_irls_gram): up to 8 tile rows
 bool irls_gram_applies(int mt);
 int irls_gram_slab_rows(int mt, long ld);
+int irls_gram_chunks(int mt);  // 64-row chunks per group of the instance that serves mt tile rows (0: none does)
 hipError_t launch_irls_gram(int fam, const double *X, const double *aux, long ld, int n, const int *cols,
                             const double *y, const double *w, const double *mask, int nslab, int mt, double *part,
                             int ntiles, const FitCtrl *ctrl, int slot, int t, int T0, const double *bcur,
-                            double *llpart, hipStream_t st, int wfloor = 1);
+                            double *llpart, hipStream_t st, int wfloor = 1, int rows_override = 0);
 hipError_t launch_gram_reduce(const double *part, int nslab, int ntiles, double *Gt, const FitCtrl *ctrl, int slot,
                               int gate_mode, hipStream_t st);
 hipError_t launch_gram(const double *X, const double *aux, long ld, const int *cols, const double *w,

@@ -693,6 +693,7 @@ int run_path(bessx_session *s, bool gs, const int *seq, int ns, const double *la
 int need_device();
 int upload_padded(Owner &sc, const double *x, int n, int p, int ld_in, int U, double **dX, long *ld_out);
 int upload_vec_padded(Owner &sc, const double *v, int n, long ld, double **dv);
+void poisson_logfact(const double *y, int n, double *lf);  // Poisson: lf[i] = sum_{j <= y_i} log j
 
 }  // namespace bessx
 

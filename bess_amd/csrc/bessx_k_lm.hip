@@ -1330,9 +1330,11 @@ hipError_t gram_lds_prepare() {
 }
 
 // fused IRLS step (k_irls_gram): slab partials of the weighted Gram + the slabs' log-likelihood terms.  The caller
-// follows it with k_gram_reduce and k_chol (whose head is the convergence test).  Slabs are NCH 64-row chunks: 8 chunks
-// up to 4 tile rows, 4 beyond (the registers that hold the slab between the two uses bound NCH x tile rows).
-// rows per slab: about one slab per compute unit (whole 64-row chunks), at least one group of chunks
+// follows it with k_gram_reduce and k_chol (whose head is the convergence test).  A slab is walked in groups of
+// NCH 64-row chunks: 8 chunks up to 3 tile rows, then 6, 5, 4, 3 and 2 at 4 .. 8 tile rows (the registers that hold a group
+// between its two uses bound NCH x tile rows).
+constexpr int IG_NCH[9] = {0, 8, 8, 8, 6, 5, 4, 3, 2};
+int irls_gram_chunks(int mt) { return mt >= 1 && mt <= 8 ? IG_NCH[mt] : 0; }
 // rows per slab: about one slab per compute unit, whole 64-row chunks
 int irls_gram_slab_rows(int mt, long ld) {
   (void)mt;
@@ -1342,9 +1344,11 @@ bool irls_gram_applies(int mt) { return g_gram_variant == 1 && mt >= 1 && mt <= 
 hipError_t launch_irls_gram(int fam, const double *X, const double *aux, long ld, int n, const int *cols,
                             const double *y, const double *w, const double *mask, int nslab, int mt, double *part,
                             int ntiles, const FitCtrl *ctrl, int slot, int t, int T0, const double *bcur,
-                            double *llpart, hipStream_t st, int wfloor) {
+                            double *llpart, hipStream_t st, int wfloor, int rows_override) {
   if (!irls_gram_applies(mt) || T0 + 2 > mt * 16) return hipErrorInvalidValue;  // intercept, T0 columns, ..., z last
-  const int rows = irls_gram_slab_rows(mt, ld);
+  // rows_override: slab height of the single-step test entry (bessx_op_glm_irls), whole 64-row chunks; the solver leaves it 0
+  if (rows_override < 0 || rows_override % 64 != 0) return hipErrorInvalidValue;
+  const int rows = rows_override ? rows_override : irls_gram_slab_rows(mt, ld);
   if ((long)nslab * rows < ld) return hipErrorInvalidValue;
 #define IG_GO(NP_, NCH_, TPW_, FAM_)                                                                               \
   do {                                                                                                             \
@@ -1360,13 +1364,13 @@ hipError_t launch_irls_gram(int fam, const double *X, const double *aux, long ld
     IG_GO(NP_, NCH_, TPW_, 3)
   switch (mt) {
     case 1:
-    case 2: IG_FAM(2, 8, 1); break;
-    case 3: IG_FAM(3, 8, 1); break;
-    case 4: IG_FAM(4, 6, 2); break;
-    case 5: IG_FAM(5, 5, 2); break;
-    case 6: IG_FAM(6, 4, 3); break;
-    case 7: IG_FAM(7, 3, 4); break;
-    default: IG_FAM(8, 2, 5); break;
+    case 2: IG_FAM(2, IG_NCH[2], 1); break;
+    case 3: IG_FAM(3, IG_NCH[3], 1); break;
+    case 4: IG_FAM(4, IG_NCH[4], 2); break;
+    case 5: IG_FAM(5, IG_NCH[5], 2); break;
+    case 6: IG_FAM(6, IG_NCH[6], 3); break;
+    case 7: IG_FAM(7, IG_NCH[7], 4); break;
+    default: IG_FAM(8, IG_NCH[8], 5); break;
   }
 #undef IG_FAM
 #undef IG_GO

@@ -507,6 +507,16 @@ int need_device() {
   return 0;
 }
 
+// sum_{j=1..y} log j per row, the loop of loglik_poisson (src/poisson.cpp:27-41)
+void poisson_logfact(const double *y, int n, double *lf) {
+  for (int i = 0; i < n; i++) {
+    double t = 0.0;
+    if (y[i] != 1.0)
+      for (double j = 1.0; j <= y[i]; j = j + 1.0) t = t + std::log(j);
+    lf[i] = t;
+  }
+}
+
 // copy a column-major (n x p, leading dimension ld_in) host matrix into a zero-padded device matrix
 int upload_padded(Owner &sc, const double *x, int n, int p, int ld_in, int U, double **dX, long *ld_out) {
   long rb = 128L * U;
@@ -1110,15 +1120,8 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
   HIPT(s->own.alloc(&s->bprev, (size_t)capA + 16));
   HIPT(s->own.alloc(&s->logfact, (size_t)ld));
   {
-    // sum_{j=1..y} log j per row, the loop of loglik_poisson (src/poisson.cpp:27-41); only Poisson reads it
-    std::vector<double> lf((size_t)ld, 0.0);
-    if (s->model_type == 3)
-      for (int i = 0; i < n; i++) {
-        double t = 0.0;
-        if (pb->y[i] != 1.0)
-          for (double j = 1.0; j <= pb->y[i]; j = j + 1.0) t = t + std::log(j);
-        lf[i] = t;
-      }
+    std::vector<double> lf((size_t)ld, 0.0);  // only Poisson reads it
+    if (s->model_type == 3) poisson_logfact(pb->y, n, lf.data());
     HIPT(hipMemcpy(s->logfact, lf.data(), (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
   }
   s->cache.assign(1, bessx_session::RsCache());

@@ -762,6 +762,37 @@ int bessx_op_cox_score(const double *x, int n, int p, const double *status, cons
 int bessx_op_cox_score_multi(const double *x, int n, int p, const double *status, const double *weight,
                              const double *mask, const int *cols, int m, const double *b, int nc, double lambda,
                              double *bd);
+/* The front half of get_A of the logistic (family 2) and Poisson (family 3) solver alone (k_glm_eta_gh through
+ * launch_glm_eta_gh, as a session calls it) for the model (cols[m], b[m], coef0); m may be 0.  x column-major n x p, padded
+ * to the session's row stride; y n; weight n or NULL (ones); mask n (1 = training row, 0 = test row of a CV fold) or NULL.
+ * g, h: n doubles each (may be NULL); loss[0] = the train_loss summands over all rows, loss[1] = the held-out summands over
+ * the rows with mask 0, the per-block pairs added in block order as the session does; the Poisson sums of log j are formed
+ * by the session's own code.  bd (p doubles, or NULL): the score pass on (g, h) and the sacrifice scores with ridge lambda,
+ * queued as the head of a PDAS iteration queues them (src/Algorithm.h:1223-1257, :1338-1361). */
+int bessx_op_glm_gh(int family, const double *x, int n, int p, const double *y, const double *weight, const double *mask,
+                    const int *cols, int m, const double *b, double coef0, double lambda, double *g, double *h,
+                    double *loss, double *bd);
+/* One IRLS step of the restricted fit (src/Algorithm.h:1148-1204, :1273-1322) from the iterate bcur[T0 + 1] (intercept
+ * first) on the design [1, X_cols], 1 <= T0 <= 254, through the solver's own launchers.  route 1: the fused step
+ * (k_irls_gram + k_gram_reduce, T0 + 2 <= 128); route 0: the five-launch step (k_glm_irls_prep + the Gram kernel); route -1:
+ * whichever a session takes for this T0; *route_taken (may be NULL) says which ran.  t: the step's number (0: no floor, no
+ * Poisson log-likelihood), wfloor: the 0.001 floor of the logistic weights for t >= 1.  rows_per_slab: 0 = the solver's
+ * slab height; otherwise a multiple of 64 that replaces it (fused step only; a test override, no session sets it).
+ * gram: (T0 + 2) x (T0 + 2), column-major, full symmetric = [1, X_A, z]^T diag(W w mask) [1, X_A, z]; *ll: the step's
+ * log-likelihood, its slab or block terms added in the order of the convergence test; wv, z (n doubles each, may be NULL):
+ * written by route 0 only; bnext[T0 + 1] (may be NULL): the solve with ridge 2 lambda off the intercept, without the
+ * convergence test.  "A session" is a session in its default state: route -1 applies the rule by the number of tile rows
+ * alone (a session also leaves the fused step when a test hook turns it off or its work space is too small for the
+ * slabs), and the pivoted fallback solve is always queued behind the solve (a session queues it once a solve of its chain
+ * has stood back). */
+int bessx_op_glm_irls(int family, int route, int t, int wfloor, double lambda, int rows_per_slab, const double *x, int n,
+                      int p, const double *y, const double *weight, const double *mask, const int *cols, int T0,
+                      const double *bcur, double *gram, double *ll, double *wv, double *z, double *bnext,
+                      int *route_taken);
+/* The geometry bessx_op_glm_irls and a session use for sparsity level T0 (1 .. 254) on n rows; needs no device.  out[0] =
+ * the padded row count, out[1] = tile rows of the step's Gram, out[2] = 64-row chunks per group of the fused kernel's
+ * instance for that many tile rows (0 beyond 8 tile rows: the five-launch step), out[3] = the solver's rows per slab. */
+int bessx_op_glm_irls_geometry(int T0, int n, int *out);
 /* Device-to-device streaming copy rate in GB/s (read+write bytes / time): the measured HBM ceiling
  * quoted next to the spec peak in bench.py. */
 int bessx_op_stream_copy_gbps(long long bytes, int repeats, double *gbps);

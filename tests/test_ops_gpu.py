@@ -1,8 +1,10 @@
 """Parity of the HIP kernels that have a single-kernel entry in the C ABI (bessx_op_*: X^T v and its multi-chain form,
 top-k, Gram, Cholesky solve, normalisation), each called alone, against NumPy / the plain-C oracle on the same seeded
 inputs.  The Cox solver's state pass, scans, loss and score passes are called alone in tests/test_cox_ops_gpu.py; the
-Newton-step kernels of the GLM / Cox fits, the covariance-form kernels and the big-system solvers have no such entry and
-are reached through sessions only."""
+logistic and Poisson solver's gradient / curvature pass (bessx_op_glm_gh) and one IRLS step by either route
+(bessx_op_glm_irls) in tests/test_glm_ops_gpu.py.  The Newton-step kernels of the Cox fit, the group kernels (k_group_*),
+the screening kernels, the covariance-form kernels and the big-system solvers have no such entry and are reached through
+sessions only."""
 import numpy as np
 import pytest
 

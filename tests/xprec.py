@@ -198,10 +198,15 @@ def assert_loss_close(got, ref, what):
     return rel
 
 
-def assert_gram_close(got, ref, col_norms, row_norms, n, what):
+def assert_gram_close(got, ref, col_norms, row_norms, n, what, extra=None, scale=1.0):
     """Per entry |G_ja - G*_ja| <= 32 sqrt(n) u |x_j| |x_a| (got, ref: p x c; col_norms: |x_a| of the c exported columns,
-    row_norms: |x_j| of all p).  Returns the largest fraction of the bound used."""
+    row_norms: |x_j| of all p).  extra (p x c, optional): what the caller's inputs carry into each entry, added to the
+    bound (tests/glmref.py: the working weights and response are computed quantities); scale: the whole bound times this
+    (two results against each other: 2).  Returns the largest fraction of the bound used."""
     bound = GRAM_FACTOR * np.sqrt(float(n)) * U * np.outer(np.asarray(row_norms, float), np.asarray(col_norms, float))
+    if extra is not None:
+        bound = bound + np.asarray(extra, dtype=np.float64)
+    bound = scale * bound
     frac = np.abs((ld(got) - ld(ref)).astype(np.float64)) / bound
     j, a = np.unravel_index(int(np.argmax(frac)), frac.shape)
     assert frac[j, a] <= 1.0, "%s: Gram entry (%d, %d) is off by %.3e = %.2f of 32 sqrt(n) u |x_j||x_a|" % (
