@@ -41,6 +41,7 @@ SYMBOLS = [
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
+    "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -106,6 +107,14 @@ class InfoInput(ctypes.Structure):
                 ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
                 ("weight_stride", _ll), ("info", _vp), ("info_ld", _ll), ("score", _vp), ("out_on_device", _i),
                 ("stream", _vp)]
+
+
+class CoxInfoInput(ctypes.Structure):
+    """bessx_cox_info_input: one Cox model, X in GPU memory, time / status / weight in host memory, where info and score
+    go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
+                ("info", _vp), ("info_ld", _ll), ("score", _vp), ("out_on_device", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -235,6 +244,9 @@ def lib():
         L.bessx_info_device.argtypes = [ctypes.POINTER(InfoInput), _D, _D]
         L.bessx_info_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
         L.bessx_op_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D]
+        L.bessx_cox_info_device.argtypes = [ctypes.POINTER(CoxInfoInput), _D, _D, _D]
+        L.bessx_cox_info_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
+        L.bessx_op_cox_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1359,32 +1371,17 @@ def op_info_bench(x, cols, repeats=20):
     return ms.value, tf.value
 
 
-def wald_table(info, score, coef, link, loss, sum_w):
-    """The coefficient table from an information matrix, on the host in fp64 NumPy.  info (M, M), score (M,), coef (M,)
-    with the intercept first, as information_device orders them; link "identity", "logistic" or "poisson"; loss and
-    sum_w as information_device returns them.  With D = diag(info)^(-1/2) and S = D info D (unit diagonal), S is
-    Cholesky-factored and cov = D S^-1 D; for the identity link cov is multiplied by dispersion = loss / (sum_w - M)
-    (the residual variance; NaN when sum_w - M <= 0), for the other links dispersion = 1.  Returns coef, se =
-    sqrt(diag(cov)), z = coef / se, p_value = erfc(|z| / sqrt(2)) -- two-sided NORMAL, for the identity link too (the
-    normal approximation, not Student's t) -- cov, score, dispersion, dof = sum_w - M, cond = the 2-norm condition number
-    of S, and positive_definite.  When a diagonal entry of info is <= 0 or not finite, or S is not positive definite
-    (duplicated columns, a separated logistic sample), se, z, p_value and cov are NaN and positive_definite is False:
-    data decide that, so nothing is raised.  A score that is not near 0 says that coef is not the unpenalised optimum
-    of its support (lambda > 0), and cov is then not its covariance."""
+def _wald(info, score, coef, dispersion, dof):
+    """The table of wald_table / cox_wald_table from an M x M information matrix, M = coef.size: cov = dispersion *
+    D S^-1 D with D = diag(info)^(-1/2) and S = D info D Cholesky-factored; NaNs and positive_definite = False when a
+    diagonal entry is <= 0 or not finite or S is not positive definite."""
     import math
-    if link not in LINKS:
-        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
     info = np.array(info, dtype=np.float64)
     coef = np.asarray(coef, dtype=np.float64).reshape(-1)
     score = np.asarray(score, dtype=np.float64).reshape(-1)
     M = coef.size
     if info.shape != (M, M) or score.shape != (M,):
         raise ValueError("info must be (%d, %d) and score (%d,), got %s and %s" % (M, M, M, info.shape, score.shape))
-    dof = float(sum_w) - M
-    if link == "identity":
-        dispersion = float(loss) / dof if dof > 0 else float("nan")
-    else:
-        dispersion = 1.0
     nan_v, nan_m = np.full(M, np.nan), np.full((M, M), np.nan)
     out = {"coef": coef, "se": nan_v, "z": nan_v.copy(), "p_value": nan_v.copy(), "cov": nan_m, "score": score,
            "dispersion": dispersion, "dof": dof, "cond": float("nan"), "positive_definite": False}
@@ -1412,6 +1409,41 @@ def wald_table(info, score, coef, link, loss, sum_w):
     pv = np.array([math.erfc(abs(v) / math.sqrt(2.0)) if v == v else float("nan") for v in z])
     out.update(se=se, z=z, p_value=pv, cov=cov, cond=float(ev[-1] / ev[0]), positive_definite=True)
     return out
+
+
+def wald_table(info, score, coef, link, loss, sum_w):
+    """The coefficient table from an information matrix, on the host in fp64 NumPy.  info (M, M), score (M,), coef (M,)
+    with the intercept first, as information_device orders them; link "identity", "logistic" or "poisson"; loss and
+    sum_w as information_device returns them.  With D = diag(info)^(-1/2) and S = D info D (unit diagonal), S is
+    Cholesky-factored and cov = D S^-1 D; for the identity link cov is multiplied by dispersion = loss / (sum_w - M)
+    (the residual variance; NaN when sum_w - M <= 0), for the other links dispersion = 1.  Returns coef, se =
+    sqrt(diag(cov)), z = coef / se, p_value = erfc(|z| / sqrt(2)) -- two-sided NORMAL, for the identity link too (the
+    normal approximation, not Student's t) -- cov, score, dispersion, dof = sum_w - M, cond = the 2-norm condition number
+    of S, and positive_definite.  When a diagonal entry of info is <= 0 or not finite, or S is not positive definite
+    (duplicated columns, a separated logistic sample), se, z, p_value and cov are NaN and positive_definite is False:
+    data decide that, so nothing is raised.  A score that is not near 0 says that coef is not the unpenalised optimum
+    of its support (lambda > 0), and cov is then not its covariance."""
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    M = np.asarray(coef, dtype=np.float64).size
+    dof = float(sum_w) - M
+    if link == "identity":
+        dispersion = float(loss) / dof if dof > 0 else float("nan")
+    else:
+        dispersion = 1.0
+    return _wald(info, score, coef, dispersion, dof)
+
+
+def cox_wald_table(info, score, coef, n_events):
+    """wald_table for a Cox model: info (m, m), score (m,) and coef (m,) as cox_information_device orders them (no
+    intercept), n_events = sum of w * status.  The dict of wald_table with dispersion = 1 and dof = n_events - m; an
+    empty model (m = 0) gives empty arrays and positive_definite = True."""
+    m = np.asarray(coef, dtype=np.float64).size
+    if m == 0:
+        z = np.zeros(0)
+        return {"coef": z, "se": z.copy(), "z": z.copy(), "p_value": z.copy(), "cov": np.zeros((0, 0)), "score": z.copy(),
+                "dispersion": 1.0, "dof": float(n_events), "cond": float("nan"), "positive_definite": True}
+    return _wald(info, score, coef, 1.0, float(n_events) - m)
 
 
 TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties
@@ -1514,6 +1546,77 @@ def _cox_model(dx, cols, B):
         raise ValueError("B must hold one model (len(cols) values), got shape %s" % (B.shape,))
     cols, B, _ = _predict_model(dx, cols, B.reshape(-1), np.zeros(1))
     return cols, np.ascontiguousarray(B.reshape(-1))
+
+
+def cox_info_workspace(n, m, n_event_rows):
+    """(doubles of scratch memory, (rows per slab, slabs) of the sweep over x, (rows per slab, slabs) of the sweep over the
+    risk-set means) of a cox_information_device call on n rows with a support of m columns and n_event_rows rows of
+    status 1 (bessx_cox_info_workspace; no device is needed).  A sweep that is not launched reports (0, 0)."""
+    nd, rps, sl = _ll(0), (_ll * 2)(), (_i * 2)()
+    _check(lib().bessx_cox_info_workspace(int(n), int(m), int(n_event_rows), ctypes.byref(nd), rps, sl))
+    return nd.value, (int(rps[0]), int(sl[0])), (int(rps[1]), int(sl[1]))
+
+
+def cox_information_device(x, cols, beta, time, status, weight=None, ties="order", stream=0):
+    """Observed information and score of ONE Cox model on a device matrix x (n x p: float64 or float32, any non-negative
+    strides), read where it lies (bessx_cox_info_device).  With the definitions of evaluate_cox_device -- eta =
+    x[:, cols] @ beta, the rows in the stable ascending order of time, e = exp(clip(eta, -30, 30)), wd = w * status --
+    r(k) = k (ties="order") or the first position with the time of k (ties="breslow"), S0_k = sum of e over the positions
+    >= r(k), S1_k = sum of e * x[., cols] over them and u_k = S1_k / S0_k:
+        loglik = sum_k wd_k (clip(eta_k) - log S0_k)         evaluate_cox_device's, bit for bit
+        score  = sum_k wd_k (x_k - u_k)                                                             (m,)
+        info   = sum_k wd_k sum_{l >= r(k)} (e_l / S0_k) (x_l - u_k)(x_l - u_k)^T      (m, m), both triangles exact mirrors
+    info is the negative Hessian of loglik in beta wherever no clip is active; where one is, it is this formula and not a
+    derivative.  It is formed as G1 - G2 = sum_l v_l x_l x_l^T - sum_events wd_k u_k u_k^T with v_l = e_l H_l, H the
+    cumulative hazard, and score = sum_l g_l x_l with the martingale residuals g = wd - v: a DIFFERENCE, so columns far
+    from centred lose digits in proportion to |G1| / |info| (survival::coxph uses the same form; centre such columns
+    first).  cols: ascending distinct column numbers (may be empty: nothing of x is read, info is (0, 0) and loglik the
+    null model's); beta: len(cols) finite values; time, status (0 or 1), weight (None = ones): n values each, host or
+    device arrays (device arrays are copied to the host).  Returns {"info", "score", "loglik", "n_events" = sum of wd,
+    "residual_sum" = sum of g, 0 up to rounding}.  x's support is read three times, no gathered copy of x[:, cols] in row
+    order is made, every sum has a fixed order (the same call gives the same bits), and a NaN inside the support view
+    propagates.  Scratch: about (m + 5) n + J m doubles for J event rows plus the sweeps' partials (cox_info_workspace:
+    3.4 GB at n = 200 000, m = 1023, J = n).  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if ties not in TIES:
+        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: cox_information_device takes one model per call")
+    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
+    if not np.isfinite(B).all():
+        raise ValueError("beta must be finite")
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, a in given:  # (every shape is checked before anything is copied)
+        _survival_vector(a, n, what, check_only=True)
+    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    m = cols.size
+    info, score = np.empty((m, m)), np.empty(m)
+    a = CoxInfoInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    a.ties, a.stream = TIES[ties], int(stream) if stream else None
+    a.info, a.info_ld, a.score, a.out_on_device = info.ctypes.data, m, score.ctypes.data, 0
+    ll, ne, rs = _d(0), _d(0), _d(0)
+    _check(lib().bessx_cox_info_device(ctypes.byref(a), ctypes.byref(ll), ctypes.byref(ne), ctypes.byref(rs)))
+    return {"info": info, "score": score, "loglik": ll.value, "n_events": ne.value, "residual_sum": rs.value}
+
+
+def op_cox_info_bench(x, cols, ties="order", repeats=20):
+    """((ms of the gather of e * x into position order, ms of the column-wise suffix scan that emits the risk-set means,
+    ms of every launch of a cox_information_device call), bytes the first two must move) on the device matrix x for the
+    support cols (at least one column), device events."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms, nbytes = np.zeros(3), _d(0)
+    _check(lib().bessx_op_cox_info_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, TIES[ties], repeats, _dp(ms), ctypes.byref(nbytes)))
+    return tuple(float(v) for v in ms), nbytes.value
 
 
 def cox_baseline_device(x, cols, B, time, status, weight=None, stream=0):

@@ -2149,3 +2149,302 @@ int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long lon
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// observed information and score of one Cox model on a caller's device matrix (include/bessx.h section 2h)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// what the kernels of bessx_k_coxinfo.hip need about the order on top of CoxOrder
+struct CoxInfoOrder {
+  std::vector<int> rowof, lastk, jptr, iota;  // row at a position; last position of a tie group; events per r(k); 0 .. m-1
+  std::vector<double> wdJ;                    // wd of the J event rows, in position order
+  int J = 0;
+  double n_events = 0.0;
+};
+
+// o->first becomes r(k): it stays first(k) for ties = 1 and becomes the identity for ties = 0
+void cox_info_order(CoxOrder *o, int n, int m, int ties, CoxInfoOrder *x) {
+  const size_t N = (size_t)n;
+  x->rowof.resize(N);
+  for (int i = 0; i < n; i++) x->rowof[(size_t)o->pos[(size_t)i]] = i;
+  if (ties) {
+    x->lastk.resize(N);
+    for (int k = n - 1, end = n - 1; k >= 0; k--) {
+      if (k < n - 1 && o->first[(size_t)k + 1] != o->first[(size_t)k]) end = k;
+      x->lastk[(size_t)k] = end;
+    }
+  } else {
+    std::iota(o->first.begin(), o->first.end(), 0);
+  }
+  x->jptr.assign(N + 1, 0);
+  x->wdJ.clear();
+  x->n_events = 0.0;
+  for (int k = 0; k < n; k++) {
+    x->n_events += o->wd[(size_t)k];
+    if (o->kg[(size_t)k] != INT_MAX) {
+      x->wdJ.push_back(o->wd[(size_t)k]);
+      x->jptr[(size_t)o->first[(size_t)k] + 1]++;
+    }
+  }
+  for (int k = 0; k < n; k++) x->jptr[(size_t)k + 1] += x->jptr[(size_t)k];
+  x->J = (int)x->wdJ.size();
+  x->iota.resize((size_t)m);
+  std::iota(x->iota.begin(), x->iota.end(), 0);
+}
+
+// doubles of device scratch of one call (the arrays of CoxInfoDev that hold doubles)
+long long cox_info_doubles(long long n, int m, long long J) {
+  const long long nb = (n + 1023) / 1024, M = (long long)m + 1;
+  long long d = 2 * n + cox_eval_workspace(n, 1) + 2 + (long long)m + 1;  // eta / H, e -> S0, the scans' totals, res, B
+  if (m == 0) return d;
+  d += 3 * n + (long long)m * n + nb * m + cox_surv_workspace(n);  // e, v, g, W and the totals of its scan and of H's
+  d += info_gram_workspace(n, m) + 2 * (M * M + M);                 // the sweeps' partials and results
+  if (J > 0) d += cox_info_ldu(J) * m + J + info_gram_workspace(J, m);
+  return d;
+}
+
+struct CoxInfoDev {
+  CoxDev d;  // (d.first holds r(k); d.eta holds H once the likelihood has been formed)
+  int *rowof = nullptr, *lastk = nullptr, *jptr = nullptr, *iota = nullptr;
+  double *e = nullptr, *W = nullptr, *scr = nullptr, *hs = nullptr, *v = nullptr, *g = nullptr, *wdJ = nullptr;
+  double *U = nullptr, *part1 = nullptr, *part2 = nullptr, *G = nullptr, *res = nullptr;
+  long long ldU = 0;
+  int J = 0;
+};
+
+// buffers of `sc`, uploads queued on st (the vectors of o and x must outlive them)
+int cox_info_stage(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const int *cols, int m, const double *beta, int n,
+                   int ties, hipStream_t st, CoxInfoDev *c) {
+  const size_t N = (size_t)n, M = (size_t)m + 1;
+  if (int rc = cox_eval_stage(sc, o, cols, m, beta, 1, n, 1, 0, st, &c->d)) return rc;
+  HIPX(sc.alloc(&c->res, 2));
+  c->J = x.J;
+  if (m == 0) return 0;
+  HIPX(sc.alloc(&c->rowof, N));
+  HIPX(hipMemcpyAsync(c->rowof, x.rowof.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+  if (ties) {
+    HIPX(sc.alloc(&c->lastk, N));
+    HIPX(hipMemcpyAsync(c->lastk, x.lastk.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  HIPX(sc.alloc(&c->e, N));
+  HIPX(sc.alloc(&c->v, N));
+  HIPX(sc.alloc(&c->g, N));
+  HIPX(sc.alloc(&c->W, (size_t)m * N));
+  HIPX(sc.alloc(&c->scr, (size_t)((n + 1023) / 1024) * (size_t)m));
+  HIPX(sc.alloc(&c->hs, (size_t)cox_surv_workspace(n)));
+  HIPX(sc.alloc(&c->part1, (size_t)info_gram_workspace(n, m)));
+  HIPX(sc.alloc(&c->G, 2 * (M * M + M)));
+  if (x.J > 0) {
+    const size_t J = (size_t)x.J;
+    c->ldU = cox_info_ldu(x.J);
+    HIPX(sc.alloc(&c->jptr, N + 1));
+    HIPX(hipMemcpyAsync(c->jptr, x.jptr.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&c->iota, (size_t)m));
+    HIPX(hipMemcpyAsync(c->iota, x.iota.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&c->wdJ, J));
+    HIPX(hipMemcpyAsync(c->wdJ, x.wdJ.data(), J * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&c->U, (size_t)c->ldU * (size_t)m));
+    HIPX(sc.alloc(&c->part2, (size_t)info_gram_workspace(x.J, m)));
+  }
+  return 0;
+}
+
+// the launches of one call in order; stage >= 0 (the bench): only the gather (0) or the risk-set means (1), which need
+// the buffers as a full sequence has left them -- e and S0 are not overwritten by anything after the likelihood
+int cox_info_launch(const void *x, int f32, long long rs, long long cs, int n, int m, int ties, const CoxInfoDev &c,
+                    double *info, long long ld, double *score, hipStream_t st, int stage = -1) {
+  const CoxDev &d = c.d;
+  const size_t M = (size_t)m + 1;
+  double *G1 = c.G, *U1 = c.G + M * M, *G2 = U1 + M, *U2 = G2 + M * M;
+  if (stage < 0) {
+    HIPX(launch_cox_eval_eta(x, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
+    if (m > 0) HIPX(hipMemcpyAsync(c.e, d.ex, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, c.res, st));
+    if (m == 0) return 0;
+  }
+  if (stage < 0 || stage == 0) HIPX(launch_cox_info_gather(x, f32, rs, cs, n, d.cols, m, c.rowof, c.e, c.W, st));
+  if (stage < 0) {
+    // (eta has served: its n doubles hold h, then H)
+    HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, c.hs, nullptr, st));
+    HIPX(launch_cox_info_vg(c.e, d.eta, ties ? c.lastk : nullptr, d.wd, d.pos, n, c.v, c.g, st));
+    HIPX(launch_info_gram(x, f32, rs, cs, n, d.cols, m, c.v, c.g, c.part1, G1, (long long)M, U1, st));
+  }
+  if (c.J > 0 && (stage < 0 || stage == 1))
+    HIPX(launch_cox_info_means(c.W, d.ex, c.jptr, n, m, c.J, c.scr, c.U, c.ldU, st));
+  if (stage < 0) {
+    if (c.J > 0)
+      HIPX(launch_info_gram(c.U, 0, 1, c.ldU, c.J, c.iota, m, c.wdJ, c.wdJ, c.part2, G2, (long long)M, U2, st));
+    HIPX(launch_cox_info_finish(G1, c.J > 0 ? G2 : nullptr, U1, m, info, ld, score, c.res, st));
+  }
+  return 0;
+}
+
+int cox_info_check_args(const char *who, const bessx_cox_info_input *in, const double *loglik, const double *n_events,
+                        const double *residual_sum) {
+  const std::string w(who);
+  if (!in || !loglik || !n_events || !residual_sum) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
+  for (int k = 0; k < in->m; k++)
+    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
+  if (in->ties != 0 && in->ties != 1) return fail(BESSX_ERR_ARG, w + ": ties must be 0 (order) or 1 (breslow)");
+  for (int i = 0; i < in->n; i++) {
+    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
+    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
+  }
+  if (in->m > 0 && (!in->info || !in->score)) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->info_ld < (long long)in->m) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m");
+  if (in->m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  return 0;
+}
+
+// sc, o, x and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_info_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vector<double> &h,
+                 const bessx_cox_info_input *in, double *loglik, double *residual_sum, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32;
+  const size_t mm = (size_t)m * (size_t)m;
+  CoxInfoDev c;
+  if (int rc = cox_info_stage(sc, o, x, in->cols, m, in->beta, n, in->ties, st, &c)) return rc;
+  HIPX(hipMemsetAsync(c.res, 0, 2 * sizeof(double), st));
+  double *info_d = in->info, *score_d = in->score, *stage = nullptr;
+  long long ld = in->info_ld;
+  const bool staged = m > 0 && !in->out_on_device;
+  if (staged) {
+    HIPX(sc.alloc(&stage, mm + (size_t)m));
+    info_d = stage;
+    score_d = stage + mm;
+    ld = m;
+  }
+  if (int rc = cox_info_launch(in->x, f32, in->x_row_stride, in->x_col_stride, n, m, in->ties, c, info_d, ld, score_d, st))
+    return rc;
+  h.resize(2 + (staged ? mm + (size_t)m : 0));
+  HIPX(hipMemcpyAsync(h.data(), c.res, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (staged) HIPX(hipMemcpyAsync(h.data() + 2, stage, (mm + (size_t)m) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  *loglik = h[0];
+  *residual_sum = h[1];
+  if (staged) {
+    for (size_t j = 0; j < (size_t)m; j++)
+      std::copy(h.begin() + 2 + j * m, h.begin() + 2 + (j + 1) * m, in->info + j * in->info_ld);
+    std::copy(h.begin() + 2 + mm, h.end(), in->score);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_info_workspace(int n, int m, int n_event_rows, long long *doubles, long long *rows_per_slab, int *slabs) {
+  if (!doubles || !rows_per_slab || !slabs) return fail(BESSX_ERR_ARG, "cox_info_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_info_workspace: empty matrix");
+  if (n_event_rows < 0 || n_event_rows > n)
+    return fail(BESSX_ERR_ARG, "cox_info_workspace: n_event_rows must lie in [0, n]");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "cox_info_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  *doubles = cox_info_doubles(n, m, n_event_rows);
+  rows_per_slab[0] = rows_per_slab[1] = 0;
+  slabs[0] = slabs[1] = 0;
+  if (m > 0) {
+    info_split(n, m, &rows_per_slab[0], &slabs[0]);
+    if (n_event_rows > 0) info_split(n_event_rows, m, &rows_per_slab[1], &slabs[1]);
+  }
+  return BESSX_OK;
+}
+
+int bessx_cox_info_device(const bessx_cox_info_input *in, double *loglik, double *n_events, double *residual_sum) {
+  if (int rc = cox_info_check_args("cox_info_device", in, loglik, n_events, residual_sum)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("cox_info_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->out_on_device && in->m > 0) {
+    if (int rc = check_device_matrix("cox_info_device: info", in->info, BESSX_F64, in->info_ld, 1, in->m, in->m, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "cox_info_device: info is not on the device that owns x");
+    if (int rc = check_device_matrix("cox_info_device: score", in->score, BESSX_F64, 1, 0, in->m, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "cox_info_device: score is not on the device that owns x");
+  }
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  CoxInfoOrder x;
+  cox_info_order(&o, in->n, in->m, in->ties, &x);
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> h;
+    rc = cox_info_run(sc, o, x, h, in, loglik, residual_sum, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  if (!rc) *n_events = x.n_events;
+  return rc;
+}
+
+int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int ties, int repeats, double *stage_ms, double *bytes) {
+  if (!x || repeats < 1 || !stage_ms || !bytes || m < 1) return fail(BESSX_ERR_ARG, "op_cox_info_bench: bad arguments");
+  if (int rc = predict_check_model("op_cox_info_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (ties != 0 && ties != 1) return fail(BESSX_ERR_ARG, "op_cox_info_bench: ties must be 0 (order) or 1 (breslow)");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_info_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_info_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m), time((size_t)n), status((size_t)n);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int i = 0; i < n; i++) {  // times in an order that is not the rows'; ties = 1: groups of four equal times
+    const long long s = ((long long)i * 7919) % n;
+    time[(size_t)i] = ties ? (double)(s / 4) : (double)s + (double)i / (2.0 * n);
+    status[(size_t)i] = (double)(i % 2);
+  }
+  CoxOrder o;
+  cox_order(time.data(), status.data(), nullptr, n, &o);
+  CoxInfoOrder xo;
+  cox_info_order(&o, n, m, ties, &xo);
+  Owner sc;
+  CoxInfoDev c;
+  if (int rc = cox_info_stage(sc, o, xo, cols, m, B.data(), n, ties, nullptr, &c)) return rc;
+  double *out = nullptr;
+  HIPX(sc.alloc(&out, (size_t)m * m + (size_t)m));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  for (int stage = 2; stage >= 0; stage--) {  // (the full sequence first: stages 0 and 1 start from what it leaves)
+    float total = 0.f;
+    for (int i = -1; i < repeats; i++) {  // (i = -1: the warm-up)
+      HIPX(hipEventRecord(e0, nullptr));
+      if (int rc = cox_info_launch(x, f32, row_stride, col_stride, n, m, ties, c, out, m, out + (size_t)m * m, nullptr,
+                                   stage == 2 ? -1 : stage))
+        return rc;
+      HIPX(hipEventRecord(e1, nullptr));
+      HIPX(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPX(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 0) total += ms;
+    }
+    stage_ms[stage] = total / repeats;
+  }
+  const double item = f32 ? 4.0 : 8.0;
+  *bytes = (double)n * m * (item + 8.0) + (double)n * m * 8.0 + (double)c.J * m * 8.0;
+  return BESSX_OK;
+}
+
+}  // extern "C"

@@ -88,6 +88,7 @@ long long cox_eval_workspace(long long n, int R);
 hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                                const double *B, const double *zero, int R, const int *pos, double *eta, double *ex,
                                hipStream_t st);
+hipError_t launch_cox_eval_scan_tot(const double *e, long long n, int R, double *scr, hipStream_t st);
 hipError_t launch_cox_eval_suffix(double *ex, long long n, int R, double *scr, hipStream_t st);
 hipError_t launch_cox_eval_loglik(const double *eta, double *ex, const double *wd, const int *first, long long n, int R,
                                   double *work, double *res, hipStream_t st);
@@ -121,6 +122,21 @@ hipError_t launch_info_gram(const void *src, int f32, long long rs, long long cs
 hipError_t launch_info(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                        const double *B, const double *c, int link, const EvalData &d, double *work, double *res,
                        double *info, long long ld, double *score, hipStream_t st);
+// observed information and score of one Cox model (bessx_k_coxinfo.hip), the kernels between the predictor pass, the
+// scans and the two launch_info_gram sweeps.  _gather: W(c, k) = e[k] * x(rowof[k], cols[c]), m x n position-major.
+// _means: U(j, c) = S1(p, c) / S0[p] for jptr[p] <= j < jptr[p + 1], S1 the suffix sums of W along k (scr: ceil(n / 1024)
+// * m doubles; U column-contiguous with leading dimension ldU >= J, cox_info_ldu(J) keeps its columns 16-byte aligned).
+// _vg: v_i = e[pos[i]] * H[lastk[pos[i]]], g_i = wd[pos[i]] - v_i in ROW order (lastk null: the identity).  _finish:
+// info = G1 - G2 without the sweeps' intercept entry (G2 null: no event), score, res[1] = sum of g.  Device memory.
+long long cox_info_ldu(long long J);
+hipError_t launch_cox_info_gather(const void *src, int f32, long long rs, long long cs, long long n, const int *cols,
+                                  int m, const int *rowof, const double *e, double *W, hipStream_t st);
+hipError_t launch_cox_info_means(const double *W, const double *S0, const int *jptr, long long n, int m, int J, double *scr,
+                                 double *U, long long ldU, hipStream_t st);
+hipError_t launch_cox_info_vg(const double *e, const double *H, const int *lastk, const double *wd, const int *pos,
+                              long long n, double *v, double *g, hipStream_t st);
+hipError_t launch_cox_info_finish(const double *G1, const double *G2, const double *U1, int m, double *info, long long ld,
+                                  double *score, double *res, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

@@ -185,13 +185,21 @@ hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long
   return xb_launch(static_cast<const double *>(src), rs, cs, n, cols, m, B, zero, R, epi, st);
 }
 
+// the first launch of stage 2 alone: scr[r * nb + b] = total of block b of row r of e (R x n), nb = ceil(n / 1024).  The
+// risk-set means of bessx_k_coxinfo.hip follow it with an apply launch of their own.
+hipError_t launch_cox_eval_scan_tot(const double *e, long long n, int R, double *scr, hipStream_t st) {
+  if (!e || !scr || n < 1 || n > 0x7fffffffLL || R < 1 || R > 65535) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + CXE_B - 1) / CXE_B), (unsigned)R);
+  hipLaunchKernelGGL(k_cxe_scan_tot, grid, dim3(CXE_T), 0, st, e, n, scr);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 // stage 2 alone: ex (R x n, position-major) becomes S in place; scr: ceil(n / 1024) * R doubles (the first half of
 // cox_eval_workspace).  The baseline hazard of bessx_k_coxsurv.hip starts from the same S.
 hipError_t launch_cox_eval_suffix(double *ex, long long n, int R, double *scr, hipStream_t st) {
-  if (!ex || !scr || n < 1 || n > 0x7fffffffLL || R < 1 || R > 65535) return hipErrorInvalidValue;
+  if (hipError_t e = launch_cox_eval_scan_tot(ex, n, R, scr, st)) return e;
   const dim3 grid((unsigned)((n + CXE_B - 1) / CXE_B), (unsigned)R);
-  hipLaunchKernelGGL(k_cxe_scan_tot, grid, dim3(CXE_T), 0, st, ex, n, scr);
-  LAUNCH_CHECK();
   hipLaunchKernelGGL(k_cxe_scan_apply, grid, dim3(CXE_T), 0, st, ex, n, scr);
   LAUNCH_CHECK();
   return hipSuccess;

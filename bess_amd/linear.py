@@ -551,6 +551,71 @@ class bess_base:
             raise ValueError("concordance is for the Cox classes, this is a %s model" % self.model_type)
         return self.evaluate_survival(X, y)["c_index"]
 
+    # ---- Cox: coefficient table -------------------------------------------------------------------------------------
+    @staticmethod
+    def _cox_information_host(Xs, beta, time, status, w, ties):
+        """cox_information_device's quantities in fp64 NumPy, by the same decomposition (running sums, not the O(n^2)
+        definition): Xs (n, m) the support's columns, beta (m,), time, status, w (n,) in row order."""
+        n, m = Xs.shape
+        eta = np.zeros(n)
+        for c in range(m):  # (column by column: a row's sum does not depend on where the row lies)
+            eta += Xs[:, c] * beta[c]
+        order = np.argsort(time, kind="stable")
+        x, eta, t, d = Xs[order], eta[order], time[order], status[order]
+        wd = w[order] * d
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        starts = np.nonzero(new)[0]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        last = np.append(starts[1:] - 1, n - 1)[np.cumsum(new) - 1]
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))  # (comparisons: a NaN stays a NaN)
+        e = np.exp(a)
+        r = first if ties == "breslow" else np.arange(n)
+        S0 = np.cumsum(e[::-1])[::-1][r]
+        loglik = float(np.sum(wd * (a - np.log(S0))))
+        H = np.cumsum(wd / S0)
+        if ties == "breslow":
+            H = H[last]
+        v = e * H
+        g = wd - v
+        S1 = np.cumsum((e[:, None] * x)[::-1], axis=0)[::-1]
+        ev = d != 0
+        U = S1[r[ev]] / S0[ev][:, None]
+        info = x.T @ (v[:, None] * x) - U.T @ (wd[ev][:, None] * U)
+        info = np.tril(info) + np.tril(info, -1).T  # (both triangles from the lower one, as the kernel writes them)
+        return {"info": info, "score": x.T @ g, "loglik": loglik, "n_events": float(np.sum(wd)),
+                "residual_sum": float(np.sum(g)) if m > 0 else 0.0}
+
+    def inference_survival(self, X, y, weight=None, ties="order"):
+        """Cox only: standard errors and Wald tests of the fitted model on the rows (X, y) -- capi.cox_wald_table's dict
+        (coef, se, z, p_value, cov, score, dispersion = 1, dof = n_events - m, cond, positive_definite; no intercept) plus
+        cols, the selected columns in the order of coef, loglik and residual_sum.  y: (n, 2) time and status as in fit;
+        weight: n values or None; ties: "order" (the risk sets of the fit) or "breslow".  The information is the observed
+        information of the partial likelihood, sum_k w_k status_k Var_k(x) with Var_k the e-weighted covariance of the
+        support's columns over the risk set of k, on the original scale of X (capi.cox_information_device states it; where
+        a linear predictor is clipped at +-30 it is that formula, not a derivative).  It is formed as a difference of two
+        Gram matrices, so columns far from centred lose digits; score = sum_k w_k status_k (x_k - u_k) is 0 up to rounding
+        at the unpenalised optimum of the support, and residual_sum, the sum of the martingale residuals, is 0 up to
+        rounding always.  Selection is not corrected for.  An X in GPU memory is read in place on torch's current stream,
+        the support's columns only (y and weight may be device arrays: n values each are copied to the host); a NumPy X is
+        served in fp64 NumPy with the same decomposition.  inference() stays None for the Cox classes."""
+        if self.model_type_int != 4:
+            raise ValueError("inference_survival is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.cox_information_device(X, cols, beta[cols], time, status, weight=None if weight is None else w,
+                                              ties=ties, stream=_current_stream(X))
+        else:
+            got = self._cox_information_host(np.asarray(X, dtype=np.float64)[:, cols], beta[cols], time, status, w, ties)
+        out = capi.cox_wald_table(got["info"], got["score"], beta[cols], got["n_events"])
+        out.update(cols=cols, loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
+        return out
+
     # ---- Cox: baseline hazard and survival curves ------------------------------------------------------------------
     def _support_eta(self, X, cols, beta):
         """X[:, cols] @ beta[cols] for a NumPy X, column by column: a row's sum does not depend on where the row lies."""

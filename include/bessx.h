@@ -453,6 +453,64 @@ typedef struct {
 int bessx_info_device(const bessx_info_input *in, double *loss, double *sum_w);
 int bessx_info_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int link,
                          int weighted, long long *doubles, long long *rows_per_slab, int *slabs);
+/* ---------------------------------------------------------------------------------------
+ * 2h. Observed information and score of ONE Cox model on an X already in GPU memory (bessx_k_coxinfo.hip): the Cox
+ *     counterpart of section 2g.  Stateless like sections 2c to 2g.  x, n, p, cols, m, time, status, weight, ties,
+ *     stream: as in section 2e with R = 1; beta: m finite values in HOST memory; no intercept.  Positions, pi, first(k):
+ *     section 2e.  With eta_i = sum_c x(i, cols[c]) * beta[c] (a zero coefficient takes nothing from its column),
+ *     e = exp(clamp(eta, -30, 30)), wd_k = w_k status_k, r(k) = k (ties = 0) or first(k) (ties = 1), x_l the m support
+ *     entries of the row at position l,
+ *         S0(k) = sum_{l >= r(k)} e_l,    S1(k) = sum_{l >= r(k)} e_l x_l,    u_k = S1(k) / S0(k)
+ *         loglik = sum_k wd_k (clamp(eta_k) - log S0(k))              bit for bit section 2e's with want_pairs = 0
+ *         score  = sum_k wd_k (x_k - u_k)                             m values
+ *         info   = sum_k wd_k sum_{l >= r(k)} (e_l / S0(k)) (x_l - u_k)(x_l - u_k)^T
+ *                                          m x m, entry (j, k) at [j * info_ld + k], info_ld >= m; both triangles are
+ *                                          written and are bit-identical mirrors
+ *     (weights on the event terms only, risk sets unweighted).  info is the negative Hessian of loglik in beta wherever
+ *     no clamp is active; where one is, info is this formula and not a derivative.  It is computed as
+ *         H_l = sum_{k : r(k) <= l} wd_k / S0(k),   v_l = e_l H_l,   g_l = wd_l - v_l      (g: the martingale residuals)
+ *         score = sum_l g_l x_l,     info = G1 - G2,     G1 = sum_l v_l x_l x_l^T,     G2 = sum_{k : status_k = 1} wd_k u_k u_k^T
+ *     G1 and score are one sweep of section 2g's matrix-core kernel over x in place; G2 is a second sweep over the J x m
+ *     matrix of the u_k of the J rows with status = 1.  *residual_sum = sum_l g_l, which is 0 up to rounding (with m = 0,
+ *     where no sweep is launched, it is returned as 0).  *n_events = sum_k wd_k (host, in position order).
+ *     info = G1 - G2 is a DIFFERENCE: for columns far from centred both terms are much larger than info and digits are
+ *     lost in proportion (the form R's survival::coxph uses as well); centre such columns before the call.
+ *     Passes over the support of x: three (predictor, the gather of e_l x_l into position order, G1); no gathered copy of
+ *     x[:, cols] in row order is made.  Every scan is additions only in a fixed order, there are no floating-point
+ *     atomics, and block and slab counts depend on (n, m, J) alone: the same call gives the same bits.
+ *     Scratch memory: about (m + 5) n + J m doubles plus the two sweeps' partials (bessx_cox_info_workspace states it;
+ *     3.4 GB at n = 200 000, m = 1023, J = n), released before the call returns: counters 38 / 39 are back at their
+ *     earlier values.  A NaN INSIDE the support view is no error and propagates by IEEE rules; rows past n and columns
+ *     outside the support are not read.
+ *     info and score are device memory of x's device when out_on_device != 0 (checked as in section 2c), else host
+ *     memory; loglik, n_events, residual_sum are host memory.  m = 0 is valid: nothing of x is read, info and score are
+ *     not touched and loglik is the null model's.  m + 1 <= 1024 (the sweeps carry an intercept entry): a larger m is
+ *     BESSX_ERR_UNSUPPORTED, with every other argument error (BESSX_ERR_ARG, the messages of sections 2e / 2g) found
+ *     before any device call.
+ *     bessx_cox_info_workspace needs no device: for n rows, m columns and J event rows, the doubles of scratch memory and
+ *     the row splits of the two sweeps: rows_per_slab[0], slabs[0] of G1 over n rows and rows_per_slab[1], slabs[1] of
+ *     G2 over J rows (0, 0 for a sweep that is not launched).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  double *info;
+  long long info_ld;
+  double *score;
+  int out_on_device;
+  void *stream;
+} bessx_cox_info_input;
+int bessx_cox_info_device(const bessx_cox_info_input *in, double *loglik, double *n_events, double *residual_sum);
+int bessx_cox_info_workspace(int n, int m, int n_event_rows, long long *doubles, long long *rows_per_slab, int *slabs);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -833,6 +891,13 @@ int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long
  * 2 n (m + 1) (m + 2) useful floating-point operations (both triangles and the score) per second / 1e12. */
 int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                         const int *cols, int m, int repeats, double *avg_ms, double *tflops);
+/* The new kernels of section 2h timed the same way (every second row an event, distinct times or, ties = 1, groups of
+ * four equal times): stage_ms[0] the gather of e_l x_l into position order, [1] the column-wise suffix scan that emits
+ * the risk-set means U, [2] every launch of a bessx_cox_info_device call on device data, stages 0 and 1 included
+ * (predictor pass, S0, loglik, gather, H, v and g, the sweep over x, the means, the sweep over U, the finish).
+ * *bytes = what stages 0 and 1 must move: n m (item + 8) + n m 8 + J m 8.  m >= 1. */
+int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int ties, int repeats, double *stage_ms, double *bytes);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
