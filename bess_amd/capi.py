@@ -42,6 +42,7 @@ SYMBOLS = [
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
     "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
+    "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -107,6 +108,16 @@ class InfoInput(ctypes.Structure):
                 ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
                 ("weight_stride", _ll), ("info", _vp), ("info_ld", _ll), ("score", _vp), ("out_on_device", _i),
                 ("stream", _vp)]
+
+
+class DiagInput(ctypes.Structure):
+    """bessx_diag_input: one model, X in GPU memory, y and weight in host or GPU memory, the factor of the inverse
+    information in host memory, which kinds are wanted and where they go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("coef0", _d), ("link", _i), ("y_host", _D), ("y_dev", _vp),
+                ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
+                ("weight_stride", _ll), ("factor", _D), ("factor_ld", _ll), ("dispersion", _d),
+                ("kinds", ctypes.c_uint), ("out", _vp), ("out_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
 
 
 class CoxInfoInput(ctypes.Structure):
@@ -247,6 +258,9 @@ def lib():
         L.bessx_cox_info_device.argtypes = [ctypes.POINTER(CoxInfoInput), _D, _D, _D]
         L.bessx_cox_info_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
         L.bessx_op_cox_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _D, _D]
+        L.bessx_diag_device.argtypes = [ctypes.POINTER(DiagInput)]
+        L.bessx_diag_workspace.argtypes = [_i, _i, ctypes.c_uint, ctypes.POINTER(_ll)]
+        L.bessx_op_diag_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D, _D]
         _lib = L
     return _lib
 
@@ -1444,6 +1458,162 @@ def cox_wald_table(info, score, coef, n_events):
         return {"coef": z, "se": z.copy(), "z": z.copy(), "p_value": z.copy(), "cov": np.zeros((0, 0)), "score": z.copy(),
                 "dispersion": 1.0, "dof": float(n_events), "cond": float("nan"), "positive_definite": True}
     return _wald(info, score, coef, 1.0, float(n_events) - m)
+
+
+DIAG_KINDS = ("leverage", "response", "pearson", "deviance", "std_pearson", "std_deviance", "cooks")  # BESSX_DIAG_* bits
+DIAG_LEVERAGE_KINDS = ("leverage", "std_pearson", "std_deviance", "cooks")  # the kinds that need the factor
+
+
+def info_factor(info):
+    """(R, positive_definite) for an M x M information matrix: R lower triangular with inv(info) = R^T R, from the
+    scaled Cholesky factorisation of wald_table: D = diag(info)^(-1/2), S = D info D = L L^T, R = L^-1 D.  The tests are
+    wald_table's: a diagonal entry <= 0 or not finite, a smallest eigenvalue of S that is not above M eps times the
+    largest, or a failed factorisation give (an M x M matrix of NaN, False)."""
+    info = np.array(info, dtype=np.float64)
+    if info.ndim != 2 or info.shape[0] != info.shape[1] or info.shape[0] < 1:
+        raise ValueError("info must be a square matrix, got shape %s" % (info.shape,))
+    M = info.shape[0]
+    bad = np.full((M, M), np.nan)
+    dg = np.diag(info)
+    if not (np.isfinite(info).all() and (dg > 0).all()):
+        return bad, False
+    d = 1.0 / np.sqrt(dg)
+    S = info * d[:, None] * d[None, :]
+    S = 0.5 * (S + S.T)
+    ev = np.linalg.eigvalsh(S)
+    if not (ev[0] > M * np.finfo(np.float64).eps * ev[-1]):
+        return bad, False
+    try:
+        Lc = np.linalg.cholesky(S)
+    except np.linalg.LinAlgError:
+        return bad, False
+    return np.tril(np.linalg.solve(Lc, np.eye(M))) * d[None, :], True
+
+
+def _diag_mask(kinds):
+    """(bit mask, names in ascending bit order) of an iterable of kind names (or one name)."""
+    if isinstance(kinds, str):
+        kinds = (kinds,)
+    kinds = tuple(kinds)
+    for k in kinds:
+        if k not in DIAG_KINDS:
+            raise ValueError("kinds must be taken from %s, got %r" % (list(DIAG_KINDS), k))
+    if not kinds:
+        raise ValueError("kinds must name at least one of %s" % (list(DIAG_KINDS),))
+    names = tuple(k for k in DIAG_KINDS if k in kinds)
+    return sum(1 << DIAG_KINDS.index(k) for k in names), names
+
+
+def diag_workspace(n, m, kinds=DIAG_KINDS):
+    """Doubles of scratch memory of a diagnostics_device call on n rows with a support of m columns
+    (bessx_diag_workspace; no device is needed): v, the residual vectors that are needed but not requested, and the
+    packed factor."""
+    mask, _ = _diag_mask(kinds)
+    nd = _ll(0)
+    _check(lib().bessx_diag_workspace(int(n), int(m), mask, ctypes.byref(nd)))
+    return nd.value
+
+
+def diagnostics_device(x, cols, beta, coef0, y, factor=None, dispersion=1.0, link="identity", weight=None,
+                       kinds=DIAG_KINDS, out=None, stream=0):
+    """Per-row diagnostics of ONE model on a device matrix x (n x p: float64 or float32, any non-negative strides), read
+    where it lies (bessx_diag_device).  With eta, mu, v as in information_device, z_i = (1, x[i, cols]), M = len(cols) + 1,
+    w = 1 without weights, phi = dispersion and factor = R, lower triangular (M, M) with inv(info) = R^T R (info_factor):
+        leverage      h_i = v_i * sum_j t_ij^2,  t_ij = sum_{k <= j} R_jk z_ik
+        response      y_i - mu_i
+        pearson       rp_i = sqrt(w_i) (y_i - mu_i) / sqrt(V_i)
+        deviance      rd_i = sign(y_i - mu_i) sqrt(w_i max(d_i, 0)),  sign(0) = 0
+        std_pearson   rp_i / sqrt(phi (1 - h_i))
+        std_deviance  rd_i / sqrt(phi (1 - h_i))
+        cooks         rp_i^2 h_i / (phi M (1 - h_i)^2)
+    V = 1, d = (y - eta)^2 ("identity"); V = p (1 - p), d = 2 [f + y log y + (1 - y) log(1 - y)] ("logistic"); V =
+    exp(eta), d = 2 [f + y log y - y] ("poisson"), f the loss term of evaluate_device and 0 log 0 = 0.  No clamp besides
+    max(d, 0): h = 1 or a NaN inside the support give what IEEE arithmetic gives.  kinds: names from DIAG_KINDS; factor
+    may be None when none of DIAG_LEVERAGE_KINDS is asked for (the matrix-core kernel is then not launched), and its
+    strict upper triangle is never read.  Returns a dict from kind name to an (n,) vector: views of ONE (K, n) torch
+    tensor on x's device when x is a torch tensor (torch is looked up, never imported), NumPy arrays for any other
+    device object; out: a float64 device array of shape (K, n) with unit stride along n (its rows in DIAG_KINDS order)
+    to write into instead, whose padding between rows is left untouched.  A row's numbers depend on that row's values,
+    R, phi and M alone: the same bits wherever the row lies, whatever n is, under every layout of x.  No gathered copy
+    of x[:, cols] and nothing n x M is stored.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y,
+    weight) were produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    mask, names = _diag_mask(kinds)
+    K = len(names)
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: diagnostics_device takes one model per call")
+    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
+    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
+        raise ValueError("beta and coef0 must be finite")
+    M = cols.size + 1
+    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
+    a = DiagInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
+    a.y_stride = yrs
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [weight]
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_host = _dp(wh)
+            keep.append(wh)
+    if factor is not None:
+        fh = _f64(factor)
+        if fh.shape != (M, M):
+            raise ValueError("factor must have shape (%d, %d), got %s" % (M, M, fh.shape))
+        a.factor, a.factor_ld = _dp(fh), M
+        keep.append(fh)
+    a.dispersion, a.kinds = float(dispersion), mask
+    if out is not None:
+        if not is_device_array(out):
+            raise ValueError("out must be a device array")
+        do = _DeviceArray(out, "out", 2)
+        if do.item != 8:
+            raise ValueError("out: a device array of float64 is needed (typestr '<f8')")
+        if do.shape != (K, n) or (n > 1 and do.strides[1] != 1) or (K > 1 and do.strides[0] < n):
+            raise ValueError("out must have shape (%d, %d), unit stride along its rows and a row stride of at least %d"
+                             % (K, n, n))
+        result = [out[s] for s in range(K)]
+        a.out, a.out_ld, a.out_on_device = do.ptr, (do.strides[0] if K > 1 else n), 1
+    else:
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(x, torch.Tensor):
+            buf = torch.empty((K, n), dtype=torch.float64, device=x.device)
+            a.out, a.out_on_device = int(buf.data_ptr()), 1
+        else:
+            buf = np.empty((K, n))
+            a.out, a.out_on_device = int(buf.ctypes.data), 0
+        a.out_ld = n
+        result = [buf[s] for s in range(K)]
+    a.stream = int(stream) if stream else None
+    _check(lib().bessx_diag_device(ctypes.byref(a)))
+    return dict(zip(names, result))
+
+
+def op_diag_bench(x, cols, repeats=20):
+    """(ms per launch, fp64 TFLOP/s over n * Mpad^2 operations, bytes the launch must move) of the leverage kernel
+    k_diag_lev alone on the device matrix x for the support cols, device events."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms, tf, by = _d(0), _d(0), _d(0)
+    _check(lib().bessx_op_diag_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                     _ip(cols), cols.size, repeats, ctypes.byref(ms), ctypes.byref(tf),
+                                     ctypes.byref(by)))
+    return ms.value, tf.value, by.value
 
 
 TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties

@@ -2151,6 +2151,244 @@ int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long lon
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------
+// per-row diagnostics of one model on a caller's device matrix (include/bessx.h section 2i)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+constexpr unsigned kDiagAll = 0x7f;
+constexpr unsigned kDiagLev = BESSX_DIAG_LEVERAGE | BESSX_DIAG_STD_PEARSON | BESSX_DIAG_STD_DEVIANCE | BESSX_DIAG_COOKS;
+constexpr unsigned kDiagPhi = BESSX_DIAG_STD_PEARSON | BESSX_DIAG_STD_DEVIANCE | BESSX_DIAG_COOKS;
+
+// which n-vectors of workspace a set of kinds needs: v, the Pearson and the deviance residual when they are needed
+// but not requested
+void diag_needs(unsigned kinds, bool *v, bool *pear, bool *dev) {
+  *v = (kinds & kDiagLev) != 0;
+  *pear = (kinds & (BESSX_DIAG_STD_PEARSON | BESSX_DIAG_COOKS)) && !(kinds & BESSX_DIAG_PEARSON);
+  *dev = (kinds & BESSX_DIAG_STD_DEVIANCE) && !(kinds & BESSX_DIAG_DEVIANCE);
+}
+
+int diag_count(unsigned kinds) {
+  int K = 0;
+  for (unsigned b = 1; b <= kDiagAll; b <<= 1) K += (kinds & b) != 0;
+  return K;
+}
+
+// everything about the call that needs no device
+int diag_check_args(const char *who, const bessx_diag_input *in) {
+  const std::string w(who);
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->out) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0 || in->y_stride < 0 || in->weight_stride < 0)
+    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, in->link)) return rc;
+  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
+  for (int k = 0; k < in->m; k++)
+    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
+  if (!std::isfinite(in->coef0)) return fail(BESSX_ERR_ARG, w + ": coef0 must be finite");
+  if ((in->y_host != nullptr) == (in->y_dev != nullptr))
+    return fail(BESSX_ERR_ARG, w + ": give y as a host pointer or as a device view (one of the two)");
+  if (in->y_dev && in->y_dtype != BESSX_F64 && in->y_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": y: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->weight_host && in->weight_dev)
+    return fail(BESSX_ERR_ARG, w + ": give weight as a host pointer or as a device vector, not both");
+  if (in->weight_dev && in->weight_dtype != BESSX_F64 && in->weight_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": weight: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->kinds == 0 || (in->kinds & ~kDiagAll)) return fail(BESSX_ERR_ARG, w + ": kinds must be a non-empty set of BESSX_DIAG_* bits");
+  if (in->out_ld < (long long)in->n) return fail(BESSX_ERR_ARG, w + ": out_ld must be at least n");
+  if (in->m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if ((in->kinds & kDiagPhi) && !(std::isfinite(in->dispersion) && in->dispersion > 0.0))
+    return fail(BESSX_ERR_ARG, w + ": dispersion must be finite and positive");
+  if (in->kinds & kDiagLev) {
+    if (!in->factor) return fail(BESSX_ERR_ARG, w + ": a kind that needs the leverage needs the factor");
+    if (in->factor_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m + 1");
+    for (long long j = 0; j <= in->m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  return 0;
+}
+
+long long diag_doubles(long long n, int m, unsigned kinds) {
+  bool v, pear, dev;
+  diag_needs(kinds, &v, &pear, &dev);
+  const long long nv = (n + 1) / 2 * 2;
+  return nv * ((int)v + (int)pear + (int)dev) + (v ? diag_factor_doubles(m) : 0);
+}
+
+// sc, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int diag_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const bessx_diag_input *in, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  bessx_eval_input e{};
+  e.n = in->n;
+  e.R = 1;
+  e.y_host = in->y_host;
+  e.y_dev = in->y_dev;
+  e.y_dtype = in->y_dtype;
+  e.y_row_stride = in->y_stride;
+  e.y_cols = 1;
+  e.weight_host = in->weight_host;
+  e.weight_dev = in->weight_dev;
+  e.weight_dtype = in->weight_dtype;
+  e.weight_stride = in->weight_stride;
+  const int f32 = in->x_dtype == BESSX_F32, m = in->m, K = diag_count(in->kinds);
+  const long long n = in->n, nv = (n + 1) / 2 * 2;
+  const unsigned kinds = in->kinds;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *stage = nullptr;
+  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
+  EvalData d;
+  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  bool need_v, tmp_pear, tmp_dev;
+  diag_needs(kinds, &need_v, &tmp_pear, &tmp_dev);
+  HIPX(sc.alloc(&work, (size_t)diag_doubles(n, m, kinds)));
+  double *out_d = in->out;
+  long long ld = in->out_ld;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&stage, (size_t)K * (size_t)n));
+    out_d = stage;
+    ld = n;
+  }
+  double *slot[7];
+  int s = 0;
+  for (int b = 0; b < 7; b++) slot[b] = (kinds & (1u << b)) ? out_d + (long long)(s++) * ld : nullptr;
+  double *wp = work;
+  double *v_d = nullptr, *pear_d = slot[2], *dev_d = slot[3];
+  if (need_v) v_d = wp, wp += nv;
+  if (tmp_pear) pear_d = wp, wp += nv;
+  if (tmp_dev) dev_d = wp, wp += nv;
+  HIPX(launch_diag_eta(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, B_d, c_d, in->link, d, v_d, slot[1],
+                       pear_d, dev_d, st));
+  if (need_v) {
+    pk.resize((size_t)diag_factor_doubles(m));
+    diag_pack_factor(in->factor, in->factor_ld, m, pk.data());
+    HIPX(hipMemcpyAsync(wp, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(launch_diag_lev(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, wp, v_d, pear_d, dev_d,
+                         in->dispersion, slot[0], slot[4], slot[5], slot[6], st));
+  }
+  if (!in->out_on_device) {
+    h.resize((size_t)K * (size_t)n);
+    HIPX(hipMemcpyAsync(h.data(), stage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device)
+    for (int k = 0; k < K; k++) std::copy(h.begin() + (size_t)k * n, h.begin() + (size_t)(k + 1) * n, in->out + k * in->out_ld);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_diag_workspace(int n, int m, unsigned kinds, long long *doubles) {
+  if (!doubles) return fail(BESSX_ERR_ARG, "diag_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "diag_workspace: empty matrix");
+  if (kinds == 0 || (kinds & ~kDiagAll))
+    return fail(BESSX_ERR_ARG, "diag_workspace: kinds must be a non-empty set of BESSX_DIAG_* bits");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "diag_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  *doubles = diag_doubles(n, m, kinds);
+  return BESSX_OK;
+}
+
+int bessx_diag_device(const bessx_diag_input *in) {
+  if (int rc = diag_check_args("diag_device", in)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("diag_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->y_dev) {
+    if (int rc = check_device_matrix("diag_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "diag_device: y is not on the device that owns x");
+  }
+  if (in->weight_dev) {
+    if (int rc = check_device_matrix("diag_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
+                                     in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "diag_device: weight is not on the device that owns x");
+  }
+  if (in->out_on_device) {
+    if (int rc = check_device_matrix("diag_device: out", in->out, BESSX_F64, in->out_ld, 1, diag_count(in->kinds), in->n,
+                                     &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "diag_device: out is not on the device that owns x");
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> pk, h;
+    rc = diag_run(sc, pk, h, in, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_diag_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                        const int *cols, int m, int repeats, double *avg_ms, double *tflops, double *bytes) {
+  if (!x || repeats < 1 || !avg_ms || !tflops || !bytes) return fail(BESSX_ERR_ARG, "op_diag_bench: bad arguments");
+  if (int rc = predict_check_model("op_diag_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_diag_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_diag_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t M = (size_t)m + 1;
+  // a factor of the library's own: the scaled identity plus a small lower triangle
+  std::vector<double> R(M * M, 0.0), pk((size_t)diag_factor_doubles(m)), v((size_t)n, 0.25), r((size_t)n);
+  for (size_t j = 0; j < M; j++)
+    for (size_t k = 0; k <= j; k++) R[j * M + k] = (j == k ? 1.0 : 1.0 / 64.0) / std::sqrt((double)n);
+  diag_pack_factor(R.data(), (long long)M, m, pk.data());
+  for (size_t i = 0; i < r.size(); i++) r[i] = (i % 2) ? -0.5 : 0.5;
+  int *cols_d = nullptr;
+  double *pk_d = nullptr, *v_d = nullptr, *r_d = nullptr, *out = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&pk_d, pk.size()));
+  HIPX(sc.alloc(&v_d, v.size()));
+  HIPX(sc.alloc(&r_d, r.size()));
+  HIPX(sc.alloc(&out, 4 * (size_t)n));
+  if (m > 0) HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(pk_d, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(v_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(r_d, r.data(), r.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  const size_t N = (size_t)n;
+  HIPX(launch_diag_lev(x, f32, row_stride, col_stride, n, cols_d, m, pk_d, v_d, r_d, r_d, 1.0, out, out + N, out + 2 * N,
+                       out + 3 * N, nullptr));
+  HIPX(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < repeats; i++)
+    HIPX(launch_diag_lev(x, f32, row_stride, col_stride, n, cols_d, m, pk_d, v_d, r_d, r_d, 1.0, out, out + N,
+                         out + 2 * N, out + 3 * N, nullptr));
+  HIPX(hipEventRecord(e1, nullptr));
+  HIPX(hipEventSynchronize(e1));
+  float ms = 0.f;
+  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  const double Mpad = 16.0 * (double)((M + 15) / 16);
+  *avg_ms = ms / repeats;
+  *tflops = (double)n * Mpad * Mpad * repeats / ((double)ms * 1e-3) / 1e12;
+  *bytes = (double)n * (double)m * (f32 ? 4.0 : 8.0) + 7.0 * 8.0 * (double)n + 8.0 * (double)pk.size();
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
 // observed information and score of one Cox model on a caller's device matrix (include/bessx.h section 2h)
 // ----------------------------------------------------------------------------------------------
 namespace {

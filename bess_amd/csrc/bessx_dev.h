@@ -122,6 +122,22 @@ hipError_t launch_info_gram(const void *src, int f32, long long rs, long long cs
 hipError_t launch_info(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                        const double *B, const double *c, int link, const EvalData &d, double *work, double *res,
                        double *info, long long ld, double *score, hipStream_t st);
+// per-row diagnostics of one model (bessx_k_diag.hip).  _eta: the predictor pass (src, cols, B, c as in launch_predict,
+// R = 1) whose epilogue writes, each to n doubles or nowhere (null): v_i as in launch_info, the response residual
+// y_i - mu_i, the Pearson and the deviance residual.  _lev: h_i = v_i * sum_j t_ij^2 with T = Z R^T on the fp64 matrix
+// cores, R lower triangular (m + 1) x (m + 1), given as pk = diag_factor_doubles(m) doubles in the order of
+// diag_pack_factor (which runs on the host and never reads R's strict upper triangle); writes, each to n doubles or
+// nowhere, h, rp / sqrt(phi (1 - h)), rd / sqrt(phi (1 - h)) and rp^2 h / (phi (m + 1) (1 - h)^2).  m + 1 <= INFO_M_MAX.
+// diag_sum_depth: the additions behind one row's sum of t^2, a function of m alone.  Everything else is device memory.
+int diag_sum_depth(int m);
+long long diag_factor_doubles(int m);
+void diag_pack_factor(const double *R, long long ld, int m, double *pk);
+hipError_t launch_diag_eta(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                           const double *B, const double *c, int link, const EvalData &d, double *v, double *resp,
+                           double *pear, double *dev, hipStream_t st);
+hipError_t launch_diag_lev(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                           const double *pk, const double *vw, const double *rp, const double *rd, double phi,
+                           double *o_h, double *o_sp, double *o_sd, double *o_ck, hipStream_t st);
 // observed information and score of one Cox model (bessx_k_coxinfo.hip), the kernels between the predictor pass, the
 // scans and the two launch_info_gram sweeps.  _gather: W(c, k) = e[k] * x(rowof[k], cols[c]), m x n position-major.
 // _means: U(j, c) = S1(p, c) / S0[p] for jptr[p] <= j < jptr[p + 1], S1 the suffix sums of W along k (scr: ceil(n / 1024)

@@ -8,6 +8,7 @@
 #include "bessx_k_coxeval.hip"
 #include "bessx_k_coxsurv.hip"
 #include "bessx_k_info.hip"
+#include "bessx_k_diag.hip"
 #include "bessx_k_coxinfo.hip"
 #include "bessx_k_solve.hip"
 #include "bessx_k_glm.hip"

@@ -435,6 +435,124 @@ class bess_base:
         out["cols"] = cols
         return out
 
+    # ---- per-row diagnostics -------------------------------------------------------------------------------------
+    @staticmethod
+    def _diagnostics_host(link, Xs, beta, coef0, y, w, R, dispersion, kinds):
+        """diagnostics_device's quantities in fp64 NumPy, the same definitions: Xs (n, m) the support's columns, beta
+        (m,), y (n,), w (n,), R (M, M) lower triangular or None (no leverage kind).  T = Z R^T is formed column by
+        column with elementwise operations over the rows, so a row's result does not depend on where the row lies."""
+        n, M = Xs.shape[0], Xs.shape[1] + 1
+        eta = np.zeros(n)
+        for k in range(M - 1):
+            eta = eta + Xs[:, k] * beta[k]
+        eta = eta + coef0
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            xlogx = lambda a: np.where(a == 0, 0.0, a * np.log(np.where(a == 0, 1.0, a)))  # noqa: E731
+            if link == "identity":
+                mu, V, d = eta, np.ones(n), (y - eta) * (y - eta)
+            elif link == "logistic":
+                t = np.exp(-np.abs(eta))
+                s = 1.0 + t
+                mu, V = np.where(eta >= 0, 1.0, t) / s, t / (s * s)
+                f = (np.where(eta > 0, eta, 0.0) + np.log1p(t)) - y * eta
+                d = 2.0 * ((f + xlogx(y)) + xlogx(1.0 - y))
+            else:
+                mu = np.exp(eta)
+                V = mu
+                d = 2.0 * (((mu - y * eta) + xlogx(y)) - y)
+            r = y - mu
+            out = {"response": r, "pearson": (np.sqrt(w) * r) / np.sqrt(V),
+                   "deviance": np.sign(r) * np.sqrt(w * np.where(d < 0, 0.0, d))}
+            if any(k in capi.DIAG_LEVERAGE_KINDS for k in kinds):
+                Z = np.column_stack([np.ones(n), Xs])
+                s2 = np.zeros(n)
+                for j in range(M):
+                    tj = np.zeros(n)
+                    for k in range(j + 1):
+                        tj = tj + R[j, k] * Z[:, k]
+                    s2 = s2 + tj * tj
+                h = (w * V) * s2
+                om = 1.0 - h
+                den = np.sqrt(dispersion * om)
+                out.update(leverage=h, std_pearson=out["pearson"] / den, std_deviance=out["deviance"] / den,
+                           cooks=((out["pearson"] * out["pearson"]) * h) / ((dispersion * M) * (om * om)))
+        return {k: out[k] for k in capi.DIAG_KINDS if k in kinds}
+
+    def diagnostics(self, X, y, weight=None, kinds=None):
+        """Which rows drive the fit: a dict from kind name to an (n,) vector for the kinds asked for (None: all of
+        capi.DIAG_KINDS -- leverage, response, pearson, deviance, std_pearson, std_deviance, cooks, as
+        capi.diagnostics_device defines them), plus cols, dispersion and positive_definite.  The leverage is the diagonal
+        of the hat matrix W^(1/2) Z (Z^T W Z)^-1 Z^T W^(1/2) with z_i = (1, X[i, cols]) and the working weights of
+        inference(); the dispersion is inference()'s (loss / (n_eff - m - 1) for Lm, 1 otherwise).  An X in GPU memory is
+        read in place on torch's current stream -- the information matrix by capi.information_device, its factor by
+        capi.info_factor on the host, the rows by capi.diagnostics_device -- and the vectors are views of one tensor
+        on X's device; y and weight may be device arrays too.  A NumPy X is served in fp64 NumPy with the same
+        definitions.  When the information is not positive definite (or, for Lm, the dispersion is not positive) the
+        kinds that need the leverage are filled with NaN, the three residuals are still computed and nothing is raised.
+        Cox: None.  A 2-D beta (Lm fitted to several responses) raises ValueError: one model per call."""
+        on_device = capi.is_device_array(X)
+        shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
+        if len(shape) != 2 or shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        n = shape[0]
+        if self.model_type_int == 4:
+            return None
+        beta, cols, coef0, multi = self._model_arrays()
+        if multi:
+            raise ValueError("diagnostics() takes one model: this Lm was fitted to %d responses (a 2-D beta), which is "
+                             "not supported" % beta.shape[1])
+        _, kinds = capi._diag_mask(capi.DIAG_KINDS if kinds is None else kinds)
+        link = self._LINK[self.model_type_int]
+        y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
+        ysize = capi._DeviceArray(y, "y").size if y_dev else np.size(y)
+        if ysize != n:
+            raise ValueError("X.shape(0) should be equal to y.size")
+        if weight is not None and (capi._DeviceArray(weight, "weight").size if w_dev else np.size(weight)) != n:
+            raise ValueError("X.shape(0) should be equal to weight.size")
+        M = cols.size + 1
+        lev = [k for k in kinds if k in capi.DIAG_LEVERAGE_KINDS]
+        res = [k for k in kinds if k not in capi.DIAG_LEVERAGE_KINDS]
+        if on_device:
+            if not y_dev:
+                y = np.asarray(y, dtype=np.float64).reshape(-1)
+            st = _current_stream(X)
+            got = capi.information_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight, stream=st)
+        else:
+            Xs = np.asarray(X, dtype=np.float64)[:, cols]
+            yh = (capi.device_to_host(y, _current_stream(y)) if y_dev else np.asarray(y, dtype=np.float64)).reshape(-1)
+            if weight is None:
+                w = np.ones(n)
+            else:
+                w = (capi.device_to_host(weight, _current_stream(weight)) if w_dev
+                     else np.asarray(weight, dtype=np.float64)).reshape(-1)
+            got = self._information_host(link, Xs, beta[cols], coef0[0], yh, w)
+        dof = float(got["sum_w"]) - M
+        if link == "identity":
+            dispersion = float(got["loss"]) / dof if dof > 0 else float("nan")
+        else:
+            dispersion = 1.0
+        R, pd = capi.info_factor(got["info"])
+        ok = pd and np.isfinite(dispersion) and dispersion > 0
+        ask = kinds if ok else tuple(res)
+        out = {}
+        if ask:
+            if on_device:
+                out = capi.diagnostics_device(X, cols, beta[cols], coef0[0], y, factor=R if ok and lev else None,
+                                              dispersion=dispersion if ok else 1.0, link=link, weight=weight, kinds=ask,
+                                              stream=st)
+            else:
+                out = self._diagnostics_host(link, Xs, beta[cols], coef0[0], yh, w, R, dispersion, ask)
+        if not ok:
+            torch = sys.modules.get("torch")
+            for k in lev:
+                if on_device and torch is not None and isinstance(X, torch.Tensor):
+                    out[k] = torch.full((n,), float("nan"), dtype=torch.float64, device=X.device)
+                else:
+                    out[k] = np.full(n, np.nan)
+        out = {k: out[k] for k in kinds}
+        out.update(cols=cols, dispersion=dispersion, positive_definite=bool(pd))
+        return out
+
     def score(self, X, y, weight=None):
         """r2 (Lm), accuracy (Logistic) or d2 (Poisson) of evaluate(X, y, weight); None for Cox."""
         res = self.evaluate(X, y, weight)

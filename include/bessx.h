@@ -511,6 +511,86 @@ typedef struct {
 } bessx_cox_info_input;
 int bessx_cox_info_device(const bessx_cox_info_input *in, double *loglik, double *n_events, double *residual_sum);
 int bessx_cox_info_workspace(int n, int m, int n_event_rows, long long *doubles, long long *rows_per_slab, int *slabs);
+/* ---------------------------------------------------------------------------------------
+ * 2i. Per-row diagnostics of ONE model on an X already in GPU memory (bessx_k_diag.hip): which rows drive the fit.
+ *     Stateless like sections 2c to 2h.  x, n, p, cols, m, beta, coef0, link, y, weight, stream: as in section 2g.
+ *     eta_i, mu_i (identity: eta_i; logistic: p_i; Poisson: exp(eta_i)) and v_i are those of section 2g, the logistic
+ *     ones from t = exp(-|eta_i|) without overflow or clamp; w_i = 1 without weights; z_i = (1, x(i, cols[0]), ...),
+ *     M = m + 1; phi = dispersion; factor = R, an M x M lower-triangular matrix in HOST memory, entry (j, k) at
+ *     [j * factor_ld + k], factor_ld >= M, with inverse(info) = R^T R for the info of section 2g.  Its strict upper
+ *     triangle is never read.  One bit of `kinds` per kind, in this order (bit 0 first):
+ *         BESSX_DIAG_LEVERAGE      h_i = v_i * sum_j t_ij^2,   t_ij = sum_{k <= j} R_jk z_ik
+ *         BESSX_DIAG_RESPONSE      y_i - mu_i
+ *         BESSX_DIAG_PEARSON       rp_i = sqrt(w_i) (y_i - mu_i) / sqrt(V_i)
+ *         BESSX_DIAG_DEVIANCE      rd_i = sign(y_i - mu_i) * sqrt(w_i * max(d_i, 0)),   sign(0) = 0
+ *         BESSX_DIAG_STD_PEARSON   rp_i / sqrt(phi (1 - h_i))
+ *         BESSX_DIAG_STD_DEVIANCE  rd_i / sqrt(phi (1 - h_i))
+ *         BESSX_DIAG_COOKS         rp_i^2 h_i / (phi M (1 - h_i)^2)
+ *     link         V_i                                   d_i                                       (0 log 0 = 0)
+ *     _IDENTITY    1                                     (y_i - eta_i)^2
+ *     _LOGISTIC    t / (1 + t)^2 = p_i (1 - p_i)         2 [f(eta_i, y_i) + y_i log y_i + (1 - y_i) log(1 - y_i)]
+ *     _POISSON     exp(eta_i)                            2 [f(eta_i, y_i) + y_i log y_i - y_i]
+ *     with f the loss term of section 2d.  There is no clamp besides max(d_i, 0): h_i = 1, an underflowed V_i or a NaN
+ *     inside the support view give what IEEE arithmetic gives.  A row of weight 0 has h_i = 0 and residuals 0 where
+ *     the other factor is finite.  Rows past n, columns outside the support and the padding of the last tile are not
+ *     read; m = 0 is valid (z = (1)) and reads nothing of x.
+ *     out receives the K requested kinds in ascending bit order, kind slot s at out + s * out_ld, out_ld >= n: device
+ *     memory of x's device when out_on_device != 0 (checked as in section 2c), else host memory.
+ *     Two steps.  The predictor pass writes the residuals (and v_i); it is the whole call when no kind needs the
+ *     leverage, and factor may then be null.  It always runs the threads-along-rows loop of sections 2c / 2d, also for a
+ *     row-contiguous x, so that eta_i is the same bits under every layout of x (for a row-contiguous x, sections 2c to
+ *     2g add the support's products in another order).  The second step forms T = Z R^T in 16 x 16 tiles on the fp64
+ *     matrix cores from x in place, only the steps at or below each tile's diagonal, squares and adds per row in a
+ *     fixed order and writes h_i and the kinds derived from it; the factor is uploaded once per call, packed in the
+ *     order the lanes read it.  Nothing n x M is stored anywhere and there are no floating-point atomics.  A row's
+ *     results depend on that row's values, R, phi and M alone: they are the same bits wherever the row lies in x,
+ *     whatever n is, and under every layout of the same dtype.
+ *     m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED.  Every argument error is found before any device call
+ *     (BESSX_ERR_ARG: the messages of sections 2d / 2g; kinds zero or with unknown bits; a kind that needs the leverage
+ *     with a null factor; a dispersion that is not finite and positive when a kind uses it; a non-finite entry in the
+ *     lower triangle of the factor).  Scratch memory (bessx_diag_workspace doubles, the model, host y / weight, a K x n
+ *     staging buffer for a host out) is released before the call returns: counters 38 / 39 are back at their earlier
+ *     values.  bessx_diag_workspace needs no device: the doubles of v, of the residual vectors that are needed but not
+ *     requested, and of the packed factor.
+ * ------------------------------------------------------------------------------------- */
+enum {
+  BESSX_DIAG_LEVERAGE = 1,
+  BESSX_DIAG_RESPONSE = 2,
+  BESSX_DIAG_PEARSON = 4,
+  BESSX_DIAG_DEVIANCE = 8,
+  BESSX_DIAG_STD_PEARSON = 16,
+  BESSX_DIAG_STD_DEVIANCE = 32,
+  BESSX_DIAG_COOKS = 64
+};
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  double coef0;
+  int link;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_stride;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  const double *factor;
+  long long factor_ld;
+  double dispersion;
+  unsigned kinds;
+  double *out;
+  long long out_ld;
+  int out_on_device;
+  void *stream;
+} bessx_diag_input;
+int bessx_diag_device(const bessx_diag_input *in);
+int bessx_diag_workspace(int n, int m, unsigned kinds, long long *doubles);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -891,6 +971,12 @@ int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long
  * 2 n (m + 1) (m + 2) useful floating-point operations (both triangles and the score) per second / 1e12. */
 int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                         const int *cols, int m, int repeats, double *avg_ms, double *tflops);
+/* The matrix-core kernel of section 2i alone (k_diag_lev, every kind it writes) timed the same way, from a factor, working
+ * weights and residuals of the library's own: *avg_ms per launch, *tflops = n * Mpad^2 floating-point operations per
+ * second / 1e12 with Mpad = 16 ceil((m + 1) / 16) (two per multiply-add of the lower triangle's tiles), *bytes = what the
+ * launch must move: n m item + 7 n 8 + the packed factor once. */
+int bessx_op_diag_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                        const int *cols, int m, int repeats, double *avg_ms, double *tflops, double *bytes);
 /* The new kernels of section 2h timed the same way (every second row an event, distinct times or, ties = 1, groups of
  * four equal times): stage_ms[0] the gather of e_l x_l into position order, [1] the column-wise suffix scan that emits
  * the risk-set means U, [2] every launch of a bessx_cox_info_device call on device data, stages 0 and 1 included
