@@ -43,6 +43,7 @@ SYMBOLS = [
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
     "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
     "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
+    "bessx_cox_diag_device", "bessx_cox_diag_workspace", "bessx_op_cox_diag_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -126,6 +127,17 @@ class CoxInfoInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
                 ("info", _vp), ("info_ld", _ll), ("score", _vp), ("out_on_device", _i), ("stream", _vp)]
+
+
+class CoxDiagInput(ctypes.Structure):
+    """bessx_cox_diag_input: one Cox model, X in GPU memory, time / status / weight in host memory, the factor of the
+    inverse information and the inverse itself in host memory, which kinds are wanted and where they go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
+                ("factor", _D), ("factor_ld", _ll), ("cinv", _D), ("cinv_ld", _ll), ("kinds", ctypes.c_uint),
+                ("out_rows", _vp), ("out_rows_ld", _ll), ("out_score", _vp), ("out_score_ld", _ll),
+                ("out_dfbeta", _vp), ("out_dfbeta_ld", _ll), ("out_schoenfeld", _vp), ("out_schoenfeld_ld", _ll),
+                ("event_rows", _I), ("out_on_device", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -261,6 +273,9 @@ def lib():
         L.bessx_diag_device.argtypes = [ctypes.POINTER(DiagInput)]
         L.bessx_diag_workspace.argtypes = [_i, _i, ctypes.c_uint, ctypes.POINTER(_ll)]
         L.bessx_op_diag_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D, _D]
+        L.bessx_cox_diag_device.argtypes = [ctypes.POINTER(CoxDiagInput), _I]
+        L.bessx_cox_diag_workspace.argtypes = [_i, _i, _i, ctypes.c_uint, ctypes.POINTER(_ll)]
+        L.bessx_op_cox_diag_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1788,6 +1803,135 @@ def op_cox_info_bench(x, cols, ties="order", repeats=20):
                                          _ip(cols), cols.size, TIES[ties], repeats, _dp(ms), ctypes.byref(nbytes)))
     return tuple(float(v) for v in ms), nbytes.value
 
+
+COX_DIAG_KINDS = ("martingale", "deviance", "score", "dfbeta", "displacement", "schoenfeld")  # BESSX_COX_DIAG_* bits
+COX_DIAG_ROW_KINDS = ("martingale", "deviance", "displacement")  # the (n,) kinds, in the order of their slots
+
+
+def _cox_diag_mask(kinds):
+    """(bit mask, names in ascending bit order) of an iterable of kind names (or one name)."""
+    if isinstance(kinds, str):
+        kinds = (kinds,)
+    kinds = tuple(kinds)
+    for k in kinds:
+        if k not in COX_DIAG_KINDS:
+            raise ValueError("kinds must be taken from %s, got %r" % (list(COX_DIAG_KINDS), k))
+    if not kinds:
+        raise ValueError("kinds must name at least one of %s" % (list(COX_DIAG_KINDS),))
+    names = tuple(k for k in COX_DIAG_KINDS if k in kinds)
+    return sum(1 << COX_DIAG_KINDS.index(k) for k in names), names
+
+
+def cox_diag_workspace(n, m, n_event_rows, kinds=COX_DIAG_KINDS):
+    """Doubles of scratch memory of a cox_diagnostics_device call on n rows with a support of m columns and
+    n_event_rows rows of status 1 (bessx_cox_diag_workspace; no device is needed): about (2 m + 6) n + J m when score,
+    dfbeta, displacement or schoenfeld is asked for, n-vectors only for martingale / deviance alone."""
+    mask, _ = _cox_diag_mask(kinds)
+    nd = _ll(0)
+    _check(lib().bessx_cox_diag_workspace(int(n), int(m), int(n_event_rows), mask, ctypes.byref(nd)))
+    return nd.value
+
+
+def cox_diagnostics_device(x, cols, beta, time, status, factor=None, cinv=None, weight=None, ties="order",
+                           kinds=COX_DIAG_KINDS, stream=0):
+    """Residuals, dfbeta and case influence of ONE Cox model on a device matrix x (n x p: float64 or float32, any
+    non-negative strides), read where it lies (bessx_cox_diag_device).  With the quantities of cox_information_device
+    (positions k in time order, r(k), e, wd = w * status, S0, u_k = S1_k / S0_k, H, v = e H, g = wd - v),
+    dh_p = sum_{k: r(k) = p} wd_k / S0_p and A_l = sum_{p <= l} dh_p u_p:
+        martingale    g_k = wd_k - v_k                                                              (n,)
+        deviance      sign(g_k) sqrt(2 max(v_k - wd_k + wd_k log(wd_k / v_k), 0)), 0 log 0 = 0       (n,)
+        score         L_k = g_k x_k - wd_k u_r(k) + e_k A_k; its column sums are the score           (n, m)
+        dfbeta        L_k @ cinv, cinv = inv(info): the approximate change in beta without row k     (n, m)
+        displacement  L_k^T cinv L_k = sum_j t_kj^2, t_k = factor @ L_k (info_factor's R)            (n,)
+        schoenfeld    x_k - u_k for the J rows with status 1, in time (position) order               (J, m)
+    Everything but schoenfeld is in row order.  factor (m, m) lower triangular with inv(info) = R^T R is needed by
+    displacement, cinv (m, m) symmetric by dfbeta; both are host arrays.  time, status (0 or 1), weight (None = ones):
+    n values each, host or device arrays (device arrays are copied to the host).  Returns a dict from kind name to its
+    array plus "event_rows" (J,) int32, the row of every schoenfeld row, and "event_times" (J,): torch tensors on x's
+    device when x is a torch tensor (torch is looked up, never imported; the (n,) kinds are views of one tensor, the
+    matrices are (n, m) / (J, m) views with unit stride along n / J), NumPy arrays of the same layout for any other
+    device object; event_rows and event_times are always NumPy.  No clamp besides the one of eta at +-30 and the
+    max(., 0) of the deviance; a NaN inside the support propagates.  x's support is read three times (predictor, the
+    gather of e x, the forming of L) plus the J event rows for schoenfeld; the same call gives the same bits.
+    len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if ties not in TIES:
+        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
+    mask, names = _cox_diag_mask(kinds)
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: cox_diagnostics_device takes one model per call")
+    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
+    if not np.isfinite(B).all():
+        raise ValueError("beta must be finite")
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, a in given:  # (every shape is checked before anything is copied)
+        _survival_vector(a, n, what, check_only=True)
+    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    m = cols.size
+    J = int(np.count_nonzero(host["status"]))
+    a = CoxDiagInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    a.ties, a.stream, a.kinds = TIES[ties], int(stream) if stream else None, mask
+    keep = []
+    for what, mat in (("factor", factor), ("cinv", cinv)):
+        if mat is not None:
+            mh = _f64(mat)
+            if mh.shape != (m, m):
+                raise ValueError("%s must have shape (%d, %d), got %s" % (what, m, m, mh.shape))
+            setattr(a, what, _dp(mh))
+            setattr(a, what + "_ld", max(m, 1))
+            keep.append(mh)
+    rows = [k for k in COX_DIAG_ROW_KINDS if k in names]
+    torch = sys.modules.get("torch")
+    on_torch = torch is not None and isinstance(x, torch.Tensor)
+
+    def empty(r, c):  # (r, c) with unit stride along c
+        if on_torch:
+            t = torch.empty((r, c), dtype=torch.float64, device=x.device)
+            return t, int(t.data_ptr())
+        t = np.empty((r, c))
+        return t, int(t.ctypes.data)
+
+    out = {}
+    a.out_on_device = 1 if on_torch else 0
+    if rows:
+        buf, a.out_rows = empty(len(rows), n)
+        a.out_rows_ld = n
+        out.update((k, buf[s]) for s, k in enumerate(rows))
+    for k, cnt in (("score", n), ("dfbeta", n), ("schoenfeld", J)):
+        if k in names:
+            buf, ptr = empty(m, cnt)
+            setattr(a, "out_" + k, ptr)
+            setattr(a, "out_%s_ld" % k, max(cnt, 1))
+            out[k] = buf.T
+    ev = np.zeros(J, dtype=np.int32)
+    a.event_rows = _ip(ev)
+    nj = _i(0)
+    _check(lib().bessx_cox_diag_device(ctypes.byref(a), ctypes.byref(nj)))
+    assert nj.value == J
+    out = {k: out[k] for k in names}
+    out["event_rows"] = ev
+    out["event_times"] = host["time"][ev]
+    return out
+
+
+def op_cox_diag_bench(x, cols, ties="order", repeats=20):
+    """((ms of the increments and their forward scan, ms of those plus the forming of L, ms of L R^T with the
+    displacement epilogue, ms of L C with the dfbeta epilogue), bytes the last three must move) on the device matrix x
+    for the support cols (at least one column), device events; the data are op_cox_info_bench's."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    ms, nbytes = np.zeros(4), _d(0)
+    _check(lib().bessx_op_cox_diag_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, TIES[ties], repeats, _dp(ms), ctypes.byref(nbytes)))
+    return tuple(float(v) for v in ms), nbytes.value
 
 def cox_baseline_device(x, cols, B, time, status, weight=None, stream=0):
     """The Breslow baseline cumulative hazard of one Cox model on the rows it was fitted to, x a device matrix (n x p:

@@ -2686,3 +2686,410 @@ int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// residuals, dfbeta and case influence of one Cox model on a caller's device matrix (include/bessx.h section 2j)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+constexpr unsigned kCoxDiagAll = 63u;
+constexpr unsigned kCoxDiagRows = BESSX_COX_DIAG_MARTINGALE | BESSX_COX_DIAG_DEVIANCE | BESSX_COX_DIAG_DISPLACEMENT;
+constexpr unsigned kCoxDiagL = BESSX_COX_DIAG_SCORE | BESSX_COX_DIAG_DFBETA | BESSX_COX_DIAG_DISPLACEMENT;
+constexpr unsigned kCoxDiagU = kCoxDiagL | BESSX_COX_DIAG_SCHOENFELD;
+
+int cox_diag_rows_count(unsigned kinds) {
+  return (int)((kinds & BESSX_COX_DIAG_MARTINGALE) != 0) + (int)((kinds & BESSX_COX_DIAG_DEVIANCE) != 0) +
+         (int)((kinds & BESSX_COX_DIAG_DISPLACEMENT) != 0);
+}
+
+// doubles of device scratch of one call
+long long cox_diag_doubles(long long n, int m, long long J, unsigned kinds) {
+  const long long nb = (n + 1023) / 1024;
+  // eta / H, e -> S0, the scans' totals, res, B; e, v, g; the totals of H's scan
+  long long d = 2 * n + cox_eval_workspace(n, 1) + 2 + (long long)m + 1 + 3 * n + cox_surv_workspace(n);
+  if (m == 0) return d;
+  if ((kinds & kCoxDiagU) && J > 0) d += (long long)m * n + nb * m + cox_info_ldu(J) * m;  // W, its totals, U
+  if (kinds & kCoxDiagL) d += cox_diag_lda(n) * m + n + nb * m;                             // A / L, dh, A's totals
+  if (kinds & BESSX_COX_DIAG_DFBETA) d += cox_diag_pack_doubles(m, 0);
+  if (kinds & BESSX_COX_DIAG_DISPLACEMENT) d += cox_diag_pack_doubles(m, 1);
+  return d;
+}
+
+// what the kernels of bessx_k_coxdiag.hip need about the order on top of CoxInfoOrder
+struct CoxDiagOrder {
+  std::vector<int> evj, evrow;  // event index of a position or -1; row of an event, in position order
+};
+
+void cox_diag_order(const CoxOrder &o, const CoxInfoOrder &x, int n, CoxDiagOrder *y) {
+  y->evj.assign((size_t)n, -1);
+  y->evrow.clear();
+  for (int k = 0; k < n; k++)
+    if (o.kg[(size_t)k] != INT_MAX) {
+      y->evj[(size_t)k] = (int)y->evrow.size();
+      y->evrow.push_back(x.rowof[(size_t)k]);
+    }
+}
+
+// everything about the call that needs no device; *J = rows with status 1
+int cox_diag_check_args(const char *who, const bessx_cox_diag_input *in, const int *n_event_rows, int *J) {
+  const std::string w(who);
+  if (!in || !n_event_rows) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
+  for (int k = 0; k < in->m; k++)
+    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
+  if (in->ties != 0 && in->ties != 1) return fail(BESSX_ERR_ARG, w + ": ties must be 0 (order) or 1 (breslow)");
+  int ev = 0;
+  for (int i = 0; i < in->n; i++) {
+    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
+    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
+    ev += in->status[i] != 0.0;
+  }
+  *J = ev;
+  const unsigned kinds = in->kinds;
+  if (kinds == 0 || (kinds & ~kCoxDiagAll))
+    return fail(BESSX_ERR_ARG, w + ": kinds must be a non-empty set of BESSX_COX_DIAG_* bits");
+  if (in->m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  const long long n = in->n, m = in->m;
+  if (kinds & kCoxDiagRows) {
+    if (!in->out_rows) return fail(BESSX_ERR_ARG, w + ": a requested kind needs out_rows");
+    if (in->out_rows_ld < n) return fail(BESSX_ERR_ARG, w + ": out_rows_ld must be at least n");
+  }
+  if ((kinds & BESSX_COX_DIAG_SCORE) && m > 0) {
+    if (!in->out_score) return fail(BESSX_ERR_ARG, w + ": score needs out_score");
+    if (in->out_score_ld < n) return fail(BESSX_ERR_ARG, w + ": out_score_ld must be at least n");
+  }
+  if ((kinds & BESSX_COX_DIAG_DFBETA) && m > 0) {
+    if (!in->out_dfbeta) return fail(BESSX_ERR_ARG, w + ": dfbeta needs out_dfbeta");
+    if (in->out_dfbeta_ld < n) return fail(BESSX_ERR_ARG, w + ": out_dfbeta_ld must be at least n");
+    if (!in->cinv) return fail(BESSX_ERR_ARG, w + ": dfbeta needs cinv");
+    if (in->cinv_ld < m) return fail(BESSX_ERR_ARG, w + ": cinv_ld must be at least m");
+    for (long long j = 0; j < m; j++)
+      for (long long k = 0; k < m; k++)
+        if (!std::isfinite(in->cinv[j * in->cinv_ld + k])) return fail(BESSX_ERR_ARG, w + ": cinv must be finite");
+  }
+  if ((kinds & BESSX_COX_DIAG_DISPLACEMENT) && m > 0) {
+    if (!in->factor) return fail(BESSX_ERR_ARG, w + ": displacement needs the factor");
+    if (in->factor_ld < m) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m");
+    for (long long j = 0; j < m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  if ((kinds & BESSX_COX_DIAG_SCHOENFELD) && m > 0 && ev > 0) {
+    if (!in->out_schoenfeld) return fail(BESSX_ERR_ARG, w + ": schoenfeld needs out_schoenfeld");
+    if (in->out_schoenfeld_ld < ev) return fail(BESSX_ERR_ARG, w + ": out_schoenfeld_ld must be at least n_event_rows");
+  }
+  return 0;
+}
+
+struct CoxDiagDev {
+  CoxDev d;  // (d.first holds r(k); d.eta holds H once the likelihood has been formed; d.ex holds S0)
+  int *rowof = nullptr, *lastk = nullptr, *jptr = nullptr, *evj = nullptr, *evrow = nullptr;
+  double *e = nullptr, *v = nullptr, *g = nullptr, *hs = nullptr, *res = nullptr;
+  double *W = nullptr, *scr = nullptr, *U = nullptr, *A = nullptr, *dh = nullptr, *scrA = nullptr;
+  double *pkR = nullptr, *pkC = nullptr;
+  long long ldU = 0, ldA = 0;
+  int J = 0;
+  bool needU = false, needL = false;
+};
+
+// buffers of `sc`, uploads queued on st (the vectors of o, x and y must outlive them)
+int cox_diag_stage(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const CoxDiagOrder &y, const int *cols, int m,
+                   const double *beta, int n, int ties, unsigned kinds, hipStream_t st, CoxDiagDev *c) {
+  const size_t N = (size_t)n;
+  if (int rc = cox_eval_stage(sc, o, cols, m, beta, 1, n, 1, 0, st, &c->d)) return rc;
+  HIPX(sc.alloc(&c->res, 2));
+  c->J = x.J;
+  c->needU = m > 0 && x.J > 0 && (kinds & kCoxDiagU);
+  c->needL = m > 0 && (kinds & kCoxDiagL);
+  HIPX(sc.alloc(&c->e, N));
+  HIPX(sc.alloc(&c->v, N));
+  HIPX(sc.alloc(&c->g, N));
+  HIPX(sc.alloc(&c->hs, (size_t)cox_surv_workspace(n)));
+  if (ties) {
+    HIPX(sc.alloc(&c->lastk, N));
+    HIPX(hipMemcpyAsync(c->lastk, x.lastk.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (c->needU || c->needL) {
+    HIPX(sc.alloc(&c->rowof, N));
+    HIPX(hipMemcpyAsync(c->rowof, x.rowof.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&c->jptr, N + 1));
+    HIPX(hipMemcpyAsync(c->jptr, x.jptr.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  const size_t nb = (size_t)((n + 1023) / 1024);
+  if (c->needU) {
+    c->ldU = cox_info_ldu(x.J);
+    HIPX(sc.alloc(&c->W, (size_t)m * N));
+    HIPX(sc.alloc(&c->scr, nb * (size_t)m));
+    HIPX(sc.alloc(&c->U, (size_t)c->ldU * (size_t)m));
+    HIPX(sc.alloc(&c->evrow, (size_t)x.J));
+    HIPX(hipMemcpyAsync(c->evrow, y.evrow.data(), (size_t)x.J * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (c->needL) {
+    c->ldA = cox_diag_lda(n);
+    HIPX(sc.alloc(&c->A, (size_t)c->ldA * (size_t)m));
+    HIPX(sc.alloc(&c->dh, N));
+    HIPX(sc.alloc(&c->scrA, nb * (size_t)m));
+    HIPX(sc.alloc(&c->evj, N));
+    HIPX(hipMemcpyAsync(c->evj, y.evj.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    if (kinds & BESSX_COX_DIAG_DFBETA) HIPX(sc.alloc(&c->pkC, (size_t)cox_diag_pack_doubles(m, 0)));
+    if (kinds & BESSX_COX_DIAG_DISPLACEMENT) HIPX(sc.alloc(&c->pkR, (size_t)cox_diag_pack_doubles(m, 1)));
+  }
+  return 0;
+}
+
+// section 2h's launches up to v and g (row order), W and U -- the same launchers with the same arguments
+int cox_diag_launch_base(const void *x, int f32, long long rs, long long cs, int n, int m, int ties, const CoxDiagDev &c,
+                         hipStream_t st) {
+  const CoxDev &d = c.d;
+  HIPX(launch_cox_eval_eta(x, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
+  HIPX(hipMemcpyAsync(c.e, d.ex, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, c.res, st));
+  if (c.needU) HIPX(launch_cox_info_gather(x, f32, rs, cs, n, d.cols, m, c.rowof, c.e, c.W, st));
+  HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, c.hs, nullptr, st));  // (eta's n doubles hold H)
+  HIPX(launch_cox_info_vg(c.e, d.eta, ties ? c.lastk : nullptr, d.wd, d.pos, n, c.v, c.g, st));
+  if (c.needU) HIPX(launch_cox_info_means(c.W, d.ex, c.jptr, n, m, c.J, c.scr, c.U, c.ldU, st));
+  return 0;
+}
+
+// A, then L in place over it
+int cox_diag_launch_L(const void *x, int f32, long long rs, long long cs, int n, int m, int ties, const CoxDiagDev &c,
+                      hipStream_t st, bool form = true) {
+  const CoxDev &d = c.d;
+  HIPX(launch_cox_diag_accum(c.U, c.ldU, c.jptr, d.wd, d.ex, d.first, ties ? c.lastk : nullptr, n, m, c.dh, c.scrA, c.A,
+                             c.ldA, st));
+  if (form)
+    HIPX(launch_cox_diag_form(x, f32, rs, cs, n, d.cols, m, c.rowof, c.g, d.wd, c.e, c.evj, c.U, c.ldU, c.A, c.ldA, st));
+  return 0;
+}
+
+// sc, o, x, y, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_diag_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const CoxDiagOrder &y, std::vector<double> &pk,
+                 std::vector<double> &h, const bessx_cox_diag_input *in, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, J = x.J;
+  const unsigned kinds = in->kinds;
+  const size_t N = (size_t)n;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  CoxDiagDev c;
+  if (int rc = cox_diag_stage(sc, o, x, y, in->cols, m, in->beta, n, in->ties, kinds, st, &c)) return rc;
+  HIPX(hipMemsetAsync(c.res, 0, 2 * sizeof(double), st));
+  const int K = cox_diag_rows_count(kinds);
+  const bool w_score = m > 0 && (kinds & BESSX_COX_DIAG_SCORE), w_dfb = m > 0 && (kinds & BESSX_COX_DIAG_DFBETA);
+  const bool w_sch = m > 0 && J > 0 && (kinds & BESSX_COX_DIAG_SCHOENFELD);
+  double *rows_d = in->out_rows, *score_d = in->out_score, *dfb_d = in->out_dfbeta, *sch_d = in->out_schoenfeld;
+  long long rows_ld = in->out_rows_ld, score_ld = in->out_score_ld, dfb_ld = in->out_dfbeta_ld,
+            sch_ld = in->out_schoenfeld_ld;
+  const size_t s_rows = (size_t)K * N, s_mat = (size_t)m * N, s_sch = (size_t)m * (size_t)J;
+  size_t o_score = 0, o_dfb = 0, o_sch = 0, total = 0;
+  if (!in->out_on_device) {
+    total = s_rows;
+    o_score = total, total += w_score ? s_mat : 0;
+    o_dfb = total, total += w_dfb ? s_mat : 0;
+    o_sch = total, total += w_sch ? s_sch : 0;
+    double *stage = nullptr;
+    HIPX(sc.alloc(&stage, total > 0 ? total : 1));
+    rows_d = stage, rows_ld = n;
+    score_d = stage + o_score, score_ld = n;
+    dfb_d = stage + o_dfb, dfb_ld = n;
+    sch_d = stage + o_sch, sch_ld = J;
+  }
+  int s = 0;
+  double *mart = (kinds & BESSX_COX_DIAG_MARTINGALE) ? rows_d + (long long)(s++) * rows_ld : nullptr;
+  double *devr = (kinds & BESSX_COX_DIAG_DEVIANCE) ? rows_d + (long long)(s++) * rows_ld : nullptr;
+  double *disp = (kinds & BESSX_COX_DIAG_DISPLACEMENT) ? rows_d + (long long)(s++) * rows_ld : nullptr;
+  if (int rc = cox_diag_launch_base(in->x, f32, rs, cs, n, m, in->ties, c, st)) return rc;
+  if (mart) HIPX(hipMemcpyAsync(mart, c.g, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (devr) HIPX(launch_cox_diag_deviance(c.v, c.g, c.d.wd, c.d.pos, n, devr, st));
+  if (disp && m == 0) HIPX(hipMemsetAsync(disp, 0, N * sizeof(double), st));
+  if (c.needL) {
+    if (int rc = cox_diag_launch_L(in->x, f32, rs, cs, n, m, in->ties, c, st)) return rc;
+    if (w_score) HIPX(launch_cox_diag_perm(c.A, c.ldA, n, m, c.rowof, score_d, score_ld, st));
+    const size_t nC = w_dfb ? (size_t)cox_diag_pack_doubles(m, 0) : 0, nR = disp ? (size_t)cox_diag_pack_doubles(m, 1) : 0;
+    pk.resize(nC + nR);
+    if (w_dfb) {
+      cox_diag_pack(in->cinv, in->cinv_ld, m, 0, pk.data());
+      HIPX(hipMemcpyAsync(c.pkC, pk.data(), nC * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPX(launch_cox_diag_apply(c.A, c.ldA, n, m, c.pkC, 0, c.rowof, dfb_d, dfb_ld, st));
+    }
+    if (disp) {
+      cox_diag_pack(in->factor, in->factor_ld, m, 1, pk.data() + nC);
+      HIPX(hipMemcpyAsync(c.pkR, pk.data() + nC, nR * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPX(launch_cox_diag_apply(c.A, c.ldA, n, m, c.pkR, 1, c.rowof, disp, n, st));
+    }
+  }
+  if (w_sch)
+    HIPX(launch_cox_diag_schoenfeld(in->x, f32, rs, cs, c.d.cols, m, c.evrow, J, c.U, c.ldU, sch_d, sch_ld, st));
+  if (!in->out_on_device && total > 0) {
+    h.resize(total);
+    HIPX(hipMemcpyAsync(h.data(), rows_d, total * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device) {
+    for (int k = 0; k < K; k++)
+      std::copy(h.begin() + (size_t)k * N, h.begin() + (size_t)(k + 1) * N, in->out_rows + k * in->out_rows_ld);
+    for (size_t cc = 0; cc < (size_t)m; cc++) {
+      if (w_score)
+        std::copy(h.begin() + o_score + cc * N, h.begin() + o_score + (cc + 1) * N, in->out_score + cc * in->out_score_ld);
+      if (w_dfb)
+        std::copy(h.begin() + o_dfb + cc * N, h.begin() + o_dfb + (cc + 1) * N, in->out_dfbeta + cc * in->out_dfbeta_ld);
+      if (w_sch)
+        std::copy(h.begin() + o_sch + cc * (size_t)J, h.begin() + o_sch + (cc + 1) * (size_t)J,
+                  in->out_schoenfeld + cc * in->out_schoenfeld_ld);
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_diag_workspace(int n, int m, int n_event_rows, unsigned kinds, long long *doubles) {
+  if (!doubles) return fail(BESSX_ERR_ARG, "cox_diag_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_diag_workspace: empty matrix");
+  if (n_event_rows < 0 || n_event_rows > n)
+    return fail(BESSX_ERR_ARG, "cox_diag_workspace: n_event_rows must lie in [0, n]");
+  if (kinds == 0 || (kinds & ~kCoxDiagAll))
+    return fail(BESSX_ERR_ARG, "cox_diag_workspace: kinds must be a non-empty set of BESSX_COX_DIAG_* bits");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "cox_diag_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  *doubles = cox_diag_doubles(n, m, n_event_rows, kinds);
+  return BESSX_OK;
+}
+
+int bessx_cox_diag_device(const bessx_cox_diag_input *in, int *n_event_rows) {
+  int J = 0;
+  if (int rc = cox_diag_check_args("cox_diag_device", in, n_event_rows, &J)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("cox_diag_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->out_on_device) {
+    const unsigned kinds = in->kinds;
+    struct {
+      const char *what;
+      double *p;
+      long long ld;
+      int cols, rows;
+      bool on;
+    } outs[] = {
+        {"out_rows", in->out_rows, in->out_rows_ld, cox_diag_rows_count(kinds), in->n, (kinds & kCoxDiagRows) != 0},
+        {"out_score", in->out_score, in->out_score_ld, in->m, in->n, in->m > 0 && (kinds & BESSX_COX_DIAG_SCORE)},
+        {"out_dfbeta", in->out_dfbeta, in->out_dfbeta_ld, in->m, in->n, in->m > 0 && (kinds & BESSX_COX_DIAG_DFBETA)},
+        {"out_schoenfeld", in->out_schoenfeld, in->out_schoenfeld_ld, in->m, J,
+         in->m > 0 && J > 0 && (kinds & BESSX_COX_DIAG_SCHOENFELD)},
+    };
+    for (const auto &t : outs) {
+      if (!t.on) continue;
+      const std::string nm = std::string("cox_diag_device: ") + t.what;
+      if (int rc = check_device_matrix(nm.c_str(), t.p, BESSX_F64, t.ld, 1, t.cols, t.rows, &od)) return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, nm + " is not on the device that owns x");
+    }
+  }
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  CoxInfoOrder x;
+  cox_info_order(&o, in->n, in->m, in->ties, &x);
+  CoxDiagOrder y;
+  cox_diag_order(o, x, in->n, &y);
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> pk, h;
+    rc = cox_diag_run(sc, o, x, y, pk, h, in, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  if (!rc) {
+    *n_event_rows = x.J;
+    if (in->event_rows) std::copy(y.evrow.begin(), y.evrow.end(), in->event_rows);
+  }
+  return rc;
+}
+
+int bessx_op_cox_diag_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int ties, int repeats, double *stage_ms, double *bytes) {
+  if (!x || repeats < 1 || !stage_ms || !bytes || m < 1) return fail(BESSX_ERR_ARG, "op_cox_diag_bench: bad arguments");
+  if (int rc = predict_check_model("op_cox_diag_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (ties != 0 && ties != 1) return fail(BESSX_ERR_ARG, "op_cox_diag_bench: ties must be 0 (order) or 1 (breslow)");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_diag_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_diag_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m), time((size_t)n), status((size_t)n);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int i = 0; i < n; i++) {  // (the data of op_cox_info_bench)
+    const long long s = ((long long)i * 7919) % n;
+    time[(size_t)i] = ties ? (double)(s / 4) : (double)s + (double)i / (2.0 * n);
+    status[(size_t)i] = (double)(i % 2);
+  }
+  CoxOrder o;
+  cox_order(time.data(), status.data(), nullptr, n, &o);
+  CoxInfoOrder xo;
+  cox_info_order(&o, n, m, ties, &xo);
+  CoxDiagOrder yo;
+  cox_diag_order(o, xo, n, &yo);
+  const unsigned kinds = kCoxDiagL;
+  // a P of the library's own: the scaled identity plus a small symmetric remainder (its lower triangle serves as R)
+  const size_t M = (size_t)m;
+  std::vector<double> P(M * M), pk((size_t)(cox_diag_pack_doubles(m, 0) + cox_diag_pack_doubles(m, 1)));
+  for (size_t j = 0; j < M; j++)
+    for (size_t k = 0; k < M; k++) P[j * M + k] = (j == k ? 1.0 : 1.0 / 64.0) / std::sqrt((double)n);
+  cox_diag_pack(P.data(), (long long)M, m, 0, pk.data());
+  cox_diag_pack(P.data(), (long long)M, m, 1, pk.data() + cox_diag_pack_doubles(m, 0));
+  Owner sc;
+  CoxDiagDev c;
+  if (int rc = cox_diag_stage(sc, o, xo, yo, cols, m, B.data(), n, ties, kinds, nullptr, &c)) return rc;
+  double *out = nullptr;
+  HIPX(sc.alloc(&out, (size_t)m * (size_t)n + (size_t)n));
+  HIPX(hipMemcpy(c.pkC, pk.data(), (size_t)cox_diag_pack_doubles(m, 0) * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(c.pkR, pk.data() + cox_diag_pack_doubles(m, 0), (size_t)cox_diag_pack_doubles(m, 1) * sizeof(double),
+                 hipMemcpyHostToDevice));
+  HIPX(hipMemset(c.res, 0, 2 * sizeof(double)));
+  const int f32 = dtype == BESSX_F32;
+  if (int rc = cox_diag_launch_base(x, f32, row_stride, col_stride, n, m, ties, c, nullptr)) return rc;
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  for (int stage = 0; stage < 4; stage++) {  // (stage 1 leaves L for stages 2 and 3)
+    float total = 0.f;
+    for (int i = -1; i < repeats; i++) {  // (i = -1: the warm-up)
+      HIPX(hipEventRecord(e0, nullptr));
+      if (stage < 2) {
+        if (int rc = cox_diag_launch_L(x, f32, row_stride, col_stride, n, m, ties, c, nullptr, stage == 1)) return rc;
+      } else if (stage == 2) {
+        HIPX(launch_cox_diag_apply(c.A, c.ldA, n, m, c.pkR, 1, c.rowof, out, n, nullptr));
+      } else {
+        HIPX(launch_cox_diag_apply(c.A, c.ldA, n, m, c.pkC, 0, c.rowof, out + n, n, nullptr));
+      }
+      HIPX(hipEventRecord(e1, nullptr));
+      HIPX(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPX(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 0) total += ms;
+    }
+    stage_ms[stage] = total / repeats;
+  }
+  const double item = f32 ? 4.0 : 8.0;
+  *bytes = (double)n * m * (item + 5.0 * 8.0) + 2.0 * (double)c.J * m * 8.0;
+  return BESSX_OK;
+}
+
+}  // extern "C"

@@ -153,6 +153,34 @@ hipError_t launch_cox_info_vg(const double *e, const double *H, const int *lastk
                               long long n, double *v, double *g, hipStream_t st);
 hipError_t launch_cox_info_finish(const double *G1, const double *G2, const double *U1, int m, double *info, long long ld,
                                   double *score, double *res, hipStream_t st);
+// residuals and case influence of one Cox model (bessx_k_coxdiag.hip), on top of the arrays of bessx_k_coxinfo.hip.
+// _accum: A(c, l) = sum_{p <= l} dh_p U(jptr[p], c), m x n position-major with leading dimension ldA = cox_diag_lda(n)
+// (dh: n doubles, scr: ceil(n / 1024) * m doubles; U null: no event, A = 0).  _form: L(c, k) = g[rowof[k]] x(rowof[k],
+// cols[c]) - wd[k] U(evj[k], c) + e[k] A(c, k) in place over A (evj[k] < 0: no event at k).  _apply: L P^T on the fp64
+// matrix cores from pk = cox_diag_pack(P): tri: out[rowof[k]] = sum_j (P L_k)_j^2 with P lower triangular, else
+// out[j * ldo + rowof[k]] = (P L_k)_j.  _deviance: the deviance residuals in row order from v, g (row order) and wd
+// (position order).  _perm: out[c * ldo + rowof[k]] = L(c, k).  _schoenfeld: out[c * ldo + j] = x(evrow[j], cols[c]) -
+// U(j, c).  cox_diag_pack runs on the host.  Everything else is device memory.
+long long cox_diag_lda(long long n);
+int cox_diag_dot_depth(int m);
+int cox_diag_sum_depth(int m);
+long long cox_diag_pack_doubles(int m, int tri);
+void cox_diag_pack(const double *P, long long ld, int m, int tri, double *pk);
+hipError_t launch_cox_diag_accum(const double *U, long long ldU, const int *jptr, const double *wd, const double *S0,
+                                 const int *first, const int *lastk, long long n, int m, double *dh, double *scr,
+                                 double *A, long long ldA, hipStream_t st);
+hipError_t launch_cox_diag_form(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                                const int *rowof, const double *g, const double *wd, const double *e, const int *evj,
+                                const double *U, long long ldU, double *A, long long ldA, hipStream_t st);
+hipError_t launch_cox_diag_apply(const double *L, long long ldL, long long n, int m, const double *pk, int tri,
+                                 const int *rowof, double *out, long long ldo, hipStream_t st);
+hipError_t launch_cox_diag_deviance(const double *v, const double *g, const double *wd, const int *pos, long long n,
+                                    double *out, hipStream_t st);
+hipError_t launch_cox_diag_perm(const double *L, long long ldL, long long n, int m, const int *rowof, double *out,
+                                long long ldo, hipStream_t st);
+hipError_t launch_cox_diag_schoenfeld(const void *src, int f32, long long rs, long long cs, const int *cols, int m,
+                                      const int *evrow, int J, const double *U, long long ldU, double *out,
+                                      long long ldo, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

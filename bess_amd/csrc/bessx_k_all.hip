@@ -10,6 +10,7 @@
 #include "bessx_k_info.hip"
 #include "bessx_k_diag.hip"
 #include "bessx_k_coxinfo.hip"
+#include "bessx_k_coxdiag.hip"
 #include "bessx_k_solve.hip"
 #include "bessx_k_glm.hip"
 #include "bessx_k_cox.hip"

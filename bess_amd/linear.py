@@ -734,6 +734,151 @@ class bess_base:
         out.update(cols=cols, loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
         return out
 
+    # ---- Cox: residuals, dfbeta and case influence -------------------------------------------------------------------
+    @staticmethod
+    def _cox_diagnostics_host(Xs, beta, time, status, w, ties, R, C, kinds):
+        """cox_diagnostics_device's quantities in fp64 NumPy, by the same decomposition (running sums, not the O(n^2)
+        definition): Xs (n, m) the support's columns, beta (m,), time, status, w (n,) in row order, R (m, m) lower
+        triangular and C (m, m) as capi.cox_diagnostics_device takes them (needed by their kinds only)."""
+        n, m = Xs.shape
+        eta = np.zeros(n)
+        for c in range(m):  # (column by column: a row's sum does not depend on where the row lies)
+            eta += Xs[:, c] * beta[c]
+        order = np.argsort(time, kind="stable")
+        x, eta, t, d = Xs[order], eta[order], time[order], status[order]
+        wd = w[order] * d
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        starts = np.nonzero(new)[0]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        last = np.append(starts[1:] - 1, n - 1)[np.cumsum(new) - 1]
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))  # (comparisons: a NaN stays a NaN)
+        e = np.exp(a)
+        breslow = ties == "breslow"
+        r = first if breslow else np.arange(n)
+        S0 = np.cumsum(e[::-1])[::-1][r]
+        h = wd / S0
+        H = np.cumsum(h)
+        if breslow:
+            H = H[last]
+        v = e * H
+        g = wd - v
+        ev = d != 0
+
+        def rows(z):  # position order -> row order
+            out = np.empty_like(z)
+            out[order] = z
+            return out
+
+        out = {"event_rows": order[ev].astype(np.int32), "event_times": t[ev]}
+        if "martingale" in kinds:
+            out["martingale"] = rows(g)
+        if "deviance" in kinds:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                dd = (v - wd) + np.where(wd == 0, 0.0, wd * np.log(np.where(wd == 0, 1.0, wd) / np.where(wd == 0, 1.0, v)))
+            out["deviance"] = rows(np.sign(g) * np.sqrt(2.0 * np.where(dd < 0, 0.0, dd)))
+        if m == 0:
+            if "displacement" in kinds:
+                out["displacement"] = np.zeros(n)
+            for k in ("score", "dfbeta"):
+                if k in kinds:
+                    out[k] = np.zeros((n, 0))
+            if "schoenfeld" in kinds:
+                out["schoenfeld"] = np.zeros((int(ev.sum()), 0))
+            return out
+        u = np.cumsum((e[:, None] * x)[::-1], axis=0)[::-1][r] / S0[:, None]
+        if "schoenfeld" in kinds:
+            out["schoenfeld"] = x[ev] - u[ev]
+        if any(k in kinds for k in ("score", "dfbeta", "displacement")):
+            if breslow:
+                dh = np.zeros(n)
+                dh[starts] = np.add.reduceat(h, starts)
+                has = np.zeros(n, dtype=bool)
+                has[starts] = np.maximum.reduceat(d, starts) > 0
+            else:
+                dh, has = h, ev
+            with np.errstate(invalid="ignore"):
+                A = np.cumsum(np.where(has[:, None], dh[:, None] * u, 0.0), axis=0)
+                L = (g[:, None] * x - np.where(ev[:, None], wd[:, None] * u, 0.0)) + e[:, None] * A
+            if "score" in kinds:
+                out["score"] = rows(L)
+            if "dfbeta" in kinds:
+                T = np.zeros((n, m))
+                for c in range(m):
+                    T = T + L[:, c, None] * C[c][None, :]
+                out["dfbeta"] = rows(T)
+            if "displacement" in kinds:
+                s2 = np.zeros(n)
+                for j in range(m):
+                    tj = np.zeros(n)
+                    for k in range(j + 1):
+                        tj = tj + R[j, k] * L[:, k]
+                    s2 = s2 + tj * tj
+                out["displacement"] = rows(s2)
+        return out
+
+    def diagnostics_survival(self, X, y, weight=None, ties="order", kinds=None):
+        """Cox only: which subjects the model fits badly and which move a coefficient, on the rows (X, y).  A dict with
+        the kinds asked for (None: all of capi.COX_DIAG_KINDS, as capi.cox_diagnostics_device defines them) --
+        martingale, deviance and displacement (n,), score and dfbeta (n, m) in row order, schoenfeld (J, m) for the J
+        rows with status 1 in time order -- plus cols, event_rows and event_times (the row and time of every schoenfeld
+        row), positive_definite, loglik and residual_sum.  y: (n, 2) time and status as in fit; weight: n values or
+        None (on the event terms only); ties: "order" or "breslow".  dfbeta = score @ inv(info) approximates the change
+        in beta when a row is dropped; displacement = score_k^T inv(info) score_k is the likelihood displacement, Cox's
+        counterpart of Cook's distance.  An X in GPU memory is read in place on torch's current stream -- the
+        information by capi.cox_information_device, its factor by capi.info_factor on the host, the rows by
+        capi.cox_diagnostics_device -- and the results are tensors on X's device; a NumPy X is served in fp64 NumPy
+        with the same decomposition.  When the information is not positive definite dfbeta and displacement are filled
+        with NaN, the other kinds are still computed and nothing is raised.  diagnostics() stays None for the Cox
+        classes."""
+        if self.model_type_int != 4:
+            raise ValueError("diagnostics_survival is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        _, kinds = capi._cox_diag_mask(capi.COX_DIAG_KINDS if kinds is None else kinds)
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        m = cols.size
+        wt = None if weight is None else w
+        if on_device:
+            st = _current_stream(X)
+            got = capi.cox_information_device(X, cols, beta[cols], time, status, weight=wt, ties=ties, stream=st)
+        else:
+            Xs = np.asarray(X, dtype=np.float64)[:, cols]
+            got = self._cox_information_host(Xs, beta[cols], time, status, w, ties)
+        if m > 0:
+            R, pd = capi.info_factor(got["info"])
+        else:
+            R, pd = np.zeros((0, 0)), True
+        C = R.T @ R
+        need = [k for k in kinds if k in ("dfbeta", "displacement")]
+        ask = kinds if pd else tuple(k for k in kinds if k not in need)
+        out = {}
+        if on_device:
+            if ask:
+                out = capi.cox_diagnostics_device(X, cols, beta[cols], time, status, factor=R if pd else None,
+                                                  cinv=C if pd else None, weight=wt, ties=ties, kinds=ask, stream=st)
+            else:
+                ev = np.argsort(time, kind="stable")
+                ev = ev[status[ev] != 0].astype(np.int32)
+                out = {"event_rows": ev, "event_times": time[ev]}
+        else:
+            out = self._cox_diagnostics_host(Xs, beta[cols], time, status, w, ties, R, C, ask)
+        if not pd:
+            torch = sys.modules.get("torch")
+            for k in need:
+                shape = (n,) if k == "displacement" else (n, m)
+                if on_device and torch is not None and isinstance(X, torch.Tensor):
+                    out[k] = torch.full(shape, float("nan"), dtype=torch.float64, device=X.device)
+                else:
+                    out[k] = np.full(shape, np.nan)
+        res = {k: out[k] for k in kinds}
+        res.update(cols=cols, event_rows=out["event_rows"], event_times=out["event_times"], positive_definite=bool(pd),
+                   loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
+        return res
+
     # ---- Cox: baseline hazard and survival curves ------------------------------------------------------------------
     def _support_eta(self, X, cols, beta):
         """X[:, cols] @ beta[cols] for a NumPy X, column by column: a row's sum does not depend on where the row lies."""

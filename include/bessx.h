@@ -591,6 +591,86 @@ typedef struct {
 } bessx_diag_input;
 int bessx_diag_device(const bessx_diag_input *in);
 int bessx_diag_workspace(int n, int m, unsigned kinds, long long *doubles);
+/* ---------------------------------------------------------------------------------------
+ * 2j. Residuals, dfbeta and case influence of ONE Cox model on an X already in GPU memory (bessx_k_coxdiag.hip): the Cox
+ *     counterpart of section 2i.  Stateless like sections 2c to 2i.  x, n, p, cols, m, beta, time, status, weight, ties,
+ *     stream and the notation (positions k, r(k), e, wd, S0, u_k, H, v, g): section 2h.  Weights act on the event terms
+ *     only.  With dh_p = sum_{k : r(k) = p} wd_k / S0(p), the hazard increment at position p, and the m-vector
+ *     A_l = sum_{p <= l} dh_p u_p (a forward prefix sum of a quantity that comes from the suffix scan), one bit of
+ *     `kinds` per kind:
+ *         BESSX_COX_DIAG_MARTINGALE    g_k = wd_k - v_k                                                          n
+ *         BESSX_COX_DIAG_DEVIANCE      sign(g_k) sqrt(2 max(v_k - wd_k + wd_k log(wd_k / v_k), 0))               n
+ *                                      (0 log 0 = 0, sign(0) = 0)
+ *         BESSX_COX_DIAG_SCORE         L_k = g_k x_k - wd_k u_{r(k)} + e_k A_k                                   n x m
+ *                                      = wd_k (x_k - u_k) - e_k sum_{j : r(j) <= k} (wd_j / S0(j)) (x_k - u_j); its
+ *                                      column sums are section 2h's score
+ *         BESSX_COX_DIAG_DFBETA        L_k C,  C = cinv = inverse(info), symmetric                               n x m
+ *         BESSX_COX_DIAG_DISPLACEMENT  L_k^T C L_k = sum_j t_kj^2,  t_k = R L_k,  R = factor, C = R^T R          n
+ *         BESSX_COX_DIAG_SCHOENFELD    x_{k_j} - u_{k_j} for the J rows with status = 1, in POSITION order       J x m
+ *     Results are in ROW order except schoenfeld.  factor (lower triangular, its strict upper triangle is never read) and
+ *     cinv are m x m in HOST memory, entry (j, k) at [j * ld + k], ld >= m; each is needed only by its kind.
+ *     out_rows receives the requested n-vector kinds (martingale, deviance, displacement) in ascending bit order, slot
+ *     s at out_rows + s * out_rows_ld, ld >= n; out_score and out_dfbeta hold column c at + c * ld, ld >= n;
+ *     out_schoenfeld holds column c at + c * ld, ld >= J.  They are device memory of x's device when out_on_device != 0
+ *     (checked as in section 2c), else host memory.  event_rows (HOST memory, J ints, may be null) receives the row of
+ *     every schoenfeld row; *n_event_rows = J.  J is the number of rows with status = 1, which the caller counts to
+ *     size out_schoenfeld.
+ *     Apart from the clamp of eta and the max(., 0) of the deviance there is no clamp; a NaN inside the support view
+ *     propagates by IEEE rules.  m = 0 is valid: martingale and deviance are the null model's, displacement is 0, the
+ *     matrix kinds are empty and nothing of x is read.  J = 0 is valid: v = g = 0, L = 0, schoenfeld has no rows.
+ *     The predictor pass, S0, H, W = e x, the means U, v and g are section 2h's launches as they are.  New: the
+ *     increments dh_p u_p and their forward scan per column (two launches, additions only, fixed order), L formed in
+ *     place over A from the exact elements of x (the third pass over the support of x: predictor, the gather of W, this
+ *     one; schoenfeld reads the J event rows once more), and L P^T in 16 x 16 tiles on the fp64 matrix cores with P = R
+ *     (only the k-steps at or below each tile's diagonal, squares added per row in a fixed order) or P = C (every
+ *     k-step, tiles stored).  No n x m intermediate besides W and A / L, no floating-point atomics: the same call
+ *     gives the same bits, and a row's dfbeta and displacement depend on that row's L and P alone.
+ *     Scratch memory (bessx_cox_diag_workspace; no device needed): about (2 m + 6) n + J m doubles when score, dfbeta,
+ *     displacement or schoenfeld is asked for, n-vectors only when just martingale / deviance are (then no gather, no
+ *     U and no A are formed); released before the call returns: counters 38 / 39 are back at their earlier values.
+ *     m + 1 <= 1024 as in section 2h: a larger m is BESSX_ERR_UNSUPPORTED.  Every argument error is found before any
+ *     device call (BESSX_ERR_ARG: the messages of sections 2e / 2g / 2h; kinds zero or with unknown bits; a requested
+ *     kind whose output, factor or cinv pointer is null; a non-finite entry in the read part of factor / cinv).
+ * ------------------------------------------------------------------------------------- */
+enum {
+  BESSX_COX_DIAG_MARTINGALE = 1,
+  BESSX_COX_DIAG_DEVIANCE = 2,
+  BESSX_COX_DIAG_SCORE = 4,
+  BESSX_COX_DIAG_DFBETA = 8,
+  BESSX_COX_DIAG_DISPLACEMENT = 16,
+  BESSX_COX_DIAG_SCHOENFELD = 32
+};
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  const double *factor;
+  long long factor_ld;
+  const double *cinv;
+  long long cinv_ld;
+  unsigned kinds;
+  double *out_rows;
+  long long out_rows_ld;
+  double *out_score;
+  long long out_score_ld;
+  double *out_dfbeta;
+  long long out_dfbeta_ld;
+  double *out_schoenfeld;
+  long long out_schoenfeld_ld;
+  int *event_rows;
+  int out_on_device;
+  void *stream;
+} bessx_cox_diag_input;
+int bessx_cox_diag_device(const bessx_cox_diag_input *in, int *n_event_rows);
+int bessx_cox_diag_workspace(int n, int m, int n_event_rows, unsigned kinds, long long *doubles);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -983,6 +1063,11 @@ int bessx_op_diag_bench(const void *x, int dtype, long long row_stride, long lon
  * (predictor pass, S0, loglik, gather, H, v and g, the sweep over x, the means, the sweep over U, the finish).
  * *bytes = what stages 0 and 1 must move: n m (item + 8) + n m 8 + J m 8.  m >= 1. */
 int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int ties, int repeats, double *stage_ms, double *bytes);
+/* The new kernels of section 2j timed the same way on the same data, with a P of the library's own: stage_ms[0] the
+ * increments and their forward scan (A), [1] A and the forming of L over it, [2] L R^T with the displacement epilogue,
+ * [3] L C with the dfbeta epilogue.  *bytes = what stages 1 to 3 must move: n m (item + 5 * 8) + 2 J m 8.  m >= 1. */
+int bessx_op_cox_diag_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int ties, int repeats, double *stage_ms, double *bytes);
 
 /* ---------------------------------------------------------------------------------------
