@@ -44,6 +44,7 @@ SYMBOLS = [
     "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
     "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
     "bessx_cox_diag_device", "bessx_cox_diag_workspace", "bessx_op_cox_diag_bench",
+    "bessx_meat_device", "bessx_sandwich_device", "bessx_sandwich_workspace", "bessx_op_sandwich_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -138,6 +139,28 @@ class CoxDiagInput(ctypes.Structure):
                 ("out_rows", _vp), ("out_rows_ld", _ll), ("out_score", _vp), ("out_score_ld", _ll),
                 ("out_dfbeta", _vp), ("out_dfbeta_ld", _ll), ("out_schoenfeld", _vp), ("out_schoenfeld_ld", _ll),
                 ("event_rows", _I), ("out_on_device", _i), ("stream", _vp)]
+
+
+class MeatInput(ctypes.Structure):
+    """bessx_meat_input: a source matrix in GPU memory, the support, an optional row scalar u and optional cluster
+    labels in host or GPU memory, where the meat and the sum vector go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("intercept", _i), ("u_host", _D), ("u_dev", _vp),
+                ("cluster_host", ctypes.POINTER(_ll)), ("cluster_dev", _vp), ("cluster_dtype", _i),
+                ("cluster_stride", _ll), ("meat", _vp), ("meat_ld", _ll), ("sums", _vp), ("out_on_device", _i),
+                ("stream", _vp)]
+
+
+class SandwichInput(ctypes.Structure):
+    """bessx_sandwich_input: bessx_info_input plus the kind HC0 .. HC3, the factor of the inverse information in host
+    memory, optional cluster labels in host or GPU memory and where the meat goes."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("coef0", _d), ("link", _i), ("y_host", _D), ("y_dev", _vp),
+                ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
+                ("weight_stride", _ll), ("kind", _i), ("factor", _D), ("factor_ld", _ll),
+                ("cluster_host", ctypes.POINTER(_ll)), ("cluster_dev", _vp), ("cluster_dtype", _i),
+                ("cluster_stride", _ll), ("info", _vp), ("info_ld", _ll), ("score", _vp), ("meat", _vp),
+                ("meat_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -276,6 +299,11 @@ def lib():
         L.bessx_cox_diag_device.argtypes = [ctypes.POINTER(CoxDiagInput), _I]
         L.bessx_cox_diag_workspace.argtypes = [_i, _i, _i, ctypes.c_uint, ctypes.POINTER(_ll)]
         L.bessx_op_cox_diag_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _D, _D]
+        L.bessx_meat_device.argtypes = [ctypes.POINTER(MeatInput), _I]
+        L.bessx_sandwich_device.argtypes = [ctypes.POINTER(SandwichInput), _D, _D, _I]
+        L.bessx_sandwich_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_ll),
+                                               ctypes.POINTER(_ll), _I, ctypes.POINTER(_ll), _I, _I, _I]
+        L.bessx_op_sandwich_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, ctypes.POINTER(_ll), _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1632,6 +1660,302 @@ def op_diag_bench(x, cols, repeats=20):
 
 
 TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties
+
+
+COV_TYPES = ("HC0", "HC1", "HC2", "HC3")  # BESSX_HC0 .. BESSX_HC3
+SANDWICH_RUN = 64  # rows per run of a cluster's sum (SW_RUN of bessx_k_sandwich.hip)
+
+
+def _cov_kind(kind):
+    if kind not in COV_TYPES:
+        raise ValueError("kind must be one of %s, got %r" % (list(COV_TYPES), kind))
+    return COV_TYPES.index(kind)
+
+
+def cluster_labels(cluster, n):
+    """Cluster labels as the library takes them, checked without a device call: (host int64 array or None, device
+    pointer or None, BESSX_I64 / BESSX_I32, element stride, the object to keep alive).  cluster: n integer labels, a host
+    array or a device array (__cuda_array_interface__) of int64 or int32; any values, any order."""
+    if is_device_array(cluster):
+        cai = cluster.__cuda_array_interface__
+        shape = tuple(int(v) for v in cai["shape"])
+        typestr = cai["typestr"]
+        if typestr not in ("<i8", "<i4"):
+            raise ValueError("cluster: a device array must be int64 or int32 (typestr '<i8' or '<i4'), got %r" % typestr)
+        item = 8 if typestr == "<i8" else 4
+        size = int(np.prod(shape)) if shape else 1
+        if size != n:
+            raise ValueError("X.shape(0) should be equal to cluster.size")
+        if len([v for v in shape if v != 1]) > 1:
+            raise ValueError("cluster: expected a vector, got shape %s" % (shape,))
+        strides = cai.get("strides")
+        stride = 1
+        if strides is not None:
+            big = [int(st) for v, st in zip(shape, strides) if v != 1]
+            stride = big[0] // item if big else 1
+            if big and (big[0] < 0 or big[0] % item):
+                raise ValueError("cluster: byte strides of a device array must be non-negative multiples of the item size")
+        ptr = int(cai["data"][0])
+        if not ptr:
+            raise ValueError("cluster: null device pointer")
+        return None, ptr, 0 if item == 8 else 1, stride, cluster
+    a = np.asarray(cluster)
+    if a.dtype.kind not in "iu":
+        raise ValueError("cluster must hold integer labels, got dtype %s" % a.dtype)
+    if a.dtype.kind == "u" and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError("cluster labels must fit int64")
+    a = np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
+    if a.size != n:
+        raise ValueError("X.shape(0) should be equal to cluster.size")
+    return a, None, 0, 1, a
+
+
+def _set_cluster(a, cluster, n, keep):
+    if cluster is None:
+        return
+    host, ptr, dt, stride, obj = cluster_labels(cluster, n)
+    keep.append(obj)
+    if host is not None:
+        a.cluster_host = host.ctypes.data_as(ctypes.POINTER(_ll))
+    else:
+        a.cluster_dev, a.cluster_dtype, a.cluster_stride = ptr, dt, stride
+
+
+def sandwich_workspace(n, m, link="identity", weighted=False, kind="HC0", n_clusters=0, max_cluster_rows=0,
+                       dtype=np.float64, row_stride=None, col_stride=1):
+    """What a sandwich_device call on n rows with a support of m columns needs and how it adds, without a device
+    (bessx_sandwich_workspace): a dict with
+        doubles                 device scratch in doubles (an upper bound for n_clusters clusters the longest of which has
+                                max_cluster_rows rows; n_clusters = 0: no cluster labels)
+        rows_per_slab, slabs    the row split of the Gram sweeps over x (information_device's for (n, m))
+        cluster_rows_per_slab, cluster_slabs   the split of the sweep over the n_clusters rows of S (0, 0 without labels)
+        sum_depth               additions behind an entry of s_g for a cluster of max_cluster_rows rows: a chain of
+                                min(r, 64) FMAs in row order, then the ceil(r / 64) runs in run order
+        sq_depth                additions behind meat[0, 0] = sum_g s_g0^2 with labels: ceil(G / 256) + 8."""
+    nd, rps, sl, crps, csl, sd, qd = _ll(0), _ll(0), _i(0), _ll(0), _i(0), _i(0), _i(0)
+    rs = int(row_stride) if row_stride is not None else max(int(m), 1)
+    _check(lib().bessx_sandwich_workspace(1 if np.dtype(dtype) == np.float32 else 0, rs, int(col_stride), int(n), int(m),
+                                          LINKS[link], int(bool(weighted)), _cov_kind(kind), int(n_clusters),
+                                          int(max_cluster_rows), ctypes.byref(nd), ctypes.byref(rps), ctypes.byref(sl),
+                                          ctypes.byref(crps), ctypes.byref(csl), ctypes.byref(sd), ctypes.byref(qd)))
+    return {"doubles": nd.value, "rows_per_slab": rps.value, "slabs": sl.value, "cluster_rows_per_slab": crps.value,
+            "cluster_slabs": csl.value, "sum_depth": sd.value, "sq_depth": qd.value}
+
+
+def meat_device(x, cols, u=None, cluster=None, intercept=True, stream=0):
+    """The meat of a sandwich covariance from a device matrix x (n x p: float64 or float32, any non-negative strides),
+    read where it lies (bessx_meat_device).  With z_i = (1, x[i, cols]) (intercept=True) or x[i, cols] (intercept=False,
+    a dense source such as the Cox score residuals L; len(cols) >= 1), M entries, and a row scalar u (n float64 values,
+    host or device with unit stride; None = ones):
+        without cluster   meat = sum_i u_i^2 z_i z_i^T,            sums = sum_i u_i z_i
+        with cluster      meat = sum_g s_g s_g^T,  s_g = sum_{i in g} u_i z_i,   sums = sum_g s_g
+    cluster: n integer labels (any values, any order; a host array, or a device array of int64 / int32 that is copied
+    to the host).  Returns {"meat" (M, M) with both triangles exact mirrors, "sums" (M,), "n_clusters": G or None}.  The
+    rows are sorted by label on the host (stable); s_g is formed by one kernel from x in place -- a cluster of r rows
+    is min(r, 64) + ceil(r / 64) - 1 additions in an order that depends on r alone, so its bits depend on the cluster's
+    rows in their original order and on u, not on the layout of x or the other clusters -- and the meat is the
+    matrix-core Gram sweep of information_device over the G x M sums (without cluster and with the intercept: over x in
+    place, with u^2 as the working weight; without cluster and without the intercept the sweep runs over x in place
+    as well, and only with a u is every row its own cluster, an n x M copy).
+    No floating-point atomics: the same call gives the same bits.  A NaN inside the support view propagates, nothing
+    outside it is read.  len(cols) + intercept <= 1024.  stream: raw handle of the stream x (and u) were produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    cols, _, _ = _predict_model(dx, cols)
+    icpt = 1 if intercept else 0
+    M = cols.size + icpt
+    if M < 1:
+        raise ValueError("an empty support needs intercept=True")
+    a = MeatInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.intercept = _ip(cols), cols.size, icpt
+    keep = [dx, cols]
+    if u is not None:
+        if is_device_array(u):
+            du = _DeviceArray(u, "u")
+            if du.size != n:
+                raise ValueError("X.shape(0) should be equal to u.size")
+            if du.item != 8 or (n > 1 and du.as_vector("u") != 1):
+                raise ValueError("u: a device array of float64 with unit stride is needed")
+            a.u_dev = du.ptr
+            keep.append(du)
+        else:
+            uh = _f64(u).reshape(-1)
+            if uh.size != n:
+                raise ValueError("X.shape(0) should be equal to u.size")
+            a.u_host = _dp(uh)
+            keep.append(uh)
+    _set_cluster(a, cluster, n, keep)
+    meat, sums = np.empty((M, M)), np.empty(M)
+    a.meat, a.meat_ld, a.sums, a.out_on_device = meat.ctypes.data, M, sums.ctypes.data, 0
+    a.stream = int(stream) if stream else None
+    G = _i(0)
+    _check(lib().bessx_meat_device(ctypes.byref(a), ctypes.byref(G)))
+    return {"meat": meat, "sums": sums, "n_clusters": G.value if cluster is not None else None}
+
+
+def sandwich_device(x, cols, beta, coef0, y, link="identity", weight=None, kind="HC0", factor=None, cluster=None,
+                    stream=0):
+    """Information, score and the meat of the robust (Huber-White) or cluster-robust covariance of ONE model on a device
+    matrix x, read where it lies, in one call (bessx_sandwich_device).  Notation of information_device: z_i = (1,
+    x[i, cols]), M = len(cols) + 1, v_i and g_i the working and score weights of the link, info = sum_i v_i z_i z_i^T.
+    With weights g_i = w_i (y_i - mu_i), so the meat carries w_i^2: the estimating-function convention.
+        row scalar   "HC0", "HC1": u_i = g_i;  "HC2": u_i = g_i / sqrt(1 - h_i);  "HC3": u_i = g_i / (1 - h_i), with h_i
+                     diagnostics_device's leverage from the same factor R (info_factor(info)[0]; needed by HC2 / HC3
+                     only).  No clamp: h_i = 1 gives what IEEE arithmetic gives.
+        meat         B = sum_i u_i^2 z_i z_i^T without cluster;  B = sum_g s_g s_g^T, s_g = sum_{i in g} u_i z_i with
+                     cluster (n integer labels, any values, any order, host or device).  (M, M), exact mirrors.
+    The covariance c * inv(info) B inv(info) and its scale factor c are sandwich_table's; "HC0" and "HC1" give the same
+    meat.  cluster with "HC2" / "HC3" raises ValueError (the block-leverage corrections are not built).  Returns {"info",
+    "score", "loss", "sum_w"} -- information_device's for the same arguments, bit for bit -- plus "meat" and
+    "n_clusters" (G, or None without cluster).  A row or a cluster of weight 0 counts as a row / a cluster.  No gathered
+    copy of x[:, cols] and no n x M score matrix: the scratch is n-vectors, the Gram partials and G * M doubles of
+    cluster sums.  The same call gives the same bits, and with cluster the meat is the same bits under every layout of
+    the same x.  A NaN inside the support view propagates.  len(cols) + 1 <= 1024."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    k = _cov_kind(kind)
+    if cluster is not None and k >= 2:
+        raise ValueError("cluster goes with kind 'HC0' (CR0) or 'HC1' (CR1), got %r" % kind)
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: sandwich_device takes one model per call")
+    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
+    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
+        raise ValueError("beta and coef0 must be finite")
+    M = cols.size + 1
+    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
+    a = SandwichInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
+    a.y_stride = yrs
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [weight]
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_host = _dp(wh)
+            keep.append(wh)
+    a.kind = k
+    if k >= 2:
+        if factor is None:
+            raise ValueError("kind %r needs the factor (info_factor)" % kind)
+        fh = _f64(factor)
+        if fh.shape != (M, M):
+            raise ValueError("factor must have shape (%d, %d), got %s" % (M, M, fh.shape))
+        if not np.isfinite(np.tril(fh)).all():
+            raise ValueError("the lower triangle of the factor must be finite")
+        a.factor, a.factor_ld = _dp(fh), M
+        keep.append(fh)
+    _set_cluster(a, cluster, n, keep)
+    info, score, meat = np.empty((M, M)), np.empty(M), np.empty((M, M))
+    a.info, a.info_ld, a.score, a.meat, a.meat_ld = info.ctypes.data, M, score.ctypes.data, meat.ctypes.data, M
+    a.out_on_device = 0
+    a.stream = int(stream) if stream else None
+    loss, sw, G = _d(0), _d(0), _i(0)
+    _check(lib().bessx_sandwich_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw), ctypes.byref(G)))
+    return {"info": info, "score": score, "loss": loss.value, "sum_w": sw.value, "meat": meat,
+            "n_clusters": G.value if cluster is not None else None}
+
+
+def op_sandwich_bench(x, cols, cluster, repeats=20):
+    """(ms per launch, bytes the algorithm needs: the support and u once, S once) of the cluster-sum kernel alone (and the addition of the partials of
+    clusters longer than a run) on the device matrix x for the intercept and the support cols and n host labels,
+    device events."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    lab, _, _, _, _ = cluster_labels(np.asarray(cluster), dx.shape[0])
+    ms, by = _d(0), _d(0)
+    _check(lib().bessx_op_sandwich_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, lab.ctypes.data_as(ctypes.POINTER(_ll)), repeats,
+                                         ctypes.byref(ms), ctypes.byref(by)))
+    return ms.value, by.value
+
+
+def _sandwich(info, meat, score, coef, scale, cov_type, n_clusters, dof):
+    """_wald's table with cov = scale * inv(info) meat inv(info), inv(info) = R^T R from info_factor."""
+    import math
+    coef = np.asarray(coef, dtype=np.float64).reshape(-1)
+    M = coef.size
+    meat = np.array(meat, dtype=np.float64)
+    if meat.shape != (M, M):
+        raise ValueError("meat must be (%d, %d), got %s" % (M, M, meat.shape))
+    out = _wald(info, score, coef, 1.0, dof)  # (shapes, the NaN table, cond and positive_definite)
+    out.update(cov_type=cov_type, n_clusters=n_clusters, scale=scale, meat=meat)
+    if not out["positive_definite"]:
+        return out
+    R, _ = info_factor(info)
+    A = R.T @ R
+    cov = scale * (A @ meat @ A)
+    cov = 0.5 * (cov + cov.T)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        se = np.sqrt(np.diag(cov))
+        z = coef / se
+    pv = np.array([math.erfc(abs(v) / math.sqrt(2.0)) if v == v else float("nan") for v in z])
+    out.update(cov=cov, se=se, z=z, p_value=pv)
+    return out
+
+
+def sandwich_table(info, meat, score, coef, kind, n, n_clusters=None):
+    """The coefficient table with a robust covariance, on the host in fp64 NumPy: wald_table's dict with
+        cov = c * inv(info) meat inv(info)        (formed as (R^T R) meat (R^T R), R = info_factor(info)[0])
+    and se, z, p_value from it; no dispersion factor, for the identity link too (dispersion = 1).  info, meat (M, M),
+    score, coef (M,) as sandwich_device orders them (intercept first); n: the number of rows passed; n_clusters: G, the
+    number of distinct labels, or None without clusters.  The scale factor c:
+        "HC0", "HC2", "HC3"          c = 1
+        "HC1", no clusters           c = n / (n - M)
+        "HC0" with clusters (CR0)    c = 1
+        "HC1" with clusters (CR1)    c = G / (G - 1) * (n - 1) / (n - M)
+    Rows and clusters of weight 0 count in n and G.  A non-positive denominator (n <= M, G = 1) gives c = NaN and a NaN
+    table; nothing is raised.  Adds cov_type, n_clusters, scale (= c) and meat; dof = n - M.  The NaN /
+    positive_definite rules are wald_table's: an info that is not positive definite gives NaN tables and
+    positive_definite = False.  n_clusters with "HC2" / "HC3" raises ValueError."""
+    k = _cov_kind(kind)
+    M = np.asarray(coef, dtype=np.float64).size
+    n = int(n)
+    if n_clusters is not None and k >= 2:
+        raise ValueError("clusters go with kind 'HC0' (CR0) or 'HC1' (CR1), got %r" % kind)
+    c = 1.0
+    if k == 1:
+        if n_clusters is None:
+            c = n / (n - M) if n - M > 0 else float("nan")
+        else:
+            G = int(n_clusters)
+            c = (G / (G - 1)) * ((n - 1) / (n - M)) if (G - 1 > 0 and n - M > 0) else float("nan")
+    return _sandwich(info, meat, score, coef, c, kind, None if n_clusters is None else int(n_clusters), float(n - M))
+
+
+def cox_sandwich_table(info, meat, score, coef, kind, n_clusters=None):
+    """sandwich_table for a Cox model (Lin-Wei): info, meat (m, m), score, coef (m,) as cox_information_device orders
+    them (no intercept), meat = sum_k L_k L_k^T or sum_g s_g s_g^T, s_g = sum_{k in g} L_k, from the score residuals L
+    of cox_diagnostics_device (meat_device(L, iota, intercept=False)).  cov = c * inv(info) meat inv(info) with c = 1
+    for "HC0" and c = G / (G - 1) for "HC1" with clusters (NaN for G = 1); "HC1" without clusters and "HC2" / "HC3"
+    raise ValueError.  dispersion = 1 and dof = NaN (the events are not passed); an empty model gives empty arrays."""
+    k = _cov_kind(kind)
+    if k >= 2 or (k == 1 and n_clusters is None):
+        raise ValueError("a Cox model takes kind 'HC0', or 'HC1' with clusters, got %r" % kind)
+    m = np.asarray(coef, dtype=np.float64).size
+    G = None if n_clusters is None else int(n_clusters)
+    c = 1.0
+    if k == 1:
+        c = G / (G - 1) if G - 1 > 0 else float("nan")
+    if m == 0:
+        z = np.zeros(0)
+        return {"coef": z, "se": z.copy(), "z": z.copy(), "p_value": z.copy(), "cov": np.zeros((0, 0)), "score": z.copy(),
+                "dispersion": 1.0, "dof": float("nan"), "cond": float("nan"), "positive_definite": True,
+                "cov_type": kind, "n_clusters": G, "scale": c, "meat": np.zeros((0, 0))}
+    return _sandwich(info, meat, score, coef, c, kind, G, float("nan"))
 
 
 def _survival_vector(a, n, what, stream=0, check_only=False):

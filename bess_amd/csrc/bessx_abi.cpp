@@ -3093,3 +3093,551 @@ int bessx_op_cox_diag_bench(const void *x, int dtype, long long row_stride, long
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// the meat of a robust / cluster-robust covariance on a caller's device matrix (include/bessx.h section 2k)
+// ----------------------------------------------------------------------------------------------
+static_assert((int)BESSX_HC0 == (int)SANDWICH_HC0 && (int)BESSX_HC1 == (int)SANDWICH_HC1 &&
+                  (int)BESSX_HC2 == (int)SANDWICH_HC2 && (int)BESSX_HC3 == (int)SANDWICH_HC3, "kind codes of the launcher");
+namespace {
+
+// the rows in cluster order, cut into runs (host side of bessx_k_sandwich.hip)
+struct ClusterPlan {
+  std::vector<int> rowof, rptr, rdst, lptr, lgrp, iota1;  // rowof is empty when the labels are already sorted
+  int G = 0, NR = 0, NL = 0;
+  long long max_rows = 0, prow = 0;  // longest cluster; rows of P in use
+};
+
+// lab null: every row is its own cluster
+void cluster_plan(const long long *lab, int n, int Ms, ClusterPlan *c) {
+  const int RUN = sandwich_run_rows();
+  std::vector<int> cptr;
+  cptr.push_back(0);
+  if (lab) {
+    bool sorted = true;
+    for (int i = 1; i < n && sorted; i++) sorted = lab[i - 1] <= lab[i];
+    if (!sorted) {
+      c->rowof.resize((size_t)n);
+      std::iota(c->rowof.begin(), c->rowof.end(), 0);
+      std::stable_sort(c->rowof.begin(), c->rowof.end(), [lab](int a, int b) { return lab[a] < lab[b]; });
+    }
+    for (int k = 1; k < n; k++) {
+      const long long a = lab[c->rowof.empty() ? k - 1 : c->rowof[(size_t)k - 1]];
+      const long long b = lab[c->rowof.empty() ? k : c->rowof[(size_t)k]];
+      if (a != b) cptr.push_back(k);
+    }
+    cptr.push_back(n);
+  } else {
+    cptr.resize((size_t)n + 1);
+    std::iota(cptr.begin(), cptr.end(), 0);
+  }
+  c->G = (int)cptr.size() - 1;
+  c->lptr.push_back(0);
+  for (int g = 0; g < c->G; g++) {
+    const int k0 = cptr[(size_t)g], k1 = cptr[(size_t)g + 1], len = k1 - k0;
+    c->max_rows = std::max<long long>(c->max_rows, len);
+    if (len <= RUN) {
+      c->rptr.push_back(k0);
+      c->rdst.push_back(g);
+    } else {
+      for (int k = k0; k < k1; k += RUN) {
+        c->rptr.push_back(k);
+        c->rdst.push_back(-1 - (int)c->prow++);
+      }
+      c->lptr.push_back((int)c->prow);
+      c->lgrp.push_back(g);
+    }
+  }
+  c->rptr.push_back(n);
+  c->NR = (int)c->rdst.size();
+  c->NL = (int)c->lgrp.size();
+  c->iota1.resize((size_t)std::max(Ms - 1, 0));
+  std::iota(c->iota1.begin(), c->iota1.end(), 1);
+}
+
+struct ClusterDev {
+  int *rowof = nullptr, *rptr = nullptr, *rdst = nullptr, *lptr = nullptr, *lgrp = nullptr, *iota1 = nullptr;
+  double *S = nullptr, *P = nullptr, *gwork = nullptr;
+  long long ldS = 0, ldP = 0;
+};
+
+int cluster_stage(Owner &sc, const ClusterPlan &c, int Ms, hipStream_t st, ClusterDev *d) {
+  auto up = [&](int **dst, const std::vector<int> &v) -> int {
+    if (v.empty()) return 0;
+    HIPX(sc.alloc(dst, v.size()));
+    HIPX(hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    return 0;
+  };
+  if (int rc = up(&d->rowof, c.rowof)) return rc;
+  if (int rc = up(&d->rptr, c.rptr)) return rc;
+  if (int rc = up(&d->rdst, c.rdst)) return rc;
+  if (c.NL > 0) {
+    if (int rc = up(&d->lptr, c.lptr)) return rc;
+    if (int rc = up(&d->lgrp, c.lgrp)) return rc;
+  }
+  if (int rc = up(&d->iota1, c.iota1)) return rc;
+  d->ldS = sandwich_ld(c.G);
+  HIPX(sc.alloc(&d->S, (size_t)d->ldS * (size_t)Ms));
+  if (c.NL > 0) {
+    d->ldP = sandwich_ld(c.prow);
+    HIPX(sc.alloc(&d->P, (size_t)d->ldP * (size_t)Ms));
+  }
+  HIPX(sc.alloc(&d->gwork, (size_t)sandwich_gram_workspace(c.G, Ms)));
+  return 0;
+}
+
+// S, then B and the sum vector (device memory)
+int cluster_launch(const void *x, int f32, long long rs, long long cs, int n, const int *cols_d, int m, int icpt,
+                   const double *u_d, const ClusterPlan &c, const ClusterDev &d, double *B, long long ld, double *sums,
+                   hipStream_t st) {
+  const int Ms = m + (icpt ? 1 : 0);
+  HIPX(launch_sandwich_sums(x, f32, rs, cs, n, cols_d, m, icpt, u_d, d.rowof, d.rptr, d.rdst, c.NR, d.lptr, d.lgrp, c.NL,
+                            d.S, d.ldS, d.P, d.ldP, st));
+  HIPX(launch_sandwich_gram(d.S, 0, 1, d.ldS, c.G, Ms, d.iota1, d.S, d.gwork, B, ld, sums, st));
+  return 0;
+}
+
+// the labels on the host as int64 (a device vector is copied: n elements, or ONE when its stride is 0 -- the view is then
+// known to hold one element only); nullptr without labels
+int cluster_labels(const long long *host, const void *dev, int dtype, long long stride, int n, hipStream_t st,
+                   std::vector<long long> &buf, const long long **out) {
+  *out = host;
+  if (!dev) return 0;
+  buf.resize((size_t)n);
+  const size_t cnt = stride == 0 ? 1 : (size_t)n, item = dtype == BESSX_I64 ? 8 : 4;
+  const size_t pitch = (size_t)std::max<long long>(stride, 1) * item;
+  if (dtype == BESSX_I64) {
+    HIPX(hipMemcpy2DAsync(buf.data(), 8, dev, pitch, 8, cnt, hipMemcpyDeviceToHost, st));
+    HIPX(hipStreamSynchronize(st));
+  } else {
+    std::vector<int> t(cnt);
+    HIPX(hipMemcpy2DAsync(t.data(), 4, dev, pitch, 4, cnt, hipMemcpyDeviceToHost, st));
+    HIPX(hipStreamSynchronize(st));
+    for (size_t i = 0; i < cnt; i++) buf[i] = t[i];
+  }
+  if (stride == 0) std::fill(buf.begin(), buf.end(), buf[0]);
+  *out = buf.data();
+  return 0;
+}
+
+int cluster_check_args(const std::string &w, const long long *host, const void *dev, int dtype, long long stride) {
+  if (host && dev) return fail(BESSX_ERR_ARG, w + ": give cluster as a host pointer or as a device vector, not both");
+  if (dev && dtype != BESSX_I64 && dtype != BESSX_I32)
+    return fail(BESSX_ERR_ARG, w + ": cluster: dtype must be BESSX_I64 or BESSX_I32");
+  if (stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  return 0;
+}
+
+int cluster_check_device(const std::string &w, const void *dev, int dtype, long long stride, int n, int xdev) {
+  if (!dev) return 0;
+  int od = -1;
+  if (int rc = check_device_matrix((w + ": cluster").c_str(), dev, dtype == BESSX_I32 ? BESSX_F32 : BESSX_F64, stride, 0,
+                                   n, 1, &od))
+    return rc;
+  if (od != xdev) return fail(BESSX_ERR_ARG, w + ": cluster is not on the device that owns x");
+  return 0;
+}
+
+int meat_check_args(const bessx_meat_input *in, const int *n_clusters) {
+  const std::string w("meat_device");
+  if (!in || !n_clusters) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (!in->x || !in->meat || !in->sums) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (int rc = predict_check_model("meat_device", in->n, in->p, in->cols, in->m, 1, BESSX_LINK_IDENTITY)) return rc;
+  const long long Ms = (long long)in->m + (in->intercept ? 1 : 0);
+  if (Ms < 1) return fail(BESSX_ERR_ARG, w + ": an empty support needs the intercept");
+  if (in->u_host && in->u_dev) return fail(BESSX_ERR_ARG, w + ": give u as a host pointer or as a device vector, not both");
+  if (int rc = cluster_check_args(w, in->cluster_host, in->cluster_dev, in->cluster_dtype, in->cluster_stride)) return rc;
+  if (in->meat_ld < Ms) return fail(BESSX_ERR_ARG, w + ": meat_ld must be at least m + intercept");
+  if (Ms > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + intercept must be at most " + std::to_string(INFO_M_MAX));
+  return 0;
+}
+
+// sc, the plan and the vectors belong to the caller: they must outlive everything this function queues on st
+int meat_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std::vector<double> &h,
+             const bessx_meat_input *in, int *n_clusters, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int f32 = in->x_dtype == BESSX_F32, m = in->m, n = in->n, icpt = in->intercept ? 1 : 0, Ms = m + icpt;
+  const size_t M = (size_t)Ms, nv = ((size_t)n + 1) / 2 * 2;
+  const long long *lab = nullptr;
+  if (int rc = cluster_labels(in->cluster_host, in->cluster_dev, in->cluster_dtype, in->cluster_stride, n, st, lbuf, &lab))
+    return rc;
+  int *cols_d = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  if (m > 0) HIPX(hipMemcpyAsync(cols_d, in->cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+  const double *u_d = in->u_dev;
+  if (in->u_host) {
+    double *t = nullptr;
+    HIPX(sc.alloc(&t, nv));
+    HIPX(hipMemcpyAsync(t, in->u_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    u_d = t;
+  }
+  double *stage = nullptr, *B = in->meat, *sums = in->sums;
+  long long ld = in->meat_ld;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&stage, M * M + M));
+    B = stage;
+    sums = stage + M * M;
+    ld = (long long)M;
+  }
+  if (!lab && icpt) {
+    // one sweep over x in place: vw = u^2, gw = u (ones without u)
+    double *w = nullptr;
+    HIPX(sc.alloc(&w, 2 * nv + (size_t)info_gram_workspace(n, m)));
+    if (u_d) {
+      HIPX(launch_sandwich_u(u_d, nullptr, SANDWICH_HC0, n, w, w + nv, st));
+    } else {
+      std::vector<double> &ones = h;  // (h outlives the copy; it is resized for the results only after the sync below)
+      ones.assign(nv, 1.0);
+      HIPX(hipMemcpyAsync(w, ones.data(), nv * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPX(hipMemcpyAsync(w + nv, ones.data(), nv * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIPX(launch_info_gram(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, w + nv, w, w + 2 * nv, B, ld,
+                          sums, st));
+    *n_clusters = 0;
+  } else if (!lab && !u_d) {
+    // a dense source as it is: column cols[0] is copied to an n-vector (the sweep's score weight), the sweep runs over
+    // the other columns of x in place -- launch_sandwich_gram's use of the sweep, with x in the place of S
+    double *w = nullptr;
+    HIPX(sc.alloc(&w, nv + (size_t)sandwich_gram_workspace(n, Ms)));
+    HIPX(launch_sandwich_column(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, w, st));
+    HIPX(launch_sandwich_gram(in->x, f32, in->x_row_stride, in->x_col_stride, n, Ms, cols_d + 1, w, w + nv, B, ld, sums,
+                              st));
+    *n_clusters = 0;
+  } else {
+    cluster_plan(lab, n, Ms, &plan);
+    ClusterDev d;
+    if (int rc = cluster_stage(sc, plan, Ms, st, &d)) return rc;
+    if (int rc = cluster_launch(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, icpt, u_d, plan, d, B, ld,
+                                sums, st))
+      return rc;
+    *n_clusters = lab ? plan.G : 0;
+  }
+  if (!in->out_on_device) {
+    HIPX(hipStreamSynchronize(st));
+    h.resize(M * M + M);
+    HIPX(hipMemcpyAsync(h.data(), stage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device) {
+    for (size_t j = 0; j < M; j++) std::copy(h.begin() + j * M, h.begin() + (j + 1) * M, in->meat + j * in->meat_ld);
+    std::copy(h.begin() + M * M, h.end(), in->sums);
+  }
+  return 0;
+}
+
+bessx_info_input sandwich_as_info(const bessx_sandwich_input *in) {
+  bessx_info_input e{};
+  e.x = in->x;
+  e.x_dtype = in->x_dtype;
+  e.x_row_stride = in->x_row_stride;
+  e.x_col_stride = in->x_col_stride;
+  e.n = in->n;
+  e.p = in->p;
+  e.cols = in->cols;
+  e.m = in->m;
+  e.beta = in->beta;
+  e.coef0 = in->coef0;
+  e.link = in->link;
+  e.y_host = in->y_host;
+  e.y_dev = in->y_dev;
+  e.y_dtype = in->y_dtype;
+  e.y_stride = in->y_stride;
+  e.weight_host = in->weight_host;
+  e.weight_dev = in->weight_dev;
+  e.weight_dtype = in->weight_dtype;
+  e.weight_stride = in->weight_stride;
+  e.info = in->info;
+  e.info_ld = in->info_ld;
+  e.score = in->score;
+  e.out_on_device = in->out_on_device;
+  e.stream = in->stream;
+  return e;
+}
+
+int sandwich_check_args(const bessx_sandwich_input *in, const double *loss, const double *sum_w, const int *n_clusters) {
+  const std::string w("sandwich_device");
+  if (!in || !n_clusters) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const bessx_info_input e = sandwich_as_info(in);
+  if (int rc = info_check_args("sandwich_device", &e, loss, sum_w)) return rc;
+  if (!in->meat) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->meat_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": meat_ld must be at least m + 1");
+  if (in->kind < BESSX_HC0 || in->kind > BESSX_HC3) return fail(BESSX_ERR_ARG, w + ": kind must be one of BESSX_HC0 .. BESSX_HC3");
+  if (int rc = cluster_check_args(w, in->cluster_host, in->cluster_dev, in->cluster_dtype, in->cluster_stride)) return rc;
+  if ((in->cluster_host || in->cluster_dev) && in->kind >= BESSX_HC2)
+    return fail(BESSX_ERR_ARG, w + ": cluster labels go with BESSX_HC0 or BESSX_HC1 only");
+  if (in->kind >= BESSX_HC2) {
+    if (!in->factor) return fail(BESSX_ERR_ARG, w + ": BESSX_HC2 and BESSX_HC3 need the factor");
+    if (in->factor_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m + 1");
+    for (long long j = 0; j <= in->m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  return 0;
+}
+
+// doubles of device scratch of a sandwich call besides the model and host y / weight (an upper bound when the labels
+// are not known: G clusters, the longest of max_rows rows; G = 0: no labels)
+long long sandwich_doubles(int f32, long long rs, long long cs, long long n, int m, int link, int weighted, int kind,
+                           long long G, long long max_rows) {
+  const long long nv = (n + 1) / 2 * 2, M = (long long)m + 1;
+  long long d = info_workspace(f32, rs, cs, n, m, link, weighted) + 3 + 2 * nv + M;  // res, u, u^2, the sweep's score
+  if (kind >= BESSX_HC2) d += nv + diag_factor_doubles(m);
+  if (G > 0) {
+    d += sandwich_ld(G) * M + sandwich_gram_workspace(G, (int)M);
+    const long long pr = sandwich_partial_rows(n, G, max_rows);
+    if (pr > 0) d += sandwich_ld(pr) * M;
+  }
+  return d;
+}
+
+int sandwich_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std::vector<double> &pk,
+                 std::vector<double> &h, const bessx_sandwich_input *in, double *loss, double *sum_w, int *n_clusters,
+                 hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const bessx_info_input ii = sandwich_as_info(in);
+  const bessx_eval_input e = info_as_eval(&ii);
+  const int f32 = in->x_dtype == BESSX_F32, m = in->m, n = in->n, kind = in->kind;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  const size_t M = (size_t)m + 1, nv = ((size_t)n + 1) / 2 * 2;
+  const long long *lab = nullptr;
+  if (int rc = cluster_labels(in->cluster_host, in->cluster_dev, in->cluster_dtype, in->cluster_stride, n, st, lbuf, &lab))
+    return rc;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *res = nullptr, *stage = nullptr, *uw = nullptr;
+  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
+  EvalData d;
+  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  HIPX(sc.alloc(&work, (size_t)info_workspace(f32, rs, cs, n, m, in->link, d.w != nullptr)));
+  HIPX(sc.alloc(&res, 3));
+  HIPX(sc.alloc(&uw, 2 * nv + M));
+  double *info_d = in->info, *score_d = in->score, *meat_d = in->meat;
+  long long ld = in->info_ld, mld = in->meat_ld;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&stage, 2 * M * M + M));
+    info_d = stage;
+    score_d = stage + M * M;
+    meat_d = score_d + M;
+    ld = mld = (long long)M;
+  }
+  HIPX(launch_info(in->x, f32, rs, cs, n, cols_d, m, B_d, c_d, in->link, d, work, res, info_d, ld, score_d, st));
+  // launch_info's work starts with v and g (nv doubles each) and the partials of its sweep, which have served
+  double *v_d = work, *g_d = work + nv, *part = work + 2 * nv, *u_d = uw, *u2_d = uw + nv, *sc2 = uw + 2 * nv;
+  // with labels u must be the same bits under every layout: the pass with threads along rows (without labels nothing
+  // needs that, and on a row-contiguous x the second pass would cost as much as the first)
+  if (lab && !info_eta_by_rows(rs, cs, m))
+    HIPX(launch_info_vg(in->x, f32, rs, cs, n, cols_d, m, B_d, c_d, in->link, d, v_d, g_d, st));
+  double *h_d = nullptr;
+  if (kind >= BESSX_HC2) {
+    double *pk_d = nullptr;
+    pk.resize((size_t)diag_factor_doubles(m));
+    diag_pack_factor(in->factor, in->factor_ld, m, pk.data());
+    HIPX(sc.alloc(&h_d, nv));
+    HIPX(sc.alloc(&pk_d, pk.size()));
+    HIPX(hipMemcpyAsync(pk_d, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(launch_diag_lev(in->x, f32, rs, cs, n, cols_d, m, pk_d, v_d, nullptr, nullptr, 1.0, h_d, nullptr, nullptr,
+                         nullptr, st));
+  }
+  HIPX(launch_sandwich_u(g_d, h_d, kind, n, u_d, u2_d, st));
+  if (!lab) {
+    HIPX(launch_info_gram(in->x, f32, rs, cs, n, cols_d, m, u2_d, g_d, part, meat_d, mld, sc2, st));
+    *n_clusters = 0;
+  } else {
+    cluster_plan(lab, n, (int)M, &plan);
+    ClusterDev cd;
+    if (int rc = cluster_stage(sc, plan, (int)M, st, &cd)) return rc;
+    if (int rc = cluster_launch(in->x, f32, rs, cs, n, cols_d, m, 1, u_d, plan, cd, meat_d, mld, sc2, st)) return rc;
+    *n_clusters = plan.G;
+  }
+  h.resize(3 + (in->out_on_device ? 0 : 2 * M * M + M));
+  HIPX(hipMemcpyAsync(h.data(), res, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (!in->out_on_device)
+    HIPX(hipMemcpyAsync(h.data() + 3, stage, (2 * M * M + M) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  *loss = h[0];
+  *sum_w = d.w ? h[2] : (double)n;
+  if (!in->out_on_device) {
+    const double *hi = h.data() + 3, *hs = hi + M * M, *hm = hs + M;
+    for (size_t j = 0; j < M; j++) {
+      std::copy(hi + j * M, hi + (j + 1) * M, in->info + j * in->info_ld);
+      std::copy(hm + j * M, hm + (j + 1) * M, in->meat + j * in->meat_ld);
+    }
+    std::copy(hs, hs + M, in->score);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int link,
+                             int weighted, int kind, int n_clusters, int max_cluster_rows, long long *doubles,
+                             long long *rows_per_slab, int *slabs, long long *cluster_rows_per_slab, int *cluster_slabs,
+                             int *sum_depth, int *sq_depth) {
+  if (!doubles || !rows_per_slab || !slabs || !cluster_rows_per_slab || !cluster_slabs || !sum_depth || !sq_depth)
+    return fail(BESSX_ERR_ARG, "sandwich_workspace: null argument");
+  if (x_dtype != BESSX_F64 && x_dtype != BESSX_F32)
+    return fail(BESSX_ERR_ARG, "sandwich_workspace: x: dtype must be BESSX_F64 or BESSX_F32");
+  if (x_row_stride < 0 || x_col_stride < 0)
+    return fail(BESSX_ERR_ARG, "sandwich_workspace: strides must be non-negative");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "sandwich_workspace: empty matrix");
+  if (link != BESSX_LINK_IDENTITY && link != BESSX_LINK_LOGISTIC && link != BESSX_LINK_POISSON)
+    return fail(BESSX_ERR_ARG, "sandwich_workspace: unknown link");
+  if (kind < BESSX_HC0 || kind > BESSX_HC3)
+    return fail(BESSX_ERR_ARG, "sandwich_workspace: kind must be one of BESSX_HC0 .. BESSX_HC3");
+  if (n_clusters < 0 || n_clusters > n || max_cluster_rows < 0 || max_cluster_rows > n ||
+      (n_clusters > 0 && max_cluster_rows < 1))
+    return fail(BESSX_ERR_ARG, "sandwich_workspace: n_clusters and max_cluster_rows must lie in [0, n]");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "sandwich_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  *doubles = sandwich_doubles(x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, m, link, weighted != 0, kind,
+                              n_clusters, max_cluster_rows);
+  info_split(n, m, rows_per_slab, slabs);
+  *cluster_rows_per_slab = 0;
+  *cluster_slabs = 0;
+  if (n_clusters > 0) info_split(n_clusters, m, cluster_rows_per_slab, cluster_slabs);  // (the sweep's M is m + 1)
+  *sum_depth = n_clusters > 0 ? sandwich_sum_depth(max_cluster_rows) : 0;
+  *sq_depth = n_clusters > 0 ? sandwich_sq_depth(n_clusters) : 0;
+  return BESSX_OK;
+}
+
+int bessx_meat_device(const bessx_meat_input *in, int *n_clusters) {
+  if (int rc = meat_check_args(in, n_clusters)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("meat_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->u_dev) {
+    if (int rc = check_device_matrix("meat_device: u", in->u_dev, BESSX_F64, 1, 0, in->n, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "meat_device: u is not on the device that owns x");
+  }
+  if (int rc = cluster_check_device("meat_device", in->cluster_dev, in->cluster_dtype, in->cluster_stride, in->n, dev))
+    return rc;
+  if (in->out_on_device) {
+    const int Ms = in->m + (in->intercept ? 1 : 0);
+    if (int rc = check_device_matrix("meat_device: meat", in->meat, BESSX_F64, in->meat_ld, 1, Ms, Ms, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "meat_device: meat is not on the device that owns x");
+    if (int rc = check_device_matrix("meat_device: sums", in->sums, BESSX_F64, 1, 0, Ms, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "meat_device: sums is not on the device that owns x");
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    ClusterPlan plan;
+    std::vector<long long> lbuf;
+    std::vector<double> h;
+    rc = meat_run(sc, plan, lbuf, h, in, n_clusters, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_sandwich_device(const bessx_sandwich_input *in, double *loss, double *sum_w, int *n_clusters) {
+  if (int rc = sandwich_check_args(in, loss, sum_w, n_clusters)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("sandwich_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->y_dev) {
+    if (int rc = check_device_matrix("sandwich_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: y is not on the device that owns x");
+  }
+  if (in->weight_dev) {
+    if (int rc = check_device_matrix("sandwich_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
+                                     in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: weight is not on the device that owns x");
+  }
+  if (int rc = cluster_check_device("sandwich_device", in->cluster_dev, in->cluster_dtype, in->cluster_stride, in->n,
+                                    dev))
+    return rc;
+  if (in->out_on_device) {
+    const int M = in->m + 1;
+    if (int rc = check_device_matrix("sandwich_device: info", in->info, BESSX_F64, in->info_ld, 1, M, M, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: info is not on the device that owns x");
+    if (int rc = check_device_matrix("sandwich_device: score", in->score, BESSX_F64, 1, 0, M, 1, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: score is not on the device that owns x");
+    if (int rc = check_device_matrix("sandwich_device: meat", in->meat, BESSX_F64, in->meat_ld, 1, M, M, &od)) return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: meat is not on the device that owns x");
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    ClusterPlan plan;
+    std::vector<long long> lbuf;
+    std::vector<double> pk, h;
+    rc = sandwich_run(sc, plan, lbuf, pk, h, in, loss, sum_w, n_clusters, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, const long long *cluster, int repeats, double *avg_ms,
+                            double *bytes) {
+  if (!x || !cluster || repeats < 1 || !avg_ms || !bytes) return fail(BESSX_ERR_ARG, "op_sandwich_bench: bad arguments");
+  if (int rc = predict_check_model("op_sandwich_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_sandwich_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_sandwich_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const int Ms = m + 1, f32 = dtype == BESSX_F32;
+  ClusterPlan plan;
+  cluster_plan(cluster, n, Ms, &plan);
+  ClusterDev d;
+  if (int rc = cluster_stage(sc, plan, Ms, nullptr, &d)) return rc;
+  std::vector<double> u((size_t)n);
+  for (size_t i = 0; i < u.size(); i++) u[i] = (i % 2) ? -0.5 : 0.5;
+  int *cols_d = nullptr;
+  double *u_d = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&u_d, u.size()));
+  if (m > 0) HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(u_d, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  auto run = [&]() {
+    return launch_sandwich_sums(x, f32, row_stride, col_stride, n, cols_d, m, 1, u_d, d.rowof, d.rptr, d.rdst, plan.NR,
+                                d.lptr, d.lgrp, plan.NL, d.S, d.ldS, d.P, d.ldP, nullptr);
+  };
+  HIPX(run());
+  HIPX(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < repeats; i++) HIPX(run());
+  HIPX(hipEventRecord(e1, nullptr));
+  HIPX(hipEventSynchronize(e1));
+  float ms = 0.f;
+  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  *avg_ms = ms / repeats;
+  // what the algorithm needs: the support and u once, S once
+  *bytes = (double)n * m * (f32 ? 4.0 : 8.0) + 8.0 * (double)n + 8.0 * (double)Ms * (double)plan.G;
+  return BESSX_OK;
+}
+
+}  // extern "C"

@@ -122,6 +122,40 @@ hipError_t launch_info_gram(const void *src, int f32, long long rs, long long cs
 hipError_t launch_info(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                        const double *B, const double *c, int link, const EvalData &d, double *work, double *res,
                        double *info, long long ld, double *score, hipStream_t st);
+// launch_info_vg: the eta pass of launch_info alone, always with threads along rows: v and g (n doubles each) are the
+// same bits under every layout of x.  info_eta_by_rows: whether launch_info's own pass is that one (its work then
+// starts with exactly these v and g, each (n + 1) / 2 * 2 doubles).
+bool info_eta_by_rows(long long rs, long long cs, int m);
+hipError_t launch_info_vg(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                          const double *B, const double *c, int link, const EvalData &d, double *v, double *g,
+                          hipStream_t st);
+// the meat of a robust (sandwich) covariance (bessx_k_sandwich.hip).  _sums: S(g, a) = sum_{i in g} u_i z_ia, z_i = (1,
+// x(i, cols[..])) (icpt) or (x(i, cols[..])), Ms = m + icpt entries, u null = ones, for clusters given as runs of at
+// most sandwich_run_rows() rows: rowof (row at a sorted position; null: identity), rptr (NR + 1 run starts), rdst (NR:
+// g >= 0, or -1 - row of P for a cluster of several runs), lptr (NL + 1) / lgrp (NL): the rows of P and the cluster of
+// every such cluster.  S and P are column-contiguous with leading dimensions ldS / ldP (sandwich_ld).  _u: u and u^2
+// from g and the leverage h.  _gram: B = sum_g y_g y_g^T (Ms x Ms, both triangles) and the sum vector for the rows y_g =
+// (gw[g], src(g, cols1[..])), from one launch_info_gram sweep plus a fixed-order sum for B(0, 0): src = S with cols1 = 1 ..
+// Ms - 1 and gw = S(:, 0), or a dense source in place with gw its first support column (_column copies it); work:
+// sandwich_gram_workspace(G, Ms) doubles.  The depth functions count the additions behind an entry.  Device memory.
+enum { SANDWICH_HC0 = 0, SANDWICH_HC1 = 1, SANDWICH_HC2 = 2, SANDWICH_HC3 = 3 };
+int sandwich_run_rows();
+int sandwich_sum_depth(long long rows);
+int sandwich_sq_depth(long long G);
+long long sandwich_ld(long long G);
+long long sandwich_partial_rows(long long n, long long G, long long max_rows);
+long long sandwich_gram_workspace(long long G, int Ms);
+hipError_t launch_sandwich_sums(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                                int icpt, const double *u, const int *rowof, const int *rptr, const int *rdst, int NR,
+                                const int *lptr, const int *lgrp, int NL, double *S, long long ldS, double *P,
+                                long long ldP, hipStream_t st);
+hipError_t launch_sandwich_u(const double *g, const double *h, int kind, long long n, double *u, double *u2,
+                             hipStream_t st);
+hipError_t launch_sandwich_column(const void *src, int f32, long long rs, long long cs, long long n, const int *cols,
+                                  double *out, hipStream_t st);
+hipError_t launch_sandwich_gram(const void *src, int f32, long long rs, long long cs, long long G, int Ms,
+                                const int *cols1, const double *gw, double *work, double *B, long long ld, double *sums,
+                                hipStream_t st);
 // per-row diagnostics of one model (bessx_k_diag.hip).  _eta: the predictor pass (src, cols, B, c as in launch_predict,
 // R = 1) whose epilogue writes, each to n doubles or nowhere (null): v_i as in launch_info, the response residual
 // y_i - mu_i, the Pearson and the deviance residual.  _lev: h_i = v_i * sum_j t_ij^2 with T = Z R^T on the fp64 matrix

@@ -9,6 +9,7 @@
 #include "bessx_k_coxsurv.hip"
 #include "bessx_k_info.hip"
 #include "bessx_k_diag.hip"
+#include "bessx_k_sandwich.hip"
 #include "bessx_k_coxinfo.hip"
 #include "bessx_k_coxdiag.hip"
 #include "bessx_k_solve.hip"

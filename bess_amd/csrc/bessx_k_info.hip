@@ -323,4 +323,35 @@ hipError_t launch_info(const void *src, int f32, long long rs, long long cs, lon
   return launch_eval(src, f32, rs, cs, n, cols, m, B, c, 1, link, d1, ework, res, st);
 }
 
+// the eta pass alone, ALWAYS k_xb_rows (never k_xb_gather, whose sums have another order): v_i and g_i are the same
+// bits under every layout of X, which the robust covariance's cluster sums rely on (bessx_k_sandwich.hip)
+template <typename T>
+static hipError_t info_launch_vg_rows(const T *src, long long rs, long long cs, long long n, const int *cols, int m,
+                                      const double *B, const double *c, const InfoStore &epi, hipStream_t st) {
+  const long long per16 = 16 / (long long)sizeof(T);
+  const bool vec = rs == 1 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && cs % per16 == 0;
+  const long long rows_per_block = 64LL * PrVec<T>::N;
+  const dim3 grid((unsigned)((n + rows_per_block - 1) / rows_per_block), 1);
+  if (vec)
+    hipLaunchKernelGGL((k_xb_rows<T, 1, true, InfoStore>), grid, dim3(256), 0, st, src, rs, cs, n, cols, m, B, c, 1, epi);
+  else
+    hipLaunchKernelGGL((k_xb_rows<T, 1, false, InfoStore>), grid, dim3(256), 0, st, src, rs, cs, n, cols, m, B, c, 1, epi);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+// whether launch_info's own eta pass is k_xb_rows, i.e. its v and g are already those of launch_info_vg
+bool info_eta_by_rows(long long rs, long long cs, int m) { return !(cs == 1 && rs != 1 && m > 0); }
+
+hipError_t launch_info_vg(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                          const double *B, const double *c, int link, const EvalData &d, double *v, double *g,
+                          hipStream_t st) {
+  if (!src || !c || !d.y || !v || !g || n < 1 || n > 0x7fffffffLL || m < 0 || (m > 0 && (!cols || !B)) || rs < 0 ||
+      cs < 0 || d.yrs < 0 || d.ws < 0 || link < PREDICT_IDENTITY || link > PREDICT_POISSON)
+    return hipErrorInvalidValue;
+  const InfoStore epi{d, link, v, g};
+  return f32 ? info_launch_vg_rows(static_cast<const float *>(src), rs, cs, n, cols, m, B, c, epi, st)
+             : info_launch_vg_rows(static_cast<const double *>(src), rs, cs, n, cols, m, B, c, epi, st);
+}
+
 }  // namespace bessx

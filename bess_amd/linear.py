@@ -388,7 +388,71 @@ class bess_base:
         info = np.tril(info) + np.tril(info, -1).T  # (both triangles from the lower one, as the kernel writes them)
         return {"info": info, "score": Z.T @ g, "loss": float((w * f).sum()), "sum_w": float(w.sum())}
 
-    def inference(self, X, y, weight=None):
+    @staticmethod
+    def _labels_host(cluster):
+        """Cluster labels as a host int64 vector (a device array is copied to the host)."""
+        if capi.is_device_array(cluster):
+            torch = sys.modules.get("torch")
+            if torch is not None and isinstance(cluster, torch.Tensor):
+                cluster = cluster.detach().cpu().numpy()
+            elif hasattr(cluster, "get"):
+                cluster = cluster.get()
+            else:
+                raise ValueError("cluster: a device array that is no torch tensor cannot be copied to the host here")
+        return np.ascontiguousarray(np.asarray(cluster).reshape(-1), dtype=np.int64)
+
+    @staticmethod
+    def _cov_args(cov_type, cluster, n, allowed):
+        """The checks of cov_type / cluster that inference() and inference_survival() share; no device call."""
+        if cov_type != "model" and cov_type not in capi.COV_TYPES:
+            raise ValueError("cov_type must be 'model' or one of %s, got %r" % (list(capi.COV_TYPES), cov_type))
+        if cluster is not None:
+            if cov_type == "model":
+                raise ValueError("cluster needs a robust cov_type ('HC0' or 'HC1'), got cov_type='model'")
+            capi.cluster_labels(cluster, n)  # (size and dtype)
+        if cov_type != "model" and not allowed(cov_type, cluster is not None):
+            raise ValueError("cov_type %r is not available %s cluster for this model"
+                             % (cov_type, "with" if cluster is not None else "without"))
+
+    @staticmethod
+    def _meat_host(Y, labels):
+        """sum_g s_g s_g^T (labels: host int64) or sum_i y_i y_i^T (labels None) for the rows y_i of Y (n, M); both
+        triangles from the lower one.  Returns (meat, G or None)."""
+        G = None
+        if labels is not None:
+            order = np.argsort(labels, kind="stable")
+            ls = labels[order]
+            starts = np.nonzero(np.concatenate([[True], ls[1:] != ls[:-1]]))[0]
+            Y = np.add.reduceat(Y[order], starts, axis=0)
+            G = int(starts.size)
+        B = Y.T @ Y
+        return np.tril(B) + np.tril(B, -1).T, G
+
+    @classmethod
+    def _sandwich_host(cls, link, Xs, beta, coef0, y, w, kind, R, labels):
+        """sandwich_device's meat in fp64 NumPy with the same definitions: Xs (n, m) the support's columns, R the factor
+        of info_factor (HC2 / HC3 only), labels host int64 or None.  Returns (meat, G or None)."""
+        n, M = Xs.shape[0], Xs.shape[1] + 1
+        eta = Xs @ beta + coef0
+        if link == "identity":
+            v, g = w.copy(), w * (y - eta)
+        elif link == "logistic":
+            t = np.exp(-np.abs(eta))
+            p = np.where(eta >= 0, 1.0, t) / (1.0 + t)
+            v, g = w * (t / ((1.0 + t) * (1.0 + t))), w * (y - p)
+        else:
+            e = np.exp(eta)
+            v, g = w * e, w * (y - e)
+        Z = np.column_stack([np.ones(n), Xs])
+        u = g
+        if kind in ("HC2", "HC3"):
+            T = Z @ np.tril(R).T
+            h = v * np.sum(T * T, axis=1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                u = g / np.sqrt(1.0 - h) if kind == "HC2" else g / (1.0 - h)
+        return cls._meat_host(u[:, None] * Z, labels)
+
+    def inference(self, X, y, weight=None, cov_type="model", cluster=None):
         """Standard errors and Wald tests of the fitted model on the rows (X, y): capi.wald_table's dict -- coef
         (intercept first), se, z, p_value, cov, score, dispersion, dof, cond, positive_definite -- plus cols, the
         selected columns in the order of coef[1:].  The information is the unpenalised expected information
@@ -398,12 +462,22 @@ class bess_base:
         fitted with lambda > 0 shows score != 0.  Selection is not corrected for.  An X in GPU memory is read in place on
         torch's current stream, the support's columns only, and y and weight may be device arrays too; a NumPy X is
         served in fp64 NumPy with the same definitions.  Cox: None.  A 2-D beta (Lm fitted to several responses) raises
-        ValueError: one model per call."""
+        ValueError: one model per call.
+        cov_type: "model" (the default: the model-based covariance above, dispersion * inv(info)) or "HC0", "HC1", "HC2",
+        "HC3": the robust (Huber-White sandwich) covariance c * inv(info) B inv(info) of capi.sandwich_table -- B = sum_i
+        u_i^2 z_i z_i^T with u_i = g_i (HC0, HC1), g_i / sqrt(1 - h_i) (HC2), g_i / (1 - h_i) (HC3), no dispersion factor
+        -- and the dict gains cov_type, n_clusters, scale and meat.  cluster: n integer labels (host or device array, any
+        values, any order) for the cluster-robust covariance B = sum_g s_g s_g^T, s_g = sum_{i in g} u_i z_i: "HC0" is CR0,
+        "HC1" is CR1 with c = G / (G - 1) * (n - 1) / (n - M); with "HC2" / "HC3" or with "model" it raises ValueError.
+        With weights g carries w, so B carries w^2 (the estimating-function convention), and a row or a cluster of weight
+        0 counts in n and G.  An X in GPU memory takes capi.sandwich_device (after capi.information_device and
+        capi.info_factor when the leverage is needed)."""
         on_device = capi.is_device_array(X)
         shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
         if len(shape) != 2 or shape[1] != self.p:
             raise ValueError("X.shape[1] should be " + str(self.p))
         n = shape[0]
+        self._cov_args(cov_type, cluster, n, lambda k, cl: not (cl and k in ("HC2", "HC3")))
         if self.model_type_int == 4:
             return None
         beta, cols, coef0, multi = self._model_arrays()
@@ -420,8 +494,19 @@ class bess_base:
         if on_device:
             if not y_dev:
                 y = np.asarray(y, dtype=np.float64).reshape(-1)
-            got = capi.information_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight,
-                                          stream=_current_stream(X))
+            st = _current_stream(X)
+            if cov_type in ("model", "HC2", "HC3"):
+                got = capi.information_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight, stream=st)
+            if cov_type in ("HC2", "HC3"):
+                R, pd = capi.info_factor(got["info"])
+                if pd:
+                    got = capi.sandwich_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight, kind=cov_type,
+                                               factor=R, stream=st)
+                else:
+                    got.update(meat=np.full_like(got["info"], np.nan), n_clusters=None)
+            elif cov_type != "model":
+                got = capi.sandwich_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight, kind=cov_type,
+                                           cluster=cluster, stream=st)
         else:
             yh = (capi.device_to_host(y, _current_stream(y)) if y_dev else np.asarray(y, dtype=np.float64)).reshape(-1)
             if weight is None:
@@ -429,9 +514,21 @@ class bess_base:
             else:
                 w = (capi.device_to_host(weight, _current_stream(weight)) if w_dev
                      else np.asarray(weight, dtype=np.float64)).reshape(-1)
-            got = self._information_host(link, np.asarray(X, dtype=np.float64)[:, cols], beta[cols], coef0[0], yh, w)
-        out = capi.wald_table(got["info"], got["score"], np.concatenate([coef0[:1], beta[cols]]), link, got["loss"],
-                              got["sum_w"])
+            Xs = np.asarray(X, dtype=np.float64)[:, cols]
+            got = self._information_host(link, Xs, beta[cols], coef0[0], yh, w)
+            if cov_type != "model":
+                R, pd = capi.info_factor(got["info"]) if cov_type in ("HC2", "HC3") else (None, True)
+                if pd:
+                    labels = None if cluster is None else self._labels_host(cluster)
+                    got["meat"], got["n_clusters"] = self._sandwich_host(link, Xs, beta[cols], coef0[0], yh, w, cov_type,
+                                                                         R, labels)
+                else:
+                    got.update(meat=np.full_like(got["info"], np.nan), n_clusters=None)
+        coef = np.concatenate([coef0[:1], beta[cols]])
+        if cov_type == "model":
+            out = capi.wald_table(got["info"], got["score"], coef, link, got["loss"], got["sum_w"])
+        else:
+            out = capi.sandwich_table(got["info"], got["meat"], got["score"], coef, cov_type, n, got["n_clusters"])
         out["cols"] = cols
         return out
 
@@ -704,7 +801,13 @@ class bess_base:
         return {"info": info, "score": x.T @ g, "loglik": loglik, "n_events": float(np.sum(wd)),
                 "residual_sum": float(np.sum(g)) if m > 0 else 0.0}
 
-    def inference_survival(self, X, y, weight=None, ties="order"):
+    @classmethod
+    def _cox_sandwich_host(cls, L, labels):
+        """The Lin-Wei meat from the score residuals L (n, m) in fp64 NumPy: sum_k L_k L_k^T, or sum_g s_g s_g^T with
+        s_g = sum_{k in g} L_k (labels: host int64).  Returns (meat, G or None)."""
+        return cls._meat_host(np.asarray(L, dtype=np.float64), labels)
+
+    def inference_survival(self, X, y, weight=None, ties="order", cov_type="model", cluster=None):
         """Cox only: standard errors and Wald tests of the fitted model on the rows (X, y) -- capi.cox_wald_table's dict
         (coef, se, z, p_value, cov, score, dispersion = 1, dof = n_events - m, cond, positive_definite; no intercept) plus
         cols, the selected columns in the order of coef, loglik and residual_sum.  y: (n, 2) time and status as in fit;
@@ -716,20 +819,51 @@ class bess_base:
         at the unpenalised optimum of the support, and residual_sum, the sum of the martingale residuals, is 0 up to
         rounding always.  Selection is not corrected for.  An X in GPU memory is read in place on torch's current stream,
         the support's columns only (y and weight may be device arrays: n values each are copied to the host); a NumPy X is
-        served in fp64 NumPy with the same decomposition.  inference() stays None for the Cox classes."""
+        served in fp64 NumPy with the same decomposition.  inference() stays None for the Cox classes.
+        cov_type: "model" (the default, inv(info)) or the Lin-Wei robust covariance c * inv(info) B inv(info) of
+        capi.cox_sandwich_table, with L the score residuals of capi.cox_diagnostics_device (they carry the weights):
+        "HC0": B = sum_k L_k L_k^T, or with cluster (n integer labels, host or device) B = sum_g s_g s_g^T, s_g = sum_{k
+        in g} L_k, c = 1; "HC1" with cluster: c = G / (G - 1).  "HC1" without cluster, "HC2", "HC3" and cluster with
+        "model" raise ValueError.  The dict then gains cov_type, n_clusters, scale and meat, and dof stays n_events - m.
+        An X in GPU memory takes capi.cox_information_device, capi.cox_diagnostics_device(kinds=("score",)) and
+        capi.meat_device on L where it lies."""
         if self.model_type_int != 4:
             raise ValueError("inference_survival is for the Cox classes, this is a %s model" % self.model_type)
         if ties not in capi.TIES:
             self._survival_x(X)
             raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        self._cov_args(cov_type, cluster, self._survival_x(X)[1], lambda k, cl: k == "HC0" or (k == "HC1" and cl))
         on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
         beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
         cols = np.nonzero(beta)[0]
+        m = cols.size
+        wt = None if weight is None else w
         if on_device:
-            got = capi.cox_information_device(X, cols, beta[cols], time, status, weight=None if weight is None else w,
-                                              ties=ties, stream=_current_stream(X))
+            st = _current_stream(X)
+            got = capi.cox_information_device(X, cols, beta[cols], time, status, weight=wt, ties=ties, stream=st)
         else:
-            got = self._cox_information_host(np.asarray(X, dtype=np.float64)[:, cols], beta[cols], time, status, w, ties)
+            Xs = np.asarray(X, dtype=np.float64)[:, cols]
+            got = self._cox_information_host(Xs, beta[cols], time, status, w, ties)
+        if cov_type != "model":
+            meat, G, L = np.zeros((0, 0)), None, None
+            if m > 0 and on_device:
+                L = capi.cox_diagnostics_device(X, cols, beta[cols], time, status, weight=wt, ties=ties,
+                                                kinds=("score",), stream=st)["score"]
+                if capi.is_device_array(L):
+                    got_m = capi.meat_device(L, np.arange(m), cluster=cluster, intercept=False, stream=st)
+                    meat, G, L = got_m["meat"], got_m["n_clusters"], None
+            elif m > 0:
+                L = self._cox_diagnostics_host(Xs, beta[cols], time, status, w, ties, None, None, ("score",))["score"]
+            if L is not None or (m == 0 and cluster is not None):  # (labels on the host: the NumPy sums, or G alone)
+                labels = None if cluster is None else self._labels_host(cluster)
+                if L is not None:
+                    meat, G = self._cox_sandwich_host(L, labels)
+                else:
+                    G = int(np.unique(labels).size)
+            out = capi.cox_sandwich_table(got["info"], meat, got["score"], beta[cols], cov_type, G)
+            out["dof"] = float(got["n_events"]) - m
+            out.update(cols=cols, loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
+            return out
         out = capi.cox_wald_table(got["info"], got["score"], beta[cols], got["n_events"])
         out.update(cols=cols, loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
         return out

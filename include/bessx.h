@@ -671,6 +671,112 @@ typedef struct {
 } bessx_cox_diag_input;
 int bessx_cox_diag_device(const bessx_cox_diag_input *in, int *n_event_rows);
 int bessx_cox_diag_workspace(int n, int m, int n_event_rows, unsigned kinds, long long *doubles);
+/* ---------------------------------------------------------------------------------------
+ * 2k. The "meat" of a robust (Huber-White sandwich) or cluster-robust covariance on an X already in GPU memory
+ *     (bessx_k_sandwich.hip).  Stateless like sections 2c to 2j.  Notation of section 2g: z_i = (1, x(i, cols[0]), ...),
+ *     M = m + 1, v_i and g_i the working and score weights of the link, info = sum_i v_i z_i z_i^T.  With weights
+ *     g_i = w_i (y_i - mu_i), so the meat carries w_i^2: the ESTIMATING-FUNCTION convention (weights are part of the
+ *     estimating equation, not frequencies).
+ *         row scalar   BESSX_HC0, BESSX_HC1: u_i = g_i;  BESSX_HC2: u_i = g_i / sqrt(1 - h_i);  BESSX_HC3: u_i = g_i /
+ *                      (1 - h_i), with h_i the leverage of section 2i from the same factor R (inverse(info) = R^T R).
+ *                      No clamp: h_i = 1 gives what IEEE arithmetic gives.
+ *         meat         B = sum_i u_i^2 z_i z_i^T without clusters;  with cluster labels (n integers, any values, any
+ *                      order) B = sum_g s_g s_g^T, s_g = sum_{i in g} u_i z_i.  M x M, entry (j, k) at [j * meat_ld + k],
+ *                      both triangles written, exact mirrors.
+ *     The covariance c * inverse(info) B inverse(info) and its scale factor c are the host's business (capi.py:
+ *     sandwich_table); BESSX_HC0 and BESSX_HC1 give the same B.  Cluster labels with BESSX_HC2 / BESSX_HC3 are
+ *     BESSX_ERR_ARG (the block-leverage corrections are not built).  A row or a cluster of weight 0 is a row / a cluster.
+ *
+ *     bessx_meat_device is the generic primitive: B and sums = sum_g s_g (without clusters sum_i u_i z_i) for a source
+ *     matrix x (as in section 2c), a support cols, intercept != 0 (z has the leading 1) or 0 (z_i = x(i, cols), M = m >=
+ *     1: a dense source such as the Cox score residuals L of section 2j), an optional u (n doubles with unit stride, host
+ *     or device; both null = ones) and optional labels (host int64, or a device vector of BESSX_I64 / BESSX_I32 with an
+ *     element stride, which is copied to the host; stride 0: one element is read and stands for every row).  *n_clusters = G, or 0 without labels.
+ *     bessx_sandwich_device is the GLM route in one call, with no host round trip between the predictor pass and the
+ *     meat: the arguments of section 2g plus kind, the factor R (HOST, as in section 2i; needed by BESSX_HC2 / _HC3
+ *     only) and the labels.  info, score, *loss and *sum_w are section 2g's for the same arguments, bit for bit.
+ *
+ *     How: the host sorts the rows by label (std::stable_sort: a cluster's rows keep their order) and cuts every cluster
+ *     into runs of at most 64 rows.  One kernel forms S(g, a) = sum_{i in g} u_i z_ia (G x M, column-contiguous) from x
+ *     in place: a run is a chain of FMAs in row order, a cluster of several runs adds its runs' partial sums in run
+ *     order -- min(r, 64) + ceil(r / 64) - 1 additions for a cluster of r rows, so the bits of S(g, :) depend on the
+ *     cluster's rows in their original order and on u alone (not on the layout of x, on n, on where the cluster lies
+ *     or on the other clusters).  Three access shapes with the same arithmetic: 16-byte loads (labels already sorted,
+ *     column-contiguous aligned source), element loads at any strides, and a row-contiguous source with lanes across
+ *     the support.  u and v come from a predictor pass with threads along rows under every layout.  B is then section
+ *     2g's matrix-core sweep over S (columns 1 .. M - 1, with S(:, 0) as the score weight) plus one fixed-order sum for
+ *     B(0, 0) (ceil(G / 256) + 8 additions); without clusters it is that sweep over x in place with u_i^2 as the
+ *     working weight (intercept == 0 without clusters: the sweep runs over x in place with column cols[0], copied to an
+ *     n-vector, as the score weight; only with a u is every row its own cluster and S = u x an n x m copy).  No
+ *     floating-point atomics: the same call gives the same bits.  The constant entry is not read, nothing outside the
+ *     n x m view is read, a NaN inside it propagates.  m + intercept <= 1024, else BESSX_ERR_UNSUPPORTED; every
+ *     argument error is found before any device call.  Outputs are device memory of x's device when out_on_device != 0.
+ *     bessx_sandwich_workspace needs no device: the doubles of device scratch of a bessx_sandwich_device call (an upper
+ *     bound for n_clusters clusters the longest of which has max_cluster_rows rows; n_clusters = 0: no labels), the row
+ *     split of the sweep over x (section 2g's for (n, m)) and of the sweep over S (that of (n_clusters, m); 0, 0 without
+ *     labels), the additions behind an entry of S for a cluster of max_cluster_rows rows, and those behind B(0, 0).
+ * ------------------------------------------------------------------------------------- */
+enum { BESSX_HC0 = 0, BESSX_HC1 = 1, BESSX_HC2 = 2, BESSX_HC3 = 3 };
+enum { BESSX_I64 = 0, BESSX_I32 = 1 };
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  int intercept;
+  const double *u_host;
+  const double *u_dev;
+  const long long *cluster_host;
+  const void *cluster_dev;
+  int cluster_dtype;
+  long long cluster_stride;
+  double *meat;
+  long long meat_ld;
+  double *sums;
+  int out_on_device;
+  void *stream;
+} bessx_meat_input;
+int bessx_meat_device(const bessx_meat_input *in, int *n_clusters);
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  double coef0;
+  int link;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_stride;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  int kind;
+  const double *factor;
+  long long factor_ld;
+  const long long *cluster_host;
+  const void *cluster_dev;
+  int cluster_dtype;
+  long long cluster_stride;
+  double *info;
+  long long info_ld;
+  double *score;
+  double *meat;
+  long long meat_ld;
+  int out_on_device;
+  void *stream;
+} bessx_sandwich_input;
+int bessx_sandwich_device(const bessx_sandwich_input *in, double *loss, double *sum_w, int *n_clusters);
+int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int link,
+                             int weighted, int kind, int n_clusters, int max_cluster_rows, long long *doubles,
+                             long long *rows_per_slab, int *slabs, long long *cluster_rows_per_slab, int *cluster_slabs,
+                             int *sum_depth, int *sq_depth);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1069,6 +1175,13 @@ int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long
  * [3] L C with the dfbeta epilogue.  *bytes = what stages 1 to 3 must move: n m (item + 5 * 8) + 2 J m 8.  m >= 1. */
 int bessx_op_cox_diag_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int ties, int repeats, double *stage_ms, double *bytes);
+/* The cluster-sum kernel of section 2k alone (and the addition of the partials of clusters longer than a run) timed the
+ * same way for the intercept and the support cols, a u of the library's own and n host labels.  *bytes = what the
+ * algorithm needs: the support and u once, S once (the kernel's re-reads of u, the row order and the run table per four
+ * entries are not counted). */
+int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, const long long *cluster, int repeats, double *avg_ms,
+                            double *bytes);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
