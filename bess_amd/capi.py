@@ -45,6 +45,7 @@ SYMBOLS = [
     "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
     "bessx_cox_diag_device", "bessx_cox_diag_workspace", "bessx_op_cox_diag_bench",
     "bessx_meat_device", "bessx_sandwich_device", "bessx_sandwich_workspace", "bessx_op_sandwich_bench",
+    "bessx_addscore_device", "bessx_addscore_workspace", "bessx_op_addscore_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -161,6 +162,18 @@ class SandwichInput(ctypes.Structure):
                 ("cluster_host", ctypes.POINTER(_ll)), ("cluster_dev", _vp), ("cluster_dtype", _i),
                 ("cluster_stride", _ll), ("info", _vp), ("info_ld", _ll), ("score", _vp), ("meat", _vp),
                 ("meat_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class AddscoreInput(ctypes.Structure):
+    """bessx_addscore_input: bessx_info_input's model and data, the factor of the inverse information in host memory (or
+    null), the candidate columns (or null = all), the candidate block, and where info, score, u, d, s, a and the cross
+    information go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("coef0", _d), ("link", _i), ("y_host", _D), ("y_dev", _vp),
+                ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
+                ("weight_stride", _ll), ("factor", _D), ("factor_ld", _ll), ("candidates", _I), ("q", _i),
+                ("candidate_block", _i), ("info", _D), ("info_ld", _ll), ("score", _D), ("u", _vp), ("d", _vp),
+                ("s", _vp), ("a", _vp), ("cross", _vp), ("cross_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -304,6 +317,10 @@ def lib():
         L.bessx_sandwich_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_ll),
                                                ctypes.POINTER(_ll), _I, ctypes.POINTER(_ll), _I, _I, _I]
         L.bessx_op_sandwich_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, ctypes.POINTER(_ll), _i, _D, _D]
+        L.bessx_addscore_device.argtypes = [ctypes.POINTER(AddscoreInput), _D, _D]
+        L.bessx_addscore_workspace.argtypes = [_i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I, _I,
+                                               ctypes.POINTER(_ll), _I]
+        L.bessx_op_addscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _i, _i, _D]
         _lib = L
     return _lib
 
@@ -1657,6 +1674,160 @@ def op_diag_bench(x, cols, repeats=20):
                                      _ip(cols), cols.size, repeats, ctypes.byref(ms), ctypes.byref(tf),
                                      ctypes.byref(by)))
     return ms.value, tf.value, by.value
+
+
+def _candidates(candidates, p):
+    """(int32 array or None, q) of a candidate list: None = all p columns, else ascending distinct columns of x."""
+    if candidates is None:
+        return None, p
+    cand = np.asarray(candidates)
+    if cand.ndim != 1 or cand.size < 1:
+        raise ValueError("candidates must be a non-empty 1-D list of column numbers or None")
+    if not np.issubdtype(cand.dtype, np.integer):
+        raise ValueError("candidates must be integers")
+    if cand.min() < 0 or cand.max() >= p:
+        raise ValueError("candidates must be columns of X (0 .. %d)" % (p - 1))
+    if (np.diff(cand) <= 0).any():
+        raise ValueError("candidates must be ascending and distinct")
+    return _i32(cand), int(cand.size)
+
+
+def addscore_workspace(n, m, q, candidate_block=0):
+    """What an addscore_device call on n rows with a support of m columns and q candidates needs and how it is split
+    (bessx_addscore_workspace; no device is needed): {"doubles": scratch memory in all (2 n for v and g, the panel of
+    n_pad x Mp, the block workspace), "rows_per_slab", "slabs": the row split, a function of (n, m, q, candidate_block)
+    alone, "block": candidates per block, "block_doubles": the part of the scratch memory beyond v, g and the panel,
+    which does not depend on p, "sum_depth": the additions behind one s_j}."""
+    nd, rps, sl, bl, bd, dp = _ll(0), _ll(0), _i(0), _i(0), _ll(0), _i(0)
+    _check(lib().bessx_addscore_workspace(int(n), int(m), int(q), int(candidate_block), ctypes.byref(nd),
+                                          ctypes.byref(rps), ctypes.byref(sl), ctypes.byref(bl), ctypes.byref(bd),
+                                          ctypes.byref(dp)))
+    return {"doubles": nd.value, "rows_per_slab": rps.value, "slabs": sl.value, "block": bl.value,
+            "block_doubles": bd.value, "sum_depth": dp.value}
+
+
+def addscore_device(x, cols, beta, coef0, y, link="identity", weight=None, factor=None, candidates=None,
+                    want_cross=False, stream=0, candidate_block=0):
+    """The ingredients of the Rao score test of every candidate column against ONE model on a device matrix x (n x p:
+    float64 or float32, any non-negative strides), read where it lies (bessx_addscore_device).  The model and v, g, z,
+    M = len(cols) + 1, info, score, loss, sum_w are information_device's (the same bits).  candidates: None = all p
+    columns, else ascending distinct column numbers.  factor: R, lower triangular (M, M) with inv(info) = R^T R; None =
+    information_device and info_factor are called first (and when the information is not positive definite, s and a
+    are NaN).  With r = inv(info) @ score, for candidate j
+        u_j = sum_i g_i x_ij,   c_j = sum_i v_i x_ij z_i,   d_j = sum_i v_i x_ij^2,   s_j = |R c_j|^2,   a_j = c_j . r
+    Returns {"columns", "u", "d", "s", "a", "info", "score", "loss", "sum_w", "positive_definite"} (NumPy, host) plus
+    "cross" (q, M), the c_j, when want_cross.  The subtractions u - a and d - s are score_test_table's.  One pass over
+    all candidate columns on the fp64 matrix cores; no x-sized temporary; candidates go in blocks of candidate_block (0
+    = the library's choice; a multiple of 16), so scratch beyond the n x Mp panel does not depend on p (addscore_workspace).
+    The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  Not for
+    Cox models, not for groups of columns with more than one degree of freedom, not corrected for selection.
+    len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: addscore_device takes one model per call")
+    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
+    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
+        raise ValueError("beta and coef0 must be finite")
+    cand, q = _candidates(candidates, p)
+    M = cols.size + 1
+    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
+    a = AddscoreInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
+    a.y_stride = yrs
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [weight]
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_host = _dp(wh)
+            keep.append(wh)
+    pd = True
+    if factor is None:
+        first = information_device(x, cols, B.reshape(-1), float(c0[0]), y, link=link, weight=weight, stream=stream)
+        fh, pd = info_factor(first["info"])
+    else:
+        fh = _f64(factor)
+        if fh.shape != (M, M):
+            raise ValueError("factor must have shape (%d, %d), got %s" % (M, M, fh.shape))
+    if pd:
+        a.factor, a.factor_ld = _dp(fh), M
+    a.candidates, a.q, a.candidate_block = _ip(cand), q, int(candidate_block)
+    info, score = np.empty((M, M)), np.empty(M)
+    out = np.full((4, q), np.nan)
+    a.info, a.info_ld, a.score = _dp(info), M, _dp(score)
+    a.u, a.d, a.s, a.a = (out[k].ctypes.data for k in range(4))
+    cross = None
+    if want_cross:
+        cross = np.empty((q, M))
+        a.cross, a.cross_ld = cross.ctypes.data, M
+    a.out_on_device = 0
+    a.stream = int(stream) if stream else None
+    loss, sw = _d(0), _d(0)
+    _check(lib().bessx_addscore_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw)))
+    got = {"columns": np.arange(p, dtype=np.int64) if cand is None else cand.astype(np.int64), "u": out[0], "d": out[1],
+           "s": out[2], "a": out[3], "info": info, "score": score, "loss": loss.value, "sum_w": sw.value,
+           "positive_definite": bool(pd), "support": cols.astype(np.int64)}
+    if want_cross:
+        got["cross"] = cross
+    return got
+
+
+def score_test_table(got, link):
+    """The Rao score test of every candidate from what addscore_device (or the NumPy route) returns, on the host in
+    fp64: adj = u - a, variance = d - s, statistic = adj^2 / (dispersion * variance) where variance is finite and > 0,
+    else NaN; p_value = erfc(sqrt(statistic / 2)), chi-square with 1 degree of freedom.  dispersion is wald_table's:
+    loss / (sum_w - M) for the identity link (NaN when sum_w - M <= 0), 1 otherwise.  A candidate that is in the model's
+    support ("support" of got) has in_model = True and NaN for statistic and p_value: its variance is rounding noise.
+    For the identity link the statistic is the F-to-enter numerator over the CURRENT model's residual variance.
+    Returns {"columns", "score", "variance", "statistic", "p_value", "in_model", "dispersion"}.  Selection is not
+    corrected for."""
+    import math
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    u, a = np.asarray(got["u"], dtype=np.float64), np.asarray(got["a"], dtype=np.float64)
+    d, s = np.asarray(got["d"], dtype=np.float64), np.asarray(got["s"], dtype=np.float64)
+    columns = np.asarray(got["columns"], dtype=np.int64)
+    M = np.asarray(got["score"]).size
+    if link == "identity":
+        dof = float(got["sum_w"]) - M
+        dispersion = float(got["loss"]) / dof if dof > 0 else float("nan")
+    else:
+        dispersion = 1.0
+    adj, var = u - a, d - s
+    in_model = np.isin(columns, np.asarray(got.get("support", np.zeros(0)), dtype=np.int64))
+    ok = np.isfinite(var) & (var > 0) & ~in_model
+    stat = np.full(columns.size, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        stat[ok] = (adj[ok] * adj[ok]) / (dispersion * var[ok])
+    pv = np.array([math.erfc(math.sqrt(v / 2.0)) if (v == v and v >= 0) else float("nan") for v in stat])
+    return {"columns": columns, "score": adj, "variance": var, "statistic": stat, "p_value": pv, "in_model": in_model,
+            "dispersion": dispersion}
+
+
+def op_addscore_bench(x, cols, candidates=None, candidate_block=0, repeats=5):
+    """ms per stage of the score-test kernels on the device matrix x for the support cols, device events, each over
+    every block of candidates: {"pack", "cross", "finish", "statistic"} (bessx_op_addscore_bench)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    cand, q = _candidates(candidates, dx.shape[1])
+    ms = (_d * 4)()
+    _check(lib().bessx_op_addscore_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, _ip(cand), q, int(candidate_block), repeats, ms))
+    return dict(zip(("pack", "cross", "finish", "statistic"), [float(v) for v in ms]))
 
 
 TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties

@@ -3641,3 +3641,326 @@ int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// score tests of candidate columns against one model on a caller's device matrix (include/bessx.h section 2l)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the fields bessx_addscore_input shares with bessx_info_input, as section 2g's helpers take them
+bessx_info_input addscore_as_info(const bessx_addscore_input *in) {
+  bessx_info_input a{};
+  a.x = in->x;
+  a.x_dtype = in->x_dtype;
+  a.x_row_stride = in->x_row_stride;
+  a.x_col_stride = in->x_col_stride;
+  a.n = in->n;
+  a.p = in->p;
+  a.cols = in->cols;
+  a.m = in->m;
+  a.beta = in->beta;
+  a.coef0 = in->coef0;
+  a.link = in->link;
+  a.y_host = in->y_host;
+  a.y_dev = in->y_dev;
+  a.y_dtype = in->y_dtype;
+  a.y_stride = in->y_stride;
+  a.weight_host = in->weight_host;
+  a.weight_dev = in->weight_dev;
+  a.weight_dtype = in->weight_dtype;
+  a.weight_stride = in->weight_stride;
+  a.info = in->info;
+  a.info_ld = in->info_ld;
+  a.score = in->score;
+  a.out_on_device = 0;
+  a.stream = in->stream;
+  return a;
+}
+
+int addscore_check_block(const std::string &w, int block) {
+  if (block < 0 || block % 16) return fail(BESSX_ERR_ARG, w + ": candidate_block must be 0 or a positive multiple of 16");
+  return 0;
+}
+
+// everything about the call that needs no device
+int addscore_check_args(const char *who, const bessx_addscore_input *in, const double *loss, const double *sum_w) {
+  const std::string w(who);
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const bessx_info_input a = addscore_as_info(in);
+  if (int rc = info_check_args(who, &a, loss, sum_w)) return rc;
+  if (!in->u || !in->d) return fail(BESSX_ERR_ARG, w + ": null argument (u, d)");
+  if (in->factor && (!in->s || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (s, a)");
+  if (in->q < 1) return fail(BESSX_ERR_ARG, w + ": q must be at least 1");
+  if (!in->candidates && in->q != in->p) return fail(BESSX_ERR_ARG, w + ": without a candidate list q must be p");
+  if (in->candidates) {
+    for (int j = 0; j < in->q; j++) {
+      if (in->candidates[j] < 0 || in->candidates[j] >= in->p)
+        return fail(BESSX_ERR_ARG, w + ": a candidate is not a column of x");
+      if (j > 0 && in->candidates[j] <= in->candidates[j - 1])
+        return fail(BESSX_ERR_ARG, w + ": candidates must be ascending and distinct");
+    }
+  }
+  if (int rc = addscore_check_block(w, in->candidate_block)) return rc;
+  if (in->cross && in->cross_ld < (long long)in->m + 1)
+    return fail(BESSX_ERR_ARG, w + ": cross_ld must be at least m + 1");
+  if (in->factor) {
+    if (in->factor_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m + 1");
+    for (long long j = 0; j <= in->m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  return 0;
+}
+
+// sc, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int addscore_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const bessx_addscore_input *in, double *loss,
+                 double *sum_w, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const bessx_info_input ia = addscore_as_info(in);
+  const bessx_eval_input e = info_as_eval(&ia);
+  const int f32 = in->x_dtype == BESSX_F32, m = in->m, q = in->q, block = in->candidate_block;
+  const long long n = in->n, nv = (n + 1) / 2 * 2;
+  const size_t M = (size_t)m + 1, Q = (size_t)q;
+  const bool with_stat = in->factor != nullptr, want_c = in->cross != nullptr;
+  long long panel = 0, blk = 0, rps = 0;
+  int slabs = 0, cb = 0, depth = 0;
+  addscore_split(n, m, q, block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  int *cols_d = nullptr, *cand_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *iwork = nullptr, *res = nullptr, *istage = nullptr, *vg = nullptr, *P = nullptr,
+         *work = nullptr, *ostage = nullptr;
+  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
+  EvalData d;
+  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  // 1. info, score, loss and sum_w: launch_info as bessx_info_device runs it (the same bits)
+  HIPX(sc.alloc(&iwork, (size_t)info_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, m, in->link,
+                                                d.w != nullptr)));
+  HIPX(sc.alloc(&res, 3));
+  HIPX(sc.alloc(&istage, M * M + M));
+  HIPX(launch_info(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, B_d, c_d, in->link, d, iwork, res, istage,
+                   (long long)M, istage + M * M, st));
+  h.resize(3 + M * M + 2 * M);
+  HIPX(hipMemcpyAsync(h.data(), res, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipMemcpyAsync(h.data() + 3, istage, (M * M + M) * sizeof(double), hipMemcpyDeviceToHost, st));
+  // the row weights, always by rows: the same bits under every layout of x
+  HIPX(sc.alloc(&vg, (size_t)(2 * nv)));
+  HIPX(launch_info_vg(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, B_d, c_d, in->link, d, vg, vg + nv,
+                      st));
+  HIPX(sc.alloc(&P, (size_t)panel));
+  HIPX(sc.alloc(&work, (size_t)blk));
+  if (in->candidates) {
+    HIPX(sc.alloc(&cand_d, Q));
+    HIPX(hipMemcpyAsync(cand_d, in->candidates, Q * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  HIPX(launch_addscore_pack(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, q, block, vg, vg + nv, P, st));
+  // the score behind r, summed by this section's own kernels over the list (constant column, support): the same bits
+  // under every layout of x, which launch_info's score is not
+  std::vector<int> cand0;
+  double *u0 = nullptr;
+  if (with_stat) {
+    long long panel0 = 0, blk0 = 0, rps0 = 0;
+    int slabs0 = 0, cb0 = 0, depth0 = 0, *cand0_d = nullptr;
+    double *work0 = nullptr;
+    addscore_split(n, m, (int)M, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+    cand0.assign(M, -1);
+    std::copy(in->cols, in->cols + m, cand0.begin() + 1);
+    HIPX(sc.alloc(&cand0_d, M));
+    HIPX(sc.alloc(&work0, (size_t)blk0));
+    HIPX(sc.alloc(&u0, 2 * M));
+    HIPX(hipMemcpyAsync(cand0_d, cand0.data(), M * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(launch_addscore_blocks(in->x, f32, in->x_row_stride, in->x_col_stride, n, m, cand0_d, (int)M, 0, P, work0, 0, u0,
+                                u0 + M, nullptr, nullptr, nullptr, 0, 0, st));
+    HIPX(hipMemcpyAsync(h.data() + 3 + M * M + M, u0, M * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  *loss = h[0];
+  *sum_w = d.w ? h[2] : (double)in->n;
+  for (size_t j = 0; j < M; j++) std::copy(h.begin() + 3 + j * M, h.begin() + 3 + (j + 1) * M, in->info + j * in->info_ld);
+  std::copy(h.begin() + 3 + M * M, h.begin() + 3 + M * M + M, in->score);
+  if (with_stat) {
+    // r = inverse(info) U = R^T (R U), on the host in fp64
+    const double *U0 = h.data() + 3 + M * M + M;
+    std::vector<double> t(M, 0.0), r(M, 0.0);
+    for (size_t j = 0; j < M; j++)
+      for (size_t k = 0; k <= j; k++) t[j] += in->factor[j * in->factor_ld + k] * U0[k];
+    for (size_t j = 0; j < M; j++)
+      for (size_t k = 0; k <= j; k++) r[k] += in->factor[j * in->factor_ld + k] * t[j];
+    pk.resize((size_t)diag_factor_doubles(m + 1));
+    addscore_pack_factor(in->factor, in->factor_ld, r.data(), m, pk.data());
+    HIPX(hipMemcpyAsync(work + blk - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice,
+                        st));
+  }
+  double *u = in->u, *dd = in->d, *s = in->s, *a = in->a, *C = in->cross;
+  long long ldc = in->cross_ld;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&ostage, 4 * Q + (want_c ? Q * M : 0)));
+    u = ostage, dd = ostage + Q, s = ostage + 2 * Q, a = ostage + 3 * Q;
+    C = want_c ? ostage + 4 * Q : nullptr;
+    ldc = (long long)M;
+  }
+  HIPX(launch_addscore_blocks(in->x, f32, in->x_row_stride, in->x_col_stride, n, m, cand_d, q, block, P, work,
+                              with_stat ? 1 : 0, u, dd, s, a, C, ldc, 0, st));
+  if (!in->out_on_device) {
+    h.resize(4 * Q + (want_c ? Q * M : 0));
+    HIPX(hipMemcpyAsync(h.data(), ostage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device) {
+    std::copy(h.begin(), h.begin() + Q, in->u);
+    std::copy(h.begin() + Q, h.begin() + 2 * Q, in->d);
+    if (with_stat) {
+      std::copy(h.begin() + 2 * Q, h.begin() + 3 * Q, in->s);
+      std::copy(h.begin() + 3 * Q, h.begin() + 4 * Q, in->a);
+    }
+    if (want_c)
+      for (size_t j = 0; j < Q; j++)
+        std::copy(h.begin() + 4 * Q + j * M, h.begin() + 4 * Q + (j + 1) * M, in->cross + j * in->cross_ld);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_addscore_workspace(int n, int m, int q, int candidate_block, long long *doubles, long long *rows_per_slab,
+                             int *slabs, int *block, long long *block_doubles, int *sum_depth) {
+  if (!doubles || !rows_per_slab || !slabs || !block || !block_doubles || !sum_depth)
+    return fail(BESSX_ERR_ARG, "addscore_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "addscore_workspace: empty matrix");
+  if (q < 1) return fail(BESSX_ERR_ARG, "addscore_workspace: q must be at least 1");
+  if (int rc = addscore_check_block("addscore_workspace", candidate_block)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "addscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  long long panel = 0;
+  addscore_split(n, m, q, candidate_block, &panel, block_doubles, rows_per_slab, slabs, block, sum_depth);
+  // (plus the block workspace of the score behind r, whose candidates are the constant column and the support)
+  long long panel0 = 0, blk0 = 0, rps0 = 0;
+  int slabs0 = 0, cb0 = 0, depth0 = 0;
+  addscore_split(n, m, m + 1, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+  *block_doubles += blk0 + 2 * ((long long)m + 1);
+  *doubles = 2 * (((long long)n + 1) / 2 * 2) + panel + *block_doubles;
+  return BESSX_OK;
+}
+
+int bessx_addscore_device(const bessx_addscore_input *in, double *loss, double *sum_w) {
+  if (int rc = addscore_check_args("addscore_device", in, loss, sum_w)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("addscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->y_dev) {
+    if (int rc = check_device_matrix("addscore_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: y is not on the device that owns x");
+  }
+  if (in->weight_dev) {
+    if (int rc = check_device_matrix("addscore_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
+                                     in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: weight is not on the device that owns x");
+  }
+  if (in->out_on_device) {
+    double *const vec[4] = {in->u, in->d, in->factor ? in->s : nullptr, in->factor ? in->a : nullptr};
+    for (double *v : vec) {
+      if (!v) continue;
+      if (int rc = check_device_matrix("addscore_device: u, d, s, a", v, BESSX_F64, 1, 0, in->q, 1, &od)) return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: an output is not on the device that owns x");
+    }
+    if (in->cross) {
+      if (int rc = check_device_matrix("addscore_device: cross", in->cross, BESSX_F64, in->cross_ld, 1, in->q, in->m + 1,
+                                       &od))
+        return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: cross is not on the device that owns x");
+    }
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> pk, h;
+    rc = addscore_run(sc, pk, h, in, loss, sum_w, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, const int *candidates, int q, int candidate_block, int repeats,
+                            double *stage_ms) {
+  if (!x || repeats < 1 || !stage_ms || q < 1) return fail(BESSX_ERR_ARG, "op_addscore_bench: bad arguments");
+  if (int rc = predict_check_model("op_addscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_addscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = addscore_check_block("op_addscore_bench", candidate_block)) return rc;
+  if (!candidates && q != p) return fail(BESSX_ERR_ARG, "op_addscore_bench: without a candidate list q must be p");
+  if (candidates)
+    for (int j = 0; j < q; j++)
+      if (candidates[j] < 0 || candidates[j] >= p || (j > 0 && candidates[j] <= candidates[j - 1]))
+        return fail(BESSX_ERR_ARG, "op_addscore_bench: candidates must be ascending distinct columns of x");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_addscore_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t M = (size_t)m + 1, Q = (size_t)q;
+  long long panel = 0, blk = 0, rps = 0;
+  int slabs = 0, cb = 0, depth = 0;
+  addscore_split(n, m, q, candidate_block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  // row weights and a factor of the library's own: the scaled identity plus a small lower triangle
+  std::vector<double> v((size_t)n, 0.25), g((size_t)n), R(M * M, 0.0), r(M, 1.0 / 128.0),
+      pk((size_t)diag_factor_doubles(m + 1));
+  for (size_t i = 0; i < g.size(); i++) g[i] = (i % 2) ? -0.5 : 0.5;
+  for (size_t j = 0; j < M; j++)
+    for (size_t k = 0; k <= j; k++) R[j * M + k] = (j == k ? 1.0 : 1.0 / 64.0) / std::sqrt((double)n);
+  addscore_pack_factor(R.data(), (long long)M, r.data(), m, pk.data());
+  int *cols_d = nullptr, *cand_d = nullptr;
+  double *v_d = nullptr, *g_d = nullptr, *P = nullptr, *work = nullptr, *out = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&v_d, v.size()));
+  HIPX(sc.alloc(&g_d, g.size()));
+  HIPX(sc.alloc(&P, (size_t)panel));
+  HIPX(sc.alloc(&work, (size_t)blk));
+  HIPX(sc.alloc(&out, 4 * Q));
+  if (m > 0) HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+  if (candidates) {
+    HIPX(sc.alloc(&cand_d, Q));
+    HIPX(hipMemcpy(cand_d, candidates, Q * sizeof(int), hipMemcpyHostToDevice));
+  }
+  HIPX(hipMemcpy(v_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(work + blk - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  auto run = [&](int stage) {
+    if (stage == 0)
+      return launch_addscore_pack(x, f32, row_stride, col_stride, n, cols_d, m, q, candidate_block, v_d, g_d, P, nullptr);
+    return launch_addscore_blocks(x, f32, row_stride, col_stride, n, m, cand_d, q, candidate_block, P, work, 1, out,
+                                  out + Q, out + 2 * Q, out + 3 * Q, nullptr, 0, stage, nullptr);
+  };
+  // (stage 0 = pack, 1 = cross, 2 = finish, 3 = statistic; each over every block of candidates, in this order, so that
+  // a later stage finds the earlier one's results of the last block)
+  for (int stage = 0; stage < 4; stage++) {
+    HIPX(run(stage));  // the warm-up
+    HIPX(hipEventRecord(e0, nullptr));
+    for (int i = 0; i < repeats; i++) HIPX(run(stage));
+    HIPX(hipEventRecord(e1, nullptr));
+    HIPX(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    stage_ms[stage] = ms / repeats;
+  }
+  return BESSX_OK;
+}
+
+}  // extern "C"

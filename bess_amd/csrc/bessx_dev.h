@@ -172,6 +172,22 @@ hipError_t launch_diag_eta(const void *src, int f32, long long rs, long long cs,
 hipError_t launch_diag_lev(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                            const double *pk, const double *vw, const double *rp, const double *rd, double phi,
                            double *o_h, double *o_sp, double *o_sd, double *o_ck, hipStream_t st);
+// score tests of candidate columns against one model (bessx_k_addscore.hip).  addscore_split: for n rows, m support
+// columns, q candidates and a candidate block asked for (0: the library's, else a multiple of 16), the doubles of the
+// panel P and of the block workspace (partials, the block's rows of C, and LAST the packed factor:
+// diag_factor_doubles(m + 1) doubles), the row split, the block used and the additions behind a candidate's sum of
+// squares.  _pack_factor runs on the host: R ((m + 1) x (m + 1), lower triangular) with r appended as one more row.
+// _pack writes P from the n-vectors v and g; _blocks runs cross, finish and (with_stat) the statistic kernel per block
+// of candidates (cand: q ascending columns, -1 = the constant column, or null = 0 .. q - 1): u, d, s, a q doubles each, Cout q x ldc or null; only
+// = 1 / 2 / 3 launches one of the three kernels alone.  m + 1 <= INFO_M_MAX.  Everything else is device memory.
+void addscore_split(long long n, int m, int q, int block, long long *panel_doubles, long long *block_doubles,
+                    long long *rows_per_slab, int *slabs, int *cand_block, int *stat_depth);
+void addscore_pack_factor(const double *R, long long ld, const double *r, int m, double *pk);
+hipError_t launch_addscore_pack(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                                int q, int block, const double *vw, const double *gw, double *P, hipStream_t st);
+hipError_t launch_addscore_blocks(const void *src, int f32, long long rs, long long cs, long long n, int m, const int *cand,
+                                  int q, int block, const double *P, double *work, int with_stat, double *u, double *d,
+                                  double *s, double *a, double *Cout, long long ldc, int only, hipStream_t st);
 // observed information and score of one Cox model (bessx_k_coxinfo.hip), the kernels between the predictor pass, the
 // scans and the two launch_info_gram sweeps.  _gather: W(c, k) = e[k] * x(rowof[k], cols[c]), m x n position-major.
 // _means: U(j, c) = S1(p, c) / S0[p] for jptr[p] <= j < jptr[p + 1], S1 the suffix sums of W along k (scr: ceil(n / 1024)

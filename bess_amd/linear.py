@@ -650,6 +650,100 @@ class bess_base:
         out.update(cols=cols, dispersion=dispersion, positive_definite=bool(pd))
         return out
 
+    # ---- score tests of the columns left out ---------------------------------------------------------------------
+    @staticmethod
+    def _score_tests_host(link, X, cols, beta, coef0, y, w, cand):
+        """addscore_device's quantities in fp64 NumPy with the same definitions: X (n, p), cols the support, beta (m,),
+        y (n,), w (n,), cand the candidate columns (int64) or None = all.  Matrix products over the n rows."""
+        n, p = X.shape
+        Xs = X[:, cols]
+        eta = Xs @ beta + coef0
+        if link == "identity":
+            v, g, f = w.copy(), w * (y - eta), (y - eta) ** 2
+        elif link == "logistic":
+            t = np.exp(-np.abs(eta))
+            pr = np.where(eta >= 0, 1.0, t) / (1.0 + t)
+            v, g = w * (t / ((1.0 + t) * (1.0 + t))), w * (y - pr)
+            f = np.maximum(eta, 0.0) + np.log1p(t) - y * eta
+        else:
+            e = np.exp(eta)
+            v, g, f = w * e, w * (y - e), e - y * eta
+        Z = np.column_stack([np.ones(n), Xs])
+        P = v[:, None] * Z
+        info = Z.T @ P
+        info = np.tril(info) + np.tril(info, -1).T
+        score = Z.T @ g
+        columns = np.arange(p, dtype=np.int64) if cand is None else np.asarray(cand, dtype=np.int64)
+        R, pd = capi.info_factor(info)
+        q = columns.size
+        u, d, C = np.empty(q), np.empty(q), np.empty((q, Z.shape[1]))
+        for j0 in range(0, q, 2048):  # (in blocks: no X-sized temporary here either)
+            XJ = X[:, columns[j0:j0 + 2048]]
+            u[j0:j0 + 2048] = XJ.T @ g
+            C[j0:j0 + 2048] = XJ.T @ P
+            d[j0:j0 + 2048] = v @ (XJ * XJ)
+        if pd:
+            r = R.T @ (R @ score)
+            T = C @ np.tril(R).T
+            s, a = np.sum(T * T, axis=1), C @ r
+        else:
+            s, a = np.full(q, np.nan), np.full(q, np.nan)
+        return {"columns": columns, "u": u, "d": d, "s": s, "a": a, "info": info, "score": score,
+                "loss": float((w * f).sum()), "sum_w": float(w.sum()), "positive_definite": bool(pd),
+                "support": np.asarray(cols, dtype=np.int64), "cross": C}
+
+    def score_tests(self, X, y, weight=None, candidates=None):
+        """Did the selection leave out a column that matters?  The Rao score test of every candidate column against the
+        fitted model on the rows (X, y) -- R's add1(fit, scope, test = "Rao"); for Lm the F-to-enter statistic over the
+        current model's residual variance -- without refitting anything: capi.score_test_table's dict -- columns, score
+        (the adjusted score u - a), variance (d - s), statistic = score^2 / (dispersion * variance), p_value (chi-square,
+        1 degree of freedom), in_model, dispersion -- plus cols, the model's support.  candidates: None = all p columns,
+        else ascending distinct column numbers.  A candidate that is in the support has in_model = True and NaN for
+        statistic and p_value; a candidate whose variance is not positive (a column that the support reproduces) has
+        NaN as well.  The information and the dispersion are inference()'s.  An X in GPU memory is read in place on
+        torch's current stream in one pass over the candidate columns on the fp64 matrix cores
+        (capi.addscore_device), with no X-sized temporary, and y and weight may be device arrays too; a NumPy X is
+        served in fp64 NumPy with the same definitions.  When the information is not positive definite statistic and
+        p_value are NaN and nothing is raised.  A model fitted with group selection is tested column by column, one
+        degree of freedom each: group tests with more degrees of freedom are not offered.  Selection is not corrected
+        for: the p-values are those of a test chosen before seeing the data.  Cox: None (its score test needs the
+        risk-set means of all p columns).  A 2-D beta (Lm fitted to several responses) raises ValueError."""
+        on_device = capi.is_device_array(X)
+        shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
+        if len(shape) != 2 or shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        n = shape[0]
+        cand, _ = capi._candidates(candidates, self.p)
+        if self.model_type_int == 4:
+            return None
+        beta, cols, coef0, multi = self._model_arrays()
+        if multi:
+            raise ValueError("score_tests() takes one model: this Lm was fitted to %d responses (a 2-D beta), which is "
+                             "not supported" % beta.shape[1])
+        link = self._LINK[self.model_type_int]
+        y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
+        ysize = capi._DeviceArray(y, "y").size if y_dev else np.size(y)
+        if ysize != n:
+            raise ValueError("X.shape(0) should be equal to y.size")
+        if weight is not None and (capi._DeviceArray(weight, "weight").size if w_dev else np.size(weight)) != n:
+            raise ValueError("X.shape(0) should be equal to weight.size")
+        if on_device:
+            if not y_dev:
+                y = np.asarray(y, dtype=np.float64).reshape(-1)
+            got = capi.addscore_device(X, cols, beta[cols], coef0[0], y, link=link, weight=weight, candidates=cand,
+                                       stream=_current_stream(X))
+        else:
+            yh = (capi.device_to_host(y, _current_stream(y)) if y_dev else np.asarray(y, dtype=np.float64)).reshape(-1)
+            if weight is None:
+                w = np.ones(n)
+            else:
+                w = (capi.device_to_host(weight, _current_stream(weight)) if w_dev
+                     else np.asarray(weight, dtype=np.float64)).reshape(-1)
+            got = self._score_tests_host(link, np.asarray(X, dtype=np.float64), cols, beta[cols], coef0[0], yh, w, cand)
+        out = capi.score_test_table(got, link)
+        out["cols"] = cols
+        return out
+
     def score(self, X, y, weight=None):
         """r2 (Lm), accuracy (Logistic) or d2 (Poisson) of evaluate(X, y, weight); None for Cox."""
         res = self.evaluate(X, y, weight)

@@ -777,6 +777,83 @@ int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_co
                              int weighted, int kind, int n_clusters, int max_cluster_rows, long long *doubles,
                              long long *rows_per_slab, int *slabs, long long *cluster_rows_per_slab, int *cluster_slabs,
                              int *sum_depth, int *sq_depth);
+/* ---------------------------------------------------------------------------------------
+ * 2l. Rao score tests of candidate columns against ONE fitted model on an X already in GPU memory
+ *     (bessx_k_addscore.hip): did the selection leave out a column that matters?  Stateless like sections 2c to 2k.  x,
+ *     n, p, cols, m, beta, coef0, link, y, weight, stream, info, info_ld, score, loss, sum_w: section 2g (info and score
+ *     are HOST memory here); v_i, g_i, z_i, M = m + 1 as there.  Candidates: q ascending distinct column numbers in HOST
+ *     memory, or null = all p columns (q = p).  factor = R, M x M lower triangular in HOST memory as in section 2i
+ *     (inverse(info) = R^T R; its strict upper triangle is never read), and r = R^T (R score) = inverse(info) score,
+ *     formed on the host in fp64.  For candidate j with column x_j:
+ *         u_j = sum_i g_i x_ij                 raw score
+ *         c_j = sum_i v_i x_ij z_i             cross information, M entries; cross[j * cross_ld + k], cross_ld >= M
+ *         d_j = sum_i v_i x_ij^2               curvature
+ *         s_j = || R c_j ||^2                  curvature explained by the support
+ *         a_j = c_j . r                        shift of the score (0 at the unpenalised optimum)
+ *     The score statistic is (u_j - a_j)^2 / (dispersion (d_j - s_j)): the two subtractions, which can cancel, are left
+ *     to the caller's fp64 host code.  A candidate that is in the support has d_j - s_j = rounding noise.  factor null:
+ *     s and a are not formed (and may be null); cross null: c_j is not returned.  u, d, s, a (q values each) and cross
+ *     are device memory of x's device when out_on_device != 0 (checked as in section 2c), else host memory.
+ *     Steps: the row weights v, g by the threads-along-rows predictor pass (the same bits under every layout of x);
+ *     info, score, loss and sum_w by section 2g's launches (the same bits as bessx_info_device); the panel P = (v_i z_i,
+ *     g_i, zeros) of n x Mp doubles, Mp = 16 ceil((M + 1) / 16), written once -- the one place where the support is
+ *     gathered; X_J^T P in 16 x 16 tiles on the fp64 matrix cores with the candidates read from x in place and P shared
+ *     by four candidate tile rows through double-buffered LDS; a fixed-order addition of the row slabs' partials; and
+ *     C Rx^T on the matrix cores (Rx = R with r appended as one more row, only the steps at or below each tile's
+ *     diagonal) whose squares are added per candidate in a fixed order.  No floating-point atomics: the same call gives
+ *     the same bits, and u, d, s, a, cross are the same bits under every layout of the same element type.  Rows past n,
+ *     columns that are neither in the support nor candidates and the padding of tiles are not read; a NaN inside the
+ *     view propagates by IEEE rules.  No x-sized temporary is made: candidates are processed in blocks of
+ *     candidate_block columns (0 = the library's choice, else a positive multiple of 16), so scratch memory is 2 n + n_pad
+ *     Mp doubles plus a block workspace that does not depend on p.
+ *     bessx_addscore_workspace needs no device: *doubles of scratch memory in all, the row split (*rows_per_slab,
+ *     *slabs: a function of n, m, q and candidate_block alone), the *block of candidates used, the *block_doubles of it
+ *     that do not depend on p, and *sum_depth, the additions behind one s_j.  An entry of u, c or d is a chain of at
+ *     most rows_per_slab + ceil(slabs / 16) + 4 additions.
+ *     m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED; q >= 1; n <= 2^31 - 1.  Every argument error is found before any
+ *     device call (BESSX_ERR_ARG: the messages of sections 2d / 2g / 2i; candidates not ascending and distinct or not
+ *     columns of x; q != p without a list; a candidate_block that is not a multiple of 16).  Scratch memory is released
+ *     before the call returns.  Out of scope: Cox models, tests of groups of columns with more than one degree of
+ *     freedom, any correction for selection.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  double coef0;
+  int link;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_stride;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  const double *factor;
+  long long factor_ld;
+  const int *candidates;
+  int q;
+  int candidate_block;
+  double *info;
+  long long info_ld;
+  double *score;
+  double *u;
+  double *d;
+  double *s;
+  double *a;
+  double *cross;
+  long long cross_ld;
+  int out_on_device;
+  void *stream;
+} bessx_addscore_input;
+int bessx_addscore_device(const bessx_addscore_input *in, double *loss, double *sum_w);
+int bessx_addscore_workspace(int n, int m, int q, int candidate_block, long long *doubles, long long *rows_per_slab,
+                             int *slabs, int *block, long long *block_doubles, int *sum_depth);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1182,6 +1259,12 @@ int bessx_op_cox_diag_bench(const void *x, int dtype, long long row_stride, long
 int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, const long long *cluster, int repeats, double *avg_ms,
                             double *bytes);
+/* The four kernels of section 2l timed the same way, from row weights and a factor of the library's own, each over
+ * every block of candidates: stage_ms[0] the pack of the panel, [1] the cross product on the matrix cores, [2] the
+ * addition of the partials, [3] the statistic kernel.  candidates / q / candidate_block as in section 2l. */
+int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, const int *candidates, int q, int candidate_block, int repeats,
+                            double *stage_ms);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
