@@ -35,6 +35,7 @@ SYMBOLS = [
     "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
     "bessx_op_cox_state", "bessx_op_cox_score", "bessx_op_cox_score_multi", "bessx_op_glm_gh", "bessx_op_glm_irls", "bessx_op_glm_irls_geometry",
+    "bessx_op_group_scores", "bessx_op_group_lsq",
     "bessx_op_xtv_multi", "bessx_op_xtv_multi_bench", "bessx_session_set_responses", "bessx_session_sequential_path_multi",
     "bessx_session_create_device", "bessx_session_set_responses_device", "bessx_pywrap_bess_device", "bessx_op_ingest",
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
@@ -278,6 +279,8 @@ def lib():
         L.bessx_op_glm_gh.argtypes = [_i, _D, _i, _i, _D, _D, _D, _I, _i, _D, _d, _d, _D, _D, _D, _D]
         L.bessx_op_glm_irls.argtypes = [_i, _i, _i, _i, _d, _i, _D, _i, _i, _D, _D, _D, _I, _i, _D, _D, _D, _D, _D, _D, _I]
         L.bessx_op_glm_irls_geometry.argtypes = [_i, _i, _I]
+        L.bessx_op_group_scores.argtypes = [_D, _i, _i, _i, _I, _i, _D, _D, _D, _i, _d, _d, _vp, _D, _i, _D, _D, _D]
+        L.bessx_op_group_lsq.argtypes = [_D, _i, _i, _I, _i, _D, _vp, _D]
         L.bessx_op_xtv_multi.argtypes = [_D, _i, _i, _i, _D, _D, _i, _D, _D]
         L.bessx_op_xtv_multi_bench.argtypes = [_i, _i, _i, _i, _i, _D, _D]
         L.bessx_op_topk_bench.argtypes = [_i, _i, _i, _i, _D]
@@ -1065,6 +1068,64 @@ def op_glm_irls(family, x, y, cols, bcur, route=-1, t=0, wfloor=1, lam=0.0, rows
     five = taken.value == 0
     return {"gram": np.array(gram), "ll": ll.value, "bnext": bnext, "route": taken.value, "wv": wv if five else None,
             "z": z if five else None}
+
+
+def _group_op_layout(gidx, p):
+    gidx = _i32(gidx).reshape(-1)
+    sizes = np.diff(np.concatenate([gidx, [p]])).astype(np.int64)
+    return gidx, sizes, np.concatenate([[0], np.cumsum(sizes * sizes)])
+
+
+def _flags(always, N):
+    if always is None:
+        return None, None
+    fl = np.ascontiguousarray(always, dtype=np.uint8).reshape(-1)
+    assert fl.size == N
+    return fl, fl.ctypes.data_as(_vp)
+
+
+def op_group_scores(x, gidx, beta_dense, w1=None, w2=None, lm=False, n_t=1.0, lam=0.0, always=None, part=None,
+                    dcol=None, cshift=0, p=None):
+    """The group moment and score kernels alone (bessx_op_group_scores): a dict of mblk (list of the N blocks, s x s
+    each), mblk_flat, dcol (p; given as `dcol`, zeros without, and overwritten only where w2 is given) and bd (3 x N: row
+    m = eig_mode m).  gidx: the groups' first columns; part: nrb x p (lm).  With cshift > 0, x holds the columns from
+    cshift on only (p then has to be given) and the groups before that column are not launched."""
+    x = np.asfortranarray(x, dtype=np.float64)
+    n = x.shape[0]
+    p = x.shape[1] + int(cshift) if p is None else int(p)
+    assert x.shape[1] == p - int(cshift)
+    gidx, sizes, off = _group_op_layout(gidx, p)
+    N = gidx.size
+    beta = _f64(beta_dense).reshape(-1)
+    assert beta.size == p
+    w1 = None if w1 is None else _f64(w1)
+    w2 = None if w2 is None else _f64(w2)
+    nrb = 0
+    if part is not None:
+        part = np.ascontiguousarray(np.atleast_2d(part), dtype=np.float64)
+        assert part.shape[1] == p
+        nrb = part.shape[0]
+    dc = np.zeros(p) if dcol is None else np.array(dcol, dtype=np.float64).reshape(-1)
+    assert dc.size == p
+    flat, bd = np.zeros(max(int(off[-1]), 1)), np.zeros((3, N))
+    fl, flp = _flags(always, N)
+    _check(lib().bessx_op_group_scores(_dp(x), n, p, int(cshift), _ip(gidx), N, _dp(w1), _dp(w2), _dp(beta), int(bool(lm)),
+                                       float(n_t), float(lam), flp, _dp(part), nrb, _dp(flat), _dp(dc), _dp(bd)))
+    blocks = [flat[off[g]:off[g + 1]].reshape(sizes[g], sizes[g], order="F").copy() for g in range(N)]
+    return {"mblk": blocks, "mblk_flat": flat[:int(off[-1])], "dcol": dc, "bd": bd}
+
+
+def op_group_lsq(x, gidx, yw, always=None):
+    """Grouped LM screening alone (bessx_op_group_lsq): score (N) = |(X_g^T X_g)^-1 X_g^T yw|^2 / s_g."""
+    x = np.asfortranarray(x, dtype=np.float64)
+    n, p = x.shape
+    gidx, _, _ = _group_op_layout(gidx, p)
+    yw = _f64(yw)
+    assert yw.size == n
+    score = np.zeros(gidx.size)
+    fl, flp = _flags(always, gidx.size)
+    _check(lib().bessx_op_group_lsq(_dp(x), n, p, _ip(gidx), gidx.size, _dp(yw), flp, _dp(score)))
+    return score
 
 
 def op_glm_irls_geometry(T0, n):

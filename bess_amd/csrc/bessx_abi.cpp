@@ -931,6 +931,124 @@ int bessx_op_glm_gh(int family, const double *x, int n, int p, const double *y, 
   return BESSX_OK;
 }
 
+namespace {
+
+// first column, width and block offset (sum of s^2) of every group, as a session holds them, on the device: gd, gd + N,
+// gd + 2 N (N + 1 offsets)
+struct GroupOpLayout {
+  int smax = 1;
+  std::vector<int> sz, off;
+  int *gd = nullptr;
+};
+
+int group_op_layout(const char *who, Owner &sc, const int *gidx, int N, int p, GroupOpLayout *o) {
+  if (!gidx || N < 1 || p < 1 || N > p || gidx[0] != 0) return fail(BESSX_ERR_ARG, std::string(who) + ": bad group starts");
+  o->sz.resize((size_t)N);
+  o->off.assign((size_t)N + 1, 0);
+  long long tot = 0;
+  for (int g = 0; g < N; g++) {
+    const int hi = g + 1 < N ? gidx[g + 1] : p;
+    if (hi <= gidx[g] || hi > p) return fail(BESSX_ERR_ARG, std::string(who) + ": group starts must ascend below p");
+    o->sz[g] = hi - gidx[g];
+    tot += (long long)o->sz[g] * o->sz[g];
+    if (tot > INT_MAX) return fail(BESSX_ERR_ARG, std::string(who) + ": the group blocks exceed 2^31 entries");
+    o->off[g + 1] = (int)tot;
+    o->smax = std::max(o->smax, o->sz[g]);
+  }
+  HIPX(sc.alloc(&o->gd, (size_t)3 * N + 1));
+  HIPX(hipMemcpy(o->gd, gidx, (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(o->gd + N, o->sz.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(o->gd + 2 * N, o->off.data(), ((size_t)N + 1) * sizeof(int), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int upload_flags(Owner &sc, const unsigned char *always, int N, unsigned char **d) {
+  *d = nullptr;
+  if (!always) return 0;
+  HIPX(sc.alloc(d, (size_t)N));
+  HIPX(hipMemcpy(*d, always, (size_t)N, hipMemcpyHostToDevice));
+  return 0;
+}
+
+}  // namespace
+
+int bessx_op_group_scores(const double *x, int n, int p, int cshift, const int *gidx, int N, const double *w1,
+                          const double *w2, const double *beta_dense, int lm, double n_t, double lambda,
+                          const unsigned char *always, const double *part, int nrb, double *mblk, double *dcol,
+                          double *bd) {
+  if (int rc = need_device()) return rc;
+  if (!x || n < 1 || !beta_dense || !mblk || !dcol || !bd || cshift < 0 || cshift >= p)
+    return fail(BESSX_ERR_ARG, "op_group_scores: bad arguments");
+  if (lm && (!part || nrb < 1 || !(n_t > 0.0))) return fail(BESSX_ERR_ARG, "op_group_scores: lm needs part, nrb >= 1 and n_t > 0");
+  Owner sc;
+  GroupOpLayout L;
+  if (int rc = group_op_layout("op_group_scores", sc, gidx, N, p, &L)) return rc;
+  int g0 = 0;  // the panel: the groups from global column cshift on
+  while (g0 < N && gidx[g0] != cshift) g0++;
+  if (g0 == N) return fail(BESSX_ERR_ARG, "op_group_scores: cshift is not the first column of a group");
+  const int Np = N - g0;
+  const size_t tot = (size_t)L.off[N];
+  double *dX, *dw1 = nullptr, *dw2 = nullptr, *dbeta, *dpart = nullptr, *dm, *dd, *dbd, *work, *zwork, *ev, *el;
+  unsigned char *dal;
+  long ld;
+  if (int rc = upload_padded(sc, x, n, p - cshift, n, 1, &dX, &ld)) return rc;
+  if (w1)
+    if (int rc = upload_vec_padded(sc, w1, n, ld, &dw1)) return rc;
+  if (w2)
+    if (int rc = upload_vec_padded(sc, w2, n, ld, &dw2)) return rc;
+  if (int rc = upload_flags(sc, always, N, &dal)) return rc;
+  HIPX(sc.alloc(&dbeta, (size_t)p));
+  HIPX(hipMemcpy(dbeta, beta_dense, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+  if (lm) {
+    HIPX(sc.alloc(&dpart, (size_t)nrb * p));
+    HIPX(hipMemcpy(dpart, part, (size_t)nrb * p * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIPX(sc.zeros(&dm, tot));
+  HIPX(sc.alloc(&dd, (size_t)p));
+  HIPX(hipMemcpy(dd, dcol, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(sc.zeros(&dbd, (size_t)3 * N));
+  HIPX(sc.zeros(&work, tot));  // sized as the session sizes them: sum of s^2, 2 p
+  HIPX(sc.zeros(&zwork, (size_t)2 * p));
+  HIPX(sc.zeros(&ev, tot));
+  HIPX(sc.zeros(&el, (size_t)p));
+  const int *gi = L.gd + g0, *gs = L.gd + N + g0, *go = L.gd + 2 * N + g0;
+  HIPX(launch_group_moments(L.smax, dX, ld, n, dw1, dw2, Np, gi, gs, go, dm, dd, nullptr, cshift));
+  for (int mode = 0; mode < 3; mode++)
+    HIPX(launch_group_score(Np, gi, gs, go, dm, dd, dpart, nrb, p, lm, n_t, lambda, dbeta, dal ? dal + g0 : nullptr,
+                            dbd + (size_t)mode * N + g0, nullptr, L.smax, work, zwork, nullptr, 0, mode, ev, el));
+  HIPX(hipDeviceSynchronize());
+  HIPX(hipMemcpy(mblk, dm, tot * sizeof(double), hipMemcpyDeviceToHost));
+  HIPX(hipMemcpy(dcol, dd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+  HIPX(hipMemcpy(bd, dbd, (size_t)3 * N * sizeof(double), hipMemcpyDeviceToHost));
+  return BESSX_OK;
+}
+
+int bessx_op_group_lsq(const double *x, int n, int p, const int *gidx, int N, const double *yw,
+                       const unsigned char *always, double *score) {
+  if (int rc = need_device()) return rc;
+  if (!x || n < 1 || !yw || !score) return fail(BESSX_ERR_ARG, "op_group_lsq: bad arguments");
+  Owner sc;
+  GroupOpLayout L;
+  if (int rc = group_op_layout("op_group_lsq", sc, gidx, N, p, &L)) return rc;
+  const size_t tot = (size_t)L.off[N];
+  double *dX, *dyw, *dm, *dd, *work, *zwork, *ds;
+  unsigned char *dal;
+  long ld;
+  if (int rc = upload_padded(sc, x, n, p, n, 1, &dX, &ld)) return rc;
+  if (int rc = upload_vec_padded(sc, yw, n, ld, &dyw)) return rc;
+  if (int rc = upload_flags(sc, always, N, &dal)) return rc;
+  HIPX(sc.zeros(&dm, tot));
+  HIPX(sc.zeros(&dd, (size_t)p));
+  HIPX(sc.zeros(&work, tot));
+  HIPX(sc.zeros(&zwork, (size_t)p));
+  HIPX(sc.zeros(&ds, (size_t)N));
+  HIPX(launch_group_moments(L.smax, dX, ld, n, nullptr, dyw, N, L.gd, L.gd + N, L.gd + 2 * N, dm, dd, nullptr));
+  HIPX(launch_group_lsq_score(N, L.gd, L.gd + N, L.gd + 2 * N, dm, dd, dal, work, zwork, ds, nullptr));
+  HIPX(hipDeviceSynchronize());
+  HIPX(hipMemcpy(score, ds, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  return BESSX_OK;
+}
+
 int bessx_op_glm_irls_geometry(int T0, int n, int *out) {
   if (T0 < 1 || T0 > T0_FAST || n < 1 || !out) return fail(BESSX_ERR_ARG, "op_glm_irls_geometry: bad arguments");
   const int U = n >= 4096 ? 8 : (n >= 2048 ? 4 : (n >= 1024 ? 2 : 1));

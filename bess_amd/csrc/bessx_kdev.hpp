@@ -73,6 +73,7 @@ constexpr int CH_W = 8;                                                   // wav
 constexpr int CH_MT = 16;                                                 // max tile rows
 constexpr int CH_LDT = 17;                                                // padded tile row stride (doubles)
 constexpr int GRP_MAX = 16;  // largest group size built
+static_assert(GRP_EIG_MAX == GRP_MAX, "the host keeps stored eigenvectors for exactly the widths k_group_score takes");
 
 // ------------------------------------------------------------------------------------------
 // small helpers

@@ -1190,6 +1190,27 @@ int bessx_op_glm_irls(int family, int route, int t, int wfloor, double lambda, i
                       int p, const double *y, const double *weight, const double *mask, const int *cols, int T0,
                       const double *bcur, double *gram, double *ll, double *wv, double *z, double *bnext,
                       int *route_taken);
+/* The group-selection kernels alone, through the launchers a grouped fit calls (launch_group_moments, then
+ * launch_group_score three times on the same inputs: eig_mode 0 = diagonalise, 1 = diagonalise and store, 2 = load what 1
+ * stored).  p columns in N groups, gidx[N] their first columns (gidx[0] = 0, ascending; group g ends where g + 1 starts, the
+ * last one at p), s_g their widths.  w1, w2: n row weights each or NULL (ones / no X^T w2 pass: dcol is then left as given).
+ * mblk (out, sum of s_g^2 doubles, zero-filled first): block g, column-major s_g x s_g, = X_g^T diag(w1) X_g as the moment
+ * kernels leave it (no division, no ridge).  dcol (p doubles, IN and out): X^T w2 where w2 is given.  The score reads
+ * M_g = mblk_g (/ n_t with lm) + 2 lambda I and d = dcol (lm: the sum over the nrb rows of part[nrb x p], / n_t) - 2 lambda
+ * beta_dense, and gives bd_g = |sqrtm(M_g) beta_g + sqrtm(M_g)^-1 d_g|^2 / s_g; bd (out) is 3 x N, row m = eig_mode m.  always:
+ * N flags or NULL; a flagged group scores DBL_MAX.  Work space as a session sizes it: sum of s_g^2 and 2 p doubles.
+ * cshift > 0 (the first column of some group g0): x holds only the columns from cshift on, n x (p - cshift), and only the
+ * groups g0 .. N - 1 are launched, with gidx, mblk, dcol and bd still indexed globally -- the panel form of the Cox group
+ * branch; the blocks and scores of the groups before g0 stay zero. */
+int bessx_op_group_scores(const double *x, int n, int p, int cshift, const int *gidx, int N, const double *w1,
+                          const double *w2, const double *beta_dense, int lm, double n_t, double lambda,
+                          const unsigned char *always, const double *part, int nrb, double *mblk, double *dcol,
+                          double *bd);
+/* Grouped LM screening alone: launch_group_moments(..., NULL, yw, ...) and launch_group_lsq_score.  score[N] =
+ * |(X_g^T X_g)^-1 X_g^T yw|^2 / s_g; a column that depends exactly on the ones before it is dropped, an all-zero column
+ * gives HUGE_VAL, a flagged group (always, N flags or NULL) DBL_MAX. */
+int bessx_op_group_lsq(const double *x, int n, int p, const int *gidx, int N, const double *yw,
+                       const unsigned char *always, double *score);
 /* The geometry bessx_op_glm_irls and a session use for sparsity level T0 (1 .. 254) on n rows; needs no device.  out[0] =
  * the padded row count, out[1] = tile rows of the step's Gram, out[2] = 64-row chunks per group of the fused kernel's
  * instance for that many tile rows (0 beyond 8 tile rows: the five-launch step), out[3] = the solver's rows per slab. */

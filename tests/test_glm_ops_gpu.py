@@ -12,8 +12,8 @@ systems of both families (bnext is compared only where the condition number is u
 same (inside (a) to (d)), (f) the loss a session's fit returns.
 
 Not covered here: the convergence rule and the chain of steps (reached through Session.fit only: tests/test_glm_gpu.py and
-the full-size golden tests), the pivoted fallback solve on a singular system, k_group_*, the screening kernels, the
-covariance-form kernels.
+the full-size golden tests), the pivoted fallback solve on a singular system, the screening kernels, the covariance-form
+kernels.  (k_group_* are called alone in tests/test_group_ops_gpu.py.)
 
 Measured on an MI355X (every test prints the fraction of each bound it uses, -s shows them): the file's 32 tests pass in
 5.6 s.  Largest fraction of each bound used: g 0.134, h 0.131, loss 0.124, held-out loss 0.122, bd 0.187; Gram 0.108, ll

@@ -2,9 +2,10 @@
 top-k, Gram, Cholesky solve, normalisation), each called alone, against NumPy / the plain-C oracle on the same seeded
 inputs.  The Cox solver's state pass, scans, loss and score passes are called alone in tests/test_cox_ops_gpu.py; the
 logistic and Poisson solver's gradient / curvature pass (bessx_op_glm_gh) and one IRLS step by either route
-(bessx_op_glm_irls) in tests/test_glm_ops_gpu.py.  The Newton-step kernels of the Cox fit, the group kernels (k_group_*),
-the screening kernels, the covariance-form kernels and the big-system solvers have no such entry and are reached through
-sessions only."""
+(bessx_op_glm_irls) in tests/test_glm_ops_gpu.py; the group-selection kernels (k_group_*: bessx_op_group_scores,
+bessx_op_group_lsq) in tests/test_group_ops_gpu.py.  The Newton-step kernels of the Cox fit, the Cox group branch as a whole
+(launch_cox_group_moments), the per-group screening fits (k_screen_*_group) and the other screening kernels, the
+covariance-form kernels and the big-system solvers have no such entry and are reached through sessions only."""
 import numpy as np
 import pytest
 
