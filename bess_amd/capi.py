@@ -47,6 +47,7 @@ SYMBOLS = [
     "bessx_cox_diag_device", "bessx_cox_diag_workspace", "bessx_op_cox_diag_bench",
     "bessx_meat_device", "bessx_sandwich_device", "bessx_sandwich_workspace", "bessx_op_sandwich_bench",
     "bessx_addscore_device", "bessx_addscore_workspace", "bessx_op_addscore_bench",
+    "bessx_cox_addscore_device", "bessx_cox_addscore_workspace", "bessx_op_cox_addscore_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -175,6 +176,17 @@ class AddscoreInput(ctypes.Structure):
                 ("weight_stride", _ll), ("factor", _D), ("factor_ld", _ll), ("candidates", _I), ("q", _i),
                 ("candidate_block", _i), ("info", _D), ("info_ld", _ll), ("score", _D), ("u", _vp), ("d", _vp),
                 ("s", _vp), ("a", _vp), ("cross", _vp), ("cross_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class CoxAddscoreInput(ctypes.Structure):
+    """bessx_cox_addscore_input: bessx_cox_info_input's model and data, the factor of the inverse information in host
+    memory (or null), the candidate columns (or null = all), the candidate block, and where info, score, u, d, t, s, a and
+    the cross information go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
+                ("factor", _D), ("factor_ld", _ll), ("candidates", _I), ("q", _i), ("candidate_block", _i),
+                ("info", _D), ("info_ld", _ll), ("score", _D), ("u", _vp), ("d", _vp), ("t", _vp), ("s", _vp),
+                ("a", _vp), ("cross", _vp), ("cross_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -324,6 +336,10 @@ def lib():
         L.bessx_addscore_workspace.argtypes = [_i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I, _I,
                                                ctypes.POINTER(_ll), _I]
         L.bessx_op_addscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _i, _i, _D]
+        L.bessx_cox_addscore_device.argtypes = [ctypes.POINTER(CoxAddscoreInput), _D, _D, _D]
+        L.bessx_cox_addscore_workspace.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll),
+                                                   ctypes.POINTER(_ll), _I, _I, _I, _I]
+        L.bessx_op_cox_addscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _i, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1780,8 +1796,8 @@ def addscore_device(x, cols, beta, coef0, y, link="identity", weight=None, facto
     "cross" (q, M), the c_j, when want_cross.  The subtractions u - a and d - s are score_test_table's.  One pass over
     all candidate columns on the fp64 matrix cores; no x-sized temporary; candidates go in blocks of candidate_block (0
     = the library's choice; a multiple of 16), so scratch beyond the n x Mp panel does not depend on p (addscore_workspace).
-    The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  Not for
-    Cox models, not for groups of columns with more than one degree of freedom, not corrected for selection.
+    The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  Cox
+    models: cox_addscore_device.  Not for groups of columns with more than one degree of freedom, not corrected for selection.
     len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
     dx = _DeviceArray(x, "x", 2)
     n, p = dx.shape
@@ -2358,6 +2374,142 @@ def op_cox_info_bench(x, cols, ties="order", repeats=20):
     _check(lib().bessx_op_cox_info_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                          _ip(cols), cols.size, TIES[ties], repeats, _dp(ms), ctypes.byref(nbytes)))
     return tuple(float(v) for v in ms), nbytes.value
+
+
+def cox_addscore_workspace(n, m, n_event_rows, q, candidate_block=0):
+    """What a cox_addscore_device call on n rows (n_event_rows of them with status 1) with a support of m columns and q
+    candidates needs and how it is split (bessx_cox_addscore_workspace; no device is needed): {"doubles": scratch
+    memory in all, "block_doubles": the part of it that does not depend on p, "rows_per_slab", "slabs": the row split of
+    the matrix-core pass behind u, c, d, "quad_rows_per_slab", "quad_slabs": the position split of the streaming pass
+    behind t -- functions of (n, m, q, candidate_block) alone --, "block": candidates per block, "sum_depth": the
+    additions behind one s_j, "chain": the longest chain of additions behind an entry of u, c, d, "quad_chain": behind
+    a t_j}."""
+    nd, bd, rps, sl, bl, dp, ch = _ll(0), _ll(0), (_ll * 2)(), (_i * 2)(), _i(0), _i(0), (_i * 2)()
+    _check(lib().bessx_cox_addscore_workspace(int(n), int(m), int(n_event_rows), int(q), int(candidate_block),
+                                              ctypes.byref(nd), ctypes.byref(bd), rps, sl, ctypes.byref(bl),
+                                              ctypes.byref(dp), ch))
+    return {"doubles": nd.value, "block_doubles": bd.value, "rows_per_slab": int(rps[0]), "slabs": int(sl[0]),
+            "quad_rows_per_slab": int(rps[1]), "quad_slabs": int(sl[1]), "block": bl.value, "sum_depth": dp.value,
+            "chain": int(ch[0]), "quad_chain": int(ch[1])}
+
+
+def cox_addscore_device(x, cols, beta, time, status, weight=None, ties="order", factor=None, candidates=None,
+                        candidate_block=0, want_cross=False, stream=0):
+    """The ingredients of the Rao score test of every candidate column against ONE Cox model on a device matrix x (n x p:
+    float64 or float32, any non-negative strides), read where it lies (bessx_cox_addscore_device).  The model, the
+    positions and e, wd, S0, v, g, info, score, loglik, n_events, residual_sum are cox_information_device's (the same
+    bits).  candidates: None = all p columns, else ascending distinct column numbers.  factor: R, lower triangular (m,
+    m) with inv(info) = R^T R; None = cox_information_device and info_factor are called first (and when the information
+    is not positive definite, s and a are NaN).  With dh_p the hazard increment at position p, u_p the risk-set mean
+    over the support, A_l = sum_{p <= l} dh_p u_p, r = inv(info) @ score, for candidate j
+        u_j = sum_l g_l x_lj,   c_j = sum_l x_lj (v_l x_l - e_l A_l),   d_j = sum_l v_l x_lj^2,
+        t_j = sum_p (dh_p / S0_p) (sum_{l >= p} e_l x_lj)^2,   s_j = |R c_j|^2,   a_j = c_j . r
+    -- row j of the score and of the observed information of the model extended by column j at coefficient 0, whose
+    diagonal entry is d_j - t_j.  Returns {"columns", "u", "d", "t", "s", "a", "info", "score", "loglik", "n_events",
+    "residual_sum", "positive_definite", "support"} (NumPy, host) plus "cross" (q, m), the c_j, when want_cross.  The
+    subtractions u - a and (d - t) - s are cox_score_test_table's; d - t loses digits for columns far from centred
+    (cox_information_device's G1 - G2 caveat).  m = 0 is the test against the null model (s = a = 0).  u, c, d take one
+    pass over the candidate columns on the fp64 matrix cores and t a second, streaming one; no n x q temporary and no
+    risk-set mean of a candidate is formed; candidates go in blocks of candidate_block (0 = the library's choice; a
+    multiple of 16), so scratch beyond the support-sized arrays and the panel does not depend on p
+    (cox_addscore_workspace).  The same call gives the same bits, and every layout of the same values of one dtype
+    gives the same bits.  Not for Efron ties, strata, groups of columns with more than one degree of freedom, not
+    corrected for selection.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if ties not in TIES:
+        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: cox_addscore_device takes one model per call")
+    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
+    if not np.isfinite(B).all():
+        raise ValueError("beta must be finite")
+    cand, q = _candidates(candidates, p)
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, a in given:  # (every shape is checked before anything is copied)
+        _survival_vector(a, n, what, check_only=True)
+    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    m = cols.size
+    pd = True
+    fh = None
+    if m == 0:
+        pass
+    elif factor is None:
+        first = cox_information_device(x, cols, B, host["time"], host["status"], weight=host.get("weight"), ties=ties,
+                                       stream=stream)
+        fh, pd = info_factor(first["info"])
+    else:
+        fh = _f64(factor)
+        if fh.shape != (m, m):
+            raise ValueError("factor must have shape (%d, %d), got %s" % (m, m, fh.shape))
+    a = CoxAddscoreInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    a.ties, a.stream = TIES[ties], int(stream) if stream else None
+    if pd and m > 0:
+        a.factor, a.factor_ld = _dp(fh), m
+    a.candidates, a.q, a.candidate_block = _ip(cand), q, int(candidate_block)
+    info, score = np.empty((m, m)), np.empty(m)
+    out = np.full((5, q), np.nan)
+    a.info, a.info_ld, a.score = _dp(info), m, _dp(score)
+    a.u, a.d, a.t, a.s, a.a = (out[k].ctypes.data for k in range(5))
+    cross = None
+    if want_cross:
+        cross = np.empty((q, m + 1))
+        a.cross, a.cross_ld = cross.ctypes.data, m + 1
+    a.out_on_device = 0
+    ll, ne, rs = _d(0), _d(0), _d(0)
+    _check(lib().bessx_cox_addscore_device(ctypes.byref(a), ctypes.byref(ll), ctypes.byref(ne), ctypes.byref(rs)))
+    got = {"columns": np.arange(p, dtype=np.int64) if cand is None else cand.astype(np.int64), "u": out[0], "d": out[1],
+           "t": out[2], "s": out[3], "a": out[4], "info": info, "score": score, "loglik": ll.value, "n_events": ne.value,
+           "residual_sum": rs.value, "positive_definite": bool(pd), "support": cols.astype(np.int64)}
+    if want_cross:
+        got["cross"] = np.ascontiguousarray(cross[:, 1:])  # (column 0 is sum_l v_l x_lj: not an entry of c_j)
+    return got
+
+
+def cox_score_test_table(got):
+    """The Rao score test of every candidate from what cox_addscore_device (or the NumPy route) returns, on the host in
+    fp64: score = u - a, variance = (d - t) - s, statistic = score^2 / variance where variance is finite and > 0, else
+    NaN; p_value = erfc(sqrt(statistic / 2)), chi-square with 1 degree of freedom; dispersion = 1.  A candidate that is
+    in the model's support ("support" of got) has in_model = True and NaN for statistic and p_value: its variance is
+    rounding noise.  When the information is not positive definite s and a are NaN and so is every statistic.  Returns
+    {"columns", "score", "variance", "statistic", "p_value", "in_model", "dispersion"}.  Selection is not corrected
+    for."""
+    import math
+    u, a = np.asarray(got["u"], dtype=np.float64), np.asarray(got["a"], dtype=np.float64)
+    d, t = np.asarray(got["d"], dtype=np.float64), np.asarray(got["t"], dtype=np.float64)
+    s = np.asarray(got["s"], dtype=np.float64)
+    columns = np.asarray(got["columns"], dtype=np.int64)
+    adj, var = u - a, (d - t) - s
+    in_model = np.isin(columns, np.asarray(got.get("support", np.zeros(0)), dtype=np.int64))
+    ok = np.isfinite(var) & (var > 0) & ~in_model
+    stat = np.full(columns.size, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        stat[ok] = (adj[ok] * adj[ok]) / var[ok]
+    pv = np.array([math.erfc(math.sqrt(v / 2.0)) if (v == v and v >= 0) else float("nan") for v in stat])
+    return {"columns": columns, "score": adj, "variance": var, "statistic": stat, "p_value": pv, "in_model": in_model,
+            "dispersion": 1.0}
+
+
+def op_cox_addscore_bench(x, cols, candidates=None, candidate_block=0, sorted_rows=False, repeats=5):
+    """(ms per stage, bytes the streaming pass needs) of the Cox score-test kernels on the device matrix x for the support
+    cols, device events, each over every block of candidates: {"pack", "cross", "quad", "quad_finish", "finish",
+    "statistic"} (bessx_op_cox_addscore_bench).  sorted_rows: the rows are taken to be in time order already; else a
+    scattered order.  The bytes are the candidate columns read once."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    cand, q = _candidates(candidates, dx.shape[1])
+    ms, nbytes = (_d * 6)(), _d(0)
+    _check(lib().bessx_op_cox_addscore_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                             _ip(cols), cols.size, _ip(cand), q, int(candidate_block),
+                                             1 if sorted_rows else 0, repeats, ms, ctypes.byref(nbytes)))
+    return dict(zip(("pack", "cross", "quad", "quad_finish", "finish", "statistic"), [float(v) for v in ms])), nbytes.value
 
 
 COX_DIAG_KINDS = ("martingale", "deviance", "score", "dfbeta", "displacement", "schoenfeld")  # BESSX_COX_DIAG_* bits

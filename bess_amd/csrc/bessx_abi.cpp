@@ -4082,3 +4082,413 @@ int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// score tests of candidate columns against one Cox model on a caller's device matrix (include/bessx.h section 2m)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the fields bessx_cox_addscore_input shares with bessx_cox_info_input, as section 2h's helpers take them
+bessx_cox_info_input cox_addscore_as_info(const bessx_cox_addscore_input *in) {
+  bessx_cox_info_input a{};
+  a.x = in->x;
+  a.x_dtype = in->x_dtype;
+  a.x_row_stride = in->x_row_stride;
+  a.x_col_stride = in->x_col_stride;
+  a.n = in->n;
+  a.p = in->p;
+  a.cols = in->cols;
+  a.m = in->m;
+  a.beta = in->beta;
+  a.time = in->time;
+  a.status = in->status;
+  a.weight = in->weight;
+  a.ties = in->ties;
+  a.info = in->info;
+  a.info_ld = in->info_ld;
+  a.score = in->score;
+  a.out_on_device = 0;
+  a.stream = in->stream;
+  return a;
+}
+
+// everything about the call that needs no device
+int cox_addscore_check_args(const char *who, const bessx_cox_addscore_input *in, const double *loglik,
+                            const double *n_events, const double *residual_sum) {
+  const std::string w(who);
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const bessx_cox_info_input a = cox_addscore_as_info(in);
+  if (int rc = cox_info_check_args(who, &a, loglik, n_events, residual_sum)) return rc;
+  if (!in->u || !in->d || !in->t) return fail(BESSX_ERR_ARG, w + ": null argument (u, d, t)");
+  if (in->factor && (!in->s || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (s, a)");
+  if (in->q < 1) return fail(BESSX_ERR_ARG, w + ": q must be at least 1");
+  if (!in->candidates && in->q != in->p) return fail(BESSX_ERR_ARG, w + ": without a candidate list q must be p");
+  if (in->candidates) {
+    for (int j = 0; j < in->q; j++) {
+      if (in->candidates[j] < 0 || in->candidates[j] >= in->p)
+        return fail(BESSX_ERR_ARG, w + ": a candidate is not a column of x");
+      if (j > 0 && in->candidates[j] <= in->candidates[j - 1])
+        return fail(BESSX_ERR_ARG, w + ": candidates must be ascending and distinct");
+    }
+  }
+  if (int rc = addscore_check_block(w, in->candidate_block)) return rc;
+  if (in->cross && in->cross_ld < (long long)in->m + 1)
+    return fail(BESSX_ERR_ARG, w + ": cross_ld must be at least m + 1");
+  if (in->factor && in->m > 0) {
+    if (in->factor_ld < (long long)in->m) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m");
+    for (long long j = 0; j < in->m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  return 0;
+}
+
+// doubles of device scratch of one call beyond section 2h's, and the part of them that does not depend on p
+void cox_addscore_doubles(long long n, int m, long long J, int q, int block, long long *all, long long *blockpart) {
+  const long long nb = (n + 1023) / 1024, M = (long long)m + 1;
+  long long panel = 0, blk = 0, rps = 0, part = 0, rpsq = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsq = 0, tdepth = 0;
+  addscore_split(n, m, q, block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  cox_addscore_split(n, q, block, &part, &rpsq, &slabsq, &tdepth);
+  long long d = cox_info_doubles(n, m, J) + (long long)m * m + m + 2;
+  if (m == 0) d += 3 * n + cox_surv_workspace(n);  // e, v, g and the totals of H's scan, which section 2h skips at m = 0
+  if (m > 0) d += cox_diag_lda(n) * m + n + nb * m;  // A, dh, A's totals
+  d += n + nb + panel + blk + part;                  // Cc and its totals, the panel, the block workspaces
+  long long bp = blk + part;
+  if (m > 0) {  // the score behind r: the support as candidates
+    long long panel0 = 0, blk0 = 0, rps0 = 0;
+    int slabs0 = 0, cb0 = 0, depth0 = 0;
+    addscore_split(n, m, m, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+    d += blk0 + 2 * M;
+    bp += blk0 + 2 * M;
+  }
+  *all = d;
+  *blockpart = bp;
+}
+
+// sc, o, x, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vector<double> &pk, std::vector<double> &h,
+                     const bessx_cox_addscore_input *in, double *loglik, double *residual_sum, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, q = in->q, block = in->candidate_block;
+  const int ties = in->ties;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  const size_t N = (size_t)n, mm = (size_t)m * (size_t)m, M = (size_t)m + 1, Q = (size_t)q;
+  const size_t nb = (size_t)((n + 1023) / 1024);
+  const bool with_stat = in->factor != nullptr && m > 0, want_c = in->cross != nullptr;
+  // 1. info, score, loglik and residual_sum: section 2h's launches as bessx_cox_info_device runs them (the same bits)
+  CoxInfoDev c;
+  if (int rc = cox_info_stage(sc, o, x, in->cols, m, in->beta, n, ties, st, &c)) return rc;
+  const CoxDev &d = c.d;
+  HIPX(hipMemsetAsync(c.res, 0, 2 * sizeof(double), st));
+  double *istage = nullptr, *res2 = nullptr;
+  h.resize(2 + mm + 2 * (size_t)m);
+  if (m > 0) {
+    HIPX(sc.alloc(&istage, mm + (size_t)m));
+    if (int rc = cox_info_launch(in->x, f32, rs, cs, n, m, ties, c, istage, m, istage + mm, st)) return rc;
+    HIPX(hipMemcpyAsync(h.data() + 2, istage, (mm + (size_t)m) * sizeof(double), hipMemcpyDeviceToHost, st));
+  } else {
+    // (section 2h stops after the likelihood at m = 0: the arrays behind v and g are this section's own)
+    HIPX(sc.alloc(&c.rowof, N));
+    HIPX(hipMemcpyAsync(c.rowof, x.rowof.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    if (ties) {
+      HIPX(sc.alloc(&c.lastk, N));
+      HIPX(hipMemcpyAsync(c.lastk, x.lastk.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    HIPX(sc.alloc(&c.e, N));
+    HIPX(sc.alloc(&c.v, N));
+    HIPX(sc.alloc(&c.g, N));
+    HIPX(sc.alloc(&c.hs, (size_t)cox_surv_workspace(n)));
+    HIPX(launch_cox_eval_eta(in->x, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
+    HIPX(hipMemcpyAsync(c.e, d.ex, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, c.res, st));
+    HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, c.hs, nullptr, st));
+    HIPX(launch_cox_info_vg(c.e, d.eta, ties ? c.lastk : nullptr, d.wd, d.pos, n, c.v, c.g, st));
+  }
+  HIPX(hipMemcpyAsync(h.data(), c.res, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  // 2. where section 2h's predictor pass is the gathering one, e and what follows it once more from the pass with threads
+  // along rows: the same bits under every layout of x
+  if (!cox_eval_eta_by_rows(rs, cs, m)) {
+    HIPX(sc.alloc(&res2, 2));
+    HIPX(launch_cox_eval_eta_rows(in->x, f32, rs, cs, n, d.cols, m, d.B, d.zero, d.pos, d.eta, d.ex, st));
+    HIPX(hipMemcpyAsync(c.e, d.ex, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, res2, st));
+    HIPX(launch_cox_info_gather(in->x, f32, rs, cs, n, d.cols, m, c.rowof, c.e, c.W, st));
+    HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, c.hs, nullptr, st));
+    HIPX(launch_cox_info_vg(c.e, d.eta, ties ? c.lastk : nullptr, d.wd, d.pos, n, c.v, c.g, st));
+    if (c.J > 0) HIPX(launch_cox_info_means(c.W, d.ex, c.jptr, n, m, c.J, c.scr, c.U, c.ldU, st));
+  }
+  // 3. A (section 2j's launches) and Cc
+  double *A = nullptr, *dh = nullptr, *scrA = nullptr, *Cc = nullptr, *scrC = nullptr;
+  const long long ldA = cox_diag_lda(n);
+  if (m > 0) {
+    HIPX(sc.alloc(&A, (size_t)ldA * (size_t)m));
+    HIPX(sc.alloc(&dh, N));
+    HIPX(sc.alloc(&scrA, nb * (size_t)m));
+    HIPX(launch_cox_diag_accum(c.U, c.ldU, c.jptr, d.wd, d.ex, d.first, ties ? c.lastk : nullptr, n, m, dh, scrA, A, ldA,
+                               st));
+  }
+  HIPX(sc.alloc(&Cc, N));
+  HIPX(sc.alloc(&scrC, nb));
+  HIPX(launch_cox_addscore_cc(d.wd, d.ex, d.first, ties ? c.lastk : nullptr, n, scrC, Cc, st));
+  // 4. the panel
+  long long panel = 0, blk = 0, rps = 0, part_d = 0, rpsq = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsq = 0, tdepth = 0;
+  addscore_split(n, m, q, block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  cox_addscore_split(n, q, block, &part_d, &rpsq, &slabsq, &tdepth);
+  int *cand_d = nullptr;
+  double *P = nullptr, *work = nullptr, *part = nullptr, *ostage = nullptr;
+  HIPX(sc.alloc(&P, (size_t)panel));
+  HIPX(sc.alloc(&work, (size_t)blk));
+  HIPX(sc.alloc(&part, (size_t)part_d));
+  if (in->candidates) {
+    HIPX(sc.alloc(&cand_d, Q));
+    HIPX(hipMemcpyAsync(cand_d, in->candidates, Q * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  HIPX(launch_cox_addscore_pack(in->x, f32, rs, cs, n, d.cols, m, q, block, c.v, c.g, c.e, d.pos, A, ldA, P, st));
+  // the score behind r, summed by section 2l's kernels over the support as candidates: the same bits under every
+  // layout of x, which section 2h's score is not
+  if (with_stat) {
+    long long panel0 = 0, blk0 = 0, rps0 = 0;
+    int slabs0 = 0, cb0 = 0, depth0 = 0;
+    double *work0 = nullptr, *u0 = nullptr;
+    addscore_split(n, m, m, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+    HIPX(sc.alloc(&work0, (size_t)blk0));
+    HIPX(sc.alloc(&u0, 2 * M));
+    HIPX(launch_addscore_blocks(in->x, f32, rs, cs, n, m, d.cols, m, 0, P, work0, 0, u0, u0 + M, nullptr, nullptr, nullptr,
+                                0, 0, st));
+    HIPX(hipMemcpyAsync(h.data() + 2 + mm + (size_t)m, u0, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  *loglik = h[0];
+  *residual_sum = h[1];
+  for (size_t j = 0; j < (size_t)m; j++)
+    std::copy(h.begin() + 2 + j * m, h.begin() + 2 + (j + 1) * m, in->info + j * in->info_ld);
+  if (m > 0) std::copy(h.begin() + 2 + mm, h.begin() + 2 + mm + (size_t)m, in->score);
+  if (with_stat) {
+    // r = inverse(info) U = R^T (R U) on the host in fp64; the factor gets a zero row and column in front for the panel's
+    // column 0 (v), whose cross product has no part in s and a
+    const double *U0 = h.data() + 2 + mm + (size_t)m;
+    std::vector<double> t((size_t)m, 0.0), Rx(M * M, 0.0), rx(M, 0.0);
+    for (size_t j = 0; j < (size_t)m; j++)
+      for (size_t k = 0; k <= j; k++) {
+        const double f = in->factor[j * in->factor_ld + k];
+        t[j] += f * U0[k];
+        Rx[(j + 1) * M + k + 1] = f;
+      }
+    for (size_t j = 0; j < (size_t)m; j++)
+      for (size_t k = 0; k <= j; k++) rx[k + 1] += in->factor[j * in->factor_ld + k] * t[j];
+    pk.resize((size_t)diag_factor_doubles(m + 1));
+    addscore_pack_factor(Rx.data(), (long long)M, rx.data(), m, pk.data());
+    HIPX(hipMemcpyAsync(work + blk - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice,
+                        st));
+  }
+  // 5. u, c, d, s, a by section 2l's kernels; t by the streaming pass
+  double *u = in->u, *dd = in->d, *tt = in->t, *s = in->s, *a = in->a, *C = in->cross;
+  long long ldc = in->cross_ld;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&ostage, 5 * Q + (want_c ? Q * M : 0)));
+    u = ostage, dd = ostage + Q, tt = ostage + 2 * Q, s = ostage + 3 * Q, a = ostage + 4 * Q;
+    C = want_c ? ostage + 5 * Q : nullptr;
+    ldc = (long long)M;
+  }
+  HIPX(launch_addscore_blocks(in->x, f32, rs, cs, n, m, cand_d, q, block, P, work, with_stat ? 1 : 0, u, dd, s, a, C, ldc,
+                              0, st));
+  HIPX(launch_cox_addscore_quad(in->x, f32, rs, cs, n, cand_d, q, block, c.rowof, c.e, Cc, part, tt, 0, st));
+  const bool zero_sa = m == 0 && s && a;  // (the null model: nothing is explained by a support)
+  if (zero_sa) {
+    HIPX(hipMemsetAsync(s, 0, Q * sizeof(double), st));
+    HIPX(hipMemsetAsync(a, 0, Q * sizeof(double), st));
+  }
+  if (!in->out_on_device) {
+    h.resize(5 * Q + (want_c ? Q * M : 0));
+    HIPX(hipMemcpyAsync(h.data(), ostage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device) {
+    std::copy(h.begin(), h.begin() + Q, in->u);
+    std::copy(h.begin() + Q, h.begin() + 2 * Q, in->d);
+    std::copy(h.begin() + 2 * Q, h.begin() + 3 * Q, in->t);
+    if ((with_stat || m == 0) && in->s && in->a) {
+      std::copy(h.begin() + 3 * Q, h.begin() + 4 * Q, in->s);
+      std::copy(h.begin() + 4 * Q, h.begin() + 5 * Q, in->a);
+    }
+    if (want_c)
+      for (size_t j = 0; j < Q; j++)
+        std::copy(h.begin() + 5 * Q + j * M, h.begin() + 5 * Q + (j + 1) * M, in->cross + j * in->cross_ld);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_addscore_workspace(int n, int m, int n_event_rows, int q, int candidate_block, long long *doubles,
+                                 long long *block_doubles, long long *rows_per_slab, int *slabs, int *block,
+                                 int *sum_depth, int *chain) {
+  if (!doubles || !block_doubles || !rows_per_slab || !slabs || !block || !sum_depth || !chain)
+    return fail(BESSX_ERR_ARG, "cox_addscore_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_addscore_workspace: empty matrix");
+  if (n_event_rows < 0 || n_event_rows > n)
+    return fail(BESSX_ERR_ARG, "cox_addscore_workspace: n_event_rows must lie in [0, n]");
+  if (q < 1) return fail(BESSX_ERR_ARG, "cox_addscore_workspace: q must be at least 1");
+  if (int rc = addscore_check_block("cox_addscore_workspace", candidate_block)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "cox_addscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  long long panel = 0, blk = 0, part = 0;
+  addscore_split(n, m, q, candidate_block, &panel, &blk, &rows_per_slab[0], &slabs[0], block, sum_depth);
+  cox_addscore_split(n, q, candidate_block, &part, &rows_per_slab[1], &slabs[1], &chain[1]);
+  chain[0] = (int)std::min<long long>(0x7fffffffLL, rows_per_slab[0] + (slabs[0] + 15) / 16 + 4);
+  cox_addscore_doubles(n, m, n_event_rows, q, candidate_block, doubles, block_doubles);
+  return BESSX_OK;
+}
+
+int bessx_cox_addscore_device(const bessx_cox_addscore_input *in, double *loglik, double *n_events,
+                              double *residual_sum) {
+  if (int rc = cox_addscore_check_args("cox_addscore_device", in, loglik, n_events, residual_sum)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("cox_addscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
+                                   in->n, in->p, &dev))
+    return rc;
+  if (in->out_on_device) {
+    const bool sa = in->factor || in->m == 0;
+    double *const vec[5] = {in->u, in->d, in->t, sa ? in->s : nullptr, sa ? in->a : nullptr};
+    for (double *v : vec) {
+      if (!v) continue;
+      if (int rc = check_device_matrix("cox_addscore_device: u, d, t, s, a", v, BESSX_F64, 1, 0, in->q, 1, &od)) return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "cox_addscore_device: an output is not on the device that owns x");
+    }
+    if (in->cross) {
+      if (int rc = check_device_matrix("cox_addscore_device: cross", in->cross, BESSX_F64, in->cross_ld, 1, in->q,
+                                       in->m + 1, &od))
+        return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "cox_addscore_device: cross is not on the device that owns x");
+    }
+  }
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  CoxInfoOrder x;
+  cox_info_order(&o, in->n, in->m, in->ties, &x);
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> pk, h;
+    rc = cox_addscore_run(sc, o, x, pk, h, in, loglik, residual_sum, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  if (!rc) *n_events = x.n_events;
+  return rc;
+}
+
+int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                                const int *cols, int m, const int *candidates, int q, int candidate_block, int sorted,
+                                int repeats, double *stage_ms, double *bytes) {
+  if (!x || repeats < 1 || !stage_ms || !bytes || q < 1) return fail(BESSX_ERR_ARG, "op_cox_addscore_bench: bad arguments");
+  if (int rc = predict_check_model("op_cox_addscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_addscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = addscore_check_block("op_cox_addscore_bench", candidate_block)) return rc;
+  if (!candidates && q != p) return fail(BESSX_ERR_ARG, "op_cox_addscore_bench: without a candidate list q must be p");
+  if (candidates)
+    for (int j = 0; j < q; j++)
+      if (candidates[j] < 0 || candidates[j] >= p || (j > 0 && candidates[j] <= candidates[j - 1]))
+        return fail(BESSX_ERR_ARG, "op_cox_addscore_bench: candidates must be ascending distinct columns of x");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_addscore_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t M = (size_t)m + 1, Q = (size_t)q, N = (size_t)n;
+  long long panel = 0, blk = 0, rps = 0, part_d = 0, rpsq = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsq = 0, tdepth = 0;
+  addscore_split(n, m, q, candidate_block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  cox_addscore_split(n, q, candidate_block, &part_d, &rpsq, &slabsq, &tdepth);
+  // n-vectors, an A and a factor of the library's own; positions in a scattered order unless the rows are sorted
+  const long long ldA = cox_diag_lda(n);
+  std::vector<double> v(N, 0.25), g(N), e(N), Cc(N), Ah((size_t)ldA * (size_t)m, 1.0 / 64.0), R(M * M, 0.0),
+      r(M, 1.0 / 128.0), pk((size_t)diag_factor_doubles(m + 1));
+  std::vector<int> pos(N), rowof(N);
+  for (size_t i = 0; i < N; i++) {
+    g[i] = (i % 2) ? -0.5 : 0.5;
+    e[i] = 1.0 + (double)(i % 7) / 8.0;
+    Cc[i] = (double)(i + 1) / ((double)n * (double)n);
+    pos[i] = sorted ? (int)i : (int)(((long long)i * 7919) % n);
+    rowof[i] = pos[i];
+  }
+  for (size_t j = 1; j < M; j++)
+    for (size_t k = 1; k <= j; k++) R[j * M + k] = (j == k ? 1.0 : 1.0 / 64.0) / std::sqrt((double)n);
+  r[0] = 0.0;
+  addscore_pack_factor(R.data(), (long long)M, r.data(), m, pk.data());
+  int *cols_d = nullptr, *cand_d = nullptr, *pos_d = nullptr, *rowof_d = nullptr;
+  double *v_d = nullptr, *g_d = nullptr, *e_d = nullptr, *Cc_d = nullptr, *A_d = nullptr, *P = nullptr, *work = nullptr,
+         *part = nullptr, *out = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&pos_d, N));
+  HIPX(sc.alloc(&rowof_d, N));
+  HIPX(sc.alloc(&v_d, N));
+  HIPX(sc.alloc(&g_d, N));
+  HIPX(sc.alloc(&e_d, N));
+  HIPX(sc.alloc(&Cc_d, N));
+  HIPX(sc.alloc(&A_d, Ah.size()));
+  HIPX(sc.alloc(&P, (size_t)panel));
+  HIPX(sc.alloc(&work, (size_t)blk));
+  HIPX(sc.alloc(&part, (size_t)part_d));
+  HIPX(sc.alloc(&out, 5 * Q));
+  if (m > 0) {
+    HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+    HIPX(hipMemcpy(A_d, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (candidates) {
+    HIPX(sc.alloc(&cand_d, Q));
+    HIPX(hipMemcpy(cand_d, candidates, Q * sizeof(int), hipMemcpyHostToDevice));
+  }
+  HIPX(hipMemcpy(pos_d, pos.data(), N * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(rowof_d, rowof.data(), N * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(v_d, v.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(g_d, g.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(e_d, e.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(Cc_d, Cc.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(work + blk - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  auto run = [&](int stage) {
+    if (stage == 0)
+      return launch_cox_addscore_pack(x, f32, row_stride, col_stride, n, cols_d, m, q, candidate_block, v_d, g_d, e_d, pos_d,
+                                      m > 0 ? A_d : nullptr, ldA, P, nullptr);
+    if (stage == 2 || stage == 3)
+      return launch_cox_addscore_quad(x, f32, row_stride, col_stride, n, cand_d, q, candidate_block, rowof_d, e_d, Cc_d,
+                                      part, out + 4 * Q, stage - 1, nullptr);
+    const int only = stage == 1 ? 1 : (stage == 4 ? 2 : 3);
+    return launch_addscore_blocks(x, f32, row_stride, col_stride, n, m, cand_d, q, candidate_block, P, work, 1, out, out + Q,
+                                  out + 2 * Q, out + 3 * Q, nullptr, 0, only, nullptr);
+  };
+  // (each stage over every block of candidates, in an order in which a later stage finds the earlier one's results of
+  // the last block)
+  for (int stage = 0; stage < 6; stage++) {
+    HIPX(run(stage));  // the warm-up
+    HIPX(hipEventRecord(e0, nullptr));
+    for (int i = 0; i < repeats; i++) HIPX(run(stage));
+    HIPX(hipEventRecord(e1, nullptr));
+    HIPX(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    stage_ms[stage] = ms / repeats;
+  }
+  *bytes = (double)n * (double)q * (f32 ? 4.0 : 8.0);
+  return BESSX_OK;
+}
+
+}  // extern "C"

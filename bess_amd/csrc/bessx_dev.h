@@ -88,6 +88,12 @@ long long cox_eval_workspace(long long n, int R);
 hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                                const double *B, const double *zero, int R, const int *pos, double *eta, double *ex,
                                hipStream_t st);
+// _eta_rows: _eta for R = 1, always with threads along rows: eta and ex are the same bits under every layout of x.
+// cox_eval_eta_by_rows: whether _eta's own pass is that one.
+bool cox_eval_eta_by_rows(long long rs, long long cs, int m);
+hipError_t launch_cox_eval_eta_rows(const void *src, int f32, long long rs, long long cs, long long n, const int *cols,
+                                    int m, const double *B, const double *zero, const int *pos, double *eta, double *ex,
+                                    hipStream_t st);
 hipError_t launch_cox_eval_scan_tot(const double *e, long long n, int R, double *scr, hipStream_t st);
 hipError_t launch_cox_eval_suffix(double *ex, long long n, int R, double *scr, hipStream_t st);
 hipError_t launch_cox_eval_loglik(const double *eta, double *ex, const double *wd, const int *first, long long n, int R,
@@ -231,6 +237,24 @@ hipError_t launch_cox_diag_perm(const double *L, long long ldL, long long n, int
 hipError_t launch_cox_diag_schoenfeld(const void *src, int f32, long long rs, long long cs, const int *cols, int m,
                                       const int *evrow, int J, const double *U, long long ldU, double *out,
                                       long long ldo, hipStream_t st);
+// score tests of candidate columns against one Cox model (bessx_k_coxaddscore.hip), on top of the arrays of
+// bessx_k_coxinfo.hip and bessx_k_coxdiag.hip.  _pack: the panel (v_i, v_i x_i - e_pos(i) A_pos(i), g_i, zeros) in
+// launch_addscore_pack's layout for the same m (launch_addscore_blocks takes it as it is: column 0 is v, where section
+// 2l has the intercept's entry).  _cc: Cc_l = sum_{p <= l} dh_p / S0(p) (scr: ceil(n / 1024) doubles).  _quad: t_j = sum_p (dh_p /
+// S0(p)) (sum_{l >= p} e_l x_lj)^2 per candidate, one pass over the candidate columns in blocks (cand: q ascending
+// columns or null = 0 .. q - 1; part: cox_addscore_split's part_doubles; only = 1 / 2 launches one of the two kernels
+// alone).  cox_addscore_split: a function of (n, q, block) alone; t_depth = the longest chain of additions behind a
+// t_j.  Device memory.
+void cox_addscore_split(long long n, int q, int block, long long *part_doubles, long long *rows_per_slab, int *slabs,
+                        int *t_depth);
+hipError_t launch_cox_addscore_pack(const void *src, int f32, long long rs, long long cs, long long n, const int *cols,
+                                    int m, int q, int block, const double *vw, const double *gw, const double *e,
+                                    const int *pos, const double *A, long long ldA, double *P, hipStream_t st);
+hipError_t launch_cox_addscore_cc(const double *wd, const double *S0, const int *first, const int *lastk, long long n,
+                                  double *scr, double *Cc, hipStream_t st);
+hipError_t launch_cox_addscore_quad(const void *src, int f32, long long rs, long long cs, long long n, const int *cand,
+                                    int q, int block, const int *rowof, const double *e, const double *Cc, double *part,
+                                    double *t, int only, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

@@ -185,6 +185,37 @@ hipError_t launch_cox_eval_eta(const void *src, int f32, long long rs, long long
   return xb_launch(static_cast<const double *>(src), rs, cs, n, cols, m, B, zero, R, epi, st);
 }
 
+// stage 1 for ONE model, ALWAYS k_xb_rows (never k_xb_gather, whose sums have another order): eta and ex are the same bits
+// under every layout of X, which the Cox score tests' layout-independent outputs rely on (bessx_k_coxaddscore.hip)
+template <typename T>
+static hipError_t cxe_launch_eta_rows(const T *src, long long rs, long long cs, long long n, const int *cols, int m,
+                                      const double *B, const double *zero, const CxStore &epi, hipStream_t st) {
+  const long long per16 = 16 / (long long)sizeof(T);
+  const bool vec = rs == 1 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && cs % per16 == 0;
+  const long long rows_per_block = 64LL * PrVec<T>::N;
+  const dim3 grid((unsigned)((n + rows_per_block - 1) / rows_per_block), 1);
+  if (vec)
+    hipLaunchKernelGGL((k_xb_rows<T, 1, true, CxStore>), grid, dim3(256), 0, st, src, rs, cs, n, cols, m, B, zero, 1, epi);
+  else
+    hipLaunchKernelGGL((k_xb_rows<T, 1, false, CxStore>), grid, dim3(256), 0, st, src, rs, cs, n, cols, m, B, zero, 1, epi);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+// whether launch_cox_eval_eta's own pass is k_xb_rows, i.e. its eta and ex are already those of launch_cox_eval_eta_rows
+bool cox_eval_eta_by_rows(long long rs, long long cs, int m) { return !(cs == 1 && rs != 1 && m > 0); }
+
+hipError_t launch_cox_eval_eta_rows(const void *src, int f32, long long rs, long long cs, long long n, const int *cols,
+                                    int m, const double *B, const double *zero, const int *pos, double *eta, double *ex,
+                                    hipStream_t st) {
+  if (!src || !zero || !pos || !eta || !ex || n < 1 || n > 0x7fffffffLL || m < 0 || (m > 0 && (!cols || !B)) || rs < 0 ||
+      cs < 0)
+    return hipErrorInvalidValue;
+  const CxStore epi{pos, n, eta, ex};
+  if (f32) return cxe_launch_eta_rows(static_cast<const float *>(src), rs, cs, n, cols, m, B, zero, epi, st);
+  return cxe_launch_eta_rows(static_cast<const double *>(src), rs, cs, n, cols, m, B, zero, epi, st);
+}
+
 // the first launch of stage 2 alone: scr[r * nb + b] = total of block b of row r of e (R x n), nb = ceil(n / 1024).  The
 // risk-set means of bessx_k_coxinfo.hip follow it with an apply launch of their own.
 hipError_t launch_cox_eval_scan_tot(const double *e, long long n, int R, double *scr, hipStream_t st) {

@@ -706,8 +706,9 @@ class bess_base:
         served in fp64 NumPy with the same definitions.  When the information is not positive definite statistic and
         p_value are NaN and nothing is raised.  A model fitted with group selection is tested column by column, one
         degree of freedom each: group tests with more degrees of freedom are not offered.  Selection is not corrected
-        for: the p-values are those of a test chosen before seeing the data.  Cox: None (its score test needs the
-        risk-set means of all p columns).  A 2-D beta (Lm fitted to several responses) raises ValueError."""
+        for: the p-values are those of a test chosen before seeing the data.  Cox: None (score_tests_survival, which
+        takes the (time, status) response and the tie rule, serves the Cox classes).  A 2-D beta (Lm fitted to several
+        responses) raises ValueError."""
         on_device = capi.is_device_array(X)
         shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
         if len(shape) != 2 or shape[1] != self.p:
@@ -960,6 +961,114 @@ class bess_base:
             return out
         out = capi.cox_wald_table(got["info"], got["score"], beta[cols], got["n_events"])
         out.update(cols=cols, loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
+        return out
+
+    # ---- Cox: score tests of the columns left out ----------------------------------------------------------------------
+    @staticmethod
+    def _cox_score_tests_host(X, cols, beta, time, status, w, ties, cand):
+        """cox_addscore_device's quantities in fp64 NumPy, by the same decomposition (running sums; no risk-set mean of a
+        candidate): X (n, p), cols the support, beta (m,), time, status, w (n,) in row order, cand the candidate columns
+        (int64) or None = all.  With a = e x_j and Cc the running sum of dh / S0, t_j = sum_l a_l (a_l Cc_l + 2 P_l), P
+        the exclusive running sum of Cc a."""
+        n, p = X.shape
+        m = cols.size
+        got = bess_base._cox_information_host(X[:, cols], beta, time, status, w, ties)
+        eta = np.zeros(n)
+        for c in range(m):  # (column by column: a row's sum does not depend on where the row lies)
+            eta += X[:, cols[c]] * beta[c]
+        order = np.argsort(time, kind="stable")
+        eta, t, d = eta[order], time[order], status[order]
+        wd = w[order] * d
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        starts = np.nonzero(new)[0]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        last = np.append(starts[1:] - 1, n - 1)[np.cumsum(new) - 1]
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))
+        e = np.exp(a)
+        breslow = ties == "breslow"
+        r = first if breslow else np.arange(n)
+        S0 = np.cumsum(e[::-1])[::-1][r]
+        h = wd / S0
+        H = np.cumsum(h)
+        if breslow:
+            H = H[last]
+            dh = np.zeros(n)
+            dh[starts] = np.add.reduceat(h, starts)
+        else:
+            dh = h
+        v = e * H
+        g = wd - v
+        Cc = np.cumsum(dh / S0)
+        xs = X[order][:, cols]
+        if m > 0:
+            u = np.cumsum((e[:, None] * xs)[::-1], axis=0)[::-1][r] / S0[:, None]
+            A = np.cumsum(dh[:, None] * u, axis=0)
+            P = v[:, None] * xs - e[:, None] * A
+        else:
+            P = np.zeros((n, 0))
+        columns = np.arange(p, dtype=np.int64) if cand is None else np.asarray(cand, dtype=np.int64)
+        q = columns.size
+        uu, dd, tt, C = np.empty(q), np.empty(q), np.empty(q), np.empty((q, m))
+        for j0 in range(0, q, 2048):  # (in blocks: no X-sized temporary here either)
+            XJ = X[:, columns[j0:j0 + 2048]][order]
+            uu[j0:j0 + 2048] = XJ.T @ g
+            C[j0:j0 + 2048] = XJ.T @ P
+            dd[j0:j0 + 2048] = v @ (XJ * XJ)
+            aj = e[:, None] * XJ
+            ca = Cc[:, None] * aj
+            Pl = np.cumsum(ca, axis=0) - ca
+            tt[j0:j0 + 2048] = np.sum(aj * (aj * Cc[:, None] + 2.0 * Pl), axis=0)
+        pd = True
+        if m == 0:
+            s, aa = np.zeros(q), np.zeros(q)
+        else:
+            R, pd = capi.info_factor(got["info"])
+            if pd:
+                rr = R.T @ (R @ got["score"])
+                T = C @ np.tril(R).T
+                s, aa = np.sum(T * T, axis=1), C @ rr
+            else:
+                s, aa = np.full(q, np.nan), np.full(q, np.nan)
+        out = dict(got)
+        out.update(columns=columns, u=uu, d=dd, t=tt, s=s, a=aa, cross=C, positive_definite=bool(pd),
+                   support=np.asarray(cols, dtype=np.int64))
+        return out
+
+    def score_tests_survival(self, X, y, weight=None, ties="order", candidates=None):
+        """Cox only: did the selection leave out a column that matters?  The Rao score test of every candidate column
+        against the fitted model on the rows (X, y), without refitting anything: capi.cox_score_test_table's dict --
+        columns, score (the adjusted score u - a), variance ((d - t) - s), statistic = score^2 / variance, p_value
+        (chi-square, 1 degree of freedom), in_model, dispersion = 1 -- plus cols, the model's support, loglik and
+        positive_definite.  y: (n, 2) time and status as in fit; weight: n values or None; ties: "order" (the risk sets
+        of the fit) or "breslow"; candidates: None = all p columns, else ascending distinct column numbers.  score and
+        variance are row j of the score and the Schur complement of the observed information of the partial likelihood
+        of the model extended by column j at coefficient 0 (capi.cox_addscore_device states the sums).  A candidate in
+        the support has in_model = True and NaN for statistic and p_value; a non-positive variance or an information
+        that is not positive definite gives NaN and nothing is raised.  An X in GPU memory is read in place on torch's
+        current stream, in one pass over the candidate columns on the fp64 matrix cores and one streaming pass for the
+        risk-set term, with no n x p temporary (y and weight may be device arrays: n values each are copied to the
+        host); a NumPy X is served in fp64 NumPy with the same decomposition.  Columns far from centred lose digits in
+        d - t (inference_survival's caveat).  Selection is not corrected for.  score_tests() stays None for the Cox
+        classes."""
+        if self.model_type_int != 4:
+            raise ValueError("score_tests_survival is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        self._survival_x(X)
+        cand, _ = capi._candidates(candidates, self.p)
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.cox_addscore_device(X, cols, beta[cols], time, status, weight=None if weight is None else w,
+                                           ties=ties, candidates=cand, stream=_current_stream(X))
+        else:
+            got = self._cox_score_tests_host(np.asarray(X, dtype=np.float64), cols, beta[cols], time, status, w, ties,
+                                             cand)
+        out = capi.cox_score_test_table(got)
+        out.update(cols=cols, loglik=float(got["loglik"]), positive_definite=bool(got["positive_definite"]))
         return out
 
     # ---- Cox: residuals, dfbeta and case influence -------------------------------------------------------------------

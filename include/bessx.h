@@ -813,8 +813,8 @@ int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_co
  *     m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED; q >= 1; n <= 2^31 - 1.  Every argument error is found before any
  *     device call (BESSX_ERR_ARG: the messages of sections 2d / 2g / 2i; candidates not ascending and distinct or not
  *     columns of x; q != p without a list; a candidate_block that is not a multiple of 16).  Scratch memory is released
- *     before the call returns.  Out of scope: Cox models, tests of groups of columns with more than one degree of
- *     freedom, any correction for selection.
+ *     before the call returns.  Out of scope: tests of groups of columns with more than one degree of freedom, any
+ *     correction for selection.  Cox models: section 2m.
  * ------------------------------------------------------------------------------------- */
 typedef struct {
   const void *x;
@@ -854,6 +854,81 @@ typedef struct {
 int bessx_addscore_device(const bessx_addscore_input *in, double *loss, double *sum_w);
 int bessx_addscore_workspace(int n, int m, int q, int candidate_block, long long *doubles, long long *rows_per_slab,
                              int *slabs, int *block, long long *block_doubles, int *sum_depth);
+/* ---------------------------------------------------------------------------------------
+ * 2m. Rao score tests of candidate columns against ONE Cox model on an X already in GPU memory
+ *     (bessx_k_coxaddscore.hip): section 2l's question for the model of section 2h.  Stateless like sections 2c to 2l.
+ *     x, n, p, cols, m, beta, time, status, weight, ties, stream, loglik, n_events, residual_sum and the definitions of
+ *     positions l, r(k), e, wd, S0, H, v, g: section 2h; info (m x m, info_ld >= m) and score are HOST memory here and,
+ *     with loglik, n_events and residual_sum, bit for bit those of bessx_cox_info_device for the same arguments.
+ *     candidates, q, candidate_block, out_on_device: section 2l.  factor = R, m x m lower triangular in HOST memory
+ *     (inverse(info) = R^T R; its strict upper triangle is never read), r = R^T (R score).  With dh_p = sum_{k : r(k) = p}
+ *     wd_k / S0(p), u_p = S1(p) / S0(p) the risk-set mean over the support and A_l = sum_{p <= l} dh_p u_p (section 2j), for
+ *     candidate j with entries x_lj at position l -- row j of the score and of the observed information of the model
+ *     extended by column j at coefficient 0:
+ *         u_j = sum_l g_l x_lj                                   raw score
+ *         c_j = sum_l x_lj (v_l x_l - e_l A_l)                   cross information with the support, m entries
+ *         d_j = sum_l v_l x_lj^2                                 first curvature term
+ *         t_j = sum_p (dh_p / S0(p)) (sum_{l >= p} e_l x_lj)^2   risk-set term: the information's diagonal entry is d_j - t_j
+ *         s_j = || R c_j ||^2,   a_j = c_j . r
+ *     The score statistic is (u_j - a_j)^2 / ((d_j - t_j) - s_j), chi-square with 1 degree of freedom, dispersion 1; the
+ *     subtractions, which can cancel, are left to the caller's fp64 host code (d - t loses digits for columns far from
+ *     centred: section 2h's G1 - G2 caveat).  u, d, t, s, a: q values each; cross: q rows of m + 1 values, cross[j *
+ *     cross_ld] = sum_l v_l x_lj (the panel's weight column, not part of the statistic) followed by the m entries of c_j,
+ *     cross_ld >= m + 1; null: not returned.  factor null: s and a are not formed (and may be null).  m = 0 is the test of
+ *     every column against the null model: s = a = 0 and the factor is not read.  No event at all: every output is 0.
+ *     Steps: section 2h's launches for info, score and loglik; where x is row-contiguous the predictor pass is repeated with
+ *     threads along rows, so that e and everything after it are the same bits under every layout; section 2j's A; the
+ *     panel P = (v_i, v_i x_i - e_i A_pos(i), g_i, zeros) in section 2l's layout, from which section 2l's kernels form u,
+ *     c, d on the fp64 matrix cores and s, a from the factor packed with a zero row and column in front; and t by one
+ *     streaming pass over the candidate columns: with a_l = e_l x_lj and Cc_l = sum_{p <= l} dh_p / S0(p),
+ *     t_j = sum_l a_l (a_l Cc_l + 2 sum_{l' < l} Cc_l' a_l'), a recurrence per candidate over slabs of positions whose
+ *     three partial numbers per slab are added in ascending order with a carry.  No n x q temporary, no risk-set mean of a
+ *     candidate, no floating-point atomics: the same call gives the same bits, and u, d, t, s, a, cross are the same bits
+ *     under every layout of the same element type.  A NaN inside a candidate column reaches that candidate only.
+ *     bessx_cox_addscore_workspace needs no device: *doubles of scratch memory in all for J = n_event_rows, the
+ *     *block_doubles of it that do not depend on p, the row split of the matrix-core pass (rows_per_slab[0], slabs[0])
+ *     and of the risk-set pass (rows_per_slab[1], slabs[1]) -- functions of n, m, q and candidate_block alone --, the
+ *     *block of candidates used, *sum_depth = the additions behind one s_j, chain[0] = the longest chain of additions
+ *     behind an entry of u, c, d (rows_per_slab[0] + ceil(slabs[0] / 16) + 4) and chain[1] behind a t_j.
+ *     m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED; q >= 1; n <= 2^31 - 1.  Every argument error is found before any
+ *     device call (BESSX_ERR_ARG: the messages of sections 2e / 2h / 2l).  Scratch memory is released before the call
+ *     returns.  Out of scope: Efron ties, strata, tests of groups with more than one degree of freedom, any correction
+ *     for selection.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  const double *factor;
+  long long factor_ld;
+  const int *candidates;
+  int q;
+  int candidate_block;
+  double *info;
+  long long info_ld;
+  double *score;
+  double *u;
+  double *d;
+  double *t;
+  double *s;
+  double *a;
+  double *cross;
+  long long cross_ld;
+  int out_on_device;
+  void *stream;
+} bessx_cox_addscore_input;
+int bessx_cox_addscore_device(const bessx_cox_addscore_input *in, double *loglik, double *n_events, double *residual_sum);
+int bessx_cox_addscore_workspace(int n, int m, int n_event_rows, int q, int candidate_block, long long *doubles,
+                                 long long *block_doubles, long long *rows_per_slab, int *slabs, int *block,
+                                 int *sum_depth, int *chain);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1286,6 +1361,14 @@ int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long
 int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, const int *candidates, int q, int candidate_block, int repeats,
                             double *stage_ms);
+/* The kernels of section 2m timed the same way, from n-vectors, an A and a factor of the library's own, each over every
+ * block of candidates: stage_ms[0] the pack of the panel, [1] the cross product on the matrix cores, [2] the streaming
+ * pass of the risk-set term, [3] the addition of its slabs, [4] the addition of the cross partials, [5] the statistic
+ * kernel.  sorted != 0: the rows are in time order already; else a scattered order.  *bytes = what stage 2 needs: the
+ * candidate columns once.  m >= 0. */
+int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                                const int *cols, int m, const int *candidates, int q, int candidate_block, int sorted,
+                                int repeats, double *stage_ms, double *bytes);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
