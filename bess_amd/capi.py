@@ -48,6 +48,7 @@ SYMBOLS = [
     "bessx_meat_device", "bessx_sandwich_device", "bessx_sandwich_workspace", "bessx_op_sandwich_bench",
     "bessx_addscore_device", "bessx_addscore_workspace", "bessx_op_addscore_bench",
     "bessx_cox_addscore_device", "bessx_cox_addscore_workspace", "bessx_op_cox_addscore_bench",
+    "bessx_groupscore_device", "bessx_groupscore_workspace", "bessx_op_groupscore_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -187,6 +188,19 @@ class CoxAddscoreInput(ctypes.Structure):
                 ("factor", _D), ("factor_ld", _ll), ("candidates", _I), ("q", _i), ("candidate_block", _i),
                 ("info", _D), ("info_ld", _ll), ("score", _D), ("u", _vp), ("d", _vp), ("t", _vp), ("s", _vp),
                 ("a", _vp), ("cross", _vp), ("cross_ld", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class GroupscoreInput(ctypes.Structure):
+    """bessx_groupscore_input: bessx_info_input's model and data, the factor of the inverse information in host memory (or
+    null), the partition of the columns into contiguous groups, the tested groups (or null = all), the candidate block,
+    and where info, score, u, a, the packed blocks D and S and their offsets go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("coef0", _d), ("link", _i), ("y_host", _D), ("y_dev", _vp),
+                ("y_dtype", _i), ("y_stride", _ll), ("weight_host", _D), ("weight_dev", _vp), ("weight_dtype", _i),
+                ("weight_stride", _ll), ("factor", _D), ("factor_ld", _ll), ("group_starts", _I), ("n_groups", _i),
+                ("groups", _I), ("n_tested", _i), ("candidate_block", _i), ("info", _D), ("info_ld", _ll), ("score", _D),
+                ("u", _vp), ("a", _vp), ("D", _vp), ("S", _vp), ("offsets", ctypes.POINTER(_ll)), ("out_on_device", _i),
+                ("stream", _vp)]
 
 
 class RResult(ctypes.Structure):
@@ -340,6 +354,10 @@ def lib():
         L.bessx_cox_addscore_workspace.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll),
                                                    ctypes.POINTER(_ll), _I, _I, _I, _I]
         L.bessx_op_cox_addscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _i, _i, _i, _D, _D]
+        L.bessx_groupscore_device.argtypes = [ctypes.POINTER(GroupscoreInput), _D, _D]
+        L.bessx_groupscore_workspace.argtypes = [_i, _i, _i, _I, _i, _I, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll),
+                                                 ctypes.POINTER(_ll), _I, _I, _I, _I, _I]
+        L.bessx_op_groupscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _I, _i, _i, _i, _D]
         _lib = L
     return _lib
 
@@ -1797,7 +1815,8 @@ def addscore_device(x, cols, beta, coef0, y, link="identity", weight=None, facto
     all candidate columns on the fp64 matrix cores; no x-sized temporary; candidates go in blocks of candidate_block (0
     = the library's choice; a multiple of 16), so scratch beyond the n x Mp panel does not depend on p (addscore_workspace).
     The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  Cox
-    models: cox_addscore_device.  Not for groups of columns with more than one degree of freedom, not corrected for selection.
+    models: cox_addscore_device.  Groups of columns with more than one degree of freedom: groupscore_device.  Not corrected
+    for selection.
     len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
     dx = _DeviceArray(x, "x", 2)
     n, p = dx.shape
@@ -1905,6 +1924,276 @@ def op_addscore_bench(x, cols, candidates=None, candidate_block=0, repeats=5):
     _check(lib().bessx_op_addscore_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                          _ip(cols), cols.size, _ip(cand), q, int(candidate_block), repeats, ms))
     return dict(zip(("pack", "cross", "finish", "statistic"), [float(v) for v in ms]))
+
+
+GROUPSCORE_WIDTH_MAX = 64  # columns of a tested group (bessx_groupscore_device)
+
+
+def _group_lists(group_starts, groups, p):
+    """(int32 starts, int32 tested groups or None) as the library takes them.  Only the shapes and dtypes are checked
+    here: what the lists must satisfy is the library's to say (BESSX_ERR_ARG / BESSX_ERR_UNSUPPORTED)."""
+    gs = np.asarray(group_starts)
+    if gs.ndim != 1 or gs.size < 1 or not np.issubdtype(gs.dtype, np.integer):
+        raise ValueError("group_starts must be a non-empty 1-D list of integer column numbers")
+    tg = None
+    if groups is not None:
+        tg = np.asarray(groups)
+        if tg.ndim != 1 or tg.size < 1 or not np.issubdtype(tg.dtype, np.integer):
+            raise ValueError("groups must be a non-empty 1-D list of integer group numbers or None")
+        tg = _i32(tg)
+    return _i32(gs), tg
+
+
+def _group_columns(gs, tg, p):
+    """(tested group numbers, widths, columns, group_of_column) of lists the library accepts, else None."""
+    G = gs.size
+    if gs[0] != 0 or (np.diff(gs) <= 0).any() or gs[-1] >= p:
+        return None
+    tested = np.arange(G, dtype=np.int64) if tg is None else tg.astype(np.int64)
+    if tested.min() < 0 or tested.max() >= G or (np.diff(tested) <= 0).any():
+        return None
+    ends = np.append(gs[1:], p).astype(np.int64)
+    width = ends[tested] - gs[tested]
+    columns = np.concatenate([np.arange(gs[g], ends[g], dtype=np.int64) for g in tested])
+    return tested, width, columns, np.repeat(tested, width)
+
+
+def groupscore_workspace(n, p, m, group_starts, groups=None, candidate_block=0):
+    """What a groupscore_device call on n rows and p columns with a support of m columns needs and how it is split
+    (bessx_groupscore_workspace; no device is needed): {"doubles": scratch memory in all, "block_doubles": the part of it
+    beyond v, g and the panel, which does not depend on p, "rows_per_slab", "slabs": the row split of u and C (section 2l's,
+    for the block with the longest chain), "gram_rows_per_slab", "gram_slabs": the row split of D, a function of n alone,
+    "blocks", "block_first": the first tested group of every block, then the number of tested groups -- a function of
+    (group_starts, groups, candidate_block) alone --, "band": w, and the longest chains of additions "depth" (u, C),
+    "score_depth" (the score behind r), "gram_depth" (D), "s_depth" (S)}."""
+    gs, tg = _group_lists(group_starts, groups, p)
+    nt = gs.size if tg is None else tg.size
+    nd, bd, rps, sl, nb, first, band, dep = _ll(0), _ll(0), (_ll * 2)(), (_i * 2)(), _i(0), (_i * (nt + 1))(), _i(0), (_i * 4)()
+    _check(lib().bessx_groupscore_workspace(int(n), int(p), int(m), _ip(gs), gs.size, _ip(tg), nt, int(candidate_block),
+                                            ctypes.byref(nd), ctypes.byref(bd), rps, sl, ctypes.byref(nb), first,
+                                            ctypes.byref(band), dep))
+    return {"doubles": nd.value, "block_doubles": bd.value, "rows_per_slab": rps[0], "slabs": sl[0],
+            "gram_rows_per_slab": rps[1], "gram_slabs": sl[1], "blocks": nb.value,
+            "block_first": [int(first[k]) for k in range(nb.value + 1)], "band": band.value, "depth": dep[0],
+            "score_depth": dep[1], "gram_depth": dep[2], "s_depth": dep[3]}
+
+
+def groupscore_device(x, cols, beta, coef0, y, group_starts, groups=None, link="identity", weight=None, factor=None,
+                      stream=0, candidate_block=0):
+    """The ingredients of the Rao score test of every tested GROUP of columns against ONE model on a device matrix x
+    (n x p: float64 or float32, any non-negative strides), read where it lies (bessx_groupscore_device).  The model and
+    v, g, z, M, info, score, loss, sum_w, factor and r are addscore_device's.  group_starts: G ascending start columns
+    with group_starts[0] = 0, group g = columns group_starts[g] .. group_starts[g + 1] - 1 (the last one ends at p - 1);
+    groups: ascending distinct group numbers, None = all.  For a tested group with columns J, d = len(J) <= 64:
+        u = X_J^T g,   C = X_J^T diag(v) Z,   a = C r,   D = X_J^T diag(v) X_J,   S = (C R^T)(C R^T)^T
+    Returns {"columns", "group_of_column", "u", "a" (one value per tested column), "D", "S" (the d x d blocks one after
+    another, row-major, block t at offsets[t], each exactly symmetric), "offsets" (len(groups) + 1), "info", "score",
+    "loss", "sum_w", "positive_definite", "support"} (NumPy, host).  The subtractions u - a and D - S, the d x d
+    Cholesky factor and the quadratic form are group_score_test_table's.  factor None: information_device and
+    info_factor are called first (and when the information is not positive definite, S and a are NaN).  The band of
+    X_J^T diag(v) X_J around the diagonal is formed on the fp64 matrix cores with x read in place; no x-sized temporary;
+    blocks of candidate_block columns (0 = the library's choice; a multiple of 16, at least the widest tested group
+    rounded up to 16) hold whole groups, so scratch beyond the n x Mp panel does not depend on p (groupscore_workspace).
+    The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  A tested
+    group wider than 64 columns is BessxError code 3.  Not for Cox models, not corrected for selection.  len(cols) + 1 <=
+    1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: groupscore_device takes one model per call")
+    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
+    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
+        raise ValueError("beta and coef0 must be finite")
+    gs, tg = _group_lists(group_starts, groups, p)
+    nt = gs.size if tg is None else tg.size
+    lists = _group_columns(gs, tg, p)
+    ok = lists is not None and lists[1].max() <= GROUPSCORE_WIDTH_MAX  # (else the library refuses before it writes)
+    q, tot = (int(lists[1].sum()), int((lists[1] * lists[1]).sum())) if ok else (1, 1)
+    M = cols.size + 1
+    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
+    a = GroupscoreInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
+    a.y_stride = yrs
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [weight]
+    if weight is not None:
+        if is_device_array(weight):
+            dw = _DeviceArray(weight, "weight")
+            if dw.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        else:
+            wh = _f64(weight).reshape(-1)
+            if wh.size != n:
+                raise ValueError("X.shape(0) should be equal to weight.size")
+            a.weight_host = _dp(wh)
+            keep.append(wh)
+    pd = True
+    if factor is None:
+        first = information_device(x, cols, B.reshape(-1), float(c0[0]), y, link=link, weight=weight, stream=stream)
+        fh, pd = info_factor(first["info"])
+    else:
+        fh = _f64(factor)
+        if fh.shape != (M, M):
+            raise ValueError("factor must have shape (%d, %d), got %s" % (M, M, fh.shape))
+    if pd:
+        a.factor, a.factor_ld = _dp(fh), M
+    a.group_starts, a.n_groups, a.groups, a.n_tested = _ip(gs), gs.size, _ip(tg), nt
+    a.candidate_block = int(candidate_block)
+    info, score = np.empty((M, M)), np.empty(M)
+    vec, blk, offsets = np.full((2, q), np.nan), np.full((2, tot), np.nan), np.zeros(nt + 1, dtype=np.int64)
+    a.info, a.info_ld, a.score = _dp(info), M, _dp(score)
+    a.u, a.a, a.D, a.S = vec[0].ctypes.data, vec[1].ctypes.data, blk[0].ctypes.data, blk[1].ctypes.data
+    a.offsets = offsets.ctypes.data_as(ctypes.POINTER(_ll))
+    a.out_on_device = 0
+    a.stream = int(stream) if stream else None
+    loss, sw = _d(0), _d(0)
+    _check(lib().bessx_groupscore_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw)))
+    return {"columns": lists[2], "group_of_column": lists[3], "u": vec[0], "a": vec[1], "D": blk[0], "S": blk[1],
+            "offsets": offsets, "info": info, "score": score, "loss": loss.value, "sum_w": sw.value,
+            "positive_definite": bool(pd), "support": cols.astype(np.int64)}
+
+
+def chi2_sf(x, df):
+    """The upper tail of the chi-square distribution with df > 0 degrees of freedom at x: Q(df / 2, x / 2), the
+    regularised upper incomplete gamma function, in fp64 with no dependence outside the standard library.  For an
+    integer df up to 512 (and x / 2 <= 700, so that exp(-x / 2) is a normal number) the finite recurrence
+    Q(a + 1, y) = Q(a, y) + y^a exp(-y) / Gamma(a + 1) is run from Q(1/2, y) = erfc(sqrt(y)) or Q(1, y) = exp(-y): sums of
+    positive terms, so df = 1 and df = 2 are score_test_table's erfc and the exponential to the last bits.  Otherwise
+    1 - the series of the lower function below y = a + 1 and the continued fraction (modified Lentz) above.  NaN for a
+    NaN or negative x; 1 at 0; 0 at inf."""
+    import math
+    x, a = float(x), 0.5 * float(df)
+    if not a > 0:
+        raise ValueError("df must be positive")
+    if x != x or x < 0:
+        return float("nan")
+    if x == 0:
+        return 1.0
+    if x == float("inf"):
+        return 0.0
+    y = 0.5 * x
+    if float(df) == int(df) and df <= 512 and y <= 700.0:
+        df = int(df)
+        if df % 2:
+            s, t, k, steps = math.erfc(math.sqrt(y)), 2.0 * math.sqrt(y / math.pi) * math.exp(-y), 1.5, (df - 1) // 2
+        else:
+            s = math.exp(-y)
+            t, k, steps = y * s, 2.0, df // 2 - 1
+        for _ in range(steps):  # t = y^(k - 1) exp(-y) / Gamma(k): the step from Q(k - 1, y) to Q(k, y)
+            s += t
+            t *= y / k
+            k += 1.0
+        return min(s, 1.0)
+    front = math.exp(-y + a * math.log(y) - math.lgamma(a))
+    if y < a + 1.0:
+        term = total = 1.0 / a
+        ak = a
+        for _ in range(10000):
+            ak += 1.0
+            term *= y / ak
+            total += term
+            if term < total * 1e-17:
+                break
+        return min(max(1.0 - front * total, 0.0), 1.0)
+    tiny = 1e-300
+    b = y + 1.0 - a
+    c, dd = 1.0 / tiny, 1.0 / b
+    hh = dd
+    for i in range(1, 10000):
+        an = -i * (i - a)
+        b += 2.0
+        dd = an * dd + b
+        dd = tiny if abs(dd) < tiny else dd
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        dd = 1.0 / dd
+        de = dd * c
+        hh *= de
+        if abs(de - 1.0) < 1e-15:
+            break
+    return min(max(front * hh, 0.0), 1.0)
+
+
+def group_score_test_table(got, link):
+    """The Rao score test of every tested group from what groupscore_device (or the NumPy route) returns, on the host in
+    fp64.  For a group with d columns: adj = u - a, V = D - S, statistic = adj^T inverse(V) adj / dispersion through the
+    Cholesky factor of V scaled to unit diagonal, p_value = chi2_sf(statistic, d).  dispersion is score_test_table's:
+    loss / (sum_w - M) for the identity link (NaN when sum_w - M <= 0), 1 otherwise.  A group with any column in the
+    model's support ("support" of got) has in_model = True and NaN for statistic and p_value.  A group whose V has a
+    diagonal entry that is not finite and positive, or whose scaled V has no Cholesky factor with positive pivots (a
+    group that the support, or the rest of the group, reproduces) has NaN as well; nothing is raised.  Returns {"group",
+    "first_column", "df" (one value per tested group), "score" (a list: the adjusted vector of each group), "statistic",
+    "p_value", "in_model", "dispersion"}.  Selection is not corrected for."""
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    u, a = np.asarray(got["u"], dtype=np.float64), np.asarray(got["a"], dtype=np.float64)
+    D, S = np.asarray(got["D"], dtype=np.float64), np.asarray(got["S"], dtype=np.float64)
+    columns = np.asarray(got["columns"], dtype=np.int64)
+    goc = np.asarray(got["group_of_column"], dtype=np.int64)
+    offsets = np.asarray(got["offsets"], dtype=np.int64)
+    M = np.asarray(got["score"]).size
+    if link == "identity":
+        dof = float(got["sum_w"]) - M
+        dispersion = float(got["loss"]) / dof if dof > 0 else float("nan")
+    else:
+        dispersion = 1.0
+    nt = offsets.size - 1
+    df = np.rint(np.sqrt(np.diff(offsets))).astype(np.int64)
+    pos = np.concatenate([[0], np.cumsum(df)])
+    support = np.asarray(got.get("support", np.zeros(0)), dtype=np.int64)
+    col_in = np.isin(columns, support)
+    group, first = np.empty(nt, dtype=np.int64), np.empty(nt, dtype=np.int64)
+    stat, pv, in_model, adjs = np.full(nt, np.nan), np.full(nt, np.nan), np.zeros(nt, dtype=bool), []
+    adj_all = u - a
+    for t in range(nt):
+        j0, j1, d = int(pos[t]), int(pos[t + 1]), int(df[t])
+        group[t], first[t] = goc[j0], columns[j0]
+        adj = adj_all[j0:j1]
+        adjs.append(adj)
+        in_model[t] = bool(col_in[j0:j1].any())
+        if in_model[t]:
+            continue
+        V = D[offsets[t]:offsets[t + 1]].reshape(d, d) - S[offsets[t]:offsets[t + 1]].reshape(d, d)
+        dg = np.diag(V)
+        if not (np.isfinite(V).all() and np.isfinite(adj).all() and (dg > 0).all()):
+            continue
+        sc = 1.0 / np.sqrt(dg)
+        try:
+            L = np.linalg.cholesky((V * sc[:, None]) * sc[None, :])
+        except np.linalg.LinAlgError:
+            continue
+        if not (np.isfinite(L).all() and (np.diag(L) > 0).all()):
+            continue
+        z, rhs = np.zeros(d), adj * sc
+        for j in range(d):  # (forward substitution: the operations the tests' error bound is derived for)
+            z[j] = (rhs[j] - L[j, :j] @ z[:j]) / L[j, j]
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            stat[t] = float(z @ z) / dispersion
+        if stat[t] == stat[t] and stat[t] >= 0:
+            pv[t] = chi2_sf(stat[t], d)
+    return {"group": group, "first_column": first, "df": df, "score": adjs, "statistic": stat, "p_value": pv,
+            "in_model": in_model, "dispersion": dispersion}
+
+
+def op_groupscore_bench(x, cols, group_starts, groups=None, candidate_block=0, repeats=5):
+    """ms per step of the group score test on the device matrix x for the support cols, device events, each over every
+    block of candidates: {"pack", "cross", "finish", "gram", "gram_sum", "s_band", "extract"}
+    (bessx_op_groupscore_bench)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    gs, tg = _group_lists(group_starts, groups, dx.shape[1])
+    ms = (_d * 7)()
+    _check(lib().bessx_op_groupscore_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                           _ip(cols), cols.size, _ip(gs), gs.size, _ip(tg),
+                                           gs.size if tg is None else tg.size, int(candidate_block), repeats, ms))
+    return dict(zip(("pack", "cross", "finish", "gram", "gram_sum", "s_band", "extract"), [float(v) for v in ms]))
 
 
 TIES = {"order": 0, "breslow": 1}  # bessx_cox_eval_input.ties

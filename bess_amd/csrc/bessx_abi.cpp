@@ -4492,3 +4492,449 @@ int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, 
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// score tests of groups of candidate columns against one model on a caller's device matrix (include/bessx.h section 2n)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int GS_WIDTH_MAX = 64;   // columns of a tested group
+constexpr int GS_BLOCK = 2048;     // candidates per block unless the caller asks for fewer (AS_BLOCK)
+
+// the tested columns and how they are cut: everything about a call that follows from (starts, groups, candidate_block)
+struct GsPlan {
+  std::vector<int> cand, lpos, width, first;  // tested columns; list position of each tested group (+ q); widths; blocks
+  std::vector<long long> offs;                // where each tested group's d x d block starts (+ the total)
+  int nt = 0, q = 0, dmax = 0, band = 0, blocks = 0, qmax = 0, block = 0;
+};
+
+int groupscore_plan(const std::string &w, int p, const int *starts, int G, const int *groups, int n_tested, int block,
+                    GsPlan *pl) {
+  if (!starts || G < 1) return fail(BESSX_ERR_ARG, w + ": group_starts must hold at least one group");
+  if (starts[0] != 0) return fail(BESSX_ERR_ARG, w + ": group_starts must begin with column 0");
+  for (int g = 1; g < G; g++)
+    if (starts[g] <= starts[g - 1]) return fail(BESSX_ERR_ARG, w + ": group_starts must be ascending and distinct");
+  if (starts[G - 1] >= p) return fail(BESSX_ERR_ARG, w + ": a group start is not a column of x");
+  pl->nt = groups ? n_tested : G;
+  if (pl->nt < 1) return fail(BESSX_ERR_ARG, w + ": n_tested must be at least 1");
+  if (groups)
+    for (int t = 0; t < pl->nt; t++) {
+      if (groups[t] < 0 || groups[t] >= G) return fail(BESSX_ERR_ARG, w + ": a tested group is not a group of the partition");
+      if (t > 0 && groups[t] <= groups[t - 1]) return fail(BESSX_ERR_ARG, w + ": groups must be ascending and distinct");
+    }
+  if (int rc = addscore_check_block(w, block)) return rc;
+  pl->block = block > 0 ? block : GS_BLOCK;
+  pl->width.resize((size_t)pl->nt);
+  pl->lpos.assign((size_t)pl->nt + 1, 0);
+  pl->offs.assign((size_t)pl->nt + 1, 0);
+  pl->cand.clear();
+  for (int t = 0; t < pl->nt; t++) {
+    const int g = groups ? groups[t] : t, c0 = starts[g], c1 = g + 1 < G ? starts[g + 1] : p, d = c1 - c0;
+    if (d > GS_WIDTH_MAX)
+      return fail(BESSX_ERR_UNSUPPORTED, w + ": group " + std::to_string(g) + " has " + std::to_string(d) +
+                                             " columns; a tested group may have at most " + std::to_string(GS_WIDTH_MAX));
+    pl->width[(size_t)t] = d;
+    pl->dmax = std::max(pl->dmax, d);
+    pl->lpos[(size_t)t + 1] = pl->lpos[(size_t)t] + d;
+    pl->offs[(size_t)t + 1] = pl->offs[(size_t)t] + (long long)d * d;
+    for (int c = c0; c < c1; c++) pl->cand.push_back(c);
+  }
+  pl->q = pl->lpos[(size_t)pl->nt];
+  if (pl->block < (pl->dmax + 15) / 16 * 16)
+    return fail(BESSX_ERR_ARG, w + ": candidate_block must be at least the widest tested group rounded up to 16 (" +
+                                   std::to_string((pl->dmax + 15) / 16 * 16) + ")");
+  pl->band = groupscore_band(pl->dmax);
+  pl->first.assign((size_t)pl->nt + 1, 0);
+  pl->blocks = groupscore_cut(pl->width.data(), pl->nt, pl->block, pl->first.data());
+  pl->first.resize((size_t)pl->blocks + 1);
+  for (int b = 0; b < pl->blocks; b++)
+    pl->qmax = std::max(pl->qmax, pl->lpos[(size_t)pl->first[(size_t)b + 1]] - pl->lpos[(size_t)pl->first[(size_t)b]]);
+  return 0;
+}
+
+// section 2l's block workspace for the blocks of a plan (the largest over the blocks) and the longest chain of additions
+// behind an entry of u or C
+void groupscore_cross_figures(long long n, int m, const GsPlan &pl, long long *work, long long *rps_max, int *slabs_at,
+                              int *chain) {
+  *work = 0, *rps_max = 0, *slabs_at = 0, *chain = 0;
+  for (int b = 0; b < pl.blocks; b++) {
+    const int qb = pl.lpos[(size_t)pl.first[(size_t)b + 1]] - pl.lpos[(size_t)pl.first[(size_t)b]];
+    long long panel = 0, blk = 0, rps = 0;
+    int slabs = 0, cb = 0, depth = 0;
+    addscore_split(n, m, qb, pl.block, &panel, &blk, &rps, &slabs, &cb, &depth);
+    *work = std::max(*work, blk);
+    const int ch = (int)std::min<long long>(0x7fffffffLL, rps + (slabs + 15) / 16 + 4);
+    if (ch > *chain) *chain = ch, *rps_max = rps, *slabs_at = slabs;
+  }
+}
+
+bessx_info_input groupscore_as_info(const bessx_groupscore_input *in) {
+  bessx_info_input a{};
+  a.x = in->x;
+  a.x_dtype = in->x_dtype;
+  a.x_row_stride = in->x_row_stride;
+  a.x_col_stride = in->x_col_stride;
+  a.n = in->n;
+  a.p = in->p;
+  a.cols = in->cols;
+  a.m = in->m;
+  a.beta = in->beta;
+  a.coef0 = in->coef0;
+  a.link = in->link;
+  a.y_host = in->y_host;
+  a.y_dev = in->y_dev;
+  a.y_dtype = in->y_dtype;
+  a.y_stride = in->y_stride;
+  a.weight_host = in->weight_host;
+  a.weight_dev = in->weight_dev;
+  a.weight_dtype = in->weight_dtype;
+  a.weight_stride = in->weight_stride;
+  a.info = in->info;
+  a.info_ld = in->info_ld;
+  a.score = in->score;
+  a.out_on_device = 0;
+  a.stream = in->stream;
+  return a;
+}
+
+// everything about the call that needs no device
+int groupscore_check_args(const char *who, const bessx_groupscore_input *in, const double *loss, const double *sum_w,
+                          GsPlan *pl) {
+  const std::string w(who);
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const bessx_info_input a = groupscore_as_info(in);
+  if (int rc = info_check_args(who, &a, loss, sum_w)) return rc;
+  if (!in->u || !in->D || !in->offsets) return fail(BESSX_ERR_ARG, w + ": null argument (u, D, offsets)");
+  if (in->factor && (!in->S || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (S, a)");
+  if (int rc = groupscore_plan(w, in->p, in->group_starts, in->n_groups, in->groups, in->n_tested, in->candidate_block, pl))
+    return rc;
+  if (in->factor) {
+    if (in->factor_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m + 1");
+    for (long long j = 0; j <= in->m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  return 0;
+}
+
+// the device arrays of the blocks' loop
+struct GsDev {
+  const void *x;
+  int f32;
+  long long rs, cs, n;
+  int m;
+  int *cand, *lpos;
+  long long *offs;
+  double *v, *P, *work_as, *work_gs, *dd;  // row weights, the panel, section 2l's and this section's block workspace
+};
+
+// stage: 0 = everything, else ONE step over every block (bessx_op_groupscore_bench): 1 = the cross product, 2 = the
+// addition of its partials, 3 = the Gram band, 4 = the addition of its partials, 5 = T, the band of S and a, 6 = the
+// extraction of D and S.  with_s: the factor is packed in work_gs's tail.  u, a: q doubles; D, S: offs[nt] doubles.
+int groupscore_blocks(const GsPlan &pl, const GsDev &d, int with_s, double *u, double *a, double *D, double *S, int stage,
+                      hipStream_t st) {
+  const int M = d.m + 1, Mp = 16 * ((M + 1 + 15) / 16), NT = pl.band + 1;
+  long long rps = 0;
+  int slabs = 0;
+  groupscore_rows(d.n, &rps, &slabs);
+  const long long trm = (pl.qmax + 15) / 16;
+  // groupscore_doubles' layout for the largest block: partials and band of D (launch_groupscore_gram puts a block's
+  // band right behind that block's partials), band of S, the block's rows of C and of T, the packed factor
+  double *bandS = d.work_gs + (slabs + 1) * trm * NT * 256, *Cb = bandS + trm * NT * 256, *Tb = Cb + trm * 16 * Mp,
+         *pk = Tb + trm * 16 * Mp;
+  for (int b = 0; b < pl.blocks; b++) {
+    const int g0 = pl.first[(size_t)b], g1 = pl.first[(size_t)b + 1], j0 = pl.lpos[(size_t)g0], qb = pl.lpos[(size_t)g1] - j0;
+    const long long trb = (qb + 15) / 16;
+    // u and the block's rows of C (leading dimension Mp; what k_as_finish does not write stays zero)
+    if (stage == 0 || stage == 1) HIPX(hipMemsetAsync(Cb, 0, (size_t)(trb * 16 * Mp) * sizeof(double), st));
+    if (stage <= 2)
+      HIPX(launch_addscore_blocks(d.x, d.f32, d.rs, d.cs, d.n, d.m, d.cand + j0, qb, pl.block, d.P, d.work_as, 0, u + j0, d.dd,
+                                  nullptr, nullptr, Cb, (long long)Mp, stage, st));
+    if (stage == 0 || stage == 3 || stage == 4)
+      HIPX(launch_groupscore_gram(d.x, d.f32, d.rs, d.cs, d.n, d.cand + j0, qb, pl.band, d.v, d.work_gs,
+                                  stage == 0 ? 0 : stage - 2, st));
+    if (with_s && (stage == 0 || stage == 5))
+      HIPX(launch_groupscore_sband(Cb, d.m, qb, pl.band, pk, Tb, bandS, a + j0, st));
+    if (stage == 0 || stage == 6) {
+      HIPX(launch_groupscore_extract(d.work_gs + (long long)slabs * trb * NT * 256, pl.band, d.lpos, d.offs, g0, g1 - g0, D,
+                                     st));
+      if (with_s) HIPX(launch_groupscore_extract(bandS, pl.band, d.lpos, d.offs, g0, g1 - g0, S, st));
+    }
+  }
+  return 0;
+}
+
+// the lists of a plan in device memory
+int groupscore_upload_plan(Owner &sc, const GsPlan &pl, hipStream_t st, GsDev *d) {
+  HIPX(sc.alloc(&d->cand, (size_t)pl.q));
+  HIPX(sc.alloc(&d->lpos, pl.lpos.size()));
+  HIPX(sc.alloc(&d->offs, pl.offs.size()));
+  HIPX(hipMemcpyAsync(d->cand, pl.cand.data(), (size_t)pl.q * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->lpos, pl.lpos.data(), pl.lpos.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->offs, pl.offs.data(), pl.offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// sc, pl, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int groupscore_run(Owner &sc, const GsPlan &pl, std::vector<double> &pk, std::vector<double> &h,
+                   const bessx_groupscore_input *in, double *loss, double *sum_w, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const bessx_info_input ia = groupscore_as_info(in);
+  const bessx_eval_input e = info_as_eval(&ia);
+  const int f32 = in->x_dtype == BESSX_F32, m = in->m;
+  const long long n = in->n, nv = (n + 1) / 2 * 2;
+  const size_t M = (size_t)m + 1, Q = (size_t)pl.q, TOT = (size_t)pl.offs[(size_t)pl.nt];
+  const bool with_s = in->factor != nullptr;
+  long long panel = 0, blk = 0, rps = 0, work_as = 0, rpsx = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsx = 0, chain = 0;
+  addscore_split(n, m, pl.qmax, pl.block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  groupscore_cross_figures(n, m, pl, &work_as, &rpsx, &slabsx, &chain);
+  const long long work_gs = groupscore_doubles(n, m, pl.qmax, pl.band);
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *c_d = nullptr, *iwork = nullptr, *res = nullptr, *istage = nullptr, *vg = nullptr,
+         *ostage = nullptr;
+  GsDev d{};
+  d.x = in->x, d.f32 = f32, d.rs = in->x_row_stride, d.cs = in->x_col_stride, d.n = n, d.m = m;
+  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
+  EvalData ed;
+  if (int rc = eval_stage_data(sc, &e, st, &ed)) return rc;
+  // 1. info, score, loss and sum_w: launch_info as bessx_info_device runs it (the same bits)
+  HIPX(sc.alloc(&iwork, (size_t)info_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, m, in->link,
+                                                ed.w != nullptr)));
+  HIPX(sc.alloc(&res, 3));
+  HIPX(sc.alloc(&istage, M * M + M));
+  HIPX(launch_info(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, B_d, c_d, in->link, ed, iwork, res, istage,
+                   (long long)M, istage + M * M, st));
+  h.resize(3 + M * M + 2 * M);
+  HIPX(hipMemcpyAsync(h.data(), res, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipMemcpyAsync(h.data() + 3, istage, (M * M + M) * sizeof(double), hipMemcpyDeviceToHost, st));
+  // 2. the row weights, always by rows, and section 2l's panel
+  HIPX(sc.alloc(&vg, (size_t)(2 * nv)));
+  HIPX(launch_info_vg(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, B_d, c_d, in->link, ed, vg, vg + nv,
+                      st));
+  d.v = vg;
+  HIPX(sc.alloc(&d.P, (size_t)panel));
+  HIPX(sc.alloc(&d.work_as, (size_t)work_as));
+  HIPX(sc.alloc(&d.work_gs, (size_t)work_gs));
+  HIPX(sc.alloc(&d.dd, (size_t)(pl.qmax + 15) / 16 * 16));
+  if (int rc = groupscore_upload_plan(sc, pl, st, &d)) return rc;
+  HIPX(launch_addscore_pack(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, pl.qmax, pl.block, vg, vg + nv,
+                            d.P, st));
+  // the score behind r, summed by section 2l's kernels over the list (constant column, support), as section 2l does
+  std::vector<int> cand0;
+  double *u0 = nullptr;
+  if (with_s) {
+    long long panel0 = 0, blk0 = 0, rps0 = 0;
+    int slabs0 = 0, cb0 = 0, depth0 = 0, *cand0_d = nullptr;
+    double *work0 = nullptr;
+    addscore_split(n, m, (int)M, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+    cand0.assign(M, -1);
+    std::copy(in->cols, in->cols + m, cand0.begin() + 1);
+    HIPX(sc.alloc(&cand0_d, M));
+    HIPX(sc.alloc(&work0, (size_t)blk0));
+    HIPX(sc.alloc(&u0, 2 * M));
+    HIPX(hipMemcpyAsync(cand0_d, cand0.data(), M * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(launch_addscore_blocks(in->x, f32, in->x_row_stride, in->x_col_stride, n, m, cand0_d, (int)M, 0, d.P, work0, 0, u0,
+                                u0 + M, nullptr, nullptr, nullptr, 0, 0, st));
+    HIPX(hipMemcpyAsync(h.data() + 3 + M * M + M, u0, M * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  *loss = h[0];
+  *sum_w = ed.w ? h[2] : (double)in->n;
+  for (size_t j = 0; j < M; j++) std::copy(h.begin() + 3 + j * M, h.begin() + 3 + (j + 1) * M, in->info + j * in->info_ld);
+  std::copy(h.begin() + 3 + M * M, h.begin() + 3 + M * M + M, in->score);
+  if (with_s) {
+    // r = inverse(info) U = R^T (R U), on the host in fp64
+    const double *U0 = h.data() + 3 + M * M + M;
+    std::vector<double> t(M, 0.0), r(M, 0.0);
+    for (size_t j = 0; j < M; j++)
+      for (size_t k = 0; k <= j; k++) t[j] += in->factor[j * in->factor_ld + k] * U0[k];
+    for (size_t j = 0; j < M; j++)
+      for (size_t k = 0; k <= j; k++) r[k] += in->factor[j * in->factor_ld + k] * t[j];
+    pk.resize((size_t)diag_factor_doubles(m + 1));
+    addscore_pack_factor(in->factor, in->factor_ld, r.data(), m, pk.data());
+    HIPX(hipMemcpyAsync(d.work_gs + work_gs - (long long)pk.size(), pk.data(), pk.size() * sizeof(double),
+                        hipMemcpyHostToDevice, st));
+  }
+  double *u = in->u, *a = in->a, *D = in->D, *S = in->S;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&ostage, 2 * Q + 2 * TOT));
+    u = ostage, a = ostage + Q, D = ostage + 2 * Q, S = D + TOT;
+  }
+  if (int rc = groupscore_blocks(pl, d, with_s ? 1 : 0, u, a, D, S, 0, st)) return rc;
+  if (!in->out_on_device) {
+    h.resize(2 * Q + 2 * TOT);
+    HIPX(hipMemcpyAsync(h.data(), ostage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device) {
+    std::copy(h.begin(), h.begin() + Q, in->u);
+    std::copy(h.begin() + 2 * Q, h.begin() + 2 * Q + TOT, in->D);
+    if (with_s) {
+      std::copy(h.begin() + Q, h.begin() + 2 * Q, in->a);
+      std::copy(h.begin() + 2 * Q + TOT, h.begin() + 2 * Q + 2 * TOT, in->S);
+    }
+  }
+  std::copy(pl.offs.begin(), pl.offs.end(), in->offsets);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_groupscore_workspace(int n, int p, int m, const int *group_starts, int n_groups, const int *groups,
+                               int n_tested, int candidate_block, long long *doubles, long long *block_doubles,
+                               long long *rows_per_slab, int *slabs, int *n_blocks, int *block_first, int *band,
+                               int *depth) {
+  if (!doubles || !block_doubles || !rows_per_slab || !slabs || !n_blocks || !band || !depth)
+    return fail(BESSX_ERR_ARG, "groupscore_workspace: null argument");
+  if (n < 1 || p < 1 || m < 0) return fail(BESSX_ERR_ARG, "groupscore_workspace: empty matrix");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "groupscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  GsPlan pl;
+  if (int rc = groupscore_plan("groupscore_workspace", p, group_starts, n_groups, groups, n_tested, candidate_block, &pl))
+    return rc;
+  long long panel = 0, blk = 0, rps = 0, work_as = 0;
+  int sl = 0, cb = 0, dp = 0;
+  addscore_split(n, m, pl.qmax, pl.block, &panel, &blk, &rps, &sl, &cb, &dp);
+  groupscore_cross_figures(n, m, pl, &work_as, &rows_per_slab[0], &slabs[0], &depth[0]);
+  groupscore_rows(n, &rows_per_slab[1], &slabs[1]);
+  // (plus the block workspace of the score behind r, whose candidates are the constant column and the support)
+  long long panel0 = 0, blk0 = 0, rps0 = 0;
+  int slabs0 = 0, cb0 = 0, depth0 = 0;
+  addscore_split(n, m, m + 1, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+  depth[1] = (int)std::min<long long>(0x7fffffffLL, rps0 + (slabs0 + 15) / 16 + 4);
+  depth[2] = (int)std::min<long long>(0x7fffffffLL, rows_per_slab[1] + slabs[1]);
+  depth[3] = 16 * ((m + 2 + 15) / 16);
+  *block_doubles = work_as + groupscore_doubles(n, m, pl.qmax, pl.band) + (pl.qmax + 15) / 16 * 16 + blk0 +
+                   2 * ((long long)m + 1);
+  *doubles = 2 * (((long long)n + 1) / 2 * 2) + panel + *block_doubles;
+  *n_blocks = pl.blocks;
+  *band = pl.band;
+  if (block_first) std::copy(pl.first.begin(), pl.first.end(), block_first);
+  return BESSX_OK;
+}
+
+int bessx_groupscore_device(const bessx_groupscore_input *in, double *loss, double *sum_w) {
+  GsPlan pl;
+  if (int rc = groupscore_check_args("groupscore_device", in, loss, sum_w, &pl)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("groupscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
+                                   in->p, &dev))
+    return rc;
+  if (in->y_dev) {
+    if (int rc = check_device_matrix("groupscore_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "groupscore_device: y is not on the device that owns x");
+  }
+  if (in->weight_dev) {
+    if (int rc = check_device_matrix("groupscore_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
+                                     in->n, 1, &od))
+      return rc;
+    if (od != dev) return fail(BESSX_ERR_ARG, "groupscore_device: weight is not on the device that owns x");
+  }
+  if (in->out_on_device) {
+    const long long tot = pl.offs[(size_t)pl.nt];
+    double *const vec[4] = {in->u, in->factor ? in->a : nullptr, in->D, in->factor ? in->S : nullptr};
+    const long long len[4] = {pl.q, pl.q, tot, tot};
+    for (int k = 0; k < 4; k++) {
+      if (!vec[k]) continue;
+      if (len[k] > 0x7fffffffLL) return fail(BESSX_ERR_ARG, "groupscore_device: too many block entries for device output");
+      if (int rc = check_device_matrix("groupscore_device: u, a, D, S", vec[k], BESSX_F64, 1, 0, (int)len[k], 1, &od))
+        return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "groupscore_device: an output is not on the device that owns x");
+    }
+  }
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> pk, h;
+    rc = groupscore_run(sc, pl, pk, h, in, loss, sum_w, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                              const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
+                              int n_tested, int candidate_block, int repeats, double *stage_ms) {
+  if (!x || repeats < 1 || !stage_ms) return fail(BESSX_ERR_ARG, "op_groupscore_bench: bad arguments");
+  if (int rc = predict_check_model("op_groupscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_groupscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  GsPlan pl;
+  if (int rc = groupscore_plan("op_groupscore_bench", p, group_starts, n_groups, groups, n_tested, candidate_block, &pl))
+    return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_groupscore_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t M = (size_t)m + 1, Q = (size_t)pl.q, TOT = (size_t)pl.offs[(size_t)pl.nt];
+  long long panel = 0, blk = 0, rps = 0, work_as = 0, rpsx = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsx = 0, chain = 0;
+  addscore_split(n, m, pl.qmax, pl.block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  groupscore_cross_figures(n, m, pl, &work_as, &rpsx, &slabsx, &chain);
+  const long long work_gs = groupscore_doubles(n, m, pl.qmax, pl.band);
+  // row weights and a factor of the library's own, as bessx_op_addscore_bench has them
+  std::vector<double> v((size_t)n, 0.25), g((size_t)n), R(M * M, 0.0), r(M, 1.0 / 128.0),
+      pk((size_t)diag_factor_doubles(m + 1));
+  for (size_t i = 0; i < g.size(); i++) g[i] = (i % 2) ? -0.5 : 0.5;
+  for (size_t j = 0; j < M; j++)
+    for (size_t k = 0; k <= j; k++) R[j * M + k] = (j == k ? 1.0 : 1.0 / 64.0) / std::sqrt((double)n);
+  addscore_pack_factor(R.data(), (long long)M, r.data(), m, pk.data());
+  int *cols_d = nullptr;
+  double *g_d = nullptr, *out = nullptr;
+  GsDev d{};
+  d.x = x, d.f32 = dtype == BESSX_F32, d.rs = row_stride, d.cs = col_stride, d.n = n, d.m = m;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&d.v, v.size()));
+  HIPX(sc.alloc(&g_d, g.size()));
+  HIPX(sc.alloc(&d.P, (size_t)panel));
+  HIPX(sc.alloc(&d.work_as, (size_t)work_as));
+  HIPX(sc.alloc(&d.work_gs, (size_t)work_gs));
+  HIPX(sc.alloc(&d.dd, (size_t)(pl.qmax + 15) / 16 * 16));
+  HIPX(sc.alloc(&out, 2 * Q + 2 * TOT));
+  if (int rc = groupscore_upload_plan(sc, pl, nullptr, &d)) return rc;
+  if (m > 0) HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(d.v, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(d.work_gs + work_gs - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  auto run = [&](int stage) -> int {
+    if (stage == 0) {
+      HIPX(launch_addscore_pack(x, d.f32, row_stride, col_stride, n, cols_d, m, pl.qmax, pl.block, d.v, g_d, d.P, nullptr));
+      return 0;
+    }
+    return groupscore_blocks(pl, d, 1, out, out + Q, out + 2 * Q, out + 2 * Q + TOT, stage, nullptr);
+  };
+  // (stage 0 = pack, then groupscore_blocks' steps 1 .. 6, each over every block, in an order in which a later stage
+  // finds the earlier one's results of the last block)
+  for (int stage = 0; stage < 7; stage++) {
+    if (int rc = run(stage)) return rc;  // the warm-up
+    HIPX(hipEventRecord(e0, nullptr));
+    for (int i = 0; i < repeats; i++)
+      if (int rc = run(stage)) return rc;
+    HIPX(hipEventRecord(e1, nullptr));
+    HIPX(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    stage_ms[stage] = ms / repeats;
+  }
+  return BESSX_OK;
+}
+
+}  // extern "C"

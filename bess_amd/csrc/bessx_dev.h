@@ -255,6 +255,24 @@ hipError_t launch_cox_addscore_cc(const double *wd, const double *S0, const int 
 hipError_t launch_cox_addscore_quad(const void *src, int f32, long long rs, long long cs, long long n, const int *cand,
                                     int q, int block, const int *rowof, const double *e, const double *Cc, double *part,
                                     double *t, int only, hipStream_t st);
+// score tests of groups of candidate columns against one model (bessx_k_groupscore.hip), on top of launch_info_vg and
+// the launchers of bessx_k_addscore.hip.  _band: w = the furthest tile a group of at most dmax columns reaches beyond the
+// tile it starts in.  _rows: the row split of the Gram kernel, a function of n alone.  _cut: the tested groups (widths d,
+// each <= block) in blocks of whole groups, first[b] = first group of block b, first[blocks] = nt (host; returns blocks).
+// _doubles: this unit's workspace for blocks of at most qmax columns: partials and band of D, band of S, the block's rows
+// of C and of T, and LAST the packed factor of addscore_pack_factor.  _gram: the band of D of one block (only = 1 / 2
+// launches one of its two kernels alone); _sband: T = C Rx^T, the band of S and a; _extract: the groups' d x d blocks out
+// of a band, upper triangle mirrored.  band + 1 <= 5.  Everything else is device memory.
+int groupscore_band(int dmax);
+void groupscore_rows(long long n, long long *rows_per_slab, int *slabs);
+int groupscore_cut(const int *d, int nt, int block, int *first);
+long long groupscore_doubles(long long n, int m, int qmax, int band);
+hipError_t launch_groupscore_gram(const void *src, int f32, long long rs, long long cs, long long n, const int *cand,
+                                  int qb, int band, const double *vw, double *work, int only, hipStream_t st);
+hipError_t launch_groupscore_sband(const double *Cb, int m, int qb, int band, const double *pk, double *Tb, double *bandS,
+                                   double *a, hipStream_t st);
+hipError_t launch_groupscore_extract(const double *bandT, int band, const int *lpos, const long long *offs, int g0, int ng,
+                                     double *out, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

@@ -704,8 +704,8 @@ class bess_base:
         torch's current stream in one pass over the candidate columns on the fp64 matrix cores
         (capi.addscore_device), with no X-sized temporary, and y and weight may be device arrays too; a NumPy X is
         served in fp64 NumPy with the same definitions.  When the information is not positive definite statistic and
-        p_value are NaN and nothing is raised.  A model fitted with group selection is tested column by column, one
-        degree of freedom each: group tests with more degrees of freedom are not offered.  Selection is not corrected
+        p_value are NaN and nothing is raised.  Every column is tested on its own, one degree of freedom each: the test
+        of a whole group of columns (a model fitted with group selection) is score_tests_groups.  Selection is not corrected
         for: the p-values are those of a test chosen before seeing the data.  Cox: None (score_tests_survival, which
         takes the (time, status) response and the tie rule, serves the Cox classes).  A 2-D beta (Lm fitted to several
         responses) raises ValueError."""
@@ -742,6 +742,135 @@ class bess_base:
                      else np.asarray(weight, dtype=np.float64)).reshape(-1)
             got = self._score_tests_host(link, np.asarray(X, dtype=np.float64), cols, beta[cols], coef0[0], yh, w, cand)
         out = capi.score_test_table(got, link)
+        out["cols"] = cols
+        return out
+
+    @staticmethod
+    def _group_runs(group, p):
+        """The start column of every run of equal labels in the length-p label vector fit() takes: labels must be
+        non-decreasing, so that each group is one contiguous run."""
+        g = np.asarray(group).reshape(-1)
+        if g.size != p:
+            raise ValueError("group should have one label per column of X (%d), got %d" % (p, g.size))
+        if p > 1 and (np.diff(g) < 0).any():
+            raise ValueError("group labels must be non-decreasing: every group is a contiguous run of columns")
+        return np.concatenate([[0], np.flatnonzero(np.diff(g) != 0) + 1]).astype(np.int32)
+
+    @staticmethod
+    def _score_tests_groups_host(link, X, cols, beta, coef0, y, w, starts, groups):
+        """groupscore_device's quantities in fp64 NumPy with the same definitions: X (n, p), cols the support, beta
+        (m,), y (n,), w (n,), starts the groups' start columns, groups the tested group numbers or None = all.  Matrix
+        products over the n rows; the tested columns go in blocks of at most 2 048 that hold whole groups."""
+        n, p = X.shape
+        Xs = X[:, cols]
+        eta = Xs @ beta + coef0
+        if link == "identity":
+            v, g, f = w.copy(), w * (y - eta), (y - eta) ** 2
+        elif link == "logistic":
+            t = np.exp(-np.abs(eta))
+            pr = np.where(eta >= 0, 1.0, t) / (1.0 + t)
+            v, g = w * (t / ((1.0 + t) * (1.0 + t))), w * (y - pr)
+            f = np.maximum(eta, 0.0) + np.log1p(t) - y * eta
+        else:
+            e = np.exp(eta)
+            v, g, f = w * e, w * (y - e), e - y * eta
+        Z = np.column_stack([np.ones(n), Xs])
+        P = v[:, None] * Z
+        info = Z.T @ P
+        info = np.tril(info) + np.tril(info, -1).T
+        score = Z.T @ g
+        R, pd = capi.info_factor(info)
+        lists = capi._group_columns(np.asarray(starts, dtype=np.int32), None if groups is None else
+                                    np.asarray(groups, dtype=np.int32), p)
+        if lists is None:
+            raise ValueError("groups must be ascending distinct group numbers")
+        tested, width, columns, goc = lists
+        q, nt = columns.size, tested.size
+        pos = np.concatenate([[0], np.cumsum(width)])
+        offsets = np.concatenate([[0], np.cumsum(width * width)]).astype(np.int64)
+        u, a = np.empty(q), np.full(q, np.nan)
+        D, S = np.empty(int(offsets[-1])), np.full(int(offsets[-1]), np.nan)
+        if pd:
+            r, Rl = R.T @ (R @ score), np.tril(R)
+        t0 = 0
+        while t0 < nt:  # (a block: whole groups, at most 2 048 columns unless one group alone is wider)
+            t1 = t0 + 1
+            while t1 < nt and pos[t1 + 1] - pos[t0] <= 2048:
+                t1 += 1
+            j0 = int(pos[t0])
+            XJ = X[:, columns[j0:int(pos[t1])]]
+            u[j0:int(pos[t1])] = XJ.T @ g
+            C = XJ.T @ P
+            VX = v[:, None] * XJ
+            if pd:
+                a[j0:int(pos[t1])] = C @ r
+                T = C @ Rl.T
+            for t in range(t0, t1):
+                k0, k1 = int(pos[t]) - j0, int(pos[t + 1]) - j0
+                Dg = np.triu(XJ[:, k0:k1].T @ VX[:, k0:k1])
+                D[offsets[t]:offsets[t + 1]] = (Dg + np.triu(Dg, 1).T).reshape(-1)
+                if pd:
+                    Sg = np.triu(T[k0:k1] @ T[k0:k1].T)
+                    S[offsets[t]:offsets[t + 1]] = (Sg + np.triu(Sg, 1).T).reshape(-1)
+            t0 = t1
+        return {"columns": columns, "group_of_column": goc, "u": u, "a": a, "D": D, "S": S, "offsets": offsets,
+                "info": info, "score": score, "loss": float((w * f).sum()), "sum_w": float(w.sum()),
+                "positive_definite": bool(pd), "support": np.asarray(cols, dtype=np.int64)}
+
+    def score_tests_groups(self, X, y, group, weight=None, groups=None):
+        """Did the selection leave out a GROUP that matters?  The Rao score test of every group of columns -- a
+        dummy-coded factor, a spline basis: the units fit(..., group=...) selects -- against the fitted model on the
+        rows (X, y), d degrees of freedom for a group of d columns, without refitting anything:
+        capi.group_score_test_table's dict -- group (the number of the group in the order of its columns), first_column,
+        df, score (the adjusted score vector u - a of each group), statistic = score^T inverse(D - S) score / dispersion,
+        p_value (chi-square, df degrees of freedom), in_model, dispersion -- plus cols, the model's support.  group: the
+        length-p label vector fit() takes; labels must be non-decreasing, so that every group is a contiguous run of
+        columns (ValueError otherwise).  groups: None = all groups, else ascending distinct group numbers (0 = the
+        first run).  A group with a column in the support has in_model = True and NaN for statistic and p_value; a
+        group whose D - S is not positive definite (one that the support, or the rest of the group, reproduces) has NaN
+        as well.  The information and the dispersion are inference()'s.  An X in GPU memory is read in place on torch's
+        current stream (capi.groupscore_device: a tested group may have at most 64 columns), with no X-sized temporary,
+        and y and weight may be device arrays too; a NumPy X is served in fp64 NumPy with the same definitions.  When
+        the information is not positive definite statistic and p_value are NaN and nothing is raised.  For Lm,
+        statistic * dispersion is the drop in the residual sum of squares on adding the whole group.  Selection is not
+        corrected for.  Cox: None.  A 2-D beta (Lm fitted to several responses) raises ValueError."""
+        on_device = capi.is_device_array(X)
+        shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
+        if len(shape) != 2 or shape[1] != self.p:
+            raise ValueError("X.shape[1] should be " + str(self.p))
+        n = shape[0]
+        starts = self._group_runs(group, self.p)
+        _, tg = capi._group_lists(starts, groups, self.p)
+        if tg is not None and (tg.min() < 0 or tg.max() >= starts.size or (np.diff(tg) <= 0).any()):
+            raise ValueError("groups must be ascending distinct group numbers (0 .. %d)" % (starts.size - 1))
+        if self.model_type_int == 4:
+            return None
+        beta, cols, coef0, multi = self._model_arrays()
+        if multi:
+            raise ValueError("score_tests_groups() takes one model: this Lm was fitted to %d responses (a 2-D beta), "
+                             "which is not supported" % beta.shape[1])
+        link = self._LINK[self.model_type_int]
+        y_dev, w_dev = capi.is_device_array(y), weight is not None and capi.is_device_array(weight)
+        ysize = capi._DeviceArray(y, "y").size if y_dev else np.size(y)
+        if ysize != n:
+            raise ValueError("X.shape(0) should be equal to y.size")
+        if weight is not None and (capi._DeviceArray(weight, "weight").size if w_dev else np.size(weight)) != n:
+            raise ValueError("X.shape(0) should be equal to weight.size")
+        if on_device:
+            if not y_dev:
+                y = np.asarray(y, dtype=np.float64).reshape(-1)
+            got = capi.groupscore_device(X, cols, beta[cols], coef0[0], y, starts, groups=tg, link=link, weight=weight,
+                                         stream=_current_stream(X))
+        else:
+            yh = (capi.device_to_host(y, _current_stream(y)) if y_dev else np.asarray(y, dtype=np.float64)).reshape(-1)
+            if weight is None:
+                w = np.ones(n)
+            else:
+                w = (capi.device_to_host(weight, _current_stream(weight)) if w_dev
+                     else np.asarray(weight, dtype=np.float64)).reshape(-1)
+            got = self._score_tests_groups_host(link, np.asarray(X, dtype=np.float64), cols, beta[cols], coef0[0], yh, w,
+                                                starts, tg)
+        out = capi.group_score_test_table(got, link)
         out["cols"] = cols
         return out
 

@@ -813,8 +813,8 @@ int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_co
  *     m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED; q >= 1; n <= 2^31 - 1.  Every argument error is found before any
  *     device call (BESSX_ERR_ARG: the messages of sections 2d / 2g / 2i; candidates not ascending and distinct or not
  *     columns of x; q != p without a list; a candidate_block that is not a multiple of 16).  Scratch memory is released
- *     before the call returns.  Out of scope: tests of groups of columns with more than one degree of freedom, any
- *     correction for selection.  Cox models: section 2m.
+ *     before the call returns.  Tests of groups of columns with more than one degree of freedom: section 2n.  Cox
+ *     models: section 2m.  Out of scope: any correction for selection.
  * ------------------------------------------------------------------------------------- */
 typedef struct {
   const void *x;
@@ -929,6 +929,95 @@ int bessx_cox_addscore_device(const bessx_cox_addscore_input *in, double *loglik
 int bessx_cox_addscore_workspace(int n, int m, int n_event_rows, int q, int candidate_block, long long *doubles,
                                  long long *block_doubles, long long *rows_per_slab, int *slabs, int *block,
                                  int *sum_depth, int *chain);
+/* ---------------------------------------------------------------------------------------
+ * 2n. Rao score tests of GROUPS of candidate columns against ONE fitted model on an X already in GPU memory
+ *     (bessx_k_groupscore.hip): did the selection leave out a group -- a dummy-coded factor, a spline basis -- that
+ *     matters?  Stateless like sections 2c to 2m.  x, n, p, cols, m, beta, coef0, link, y, weight, stream, info, info_ld,
+ *     score, loss, sum_w, factor = R, r, v_i, g_i, z_i, M = m + 1: section 2l.  The p columns are partitioned into
+ *     n_groups contiguous groups by group_starts (HOST memory): ascending distinct start columns, group_starts[0] = 0,
+ *     group g = columns group_starts[g] .. group_starts[g + 1] - 1, the last group ends at p - 1.  groups: n_tested
+ *     ascending distinct group numbers in HOST memory, or null = all groups (n_tested is then not read).  For a tested
+ *     group with columns J, d = |J|:
+ *         u_g = X_J^T g                        raw score, d values
+ *         C_g = X_J^T diag(v) Z                cross information, d x M (not returned)
+ *         a_g = C_g r                          shift of the score, d values
+ *         D_g = X_J^T diag(v) X_J              curvature, d x d
+ *         S_g = (C_g R^T) (C_g R^T)^T          curvature explained by the support, d x d; its diagonal is section 2l's s_j
+ *     The score statistic is (u_g - a_g)^T inverse(D_g - S_g) (u_g - a_g) / dispersion, chi-square with d degrees of
+ *     freedom: the subtractions, which can cancel, the d x d Cholesky factor and the quadratic form are left to the
+ *     caller's fp64 host code.  u and a hold one value per tested column, the tested groups' columns one after another
+ *     in ascending order; D and S hold the blocks one after another, block t row-major d x d at offsets[t] doubles, and
+ *     every block is exactly symmetric (the upper triangle is formed and mirrored).  offsets (n_tested + 1 values, the
+ *     last one the length of D and of S) is always HOST memory; u, a, D, S are device memory of x's device when
+ *     out_on_device != 0, else host memory.  factor null: S and a are not formed (and may be null).
+ *     Steps: v, g, info, score, loss, sum_w, the panel P, u and the rows of C exactly as in section 2l, by its launches;
+ *     the tested columns of a block are tiled 16 per tile in ascending order whatever the group boundaries are, and for
+ *     every tile row t the band tiles (t, t) .. (t, t + w) of X^T diag(v) X are formed on the fp64 matrix cores with both
+ *     operands read from x in place, w = (widest tested group + 14) / 16 the furthest tile a group reaches beyond the one
+ *     it starts in; the row slabs' partials are added in ascending order; T = C Rx^T as in section 2l, written out, its
+ *     column M being a; the band tiles T_t T_{t+k}^T on the matrix cores over the columns < M in ascending steps; and a
+ *     copy of every group's block out of the two bands.  Above the diagonal an entry of D is always sum_i x_ij (v_i
+ *     x_ij') with j < j'.  No floating-point atomics: the same call gives the same bits, and u, a, D, S are the same bits
+ *     under every layout of the same element type.  Rows past n, columns outside the support and the tested groups and
+ *     the padding of tiles are not read; a NaN inside the view propagates by IEEE rules.  Blocks of candidates hold whole
+ *     groups: a block is closed when the next tested group would take it past candidate_block columns (0 = the
+ *     library's choice, else a positive multiple of 16), a function of (group_starts, groups, candidate_block) alone;
+ *     scratch memory is 2 n + n_pad Mp doubles plus a block workspace that does not depend on p.  The row split of u and
+ *     C is section 2l's for the block's number of columns; that of D is a function of n alone.
+ *     bessx_groupscore_workspace needs no device: *doubles of scratch memory in all, the *block_doubles of it that do
+ *     not depend on p, the row split of u and C for the block with the longest chain (rows_per_slab[0], slabs[0]) and
+ *     of D (rows_per_slab[1], slabs[1]), *n_blocks and, where block_first is not null, the first tested group of every
+ *     block followed by n_tested (n_blocks + 1 values; room for n_tested + 1), the *band width w, and the longest chains
+ *     of additions: depth[0] behind an entry of u or C (rows_per_slab[0] + ceil(slabs[0] / 16) + 4), depth[1] behind an
+ *     entry of the score that r is formed from, depth[2] behind an entry of D (rows_per_slab[1] + slabs[1]), depth[3]
+ *     behind an entry of S (Mp).
+ *     A tested group of more than 64 columns is BESSX_ERR_UNSUPPORTED (the message names the group), as is m + 1 > 1024;
+ *     n <= 2^31 - 1.  Every argument error is found before any device call (BESSX_ERR_ARG: the messages of sections 2d /
+ *     2g / 2i / 2l; group_starts not ascending from 0 or not columns of x; groups not ascending and distinct or out of
+ *     range; a candidate_block that is not a multiple of 16 or is below the widest tested group rounded up to 16).
+ *     Scratch memory is released before the call returns.  Out of scope: Cox models, any correction for selection.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  double coef0;
+  int link;
+  const double *y_host;
+  const void *y_dev;
+  int y_dtype;
+  long long y_stride;
+  const double *weight_host;
+  const void *weight_dev;
+  int weight_dtype;
+  long long weight_stride;
+  const double *factor;
+  long long factor_ld;
+  const int *group_starts;
+  int n_groups;
+  const int *groups;
+  int n_tested;
+  int candidate_block;
+  double *info;
+  long long info_ld;
+  double *score;
+  double *u;
+  double *a;
+  double *D;
+  double *S;
+  long long *offsets;
+  int out_on_device;
+  void *stream;
+} bessx_groupscore_input;
+int bessx_groupscore_device(const bessx_groupscore_input *in, double *loss, double *sum_w);
+int bessx_groupscore_workspace(int n, int p, int m, const int *group_starts, int n_groups, const int *groups,
+                               int n_tested, int candidate_block, long long *doubles, long long *block_doubles,
+                               long long *rows_per_slab, int *slabs, int *n_blocks, int *block_first, int *band,
+                               int *depth);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1369,6 +1458,13 @@ int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long
 int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                                 const int *cols, int m, const int *candidates, int q, int candidate_block, int sorted,
                                 int repeats, double *stage_ms, double *bytes);
+/* The steps of section 2n timed the same way, from row weights and a factor of the library's own, each over every block
+ * of candidates: stage_ms[0] the pack of the panel, [1] section 2l's cross product, [2] the addition of its partials,
+ * [3] the Gram band on the matrix cores, [4] the addition of its partials, [5] T, the band of S and a, [6] the copy of
+ * the groups' blocks of D and S.  group_starts / n_groups / groups / n_tested / candidate_block as in section 2n. */
+int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                              const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
+                              int n_tested, int candidate_block, int repeats, double *stage_ms);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
