@@ -49,6 +49,7 @@ SYMBOLS = [
     "bessx_addscore_device", "bessx_addscore_workspace", "bessx_op_addscore_bench",
     "bessx_cox_addscore_device", "bessx_cox_addscore_workspace", "bessx_op_cox_addscore_bench",
     "bessx_groupscore_device", "bessx_groupscore_workspace", "bessx_op_groupscore_bench",
+    "bessx_cox_groupscore_device", "bessx_cox_groupscore_workspace", "bessx_op_cox_groupscore_bench",
     "bessx_comm_unique_id", "bessx_comm_init", "bessx_comm_rank", "bessx_comm_world", "bessx_comm_allgather_f64",
     "bessx_comm_destroy",
 ]
@@ -200,6 +201,18 @@ class GroupscoreInput(ctypes.Structure):
                 ("weight_stride", _ll), ("factor", _D), ("factor_ld", _ll), ("group_starts", _I), ("n_groups", _i),
                 ("groups", _I), ("n_tested", _i), ("candidate_block", _i), ("info", _D), ("info_ld", _ll), ("score", _D),
                 ("u", _vp), ("a", _vp), ("D", _vp), ("S", _vp), ("offsets", ctypes.POINTER(_ll)), ("out_on_device", _i),
+                ("stream", _vp)]
+
+
+class CoxGroupscoreInput(ctypes.Structure):
+    """bessx_cox_groupscore_input: bessx_cox_addscore_input's model and data, the factor of the inverse information in host
+    memory (or null), bessx_groupscore_input's partition, tested groups and candidate block, and where info, score, u, a,
+    the packed blocks D, T and S and their offsets go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
+                ("factor", _D), ("factor_ld", _ll), ("group_starts", _I), ("n_groups", _i), ("groups", _I),
+                ("n_tested", _i), ("candidate_block", _i), ("info", _D), ("info_ld", _ll), ("score", _D), ("u", _vp),
+                ("a", _vp), ("D", _vp), ("T", _vp), ("S", _vp), ("offsets", ctypes.POINTER(_ll)), ("out_on_device", _i),
                 ("stream", _vp)]
 
 
@@ -358,6 +371,10 @@ def lib():
         L.bessx_groupscore_workspace.argtypes = [_i, _i, _i, _I, _i, _I, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll),
                                                  ctypes.POINTER(_ll), _I, _I, _I, _I, _I]
         L.bessx_op_groupscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _I, _i, _i, _i, _D]
+        L.bessx_cox_groupscore_device.argtypes = [ctypes.POINTER(CoxGroupscoreInput), _D, _D, _D]
+        L.bessx_cox_groupscore_workspace.argtypes = [_i, _i, _i, _i, _I, _i, _I, _i, _i, ctypes.POINTER(_ll),
+                                                     ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I, _I, _I, _I, _I]
+        L.bessx_op_cox_groupscore_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _I, _i, _I, _i, _i, _i, _i, _D, _D]
         _lib = L
     return _lib
 
@@ -1995,8 +2012,8 @@ def groupscore_device(x, cols, beta, coef0, y, group_starts, groups=None, link="
     blocks of candidate_block columns (0 = the library's choice; a multiple of 16, at least the widest tested group
     rounded up to 16) hold whole groups, so scratch beyond the n x Mp panel does not depend on p (groupscore_workspace).
     The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  A tested
-    group wider than 64 columns is BessxError code 3.  Not for Cox models, not corrected for selection.  len(cols) + 1 <=
-    1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
+    group wider than 64 columns is BessxError code 3.  Cox models: cox_groupscore_device.  Not corrected for selection.
+    len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
     dx = _DeviceArray(x, "x", 2)
     n, p = dx.shape
     if link not in LINKS:
@@ -2133,17 +2150,23 @@ def group_score_test_table(got, link):
     "p_value", "in_model", "dispersion"}.  Selection is not corrected for."""
     if link not in LINKS:
         raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
-    u, a = np.asarray(got["u"], dtype=np.float64), np.asarray(got["a"], dtype=np.float64)
     D, S = np.asarray(got["D"], dtype=np.float64), np.asarray(got["S"], dtype=np.float64)
-    columns = np.asarray(got["columns"], dtype=np.int64)
-    goc = np.asarray(got["group_of_column"], dtype=np.int64)
-    offsets = np.asarray(got["offsets"], dtype=np.int64)
     M = np.asarray(got["score"]).size
     if link == "identity":
         dof = float(got["sum_w"]) - M
         dispersion = float(got["loss"]) / dof if dof > 0 else float("nan")
     else:
         dispersion = 1.0
+    return _group_score_table(got, lambda lo, hi: D[lo:hi] - S[lo:hi], dispersion)
+
+
+def _group_score_table(got, v_of, dispersion):
+    """The loop of group_score_test_table and cox_group_score_test_table: v_of(lo, hi) gives the d * d entries of a
+    group's V from the packed blocks' entries lo .. hi - 1."""
+    u, a = np.asarray(got["u"], dtype=np.float64), np.asarray(got["a"], dtype=np.float64)
+    columns = np.asarray(got["columns"], dtype=np.int64)
+    goc = np.asarray(got["group_of_column"], dtype=np.int64)
+    offsets = np.asarray(got["offsets"], dtype=np.int64)
     nt = offsets.size - 1
     df = np.rint(np.sqrt(np.diff(offsets))).astype(np.int64)
     pos = np.concatenate([[0], np.cumsum(df)])
@@ -2160,7 +2183,7 @@ def group_score_test_table(got, link):
         in_model[t] = bool(col_in[j0:j1].any())
         if in_model[t]:
             continue
-        V = D[offsets[t]:offsets[t + 1]].reshape(d, d) - S[offsets[t]:offsets[t + 1]].reshape(d, d)
+        V = v_of(offsets[t], offsets[t + 1]).reshape(d, d)
         dg = np.diag(V)
         if not (np.isfinite(V).all() and np.isfinite(adj).all() and (dg > 0).all()):
             continue
@@ -2702,8 +2725,8 @@ def cox_addscore_device(x, cols, beta, time, status, weight=None, ties="order", 
     risk-set mean of a candidate is formed; candidates go in blocks of candidate_block (0 = the library's choice; a
     multiple of 16), so scratch beyond the support-sized arrays and the panel does not depend on p
     (cox_addscore_workspace).  The same call gives the same bits, and every layout of the same values of one dtype
-    gives the same bits.  Not for Efron ties, strata, groups of columns with more than one degree of freedom, not
-    corrected for selection.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
+    gives the same bits.  Groups of columns with more than one degree of freedom: cox_groupscore_device.  Not for Efron
+    ties or strata, not corrected for selection.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
     dx = _DeviceArray(x, "x", 2)
     n, p = dx.shape
     if ties not in TIES:
@@ -2799,6 +2822,127 @@ def op_cox_addscore_bench(x, cols, candidates=None, candidate_block=0, sorted_ro
                                              _ip(cols), cols.size, _ip(cand), q, int(candidate_block),
                                              1 if sorted_rows else 0, repeats, ms, ctypes.byref(nbytes)))
     return dict(zip(("pack", "cross", "quad", "quad_finish", "finish", "statistic"), [float(v) for v in ms])), nbytes.value
+
+
+def cox_groupscore_workspace(n, p, m, n_event_rows, group_starts, groups=None, candidate_block=0):
+    """What a cox_groupscore_device call on n rows (n_event_rows of them with status 1) and p columns with a support of m
+    columns needs and how it is split (bessx_cox_groupscore_workspace; no device is needed): groupscore_workspace's dict
+    ("doubles", "block_doubles", "rows_per_slab", "slabs", "gram_rows_per_slab", "gram_slabs", "blocks", "block_first",
+    "band", "depth", "score_depth", "gram_depth", "s_depth") plus "t_rows_per_slab", "t_slabs": the position split of
+    the risk-set term T, a function of n alone, and "t_depth": the roundings behind a term of an entry of T."""
+    gs, tg = _group_lists(group_starts, groups, p)
+    nt = gs.size if tg is None else tg.size
+    nd, bd, rps, sl, nb, first, band, dep = _ll(0), _ll(0), (_ll * 3)(), (_i * 3)(), _i(0), (_i * (nt + 1))(), _i(0), (_i * 5)()
+    _check(lib().bessx_cox_groupscore_workspace(int(n), int(p), int(m), int(n_event_rows), _ip(gs), gs.size, _ip(tg), nt,
+                                                int(candidate_block), ctypes.byref(nd), ctypes.byref(bd), rps, sl,
+                                                ctypes.byref(nb), first, ctypes.byref(band), dep))
+    return {"doubles": nd.value, "block_doubles": bd.value, "rows_per_slab": rps[0], "slabs": sl[0],
+            "gram_rows_per_slab": rps[1], "gram_slabs": sl[1], "t_rows_per_slab": rps[2], "t_slabs": sl[2],
+            "blocks": nb.value, "block_first": [int(first[k]) for k in range(nb.value + 1)], "band": band.value,
+            "depth": dep[0], "score_depth": dep[1], "gram_depth": dep[2], "s_depth": dep[3], "t_depth": dep[4]}
+
+
+def cox_groupscore_device(x, cols, beta, time, status, group_starts, groups=None, weight=None, ties="order", factor=None,
+                          stream=0, candidate_block=0):
+    """The ingredients of the Rao score test of every tested GROUP of columns against ONE Cox model on a device matrix x
+    (n x p: float64 or float32, any non-negative strides), read where it lies (bessx_cox_groupscore_device).  The model,
+    the positions, e, S0, v, g, info, score, loglik, n_events, residual_sum, factor and r are cox_addscore_device's;
+    group_starts, groups and candidate_block are groupscore_device's.  With P cox_addscore_device's panel (rows v_i x_i -
+    e_i A_pos(i)), cc_p = dh_p / S0_p and s_p = sum_{l >= p} e_l x_{l,J} over the positions in time order, for a tested
+    group with columns J, d = len(J) <= 64:
+        u = X_J^T g,   C = X_J^T P,   a = C r,   D = X_J^T diag(v) X_J,   T = sum_p cc_p s_p s_p^T,   S = (C R^T)(C R^T)^T
+    -- the rows J of the score and the block (D - T) - S of the observed information of the model extended by the group
+    at coefficient 0.  Returns groupscore_device's dict with "T" added and "loglik", "n_events", "residual_sum" in place
+    of "loss", "sum_w".  The subtractions, the d x d Cholesky factor and the quadratic form are
+    cox_group_score_test_table's; D - T loses digits for columns far from centred.  m = 0 is the test against the null
+    model (S = 0, a = 0).  factor None: cox_information_device and info_factor are called first (and when the information
+    is not positive definite, S and a are NaN).  The band of T is formed on the fp64 matrix cores from running suffix
+    sums with x read in place; no n x q temporary; scratch beyond the panel does not depend on p
+    (cox_groupscore_workspace).  The same call gives the same bits, and every layout of the same values of one dtype and
+    every candidate_block gives the same bits.  A tested group wider than 64 columns is BessxError code 3.  Not for Efron
+    ties or strata, not corrected for selection.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was
+    produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if ties not in TIES:
+        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: cox_groupscore_device takes one model per call")
+    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
+    if not np.isfinite(B).all():
+        raise ValueError("beta must be finite")
+    gs, tg = _group_lists(group_starts, groups, p)
+    nt = gs.size if tg is None else tg.size
+    lists = _group_columns(gs, tg, p)
+    ok = lists is not None and lists[1].max() <= GROUPSCORE_WIDTH_MAX  # (else the library refuses before it writes)
+    q, tot = (int(lists[1].sum()), int((lists[1] * lists[1]).sum())) if ok else (1, 1)
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, v in given:  # (every shape is checked before anything is copied)
+        _survival_vector(v, n, what, check_only=True)
+    host = {what: _survival_vector(v, n, what, stream) for what, v in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    m = cols.size
+    pd, fh = True, None
+    if m == 0:
+        pass
+    elif factor is None:
+        first = cox_information_device(x, cols, B, host["time"], host["status"], weight=host.get("weight"), ties=ties,
+                                       stream=stream)
+        fh, pd = info_factor(first["info"])
+    else:
+        fh = _f64(factor)
+        if fh.shape != (m, m):
+            raise ValueError("factor must have shape (%d, %d), got %s" % (m, m, fh.shape))
+    a = CoxGroupscoreInput()
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    a.ties, a.stream = TIES[ties], int(stream) if stream else None
+    if pd and m > 0:
+        a.factor, a.factor_ld = _dp(fh), m
+    a.group_starts, a.n_groups, a.groups, a.n_tested = _ip(gs), gs.size, _ip(tg), nt
+    a.candidate_block = int(candidate_block)
+    info, score = np.empty((m, m)), np.empty(m)
+    vec, blk, offsets = np.full((2, q), np.nan), np.full((3, tot), np.nan), np.zeros(nt + 1, dtype=np.int64)
+    a.info, a.info_ld, a.score = _dp(info), m, _dp(score)
+    a.u, a.a = vec[0].ctypes.data, vec[1].ctypes.data
+    a.D, a.T, a.S = blk[0].ctypes.data, blk[1].ctypes.data, blk[2].ctypes.data
+    a.offsets = offsets.ctypes.data_as(ctypes.POINTER(_ll))
+    a.out_on_device = 0
+    ll, ne, rs = _d(0), _d(0), _d(0)
+    _check(lib().bessx_cox_groupscore_device(ctypes.byref(a), ctypes.byref(ll), ctypes.byref(ne), ctypes.byref(rs)))
+    return {"columns": lists[2], "group_of_column": lists[3], "u": vec[0], "a": vec[1], "D": blk[0], "T": blk[1],
+            "S": blk[2], "offsets": offsets, "info": info, "score": score, "loglik": ll.value, "n_events": ne.value,
+            "residual_sum": rs.value, "positive_definite": bool(pd), "support": cols.astype(np.int64)}
+
+
+def cox_group_score_test_table(got):
+    """The Rao score test of every tested group from what cox_groupscore_device (or the NumPy route) returns, on the host
+    in fp64: group_score_test_table's operations and NaN rules with V = (D - T) - S and dispersion 1.  Returns its dict.
+    Selection is not corrected for."""
+    D, T = np.asarray(got["D"], dtype=np.float64), np.asarray(got["T"], dtype=np.float64)
+    S = np.asarray(got["S"], dtype=np.float64)
+    return _group_score_table(got, lambda lo, hi: (D[lo:hi] - T[lo:hi]) - S[lo:hi], 1.0)
+
+
+def op_cox_groupscore_bench(x, cols, group_starts, groups=None, candidate_block=0, sorted_rows=False, repeats=5):
+    """(ms per step, bytes the band of T needs) of the Cox group score test on the device matrix x for the support cols,
+    device events, each over every block of candidates: {"pack", "cross", "finish", "gram", "gram_sum", "s_band",
+    "extract", "t_band", "t_finish"} (bessx_op_cox_groupscore_bench).  sorted_rows: the rows are taken to be in time
+    order already; else a scattered order.  The bytes are the tested columns read once."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    gs, tg = _group_lists(group_starts, groups, dx.shape[1])
+    ms, nbytes = (_d * 9)(), _d(0)
+    _check(lib().bessx_op_cox_groupscore_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                               _ip(cols), cols.size, _ip(gs), gs.size, _ip(tg),
+                                               gs.size if tg is None else tg.size, int(candidate_block),
+                                               1 if sorted_rows else 0, repeats, ms, ctypes.byref(nbytes)))
+    names = ("pack", "cross", "finish", "gram", "gram_sum", "s_band", "extract", "t_band", "t_finish")
+    return dict(zip(names, [float(v) for v in ms])), nbytes.value
 
 
 COX_DIAG_KINDS = ("martingale", "deviance", "score", "dfbeta", "displacement", "schoenfeld")  # BESSX_COX_DIAG_* bits

@@ -4167,29 +4167,22 @@ void cox_addscore_doubles(long long n, int m, long long J, int q, int block, lon
   *blockpart = bp;
 }
 
-// sc, o, x, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
-int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vector<double> &pk, std::vector<double> &h,
-                     const bessx_cox_addscore_input *in, double *loglik, double *residual_sum, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
-  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, q = in->q, block = in->candidate_block;
-  const int ties = in->ties;
-  const long long rs = in->x_row_stride, cs = in->x_col_stride;
-  const size_t N = (size_t)n, mm = (size_t)m * (size_t)m, M = (size_t)m + 1, Q = (size_t)q;
-  const size_t nb = (size_t)((n + 1023) / 1024);
-  const bool with_stat = in->factor != nullptr && m > 0, want_c = in->cross != nullptr;
+// steps 1 to 3 that sections 2m and 2o share: info, score, loglik and residual_sum by section 2h's launches (queued into h:
+// loglik, residual_sum, then info and score), e, S0, v, g -- once more by rows where section 2h's predictor pass gathers
+// -- and A (null when m = 0).  c, *A_out and *ldA_out are the caller's to use; sc and h must outlive what is queued on st
+int cox_score_stage(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const void *xp, int f32, long long rs,
+                    long long cs, int n, const int *cols, int m, const double *beta, int ties, std::vector<double> &h,
+                    hipStream_t st, CoxInfoDev &c, double **A_out, long long *ldA_out) {
+  const size_t N = (size_t)n, mm = (size_t)m * (size_t)m, nb = (size_t)((n + 1023) / 1024);
   // 1. info, score, loglik and residual_sum: section 2h's launches as bessx_cox_info_device runs them (the same bits)
-  CoxInfoDev c;
-  if (int rc = cox_info_stage(sc, o, x, in->cols, m, in->beta, n, ties, st, &c)) return rc;
+  if (int rc = cox_info_stage(sc, o, x, cols, m, beta, n, ties, st, &c)) return rc;
   const CoxDev &d = c.d;
   HIPX(hipMemsetAsync(c.res, 0, 2 * sizeof(double), st));
   double *istage = nullptr, *res2 = nullptr;
   h.resize(2 + mm + 2 * (size_t)m);
   if (m > 0) {
     HIPX(sc.alloc(&istage, mm + (size_t)m));
-    if (int rc = cox_info_launch(in->x, f32, rs, cs, n, m, ties, c, istage, m, istage + mm, st)) return rc;
+    if (int rc = cox_info_launch(xp, f32, rs, cs, n, m, ties, c, istage, m, istage + mm, st)) return rc;
     HIPX(hipMemcpyAsync(h.data() + 2, istage, (mm + (size_t)m) * sizeof(double), hipMemcpyDeviceToHost, st));
   } else {
     // (section 2h stops after the likelihood at m = 0: the arrays behind v and g are this section's own)
@@ -4203,7 +4196,7 @@ int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::v
     HIPX(sc.alloc(&c.v, N));
     HIPX(sc.alloc(&c.g, N));
     HIPX(sc.alloc(&c.hs, (size_t)cox_surv_workspace(n)));
-    HIPX(launch_cox_eval_eta(in->x, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
+    HIPX(launch_cox_eval_eta(xp, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
     HIPX(hipMemcpyAsync(c.e, d.ex, N * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, c.res, st));
     HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, c.hs, nullptr, st));
@@ -4214,16 +4207,16 @@ int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::v
   // along rows: the same bits under every layout of x
   if (!cox_eval_eta_by_rows(rs, cs, m)) {
     HIPX(sc.alloc(&res2, 2));
-    HIPX(launch_cox_eval_eta_rows(in->x, f32, rs, cs, n, d.cols, m, d.B, d.zero, d.pos, d.eta, d.ex, st));
+    HIPX(launch_cox_eval_eta_rows(xp, f32, rs, cs, n, d.cols, m, d.B, d.zero, d.pos, d.eta, d.ex, st));
     HIPX(hipMemcpyAsync(c.e, d.ex, N * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, res2, st));
-    HIPX(launch_cox_info_gather(in->x, f32, rs, cs, n, d.cols, m, c.rowof, c.e, c.W, st));
+    HIPX(launch_cox_info_gather(xp, f32, rs, cs, n, d.cols, m, c.rowof, c.e, c.W, st));
     HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, c.hs, nullptr, st));
     HIPX(launch_cox_info_vg(c.e, d.eta, ties ? c.lastk : nullptr, d.wd, d.pos, n, c.v, c.g, st));
     if (c.J > 0) HIPX(launch_cox_info_means(c.W, d.ex, c.jptr, n, m, c.J, c.scr, c.U, c.ldU, st));
   }
-  // 3. A (section 2j's launches) and Cc
-  double *A = nullptr, *dh = nullptr, *scrA = nullptr, *Cc = nullptr, *scrC = nullptr;
+  // 3. A (section 2j's launches)
+  double *A = nullptr, *dh = nullptr, *scrA = nullptr;
   const long long ldA = cox_diag_lda(n);
   if (m > 0) {
     HIPX(sc.alloc(&A, (size_t)ldA * (size_t)m));
@@ -4232,6 +4225,31 @@ int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::v
     HIPX(launch_cox_diag_accum(c.U, c.ldU, c.jptr, d.wd, d.ex, d.first, ties ? c.lastk : nullptr, n, m, dh, scrA, A, ldA,
                                st));
   }
+  *A_out = A;
+  *ldA_out = ldA;
+  return 0;
+}
+
+// sc, o, x, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vector<double> &pk, std::vector<double> &h,
+                     const bessx_cox_addscore_input *in, double *loglik, double *residual_sum, hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, q = in->q, block = in->candidate_block;
+  const int ties = in->ties;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  const size_t N = (size_t)n, mm = (size_t)m * (size_t)m, M = (size_t)m + 1, Q = (size_t)q;
+  const size_t nb = (size_t)((n + 1023) / 1024);
+  const bool with_stat = in->factor != nullptr && m > 0, want_c = in->cross != nullptr;
+  // 1. to 3. info, score, loglik and residual_sum (the same bits as bessx_cox_info_device), e, v, g by rows, A
+  CoxInfoDev c;
+  double *A = nullptr;
+  long long ldA = 0;
+  if (int rc = cox_score_stage(sc, o, x, in->x, f32, rs, cs, n, in->cols, m, in->beta, ties, h, st, c, &A, &ldA)) return rc;
+  const CoxDev &d = c.d;
+  double *Cc = nullptr, *scrC = nullptr;
   HIPX(sc.alloc(&Cc, N));
   HIPX(sc.alloc(&scrC, nb));
   HIPX(launch_cox_addscore_cc(d.wd, d.ex, d.first, ties ? c.lastk : nullptr, n, scrC, Cc, st));
@@ -4934,6 +4952,381 @@ int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, lo
     HIPX(hipEventElapsedTime(&ms, e0, e1));
     stage_ms[stage] = ms / repeats;
   }
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// score tests of groups of candidate columns against one Cox model on a caller's device matrix (include/bessx.h section 2o)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the fields bessx_cox_groupscore_input shares with bessx_cox_info_input, as section 2h's helpers take them
+bessx_cox_info_input cox_groupscore_as_info(const bessx_cox_groupscore_input *in) {
+  bessx_cox_info_input a{};
+  a.x = in->x;
+  a.x_dtype = in->x_dtype;
+  a.x_row_stride = in->x_row_stride;
+  a.x_col_stride = in->x_col_stride;
+  a.n = in->n;
+  a.p = in->p;
+  a.cols = in->cols;
+  a.m = in->m;
+  a.beta = in->beta;
+  a.time = in->time;
+  a.status = in->status;
+  a.weight = in->weight;
+  a.ties = in->ties;
+  a.info = in->info;
+  a.info_ld = in->info_ld;
+  a.score = in->score;
+  a.out_on_device = 0;
+  a.stream = in->stream;
+  return a;
+}
+
+// everything about the call that needs no device
+int cox_groupscore_check_args(const char *who, const bessx_cox_groupscore_input *in, const double *loglik,
+                              const double *n_events, const double *residual_sum, GsPlan *pl) {
+  const std::string w(who);
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const bessx_cox_info_input a = cox_groupscore_as_info(in);
+  if (int rc = cox_info_check_args(who, &a, loglik, n_events, residual_sum)) return rc;
+  if (!in->u || !in->D || !in->T || !in->offsets) return fail(BESSX_ERR_ARG, w + ": null argument (u, D, T, offsets)");
+  if (in->factor && (!in->S || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (S, a)");
+  if (int rc = groupscore_plan(w, in->p, in->group_starts, in->n_groups, in->groups, in->n_tested, in->candidate_block, pl))
+    return rc;
+  if (in->factor && in->m > 0) {
+    if (in->factor_ld < (long long)in->m) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m");
+    for (long long j = 0; j < in->m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  return 0;
+}
+
+// doubles of device scratch of one call beyond section 2h's, and the part of them that does not depend on p
+void cox_groupscore_figures(long long n, int m, long long J, const GsPlan &pl, long long *all, long long *blockpart) {
+  const long long nb = (n + 1023) / 1024, M = (long long)m + 1;
+  long long panel = 0, blk = 0, rps = 0, work_as = 0, rpsx = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsx = 0, chain = 0;
+  addscore_split(n, m, pl.qmax, pl.block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  groupscore_cross_figures(n, m, pl, &work_as, &rpsx, &slabsx, &chain);
+  long long d = cox_info_doubles(n, m, J) + (long long)m * m + m + 2;
+  if (m == 0) d += 3 * n + cox_surv_workspace(n);  // e, v, g and the totals of H's scan, which section 2h skips at m = 0
+  if (m > 0) d += cox_diag_lda(n) * m + n + nb * m;  // A, dh, A's totals
+  long long bp = work_as + groupscore_doubles(n, m, pl.qmax, pl.band) + (pl.qmax + 15) / 16 * 16 +
+                 cox_groupscore_doubles(n, pl.qmax, pl.band);
+  if (m > 0) {  // the score behind r: the support as candidates
+    long long panel0 = 0, blk0 = 0, rps0 = 0;
+    int slabs0 = 0, cb0 = 0, depth0 = 0;
+    addscore_split(n, m, m, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+    bp += blk0 + 2 * M;
+  }
+  *all = d + n + panel + bp;  // cc, the panel, the block workspaces
+  *blockpart = bp;
+}
+
+// the device arrays of the risk-set term
+struct CgsDev {
+  int *rowof;
+  double *e, *cc, *work;
+};
+
+// the band of T of every block and its groups' blocks.  stage: 0 = both kernels and the extraction, 1 = k_cgs_band, 2 =
+// k_cgs_finish and the extraction (bessx_op_cox_groupscore_bench)
+int cox_groupscore_tblocks(const GsPlan &pl, const GsDev &d, const CgsDev &t, double *T, int stage, hipStream_t st) {
+  for (int b = 0; b < pl.blocks; b++) {
+    const int g0 = pl.first[(size_t)b], g1 = pl.first[(size_t)b + 1], j0 = pl.lpos[(size_t)g0], qb = pl.lpos[(size_t)g1] - j0;
+    double *bandT = nullptr;
+    HIPX(launch_cox_groupscore_tband(d.x, d.f32, d.rs, d.cs, d.n, d.cand + j0, qb, pl.band, t.rowof, t.e, t.cc, t.work, stage,
+                                     &bandT, st));
+    if (stage == 0 || stage == 2) HIPX(launch_groupscore_extract(bandT, pl.band, d.lpos, d.offs, g0, g1 - g0, T, st));
+  }
+  return 0;
+}
+
+// sc, o, x, pl, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
+int cox_groupscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const GsPlan &pl, std::vector<double> &pk,
+                       std::vector<double> &h, const bessx_cox_groupscore_input *in, double *loglik, double *residual_sum,
+                       hipStream_t st) {
+  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
+  HIPX(sc.event(&ev, hipEventDisableTiming));
+  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
+  HIPX(hipStreamWaitEvent(st, ev, 0));
+  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, ties = in->ties;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  const size_t N = (size_t)n, mm = (size_t)m * (size_t)m, M = (size_t)m + 1, Q = (size_t)pl.q,
+               TOT = (size_t)pl.offs[(size_t)pl.nt];
+  const bool with_s = in->factor != nullptr && m > 0;
+  // 1. to 3. info, score, loglik and residual_sum (the same bits as bessx_cox_info_device), e, v, g by rows, A: section
+  // 2m's steps; then cc
+  CoxInfoDev c;
+  double *A = nullptr;
+  long long ldA = 0;
+  if (int rc = cox_score_stage(sc, o, x, in->x, f32, rs, cs, n, in->cols, m, in->beta, ties, h, st, c, &A, &ldA)) return rc;
+  const CoxDev &cd = c.d;
+  CgsDev t{};
+  t.rowof = c.rowof, t.e = c.e;
+  HIPX(sc.alloc(&t.cc, N));
+  HIPX(launch_cox_groupscore_cc(cd.wd, cd.ex, cd.first, ties ? c.lastk : nullptr, n, t.cc, st));
+  // 4. section 2m's panel and section 2n's block workspaces
+  long long panel = 0, blk = 0, rps = 0, work_as = 0, rpsx = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsx = 0, chain = 0;
+  addscore_split(n, m, pl.qmax, pl.block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  groupscore_cross_figures(n, m, pl, &work_as, &rpsx, &slabsx, &chain);
+  const long long work_gs = groupscore_doubles(n, m, pl.qmax, pl.band);
+  GsDev d{};
+  d.x = in->x, d.f32 = f32, d.rs = rs, d.cs = cs, d.n = n, d.m = m, d.v = c.v;
+  double *ostage = nullptr;
+  HIPX(sc.alloc(&d.P, (size_t)panel));
+  HIPX(sc.alloc(&d.work_as, (size_t)work_as));
+  HIPX(sc.alloc(&d.work_gs, (size_t)work_gs));
+  HIPX(sc.alloc(&d.dd, (size_t)(pl.qmax + 15) / 16 * 16));
+  HIPX(sc.alloc(&t.work, (size_t)cox_groupscore_doubles(n, pl.qmax, pl.band)));
+  if (int rc = groupscore_upload_plan(sc, pl, st, &d)) return rc;
+  HIPX(launch_cox_addscore_pack(in->x, f32, rs, cs, n, cd.cols, m, pl.qmax, pl.block, c.v, c.g, c.e, cd.pos, A, ldA, d.P, st));
+  // the score behind r, summed by section 2l's kernels over the support as candidates (section 2m's step)
+  if (with_s) {
+    long long panel0 = 0, blk0 = 0, rps0 = 0;
+    int slabs0 = 0, cb0 = 0, depth0 = 0;
+    double *work0 = nullptr, *u0 = nullptr;
+    addscore_split(n, m, m, 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+    HIPX(sc.alloc(&work0, (size_t)blk0));
+    HIPX(sc.alloc(&u0, 2 * M));
+    HIPX(launch_addscore_blocks(in->x, f32, rs, cs, n, m, cd.cols, m, 0, d.P, work0, 0, u0, u0 + M, nullptr, nullptr, nullptr,
+                                0, 0, st));
+    HIPX(hipMemcpyAsync(h.data() + 2 + mm + (size_t)m, u0, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  *loglik = h[0];
+  *residual_sum = h[1];
+  for (size_t j = 0; j < (size_t)m; j++)
+    std::copy(h.begin() + 2 + j * m, h.begin() + 2 + (j + 1) * m, in->info + j * in->info_ld);
+  if (m > 0) std::copy(h.begin() + 2 + mm, h.begin() + 2 + mm + (size_t)m, in->score);
+  if (with_s) {
+    // r = inverse(info) U = R^T (R U) on the host in fp64; the factor gets section 2m's zero row and column in front
+    const double *U0 = h.data() + 2 + mm + (size_t)m;
+    std::vector<double> tt((size_t)m, 0.0), Rx(M * M, 0.0), rx(M, 0.0);
+    for (size_t j = 0; j < (size_t)m; j++)
+      for (size_t k = 0; k <= j; k++) {
+        const double f = in->factor[j * in->factor_ld + k];
+        tt[j] += f * U0[k];
+        Rx[(j + 1) * M + k + 1] = f;
+      }
+    for (size_t j = 0; j < (size_t)m; j++)
+      for (size_t k = 0; k <= j; k++) rx[k + 1] += in->factor[j * in->factor_ld + k] * tt[j];
+    pk.resize((size_t)diag_factor_doubles(m + 1));
+    addscore_pack_factor(Rx.data(), (long long)M, rx.data(), m, pk.data());
+    HIPX(hipMemcpyAsync(d.work_gs + work_gs - (long long)pk.size(), pk.data(), pk.size() * sizeof(double),
+                        hipMemcpyHostToDevice, st));
+  }
+  // 5. u, C, D, S, a by sections 2l's and 2n's kernels; T by this section's
+  double *u = in->u, *a = in->a, *D = in->D, *T = in->T, *S = in->S;
+  if (!in->out_on_device) {
+    HIPX(sc.alloc(&ostage, 2 * Q + 3 * TOT));
+    u = ostage, a = ostage + Q, D = ostage + 2 * Q, T = D + TOT, S = T + TOT;
+  }
+  if (int rc = groupscore_blocks(pl, d, with_s ? 1 : 0, u, a, D, S, 0, st)) return rc;
+  if (int rc = cox_groupscore_tblocks(pl, d, t, T, 0, st)) return rc;
+  const bool zero_sa = m == 0 && S && a;  // (the null model: nothing is explained by a support)
+  if (zero_sa) {
+    HIPX(hipMemsetAsync(S, 0, TOT * sizeof(double), st));
+    HIPX(hipMemsetAsync(a, 0, Q * sizeof(double), st));
+  }
+  if (!in->out_on_device) {
+    h.resize(2 * Q + 3 * TOT);
+    HIPX(hipMemcpyAsync(h.data(), ostage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPX(hipStreamSynchronize(st));
+  if (!in->out_on_device) {
+    std::copy(h.begin(), h.begin() + Q, in->u);
+    std::copy(h.begin() + 2 * Q, h.begin() + 2 * Q + TOT, in->D);
+    std::copy(h.begin() + 2 * Q + TOT, h.begin() + 2 * Q + 2 * TOT, in->T);
+    if ((with_s || m == 0) && in->S && in->a) {
+      std::copy(h.begin() + Q, h.begin() + 2 * Q, in->a);
+      std::copy(h.begin() + 2 * Q + 2 * TOT, h.begin() + 2 * Q + 3 * TOT, in->S);
+    }
+  }
+  std::copy(pl.offs.begin(), pl.offs.end(), in->offsets);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_groupscore_workspace(int n, int p, int m, int n_event_rows, const int *group_starts, int n_groups,
+                                   const int *groups, int n_tested, int candidate_block, long long *doubles,
+                                   long long *block_doubles, long long *rows_per_slab, int *slabs, int *n_blocks,
+                                   int *block_first, int *band, int *depth) {
+  if (!doubles || !block_doubles || !rows_per_slab || !slabs || !n_blocks || !band || !depth)
+    return fail(BESSX_ERR_ARG, "cox_groupscore_workspace: null argument");
+  if (n < 1 || p < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_groupscore_workspace: empty matrix");
+  if (n_event_rows < 0 || n_event_rows > n)
+    return fail(BESSX_ERR_ARG, "cox_groupscore_workspace: n_event_rows must lie in [0, n]");
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "cox_groupscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  GsPlan pl;
+  if (int rc = groupscore_plan("cox_groupscore_workspace", p, group_starts, n_groups, groups, n_tested, candidate_block,
+                               &pl))
+    return rc;
+  long long work_as = 0;
+  groupscore_cross_figures(n, m, pl, &work_as, &rows_per_slab[0], &slabs[0], &depth[0]);
+  groupscore_rows(n, &rows_per_slab[1], &slabs[1]);
+  cox_groupscore_rows(n, &rows_per_slab[2], &slabs[2], &depth[4]);
+  long long panel0 = 0, blk0 = 0, rps0 = 0;
+  int slabs0 = 0, cb0 = 0, depth0 = 0;
+  addscore_split(n, m, std::max(m, 1), 0, &panel0, &blk0, &rps0, &slabs0, &cb0, &depth0);
+  depth[1] = (int)std::min<long long>(0x7fffffffLL, rps0 + (slabs0 + 15) / 16 + 4);
+  depth[2] = (int)std::min<long long>(0x7fffffffLL, rows_per_slab[1] + slabs[1]);
+  depth[3] = 16 * ((m + 2 + 15) / 16);
+  cox_groupscore_figures(n, m, n_event_rows, pl, doubles, block_doubles);
+  *n_blocks = pl.blocks;
+  *band = pl.band;
+  if (block_first) std::copy(pl.first.begin(), pl.first.end(), block_first);
+  return BESSX_OK;
+}
+
+int bessx_cox_groupscore_device(const bessx_cox_groupscore_input *in, double *loglik, double *n_events,
+                                double *residual_sum) {
+  GsPlan pl;
+  if (int rc = cox_groupscore_check_args("cox_groupscore_device", in, loglik, n_events, residual_sum, &pl)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1, od = -1;
+  if (int rc = check_device_matrix("cox_groupscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
+                                   in->n, in->p, &dev))
+    return rc;
+  if (in->out_on_device) {
+    const long long tot = pl.offs[(size_t)pl.nt];
+    const bool sa = in->factor || in->m == 0;
+    double *const vec[5] = {in->u, sa ? in->a : nullptr, in->D, in->T, sa ? in->S : nullptr};
+    const long long len[5] = {pl.q, pl.q, tot, tot, tot};
+    for (int k = 0; k < 5; k++) {
+      if (!vec[k]) continue;
+      if (len[k] > 0x7fffffffLL)
+        return fail(BESSX_ERR_ARG, "cox_groupscore_device: too many block entries for device output");
+      if (int rc = check_device_matrix("cox_groupscore_device: u, a, D, T, S", vec[k], BESSX_F64, 1, 0, (int)len[k], 1, &od))
+        return rc;
+      if (od != dev) return fail(BESSX_ERR_ARG, "cox_groupscore_device: an output is not on the device that owns x");
+    }
+  }
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  CoxInfoOrder x;
+  cox_info_order(&o, in->n, in->m, in->ties, &x);
+  HIPX(hipSetDevice(dev));
+  hipStream_t st = nullptr;
+  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc;
+  {
+    Owner sc;
+    std::vector<double> pk, h;
+    rc = cox_groupscore_run(sc, o, x, pl, pk, h, in, loglik, residual_sum, st);
+    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
+  }
+  (void)hipStreamDestroy(st);
+  if (!rc) *n_events = x.n_events;
+  return rc;
+}
+
+int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                                  const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
+                                  int n_tested, int candidate_block, int sorted, int repeats, double *stage_ms,
+                                  double *bytes) {
+  if (!x || repeats < 1 || !stage_ms || !bytes) return fail(BESSX_ERR_ARG, "op_cox_groupscore_bench: bad arguments");
+  if (int rc = predict_check_model("op_cox_groupscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (m + 1 > INFO_M_MAX)
+    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_groupscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  GsPlan pl;
+  if (int rc = groupscore_plan("op_cox_groupscore_bench", p, group_starts, n_groups, groups, n_tested, candidate_block, &pl))
+    return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_groupscore_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t M = (size_t)m + 1, Q = (size_t)pl.q, TOT = (size_t)pl.offs[(size_t)pl.nt], N = (size_t)n;
+  long long panel = 0, blk = 0, rps = 0, work_as = 0, rpsx = 0;
+  int slabs = 0, cb = 0, depth = 0, slabsx = 0, chain = 0;
+  addscore_split(n, m, pl.qmax, pl.block, &panel, &blk, &rps, &slabs, &cb, &depth);
+  groupscore_cross_figures(n, m, pl, &work_as, &rpsx, &slabsx, &chain);
+  const long long work_gs = groupscore_doubles(n, m, pl.qmax, pl.band);
+  // n-vectors, an A and a factor of the library's own, as bessx_op_cox_addscore_bench has them (cc is its Cc's increment)
+  const long long ldA = cox_diag_lda(n);
+  std::vector<double> v(N, 0.25), g(N), e(N), cc(N, 1.0 / ((double)n * (double)n)), Ah((size_t)ldA * (size_t)m, 1.0 / 64.0),
+      R(M * M, 0.0), r(M, 1.0 / 128.0), pk((size_t)diag_factor_doubles(m + 1));
+  std::vector<int> pos(N), rowof(N);
+  for (size_t i = 0; i < N; i++) {
+    g[i] = (i % 2) ? -0.5 : 0.5;
+    e[i] = 1.0 + (double)(i % 7) / 8.0;
+    pos[i] = sorted ? (int)i : (int)(((long long)i * 7919) % n);
+    rowof[i] = pos[i];
+  }
+  for (size_t j = 1; j < M; j++)
+    for (size_t k = 1; k <= j; k++) R[j * M + k] = (j == k ? 1.0 : 1.0 / 64.0) / std::sqrt((double)n);
+  r[0] = 0.0;
+  addscore_pack_factor(R.data(), (long long)M, r.data(), m, pk.data());
+  int *cols_d = nullptr, *pos_d = nullptr;
+  double *g_d = nullptr, *A_d = nullptr, *out = nullptr;
+  GsDev d{};
+  CgsDev t{};
+  d.x = x, d.f32 = dtype == BESSX_F32, d.rs = row_stride, d.cs = col_stride, d.n = n, d.m = m;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&pos_d, N));
+  HIPX(sc.alloc(&t.rowof, N));
+  HIPX(sc.alloc(&d.v, N));
+  HIPX(sc.alloc(&g_d, N));
+  HIPX(sc.alloc(&t.e, N));
+  HIPX(sc.alloc(&t.cc, N));
+  HIPX(sc.alloc(&A_d, Ah.size()));
+  HIPX(sc.alloc(&d.P, (size_t)panel));
+  HIPX(sc.alloc(&d.work_as, (size_t)work_as));
+  HIPX(sc.alloc(&d.work_gs, (size_t)work_gs));
+  HIPX(sc.alloc(&d.dd, (size_t)(pl.qmax + 15) / 16 * 16));
+  HIPX(sc.alloc(&t.work, (size_t)cox_groupscore_doubles(n, pl.qmax, pl.band)));
+  HIPX(sc.alloc(&out, 2 * Q + 3 * TOT));
+  if (int rc = groupscore_upload_plan(sc, pl, nullptr, &d)) return rc;
+  if (m > 0) {
+    HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+    HIPX(hipMemcpy(A_d, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIPX(hipMemcpy(pos_d, pos.data(), N * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(t.rowof, rowof.data(), N * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(d.v, v.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(g_d, g.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(t.e, e.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(t.cc, cc.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(d.work_gs + work_gs - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  auto run = [&](int stage) -> int {
+    if (stage == 0) {
+      HIPX(launch_cox_addscore_pack(x, d.f32, row_stride, col_stride, n, cols_d, m, pl.qmax, pl.block, d.v, g_d, t.e, pos_d,
+                                    m > 0 ? A_d : nullptr, ldA, d.P, nullptr));
+      return 0;
+    }
+    if (stage >= 7) return cox_groupscore_tblocks(pl, d, t, out + 2 * Q + TOT, stage - 6, nullptr);
+    return groupscore_blocks(pl, d, m > 0 ? 1 : 0, out, out + Q, out + 2 * Q, out + 2 * Q + 2 * TOT, stage, nullptr);
+  };
+  // (stage 0 = pack, then groupscore_blocks' steps 1 .. 6, then the band of T and its finish with the extraction, each
+  // over every block, in an order in which a later stage finds the earlier one's results of the last block)
+  for (int stage = 0; stage < 9; stage++) {
+    if (int rc = run(stage)) return rc;  // the warm-up
+    HIPX(hipEventRecord(e0, nullptr));
+    for (int i = 0; i < repeats; i++)
+      if (int rc = run(stage)) return rc;
+    HIPX(hipEventRecord(e1, nullptr));
+    HIPX(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    stage_ms[stage] = ms / repeats;
+  }
+  *bytes = (double)n * (double)pl.q * (dtype == BESSX_F32 ? 4.0 : 8.0);
   return BESSX_OK;
 }
 

@@ -273,6 +273,19 @@ hipError_t launch_groupscore_sband(const double *Cb, int m, int qb, int band, co
                                    double *a, hipStream_t st);
 hipError_t launch_groupscore_extract(const double *bandT, int band, const int *lpos, const long long *offs, int g0, int ng,
                                      double *out, hipStream_t st);
+// score tests of groups of candidate columns against one Cox model (bessx_k_coxgroupscore.hip), on top of the launchers
+// of bessx_k_coxaddscore.hip and bessx_k_groupscore.hip: the band of the risk-set term T = sum_p cc_p s_p s_p^T, s_p =
+// sum_{l >= p} e_l x_l, cc_p = dh_p / S0(p).  _rows: the position split, a function of n alone, and the longest chain of
+// roundings behind an entry of T.  _doubles: the workspace for blocks of at most qmax columns.  _cc: cc (not scanned).
+// _tband: the band of one block in k_gs_extract's tile layout (only = 1 / 2 launches one of its two kernels alone; *bandT
+// = where the band lies inside work).  band + 1 <= 5.  Device memory.
+void cox_groupscore_rows(long long n, long long *rows_per_slab, int *slabs, int *t_depth);
+long long cox_groupscore_doubles(long long n, int qmax, int band);
+hipError_t launch_cox_groupscore_cc(const double *wd, const double *S0, const int *first, const int *lastk, long long n,
+                                    double *cc, hipStream_t st);
+hipError_t launch_cox_groupscore_tband(const void *src, int f32, long long rs, long long cs, long long n, const int *cand,
+                                       int qb, int band, const int *rowof, const double *e, const double *cc, double *work,
+                                       int only, double **bandT, hipStream_t st);
 // k_y_prepare for R responses (columns of Y, stride ld, rows n..ld zero) in one launch, plus y.y of each
 hipError_t launch_y_prepare_multi(double *Y, int n, long ld, int R, const double *w, int data_type, int is_normal,
                                   int add_weight, double *y_mean, double *yy, hipStream_t st);

@@ -833,7 +833,7 @@ class bess_base:
         and y and weight may be device arrays too; a NumPy X is served in fp64 NumPy with the same definitions.  When
         the information is not positive definite statistic and p_value are NaN and nothing is raised.  For Lm,
         statistic * dispersion is the drop in the residual sum of squares on adding the whole group.  Selection is not
-        corrected for.  Cox: None.  A 2-D beta (Lm fitted to several responses) raises ValueError."""
+        corrected for.  Cox: None (score_tests_groups_survival).  A 2-D beta (Lm fitted to several responses) raises ValueError."""
         on_device = capi.is_device_array(X)
         shape = capi._DeviceArray(X, "X", 2).shape if on_device else np.shape(X)
         if len(shape) != 2 or shape[1] != self.p:
@@ -1094,11 +1094,10 @@ class bess_base:
 
     # ---- Cox: score tests of the columns left out ----------------------------------------------------------------------
     @staticmethod
-    def _cox_score_tests_host(X, cols, beta, time, status, w, ties, cand):
-        """cox_addscore_device's quantities in fp64 NumPy, by the same decomposition (running sums; no risk-set mean of a
-        candidate): X (n, p), cols the support, beta (m,), time, status, w (n,) in row order, cand the candidate columns
-        (int64) or None = all.  With a = e x_j and Cc the running sum of dh / S0, t_j = sum_l a_l (a_l Cc_l + 2 P_l), P
-        the exclusive running sum of Cc a."""
+    def _cox_score_terms(X, cols, beta, time, status, w, ties):
+        """What the Cox score tests share, in fp64 NumPy by cox_addscore_device's decomposition: (got, order, e, v, g, cc,
+        P) with got = _cox_information_host's dict, order the rows in time order, e, v, g in position order, cc = dh / S0
+        per position and P the panel's support columns v x - e A (n, m)."""
         n, p = X.shape
         m = cols.size
         got = bess_base._cox_information_host(X[:, cols], beta, time, status, w, ties)
@@ -1128,7 +1127,7 @@ class bess_base:
             dh = h
         v = e * H
         g = wd - v
-        Cc = np.cumsum(dh / S0)
+        cc = dh / S0
         xs = X[order][:, cols]
         if m > 0:
             u = np.cumsum((e[:, None] * xs)[::-1], axis=0)[::-1][r] / S0[:, None]
@@ -1136,6 +1135,18 @@ class bess_base:
             P = v[:, None] * xs - e[:, None] * A
         else:
             P = np.zeros((n, 0))
+        return got, order, e, v, g, cc, P
+
+    @staticmethod
+    def _cox_score_tests_host(X, cols, beta, time, status, w, ties, cand):
+        """cox_addscore_device's quantities in fp64 NumPy, by the same decomposition (running sums; no risk-set mean of a
+        candidate): X (n, p), cols the support, beta (m,), time, status, w (n,) in row order, cand the candidate columns
+        (int64) or None = all.  With a = e x_j and Cc the running sum of dh / S0, t_j = sum_l a_l (a_l Cc_l + 2 P_l), P
+        the exclusive running sum of Cc a."""
+        n, p = X.shape
+        m = cols.size
+        got, order, e, v, g, cc, P = bess_base._cox_score_terms(X, cols, beta, time, status, w, ties)
+        Cc = np.cumsum(cc)
         columns = np.arange(p, dtype=np.int64) if cand is None else np.asarray(cand, dtype=np.int64)
         q = columns.size
         uu, dd, tt, C = np.empty(q), np.empty(q), np.empty(q), np.empty((q, m))
@@ -1197,6 +1208,103 @@ class bess_base:
             got = self._cox_score_tests_host(np.asarray(X, dtype=np.float64), cols, beta[cols], time, status, w, ties,
                                              cand)
         out = capi.cox_score_test_table(got)
+        out.update(cols=cols, loglik=float(got["loglik"]), positive_definite=bool(got["positive_definite"]))
+        return out
+
+    # ---- Cox: score tests of the groups left out -----------------------------------------------------------------------
+    @staticmethod
+    def _cox_score_tests_groups_host(X, cols, beta, time, status, w, ties, starts, groups):
+        """cox_groupscore_device's quantities in fp64 NumPy with the same decomposition: X (n, p), cols the support, beta
+        (m,), time, status, w (n,) in row order, starts the groups' start columns, groups the tested group numbers or None
+        = all.  u, C, D, S, a are matrix products over the n rows as in _score_tests_groups_host; T = sum_p cc_p s_p s_p^T
+        from the suffix sums s of e x_J of a block.  The tested columns go in blocks of at most 2 048 that hold whole
+        groups: no X-sized temporary."""
+        n, p = X.shape
+        m = cols.size
+        got, order, e, v, g, cc, P = bess_base._cox_score_terms(X, cols, beta, time, status, w, ties)
+        lists = capi._group_columns(np.asarray(starts, dtype=np.int32), None if groups is None else
+                                    np.asarray(groups, dtype=np.int32), p)
+        if lists is None:
+            raise ValueError("groups must be ascending distinct group numbers")
+        tested, width, columns, goc = lists
+        q, nt = columns.size, tested.size
+        pos = np.concatenate([[0], np.cumsum(width)])
+        offsets = np.concatenate([[0], np.cumsum(width * width)]).astype(np.int64)
+        tot = int(offsets[-1])
+        pd = True
+        if m == 0:
+            a, S = np.zeros(q), np.zeros(tot)
+        else:
+            R, pd = capi.info_factor(got["info"])
+            a, S = np.full(q, np.nan), np.full(tot, np.nan)
+            if pd:
+                r, Rl = R.T @ (R @ got["score"]), np.tril(R)
+        u, D, T = np.empty(q), np.empty(tot), np.empty(tot)
+        t0 = 0
+        while t0 < nt:  # (a block: whole groups, at most 2 048 columns unless one group alone is wider)
+            t1 = t0 + 1
+            while t1 < nt and pos[t1 + 1] - pos[t0] <= 2048:
+                t1 += 1
+            j0, j1 = int(pos[t0]), int(pos[t1])
+            XJ = X[:, columns[j0:j1]][order]
+            u[j0:j1] = XJ.T @ g
+            VX = v[:, None] * XJ
+            sfx = np.cumsum((e[:, None] * XJ)[::-1], axis=0)[::-1]
+            CS = cc[:, None] * sfx
+            if m > 0 and pd:
+                C = XJ.T @ P
+                a[j0:j1] = C @ r
+                TC = C @ Rl.T
+            for t in range(t0, t1):
+                k0, k1 = int(pos[t]) - j0, int(pos[t + 1]) - j0
+                for out, blk in ((D, XJ[:, k0:k1].T @ VX[:, k0:k1]), (T, sfx[:, k0:k1].T @ CS[:, k0:k1])):
+                    up = np.triu(blk)
+                    out[offsets[t]:offsets[t + 1]] = (up + np.triu(up, 1).T).reshape(-1)
+                if m > 0 and pd:
+                    Sg = np.triu(TC[k0:k1] @ TC[k0:k1].T)
+                    S[offsets[t]:offsets[t + 1]] = (Sg + np.triu(Sg, 1).T).reshape(-1)
+            t0 = t1
+        out = dict(got)
+        out.update(columns=columns, group_of_column=goc, u=u, a=a, D=D, T=T, S=S, offsets=offsets,
+                   positive_definite=bool(pd), support=np.asarray(cols, dtype=np.int64))
+        return out
+
+    def score_tests_groups_survival(self, X, y, group, weight=None, ties="order", groups=None):
+        """Cox only: did the selection leave out a GROUP that matters?  The Rao score test of every group of columns --
+        the units fit(..., group=...) selects -- against the fitted model on the rows (X, y), d degrees of freedom for a
+        group of d columns, without refitting anything: capi.cox_group_score_test_table's dict -- group, first_column,
+        df, score (the adjusted score vector u - a of each group), statistic = score^T inverse((D - T) - S) score,
+        p_value (chi-square, df degrees of freedom), in_model, dispersion = 1 -- plus cols, the model's support, loglik
+        and positive_definite.  y: (n, 2) time and status as in fit; weight: n values or None; ties: "order" (the risk
+        sets of the fit) or "breslow"; group and groups as in score_tests_groups.  (D - T) - S is the Schur complement of
+        the observed information of the partial likelihood of the model extended by the group at coefficient 0
+        (capi.cox_groupscore_device states the sums).  A group with a column in the support has in_model = True and NaN
+        for statistic and p_value; a group whose (D - T) - S is not positive definite, or an information that is not
+        positive definite, gives NaN and nothing is raised.  An X in GPU memory is read in place on torch's current
+        stream (a tested group may have at most 64 columns), with no n x p temporary (y and weight may be device arrays:
+        n values each are copied to the host); a NumPy X is served in fp64 NumPy with the same definitions.  Columns far
+        from centred lose digits in D - T (inference_survival's caveat).  Selection is not corrected for.
+        score_tests_groups() and score_tests() stay None for the Cox classes."""
+        if self.model_type_int != 4:
+            raise ValueError("score_tests_groups_survival is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        self._survival_x(X)
+        starts = self._group_runs(group, self.p)
+        _, tg = capi._group_lists(starts, groups, self.p)
+        if tg is not None and (tg.min() < 0 or tg.max() >= starts.size or (np.diff(tg) <= 0).any()):
+            raise ValueError("groups must be ascending distinct group numbers (0 .. %d)" % (starts.size - 1))
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.cox_groupscore_device(X, cols, beta[cols], time, status, starts, groups=tg,
+                                             weight=None if weight is None else w, ties=ties, stream=_current_stream(X))
+        else:
+            got = self._cox_score_tests_groups_host(np.asarray(X, dtype=np.float64), cols, beta[cols], time, status, w,
+                                                    ties, starts, tg)
+        out = capi.cox_group_score_test_table(got)
         out.update(cols=cols, loglik=float(got["loglik"]), positive_definite=bool(got["positive_definite"]))
         return out
 

@@ -892,8 +892,8 @@ int bessx_addscore_workspace(int n, int m, int q, int candidate_block, long long
  *     behind an entry of u, c, d (rows_per_slab[0] + ceil(slabs[0] / 16) + 4) and chain[1] behind a t_j.
  *     m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED; q >= 1; n <= 2^31 - 1.  Every argument error is found before any
  *     device call (BESSX_ERR_ARG: the messages of sections 2e / 2h / 2l).  Scratch memory is released before the call
- *     returns.  Out of scope: Efron ties, strata, tests of groups with more than one degree of freedom, any correction
- *     for selection.
+ *     returns.  Tests of groups of columns with more than one degree of freedom: section 2o.  Out of scope: Efron ties,
+ *     strata, any correction for selection.
  * ------------------------------------------------------------------------------------- */
 typedef struct {
   const void *x;
@@ -975,7 +975,8 @@ int bessx_cox_addscore_workspace(int n, int m, int n_event_rows, int q, int cand
  *     n <= 2^31 - 1.  Every argument error is found before any device call (BESSX_ERR_ARG: the messages of sections 2d /
  *     2g / 2i / 2l; group_starts not ascending from 0 or not columns of x; groups not ascending and distinct or out of
  *     range; a candidate_block that is not a multiple of 16 or is below the widest tested group rounded up to 16).
- *     Scratch memory is released before the call returns.  Out of scope: Cox models, any correction for selection.
+ *     Scratch memory is released before the call returns.  Cox models: section 2o.  Out of scope: any correction for
+ *     selection.
  * ------------------------------------------------------------------------------------- */
 typedef struct {
   const void *x;
@@ -1018,6 +1019,85 @@ int bessx_groupscore_workspace(int n, int p, int m, const int *group_starts, int
                                int n_tested, int candidate_block, long long *doubles, long long *block_doubles,
                                long long *rows_per_slab, int *slabs, int *n_blocks, int *block_first, int *band,
                                int *depth);
+/* ---------------------------------------------------------------------------------------
+ * 2o. Rao score tests of GROUPS of candidate columns against ONE Cox model on an X already in GPU memory
+ *     (bessx_k_coxgroupscore.hip): section 2n's question for the model of section 2h.  Stateless like sections 2c to 2n.
+ *     x, n, p, cols, m, beta, time, status, weight, ties, stream, info, info_ld, score, loglik, n_events, residual_sum,
+ *     factor = R (m x m, HOST memory), r, the positions l, e, S0, v, g, dh, A: section 2m; group_starts, n_groups, groups,
+ *     n_tested, candidate_block, offsets, out_on_device and the layout of u, a and of the blocks: section 2n.  With
+ *     cc_p = dh_p / S0(p) and s_p = sum_{l >= p} e_l x_{l,J} (positions in time order), for a tested group with columns J,
+ *     d = |J| -- the rows J of the score and the block of the observed information of the model extended by the group at
+ *     coefficient 0:
+ *         u_g = X_J^T g                        raw score, d values
+ *         C_g = X_J^T P                        cross information with the support, d x (m + 1) (not returned); P = section
+ *                                              2m's panel, rows (v_i, v_i x_i - e_i A_pos(i))
+ *         a_g = C_g r                          shift of the score, d values
+ *         D_g = X_J^T diag(v) X_J              first curvature term, d x d; its diagonal is section 2m's d_j
+ *         T_g = sum_p cc_p s_p s_p^T           risk-set term, d x d; its diagonal is section 2m's t_j
+ *         S_g = (C_g R^T) (C_g R^T)^T          curvature explained by the support, d x d; its diagonal is section 2m's s_j
+ *     The information's block is (D_g - T_g) - S_g and the score statistic (u_g - a_g)^T inverse((D_g - T_g) - S_g) (u_g -
+ *     a_g), chi-square with d degrees of freedom, dispersion 1: the subtractions, which can cancel (D - T loses digits
+ *     for columns far from centred, section 2h's caveat), the Cholesky factor and the quadratic form are left to the
+ *     caller's fp64 host code.  factor null: S and a are not formed (and may be null).  m = 0 is the test against the null
+ *     model: S = 0, a = 0 and the factor is not read.
+ *     Steps: sections 2h's, 2j's and 2m's launches for info, score, loglik, e, S0, v, g, A and the panel, unchanged;
+ *     section 2n's launches for u, the rows of C, the band of D (v in row order), T_C = C Rx^T with section 2m's zero row
+ *     and column in the factor, the band of S, a and the extraction, unchanged; and the band of T by this section's
+ *     kernels: the tested columns of a block tiled 16 per tile as in section 2n, one wave per (tile row, slab of
+ *     positions) walking its slab from the last position to the first, reading row rowof[l] of x in place, keeping the
+ *     running suffix sum of each of its columns inside the slab and feeding it, and cc times it, to the fp64 matrix
+ *     cores for its own tile and the w neighbour tiles; per slab s it writes Q_s = sum cc_p s_loc s_loc^T (band), A_s =
+ *     sum e_l x_l, B_s = sum cc_p s_loc,p and sigma_s = sum cc_p, and a finish kernel adds Q_s + c_s B_s^T + B_s c_s^T +
+ *     sigma_s c_s c_s^T over the slabs in descending order with c_s = sum_{s' > s} A_s'.  No n x q temporary, no
+ *     floating-point atomics: the same call gives the same bits, and u, a, D, T, S are the same bits under every layout
+ *     of the same element type and under every candidate_block (the position split is a function of n alone).  Rows past
+ *     n, columns outside the support and the tested groups and the padding of tiles are not read.
+ *     bessx_cox_groupscore_workspace needs no device: *doubles of scratch memory in all for J = n_event_rows, the
+ *     *block_doubles of it that do not depend on p, the row split of u and C (rows_per_slab[0], slabs[0]), of D
+ *     (rows_per_slab[1], slabs[1]) and the position split of T (rows_per_slab[2], slabs[2]), *n_blocks, block_first and
+ *     *band as in section 2n, and the longest chains: depth[0] .. depth[3] as in section 2n (depth[1]: the score behind r,
+ *     summed over the support as candidates) and depth[4] = t_depth, the roundings behind a term of an entry of T.
+ *     A tested group of more than 64 columns is BESSX_ERR_UNSUPPORTED, as is m + 1 > 1024; n <= 2^31 - 1.  Every argument
+ *     error is found before any device call (BESSX_ERR_ARG: the messages of sections 2h, 2m and 2n).  Scratch memory is
+ *     released before the call returns.  Out of scope: Efron ties, strata, any correction for selection.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  const double *factor;
+  long long factor_ld;
+  const int *group_starts;
+  int n_groups;
+  const int *groups;
+  int n_tested;
+  int candidate_block;
+  double *info;
+  long long info_ld;
+  double *score;
+  double *u;
+  double *a;
+  double *D;
+  double *T;
+  double *S;
+  long long *offsets;
+  int out_on_device;
+  void *stream;
+} bessx_cox_groupscore_input;
+int bessx_cox_groupscore_device(const bessx_cox_groupscore_input *in, double *loglik, double *n_events,
+                                double *residual_sum);
+int bessx_cox_groupscore_workspace(int n, int p, int m, int n_event_rows, const int *group_starts, int n_groups,
+                                   const int *groups, int n_tested, int candidate_block, long long *doubles,
+                                   long long *block_doubles, long long *rows_per_slab, int *slabs, int *n_blocks,
+                                   int *block_first, int *band, int *depth);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1465,6 +1545,15 @@ int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, 
 int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                               const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
                               int n_tested, int candidate_block, int repeats, double *stage_ms);
+/* The steps of section 2o timed the same way, from n-vectors, an A and a factor of the library's own (those of
+ * bessx_op_cox_addscore_bench, with a constant cc): stage_ms[0] .. [6] as bessx_op_groupscore_bench with section 2m's
+ * pack, [7] the band of the risk-set term T on the matrix cores, [8] the addition of its slabs and the copy of the
+ * groups' blocks of T.  sorted != 0: the rows are in time order already; else a scattered order.  *bytes = what stage 7
+ * needs: the tested columns once. */
+int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                                  const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
+                                  int n_tested, int candidate_block, int sorted, int repeats, double *stage_ms,
+                                  double *bytes);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
