@@ -1393,6 +1393,56 @@ def _eval_y(y, n, R):
     return host, dy, strides[0], (strides[1] if len(shape) == 2 else 0), y_cols
 
 
+def _set_x(a, dx):
+    """The fields of the device matrix, which every input struct begins with."""
+    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1]
+    a.n, a.p = dx.shape
+
+
+def _set_weight(a, weight, n):
+    """weight (None = ones, else n values in a host or a device array) into the weight fields of a GLM input struct,
+    checked; returns what must stay alive for the call."""
+    if weight is None:
+        return []
+    if is_device_array(weight):
+        dw = _DeviceArray(weight, "weight")
+        if dw.size != n:
+            raise ValueError("X.shape(0) should be equal to weight.size")
+        a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
+        return [dw]
+    wh = _f64(weight).reshape(-1)
+    if wh.size != n:
+        raise ValueError("X.shape(0) should be equal to weight.size")
+    a.weight_host = _dp(wh)
+    return [wh]
+
+
+def _glm_call(a, who, x, cols, beta, coef0, y, link, weight, stream):
+    """The fields that the input structs of the one-model GLM entry points share -- x, cols / m / beta / coef0 / link, y,
+    weight, stream -- filled into a, after every check of them that needs no device (`who` names the wrapper in the
+    message about a 2-D beta).  Returns (n, p, cols, beta, coef0, what must stay alive for the call)."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if link not in LINKS:
+        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: %s takes one model per call" % who)
+    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
+    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
+        raise ValueError("beta and coef0 must be finite")
+    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
+    _set_x(a, dx)
+    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
+    a.y_stride = yrs
+    if dy is not None:
+        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
+    else:
+        a.y_host = _dp(yh)
+    keep = [dx, cols, B, yh, dy] + _set_weight(a, weight, n)
+    a.stream = int(stream) if stream else None
+    return n, p, cols, B.reshape(-1), float(c0[0]), keep
+
+
 def evaluate_device(x, cols, B, coef0, y, link="identity", weight=None, stream=0):
     """Held-out loss of R models on a device matrix x (n x p: float64 or float32, any non-negative strides) in one pass
     over the support's columns (bessx_eval_device): with eta = x[:, cols] @ B + coef0,
@@ -1411,26 +1461,14 @@ def evaluate_device(x, cols, B, coef0, y, link="identity", weight=None, stream=0
     R = B.shape[1]
     yh, dy, yrs, ycs, y_cols = _eval_y(y, n, R)
     a = EvalInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    _set_x(a, dx)
     a.cols, a.m, a.B, a.coef0, a.R, a.link = _ip(cols), cols.size, _dp(B), _dp(coef0), R, LINKS[link]
     a.y_row_stride, a.y_col_stride, a.y_cols = yrs, ycs, y_cols
     if dy is not None:
         a.y_dev, a.y_dtype = dy.ptr, dy.dtype
     else:
         a.y_host = _dp(yh)
-    keep = [weight]
-    if weight is not None:
-        if is_device_array(weight):
-            dw = _DeviceArray(weight, "weight")
-            if dw.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
-        else:
-            wh = _f64(weight).reshape(-1)
-            if wh.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_host = _dp(wh)
-            keep.append(wh)
+    keep = _set_weight(a, weight, n)  # (alive until the call has returned)
     a.stream = int(stream) if stream else None
     loss, aux, sw = np.zeros(R), np.zeros(R), _d(0)
     _check(lib().bessx_eval_device(ctypes.byref(a), _dp(loss), _dp(aux), ctypes.byref(sw)))
@@ -1506,41 +1544,11 @@ def information_device(x, cols, beta, coef0, y, link="identity", weight=None, st
     of x[:, cols] is made, every sum has a fixed order (the same call gives the same bits), and a NaN inside the support
     view propagates (also from a row of weight 0).  len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y,
     weight) were produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if link not in LINKS:
-        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: information_device takes one model per call")
-    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
-    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
-        raise ValueError("beta and coef0 must be finite")
-    yh, dy, yrs, _, y_cols = _eval_y(y, n, 1)
     a = InfoInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
-    a.y_stride = yrs
-    if dy is not None:
-        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
-    else:
-        a.y_host = _dp(yh)
-    keep = [weight]
-    if weight is not None:
-        if is_device_array(weight):
-            dw = _DeviceArray(weight, "weight")
-            if dw.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
-        else:
-            wh = _f64(weight).reshape(-1)
-            if wh.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_host = _dp(wh)
-            keep.append(wh)
+    n, p, cols, beta, coef0, keep = _glm_call(a, "information_device", x, cols, beta, coef0, y, link, weight, stream)
     M = cols.size + 1
     info, score = np.empty((M, M)), np.empty(M)
     a.info, a.info_ld, a.score, a.out_on_device = info.ctypes.data, M, score.ctypes.data, 0
-    a.stream = int(stream) if stream else None
     loss, sw = _d(0), _d(0)
     _check(lib().bessx_info_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw)))
     return {"info": info, "score": score, "loss": loss.value, "sum_w": sw.value}
@@ -1709,40 +1717,11 @@ def diagnostics_device(x, cols, beta, coef0, y, factor=None, dispersion=1.0, lin
     R, phi and M alone: the same bits wherever the row lies, whatever n is, under every layout of x.  No gathered copy
     of x[:, cols] and nothing n x M is stored.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y,
     weight) were produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if link not in LINKS:
-        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
     mask, names = _diag_mask(kinds)
     K = len(names)
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: diagnostics_device takes one model per call")
-    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
-    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
-        raise ValueError("beta and coef0 must be finite")
-    M = cols.size + 1
-    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
     a = DiagInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
-    a.y_stride = yrs
-    if dy is not None:
-        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
-    else:
-        a.y_host = _dp(yh)
-    keep = [weight]
-    if weight is not None:
-        if is_device_array(weight):
-            dw = _DeviceArray(weight, "weight")
-            if dw.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
-        else:
-            wh = _f64(weight).reshape(-1)
-            if wh.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_host = _dp(wh)
-            keep.append(wh)
+    n, p, cols, beta, coef0, keep = _glm_call(a, "diagnostics_device", x, cols, beta, coef0, y, link, weight, stream)
+    M = cols.size + 1
     if factor is not None:
         fh = _f64(factor)
         if fh.shape != (M, M):
@@ -1771,7 +1750,6 @@ def diagnostics_device(x, cols, beta, coef0, y, factor=None, dispersion=1.0, lin
             a.out, a.out_on_device = int(buf.ctypes.data), 0
         a.out_ld = n
         result = [buf[s] for s in range(K)]
-    a.stream = int(stream) if stream else None
     _check(lib().bessx_diag_device(ctypes.byref(a)))
     return dict(zip(names, result))
 
@@ -1835,42 +1813,13 @@ def addscore_device(x, cols, beta, coef0, y, link="identity", weight=None, facto
     models: cox_addscore_device.  Groups of columns with more than one degree of freedom: groupscore_device.  Not corrected
     for selection.
     len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if link not in LINKS:
-        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: addscore_device takes one model per call")
-    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
-    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
-        raise ValueError("beta and coef0 must be finite")
+    a = AddscoreInput()
+    n, p, cols, beta, coef0, keep = _glm_call(a, "addscore_device", x, cols, beta, coef0, y, link, weight, stream)
     cand, q = _candidates(candidates, p)
     M = cols.size + 1
-    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
-    a = AddscoreInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
-    a.y_stride = yrs
-    if dy is not None:
-        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
-    else:
-        a.y_host = _dp(yh)
-    keep = [weight]
-    if weight is not None:
-        if is_device_array(weight):
-            dw = _DeviceArray(weight, "weight")
-            if dw.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
-        else:
-            wh = _f64(weight).reshape(-1)
-            if wh.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_host = _dp(wh)
-            keep.append(wh)
     pd = True
     if factor is None:
-        first = information_device(x, cols, B.reshape(-1), float(c0[0]), y, link=link, weight=weight, stream=stream)
+        first = information_device(x, cols, beta, coef0, y, link=link, weight=weight, stream=stream)
         fh, pd = info_factor(first["info"])
     else:
         fh = _f64(factor)
@@ -1888,7 +1837,6 @@ def addscore_device(x, cols, beta, coef0, y, link="identity", weight=None, facto
         cross = np.empty((q, M))
         a.cross, a.cross_ld = cross.ctypes.data, M
     a.out_on_device = 0
-    a.stream = int(stream) if stream else None
     loss, sw = _d(0), _d(0)
     _check(lib().bessx_addscore_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw)))
     got = {"columns": np.arange(p, dtype=np.int64) if cand is None else cand.astype(np.int64), "u": out[0], "d": out[1],
@@ -2014,46 +1962,17 @@ def groupscore_device(x, cols, beta, coef0, y, group_starts, groups=None, link="
     The same call gives the same bits, and every layout of the same values of one dtype gives the same bits.  A tested
     group wider than 64 columns is BessxError code 3.  Cox models: cox_groupscore_device.  Not corrected for selection.
     len(cols) + 1 <= 1024.  stream: raw handle of the stream x (and y, weight) were produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if link not in LINKS:
-        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: groupscore_device takes one model per call")
-    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
-    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
-        raise ValueError("beta and coef0 must be finite")
+    a = GroupscoreInput()
+    n, p, cols, beta, coef0, keep = _glm_call(a, "groupscore_device", x, cols, beta, coef0, y, link, weight, stream)
     gs, tg = _group_lists(group_starts, groups, p)
     nt = gs.size if tg is None else tg.size
     lists = _group_columns(gs, tg, p)
     ok = lists is not None and lists[1].max() <= GROUPSCORE_WIDTH_MAX  # (else the library refuses before it writes)
     q, tot = (int(lists[1].sum()), int((lists[1] * lists[1]).sum())) if ok else (1, 1)
     M = cols.size + 1
-    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
-    a = GroupscoreInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
-    a.y_stride = yrs
-    if dy is not None:
-        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
-    else:
-        a.y_host = _dp(yh)
-    keep = [weight]
-    if weight is not None:
-        if is_device_array(weight):
-            dw = _DeviceArray(weight, "weight")
-            if dw.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
-        else:
-            wh = _f64(weight).reshape(-1)
-            if wh.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_host = _dp(wh)
-            keep.append(wh)
     pd = True
     if factor is None:
-        first = information_device(x, cols, B.reshape(-1), float(c0[0]), y, link=link, weight=weight, stream=stream)
+        first = information_device(x, cols, beta, coef0, y, link=link, weight=weight, stream=stream)
         fh, pd = info_factor(first["info"])
     else:
         fh = _f64(factor)
@@ -2069,7 +1988,6 @@ def groupscore_device(x, cols, beta, coef0, y, group_starts, groups=None, link="
     a.u, a.a, a.D, a.S = vec[0].ctypes.data, vec[1].ctypes.data, blk[0].ctypes.data, blk[1].ctypes.data
     a.offsets = offsets.ctypes.data_as(ctypes.POINTER(_ll))
     a.out_on_device = 0
-    a.stream = int(stream) if stream else None
     loss, sw = _d(0), _d(0)
     _check(lib().bessx_groupscore_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw)))
     return {"columns": lists[2], "group_of_column": lists[3], "u": vec[0], "a": vec[1], "D": blk[0], "S": blk[1],
@@ -2327,7 +2245,7 @@ def meat_device(x, cols, u=None, cluster=None, intercept=True, stream=0):
     if M < 1:
         raise ValueError("an empty support needs intercept=True")
     a = MeatInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    _set_x(a, dx)
     a.cols, a.m, a.intercept = _ip(cols), cols.size, icpt
     keep = [dx, cols]
     if u is not None:
@@ -2372,41 +2290,12 @@ def sandwich_device(x, cols, beta, coef0, y, link="identity", weight=None, kind=
     copy of x[:, cols] and no n x M score matrix: the scratch is n-vectors, the Gram partials and G * M doubles of
     cluster sums.  The same call gives the same bits, and with cluster the meat is the same bits under every layout of
     the same x.  A NaN inside the support view propagates.  len(cols) + 1 <= 1024."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if link not in LINKS:
-        raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
     k = _cov_kind(kind)
     if cluster is not None and k >= 2:
         raise ValueError("cluster goes with kind 'HC0' (CR0) or 'HC1' (CR1), got %r" % kind)
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: sandwich_device takes one model per call")
-    cols, B, c0 = _predict_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1), [coef0])
-    if not (np.isfinite(B).all() and np.isfinite(c0).all()):
-        raise ValueError("beta and coef0 must be finite")
-    M = cols.size + 1
-    yh, dy, yrs, _, _ = _eval_y(y, n, 1)
     a = SandwichInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta, a.coef0, a.link = _ip(cols), cols.size, _dp(B), float(c0[0]), LINKS[link]
-    a.y_stride = yrs
-    if dy is not None:
-        a.y_dev, a.y_dtype = dy.ptr, dy.dtype
-    else:
-        a.y_host = _dp(yh)
-    keep = [weight]
-    if weight is not None:
-        if is_device_array(weight):
-            dw = _DeviceArray(weight, "weight")
-            if dw.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_dev, a.weight_dtype, a.weight_stride = dw.ptr, dw.dtype, dw.as_vector("weight")
-        else:
-            wh = _f64(weight).reshape(-1)
-            if wh.size != n:
-                raise ValueError("X.shape(0) should be equal to weight.size")
-            a.weight_host = _dp(wh)
-            keep.append(wh)
+    n, p, cols, beta, coef0, keep = _glm_call(a, "sandwich_device", x, cols, beta, coef0, y, link, weight, stream)
+    M = cols.size + 1
     a.kind = k
     if k >= 2:
         if factor is None:
@@ -2422,7 +2311,6 @@ def sandwich_device(x, cols, beta, coef0, y, link="identity", weight=None, kind=
     info, score, meat = np.empty((M, M)), np.empty(M), np.empty((M, M))
     a.info, a.info_ld, a.score, a.meat, a.meat_ld = info.ctypes.data, M, score.ctypes.data, meat.ctypes.data, M
     a.out_on_device = 0
-    a.stream = int(stream) if stream else None
     loss, sw, G = _d(0), _d(0), _i(0)
     _check(lib().bessx_sandwich_device(ctypes.byref(a), ctypes.byref(loss), ctypes.byref(sw), ctypes.byref(G)))
     return {"info": info, "score": score, "loss": loss.value, "sum_w": sw.value, "meat": meat,
@@ -2531,6 +2419,22 @@ def _survival_vector(a, n, what, stream=0, check_only=False):
     return a
 
 
+def _cox_data(a, time, status, weight, n, stream):
+    """time, status (0 or 1) and weight (None = ones) of a Cox call -- n values each, host or device arrays -- as float64
+    host arrays in the fields of a, checked; every shape is checked before anything is copied.  Returns {"time",
+    "status"[, "weight"]}, which must stay alive for the call."""
+    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
+    for what, v in given:
+        _survival_vector(v, n, what, check_only=True)
+    host = {what: _survival_vector(v, n, what, stream) for what, v in given}
+    if np.isnan(host["time"]).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(host["status"], (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    return host
+
+
 def evaluate_cox_device(x, cols, B, time, status, weight=None, ties="order", concordance=True, stream=0):
     """Held-out Cox partial log-likelihood and Harrell's concordance of R models on a device matrix x (n x p: float64 or
     float32, any non-negative strides), read once where it lies, the support's columns only (bessx_eval_cox_device).
@@ -2552,18 +2456,10 @@ def evaluate_cox_device(x, cols, B, time, status, weight=None, ties="order", con
     B = np.asarray(B, dtype=np.float64)
     R = B.shape[1] if B.ndim == 2 else 1
     cols, B, _ = _predict_model(dx, cols, B, np.zeros(R))
-    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
-    for what, a in given:  # (every shape is checked before anything is copied)
-        _survival_vector(a, n, what, check_only=True)
-    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
-    if np.isnan(host["time"]).any():
-        raise ValueError("There is NAN value in time")
-    if not np.isin(host["status"], (0.0, 1.0)).all():
-        raise ValueError("status should be 0 or 1")
     a = CoxEvalInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    _set_x(a, dx)
     a.cols, a.m, a.B, a.R = _ip(cols), cols.size, _dp(B), R
-    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
+    host = _cox_data(a, time, status, weight, n, stream)  # (alive until the call has returned)
     a.ties, a.want_pairs, a.stream = TIES[ties], int(bool(concordance)), int(stream) if stream else None
     loglik, pairs, comp = np.zeros(R), np.zeros((R, 3), dtype=np.int64), _ll(0)
     _check(lib().bessx_eval_cox_device(ctypes.byref(a), _dp(loglik), pairs.ctypes.data_as(ctypes.POINTER(_ll)),
@@ -2617,6 +2513,27 @@ def _cox_model(dx, cols, B):
     return cols, np.ascontiguousarray(B.reshape(-1))
 
 
+def _cox_call(a, who, x, cols, beta, time, status, weight, ties, stream):
+    """The fields that the input structs of the one-model Cox entry points share -- x, cols / m / beta, time / status /
+    weight, ties, stream -- filled into a, after every check of them that needs no device (`who` names the wrapper in
+    the message about a 2-D beta).  Returns (n, p, cols, beta, the host arrays of _cox_data): what must stay alive for the
+    call."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    if ties not in TIES:
+        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: %s takes one model per call" % who)
+    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
+    if not np.isfinite(B).all():
+        raise ValueError("beta must be finite")
+    host = _cox_data(a, time, status, weight, n, stream)
+    _set_x(a, dx)
+    a.cols, a.m, a.beta = _ip(cols), cols.size, _dp(B)
+    a.ties, a.stream = TIES[ties], int(stream) if stream else None
+    return n, p, cols, B, host
+
+
 def cox_info_workspace(n, m, n_event_rows):
     """(doubles of scratch memory, (rows per slab, slabs) of the sweep over x, (rows per slab, slabs) of the sweep over the
     risk-set means) of a cox_information_device call on n rows with a support of m columns and n_event_rows rows of
@@ -2646,30 +2563,10 @@ def cox_information_device(x, cols, beta, time, status, weight=None, ties="order
     order is made, every sum has a fixed order (the same call gives the same bits), and a NaN inside the support view
     propagates.  Scratch: about (m + 5) n + J m doubles for J event rows plus the sweeps' partials (cox_info_workspace:
     3.4 GB at n = 200 000, m = 1023, J = n).  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if ties not in TIES:
-        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: cox_information_device takes one model per call")
-    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
-    if not np.isfinite(B).all():
-        raise ValueError("beta must be finite")
-    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
-    for what, a in given:  # (every shape is checked before anything is copied)
-        _survival_vector(a, n, what, check_only=True)
-    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
-    if np.isnan(host["time"]).any():
-        raise ValueError("There is NAN value in time")
-    if not np.isin(host["status"], (0.0, 1.0)).all():
-        raise ValueError("status should be 0 or 1")
+    a = CoxInfoInput()
+    n, p, cols, B, host = _cox_call(a, "cox_information_device", x, cols, beta, time, status, weight, ties, stream)
     m = cols.size
     info, score = np.empty((m, m)), np.empty(m)
-    a = CoxInfoInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
-    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
-    a.ties, a.stream = TIES[ties], int(stream) if stream else None
     a.info, a.info_ld, a.score, a.out_on_device = info.ctypes.data, m, score.ctypes.data, 0
     ll, ne, rs = _d(0), _d(0), _d(0)
     _check(lib().bessx_cox_info_device(ctypes.byref(a), ctypes.byref(ll), ctypes.byref(ne), ctypes.byref(rs)))
@@ -2727,24 +2624,9 @@ def cox_addscore_device(x, cols, beta, time, status, weight=None, ties="order", 
     (cox_addscore_workspace).  The same call gives the same bits, and every layout of the same values of one dtype
     gives the same bits.  Groups of columns with more than one degree of freedom: cox_groupscore_device.  Not for Efron
     ties or strata, not corrected for selection.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if ties not in TIES:
-        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: cox_addscore_device takes one model per call")
-    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
-    if not np.isfinite(B).all():
-        raise ValueError("beta must be finite")
+    a = CoxAddscoreInput()
+    n, p, cols, B, host = _cox_call(a, "cox_addscore_device", x, cols, beta, time, status, weight, ties, stream)
     cand, q = _candidates(candidates, p)
-    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
-    for what, a in given:  # (every shape is checked before anything is copied)
-        _survival_vector(a, n, what, check_only=True)
-    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
-    if np.isnan(host["time"]).any():
-        raise ValueError("There is NAN value in time")
-    if not np.isin(host["status"], (0.0, 1.0)).all():
-        raise ValueError("status should be 0 or 1")
     m = cols.size
     pd = True
     fh = None
@@ -2758,11 +2640,6 @@ def cox_addscore_device(x, cols, beta, time, status, weight=None, ties="order", 
         fh = _f64(factor)
         if fh.shape != (m, m):
             raise ValueError("factor must have shape (%d, %d), got %s" % (m, m, fh.shape))
-    a = CoxAddscoreInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
-    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
-    a.ties, a.stream = TIES[ties], int(stream) if stream else None
     if pd and m > 0:
         a.factor, a.factor_ld = _dp(fh), m
     a.candidates, a.q, a.candidate_block = _ip(cand), q, int(candidate_block)
@@ -2862,28 +2739,13 @@ def cox_groupscore_device(x, cols, beta, time, status, group_starts, groups=None
     every candidate_block gives the same bits.  A tested group wider than 64 columns is BessxError code 3.  Not for Efron
     ties or strata, not corrected for selection.  len(cols) + 1 <= 1024.  stream: raw handle of the stream x was
     produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if ties not in TIES:
-        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: cox_groupscore_device takes one model per call")
-    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
-    if not np.isfinite(B).all():
-        raise ValueError("beta must be finite")
+    a = CoxGroupscoreInput()
+    n, p, cols, B, host = _cox_call(a, "cox_groupscore_device", x, cols, beta, time, status, weight, ties, stream)
     gs, tg = _group_lists(group_starts, groups, p)
     nt = gs.size if tg is None else tg.size
     lists = _group_columns(gs, tg, p)
     ok = lists is not None and lists[1].max() <= GROUPSCORE_WIDTH_MAX  # (else the library refuses before it writes)
     q, tot = (int(lists[1].sum()), int((lists[1] * lists[1]).sum())) if ok else (1, 1)
-    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
-    for what, v in given:  # (every shape is checked before anything is copied)
-        _survival_vector(v, n, what, check_only=True)
-    host = {what: _survival_vector(v, n, what, stream) for what, v in given}
-    if np.isnan(host["time"]).any():
-        raise ValueError("There is NAN value in time")
-    if not np.isin(host["status"], (0.0, 1.0)).all():
-        raise ValueError("status should be 0 or 1")
     m = cols.size
     pd, fh = True, None
     if m == 0:
@@ -2896,11 +2758,6 @@ def cox_groupscore_device(x, cols, beta, time, status, group_starts, groups=None
         fh = _f64(factor)
         if fh.shape != (m, m):
             raise ValueError("factor must have shape (%d, %d), got %s" % (m, m, fh.shape))
-    a = CoxGroupscoreInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
-    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
-    a.ties, a.stream = TIES[ties], int(stream) if stream else None
     if pd and m > 0:
         a.factor, a.factor_ld = _dp(fh), m
     a.group_starts, a.n_groups, a.groups, a.n_tested = _ip(gs), gs.size, _ip(tg), nt
@@ -2995,31 +2852,12 @@ def cox_diagnostics_device(x, cols, beta, time, status, factor=None, cinv=None, 
     max(., 0) of the deviance; a NaN inside the support propagates.  x's support is read three times (predictor, the
     gather of e x, the forming of L) plus the J event rows for schoenfeld; the same call gives the same bits.
     len(cols) + 1 <= 1024.  stream: raw handle of the stream x was produced on."""
-    dx = _DeviceArray(x, "x", 2)
-    n, p = dx.shape
-    if ties not in TIES:
-        raise ValueError("ties must be one of %s, got %r" % (sorted(TIES), ties))
     mask, names = _cox_diag_mask(kinds)
-    if np.ndim(beta) > 1:
-        raise ValueError("beta must be 1-D: cox_diagnostics_device takes one model per call")
-    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
-    if not np.isfinite(B).all():
-        raise ValueError("beta must be finite")
-    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
-    for what, a in given:  # (every shape is checked before anything is copied)
-        _survival_vector(a, n, what, check_only=True)
-    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
-    if np.isnan(host["time"]).any():
-        raise ValueError("There is NAN value in time")
-    if not np.isin(host["status"], (0.0, 1.0)).all():
-        raise ValueError("status should be 0 or 1")
+    a = CoxDiagInput()
+    n, p, cols, B, host = _cox_call(a, "cox_diagnostics_device", x, cols, beta, time, status, weight, ties, stream)
     m = cols.size
     J = int(np.count_nonzero(host["status"]))
-    a = CoxDiagInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
-    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
-    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
-    a.ties, a.stream, a.kinds = TIES[ties], int(stream) if stream else None, mask
+    a.kinds = mask
     keep = []
     for what, mat in (("factor", factor), ("cinv", cinv)):
         if mat is not None:
@@ -3087,20 +2925,12 @@ def cox_baseline_device(x, cols, B, time, status, weight=None, stream=0):
     dx = _DeviceArray(x, "x", 2)
     n, p = dx.shape
     cols, B = _cox_model(dx, cols, B)
-    given = [("time", time), ("status", status)] + ([("weight", weight)] if weight is not None else [])
-    for what, a in given:  # (every shape is checked before anything is copied)
-        _survival_vector(a, n, what, check_only=True)
-    host = {what: _survival_vector(a, n, what, stream) for what, a in given}
-    if np.isnan(host["time"]).any():
-        raise ValueError("There is NAN value in time")
-    if not np.isin(host["status"], (0.0, 1.0)).all():
-        raise ValueError("status should be 0 or 1")
+    a = CoxBaselineInput()
+    host = _cox_data(a, time, status, weight, n, stream)
     if weight is not None and not (host["weight"] >= 0.0).all():
         raise ValueError("weight should be non-negative")
-    a = CoxBaselineInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    _set_x(a, dx)
     a.cols, a.m, a.B = _ip(cols), cols.size, _dp(B)
-    a.time, a.status, a.weight = _dp(host["time"]), _dp(host["status"]), _dp(host.get("weight"))
     a.stream = int(stream) if stream else None
     J, times, cumhaz = _i(0), np.zeros(n), np.zeros(n)
     _check(lib().bessx_cox_baseline_device(ctypes.byref(a), ctypes.byref(J), _dp(times), _dp(cumhaz)))
@@ -3167,7 +2997,7 @@ def cox_survival_device(x, cols, B, base_times, base_cumhaz, times=None, kind="s
             ptr, on_device = int(result.ctypes.data), 0
         ors, ocs = T, 1
     a = CoxSurvivalInput()
-    a.x, a.x_dtype, a.x_row_stride, a.x_col_stride, a.n, a.p = dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], n, p
+    _set_x(a, dx)
     a.cols, a.m, a.B, a.hg, a.T, a.kind = _ip(cols), cols.size, _dp(B), _dp(hg), T, SURV_KINDS[kind]
     a.out_row_stride, a.out_col_stride, a.out_on_device = ors, ocs, on_device
     a.stream = int(stream) if stream else None

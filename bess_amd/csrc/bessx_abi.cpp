@@ -1,7 +1,5 @@
 // bessx_abi.cpp -- the drop-in entry points bessx_pywrap_bess / bessx_bessCpp (src/bess.h:20-51) and the single-kernel ops
-#include "bessx_host.h"
-
-#include <climits>
+#include "bessx_devcall.h"
 
 extern "C" {
 
@@ -1270,50 +1268,11 @@ int bessx_op_ingest_bench(const void *x, int dtype, long long row_stride, long l
 // ----------------------------------------------------------------------------------------------
 // prediction on a caller's device matrix (include/bessx.h section 2c)
 // ----------------------------------------------------------------------------------------------
-static_assert((int)BESSX_LINK_IDENTITY == (int)PREDICT_IDENTITY && (int)BESSX_LINK_LOGISTIC == (int)PREDICT_LOGISTIC &&
-                  (int)BESSX_LINK_POISSON == (int)PREDICT_POISSON, "link codes of the launcher");
-
-// everything about a model that needs no device
-static int predict_check_model(const char *who, int n, int p, const int *cols, int m, int R, int link) {
-  const std::string w(who);
-  if (n < 1 || p < 1) return fail(BESSX_ERR_ARG, w + ": empty matrix");
-  if (R < 1) return fail(BESSX_ERR_ARG, w + ": R must be at least 1");
-  if (link != BESSX_LINK_IDENTITY && link != BESSX_LINK_LOGISTIC && link != BESSX_LINK_POISSON)
-    return fail(BESSX_ERR_ARG, w + ": unknown link");
-  if (m < 0 || m > p) return fail(BESSX_ERR_ARG, w + ": m must lie in [0, p]");
-  if (m > 0 && !cols) return fail(BESSX_ERR_ARG, w + ": null argument (cols)");
-  for (int k = 0; k < m; k++) {
-    if (cols[k] < 0 || cols[k] >= p) return fail(BESSX_ERR_ARG, w + ": column number out of range");
-    if (k > 0 && cols[k] <= cols[k - 1]) return fail(BESSX_ERR_ARG, w + ": cols must be ascending and distinct");
-  }
-  return 0;
-}
-
-// the model in one device allocation of `sc`: cols, then B, then coef0 (queued on st; the host arrays must outlive it)
-static int predict_upload_model(Owner &sc, const int *cols, int m, const double *B, const double *coef0, int R,
-                                hipStream_t st, int **cols_d, double **B_d, double **c_d) {
-  HIPX(sc.alloc(B_d, (size_t)m * R + (size_t)R));
-  HIPX(sc.alloc(cols_d, (size_t)m));
-  *c_d = *B_d + (size_t)m * R;
-  if (m > 0) {
-    HIPX(hipMemcpyAsync(*cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPX(hipMemcpyAsync(*B_d, B, (size_t)m * R * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-  HIPX(hipMemcpyAsync(*c_d, coef0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st));
-  return 0;
-}
-
-static int predict_run(const void *x, int f32, long long rs, long long cs, int n, const int *cols, int m,
-                       const double *B, const double *coef0, int R, int link, double *out, long long ors,
-                       long long ocs, double *out2, int out_on_device, hipStream_t caller, hipStream_t st) {
-  Owner sc;
+static int predict_run(Owner &sc, std::vector<double> &tmp, const void *x, int f32, long long rs, long long cs, int n,
+                       const int *cols, int m, const double *B, const double *coef0, int R, int link, double *out,
+                       long long ors, long long ocs, double *out2, int out_on_device, hipStream_t st) {
   int *cols_d = nullptr;
   double *B_d = nullptr, *c_d = nullptr, *stage = nullptr;
-  // reads and writes come after everything the caller has queued on its stream so far
-  hipEvent_t ev = nullptr;
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, caller));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   if (int rc = predict_upload_model(sc, cols, m, B, coef0, R, st, &cols_d, &B_d, &c_d)) return rc;
   const bool two = link == BESSX_LINK_LOGISTIC;
   const size_t cnt = (size_t)n * R;
@@ -1325,7 +1284,6 @@ static int predict_run(const void *x, int f32, long long rs, long long cs, int n
   HIPX(sc.alloc(&stage, cnt * (two ? 2 : 1)));
   HIPX(launch_predict(x, f32, rs, cs, n, cols_d, m, B_d, c_d, R, link, stage, R, 1, two ? stage + cnt : nullptr, st));
   const bool dense = ocs == 1 && ors == R;  // (R == 1: any ocs addresses the same elements)
-  std::vector<double> tmp;
   double *h1 = out, *h2 = out2;
   if (!(dense || (R == 1 && ors == 1))) {
     tmp.resize(cnt * (two ? 2 : 1));
@@ -1352,12 +1310,10 @@ int bessx_predict_device(const void *x, int x_dtype, long long x_row_stride, lon
                          long long out_row_stride, long long out_col_stride, double *out2, int out_on_device,
                          void *stream) {
   if (!x || !coef0 || !out) return fail(BESSX_ERR_ARG, "predict_device: null argument");
-  if (x_dtype != BESSX_F64 && x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, "predict_device: x: dtype must be BESSX_F64 or BESSX_F32");
-  if (x_row_stride < 0 || x_col_stride < 0 || out_row_stride < 0 || out_col_stride < 0)
-    return fail(BESSX_ERR_ARG, "predict_device: strides must be non-negative");
-  if (int rc = predict_check_model("predict_device", n, p, cols, m, R, link)) return rc;
-  if (m > 0 && !B) return fail(BESSX_ERR_ARG, "predict_device: null argument (B)");
+  if (int rc = check_x_model("predict_device", x, x_dtype,
+                             x_row_stride >= 0 && x_col_stride >= 0 && out_row_stride >= 0 && out_col_stride >= 0, n, p,
+                             cols, m, B, R, link, false))
+    return rc;
   if (link == BESSX_LINK_LOGISTIC && !out2) return fail(BESSX_ERR_ARG, "predict_device: the logistic link needs out2");
   if ((n > 1 && out_row_stride == 0) || (R > 1 && out_col_stride == 0))
     return fail(BESSX_ERR_ARG, "predict_device: out: a zero stride along an axis longer than 1");
@@ -1365,25 +1321,16 @@ int bessx_predict_device(const void *x, int x_dtype, long long x_row_stride, lon
   int dev = -1;
   if (int rc = check_device_matrix("predict_device: x", x, x_dtype, x_row_stride, x_col_stride, n, p, &dev)) return rc;
   if (out_on_device) {
-    int od = -1;
-    if (int rc = check_device_matrix("predict_device: out", out, BESSX_F64, out_row_stride, out_col_stride, n, R, &od))
+    if (int rc = check_on_device("predict_device", "out", out, BESSX_F64, out_row_stride, out_col_stride, n, R, dev))
       return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "predict_device: out is not on the device that owns x");
-    if (link == BESSX_LINK_LOGISTIC) {
-      if (int rc = check_device_matrix("predict_device: out2", out2, BESSX_F64, out_row_stride, out_col_stride, n, R,
-                                       &od))
+    if (link == BESSX_LINK_LOGISTIC)
+      if (int rc = check_on_device("predict_device", "out2", out2, BESSX_F64, out_row_stride, out_col_stride, n, R, dev))
         return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "predict_device: out2 is not on the device that owns x");
-    }
   }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc = predict_run(x, x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, cols, m, B, coef0, R, link, out,
-                       out_row_stride, out_col_stride, out2, out_on_device, static_cast<hipStream_t>(stream), st);
-  if (rc) (void)hipStreamSynchronize(st);  // (nothing queued may outlive the model's buffers)
-  (void)hipStreamDestroy(st);
-  return rc;
+  return dev_call(dev, static_cast<hipStream_t>(stream), [&](DevCall &dc) {
+    return predict_run(dc.sc, dc.h, x, x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, cols, m, B, coef0, R, link, out,
+                       out_row_stride, out_col_stride, out2, out_on_device, dc.st);
+  });
 }
 
 int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
@@ -1403,18 +1350,15 @@ int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long 
   const size_t cnt = (size_t)n * R;
   HIPX(sc.alloc(&out, 2 * cnt));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   const int f32 = dtype == BESSX_F32;
-  HIPX(launch_predict(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, out, R, 1, out + cnt, nullptr));
-  HIPX(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < repeats; i++)
-    HIPX(launch_predict(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, out, R, 1, out + cnt, nullptr));
-  HIPX(hipEventRecord(e1, nullptr));
-  HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
-  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  if (int rc = bt.run(repeats, &ms, [&]() -> int {
+        HIPX(launch_predict(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, out, R, 1, out + cnt, nullptr));
+        return 0;
+      }))
+    return rc;
   const double bytes = (double)n * (double)m * (f32 ? 4.0 : 8.0) + (double)cnt * 8.0;
   *avg_ms = ms / repeats;
   *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;
@@ -1427,122 +1371,73 @@ int bessx_op_predict_bench(const void *x, int dtype, long long row_stride, long 
 // held-out loss on a caller's device matrix (include/bessx.h section 2d)
 // ----------------------------------------------------------------------------------------------
 // everything about the call that needs no device
-static int eval_check_args(const char *who, const bessx_eval_input *in, const double *loss, const double *aux,
-                           const double *sum_w) {
+static int eval_check_args(const char *who, const GlmCall &c, const double *loss, const double *aux, const double *sum_w) {
   const std::string w(who);
-  if (!in || !loss || !sum_w) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (!in->x || !in->coef0) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->x_row_stride < 0 || in->x_col_stride < 0 || in->y_row_stride < 0 || in->y_col_stride < 0 ||
-      in->weight_stride < 0)
-    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, in->R, in->link)) return rc;
-  if (in->m > 0 && !in->B) return fail(BESSX_ERR_ARG, w + ": null argument (B)");
-  if (in->link == BESSX_LINK_LOGISTIC && !aux) return fail(BESSX_ERR_ARG, w + ": the logistic link needs aux");
-  if ((in->y_host != nullptr) == (in->y_dev != nullptr))
-    return fail(BESSX_ERR_ARG, w + ": give y as a host pointer or as a device view (one of the two)");
-  if (in->y_dev && in->y_dtype != BESSX_F64 && in->y_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": y: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->y_cols != 1 && in->y_cols != in->R) return fail(BESSX_ERR_ARG, w + ": y_cols must be 1 or R");
-  if (in->weight_host && in->weight_dev)
-    return fail(BESSX_ERR_ARG, w + ": give weight as a host pointer or as a device vector, not both");
-  if (in->weight_dev && in->weight_dtype != BESSX_F64 && in->weight_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": weight: dtype must be BESSX_F64 or BESSX_F32");
+  if (!loss || !sum_w) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = glm_check(who, c, false)) return rc;
+  if (c.link == BESSX_LINK_LOGISTIC && !aux) return fail(BESSX_ERR_ARG, w + ": the logistic link needs aux");
   return 0;
 }
 
 // y and the weights as the kernel reads them: the caller's device memory where it lies, host data through a buffer of `sc`
-static int eval_stage_data(Owner &sc, const bessx_eval_input *in, hipStream_t st, EvalData *d) {
-  const long long n = in->n;
-  const long long ycs = in->y_cols == 1 ? 0 : in->y_col_stride;
-  *d = EvalData{nullptr, 0, in->y_row_stride, ycs, nullptr, 0, 0};
-  if (in->y_dev) {
-    d->y = in->y_dev;
-    d->y_f32 = in->y_dtype == BESSX_F32;
+static int eval_stage_data(Owner &sc, const GlmCall &c, hipStream_t st, EvalData *d) {
+  const long long n = c.n;
+  const long long ycs = c.y_cols == 1 ? 0 : c.y_cs;
+  *d = EvalData{nullptr, 0, c.y_rs, ycs, nullptr, 0, 0};
+  if (c.y_dev) {
+    d->y = c.y_dev;
+    d->y_f32 = c.y_dtype == BESSX_F32;
   } else {
-    const size_t span = (size_t)((n - 1) * in->y_row_stride + (in->y_cols - 1) * ycs + 1);
+    const size_t span = (size_t)((n - 1) * c.y_rs + (c.y_cols - 1) * ycs + 1);
     double *yd = nullptr;
     HIPX(sc.alloc(&yd, span));
-    HIPX(hipMemcpyAsync(yd, in->y_host, span * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(yd, c.y_host, span * sizeof(double), hipMemcpyHostToDevice, st));
     d->y = yd;
   }
-  if (in->weight_dev) {
-    d->w = in->weight_dev;
-    d->w_f32 = in->weight_dtype == BESSX_F32;
-    d->ws = in->weight_stride;
-  } else if (in->weight_host) {
+  if (c.w_dev) {
+    d->w = c.w_dev;
+    d->w_f32 = c.w_dtype == BESSX_F32;
+    d->ws = c.w_stride;
+  } else if (c.w_host) {
     double *wd = nullptr;
     HIPX(sc.alloc(&wd, (size_t)n));
-    HIPX(hipMemcpyAsync(wd, in->weight_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(wd, c.w_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     d->w = wd;
     d->ws = 1;
   }
   return 0;
 }
 
-// sc and h belong to the caller: they must outlive everything this function queues on st, also when it fails half way
-static int eval_run(Owner &sc, std::vector<double> &h, const bessx_eval_input *in, double *loss, double *aux,
-                    double *sum_w, hipStream_t st) {
-  // reads come after everything the caller has queued on its stream so far
-  hipEvent_t ev = nullptr;
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
+static int eval_run(Owner &sc, std::vector<double> &h, const GlmCall &c, double *loss, double *aux, double *sum_w,
+                    hipStream_t st) {
   int *cols_d = nullptr;
   double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *res = nullptr;
-  const int R = in->R, f32 = in->x_dtype == BESSX_F32;
-  if (int rc = predict_upload_model(sc, in->cols, in->m, in->B, in->coef0, R, st, &cols_d, &B_d, &c_d)) return rc;
+  const int R = c.R, f32 = c.f32();
+  if (int rc = predict_upload_model(sc, c.cols, c.m, c.beta, c.coef0, R, st, &cols_d, &B_d, &c_d)) return rc;
   EvalData d;
-  if (int rc = eval_stage_data(sc, in, st, &d)) return rc;
-  const long long nwork =
-      eval_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, in->m, R, in->link, d.w != nullptr);
+  if (int rc = eval_stage_data(sc, c, st, &d)) return rc;
+  const long long nwork = eval_workspace(f32, c.rs, c.cs, c.n, c.m, R, c.link, d.w != nullptr);
   HIPX(sc.alloc(&work, (size_t)nwork));
   HIPX(sc.alloc(&res, 2 * (size_t)R + 1));
-  HIPX(launch_eval(in->x, f32, in->x_row_stride, in->x_col_stride, in->n, cols_d, in->m, B_d, c_d, R, in->link, d, work,
-                   res, st));
+  HIPX(launch_eval(c.x, f32, c.rs, c.cs, c.n, cols_d, c.m, B_d, c_d, R, c.link, d, work, res, st));
   h.resize(2 * (size_t)R + 1);
   HIPX(hipMemcpyAsync(h.data(), res, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPX(hipStreamSynchronize(st));
   std::copy(h.begin(), h.begin() + R, loss);
-  if (in->link == BESSX_LINK_LOGISTIC) std::copy(h.begin() + R, h.begin() + 2 * R, aux);
-  *sum_w = d.w ? h[2 * (size_t)R] : (double)in->n;
+  if (c.link == BESSX_LINK_LOGISTIC) std::copy(h.begin() + R, h.begin() + 2 * R, aux);
+  *sum_w = d.w ? h[2 * (size_t)R] : (double)c.n;
   return 0;
 }
 
 extern "C" {
 
 int bessx_eval_device(const bessx_eval_input *in, double *loss, double *aux, double *sum_w) {
-  if (int rc = eval_check_args("eval_device", in, loss, aux, sum_w)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("eval_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
-  if (in->y_dev) {
-    if (int rc = check_device_matrix("eval_device: y", in->y_dev, in->y_dtype, in->y_row_stride,
-                                     in->y_cols == 1 ? 0 : in->y_col_stride, in->n, in->y_cols, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "eval_device: y is not on the device that owns x");
-  }
-  if (in->weight_dev) {
-    if (int rc = check_device_matrix("eval_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
-                                     in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "eval_device: weight is not on the device that owns x");
-  }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> h;
-    rc = eval_run(sc, h, in, loss, aux, sum_w, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and h go after this)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  if (!in) return fail(BESSX_ERR_ARG, "eval_device: null argument");
+  const GlmCall c = glm_call(in);
+  if (int rc = eval_check_args("eval_device", c, loss, aux, sum_w)) return rc;
+  int dev = -1;
+  if (int rc = glm_check_device("eval_device", c, &dev)) return rc;
+  return dev_call(dev, c.stream, [&](DevCall &dc) { return eval_run(dc.sc, dc.h, c, loss, aux, sum_w, dc.st); });
 }
 
 int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
@@ -1571,17 +1466,14 @@ int bessx_op_eval_bench(const void *x, int dtype, long long row_stride, long lon
   HIPX(sc.alloc(&work, (size_t)eval_workspace(f32, row_stride, col_stride, n, m, R, link, 1)));
   HIPX(sc.alloc(&res, 2 * (size_t)R + 1));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
-  HIPX(launch_eval(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, d, work, res, nullptr));
-  HIPX(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < repeats; i++)
-    HIPX(launch_eval(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, d, work, res, nullptr));
-  HIPX(hipEventRecord(e1, nullptr));
-  HIPX(hipEventSynchronize(e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   float ms = 0.f;
-  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  if (int rc = bt.run(repeats, &ms, [&]() -> int {
+        HIPX(launch_eval(x, f32, row_stride, col_stride, n, cols_d, m, B_d, c_d, R, link, d, work, res, nullptr));
+        return 0;
+      }))
+    return rc;
   const double bytes = (double)n * (double)m * (f32 ? 4.0 : 8.0) + (double)n * 8.0 * (y_cols + 1.0);
   *avg_ms = ms / repeats;
   *gbps = bytes * repeats / ((double)ms * 1e-3) / 1e9;
@@ -1625,23 +1517,13 @@ void cox_order(const double *time, const double *status, const double *weight, i
   }
 }
 
-int cox_eval_check_args(const char *who, const bessx_cox_eval_input *in, const double *loglik, const long long *pairs,
-                        const long long *comparable) {
+int cox_eval_check_args(const char *who, const CoxCall &c, const bessx_cox_eval_input *in, const double *loglik,
+                        const long long *pairs, const long long *comparable) {
   const std::string w(who);
-  if (!in || !loglik || !comparable) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (!in->x || !in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, in->R, BESSX_LINK_IDENTITY)) return rc;
+  if (!loglik || !comparable) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_check(who, c, false)) return rc;
   if (in->R > 65535) return fail(BESSX_ERR_ARG, w + ": R must be at most 65535");
-  if (in->m > 0 && !in->B) return fail(BESSX_ERR_ARG, w + ": null argument (B)");
-  if (in->ties != 0 && in->ties != 1) return fail(BESSX_ERR_ARG, w + ": ties must be 0 (order) or 1 (breslow)");
   if (in->want_pairs && !pairs) return fail(BESSX_ERR_ARG, w + ": want_pairs needs pairs");
-  for (int i = 0; i < in->n; i++) {
-    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
-    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
-  }
   return 0;
 }
 
@@ -1683,13 +1565,8 @@ int cox_eval_stage(Owner &sc, const CoxOrder &o, const int *cols, int m, const d
   return 0;
 }
 
-// sc, o, hl and hc belong to the caller: they must outlive everything this function queues on st, also when it fails
 int cox_eval_run(Owner &sc, const CoxOrder &o, std::vector<double> &hl, std::vector<unsigned long long> &hc,
                  const bessx_cox_eval_input *in, double *loglik, long long *pairs, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int R = in->R, n = in->n, f32 = in->x_dtype == BESSX_F32;
   CoxDev d;
   if (int rc = cox_eval_stage(sc, o, in->cols, in->m, in->B, R, n, in->ties == 1, in->want_pairs, st, &d)) return rc;
@@ -1720,26 +1597,16 @@ int cox_eval_run(Owner &sc, const CoxOrder &o, std::vector<double> &hl, std::vec
 extern "C" {
 
 int bessx_eval_cox_device(const bessx_cox_eval_input *in, double *loglik, long long *pairs, long long *comparable) {
-  if (int rc = cox_eval_check_args("eval_cox_device", in, loglik, pairs, comparable)) return rc;
-  if (int rc = need_device()) return rc;
+  if (!in) return fail(BESSX_ERR_ARG, "eval_cox_device: null argument");
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_eval_check_args("eval_cox_device", c, in, loglik, pairs, comparable)) return rc;
   int dev = -1;
-  if (int rc = check_device_matrix("eval_cox_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
+  if (int rc = cox_check_device("eval_cox_device", c, &dev)) return rc;
   CoxOrder o;
   cox_order(in->time, in->status, in->weight, in->n, &o);
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> hl;
-    std::vector<unsigned long long> hc;
-    rc = cox_eval_run(sc, o, hl, hc, in, loglik, pairs, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, hl and hc go after this)
-  }
-  (void)hipStreamDestroy(st);
+  std::vector<unsigned long long> hc;
+  const int rc = dev_call(dev, c.stream,
+                          [&](DevCall &dc) { return cox_eval_run(dc.sc, o, dc.h, hc, in, loglik, pairs, dc.st); });
   if (!rc) *comparable = o.comparable;
   return rc;
 }
@@ -1809,18 +1676,6 @@ namespace {
 
 const double kCoxZero = 0.0;  // Cox has no intercept: the coef0 of predict_upload_model
 
-// x, cols, m, B of one model (R = 1): everything that needs no device
-int cox_surv_check_model(const char *who, const void *x, int dtype, long long rs, long long cs, int n, int p,
-                         const int *cols, int m, const double *B) {
-  const std::string w(who);
-  if (!x) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (dtype != BESSX_F64 && dtype != BESSX_F32) return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (rs < 0 || cs < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m > 0 && !B) return fail(BESSX_ERR_ARG, w + ": null argument (B)");
-  return 0;
-}
-
 // the tie groups that hold an event: their times (ascending) and last positions
 void cox_event_groups(const CoxOrder &o, const double *time, int n, std::vector<double> *times, std::vector<int> *ends) {
   std::vector<double> tpos((size_t)n);
@@ -1840,13 +1695,8 @@ void cox_event_groups(const CoxOrder &o, const double *time, int n, std::vector<
   }
 }
 
-// sc, o, ends and hh belong to the caller: they must outlive everything this function queues on st, also when it fails
 int cox_baseline_run(Owner &sc, const CoxOrder &o, const std::vector<int> &ends, std::vector<double> &hh,
                      const bessx_cox_baseline_input *in, double *cumhaz, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int n = in->n, J = (int)ends.size(), f32 = in->x_dtype == BESSX_F32;
   CoxDev d;
   if (int rc = cox_eval_stage(sc, o, in->cols, in->m, in->B, 1, n, 1, 0, st, &d)) return rc;
@@ -1868,13 +1718,8 @@ int cox_baseline_run(Owner &sc, const CoxOrder &o, const std::vector<int> &ends,
   return 0;
 }
 
-// sc and tmp belong to the caller, as above
 int cox_survival_run(Owner &sc, std::vector<double> &tmp, const bessx_cox_survival_input *in, double *out,
                      hipStream_t st) {
-  hipEvent_t ev = nullptr;
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int n = in->n, T = in->T, f32 = in->x_dtype == BESSX_F32;
   int *cols_d = nullptr;
   double *B_d = nullptr, *zero_d = nullptr, *ex = nullptr, *hg_d = nullptr, *stage = nullptr;
@@ -1913,38 +1758,21 @@ extern "C" {
 int bessx_cox_baseline_device(const bessx_cox_baseline_input *in, int *n_times, double *times, double *cumhaz) {
   const std::string w("cox_baseline_device");
   if (!in || !n_times || !times || !cumhaz) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (int rc = cox_surv_check_model("cox_baseline_device", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                    in->p, in->cols, in->m, in->B))
-    return rc;
-  if (!in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
-  for (int i = 0; i < in->n; i++) {
-    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
-    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
-    if (in->weight && !(in->weight[i] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": weight must be non-negative");
-  }
-  if (int rc = need_device()) return rc;
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_check("cox_baseline_device", c, false)) return rc;
+  if (in->weight)
+    for (int i = 0; i < in->n; i++)
+      if (!(in->weight[i] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": weight must be non-negative");
   int dev = -1;
-  if (int rc = check_device_matrix("cox_baseline_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
-                                   in->n, in->p, &dev))
-    return rc;
+  if (int rc = cox_check_device("cox_baseline_device", c, &dev)) return rc;
   CoxOrder o;
   cox_order(in->time, in->status, in->weight, in->n, &o);
   std::vector<double> gt;
   std::vector<int> ends;
   cox_event_groups(o, in->time, in->n, &gt, &ends);
   int rc = 0;
-  if (!ends.empty()) {
-    HIPX(hipSetDevice(dev));
-    hipStream_t st = nullptr;
-    HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    {
-      Owner sc;
-      std::vector<double> hh;
-      rc = cox_baseline_run(sc, o, ends, hh, in, cumhaz, st);
-      if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and hh go after this)
-    }
-    (void)hipStreamDestroy(st);
-  }
+  if (!ends.empty())
+    rc = dev_call(dev, c.stream, [&](DevCall &dc) { return cox_baseline_run(dc.sc, o, ends, dc.h, in, cumhaz, dc.st); });
   if (!rc) {
     *n_times = (int)ends.size();
     std::copy(gt.begin(), gt.end(), times);
@@ -1955,9 +1783,8 @@ int bessx_cox_baseline_device(const bessx_cox_baseline_input *in, int *n_times, 
 int bessx_cox_survival_device(const bessx_cox_survival_input *in, double *out) {
   const std::string w("cox_survival_device");
   if (!in || !out) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (int rc = cox_surv_check_model("cox_survival_device", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                    in->p, in->cols, in->m, in->B))
-    return rc;
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_check("cox_survival_device", c, false, false)) return rc;
   if (in->T < 1 || !in->hg) return fail(BESSX_ERR_ARG, w + ": hg needs T >= 1 values");
   for (int j = 0; j < in->T; j++)
     if (!(in->hg[j] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": hg must be non-negative");
@@ -1966,37 +1793,22 @@ int bessx_cox_survival_device(const bessx_cox_survival_input *in, double *out) {
   if (in->out_row_stride < 0 || in->out_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
   if ((in->n > 1 && in->out_row_stride == 0) || (in->T > 1 && in->out_col_stride == 0))
     return fail(BESSX_ERR_ARG, w + ": out: a zero stride along an axis longer than 1");
-  if (int rc = need_device()) return rc;
   int dev = -1;
-  if (int rc = check_device_matrix("cox_survival_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
-                                   in->n, in->p, &dev))
-    return rc;
-  if (in->out_on_device) {
-    int od = -1;
-    if (int rc = check_device_matrix("cox_survival_device: out", out, BESSX_F64, in->out_row_stride, in->out_col_stride,
-                                     in->n, in->T, &od))
+  if (int rc = cox_check_device("cox_survival_device", c, &dev)) return rc;
+  if (in->out_on_device)
+    if (int rc = check_on_device("cox_survival_device", "out", out, BESSX_F64, in->out_row_stride, in->out_col_stride, in->n,
+                                 in->T, dev))
       return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, w + ": out is not on the device that owns x");
-  }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> tmp;
-    rc = cox_survival_run(sc, tmp, in, out, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and tmp go after this)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  return dev_call(dev, c.stream, [&](DevCall &dc) { return cox_survival_run(dc.sc, dc.h, in, out, dc.st); });
 }
 
 int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int T, int kind, int out_col_major, int repeats, double *stage_ms) {
   if (repeats < 1 || !stage_ms || T < 1 || (kind != BESSX_SURV_SURVIVAL && kind != BESSX_SURV_CUMHAZ))
     return fail(BESSX_ERR_ARG, "op_cox_surv_bench: bad arguments");
-  if (int rc = cox_surv_check_model("op_cox_surv_bench", x, dtype, row_stride, col_stride, n, p, cols, m, &kCoxZero))
+  if (!x) return fail(BESSX_ERR_ARG, "op_cox_surv_bench: null argument");
+  if (int rc = check_x_model("op_cox_surv_bench", x, dtype, row_stride >= 0 && col_stride >= 0, n, p, cols, m, &kCoxZero, 1,
+                             BESSX_LINK_IDENTITY, false))
     return rc;  // (B is the library's own)
   if (int rc = need_device()) return rc;
   int dev = -1;
@@ -2065,80 +1877,26 @@ int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long
 // ----------------------------------------------------------------------------------------------
 namespace {
 
-// everything about the call that needs no device
-int info_check_args(const char *who, const bessx_info_input *in, const double *loss, const double *sum_w) {
+// everything about a call that returns info and score which needs no device
+int info_check_args(const char *who, const GlmCall &c, const double *info, long long info_ld, const double *score,
+                    const double *loss, const double *sum_w) {
   const std::string w(who);
-  if (!in || !loss || !sum_w) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (!in->x || !in->info || !in->score) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->x_row_stride < 0 || in->x_col_stride < 0 || in->y_stride < 0 || in->weight_stride < 0)
-    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, in->link)) return rc;
-  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
-  for (int k = 0; k < in->m; k++)
-    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
-  if (!std::isfinite(in->coef0)) return fail(BESSX_ERR_ARG, w + ": coef0 must be finite");
-  if ((in->y_host != nullptr) == (in->y_dev != nullptr))
-    return fail(BESSX_ERR_ARG, w + ": give y as a host pointer or as a device view (one of the two)");
-  if (in->y_dev && in->y_dtype != BESSX_F64 && in->y_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": y: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->weight_host && in->weight_dev)
-    return fail(BESSX_ERR_ARG, w + ": give weight as a host pointer or as a device vector, not both");
-  if (in->weight_dev && in->weight_dtype != BESSX_F64 && in->weight_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": weight: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->info_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m + 1");
-  if (in->m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
-  return 0;
+  if (!loss || !sum_w || !info || !score) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = glm_check(who, c, true)) return rc;
+  if (info_ld < (long long)c.m + 1) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m + 1");
+  return check_m_max(w, c.m);
 }
 
-// the arguments as section 2d's helpers take them (R = 1, one column of y)
-bessx_eval_input info_as_eval(const bessx_info_input *in) {
-  bessx_eval_input e{};
-  e.x = in->x;
-  e.x_dtype = in->x_dtype;
-  e.x_row_stride = in->x_row_stride;
-  e.x_col_stride = in->x_col_stride;
-  e.n = in->n;
-  e.p = in->p;
-  e.cols = in->cols;
-  e.m = in->m;
-  e.B = in->beta;
-  e.coef0 = &in->coef0;
-  e.R = 1;
-  e.link = in->link;
-  e.y_host = in->y_host;
-  e.y_dev = in->y_dev;
-  e.y_dtype = in->y_dtype;
-  e.y_row_stride = in->y_stride;
-  e.y_cols = 1;
-  e.weight_host = in->weight_host;
-  e.weight_dev = in->weight_dev;
-  e.weight_dtype = in->weight_dtype;
-  e.weight_stride = in->weight_stride;
-  e.stream = in->stream;
-  return e;
-}
-
-// sc and h belong to the caller: they must outlive everything this function queues on st, also when it fails half way
-int info_run(Owner &sc, std::vector<double> &h, const bessx_info_input *in, double *loss, double *sum_w,
+int info_run(Owner &sc, std::vector<double> &h, const GlmCall &c, const bessx_info_input *in, double *loss, double *sum_w,
              hipStream_t st) {
-  // reads and writes come after everything the caller has queued on its stream so far
-  hipEvent_t ev = nullptr;
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
-  const bessx_eval_input e = info_as_eval(in);
-  const int f32 = in->x_dtype == BESSX_F32, m = in->m;
+  const int f32 = c.f32(), m = c.m;
   const size_t M = (size_t)m + 1;
   int *cols_d = nullptr;
   double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *res = nullptr, *stage = nullptr;
-  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
+  if (int rc = predict_upload_model(sc, c.cols, m, c.beta, c.coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
   EvalData d;
-  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
-  HIPX(sc.alloc(&work, (size_t)info_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, m, in->link,
-                                               d.w != nullptr)));
+  if (int rc = eval_stage_data(sc, c, st, &d)) return rc;
+  HIPX(sc.alloc(&work, (size_t)info_workspace(f32, c.rs, c.cs, c.n, m, c.link, d.w != nullptr)));
   HIPX(sc.alloc(&res, 3));
   double *info_d = in->info, *score_d = in->score;
   long long ld = in->info_ld;
@@ -2148,18 +1906,17 @@ int info_run(Owner &sc, std::vector<double> &h, const bessx_info_input *in, doub
     score_d = stage + M * M;
     ld = (long long)M;
   }
-  HIPX(launch_info(in->x, f32, in->x_row_stride, in->x_col_stride, in->n, cols_d, m, B_d, c_d, in->link, d, work, res,
-                   info_d, ld, score_d, st));
+  HIPX(launch_info(c.x, f32, c.rs, c.cs, c.n, cols_d, m, B_d, c_d, c.link, d, work, res, info_d, ld, score_d, st));
   h.resize(3 + (in->out_on_device ? 0 : M * M + M));
   HIPX(hipMemcpyAsync(h.data(), res, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (!in->out_on_device)
     HIPX(hipMemcpyAsync(h.data() + 3, stage, (M * M + M) * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPX(hipStreamSynchronize(st));
   *loss = h[0];
-  *sum_w = d.w ? h[2] : (double)in->n;
+  *sum_w = d.w ? h[2] : (double)c.n;
   if (!in->out_on_device) {
-    for (size_t j = 0; j < M; j++) std::copy(h.begin() + 3 + j * M, h.begin() + 3 + (j + 1) * M, in->info + j * in->info_ld);
-    std::copy(h.begin() + 3 + M * M, h.end(), in->score);
+    copy_out(h.data() + 3, M, M, in->info, in->info_ld);
+    copy_out(h.data() + 3 + M * M, M, 1, in->score, 0);
   }
   return 0;
 }
@@ -2177,57 +1934,31 @@ int bessx_info_workspace(int x_dtype, long long x_row_stride, long long x_col_st
   if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "info_workspace: empty matrix");
   if (link != BESSX_LINK_IDENTITY && link != BESSX_LINK_LOGISTIC && link != BESSX_LINK_POISSON)
     return fail(BESSX_ERR_ARG, "info_workspace: unknown link");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "info_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("info_workspace", m)) return rc;
   *doubles = info_workspace(x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, m, link, weighted != 0);
   info_split(n, m, rows_per_slab, slabs);
   return BESSX_OK;
 }
 
 int bessx_info_device(const bessx_info_input *in, double *loss, double *sum_w) {
-  if (int rc = info_check_args("info_device", in, loss, sum_w)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("info_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
-  if (in->y_dev) {
-    if (int rc = check_device_matrix("info_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: y is not on the device that owns x");
-  }
-  if (in->weight_dev) {
-    if (int rc = check_device_matrix("info_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
-                                     in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: weight is not on the device that owns x");
-  }
+  if (!in) return fail(BESSX_ERR_ARG, "info_device: null argument");
+  const GlmCall c = glm_call(in);
+  if (int rc = info_check_args("info_device", c, in->info, in->info_ld, in->score, loss, sum_w)) return rc;
+  int dev = -1;
+  if (int rc = glm_check_device("info_device", c, &dev)) return rc;
   if (in->out_on_device) {
-    if (int rc = check_device_matrix("info_device: info", in->info, BESSX_F64, in->info_ld, 1, in->m + 1, in->m + 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: info is not on the device that owns x");
-    if (int rc = check_device_matrix("info_device: score", in->score, BESSX_F64, 1, 0, in->m + 1, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "info_device: score is not on the device that owns x");
+    const int M = in->m + 1;
+    if (int rc = check_on_device("info_device", "info", in->info, BESSX_F64, in->info_ld, 1, M, M, dev)) return rc;
+    if (int rc = check_on_device("info_device", "score", in->score, BESSX_F64, 1, 0, M, 1, dev)) return rc;
   }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> h;
-    rc = info_run(sc, h, in, loss, sum_w, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and h go after this)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  return dev_call(dev, c.stream, [&](DevCall &dc) { return info_run(dc.sc, dc.h, c, in, loss, sum_w, dc.st); });
 }
 
 int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                         const int *cols, int m, int repeats, double *avg_ms, double *tflops) {
   if (!x || repeats < 1 || !avg_ms || !tflops) return fail(BESSX_ERR_ARG, "op_info_bench: bad arguments");
   if (int rc = predict_check_model("op_info_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_info_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_info_bench", m)) return rc;
   if (int rc = need_device()) return rc;
   int dev = -1;
   if (int rc = check_device_matrix("op_info_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
@@ -2247,20 +1978,16 @@ int bessx_op_info_bench(const void *x, int dtype, long long row_stride, long lon
   HIPX(hipMemcpy(v_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   const int f32 = dtype == BESSX_F32;
-  HIPX(launch_info_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d, g_d, part, out, (long long)M, out + M * M,
-                        nullptr));
-  HIPX(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < repeats; i++)
-    HIPX(launch_info_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d, g_d, part, out, (long long)M, out + M * M,
-                          nullptr));
-  HIPX(hipEventRecord(e1, nullptr));
-  HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
-  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  if (int rc = bt.run(repeats, &ms, [&]() -> int {
+        HIPX(launch_info_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d, g_d, part, out, (long long)M, out + M * M,
+                              nullptr));
+        return 0;
+      }))
+    return rc;
   *avg_ms = ms / repeats;
   *tflops = 2.0 * (double)n * (double)M * (double)(M + 1) * repeats / ((double)ms * 1e-3) / 1e12;
   return BESSX_OK;
@@ -2292,31 +2019,13 @@ int diag_count(unsigned kinds) {
 }
 
 // everything about the call that needs no device
-int diag_check_args(const char *who, const bessx_diag_input *in) {
+int diag_check_args(const char *who, const GlmCall &c, const bessx_diag_input *in) {
   const std::string w(who);
-  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (!in->x || !in->out) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->x_row_stride < 0 || in->x_col_stride < 0 || in->y_stride < 0 || in->weight_stride < 0)
-    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, in->link)) return rc;
-  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
-  for (int k = 0; k < in->m; k++)
-    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
-  if (!std::isfinite(in->coef0)) return fail(BESSX_ERR_ARG, w + ": coef0 must be finite");
-  if ((in->y_host != nullptr) == (in->y_dev != nullptr))
-    return fail(BESSX_ERR_ARG, w + ": give y as a host pointer or as a device view (one of the two)");
-  if (in->y_dev && in->y_dtype != BESSX_F64 && in->y_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": y: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->weight_host && in->weight_dev)
-    return fail(BESSX_ERR_ARG, w + ": give weight as a host pointer or as a device vector, not both");
-  if (in->weight_dev && in->weight_dtype != BESSX_F64 && in->weight_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": weight: dtype must be BESSX_F64 or BESSX_F32");
+  if (!in->out) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = glm_check(who, c, true)) return rc;
   if (in->kinds == 0 || (in->kinds & ~kDiagAll)) return fail(BESSX_ERR_ARG, w + ": kinds must be a non-empty set of BESSX_DIAG_* bits");
   if (in->out_ld < (long long)in->n) return fail(BESSX_ERR_ARG, w + ": out_ld must be at least n");
-  if (in->m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max(w, in->m)) return rc;
   if ((in->kinds & kDiagPhi) && !(std::isfinite(in->dispersion) && in->dispersion > 0.0))
     return fail(BESSX_ERR_ARG, w + ": dispersion must be finite and positive");
   if (in->kinds & kDiagLev) {
@@ -2337,24 +2046,8 @@ long long diag_doubles(long long n, int m, unsigned kinds) {
   return nv * ((int)v + (int)pear + (int)dev) + (v ? diag_factor_doubles(m) : 0);
 }
 
-// sc, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
-int diag_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const bessx_diag_input *in, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
-  bessx_eval_input e{};
-  e.n = in->n;
-  e.R = 1;
-  e.y_host = in->y_host;
-  e.y_dev = in->y_dev;
-  e.y_dtype = in->y_dtype;
-  e.y_row_stride = in->y_stride;
-  e.y_cols = 1;
-  e.weight_host = in->weight_host;
-  e.weight_dev = in->weight_dev;
-  e.weight_dtype = in->weight_dtype;
-  e.weight_stride = in->weight_stride;
+int diag_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const GlmCall &c, const bessx_diag_input *in,
+             hipStream_t st) {
   const int f32 = in->x_dtype == BESSX_F32, m = in->m, K = diag_count(in->kinds);
   const long long n = in->n, nv = (n + 1) / 2 * 2;
   const unsigned kinds = in->kinds;
@@ -2362,7 +2055,7 @@ int diag_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const b
   double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *stage = nullptr;
   if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
   EvalData d;
-  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  if (int rc = eval_stage_data(sc, c, st, &d)) return rc;
   bool need_v, tmp_pear, tmp_dev;
   diag_needs(kinds, &need_v, &tmp_pear, &tmp_dev);
   HIPX(sc.alloc(&work, (size_t)diag_doubles(n, m, kinds)));
@@ -2395,8 +2088,7 @@ int diag_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const b
     HIPX(hipMemcpyAsync(h.data(), stage, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPX(hipStreamSynchronize(st));
-  if (!in->out_on_device)
-    for (int k = 0; k < K; k++) std::copy(h.begin() + (size_t)k * n, h.begin() + (size_t)(k + 1) * n, in->out + k * in->out_ld);
+  if (!in->out_on_device) copy_out(h.data(), (size_t)n, (size_t)K, in->out, in->out_ld);
   return 0;
 }
 
@@ -2409,55 +2101,28 @@ int bessx_diag_workspace(int n, int m, unsigned kinds, long long *doubles) {
   if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "diag_workspace: empty matrix");
   if (kinds == 0 || (kinds & ~kDiagAll))
     return fail(BESSX_ERR_ARG, "diag_workspace: kinds must be a non-empty set of BESSX_DIAG_* bits");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "diag_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("diag_workspace", m)) return rc;
   *doubles = diag_doubles(n, m, kinds);
   return BESSX_OK;
 }
 
 int bessx_diag_device(const bessx_diag_input *in) {
-  if (int rc = diag_check_args("diag_device", in)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("diag_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
-  if (in->y_dev) {
-    if (int rc = check_device_matrix("diag_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "diag_device: y is not on the device that owns x");
-  }
-  if (in->weight_dev) {
-    if (int rc = check_device_matrix("diag_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
-                                     in->n, 1, &od))
+  if (!in) return fail(BESSX_ERR_ARG, "diag_device: null argument");
+  const GlmCall c = glm_call(in);
+  if (int rc = diag_check_args("diag_device", c, in)) return rc;
+  int dev = -1;
+  if (int rc = glm_check_device("diag_device", c, &dev)) return rc;
+  if (in->out_on_device)
+    if (int rc = check_on_device("diag_device", "out", in->out, BESSX_F64, in->out_ld, 1, diag_count(in->kinds), in->n, dev))
       return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "diag_device: weight is not on the device that owns x");
-  }
-  if (in->out_on_device) {
-    if (int rc = check_device_matrix("diag_device: out", in->out, BESSX_F64, in->out_ld, 1, diag_count(in->kinds), in->n,
-                                     &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "diag_device: out is not on the device that owns x");
-  }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> pk, h;
-    rc = diag_run(sc, pk, h, in, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  return dev_call(dev, c.stream, [&](DevCall &dc) { return diag_run(dc.sc, dc.pk, dc.h, c, in, dc.st); });
 }
 
 int bessx_op_diag_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                         const int *cols, int m, int repeats, double *avg_ms, double *tflops, double *bytes) {
   if (!x || repeats < 1 || !avg_ms || !tflops || !bytes) return fail(BESSX_ERR_ARG, "op_diag_bench: bad arguments");
   if (int rc = predict_check_model("op_diag_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_diag_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_diag_bench", m)) return rc;
   if (int rc = need_device()) return rc;
   int dev = -1;
   if (int rc = check_device_matrix("op_diag_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
@@ -2482,21 +2147,17 @@ int bessx_op_diag_bench(const void *x, int dtype, long long row_stride, long lon
   HIPX(hipMemcpy(v_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(r_d, r.data(), r.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   const int f32 = dtype == BESSX_F32;
   const size_t N = (size_t)n;
-  HIPX(launch_diag_lev(x, f32, row_stride, col_stride, n, cols_d, m, pk_d, v_d, r_d, r_d, 1.0, out, out + N, out + 2 * N,
-                       out + 3 * N, nullptr));
-  HIPX(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < repeats; i++)
-    HIPX(launch_diag_lev(x, f32, row_stride, col_stride, n, cols_d, m, pk_d, v_d, r_d, r_d, 1.0, out, out + N,
-                         out + 2 * N, out + 3 * N, nullptr));
-  HIPX(hipEventRecord(e1, nullptr));
-  HIPX(hipEventSynchronize(e1));
   float ms = 0.f;
-  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  if (int rc = bt.run(repeats, &ms, [&]() -> int {
+        HIPX(launch_diag_lev(x, f32, row_stride, col_stride, n, cols_d, m, pk_d, v_d, r_d, r_d, 1.0, out, out + N,
+                             out + 2 * N, out + 3 * N, nullptr));
+        return 0;
+      }))
+    return rc;
   const double Mpad = 16.0 * (double)((M + 15) / 16);
   *avg_ms = ms / repeats;
   *tflops = (double)n * Mpad * Mpad * repeats / ((double)ms * 1e-3) / 1e12;
@@ -2636,37 +2297,19 @@ int cox_info_launch(const void *x, int f32, long long rs, long long cs, int n, i
   return 0;
 }
 
-int cox_info_check_args(const char *who, const bessx_cox_info_input *in, const double *loglik, const double *n_events,
-                        const double *residual_sum) {
+// everything about a call that returns info and score which needs no device (*events: rows with status 1)
+int cox_info_check_args(const char *who, const CoxCall &c, const double *info, long long info_ld, const double *score,
+                        const double *loglik, const double *n_events, const double *residual_sum, int *events = nullptr) {
   const std::string w(who);
-  if (!in || !loglik || !n_events || !residual_sum) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (!in->x || !in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
-  for (int k = 0; k < in->m; k++)
-    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
-  if (in->ties != 0 && in->ties != 1) return fail(BESSX_ERR_ARG, w + ": ties must be 0 (order) or 1 (breslow)");
-  for (int i = 0; i < in->n; i++) {
-    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
-    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
-  }
-  if (in->m > 0 && (!in->info || !in->score)) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->info_ld < (long long)in->m) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m");
-  if (in->m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
-  return 0;
+  if (!loglik || !n_events || !residual_sum) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_check(who, c, true, true, events)) return rc;
+  if (c.m > 0 && (!info || !score)) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (info_ld < (long long)c.m) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m");
+  return check_m_max(w, c.m);
 }
 
-// sc, o, x and h belong to the caller: they must outlive everything this function queues on st, also when it fails
 int cox_info_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vector<double> &h,
                  const bessx_cox_info_input *in, double *loglik, double *residual_sum, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32;
   const size_t mm = (size_t)m * (size_t)m;
   CoxInfoDev c;
@@ -2690,9 +2333,8 @@ int cox_info_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vecto
   *loglik = h[0];
   *residual_sum = h[1];
   if (staged) {
-    for (size_t j = 0; j < (size_t)m; j++)
-      std::copy(h.begin() + 2 + j * m, h.begin() + 2 + (j + 1) * m, in->info + j * in->info_ld);
-    std::copy(h.begin() + 2 + mm, h.end(), in->score);
+    copy_out(h.data() + 2, (size_t)m, (size_t)m, in->info, in->info_ld);
+    copy_out(h.data() + 2 + mm, (size_t)m, 1, in->score, 0);
   }
   return 0;
 }
@@ -2706,8 +2348,7 @@ int bessx_cox_info_workspace(int n, int m, int n_event_rows, long long *doubles,
   if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_info_workspace: empty matrix");
   if (n_event_rows < 0 || n_event_rows > n)
     return fail(BESSX_ERR_ARG, "cox_info_workspace: n_event_rows must lie in [0, n]");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "cox_info_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("cox_info_workspace", m)) return rc;
   *doubles = cox_info_doubles(n, m, n_event_rows);
   rows_per_slab[0] = rows_per_slab[1] = 0;
   slabs[0] = slabs[1] = 0;
@@ -2719,34 +2360,22 @@ int bessx_cox_info_workspace(int n, int m, int n_event_rows, long long *doubles,
 }
 
 int bessx_cox_info_device(const bessx_cox_info_input *in, double *loglik, double *n_events, double *residual_sum) {
-  if (int rc = cox_info_check_args("cox_info_device", in, loglik, n_events, residual_sum)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("cox_info_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
+  if (!in) return fail(BESSX_ERR_ARG, "cox_info_device: null argument");
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_info_check_args("cox_info_device", c, in->info, in->info_ld, in->score, loglik, n_events, residual_sum))
     return rc;
+  int dev = -1;
+  if (int rc = cox_check_device("cox_info_device", c, &dev)) return rc;
   if (in->out_on_device && in->m > 0) {
-    if (int rc = check_device_matrix("cox_info_device: info", in->info, BESSX_F64, in->info_ld, 1, in->m, in->m, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "cox_info_device: info is not on the device that owns x");
-    if (int rc = check_device_matrix("cox_info_device: score", in->score, BESSX_F64, 1, 0, in->m, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "cox_info_device: score is not on the device that owns x");
+    if (int rc = check_on_device("cox_info_device", "info", in->info, BESSX_F64, in->info_ld, 1, in->m, in->m, dev)) return rc;
+    if (int rc = check_on_device("cox_info_device", "score", in->score, BESSX_F64, 1, 0, in->m, 1, dev)) return rc;
   }
   CoxOrder o;
   cox_order(in->time, in->status, in->weight, in->n, &o);
   CoxInfoOrder x;
   cox_info_order(&o, in->n, in->m, in->ties, &x);
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> h;
-    rc = cox_info_run(sc, o, x, h, in, loglik, residual_sum, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc and h go after this)
-  }
-  (void)hipStreamDestroy(st);
+  const int rc = dev_call(dev, c.stream,
+                          [&](DevCall &dc) { return cox_info_run(dc.sc, o, x, dc.h, in, loglik, residual_sum, dc.st); });
   if (!rc) *n_events = x.n_events;
   return rc;
 }
@@ -2756,8 +2385,7 @@ int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long
   if (!x || repeats < 1 || !stage_ms || !bytes || m < 1) return fail(BESSX_ERR_ARG, "op_cox_info_bench: bad arguments");
   if (int rc = predict_check_model("op_cox_info_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
   if (ties != 0 && ties != 1) return fail(BESSX_ERR_ARG, "op_cox_info_bench: ties must be 0 (order) or 1 (breslow)");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_info_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_cox_info_bench", m)) return rc;
   if (int rc = need_device()) return rc;
   int dev = -1;
   if (int rc = check_device_matrix("op_cox_info_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
@@ -2849,30 +2477,16 @@ void cox_diag_order(const CoxOrder &o, const CoxInfoOrder &x, int n, CoxDiagOrde
 }
 
 // everything about the call that needs no device; *J = rows with status 1
-int cox_diag_check_args(const char *who, const bessx_cox_diag_input *in, const int *n_event_rows, int *J) {
+int cox_diag_check_args(const char *who, const CoxCall &c, const bessx_cox_diag_input *in, const int *n_event_rows,
+                        int *J) {
   const std::string w(who);
-  if (!in || !n_event_rows) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (!in->x || !in->time || !in->status) return fail(BESSX_ERR_ARG, w + ": null argument");
-  if (in->x_dtype != BESSX_F64 && in->x_dtype != BESSX_F32)
-    return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
-  if (in->x_row_stride < 0 || in->x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
-  if (int rc = predict_check_model(who, in->n, in->p, in->cols, in->m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (in->m > 0 && !in->beta) return fail(BESSX_ERR_ARG, w + ": null argument (beta)");
-  for (int k = 0; k < in->m; k++)
-    if (!std::isfinite(in->beta[k])) return fail(BESSX_ERR_ARG, w + ": beta must be finite");
-  if (in->ties != 0 && in->ties != 1) return fail(BESSX_ERR_ARG, w + ": ties must be 0 (order) or 1 (breslow)");
-  int ev = 0;
-  for (int i = 0; i < in->n; i++) {
-    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
-    if (in->status[i] != 0.0 && in->status[i] != 1.0) return fail(BESSX_ERR_ARG, w + ": status must be 0 or 1");
-    ev += in->status[i] != 0.0;
-  }
-  *J = ev;
+  if (!n_event_rows) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_check(who, c, true, true, J)) return rc;
+  const int ev = *J;
   const unsigned kinds = in->kinds;
   if (kinds == 0 || (kinds & ~kCoxDiagAll))
     return fail(BESSX_ERR_ARG, w + ": kinds must be a non-empty set of BESSX_COX_DIAG_* bits");
-  if (in->m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, w + ": m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max(w, in->m)) return rc;
   const long long n = in->n, m = in->m;
   if (kinds & kCoxDiagRows) {
     if (!in->out_rows) return fail(BESSX_ERR_ARG, w + ": a requested kind needs out_rows");
@@ -2987,13 +2601,8 @@ int cox_diag_launch_L(const void *x, int f32, long long rs, long long cs, int n,
   return 0;
 }
 
-// sc, o, x, y, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
 int cox_diag_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const CoxDiagOrder &y, std::vector<double> &pk,
                  std::vector<double> &h, const bessx_cox_diag_input *in, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, J = x.J;
   const unsigned kinds = in->kinds;
   const size_t N = (size_t)n;
@@ -3053,17 +2662,10 @@ int cox_diag_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const CoxD
   }
   HIPX(hipStreamSynchronize(st));
   if (!in->out_on_device) {
-    for (int k = 0; k < K; k++)
-      std::copy(h.begin() + (size_t)k * N, h.begin() + (size_t)(k + 1) * N, in->out_rows + k * in->out_rows_ld);
-    for (size_t cc = 0; cc < (size_t)m; cc++) {
-      if (w_score)
-        std::copy(h.begin() + o_score + cc * N, h.begin() + o_score + (cc + 1) * N, in->out_score + cc * in->out_score_ld);
-      if (w_dfb)
-        std::copy(h.begin() + o_dfb + cc * N, h.begin() + o_dfb + (cc + 1) * N, in->out_dfbeta + cc * in->out_dfbeta_ld);
-      if (w_sch)
-        std::copy(h.begin() + o_sch + cc * (size_t)J, h.begin() + o_sch + (cc + 1) * (size_t)J,
-                  in->out_schoenfeld + cc * in->out_schoenfeld_ld);
-    }
+    copy_out(h.data(), N, (size_t)K, in->out_rows, in->out_rows_ld);
+    if (w_score) copy_out(h.data() + o_score, N, (size_t)m, in->out_score, in->out_score_ld);
+    if (w_dfb) copy_out(h.data() + o_dfb, N, (size_t)m, in->out_dfbeta, in->out_dfbeta_ld);
+    if (w_sch) copy_out(h.data() + o_sch, (size_t)J, (size_t)m, in->out_schoenfeld, in->out_schoenfeld_ld);
   }
   return 0;
 }
@@ -3079,20 +2681,18 @@ int bessx_cox_diag_workspace(int n, int m, int n_event_rows, unsigned kinds, lon
     return fail(BESSX_ERR_ARG, "cox_diag_workspace: n_event_rows must lie in [0, n]");
   if (kinds == 0 || (kinds & ~kCoxDiagAll))
     return fail(BESSX_ERR_ARG, "cox_diag_workspace: kinds must be a non-empty set of BESSX_COX_DIAG_* bits");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "cox_diag_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("cox_diag_workspace", m)) return rc;
   *doubles = cox_diag_doubles(n, m, n_event_rows, kinds);
   return BESSX_OK;
 }
 
 int bessx_cox_diag_device(const bessx_cox_diag_input *in, int *n_event_rows) {
+  if (!in) return fail(BESSX_ERR_ARG, "cox_diag_device: null argument");
+  const CoxCall c = cox_call(in);
   int J = 0;
-  if (int rc = cox_diag_check_args("cox_diag_device", in, n_event_rows, &J)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("cox_diag_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
+  if (int rc = cox_diag_check_args("cox_diag_device", c, in, n_event_rows, &J)) return rc;
+  int dev = -1;
+  if (int rc = cox_check_device("cox_diag_device", c, &dev)) return rc;
   if (in->out_on_device) {
     const unsigned kinds = in->kinds;
     struct {
@@ -3108,12 +2708,9 @@ int bessx_cox_diag_device(const bessx_cox_diag_input *in, int *n_event_rows) {
         {"out_schoenfeld", in->out_schoenfeld, in->out_schoenfeld_ld, in->m, J,
          in->m > 0 && J > 0 && (kinds & BESSX_COX_DIAG_SCHOENFELD)},
     };
-    for (const auto &t : outs) {
-      if (!t.on) continue;
-      const std::string nm = std::string("cox_diag_device: ") + t.what;
-      if (int rc = check_device_matrix(nm.c_str(), t.p, BESSX_F64, t.ld, 1, t.cols, t.rows, &od)) return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, nm + " is not on the device that owns x");
-    }
+    for (const auto &t : outs)
+      if (t.on)
+        if (int rc = check_on_device("cox_diag_device", t.what, t.p, BESSX_F64, t.ld, 1, t.cols, t.rows, dev)) return rc;
   }
   CoxOrder o;
   cox_order(in->time, in->status, in->weight, in->n, &o);
@@ -3121,17 +2718,8 @@ int bessx_cox_diag_device(const bessx_cox_diag_input *in, int *n_event_rows) {
   cox_info_order(&o, in->n, in->m, in->ties, &x);
   CoxDiagOrder y;
   cox_diag_order(o, x, in->n, &y);
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> pk, h;
-    rc = cox_diag_run(sc, o, x, y, pk, h, in, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
-  }
-  (void)hipStreamDestroy(st);
+  const int rc = dev_call(dev, c.stream,
+                          [&](DevCall &dc) { return cox_diag_run(dc.sc, o, x, y, dc.pk, dc.h, in, dc.st); });
   if (!rc) {
     *n_event_rows = x.J;
     if (in->event_rows) std::copy(y.evrow.begin(), y.evrow.end(), in->event_rows);
@@ -3144,8 +2732,7 @@ int bessx_op_cox_diag_bench(const void *x, int dtype, long long row_stride, long
   if (!x || repeats < 1 || !stage_ms || !bytes || m < 1) return fail(BESSX_ERR_ARG, "op_cox_diag_bench: bad arguments");
   if (int rc = predict_check_model("op_cox_diag_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
   if (ties != 0 && ties != 1) return fail(BESSX_ERR_ARG, "op_cox_diag_bench: ties must be 0 (order) or 1 (breslow)");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_diag_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_cox_diag_bench", m)) return rc;
   if (int rc = need_device()) return rc;
   int dev = -1;
   if (int rc = check_device_matrix("op_cox_diag_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
@@ -3346,14 +2933,9 @@ int cluster_check_args(const std::string &w, const long long *host, const void *
   return 0;
 }
 
-int cluster_check_device(const std::string &w, const void *dev, int dtype, long long stride, int n, int xdev) {
+int cluster_check_device(const char *who, const void *dev, int dtype, long long stride, int n, int xdev) {
   if (!dev) return 0;
-  int od = -1;
-  if (int rc = check_device_matrix((w + ": cluster").c_str(), dev, dtype == BESSX_I32 ? BESSX_F32 : BESSX_F64, stride, 0,
-                                   n, 1, &od))
-    return rc;
-  if (od != xdev) return fail(BESSX_ERR_ARG, w + ": cluster is not on the device that owns x");
-  return 0;
+  return check_on_device(who, "cluster", dev, dtype == BESSX_I32 ? BESSX_F32 : BESSX_F64, stride, 0, n, 1, xdev);
 }
 
 int meat_check_args(const bessx_meat_input *in, const int *n_clusters) {
@@ -3374,13 +2956,8 @@ int meat_check_args(const bessx_meat_input *in, const int *n_clusters) {
   return 0;
 }
 
-// sc, the plan and the vectors belong to the caller: they must outlive everything this function queues on st
 int meat_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std::vector<double> &h,
              const bessx_meat_input *in, int *n_clusters, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int f32 = in->x_dtype == BESSX_F32, m = in->m, n = in->n, icpt = in->intercept ? 1 : 0, Ms = m + icpt;
   const size_t M = (size_t)Ms, nv = ((size_t)n + 1) / 2 * 2;
   const long long *lab = nullptr;
@@ -3444,46 +3021,15 @@ int meat_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std::ve
   }
   HIPX(hipStreamSynchronize(st));
   if (!in->out_on_device) {
-    for (size_t j = 0; j < M; j++) std::copy(h.begin() + j * M, h.begin() + (j + 1) * M, in->meat + j * in->meat_ld);
-    std::copy(h.begin() + M * M, h.end(), in->sums);
+    copy_out(h.data(), M, M, in->meat, in->meat_ld);
+    copy_out(h.data() + M * M, M, 1, in->sums, 0);
   }
   return 0;
 }
 
-bessx_info_input sandwich_as_info(const bessx_sandwich_input *in) {
-  bessx_info_input e{};
-  e.x = in->x;
-  e.x_dtype = in->x_dtype;
-  e.x_row_stride = in->x_row_stride;
-  e.x_col_stride = in->x_col_stride;
-  e.n = in->n;
-  e.p = in->p;
-  e.cols = in->cols;
-  e.m = in->m;
-  e.beta = in->beta;
-  e.coef0 = in->coef0;
-  e.link = in->link;
-  e.y_host = in->y_host;
-  e.y_dev = in->y_dev;
-  e.y_dtype = in->y_dtype;
-  e.y_stride = in->y_stride;
-  e.weight_host = in->weight_host;
-  e.weight_dev = in->weight_dev;
-  e.weight_dtype = in->weight_dtype;
-  e.weight_stride = in->weight_stride;
-  e.info = in->info;
-  e.info_ld = in->info_ld;
-  e.score = in->score;
-  e.out_on_device = in->out_on_device;
-  e.stream = in->stream;
-  return e;
-}
-
-int sandwich_check_args(const bessx_sandwich_input *in, const double *loss, const double *sum_w, const int *n_clusters) {
+int sandwich_check_args(const GlmCall &c, const bessx_sandwich_input *in, const double *loss, const double *sum_w) {
   const std::string w("sandwich_device");
-  if (!in || !n_clusters) return fail(BESSX_ERR_ARG, w + ": null argument");
-  const bessx_info_input e = sandwich_as_info(in);
-  if (int rc = info_check_args("sandwich_device", &e, loss, sum_w)) return rc;
+  if (int rc = info_check_args("sandwich_device", c, in->info, in->info_ld, in->score, loss, sum_w)) return rc;
   if (!in->meat) return fail(BESSX_ERR_ARG, w + ": null argument");
   if (in->meat_ld < (long long)in->m + 1) return fail(BESSX_ERR_ARG, w + ": meat_ld must be at least m + 1");
   if (in->kind < BESSX_HC0 || in->kind > BESSX_HC3) return fail(BESSX_ERR_ARG, w + ": kind must be one of BESSX_HC0 .. BESSX_HC3");
@@ -3517,14 +3063,8 @@ long long sandwich_doubles(int f32, long long rs, long long cs, long long n, int
 }
 
 int sandwich_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std::vector<double> &pk,
-                 std::vector<double> &h, const bessx_sandwich_input *in, double *loss, double *sum_w, int *n_clusters,
-                 hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
-  const bessx_info_input ii = sandwich_as_info(in);
-  const bessx_eval_input e = info_as_eval(&ii);
+                 std::vector<double> &h, const GlmCall &c, const bessx_sandwich_input *in, double *loss, double *sum_w,
+                 int *n_clusters, hipStream_t st) {
   const int f32 = in->x_dtype == BESSX_F32, m = in->m, n = in->n, kind = in->kind;
   const long long rs = in->x_row_stride, cs = in->x_col_stride;
   const size_t M = (size_t)m + 1, nv = ((size_t)n + 1) / 2 * 2;
@@ -3535,7 +3075,7 @@ int sandwich_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std
   double *B_d = nullptr, *c_d = nullptr, *work = nullptr, *res = nullptr, *stage = nullptr, *uw = nullptr;
   if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
   EvalData d;
-  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  if (int rc = eval_stage_data(sc, c, st, &d)) return rc;
   HIPX(sc.alloc(&work, (size_t)info_workspace(f32, rs, cs, n, m, in->link, d.w != nullptr)));
   HIPX(sc.alloc(&res, 3));
   HIPX(sc.alloc(&uw, 2 * nv + M));
@@ -3586,11 +3126,9 @@ int sandwich_run(Owner &sc, ClusterPlan &plan, std::vector<long long> &lbuf, std
   *sum_w = d.w ? h[2] : (double)n;
   if (!in->out_on_device) {
     const double *hi = h.data() + 3, *hs = hi + M * M, *hm = hs + M;
-    for (size_t j = 0; j < M; j++) {
-      std::copy(hi + j * M, hi + (j + 1) * M, in->info + j * in->info_ld);
-      std::copy(hm + j * M, hm + (j + 1) * M, in->meat + j * in->meat_ld);
-    }
-    std::copy(hs, hs + M, in->score);
+    copy_out(hi, M, M, in->info, in->info_ld);
+    copy_out(hs, M, 1, in->score, 0);
+    copy_out(hm, M, M, in->meat, in->meat_ld);
   }
   return 0;
 }
@@ -3617,8 +3155,7 @@ int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_co
   if (n_clusters < 0 || n_clusters > n || max_cluster_rows < 0 || max_cluster_rows > n ||
       (n_clusters > 0 && max_cluster_rows < 1))
     return fail(BESSX_ERR_ARG, "sandwich_workspace: n_clusters and max_cluster_rows must lie in [0, n]");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "sandwich_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("sandwich_workspace", m)) return rc;
   *doubles = sandwich_doubles(x_dtype == BESSX_F32, x_row_stride, x_col_stride, n, m, link, weighted != 0, kind,
                               n_clusters, max_cluster_rows);
   info_split(n, m, rows_per_slab, slabs);
@@ -3633,83 +3170,45 @@ int bessx_sandwich_workspace(int x_dtype, long long x_row_stride, long long x_co
 int bessx_meat_device(const bessx_meat_input *in, int *n_clusters) {
   if (int rc = meat_check_args(in, n_clusters)) return rc;
   if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
+  int dev = -1;
   if (int rc = check_device_matrix("meat_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
                                    in->p, &dev))
     return rc;
-  if (in->u_dev) {
-    if (int rc = check_device_matrix("meat_device: u", in->u_dev, BESSX_F64, 1, 0, in->n, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "meat_device: u is not on the device that owns x");
-  }
+  if (in->u_dev)
+    if (int rc = check_on_device("meat_device", "u", in->u_dev, BESSX_F64, 1, 0, in->n, 1, dev)) return rc;
   if (int rc = cluster_check_device("meat_device", in->cluster_dev, in->cluster_dtype, in->cluster_stride, in->n, dev))
     return rc;
   if (in->out_on_device) {
     const int Ms = in->m + (in->intercept ? 1 : 0);
-    if (int rc = check_device_matrix("meat_device: meat", in->meat, BESSX_F64, in->meat_ld, 1, Ms, Ms, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "meat_device: meat is not on the device that owns x");
-    if (int rc = check_device_matrix("meat_device: sums", in->sums, BESSX_F64, 1, 0, Ms, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "meat_device: sums is not on the device that owns x");
+    if (int rc = check_on_device("meat_device", "meat", in->meat, BESSX_F64, in->meat_ld, 1, Ms, Ms, dev)) return rc;
+    if (int rc = check_on_device("meat_device", "sums", in->sums, BESSX_F64, 1, 0, Ms, 1, dev)) return rc;
   }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    ClusterPlan plan;
-    std::vector<long long> lbuf;
-    std::vector<double> h;
-    rc = meat_run(sc, plan, lbuf, h, in, n_clusters, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  ClusterPlan plan;
+  std::vector<long long> lbuf;
+  return dev_call(dev, static_cast<hipStream_t>(in->stream),
+                  [&](DevCall &dc) { return meat_run(dc.sc, plan, lbuf, dc.h, in, n_clusters, dc.st); });
 }
 
 int bessx_sandwich_device(const bessx_sandwich_input *in, double *loss, double *sum_w, int *n_clusters) {
-  if (int rc = sandwich_check_args(in, loss, sum_w, n_clusters)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("sandwich_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
-  if (in->y_dev) {
-    if (int rc = check_device_matrix("sandwich_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: y is not on the device that owns x");
-  }
-  if (in->weight_dev) {
-    if (int rc = check_device_matrix("sandwich_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
-                                     in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: weight is not on the device that owns x");
-  }
+  if (!in || !n_clusters) return fail(BESSX_ERR_ARG, "sandwich_device: null argument");
+  const GlmCall c = glm_call(in);
+  if (int rc = sandwich_check_args(c, in, loss, sum_w)) return rc;
+  int dev = -1;
+  if (int rc = glm_check_device("sandwich_device", c, &dev)) return rc;
   if (int rc = cluster_check_device("sandwich_device", in->cluster_dev, in->cluster_dtype, in->cluster_stride, in->n,
                                     dev))
     return rc;
   if (in->out_on_device) {
     const int M = in->m + 1;
-    if (int rc = check_device_matrix("sandwich_device: info", in->info, BESSX_F64, in->info_ld, 1, M, M, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: info is not on the device that owns x");
-    if (int rc = check_device_matrix("sandwich_device: score", in->score, BESSX_F64, 1, 0, M, 1, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: score is not on the device that owns x");
-    if (int rc = check_device_matrix("sandwich_device: meat", in->meat, BESSX_F64, in->meat_ld, 1, M, M, &od)) return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "sandwich_device: meat is not on the device that owns x");
+    if (int rc = check_on_device("sandwich_device", "info", in->info, BESSX_F64, in->info_ld, 1, M, M, dev)) return rc;
+    if (int rc = check_on_device("sandwich_device", "score", in->score, BESSX_F64, 1, 0, M, 1, dev)) return rc;
+    if (int rc = check_on_device("sandwich_device", "meat", in->meat, BESSX_F64, in->meat_ld, 1, M, M, dev)) return rc;
   }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    ClusterPlan plan;
-    std::vector<long long> lbuf;
-    std::vector<double> pk, h;
-    rc = sandwich_run(sc, plan, lbuf, pk, h, in, loss, sum_w, n_clusters, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  ClusterPlan plan;
+  std::vector<long long> lbuf;
+  return dev_call(dev, c.stream, [&](DevCall &dc) {
+    return sandwich_run(dc.sc, plan, lbuf, dc.pk, dc.h, c, in, loss, sum_w, n_clusters, dc.st);
+  });
 }
 
 int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
@@ -3717,8 +3216,7 @@ int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long
                             double *bytes) {
   if (!x || !cluster || repeats < 1 || !avg_ms || !bytes) return fail(BESSX_ERR_ARG, "op_sandwich_bench: bad arguments");
   if (int rc = predict_check_model("op_sandwich_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_sandwich_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_sandwich_bench", m)) return rc;
   if (int rc = need_device()) return rc;
   int dev = -1;
   if (int rc = check_device_matrix("op_sandwich_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
@@ -3738,20 +3236,15 @@ int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long
   if (m > 0) HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(u_d, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
-  auto run = [&]() {
-    return launch_sandwich_sums(x, f32, row_stride, col_stride, n, cols_d, m, 1, u_d, d.rowof, d.rptr, d.rdst, plan.NR,
-                                d.lptr, d.lgrp, plan.NL, d.S, d.ldS, d.P, d.ldP, nullptr);
-  };
-  HIPX(run());
-  HIPX(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < repeats; i++) HIPX(run());
-  HIPX(hipEventRecord(e1, nullptr));
-  HIPX(hipEventSynchronize(e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   float ms = 0.f;
-  HIPX(hipEventElapsedTime(&ms, e0, e1));
+  if (int rc = bt.run(repeats, &ms, [&]() -> int {
+        HIPX(launch_sandwich_sums(x, f32, row_stride, col_stride, n, cols_d, m, 1, u_d, d.rowof, d.rptr, d.rdst, plan.NR,
+                                  d.lptr, d.lgrp, plan.NL, d.S, d.ldS, d.P, d.ldP, nullptr));
+        return 0;
+      }))
+    return rc;
   *avg_ms = ms / repeats;
   // what the algorithm needs: the support and u once, S once
   *bytes = (double)n * m * (f32 ? 4.0 : 8.0) + 8.0 * (double)n + 8.0 * (double)Ms * (double)plan.G;
@@ -3765,47 +3258,16 @@ int bessx_op_sandwich_bench(const void *x, int dtype, long long row_stride, long
 // ----------------------------------------------------------------------------------------------
 namespace {
 
-// the fields bessx_addscore_input shares with bessx_info_input, as section 2g's helpers take them
-bessx_info_input addscore_as_info(const bessx_addscore_input *in) {
-  bessx_info_input a{};
-  a.x = in->x;
-  a.x_dtype = in->x_dtype;
-  a.x_row_stride = in->x_row_stride;
-  a.x_col_stride = in->x_col_stride;
-  a.n = in->n;
-  a.p = in->p;
-  a.cols = in->cols;
-  a.m = in->m;
-  a.beta = in->beta;
-  a.coef0 = in->coef0;
-  a.link = in->link;
-  a.y_host = in->y_host;
-  a.y_dev = in->y_dev;
-  a.y_dtype = in->y_dtype;
-  a.y_stride = in->y_stride;
-  a.weight_host = in->weight_host;
-  a.weight_dev = in->weight_dev;
-  a.weight_dtype = in->weight_dtype;
-  a.weight_stride = in->weight_stride;
-  a.info = in->info;
-  a.info_ld = in->info_ld;
-  a.score = in->score;
-  a.out_on_device = 0;
-  a.stream = in->stream;
-  return a;
-}
-
 int addscore_check_block(const std::string &w, int block) {
   if (block < 0 || block % 16) return fail(BESSX_ERR_ARG, w + ": candidate_block must be 0 or a positive multiple of 16");
   return 0;
 }
 
 // everything about the call that needs no device
-int addscore_check_args(const char *who, const bessx_addscore_input *in, const double *loss, const double *sum_w) {
+int addscore_check_args(const char *who, const GlmCall &c, const bessx_addscore_input *in, const double *loss,
+                        const double *sum_w) {
   const std::string w(who);
-  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
-  const bessx_info_input a = addscore_as_info(in);
-  if (int rc = info_check_args(who, &a, loss, sum_w)) return rc;
+  if (int rc = info_check_args(who, c, in->info, in->info_ld, in->score, loss, sum_w)) return rc;
   if (!in->u || !in->d) return fail(BESSX_ERR_ARG, w + ": null argument (u, d)");
   if (in->factor && (!in->s || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (s, a)");
   if (in->q < 1) return fail(BESSX_ERR_ARG, w + ": q must be at least 1");
@@ -3831,15 +3293,8 @@ int addscore_check_args(const char *who, const bessx_addscore_input *in, const d
   return 0;
 }
 
-// sc, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
-int addscore_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const bessx_addscore_input *in, double *loss,
-                 double *sum_w, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
-  const bessx_info_input ia = addscore_as_info(in);
-  const bessx_eval_input e = info_as_eval(&ia);
+int addscore_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, const GlmCall &c,
+                 const bessx_addscore_input *in, double *loss, double *sum_w, hipStream_t st) {
   const int f32 = in->x_dtype == BESSX_F32, m = in->m, q = in->q, block = in->candidate_block;
   const long long n = in->n, nv = (n + 1) / 2 * 2;
   const size_t M = (size_t)m + 1, Q = (size_t)q;
@@ -3852,7 +3307,7 @@ int addscore_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, con
          *work = nullptr, *ostage = nullptr;
   if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
   EvalData d;
-  if (int rc = eval_stage_data(sc, &e, st, &d)) return rc;
+  if (int rc = eval_stage_data(sc, c, st, &d)) return rc;
   // 1. info, score, loss and sum_w: launch_info as bessx_info_device runs it (the same bits)
   HIPX(sc.alloc(&iwork, (size_t)info_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, m, in->link,
                                                 d.w != nullptr)));
@@ -3896,8 +3351,8 @@ int addscore_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, con
   HIPX(hipStreamSynchronize(st));
   *loss = h[0];
   *sum_w = d.w ? h[2] : (double)in->n;
-  for (size_t j = 0; j < M; j++) std::copy(h.begin() + 3 + j * M, h.begin() + 3 + (j + 1) * M, in->info + j * in->info_ld);
-  std::copy(h.begin() + 3 + M * M, h.begin() + 3 + M * M + M, in->score);
+  copy_out(h.data() + 3, M, M, in->info, in->info_ld);
+  copy_out(h.data() + 3 + M * M, M, 1, in->score, 0);
   if (with_stat) {
     // r = inverse(info) U = R^T (R U), on the host in fp64
     const double *U0 = h.data() + 3 + M * M + M;
@@ -3933,9 +3388,7 @@ int addscore_run(Owner &sc, std::vector<double> &pk, std::vector<double> &h, con
       std::copy(h.begin() + 2 * Q, h.begin() + 3 * Q, in->s);
       std::copy(h.begin() + 3 * Q, h.begin() + 4 * Q, in->a);
     }
-    if (want_c)
-      for (size_t j = 0; j < Q; j++)
-        std::copy(h.begin() + 4 * Q + j * M, h.begin() + 4 * Q + (j + 1) * M, in->cross + j * in->cross_ld);
+    if (want_c) copy_out(h.data() + 4 * Q, M, Q, in->cross, in->cross_ld);
   }
   return 0;
 }
@@ -3951,8 +3404,7 @@ int bessx_addscore_workspace(int n, int m, int q, int candidate_block, long long
   if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "addscore_workspace: empty matrix");
   if (q < 1) return fail(BESSX_ERR_ARG, "addscore_workspace: q must be at least 1");
   if (int rc = addscore_check_block("addscore_workspace", candidate_block)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "addscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("addscore_workspace", m)) return rc;
   long long panel = 0;
   addscore_split(n, m, q, candidate_block, &panel, block_doubles, rows_per_slab, slabs, block, sum_depth);
   // (plus the block workspace of the score behind r, whose candidates are the constant column and the support)
@@ -3965,49 +3417,23 @@ int bessx_addscore_workspace(int n, int m, int q, int candidate_block, long long
 }
 
 int bessx_addscore_device(const bessx_addscore_input *in, double *loss, double *sum_w) {
-  if (int rc = addscore_check_args("addscore_device", in, loss, sum_w)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("addscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
-  if (in->y_dev) {
-    if (int rc = check_device_matrix("addscore_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: y is not on the device that owns x");
-  }
-  if (in->weight_dev) {
-    if (int rc = check_device_matrix("addscore_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
-                                     in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: weight is not on the device that owns x");
-  }
+  if (!in) return fail(BESSX_ERR_ARG, "addscore_device: null argument");
+  const GlmCall c = glm_call(in);
+  if (int rc = addscore_check_args("addscore_device", c, in, loss, sum_w)) return rc;
+  int dev = -1;
+  if (int rc = glm_check_device("addscore_device", c, &dev)) return rc;
   if (in->out_on_device) {
     double *const vec[4] = {in->u, in->d, in->factor ? in->s : nullptr, in->factor ? in->a : nullptr};
-    for (double *v : vec) {
-      if (!v) continue;
-      if (int rc = check_device_matrix("addscore_device: u, d, s, a", v, BESSX_F64, 1, 0, in->q, 1, &od)) return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: an output is not on the device that owns x");
-    }
-    if (in->cross) {
-      if (int rc = check_device_matrix("addscore_device: cross", in->cross, BESSX_F64, in->cross_ld, 1, in->q, in->m + 1,
-                                       &od))
+    for (double *v : vec)
+      if (v)
+        if (int rc = check_on_device("addscore_device", "u, d, s, a", v, BESSX_F64, 1, 0, in->q, 1, dev, "an output"))
+          return rc;
+    if (in->cross)
+      if (int rc = check_on_device("addscore_device", "cross", in->cross, BESSX_F64, in->cross_ld, 1, in->q, in->m + 1, dev))
         return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "addscore_device: cross is not on the device that owns x");
-    }
   }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> pk, h;
-    rc = addscore_run(sc, pk, h, in, loss, sum_w, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  return dev_call(dev, c.stream,
+                  [&](DevCall &dc) { return addscore_run(dc.sc, dc.pk, dc.h, c, in, loss, sum_w, dc.st); });
 }
 
 int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
@@ -4015,8 +3441,7 @@ int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long
                             double *stage_ms) {
   if (!x || repeats < 1 || !stage_ms || q < 1) return fail(BESSX_ERR_ARG, "op_addscore_bench: bad arguments");
   if (int rc = predict_check_model("op_addscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_addscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_addscore_bench", m)) return rc;
   if (int rc = addscore_check_block("op_addscore_bench", candidate_block)) return rc;
   if (!candidates && q != p) return fail(BESSX_ERR_ARG, "op_addscore_bench: without a candidate list q must be p");
   if (candidates)
@@ -4056,26 +3481,22 @@ int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long
   HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(work + blk - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   const int f32 = dtype == BESSX_F32;
-  auto run = [&](int stage) {
+  auto run = [&](int stage) -> int {
     if (stage == 0)
-      return launch_addscore_pack(x, f32, row_stride, col_stride, n, cols_d, m, q, candidate_block, v_d, g_d, P, nullptr);
-    return launch_addscore_blocks(x, f32, row_stride, col_stride, n, m, cand_d, q, candidate_block, P, work, 1, out,
-                                  out + Q, out + 2 * Q, out + 3 * Q, nullptr, 0, stage, nullptr);
+      HIPX(launch_addscore_pack(x, f32, row_stride, col_stride, n, cols_d, m, q, candidate_block, v_d, g_d, P, nullptr));
+    else
+      HIPX(launch_addscore_blocks(x, f32, row_stride, col_stride, n, m, cand_d, q, candidate_block, P, work, 1, out,
+                                  out + Q, out + 2 * Q, out + 3 * Q, nullptr, 0, stage, nullptr));
+    return 0;
   };
   // (stage 0 = pack, 1 = cross, 2 = finish, 3 = statistic; each over every block of candidates, in this order, so that
   // a later stage finds the earlier one's results of the last block)
   for (int stage = 0; stage < 4; stage++) {
-    HIPX(run(stage));  // the warm-up
-    HIPX(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < repeats; i++) HIPX(run(stage));
-    HIPX(hipEventRecord(e1, nullptr));
-    HIPX(hipEventSynchronize(e1));
     float ms = 0.f;
-    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    if (int rc = bt.run(repeats, &ms, [&]() { return run(stage); })) return rc;
     stage_ms[stage] = ms / repeats;
   }
   return BESSX_OK;
@@ -4088,37 +3509,11 @@ int bessx_op_addscore_bench(const void *x, int dtype, long long row_stride, long
 // ----------------------------------------------------------------------------------------------
 namespace {
 
-// the fields bessx_cox_addscore_input shares with bessx_cox_info_input, as section 2h's helpers take them
-bessx_cox_info_input cox_addscore_as_info(const bessx_cox_addscore_input *in) {
-  bessx_cox_info_input a{};
-  a.x = in->x;
-  a.x_dtype = in->x_dtype;
-  a.x_row_stride = in->x_row_stride;
-  a.x_col_stride = in->x_col_stride;
-  a.n = in->n;
-  a.p = in->p;
-  a.cols = in->cols;
-  a.m = in->m;
-  a.beta = in->beta;
-  a.time = in->time;
-  a.status = in->status;
-  a.weight = in->weight;
-  a.ties = in->ties;
-  a.info = in->info;
-  a.info_ld = in->info_ld;
-  a.score = in->score;
-  a.out_on_device = 0;
-  a.stream = in->stream;
-  return a;
-}
-
 // everything about the call that needs no device
-int cox_addscore_check_args(const char *who, const bessx_cox_addscore_input *in, const double *loglik,
+int cox_addscore_check_args(const char *who, const CoxCall &c, const bessx_cox_addscore_input *in, const double *loglik,
                             const double *n_events, const double *residual_sum) {
   const std::string w(who);
-  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
-  const bessx_cox_info_input a = cox_addscore_as_info(in);
-  if (int rc = cox_info_check_args(who, &a, loglik, n_events, residual_sum)) return rc;
+  if (int rc = cox_info_check_args(who, c, in->info, in->info_ld, in->score, loglik, n_events, residual_sum)) return rc;
   if (!in->u || !in->d || !in->t) return fail(BESSX_ERR_ARG, w + ": null argument (u, d, t)");
   if (in->factor && (!in->s || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (s, a)");
   if (in->q < 1) return fail(BESSX_ERR_ARG, w + ": q must be at least 1");
@@ -4230,13 +3625,8 @@ int cox_score_stage(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const v
   return 0;
 }
 
-// sc, o, x, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
 int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::vector<double> &pk, std::vector<double> &h,
                      const bessx_cox_addscore_input *in, double *loglik, double *residual_sum, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, q = in->q, block = in->candidate_block;
   const int ties = in->ties;
   const long long rs = in->x_row_stride, cs = in->x_col_stride;
@@ -4284,9 +3674,8 @@ int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::v
   HIPX(hipStreamSynchronize(st));
   *loglik = h[0];
   *residual_sum = h[1];
-  for (size_t j = 0; j < (size_t)m; j++)
-    std::copy(h.begin() + 2 + j * m, h.begin() + 2 + (j + 1) * m, in->info + j * in->info_ld);
-  if (m > 0) std::copy(h.begin() + 2 + mm, h.begin() + 2 + mm + (size_t)m, in->score);
+  copy_out(h.data() + 2, (size_t)m, (size_t)m, in->info, in->info_ld);
+  if (m > 0) copy_out(h.data() + 2 + mm, (size_t)m, 1, in->score, 0);
   if (with_stat) {
     // r = inverse(info) U = R^T (R U) on the host in fp64; the factor gets a zero row and column in front for the panel's
     // column 0 (v), whose cross product has no part in s and a
@@ -4335,9 +3724,7 @@ int cox_addscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, std::v
       std::copy(h.begin() + 3 * Q, h.begin() + 4 * Q, in->s);
       std::copy(h.begin() + 4 * Q, h.begin() + 5 * Q, in->a);
     }
-    if (want_c)
-      for (size_t j = 0; j < Q; j++)
-        std::copy(h.begin() + 5 * Q + j * M, h.begin() + 5 * Q + (j + 1) * M, in->cross + j * in->cross_ld);
+    if (want_c) copy_out(h.data() + 5 * Q, M, Q, in->cross, in->cross_ld);
   }
   return 0;
 }
@@ -4356,8 +3743,7 @@ int bessx_cox_addscore_workspace(int n, int m, int n_event_rows, int q, int cand
     return fail(BESSX_ERR_ARG, "cox_addscore_workspace: n_event_rows must lie in [0, n]");
   if (q < 1) return fail(BESSX_ERR_ARG, "cox_addscore_workspace: q must be at least 1");
   if (int rc = addscore_check_block("cox_addscore_workspace", candidate_block)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "cox_addscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("cox_addscore_workspace", m)) return rc;
   long long panel = 0, blk = 0, part = 0;
   addscore_split(n, m, q, candidate_block, &panel, &blk, &rows_per_slab[0], &slabs[0], block, sum_depth);
   cox_addscore_split(n, q, candidate_block, &part, &rows_per_slab[1], &slabs[1], &chain[1]);
@@ -4368,42 +3754,30 @@ int bessx_cox_addscore_workspace(int n, int m, int n_event_rows, int q, int cand
 
 int bessx_cox_addscore_device(const bessx_cox_addscore_input *in, double *loglik, double *n_events,
                               double *residual_sum) {
-  if (int rc = cox_addscore_check_args("cox_addscore_device", in, loglik, n_events, residual_sum)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("cox_addscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
-                                   in->n, in->p, &dev))
-    return rc;
+  if (!in) return fail(BESSX_ERR_ARG, "cox_addscore_device: null argument");
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_addscore_check_args("cox_addscore_device", c, in, loglik, n_events, residual_sum)) return rc;
+  int dev = -1;
+  if (int rc = cox_check_device("cox_addscore_device", c, &dev)) return rc;
   if (in->out_on_device) {
     const bool sa = in->factor || in->m == 0;
     double *const vec[5] = {in->u, in->d, in->t, sa ? in->s : nullptr, sa ? in->a : nullptr};
-    for (double *v : vec) {
-      if (!v) continue;
-      if (int rc = check_device_matrix("cox_addscore_device: u, d, t, s, a", v, BESSX_F64, 1, 0, in->q, 1, &od)) return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "cox_addscore_device: an output is not on the device that owns x");
-    }
-    if (in->cross) {
-      if (int rc = check_device_matrix("cox_addscore_device: cross", in->cross, BESSX_F64, in->cross_ld, 1, in->q,
-                                       in->m + 1, &od))
+    for (double *v : vec)
+      if (v)
+        if (int rc = check_on_device("cox_addscore_device", "u, d, t, s, a", v, BESSX_F64, 1, 0, in->q, 1, dev, "an output"))
+          return rc;
+    if (in->cross)
+      if (int rc = check_on_device("cox_addscore_device", "cross", in->cross, BESSX_F64, in->cross_ld, 1, in->q, in->m + 1,
+                                   dev))
         return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "cox_addscore_device: cross is not on the device that owns x");
-    }
   }
   CoxOrder o;
   cox_order(in->time, in->status, in->weight, in->n, &o);
   CoxInfoOrder x;
   cox_info_order(&o, in->n, in->m, in->ties, &x);
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> pk, h;
-    rc = cox_addscore_run(sc, o, x, pk, h, in, loglik, residual_sum, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
-  }
-  (void)hipStreamDestroy(st);
+  const int rc = dev_call(dev, c.stream, [&](DevCall &dc) {
+    return cox_addscore_run(dc.sc, o, x, dc.pk, dc.h, in, loglik, residual_sum, dc.st);
+  });
   if (!rc) *n_events = x.n_events;
   return rc;
 }
@@ -4413,8 +3787,7 @@ int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, 
                                 int repeats, double *stage_ms, double *bytes) {
   if (!x || repeats < 1 || !stage_ms || !bytes || q < 1) return fail(BESSX_ERR_ARG, "op_cox_addscore_bench: bad arguments");
   if (int rc = predict_check_model("op_cox_addscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_addscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_cox_addscore_bench", m)) return rc;
   if (int rc = addscore_check_block("op_cox_addscore_bench", candidate_block)) return rc;
   if (!candidates && q != p) return fail(BESSX_ERR_ARG, "op_cox_addscore_bench: without a candidate list q must be p");
   if (candidates)
@@ -4478,31 +3851,27 @@ int bessx_op_cox_addscore_bench(const void *x, int dtype, long long row_stride, 
   HIPX(hipMemcpy(Cc_d, Cc.data(), N * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(work + blk - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   const int f32 = dtype == BESSX_F32;
-  auto run = [&](int stage) {
-    if (stage == 0)
-      return launch_cox_addscore_pack(x, f32, row_stride, col_stride, n, cols_d, m, q, candidate_block, v_d, g_d, e_d, pos_d,
-                                      m > 0 ? A_d : nullptr, ldA, P, nullptr);
-    if (stage == 2 || stage == 3)
-      return launch_cox_addscore_quad(x, f32, row_stride, col_stride, n, cand_d, q, candidate_block, rowof_d, e_d, Cc_d,
-                                      part, out + 4 * Q, stage - 1, nullptr);
+  auto run = [&](int stage) -> int {
     const int only = stage == 1 ? 1 : (stage == 4 ? 2 : 3);
-    return launch_addscore_blocks(x, f32, row_stride, col_stride, n, m, cand_d, q, candidate_block, P, work, 1, out, out + Q,
-                                  out + 2 * Q, out + 3 * Q, nullptr, 0, only, nullptr);
+    if (stage == 0)
+      HIPX(launch_cox_addscore_pack(x, f32, row_stride, col_stride, n, cols_d, m, q, candidate_block, v_d, g_d, e_d, pos_d,
+                                    m > 0 ? A_d : nullptr, ldA, P, nullptr));
+    else if (stage == 2 || stage == 3)
+      HIPX(launch_cox_addscore_quad(x, f32, row_stride, col_stride, n, cand_d, q, candidate_block, rowof_d, e_d, Cc_d,
+                                    part, out + 4 * Q, stage - 1, nullptr));
+    else
+      HIPX(launch_addscore_blocks(x, f32, row_stride, col_stride, n, m, cand_d, q, candidate_block, P, work, 1, out, out + Q,
+                                  out + 2 * Q, out + 3 * Q, nullptr, 0, only, nullptr));
+    return 0;
   };
   // (each stage over every block of candidates, in an order in which a later stage finds the earlier one's results of
   // the last block)
   for (int stage = 0; stage < 6; stage++) {
-    HIPX(run(stage));  // the warm-up
-    HIPX(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < repeats; i++) HIPX(run(stage));
-    HIPX(hipEventRecord(e1, nullptr));
-    HIPX(hipEventSynchronize(e1));
     float ms = 0.f;
-    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    if (int rc = bt.run(repeats, &ms, [&]() { return run(stage); })) return rc;
     stage_ms[stage] = ms / repeats;
   }
   *bytes = (double)n * (double)q * (f32 ? 4.0 : 8.0);
@@ -4586,42 +3955,11 @@ void groupscore_cross_figures(long long n, int m, const GsPlan &pl, long long *w
   }
 }
 
-bessx_info_input groupscore_as_info(const bessx_groupscore_input *in) {
-  bessx_info_input a{};
-  a.x = in->x;
-  a.x_dtype = in->x_dtype;
-  a.x_row_stride = in->x_row_stride;
-  a.x_col_stride = in->x_col_stride;
-  a.n = in->n;
-  a.p = in->p;
-  a.cols = in->cols;
-  a.m = in->m;
-  a.beta = in->beta;
-  a.coef0 = in->coef0;
-  a.link = in->link;
-  a.y_host = in->y_host;
-  a.y_dev = in->y_dev;
-  a.y_dtype = in->y_dtype;
-  a.y_stride = in->y_stride;
-  a.weight_host = in->weight_host;
-  a.weight_dev = in->weight_dev;
-  a.weight_dtype = in->weight_dtype;
-  a.weight_stride = in->weight_stride;
-  a.info = in->info;
-  a.info_ld = in->info_ld;
-  a.score = in->score;
-  a.out_on_device = 0;
-  a.stream = in->stream;
-  return a;
-}
-
 // everything about the call that needs no device
-int groupscore_check_args(const char *who, const bessx_groupscore_input *in, const double *loss, const double *sum_w,
-                          GsPlan *pl) {
+int groupscore_check_args(const char *who, const GlmCall &c, const bessx_groupscore_input *in, const double *loss,
+                          const double *sum_w, GsPlan *pl) {
   const std::string w(who);
-  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
-  const bessx_info_input a = groupscore_as_info(in);
-  if (int rc = info_check_args(who, &a, loss, sum_w)) return rc;
+  if (int rc = info_check_args(who, c, in->info, in->info_ld, in->score, loss, sum_w)) return rc;
   if (!in->u || !in->D || !in->offsets) return fail(BESSX_ERR_ARG, w + ": null argument (u, D, offsets)");
   if (in->factor && (!in->S || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (S, a)");
   if (int rc = groupscore_plan(w, in->p, in->group_starts, in->n_groups, in->groups, in->n_tested, in->candidate_block, pl))
@@ -4694,15 +4032,8 @@ int groupscore_upload_plan(Owner &sc, const GsPlan &pl, hipStream_t st, GsDev *d
   return 0;
 }
 
-// sc, pl, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
-int groupscore_run(Owner &sc, const GsPlan &pl, std::vector<double> &pk, std::vector<double> &h,
+int groupscore_run(Owner &sc, const GsPlan &pl, std::vector<double> &pk, std::vector<double> &h, const GlmCall &c,
                    const bessx_groupscore_input *in, double *loss, double *sum_w, hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
-  const bessx_info_input ia = groupscore_as_info(in);
-  const bessx_eval_input e = info_as_eval(&ia);
   const int f32 = in->x_dtype == BESSX_F32, m = in->m;
   const long long n = in->n, nv = (n + 1) / 2 * 2;
   const size_t M = (size_t)m + 1, Q = (size_t)pl.q, TOT = (size_t)pl.offs[(size_t)pl.nt];
@@ -4719,7 +4050,7 @@ int groupscore_run(Owner &sc, const GsPlan &pl, std::vector<double> &pk, std::ve
   d.x = in->x, d.f32 = f32, d.rs = in->x_row_stride, d.cs = in->x_col_stride, d.n = n, d.m = m;
   if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &in->coef0, 1, st, &cols_d, &B_d, &c_d)) return rc;
   EvalData ed;
-  if (int rc = eval_stage_data(sc, &e, st, &ed)) return rc;
+  if (int rc = eval_stage_data(sc, c, st, &ed)) return rc;
   // 1. info, score, loss and sum_w: launch_info as bessx_info_device runs it (the same bits)
   HIPX(sc.alloc(&iwork, (size_t)info_workspace(f32, in->x_row_stride, in->x_col_stride, in->n, m, in->link,
                                                 ed.w != nullptr)));
@@ -4763,8 +4094,8 @@ int groupscore_run(Owner &sc, const GsPlan &pl, std::vector<double> &pk, std::ve
   HIPX(hipStreamSynchronize(st));
   *loss = h[0];
   *sum_w = ed.w ? h[2] : (double)in->n;
-  for (size_t j = 0; j < M; j++) std::copy(h.begin() + 3 + j * M, h.begin() + 3 + (j + 1) * M, in->info + j * in->info_ld);
-  std::copy(h.begin() + 3 + M * M, h.begin() + 3 + M * M + M, in->score);
+  copy_out(h.data() + 3, M, M, in->info, in->info_ld);
+  copy_out(h.data() + 3 + M * M, M, 1, in->score, 0);
   if (with_s) {
     // r = inverse(info) U = R^T (R U), on the host in fp64
     const double *U0 = h.data() + 3 + M * M + M;
@@ -4812,8 +4143,7 @@ int bessx_groupscore_workspace(int n, int p, int m, const int *group_starts, int
   if (!doubles || !block_doubles || !rows_per_slab || !slabs || !n_blocks || !band || !depth)
     return fail(BESSX_ERR_ARG, "groupscore_workspace: null argument");
   if (n < 1 || p < 1 || m < 0) return fail(BESSX_ERR_ARG, "groupscore_workspace: empty matrix");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "groupscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("groupscore_workspace", m)) return rc;
   GsPlan pl;
   if (int rc = groupscore_plan("groupscore_workspace", p, group_starts, n_groups, groups, n_tested, candidate_block, &pl))
     return rc;
@@ -4839,24 +4169,12 @@ int bessx_groupscore_workspace(int n, int p, int m, const int *group_starts, int
 }
 
 int bessx_groupscore_device(const bessx_groupscore_input *in, double *loss, double *sum_w) {
+  if (!in) return fail(BESSX_ERR_ARG, "groupscore_device: null argument");
+  const GlmCall c = glm_call(in);
   GsPlan pl;
-  if (int rc = groupscore_check_args("groupscore_device", in, loss, sum_w, &pl)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("groupscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,
-                                   in->p, &dev))
-    return rc;
-  if (in->y_dev) {
-    if (int rc = check_device_matrix("groupscore_device: y", in->y_dev, in->y_dtype, in->y_stride, 0, in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "groupscore_device: y is not on the device that owns x");
-  }
-  if (in->weight_dev) {
-    if (int rc = check_device_matrix("groupscore_device: weight", in->weight_dev, in->weight_dtype, in->weight_stride, 0,
-                                     in->n, 1, &od))
-      return rc;
-    if (od != dev) return fail(BESSX_ERR_ARG, "groupscore_device: weight is not on the device that owns x");
-  }
+  if (int rc = groupscore_check_args("groupscore_device", c, in, loss, sum_w, &pl)) return rc;
+  int dev = -1;
+  if (int rc = glm_check_device("groupscore_device", c, &dev)) return rc;
   if (in->out_on_device) {
     const long long tot = pl.offs[(size_t)pl.nt];
     double *const vec[4] = {in->u, in->factor ? in->a : nullptr, in->D, in->factor ? in->S : nullptr};
@@ -4864,23 +4182,13 @@ int bessx_groupscore_device(const bessx_groupscore_input *in, double *loss, doub
     for (int k = 0; k < 4; k++) {
       if (!vec[k]) continue;
       if (len[k] > 0x7fffffffLL) return fail(BESSX_ERR_ARG, "groupscore_device: too many block entries for device output");
-      if (int rc = check_device_matrix("groupscore_device: u, a, D, S", vec[k], BESSX_F64, 1, 0, (int)len[k], 1, &od))
+      if (int rc = check_on_device("groupscore_device", "u, a, D, S", vec[k], BESSX_F64, 1, 0, (int)len[k], 1, dev,
+                                   "an output"))
         return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "groupscore_device: an output is not on the device that owns x");
     }
   }
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> pk, h;
-    rc = groupscore_run(sc, pl, pk, h, in, loss, sum_w, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
-  }
-  (void)hipStreamDestroy(st);
-  return rc;
+  return dev_call(dev, c.stream,
+                  [&](DevCall &dc) { return groupscore_run(dc.sc, pl, dc.pk, dc.h, c, in, loss, sum_w, dc.st); });
 }
 
 int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
@@ -4888,8 +4196,7 @@ int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, lo
                               int n_tested, int candidate_block, int repeats, double *stage_ms) {
   if (!x || repeats < 1 || !stage_ms) return fail(BESSX_ERR_ARG, "op_groupscore_bench: bad arguments");
   if (int rc = predict_check_model("op_groupscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_groupscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_groupscore_bench", m)) return rc;
   GsPlan pl;
   if (int rc = groupscore_plan("op_groupscore_bench", p, group_starts, n_groups, groups, n_tested, candidate_block, &pl))
     return rc;
@@ -4929,9 +4236,8 @@ int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, lo
   HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(d.work_gs + work_gs - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   auto run = [&](int stage) -> int {
     if (stage == 0) {
       HIPX(launch_addscore_pack(x, d.f32, row_stride, col_stride, n, cols_d, m, pl.qmax, pl.block, d.v, g_d, d.P, nullptr));
@@ -4942,14 +4248,8 @@ int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, lo
   // (stage 0 = pack, then groupscore_blocks' steps 1 .. 6, each over every block, in an order in which a later stage
   // finds the earlier one's results of the last block)
   for (int stage = 0; stage < 7; stage++) {
-    if (int rc = run(stage)) return rc;  // the warm-up
-    HIPX(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < repeats; i++)
-      if (int rc = run(stage)) return rc;
-    HIPX(hipEventRecord(e1, nullptr));
-    HIPX(hipEventSynchronize(e1));
     float ms = 0.f;
-    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    if (int rc = bt.run(repeats, &ms, [&]() { return run(stage); })) return rc;
     stage_ms[stage] = ms / repeats;
   }
   return BESSX_OK;
@@ -4962,37 +4262,11 @@ int bessx_op_groupscore_bench(const void *x, int dtype, long long row_stride, lo
 // ----------------------------------------------------------------------------------------------
 namespace {
 
-// the fields bessx_cox_groupscore_input shares with bessx_cox_info_input, as section 2h's helpers take them
-bessx_cox_info_input cox_groupscore_as_info(const bessx_cox_groupscore_input *in) {
-  bessx_cox_info_input a{};
-  a.x = in->x;
-  a.x_dtype = in->x_dtype;
-  a.x_row_stride = in->x_row_stride;
-  a.x_col_stride = in->x_col_stride;
-  a.n = in->n;
-  a.p = in->p;
-  a.cols = in->cols;
-  a.m = in->m;
-  a.beta = in->beta;
-  a.time = in->time;
-  a.status = in->status;
-  a.weight = in->weight;
-  a.ties = in->ties;
-  a.info = in->info;
-  a.info_ld = in->info_ld;
-  a.score = in->score;
-  a.out_on_device = 0;
-  a.stream = in->stream;
-  return a;
-}
-
 // everything about the call that needs no device
-int cox_groupscore_check_args(const char *who, const bessx_cox_groupscore_input *in, const double *loglik,
-                              const double *n_events, const double *residual_sum, GsPlan *pl) {
+int cox_groupscore_check_args(const char *who, const CoxCall &c, const bessx_cox_groupscore_input *in,
+                              const double *loglik, const double *n_events, const double *residual_sum, GsPlan *pl) {
   const std::string w(who);
-  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
-  const bessx_cox_info_input a = cox_groupscore_as_info(in);
-  if (int rc = cox_info_check_args(who, &a, loglik, n_events, residual_sum)) return rc;
+  if (int rc = cox_info_check_args(who, c, in->info, in->info_ld, in->score, loglik, n_events, residual_sum)) return rc;
   if (!in->u || !in->D || !in->T || !in->offsets) return fail(BESSX_ERR_ARG, w + ": null argument (u, D, T, offsets)");
   if (in->factor && (!in->S || !in->a)) return fail(BESSX_ERR_ARG, w + ": null argument (S, a)");
   if (int rc = groupscore_plan(w, in->p, in->group_starts, in->n_groups, in->groups, in->n_tested, in->candidate_block, pl))
@@ -5048,14 +4322,9 @@ int cox_groupscore_tblocks(const GsPlan &pl, const GsDev &d, const CgsDev &t, do
   return 0;
 }
 
-// sc, o, x, pl, pk and h belong to the caller: they must outlive everything this function queues on st, also when it fails
 int cox_groupscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const GsPlan &pl, std::vector<double> &pk,
                        std::vector<double> &h, const bessx_cox_groupscore_input *in, double *loglik, double *residual_sum,
                        hipStream_t st) {
-  hipEvent_t ev = nullptr;  // reads and writes come after everything the caller has queued on its stream so far
-  HIPX(sc.event(&ev, hipEventDisableTiming));
-  HIPX(hipEventRecord(ev, static_cast<hipStream_t>(in->stream)));
-  HIPX(hipStreamWaitEvent(st, ev, 0));
   const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, ties = in->ties;
   const long long rs = in->x_row_stride, cs = in->x_col_stride;
   const size_t N = (size_t)n, mm = (size_t)m * (size_t)m, M = (size_t)m + 1, Q = (size_t)pl.q,
@@ -5103,9 +4372,8 @@ int cox_groupscore_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, cons
   HIPX(hipStreamSynchronize(st));
   *loglik = h[0];
   *residual_sum = h[1];
-  for (size_t j = 0; j < (size_t)m; j++)
-    std::copy(h.begin() + 2 + j * m, h.begin() + 2 + (j + 1) * m, in->info + j * in->info_ld);
-  if (m > 0) std::copy(h.begin() + 2 + mm, h.begin() + 2 + mm + (size_t)m, in->score);
+  copy_out(h.data() + 2, (size_t)m, (size_t)m, in->info, in->info_ld);
+  if (m > 0) copy_out(h.data() + 2 + mm, (size_t)m, 1, in->score, 0);
   if (with_s) {
     // r = inverse(info) U = R^T (R U) on the host in fp64; the factor gets section 2m's zero row and column in front
     const double *U0 = h.data() + 2 + mm + (size_t)m;
@@ -5167,8 +4435,7 @@ int bessx_cox_groupscore_workspace(int n, int p, int m, int n_event_rows, const 
   if (n < 1 || p < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_groupscore_workspace: empty matrix");
   if (n_event_rows < 0 || n_event_rows > n)
     return fail(BESSX_ERR_ARG, "cox_groupscore_workspace: n_event_rows must lie in [0, n]");
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "cox_groupscore_workspace: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("cox_groupscore_workspace", m)) return rc;
   GsPlan pl;
   if (int rc = groupscore_plan("cox_groupscore_workspace", p, group_starts, n_groups, groups, n_tested, candidate_block,
                                &pl))
@@ -5192,13 +4459,12 @@ int bessx_cox_groupscore_workspace(int n, int p, int m, int n_event_rows, const 
 
 int bessx_cox_groupscore_device(const bessx_cox_groupscore_input *in, double *loglik, double *n_events,
                                 double *residual_sum) {
+  if (!in) return fail(BESSX_ERR_ARG, "cox_groupscore_device: null argument");
+  const CoxCall c = cox_call(in);
   GsPlan pl;
-  if (int rc = cox_groupscore_check_args("cox_groupscore_device", in, loglik, n_events, residual_sum, &pl)) return rc;
-  if (int rc = need_device()) return rc;
-  int dev = -1, od = -1;
-  if (int rc = check_device_matrix("cox_groupscore_device: x", in->x, in->x_dtype, in->x_row_stride, in->x_col_stride,
-                                   in->n, in->p, &dev))
-    return rc;
+  if (int rc = cox_groupscore_check_args("cox_groupscore_device", c, in, loglik, n_events, residual_sum, &pl)) return rc;
+  int dev = -1;
+  if (int rc = cox_check_device("cox_groupscore_device", c, &dev)) return rc;
   if (in->out_on_device) {
     const long long tot = pl.offs[(size_t)pl.nt];
     const bool sa = in->factor || in->m == 0;
@@ -5208,26 +4474,18 @@ int bessx_cox_groupscore_device(const bessx_cox_groupscore_input *in, double *lo
       if (!vec[k]) continue;
       if (len[k] > 0x7fffffffLL)
         return fail(BESSX_ERR_ARG, "cox_groupscore_device: too many block entries for device output");
-      if (int rc = check_device_matrix("cox_groupscore_device: u, a, D, T, S", vec[k], BESSX_F64, 1, 0, (int)len[k], 1, &od))
+      if (int rc = check_on_device("cox_groupscore_device", "u, a, D, T, S", vec[k], BESSX_F64, 1, 0, (int)len[k], 1, dev,
+                                   "an output"))
         return rc;
-      if (od != dev) return fail(BESSX_ERR_ARG, "cox_groupscore_device: an output is not on the device that owns x");
     }
   }
   CoxOrder o;
   cox_order(in->time, in->status, in->weight, in->n, &o);
   CoxInfoOrder x;
   cox_info_order(&o, in->n, in->m, in->ties, &x);
-  HIPX(hipSetDevice(dev));
-  hipStream_t st = nullptr;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  int rc;
-  {
-    Owner sc;
-    std::vector<double> pk, h;
-    rc = cox_groupscore_run(sc, o, x, pl, pk, h, in, loglik, residual_sum, st);
-    if (rc) (void)hipStreamSynchronize(st);  // (nothing queued outlives the call's buffers: sc, pk and h go after this)
-  }
-  (void)hipStreamDestroy(st);
+  const int rc = dev_call(dev, c.stream, [&](DevCall &dc) {
+    return cox_groupscore_run(dc.sc, o, x, pl, dc.pk, dc.h, in, loglik, residual_sum, dc.st);
+  });
   if (!rc) *n_events = x.n_events;
   return rc;
 }
@@ -5238,8 +4496,7 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
                                   double *bytes) {
   if (!x || repeats < 1 || !stage_ms || !bytes) return fail(BESSX_ERR_ARG, "op_cox_groupscore_bench: bad arguments");
   if (int rc = predict_check_model("op_cox_groupscore_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
-  if (m + 1 > INFO_M_MAX)
-    return fail(BESSX_ERR_UNSUPPORTED, "op_cox_groupscore_bench: m + 1 must be at most " + std::to_string(INFO_M_MAX));
+  if (int rc = check_m_max("op_cox_groupscore_bench", m)) return rc;
   GsPlan pl;
   if (int rc = groupscore_plan("op_cox_groupscore_bench", p, group_starts, n_groups, groups, n_tested, candidate_block, &pl))
     return rc;
@@ -5301,9 +4558,8 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
   HIPX(hipMemcpy(t.cc, cc.data(), N * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipMemcpy(d.work_gs + work_gs - (long long)pk.size(), pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPX(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  HIPX(sc.event(&e0));
-  HIPX(sc.event(&e1));
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
   auto run = [&](int stage) -> int {
     if (stage == 0) {
       HIPX(launch_cox_addscore_pack(x, d.f32, row_stride, col_stride, n, cols_d, m, pl.qmax, pl.block, d.v, g_d, t.e, pos_d,
@@ -5316,14 +4572,8 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
   // (stage 0 = pack, then groupscore_blocks' steps 1 .. 6, then the band of T and its finish with the extraction, each
   // over every block, in an order in which a later stage finds the earlier one's results of the last block)
   for (int stage = 0; stage < 9; stage++) {
-    if (int rc = run(stage)) return rc;  // the warm-up
-    HIPX(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < repeats; i++)
-      if (int rc = run(stage)) return rc;
-    HIPX(hipEventRecord(e1, nullptr));
-    HIPX(hipEventSynchronize(e1));
     float ms = 0.f;
-    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    if (int rc = bt.run(repeats, &ms, [&]() { return run(stage); })) return rc;
     stage_ms[stage] = ms / repeats;
   }
   *bytes = (double)n * (double)pl.q * (dtype == BESSX_F32 ? 4.0 : 8.0);
