@@ -240,8 +240,8 @@ __global__ void __launch_bounds__(256) k_cov_fill_union(const CovUnion u, int re
 
 // ------------------------------------------------------------------------------------------
 // The panel kernel (k_cov_panel_dp): ONE 8-wave workgroup per compute unit over 128 streamed columns x 32 or 64
-// right-hand-side columns on one row slab, two LDS tiles, one barrier per chunk; big = 1: issued by the host for a
-// parked fit (no slot gate).
+// right-hand-side columns on one row slab, two LDS tiles, one barrier per chunk (between its two row steps); big = 1:
+// issued by the host for a parked fit (no slot gate).
 //
 // Global loads are coalesced the way the streaming score pass does it (16 threads x 2 rows cover a 32-row chunk of one
 // column) into registers, then to an LDS tile [column][row] (row stride padded by DP_PAD doubles: conflict-free
@@ -251,13 +251,18 @@ __global__ void __launch_bounds__(256) k_cov_fill_union(const CovUnion u, int re
 // (profiles/r05_panel_*, README).  What a kernel can still change is the data it moves per flop -- every workgroup
 // stages its own copy of the right-hand-side columns from L2 -- and the phases a workgroup stands still in.  Here:
 //   * 128 streamed columns per workgroup: half the right-hand-side traffic (L2 -> LDS) per byte of X of a 64-column block;
-//   * 8 waves, wave w multiplies streamed tile w with every right-hand-side tile: two waves per SIMD;
+//   * 8 waves, two per SIMD.  One group (NT = 2): wave w multiplies streamed tile w with both right-hand-side tiles.
+//     A pair (NT = 4): waves 0-3 take the first group's two tiles, waves 4-7 the second group's, and every wave
+//     multiplies TWO streamed tiles with them -- 2 x 2 products from 4 operand tiles (64 B per lane and row step) where
+//     1 x 4 took 5 (80 B): fewer LDS bytes per matrix instruction;
 //   * 32-row chunks, TWO LDS tiles: while chunk k is multiplied out of one, chunk k + 1 is written into the other --
 //     the stores sit between the matrix instructions of the chunk's first row step, the global loads of chunk k + 3
-//     between those of the second -- and ONE barrier per chunk;
-//   * operands of the next row step are read while the current one multiplies; loads run two to three chunks ahead in
-//     two register stages; every staging operation is unconditional (a branch around one costs the compiler its count
-//     of the loads in flight).
+//     between those of the second;
+//   * ONE barrier per chunk, BETWEEN the two row steps, and the operands of every row step read one step ahead: no
+//     wave waits for LDS behind a barrier (with the barrier at the chunk's end the first operand read of the next
+//     chunk stood between the barrier and the next matrix instruction, for both waves of a SIMD at once);
+//   * loads run two to three chunks ahead in two register stages; every staging operation is unconditional (a branch
+//     around one costs the compiler its count of the loads in flight).
 // NT = 2: one 32-column group per pass, NT = 4: a pair.  Partial sums: [group][slab][64-column group jg][streamed tile
 // 0..COV_NJ-1][right-hand-side tile 0..1][256] (what k_cov_reduce adds over the slabs).  104 KB of LDS at NT = 4, 87 KB
 // at NT = 2.
@@ -277,9 +282,13 @@ __device__ __forceinline__ void cov_dp_body(const double *__restrict__ X, const 
   constexpr int NL = NS + NT / 2;               // ... and of right-hand-side columns behind them
   constexpr int COLS = DP_SC + 16 * NT;         // columns staged per chunk
   constexpr size_t BUF = (size_t)COLS * DP_LD;  // doubles per LDS tile
+  constexpr int NA = NT / 2, NB = 2;            // streamed and right-hand-side tiles per wave
   const int njg2 = (njg + 1) / 2;               // workgroups per slab (128 streamed columns each)
   const int slab = blockIdx.x / njg2, jb = blockIdx.x - slab * njg2;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, q = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, q = lane >> 4;
+  // NT = 2: wave w multiplies streamed tile w with both right-hand-side tiles; NT = 4: streamed tiles 2 (w & 3) and
+  // 2 (w & 3) + 1 with the two tiles of group w >> 2
+  const int ta = NT == 4 ? 2 * (wv & 3) : wv, tb = NT == 4 ? 2 * (wv >> 2) : 0;
   const int ru = tid & 15, cbase = tid >> 4;    // 16 threads x 2 rows cover a chunk of one column; 32 columns per load
   // streamed columns jb * 128 + cbase + 32 i (a column beyond p re-reads the last existing one of its thread: its
   // products land in rows >= p, which the reduce kernel never stores)
@@ -307,54 +316,76 @@ __device__ __forceinline__ void cov_dp_body(const double *__restrict__ X, const 
     if (MASKED && (i) >= NS) v__ = v__ * ms;                                                                    \
     *reinterpret_cast<d2 *>((buf) + 2 * ru + (size_t)((i)*32 + cbase) * DP_LD) = v__;                           \
   } while (0)
-  d4 acc[NT];
+  d4 acc[NA * NB];
 #pragma unroll
-  for (int t = 0; t < NT; t++) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-  const size_t offa = (size_t)(wv * 16 + c) * DP_LD + 4 * q, offb = (size_t)(DP_SC + c) * DP_LD + 4 * q;
+  for (int t = 0; t < NA * NB; t++) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
+  const size_t offa = (size_t)(ta * 16 + c) * DP_LD + 4 * q, offb = (size_t)(DP_SC + tb * 16 + c) * DP_LD + 4 * q;
   struct Ops {
-    d2 a0, a1, b0[NT], b1[NT];
+    d2 a0[NA], a1[NA], b0[NB], b1[NB];
   };
-  auto read_ops = [&](const double *buf, int st, Ops &o) {
-    o.a0 = *reinterpret_cast<const d2 *>(buf + offa + 16 * st);
-    o.a1 = *reinterpret_cast<const d2 *>(buf + offa + 16 * st + 2);
+  // operands of one 16-row step; rows = the tile, + 16 for its second step
+  auto read_ops = [&](const double *rows, Ops &o) {
 #pragma unroll
-    for (int t = 0; t < NT; t++) {
-      o.b0[t] = *reinterpret_cast<const d2 *>(buf + offb + (size_t)t * 16 * DP_LD + 16 * st);
-      o.b1[t] = *reinterpret_cast<const d2 *>(buf + offb + (size_t)t * 16 * DP_LD + 16 * st + 2);
+    for (int a = 0; a < NA; a++) {
+      o.a0[a] = *reinterpret_cast<const d2 *>(rows + offa + (size_t)a * 16 * DP_LD);
+      o.a1[a] = *reinterpret_cast<const d2 *>(rows + offa + (size_t)a * 16 * DP_LD + 2);
+    }
+#pragma unroll
+    for (int t = 0; t < NB; t++) {
+      o.b0[t] = *reinterpret_cast<const d2 *>(rows + offb + (size_t)t * 16 * DP_LD);
+      o.b1[t] = *reinterpret_cast<const d2 *>(rows + offb + (size_t)t * 16 * DP_LD + 2);
     }
   };
-  // One chunk: DP_RB / 16 row steps of 4 x NT matrix instructions; staging operation n (0 .. 2 NL - 1: the NL stores of
-  // the next chunk into the other tile, then the NL loads of the chunk three ahead into the stage just stored) goes
-  // behind the matrix instructions, spread evenly.
-#define DP_CHUNK(cur, nxt, st, ms, rload)                                                                       \
+  // the 4 x NT matrix instructions of one row step; every accumulator adds its rows in ascending order
+#define DP_MFMA(o, j)                                                                                           \
   do {                                                                                                          \
-    Ops oa__, ob__;                                                                                             \
-    read_ops(cur, 0, oa__);                                                                                     \
-    int n__ = 0;                                                                                                \
-    _Pragma("unroll") for (int s__ = 0; s__ < DP_RB / 16; s__++) {                                            \
-      Ops &o__ = (s__ & 1) ? ob__ : oa__;                                                                       \
-      if (s__ + 1 < DP_RB / 16) read_ops(cur, s__ + 1, (s__ & 1) ? oa__ : ob__);                                \
-      __builtin_amdgcn_sched_barrier(0);                                                                        \
-      _Pragma("unroll") for (int j__ = 0; j__ < 4; j__++) {                                                   \
-        const double a__ = j__ == 0 ? o__.a0.x : (j__ == 1 ? o__.a0.y : (j__ == 2 ? o__.a1.x : o__.a1.y));       \
-        _Pragma("unroll") for (int t__ = 0; t__ < NT; t__++) {                                                \
-          const double b__ = j__ == 0 ? o__.b0[t__].x : (j__ == 1 ? o__.b0[t__].y : (j__ == 2 ? o__.b1[t__].x : o__.b1[t__].y)); \
-          acc[t__] = __builtin_amdgcn_mfma_f64_16x16x4f64(a__, b__, acc[t__], 0, 0, 0);                         \
-        }                                                                                                       \
-        /* staging operations due after this group of NT matrix instructions */                                 \
-        const int due__ = (2 * NL * (s__ * 4 + j__ + 1)) / (4 * (DP_RB / 16));                                  \
-        _Pragma("unroll") for (int k__ = 0; k__ < 2 * NL; k__++) {                                            \
-          if (k__ >= n__ && k__ < due__) {                                                                      \
-            if (k__ < NL)                                                                                       \
-              DP_STORE1(nxt, st, ms, k__);                                                                      \
-            else                                                                                                \
-              DP_LOAD1(st, ms, rload, k__ - NL);                                                                \
-          }                                                                                                     \
-        }                                                                                                       \
-        n__ = due__;                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                      \
+    _Pragma("unroll") for (int a__ = 0; a__ < NA; a__++) {                                                    \
+      const double av__ = (j) == 0 ? (o).a0[a__].x : ((j) == 1 ? (o).a0[a__].y : ((j) == 2 ? (o).a1[a__].x : (o).a1[a__].y)); \
+      _Pragma("unroll") for (int t__ = 0; t__ < NB; t__++) {                                                  \
+        const double bv__ = (j) == 0 ? (o).b0[t__].x : ((j) == 1 ? (o).b0[t__].y : ((j) == 2 ? (o).b1[t__].x : (o).b1[t__].y)); \
+        acc[a__ * NB + t__] = __builtin_amdgcn_mfma_f64_16x16x4f64(av__, bv__, acc[a__ * NB + t__], 0, 0, 0);   \
       }                                                                                                         \
     }                                                                                                           \
+  } while (0)
+  // One chunk (tile cur): DP_RB / 16 = 2 row steps of 4 x NT matrix instructions.  Staging operation n (0 .. 2 NL - 1) goes
+  // behind the matrix instructions, spread evenly: the NL stores of the next chunk into the other tile in the first step,
+  // the NL loads of the chunk three ahead into the stage just stored in the second.  The workgroup's ONE barrier per chunk
+  // stands BETWEEN the two steps, where every wave already holds the operands of the step that follows: the second
+  // step's were read (from cur) during the first, and the first step's of the next chunk are read from nxt -- complete
+  // since the barrier -- during the second.  No wave reads LDS between a barrier and its next matrix instruction.
+  // Hazards: tile nxt is stored after the barrier of the chunk before and read after this chunk's barrier.  A wave's
+  // last reads of a tile (the second step's operands, ob) are ISSUED before the barrier of that tile's chunk and USED
+  // behind it: it is __syncthreads() -- s_waitcnt lgkmcnt(0) in front of s_barrier -- that makes them complete before
+  // any wave stores into the tile again.  A bare s_barrier builtin in its place would let those stores overtake them.
+  static_assert(DP_RB == 32, "two row steps per chunk");
+#define DP_STEP(o, s, nxt, st, ms, rload)                                                                       \
+  do {                                                                                                          \
+    int n__ = (s) * NL;                                                                                         \
+    _Pragma("unroll") for (int j__ = 0; j__ < 4; j__++) {                                                     \
+      DP_MFMA(o, j__);                                                                                          \
+      /* staging operations due after this group of NT matrix instructions */                                   \
+      const int due__ = (2 * NL * ((s) * 4 + j__ + 1)) / (4 * (DP_RB / 16));                                    \
+      _Pragma("unroll") for (int k__ = 0; k__ < 2 * NL; k__++) {                                              \
+        if (k__ >= n__ && k__ < due__) {                                                                        \
+          if (k__ < NL)                                                                                         \
+            DP_STORE1(nxt, st, ms, k__);                                                                        \
+          else                                                                                                  \
+            DP_LOAD1(st, ms, rload, k__ - NL);                                                                  \
+        }                                                                                                       \
+      }                                                                                                         \
+      n__ = due__;                                                                                              \
+      __builtin_amdgcn_sched_barrier(0);                                                                        \
+    }                                                                                                           \
+  } while (0)
+#define DP_CHUNK(cur, nxt, st, ms, rload)                                                                       \
+  do {                                                                                                          \
+    read_ops((cur) + 16, ob);                                                                                   \
+    __builtin_amdgcn_sched_barrier(0);                                                                          \
+    DP_STEP(oa, 0, nxt, st, ms, rload);                                                                         \
+    __syncthreads();                                                                                            \
+    read_ops(nxt, oa);                                                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                                          \
+    DP_STEP(ob, 1, nxt, st, ms, rload);                                                                         \
   } while (0)
   double *buf0 = smem, *buf1 = smem + BUF;
   // a load beyond the slab's last chunk re-reads that last chunk (cache hits); the tile it is stored into is never multiplied
@@ -372,6 +403,8 @@ __device__ __forceinline__ void cov_dp_body(const double *__restrict__ X, const 
     for (int i = 0; i < NL; i++) DP_LOAD1(stA, mA, r2, i);
   }
   __syncthreads();
+  Ops oa, ob;
+  read_ops(buf0, oa);
   // chunk k is in tile k & 1; chunk k + 1 waits in a register stage (odd chunks in B, even ones in A); during chunk k
   // that stage is stored into the other tile and reloaded with chunk k + 3
   for (int k = 0; k < nchunk; k += 2) {
@@ -379,29 +412,29 @@ __device__ __forceinline__ void cov_dp_body(const double *__restrict__ X, const 
       const long rl = min(r_begin + (long)(k + 3) * DP_RB, r_last);
       DP_CHUNK(buf0, buf1, stB, mB, rl);
     }
-    __syncthreads();
     if (k + 1 >= nchunk) break;
     {
       const long rl = min(r_begin + (long)(k + 4) * DP_RB, r_last);
       DP_CHUNK(buf1, buf0, stA, mA, rl);
     }
-    __syncthreads();
   }
+#undef DP_STEP
 #undef DP_CHUNK
+#undef DP_MFMA
 #undef DP_LOAD1
 #undef DP_STORE1
-  // streamed tile wv of this workgroup = tile wv & 3 of the 64-column group 2 jb + (wv >> 2) in the partial-sum
-  // layout; the last workgroup's second half may lie beyond the last group
-  const int jg = 2 * jb + (wv >> 2);
-  if (jg < njg) {
-    const size_t tiles_per_slab = (size_t)njg * COV_NJ * 2;
-    double *out = part + ((size_t)slab * tiles_per_slab + (size_t)(jg * COV_NJ + (wv & 3)) * 2) * 256;
-    *reinterpret_cast<d4 *>(out + lane * 4) = acc[0];
-    *reinterpret_cast<d4 *>(out + 256 + lane * 4) = acc[1];
-    if (NT == 4) {
-      double *out2 = out + (size_t)nslab * tiles_per_slab * 256;
-      *reinterpret_cast<d4 *>(out2 + lane * 4) = acc[NT - 2];
-      *reinterpret_cast<d4 *>(out2 + 256 + lane * 4) = acc[NT - 1];
+  // streamed tile t of this workgroup = tile t & 3 of the 64-column group 2 jb + (t >> 2) in the partial-sum layout
+  // (the last workgroup's second half may lie beyond the last group); right-hand-side tile u = tile u & 1 of group u >> 1
+  const size_t tiles_per_slab = (size_t)njg * COV_NJ * 2;
+#pragma unroll
+  for (int a = 0; a < NA; a++) {
+    const int jg = 2 * jb + ((ta + a) >> 2);
+    if (jg < njg) {
+#pragma unroll
+      for (int t = 0; t < NB; t++) {
+        double *out = part + (((size_t)((tb + t) >> 1) * nslab + slab) * tiles_per_slab + (size_t)(jg * COV_NJ + ((ta + a) & 3)) * 2 + ((tb + t) & 1)) * 256;
+        *reinterpret_cast<d4 *>(out + lane * 4) = acc[a * NB + t];
+      }
     }
   }
 }
