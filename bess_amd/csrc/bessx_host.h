@@ -499,6 +499,7 @@ struct bessx_session {
   std::vector<double> x_mean_h, x_norm_h;
   std::vector<int> cv_fold;  // test fold of every row (bessx_session_get_cv_folds)
   std::vector<int> screen_groups, scr_gidx;  // screening with groups: kept original groups; group index of the kept data
+  std::vector<double> screen_scores;  // coef_norm of every ranked unit as the selection saw it (bessx_session_get_screening_scores)
   double y_mean_h = 0.0;
   double nullloss = 0.0;  // Data::get_nullloss (src/Data.h:120-130)
   // Algorithm state (reference member names in comments)

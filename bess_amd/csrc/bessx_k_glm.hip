@@ -667,8 +667,13 @@ __global__ void __launch_bounds__(256) k_screen_logit_pass(const double *__restr
     ll += (yi * log(Pi) + (1.0 - yi) * log(1.0 - Pi)) * wi;
     double W = Pi * (1.0 - Pi);
     const double z = eta + (yi - Pi) / W;
-    W = W * wi;
-    s0 += W;
+    {
+      // W rounded once, then summed: contracted to fma(W, wi, s0) the sum s0 differs from s1 and s2 in the last bits
+      // where they are equal by definition (an all-ones column), see det below
+#pragma clang fp contract(off)
+      W = W * wi;
+      s0 += W;
+    }
     s1 += W * xi;
     s2 += (W * xi) * xi;
     t0 += W * z;
@@ -692,7 +697,14 @@ __global__ void __launch_bounds__(256) k_screen_logit_pass(const double *__restr
       st[1] = st[3];
       st[4] = ll;
     }
-    const double det = s0 * s2 - s1 * s1;
+    // two rounded products: contracted to fma(s0, s2, -(s1 * s1)) the determinant of an exactly singular system (an
+    // all-ones column: s0 = s1 = s2) is the rounding error of s1 * s1 instead of 0, and the column scores at random
+    // where the reference's LDL^T gives it the slope 0 (src/logistic.cpp:130)
+    double det;
+    {
+#pragma clang fp contract(off)
+      det = s0 * s2 - s1 * s1;
+    }
     st[2] = (s2 * t0 - s1 * t1) / det;
     st[3] = (s0 * t1 - s1 * t0) / det;
   }

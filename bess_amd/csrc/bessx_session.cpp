@@ -865,6 +865,9 @@ int session_create_impl(bessx_session **out, const bessx_problem *pb, const DevX
     HIPT(hipStreamSynchronize(s->st));
     s->screen_map.assign((size_t)ss, 0);
     HIPT(hipMemcpy(s->screen_map.data(), keep, (size_t)ss * sizeof(int), hipMemcpyDeviceToHost));
+    // the keys the selection ranked, kept for bessx_session_get_screening_scores (one copy of nunits doubles)
+    s->screen_scores.assign((size_t)nunits, 0.0);
+    HIPT(hipMemcpy(s->screen_scores.data(), score, (size_t)nunits * sizeof(double), hipMemcpyDeviceToHost));
     int pk = ss;  // columns kept
     if (gscr) {
       // kept groups -> their columns (ascending), the group index of the kept data, always_select by kept-group rank
@@ -1876,6 +1879,13 @@ int bessx_session_get_screening_groups(const bessx_session *s, int *groups, int 
   if (!s) return 0;
   const int cnt = (int)s->screen_groups.size();
   for (int g = 0; g < cnt && g < cap && groups; g++) groups[g] = s->screen_groups[g];
+  return cnt;
+}
+
+int bessx_session_get_screening_scores(const bessx_session *s, double *scores, int cap) {
+  if (!s) return 0;
+  const int cnt = (int)s->screen_scores.size();
+  for (int u = 0; u < cnt && u < cap && scores; u++) scores[u] = s->screen_scores[u];
   return cnt;
 }
 

@@ -1104,6 +1104,12 @@ int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
 /* Screening with groups of size > 1: the kept ORIGINAL group numbers (ascending) = screening_A of the
  * reference for that case; 0 when the session was not screened by groups.  Returns the count, writes min(count, cap). */
 int bessx_session_get_screening_groups(const bessx_session *s, int *groups, int cap);
+/* coef_norm of src/screening.cpp:60-64 as max_k saw it: one marginal-fit score per ranked unit (original column, or
+ * original group when screening by groups), read-only.  DBL_MAX for an always_select unit, +inf for an all-zero LM
+ * column, 0.0 for a degenerate logistic / Cox unit; a group wider than the one-block kernels take carries the score
+ * of its sub-session fit.  Returns the number of ranked units (0 for a session created without screening), writes
+ * min(count, cap).  Costs session creation one device-to-host copy of that many doubles. */
+int bessx_session_get_screening_scores(const bessx_session *s, double *scores, int cap);
 /* 1 = streaming score pass, 2 = covariance updates: what bessx_problem.score_mode resolved to for this session. */
 int bessx_session_score_mode(const bessx_session *s);
 /* Diagnostics of the covariance form since the session was created: which = 0 fits that ran chained behind their

@@ -3,9 +3,11 @@ top-k, Gram, Cholesky solve, normalisation), each called alone, against NumPy / 
 inputs.  The Cox solver's state pass, scans, loss and score passes are called alone in tests/test_cox_ops_gpu.py; the
 logistic and Poisson solver's gradient / curvature pass (bessx_op_glm_gh) and one IRLS step by either route
 (bessx_op_glm_irls) in tests/test_glm_ops_gpu.py; the group-selection kernels (k_group_*: bessx_op_group_scores,
-bessx_op_group_lsq) in tests/test_group_ops_gpu.py.  The Newton-step kernels of the Cox fit, the Cox group branch as a whole
-(launch_cox_group_moments), the per-group screening fits (k_screen_*_group) and the other screening kernels, the
-covariance-form kernels and the big-system solvers have no such entry and are reached through sessions only."""
+bessx_op_group_lsq) in tests/test_group_ops_gpu.py.  The screening kernels (k_screen_*, per column and per group) have no
+entry of their own but are reached value by value: Session.screening_scores() returns the marginal-fit score of every
+ranked unit, and tests/test_screen_scores_gpu.py holds it to a longdouble reference.  The Newton-step kernels of the
+Cox fit, the Cox group branch as a whole (launch_cox_group_moments), the covariance-form kernels and the big-system
+solvers have no such entry and are reached through sessions only."""
 import numpy as np
 import pytest
 
