@@ -17,6 +17,8 @@
 // The candidates returned are the single chain's: same supports, iteration counts and criteria
 // (tests/test_kchunks_gpu.py; at full size tests/test_fullsize_gpu.py).
 #include "bessx_host.h"
+#include "bessx_kplan.h"
+#include <optional>
 
 namespace bessx {
 
@@ -41,7 +43,11 @@ struct SharedPass {
   hipEvent_t ev_out[RING] = {};
   XtvMc xq = {};
   CoxMc cq = {};
-  int rc = 0;  // first launch error (reported by the path)
+  std::atomic<int> rc{0};  // first error of a batch (reported by the path)
+  void fail_with(hipError_t e) {  // (the first error wins)
+    int none = 0;
+    if (e != hipSuccess) rc.compare_exchange_strong(none, (int)e);
+  }
   // statistics: HIP events around every launch on the pass stream, and how many gates were open in it
   bool timing = false;
   std::vector<hipEvent_t> tev;
@@ -176,11 +182,14 @@ static bool sp_prepare(bessx_session *s, SharedPass &sp) {
 // (under the rendezvous' lock) launch the n requests collected as batch g
 static void sp_launch(bessx_session *o, SharedPass &sp, int n, unsigned long long g) {
   std::lock_guard<std::mutex> lk(sp.launch_mu);
+  // after an error (a chain's vectors may not be ordered before the batch) nothing is launched any more: the path fails
+  // with sp.rc; ev_out is recorded all the same, so that no participant waits for an event that never comes
+  const bool dead = sp.rc.load() != 0;
   hipError_t e = hipSuccess;
-  for (int i = 0; i < n && e == hipSuccess; i++) e = hipStreamWaitEvent(sp.st, sp.ev_in[i], 0);
+  for (int i = 0; i < n && e == hipSuccess && !dead; i++) e = hipStreamWaitEvent(sp.st, sp.ev_in[i], 0);
   int *ran = nullptr;
   hipEvent_t ea = nullptr, eb = nullptr;
-  if (sp.timing && sp.launches < SharedPass::RAN_CAP) {
+  if (sp.timing && !dead && sp.launches < SharedPass::RAN_CAP) {
     while (sp.tev.size() < sp.tused + 2) {
       hipEvent_t ev = nullptr;
       if (sp.own.event(&ev) != hipSuccess) break;
@@ -194,7 +203,7 @@ static void sp_launch(bessx_session *o, SharedPass &sp, int n, unsigned long lon
     }
   }
   if (ea && e == hipSuccess) e = hipEventRecord(ea, sp.st);
-  if (e == hipSuccess) {
+  if (e == hipSuccess && !dead) {
     if (sp.kind == 2) {
       sp.cq.nc = n;
       sp.cq.ran = ran;
@@ -208,10 +217,8 @@ static void sp_launch(bessx_session *o, SharedPass &sp, int n, unsigned long lon
   if (eb && e == hipSuccess) e = hipEventRecord(eb, sp.st);
   if (e == hipSuccess) e = hipEventRecord(sp.ev_out[g % SharedPass::RING], sp.st);
   sp.launches++;
-  if (e != hipSuccess && sp.rc == 0) {
-    sp.rc = (int)e;
-    (void)hipGetLastError();
-  }
+  if (e != hipSuccess) (void)hipGetLastError();
+  sp.fail_with(e);
 }
 
 bool shared_pass_applies(const bessx_session *c) {
@@ -247,12 +254,12 @@ int shared_pass_submit(bessx_session *c, const double *v, const double *v2, doub
           q.slot[i] = slot;
         }
         e_in = hipEventRecord(sp.ev_in[i], c->st);  // everything this chain has queued so far: its vectors are ready
+        sp.fail_with(e_in);  // (before the batch is launched: sp_launch then launches nothing)
       },
       [&](int n, unsigned long long g) { sp_launch(o, sp, n, g); },
       [&](unsigned long long g) { e_out = hipStreamWaitEvent(c->st, sp.ev_out[g % SharedPass::RING], 0); });
-  if (e_in != hipSuccess || e_out != hipSuccess || sp.rc != 0)
-    return fail(BESSX_ERR_HIP, std::string("shared pass over X: ") +
-                                   hipGetErrorString(e_in != hipSuccess ? e_in : (e_out != hipSuccess ? e_out : (hipError_t)sp.rc)));
+  sp.fail_with(e_out);
+  if (const int rc = sp.rc.load()) return fail(BESSX_ERR_HIP, std::string("shared pass over X: ") + hipGetErrorString((hipError_t)rc));
   return 0;
 }
 
@@ -283,11 +290,11 @@ static void sp_round(KChains *k, const std::vector<bessx_session *> &who) {
 }
 
 // after the path (every chain's stream is idle): the launches' times into the session's score-pass statistics
+// (whether or not the device answers, the counters start over: nothing carries into the session's next path)
 static int sp_collect(bessx_session *s, SharedPass &sp) {
   if (!sp.st) return 0;
-  HIPX(hipStreamSynchronize(sp.st));
   const int nl = (int)(sp.tused / 2);
-  if (sp.timing && nl > 0) {
+  auto times = [&]() -> int {
     std::vector<int> ran((size_t)nl, 0);
     HIPX(hipMemcpy(ran.data(), sp.ran, (size_t)nl * sizeof(int), hipMemcpyDeviceToHost));
     for (int i = 0; i < nl; i++) {
@@ -299,14 +306,57 @@ static int sp_collect(bessx_session *s, SharedPass &sp) {
       s->k1_bytes += 8.0 * (double)s->n * (double)s->p;
       s->sp_chain_slots += ran[(size_t)i];
     }
-  }
+    return 0;
+  };
+  int rc = stream_wait_bounded(s, sp.st, "shared pass over X");
+  if (rc == 0 && sp.timing && nl > 0) rc = times();
   s->sp_launches += sp.launches;
   s->sp_partial += (long long)sp.rdv.partial;
   sp.rdv.partial = 0;
   sp.tused = 0;
   sp.launches = 0;
-  return 0;
+  return rc;
 }
+
+// The scope of a path's shared-pass round, opened where the chunk chains start: however the driver is left, no context
+// stays a member, sp.on is off and the pass stream's launches are collected.  close() is the regular way out and reports
+// the round's errors; on a way out that fails already the destructor does the same and keeps the first error's text.
+struct SharedPassScope {
+  bessx_session *s;
+  KChains *k;
+  bool open = true;
+  SharedPassScope(bessx_session *s_, KChains *k_, int C, bool lm_cov) : s(s_), k(k_) {
+    // the chains of the streaming forms share their passes over X (SharedPass above; test hook kchunks_shared_pass=0:
+    // a pass per chain, as in round 5)
+    SharedPass &sp = k->sp;
+    const char *eh = test_hook("kchunks_shared_pass");
+    sp.kind = s->model_type == 1 ? 0 : (s->model_type == 4 ? 2 : 1);
+    sp.cap = sp.kind == 2 ? COX_MC_MAX : XTV_MC_MAX;
+    sp.on = !lm_cov && C >= 2 && C <= sp.cap && (!eh || std::atoi(eh) != 0) &&
+            (sp.kind != 2 || s->cox.one_pass) && sp_prepare(s, sp);
+    sp.timing = s->timing;
+    sp.rc = 0;
+    sp.rdv.timeout_s = std::min(0.05, s->wait_deadline_s);
+    sp_round(k, std::vector<bessx_session *>(k->ctx.begin(), k->ctx.begin() + C));
+  }
+  int close() {
+    if (!open) return 0;
+    open = false;
+    for (bessx_session *c : k->ctx) c->kch_sp_member = false;
+    k->sp.on = false;
+    // (a lost host thread may still be inside a batch: neither the pass stream nor the rendezvous is touched -- what
+    // kchains_free leaks on purpose)
+    if (k->pool.broken) return 0;
+    if (int rc = sp_collect(s, k->sp)) return rc;
+    if (const int e = k->sp.rc.load()) return fail(BESSX_ERR_HIP, std::string("shared pass over X: ") + hipGetErrorString((hipError_t)e));
+    return 0;
+  }
+  ~SharedPassScope() {
+    const std::string first = g_err;
+    if (close() != 0) (void)hipGetLastError();
+    g_err = first;
+  }
+};
 
 static void kchains_leave(KChains *k, bool failed) { k->rdv.leave(failed); }
 
@@ -411,18 +461,17 @@ namespace {
 struct ChunkRun {  // one chunk's candidates, as sequential_path stores them
   int lo = 0, hi = 0, width = 0;
   std::vector<int> T0, iters, support;
-  std::vector<double> lam, loss, ic, coef0, beta, best_beta;
+  std::vector<double> lam, loss, ic, coef0, beta;
   bessx_path_result res = {};
   bessx_path_chain chain = {};
   std::vector<int> init_idx, last_idx;
   std::vector<double> init_val, last_val;
-  double init_coef0 = 0.0, last_coef0 = 0.0;
+  double last_coef0 = 0.0;
   int last_len = 0;
   int rc = 0;
   std::string err;  // (the message of a failure on a host thread: bessx_last_error is per thread)
-  long long fits = 0;
 
-  void shape(int lo_, int hi_, int width_, int p_full) {
+  void shape(int lo_, int hi_, int width_) {
     lo = lo_;
     hi = hi_;
     width = width_;
@@ -435,23 +484,45 @@ struct ChunkRun {  // one chunk's candidates, as sequential_path stores them
     coef0.assign(m, 0.0);
     support.assign(m * width, -1);
     beta.assign(m * width, 0.0);
-    best_beta.assign((size_t)p_full, 0.0);
     last_idx.assign((size_t)width, 0);
     last_val.assign((size_t)width, 0.0);
   }
-  void bind(bessx_path_result *r) {
-    *r = bessx_path_result();
-    r->beta = best_beta.data();
-    r->capacity = hi - lo;
-    r->cand_T0 = T0.data();
-    r->cand_lambda = lam.data();
-    r->cand_iters = iters.data();
-    r->cand_train_loss = loss.data();
-    r->cand_ic = ic.data();
-    r->cand_coef0 = coef0.data();
-    r->cand_support = support.data();
-    r->cand_beta = beta.data();
-    r->max_T0 = width;
+  // The chain link this run walks, into its own arrays: from the model (idx, val, c0) -- copied in: the link points at
+  // nothing its ChunkRun does not own --, the caches kept; with `stop`: until a candidate equals one of stop's first
+  // stop_rows rows (same support, coefficients to 1e-9).  The last model goes to last_idx / last_val.
+  void link(const int *idx, const double *val, int len, double c0, const ChunkRun *stop = nullptr, int stop_rows = 0) {
+    res = bessx_path_result();
+    res.capacity = hi - lo;
+    res.cand_T0 = T0.data();
+    res.cand_lambda = lam.data();
+    res.cand_iters = iters.data();
+    res.cand_train_loss = loss.data();
+    res.cand_ic = ic.data();
+    res.cand_coef0 = coef0.data();
+    res.cand_support = support.data();
+    res.cand_beta = beta.data();
+    res.max_T0 = width;
+    init_idx.assign(idx, idx + len);
+    init_val.assign(val, val + len);
+    chain = bessx_path_chain();
+    chain.init_idx = init_idx.data();
+    chain.init_val = init_val.data();
+    chain.init_len = len;
+    chain.init_coef0 = c0;
+    chain.keep_caches = 1;
+    if (stop) {
+      chain.stop_support = stop->support.data();
+      chain.stop_beta = stop->beta.data();
+      chain.stop_rows = stop_rows;
+      chain.stop_row_len = width;
+      chain.stop_rtol = 1e-9;
+    }
+    chain.last_idx = last_idx.data();
+    chain.last_val = last_val.data();
+    chain.last_cap = width;
+  }
+  void link_behind(const ChunkRun &pred, const ChunkRun *stop = nullptr, int stop_rows = 0) {  // from pred's last model
+    link(pred.last_idx.data(), pred.last_val.data(), pred.last_len, pred.last_coef0, stop, stop_rows);
   }
 };
 
@@ -830,57 +901,63 @@ int mc_contexts(bessx_session *s, int n) {
 
 bessx_session *mc_context(bessx_session *s, int i) { return s->kch->mc_ctx[(size_t)i]; }
 
-int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lambda, int ic_type,
-                            bessx_path_result *res, bessx_path_chain *link) {
-  const int C = chains_for(s, ns, link != nullptr, link && link->init_len > 0 && link->keep_caches);
-  HIPX(hipSetDevice(s->device));
-  KChains *k = s->kch;
-  if (!k || (int)k->ctx.size() < C || k->pool.broken)
-    return fail(BESSX_ERR_HIP, "chunk chains: not prepared (kchunks_prepare)");
-  // chunk r = candidates [bounds[r], bounds[r + 1]): equal lengths.  (Lengths weighted by the level -- a candidate costs
-  // more the larger its solve -- were measured on configs[1]: 1 + k / 40 ... 1 + k / 400 gave 15.0 ... 12.5 ms per path
-  // against 12.1 for equal chunks; where the boundaries fall relative to the fills matters more than the balance.)
-  // The IRLS / Newton families: the later chunks are shorter (their sub-model systems grow with the level: logistic
-  // 123 ms with lengths weighted 1 + k / 160, 129 ms with equal ones).
-  std::vector<int> bounds((size_t)C + 1, 0);
-  if (s->model_type == 1) {
-    for (int r = 1; r <= C; r++) bounds[r] = (int)((long)ns * r / C);
-  } else {
-    // (chains that share their passes advance in step, one PDAS iteration per shared pass: equal lengths -- with the
-    // weights of round 5 the first chunk, the longest, ended 30 % after the others; test hook kchunks_len_div)
+namespace {
+
+using Clock = std::chrono::steady_clock;
+double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+struct StartModel {
+  SparseVec b;
+  double c0 = 0.0;
+};
+
+// One chunked path: what the phases of sequential_path_chunked (below, in the order they run) hand on to each other.
+struct ChunkPath {
+  bessx_session *s;
+  KChains *k;
+  const int *seq;
+  int ns;
+  double lambda;
+  int ic_type, C, width;
+  bool lm_cov;
+  std::vector<int> bounds;        // plan: chunk r = candidates [bounds[r], bounds[r + 1])
+  CoarsePlan coarse;              // plan
+  bool staged = false;            // fill_stream
+  std::vector<StartModel> start;  // coarse_chain: the model chunk r starts from (none: cold)
+  std::vector<ChunkRun> run;      // chunk_round; candidates replaced by stitch_rounds, the end by give_up_tail
+  bool early_on = false;          // chunk_round -> stitch_rounds: the refits of round 1 that are there already
+  std::vector<ChunkRun> early_st;
+  std::vector<char> early_ok;
+  long long refits = 0, iters_path = 0;
+  int give_up_from = -1;  // stitch_rounds -> give_up_tail
+  Clock::time_point t_begin, t_coarse, t_chunks;
+
+  void plan() {
     const char *esh = test_hook("kchunks_shared_pass");
     double wdiv = (!esh || std::atoi(esh) != 0) ? 1e9 : 160.0;
     if (const char *ew = test_hook("kchunks_len_div")) wdiv = std::max(1.0, std::atof(ew));
-    double tot = 0.0;
-    std::vector<double> cum((size_t)ns + 1, 0.0);
-    for (int i = 0; i < ns; i++) {
-      tot += 1.0 + (double)seq[i] / wdiv;
-      cum[(size_t)i + 1] = tot;
-    }
-    for (int r = 1; r < C; r++) {
-      const int b = (int)(std::lower_bound(cum.begin(), cum.end(), tot * r / C) - cum.begin());
-      bounds[r] = std::min(std::max(b, bounds[r - 1] + 1), ns - (C - r));
-    }
-    bounds[C] = ns;
+    bounds = chunk_bounds(s->model_type == 1, seq, ns, C, wdiv);
+    // The coarse chain.  (LM only: it is what fills the shared cache.  The other families keep no cache: their chunks start
+    // cold, side by side -- a restricted fit is cold-started anyway, only the active set is warm -- and are stitched)
+    // At most COARSE_MAX fits (coarse_plan).  Starting points only: the stitch makes the path the single chain's.
+    constexpr int COARSE_MAX = 3;
+    int M = lm_cov ? std::min(C - 1, COARSE_MAX) : 0;  // (no cache to fill otherwise)
+    if (const char *ev = test_hook("kchunks_coarse")) M = std::max(0, std::min(M, std::atoi(ev)));  // (0: every chunk starts cold)
+    coarse = coarse_plan(C, M);
   }
-  const int width = res->max_T0 > 0 ? res->max_T0 : seq[ns - 1];
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double>(b - a).count();
-  };
-  const bool lm_cov = s->model_type == 1 && s->cov_mode;
+
   // Staged fills (bessx_sync.h: FillRendezvous, concurrent rounds; test hook kchunks_staged=0/1): a chain's fill writes
   // slots no other chain can see until its last launch publishes them, so nobody stands still for a fill.
-  bool staged = false;
-  if (lm_cov) {
-    const char *ev = test_hook("kchunks_staged");
-    staged = !ev || std::atoi(ev) != 0;  // (default; 0: round 4's rendezvous -- every chain stands still for a fill)
-  }
-  if (staged && !s->kch_slot_w && k->own.alloc(&s->kch_slot_w, (size_t)s->p) != hipSuccess) {
-    (void)hipGetLastError();
-    staged = false;
-  }
-  if (staged && !s->kch_fill_st && !s->kch_fill_tried) {
+  void fill_stream() {
+    if (lm_cov) {
+      const char *ev = test_hook("kchunks_staged");
+      staged = !ev || std::atoi(ev) != 0;  // (default; 0: round 4's rendezvous -- every chain stands still for a fill)
+    }
+    if (staged && !s->kch_slot_w && k->own.alloc(&s->kch_slot_w, (size_t)s->p) != hipSuccess) {
+      (void)hipGetLastError();
+      staged = false;
+    }
+    if (!staged || s->kch_fill_st || s->kch_fill_tried) return;
     s->kch_fill_tried = true;  // (decided once per session: no unit to leave out, or no such stream to be had)
     // the fills' stream: every compute unit but a few (test hook kchunks_reserve=count[:stride of the mask bits]; 0: the
     // fills run on the filling chain's own stream)
@@ -899,388 +976,258 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     }
     if (leave > 0 && !ctx_stream_create(s->device, &s->kch_fill_st, leave, stride)) s->kch_fill_st = nullptr;
   }
-  const auto t_begin = now();
-  {
+
+  // ---- 1. the coarse chain on the session's own state (the caller has just started the caches over)
+  int coarse_chain(bessx_path_chain *link) {
+    t_begin = Clock::now();
     const char *el = test_hook("kchunks_log");
     k->log_on = el && std::atoi(el) != 0;
     k->log_t0 = t_begin;
     k->log.clear();
-  }
-  std::vector<ChunkRun> run((size_t)C);
-  SparseVec link_init;
-  double link_c0 = 0.0;
-  if (link) {  // the model the whole link starts from: chunk 0's start, and the coarse chain's
-    for (int i = 0; i < link->init_len; i++) {
-      if (link->init_idx[i] < 0 || link->init_idx[i] >= s->p) return fail(BESSX_ERR_ARG, "chain: init index out of range");
-      link_init.idx.push_back(link->init_idx[i]);
-      link_init.val.push_back(link->init_val[i]);
+    run = std::vector<ChunkRun>((size_t)C);
+    start.assign((size_t)C, StartModel());
+    if (link) {  // the model the whole link starts from: chunk 0's start, and the coarse chain's
+      for (int i = 0; i < link->init_len; i++) {
+        if (link->init_idx[i] < 0 || link->init_idx[i] >= s->p) return fail(BESSX_ERR_ARG, "chain: init index out of range");
+        start[0].b.idx.push_back(link->init_idx[i]);
+        start[0].b.val.push_back(link->init_val[i]);
+      }
+      start[0].c0 = link->init_coef0;
+      link->stopped_at = -1;
     }
-    link_c0 = link->init_coef0;
-    run[0].init_idx = link_init.idx;
-    run[0].init_val = link_init.val;
-    run[0].init_coef0 = link_c0;
-    link->stopped_at = -1;
-  }
-  s->hint.on = false;
-  // The coarse chain.  (LM only: it is what fills the shared cache.  The other families keep no cache: their chunks start
-  // cold, side by side -- a restricted fit is cold-started anyway, only the active set is warm -- and are stitched)
-  // In front of the chunks: at most COARSE_MAX coarse fits, at chunk boundaries spread evenly over the path: with more
-  // chunks than that a chunk starts from the nearest coarse model below it (or cold, in front of the first one) -- its
-  // own first fits bridge the gap side by side with the other chunks, where a coarse fit per chunk (7 for 8 chunks:
-  // + 1.2 ms on configs[1]) would run before any of them.
-  // Starting points only: the stitch makes the path the single chain's.
-  constexpr int COARSE_MAX = 3;
-  int M = lm_cov ? std::min(C - 1, COARSE_MAX) : 0;  // (no cache to fill otherwise)
-  if (const char *ev = test_hook("kchunks_coarse")) M = std::max(0, std::min(M, std::atoi(ev)));  // (0: every chunk starts cold)
-  std::vector<int> coarse_at;  // coarse fit m (1-based) ends at the lower boundary of chunk coarse_at[m - 1]
-  {
-    int done_r = 0;
-    for (int j = 1; j <= M; j++) {
-      const int r = std::max(done_r + 1, (int)((long)C * j / (M + 1)));
-      if (r >= C) break;
-      coarse_at.push_back(r);
-      done_r = r;
-    }
-  }
-  std::vector<int> start_of((size_t)C, 0);  // chunk r starts from coarse fit start_of[r] (0: cold, or the link's model)
-  for (size_t m = 0; m < coarse_at.size(); m++)
-    for (int q = coarse_at[m]; q < C; q++) start_of[(size_t)q] = (int)m + 1;
-  struct CoarseModel {
-    std::vector<int> idx;
-    std::vector<double> val;
-    double c0 = 0.0;
-  };
-  std::vector<CoarseModel> coarse_model(coarse_at.size() + 1);
-  long long coarse_fits = 0;
-  {
-    // ---- 1. the coarse chain on the session's own state (the caller has just started the caches over)
-    SparseVec init = link_init;
-    double c0 = link_c0;
-    for (size_t m = 0; m < coarse_at.size(); m++) {
-      if (int rc = run_fit(s, seq[bounds[(size_t)coarse_at[m]] - 1], lambda, init, c0)) return rc;
-      init = s->beta;
-      c0 = s->coef0;
-      coarse_model[m + 1] = {init.idx, init.val, c0};
+    s->hint.on = false;
+    StartModel at = start[0];
+    for (size_t m = 0; m < coarse.coarse_at.size(); m++) {
+      if (int rc = run_fit(s, seq[bounds[(size_t)coarse.coarse_at[m]] - 1], lambda, at.b, at.c0)) return rc;
+      at = {s->beta, s->coef0};
+      for (int r = 0; r < C; r++)
+        if (coarse.start_of[(size_t)r] == (int)m + 1) start[(size_t)r] = at;
     }
     if (int rc = settle_device_chain(s)) return rc;
     HIPX(hipStreamSynchronize(s->st));  // the cache is complete before any chunk chain reads it
-    coarse_fits = s->n_fits;
-    for (int r = 0; r < C; r++)
-      if (start_of[(size_t)r] > 0) {
-        const CoarseModel &cm = coarse_model[(size_t)start_of[(size_t)r]];
-        run[(size_t)r].init_idx = cm.idx;
-        run[(size_t)r].init_val = cm.val;
-        run[(size_t)r].init_coef0 = cm.c0;
-      }
+    t_coarse = Clock::now();
+    return 0;
   }
-  const auto t_coarse = now();
+
   // The writer's slot map is a copy of the readers' whenever a round of chains starts (no fill is in flight between two
   // rounds; what ran in between -- the coarse chain -- filled through the readers' map)
-  auto writer_map_in_step = [&]() -> int {
+  int writer_map_in_step() {
     if (!staged) return 0;
     HIPX(hipMemcpyAsync(s->kch_slot_w, s->cov[0].slot_of, (size_t)s->p * sizeof(int), hipMemcpyDeviceToDevice, s->st));
     HIPX(hipStreamSynchronize(s->st));
     return 0;
-  };
-  if (int rc = writer_map_in_step()) return rc;
-  if (lm_cov)
-    for (bessx_session *c : k->ctx) c->cov[0].slot_w = staged ? s->kch_slot_w : nullptr;
-  // ---- 2. the chunks side by side, on a stream and a host thread each
-  for (int r = 0; r < C; r++) run[r].shape(bounds[r], bounds[r + 1], width, s->p_full);
-  kchains_round(k, C, staged);
-  {
-    // the chains of the streaming forms share their passes over X (SharedPass above; test hook kchunks_shared_pass=0:
-    // a pass per chain, as in round 5)
-    SharedPass &sp = k->sp;
-    const char *eh = test_hook("kchunks_shared_pass");
-    sp.kind = s->model_type == 1 ? 0 : (s->model_type == 4 ? 2 : 1);
-    sp.cap = sp.kind == 2 ? COX_MC_MAX : XTV_MC_MAX;
-    sp.on = !lm_cov && C >= 2 && C <= sp.cap && (!eh || std::atoi(eh) != 0) &&
-            (sp.kind != 2 || s->cox.one_pass) && sp_prepare(s, sp);
-    sp.timing = s->timing;
-    sp.rc = 0;
-    sp.rdv.timeout_s = std::min(0.05, s->wait_deadline_s);
-    sp_round(k, std::vector<bessx_session *>(k->ctx.begin(), k->ctx.begin() + C));
   }
+
+  // Begin the context, walk `count` candidates from the chunk's first as t's link describes, drain the stream; the
+  // thread's error text is kept in t.  keep_model: on the thread that has just walked c's own chunk (its device is set)
+  void walk(bessx_session *c, ChunkRun &t, int count, bool keep_model = false) {
+    t.rc = (keep_model || hipSetDevice(s->device) == hipSuccess) ? context_begin(c, keep_model) : fail(BESSX_ERR_HIP, "hipSetDevice");
+    c->timing = s->timing;  // (its fills count in the session's score-pass statistics)
+    if (t.rc == 0) t.rc = sequential_path(c, seq + t.lo, count, &lambda, 1, ic_type, 0, &t.res, &t.chain);
+    if (t.rc == 0 && hipStreamSynchronize(c->st) != hipSuccess) t.rc = fail(BESSX_ERR_HIP, "chunk chain: stream");
+    if (t.rc) t.err = g_err;
+    t.last_len = t.chain.last_len;
+    t.last_coef0 = t.chain.last_coef0;
+  }
+
+  int budget_of(int r) const { return std::max(8, (run[r].hi - run[r].lo) / 6); }
+
   // The stitch's first round, early (test hook kchunks_early_stitch=0 switches it off): the thread of chunk r - 1, when its
   // chunk is walked, re-fits the first candidates of chunk r from its own last model on its own (now idle) context while
   // the later chunks are still running -- what round 1 of the stitch below would do after ALL chunks have ended.  It
   // compares with the rows chunk r has stored by then (kchains_progress); a refit that could not see `budget` rows is
   // thrown away and done again in round 1.
-  bool early_on = C <= 9;
-  if (const char *ee = test_hook("kchunks_early_stitch")) early_on = early_on && std::atoi(ee) != 0;
-  std::vector<ChunkRun> early_st((size_t)C);
-  std::vector<char> early_ok((size_t)C, 0);
-  for (int r = 0; r < 10; r++) {
-    k->progress[r].store(0, std::memory_order_relaxed);
-    k->ended[r].store(0, std::memory_order_relaxed);
-  }
-  auto budget_of = [&](int r) { return std::max(8, (run[r].hi - run[r].lo) / 6); };
-  auto early_stitch = [&](int r) {  // on the thread and the context of chunk r - 1, which has just ended without error
+  void early_stitch(int r) {  // on the thread and the context of chunk r - 1, which has just ended without error
     bessx_session *c = k->ctx[(size_t)r - 1];
     ChunkRun &q = run[(size_t)r], &t = early_st[(size_t)r];
     const int want = std::min(q.hi - q.lo, budget_of(r));
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     sp_leave(c);  // (this wait is not for the device: the other chains' shared passes must not wait for this thread)
     while (k->progress[r].load(std::memory_order_acquire) < want && k->ended[r].load(std::memory_order_acquire) == 0) {
       kchains_safe_point(c);  // (a chain that waits for every other chain to stand still must not wait for this one)
       std::this_thread::sleep_for(std::chrono::microseconds(20));
-      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > s->wait_deadline_s) return;
+      if (secs(t0, Clock::now()) > s->wait_deadline_s) return;
     }
     if (k->ended[r].load(std::memory_order_acquire) == 2) return;
     const int rows = k->progress[r].load(std::memory_order_acquire);
     if (rows < want) return;
-    const ChunkRun &pr = run[(size_t)r - 1];
-    std::vector<int> pidx(pr.last_idx.begin(), pr.last_idx.begin() + pr.last_len);
-    std::vector<double> pval(pr.last_val.begin(), pr.last_val.begin() + pr.last_len);
-    t.shape(q.lo, q.hi, width, s->p_full);
-    t.bind(&t.res);
-    t.chain = bessx_path_chain();
-    t.chain.init_idx = pidx.data();
-    t.chain.init_val = pval.data();
-    t.chain.init_len = (int)pidx.size();
-    t.chain.init_coef0 = pr.last_coef0;
-    t.chain.keep_caches = 1;
-    t.chain.stop_support = q.support.data();
-    t.chain.stop_beta = q.beta.data();
-    t.chain.stop_rows = rows;  // (the rows chunk r has stored so far: final, it only appends)
-    t.chain.stop_row_len = width;
-    t.chain.stop_rtol = 1e-9;
-    t.chain.last_idx = t.last_idx.data();
-    t.chain.last_val = t.last_val.data();
-    t.chain.last_cap = width;
+    t.shape(q.lo, q.hi, width);
+    t.link_behind(run[(size_t)r - 1], &q, rows);  // (the rows chunk r has stored so far: final, it only appends)
     kchains_log(c, "early stitch of the next chunk", q.lo, rows);
     sp_join(c);
-    t.rc = context_begin(c, true);  // (its last fit's model IS the model the refit starts from)
-    if (t.rc == 0) t.rc = sequential_path(c, seq + q.lo, want, &lambda, 1, ic_type, 0, &t.res, &t.chain);
-    if (t.rc == 0 && hipStreamSynchronize(c->st) != hipSuccess) t.rc = fail(BESSX_ERR_HIP, "chunk chain: stream");
-    t.fits = c->n_fits;
-    t.chain.init_idx = nullptr;  // (locals of this function)
-    t.chain.init_val = nullptr;
+    walk(c, t, want, true);  // (its last fit's model IS the model the refit starts from)
     // a failure here is not the path's: round 1 of the stitch does this refit again
     if (t.rc == 0) early_ok[(size_t)r] = 1;
     else (void)hipGetLastError();
     kchains_log(c, "early stitch done", t.res.n_candidates, t.chain.stopped_at);
-  };
-  auto chunk_job = [&](int r) {
+  }
+
+  void chunk_job(int r) {
     if (r >= C) return;
     bessx_session *c = k->ctx[r];
     ChunkRun &q = run[r];
-    q.rc = 0;
-    if (q.rc == 0) q.rc = hipSetDevice(s->device) == hipSuccess ? context_begin(c) : fail(BESSX_ERR_HIP, "hipSetDevice");
-    c->timing = s->timing;  // (its fills count in the session's score-pass statistics)
+    const StartModel &m = start[(size_t)r];
+    q.link(m.b.idx.data(), m.b.val.data(), (int)m.b.idx.size(), m.c0);
     kchains_log(c, "chunk starts", q.lo, q.hi);
-    if (q.rc == 0) {
-      q.bind(&q.res);
-      q.chain = bessx_path_chain();
-      q.chain.init_idx = q.init_idx.data();
-      q.chain.init_val = q.init_val.data();
-      q.chain.init_len = (int)q.init_idx.size();
-      q.chain.init_coef0 = q.init_coef0;
-      q.chain.keep_caches = 1;
-      q.chain.last_idx = q.last_idx.data();
-      q.chain.last_val = q.last_val.data();
-      q.chain.last_cap = width;
-      q.rc = sequential_path(c, seq + q.lo, q.hi - q.lo, &lambda, 1, ic_type, 0, &q.res, &q.chain);
-      q.last_len = q.chain.last_len;
-      q.last_coef0 = q.chain.last_coef0;
-      q.fits += c->n_fits;
-    }
-    if (q.rc == 0 && hipStreamSynchronize(c->st) != hipSuccess) q.rc = fail(BESSX_ERR_HIP, "chunk chain: stream");
-    if (q.rc) q.err = g_err;
+    walk(c, q, q.hi - q.lo);
     kchains_log(c, "chunk ends", q.lo, q.hi);
     if (r < 10) k->ended[r].store(q.rc ? 2 : 1, std::memory_order_release);
     if (early_on && q.rc == 0 && r + 1 < C) early_stitch(r + 1);
     sp_leave(c);
     kchains_leave(k, q.rc != 0);
-  };
-  if (!k->pool.run(chunk_job, s->wait_deadline_s)) return fail(BESSX_ERR_HIP, "chunk chains: a host thread did not come back");
-  for (int r = 0; r < C; r++)
-    if (run[r].rc) return fail(run[r].rc, "chunk chain: " + run[r].err);
-  const auto t_chunks = now();
+  }
+
+  // ---- 2. the chunks side by side, on a stream and a host thread each.  Opens the shared-pass round: `scope`
+  int chunk_round(std::optional<SharedPassScope> &scope) {
+    if (int rc = writer_map_in_step()) return rc;
+    if (lm_cov)
+      for (bessx_session *c : k->ctx) c->cov[0].slot_w = staged ? s->kch_slot_w : nullptr;
+    for (int r = 0; r < C; r++) run[r].shape(bounds[r], bounds[r + 1], width);
+    kchains_round(k, C, staged);
+    scope.emplace(s, k, C, lm_cov);
+    early_on = C <= 9;
+    if (const char *ee = test_hook("kchunks_early_stitch")) early_on = early_on && std::atoi(ee) != 0;
+    early_st = std::vector<ChunkRun>((size_t)C);
+    early_ok.assign((size_t)C, 0);
+    for (int r = 0; r < 10; r++) {
+      k->progress[r].store(0, std::memory_order_relaxed);
+      k->ended[r].store(0, std::memory_order_relaxed);
+    }
+    if (!k->pool.run([this](int r) { chunk_job(r); }, s->wait_deadline_s))
+      return fail(BESSX_ERR_HIP, "chunk chains: a host thread did not come back");
+    for (int r = 0; r < C; r++)
+      if (run[r].rc) return fail(run[r].rc, "chunk chain: " + run[r].err);
+    t_chunks = Clock::now();
+    return 0;
+  }
+
+  void stitch_job(int r, ChunkRun &t) {  // chunk r again, from its predecessor's last model as it stands before this round
+    bessx_session *c = k->ctx[r];
+    const ChunkRun &q = run[r];
+    t.shape(q.lo, q.hi, width);
+    t.link_behind(run[r - 1], &q, q.hi - q.lo);
+    walk(c, t, std::min(q.hi - q.lo, budget_of(r)));
+    sp_leave(c);
+    kchains_leave(k, t.rc != 0);
+  }
+
   // ---- 3. the stitch, in rounds until no chunk's last model changed (bess_amd.dist.StitchedKPath.step)
   // A chunk whose refit has not met its own chain after `budget` candidates is on another trajectory than the warm
   // chain (designs with many near-equivalent supports: correlated columns, weak signal) -- re-walking it, and then its
   // successors round by round, would cost more than the one chain.  The stitch then gives up: everything from the first
   // unsettled chunk on is walked as ONE chain from its predecessor's last model, and the session's automatic choice
-  // becomes one chain.
-  std::vector<char> need((size_t)C, 1), changed((size_t)C, 0);
-  need[0] = 0;
-  long long refits = 0;
-  int give_up_from = -1;
-  for (int round = 1;; round++) {
-    std::vector<ChunkRun> st((size_t)C);
-    std::vector<char> have((size_t)C, 0);  // refits of this round that are there already (the early stitch)
-    if (round == 1)
-      for (int r = 1; r < C; r++)
-        if (early_ok[(size_t)r]) {
+  // becomes one chain.  (What a round decides: bessx_kplan.h, stitch_round.)
+  int stitch_rounds() {
+    std::vector<char> need((size_t)C, 1);
+    need[0] = 0;
+    for (int round = 1;; round++) {
+      std::vector<ChunkRun> st((size_t)C);
+      std::vector<char> todo((size_t)C, 0);  // the refits of this round that are not there already (the early stitch)
+      std::vector<bessx_session *> who;
+      for (int r = 1; r < C; r++) {
+        if (round == 1 && early_ok[(size_t)r]) {
           st[(size_t)r] = std::move(early_st[(size_t)r]);
-          have[(size_t)r] = 1;
+        } else if (need[r]) {
+          todo[(size_t)r] = 1;
+          who.push_back(k->ctx[r]);
         }
-    std::vector<std::vector<int>> pred_idx((size_t)C);
-    std::vector<std::vector<double>> pred_val((size_t)C);
-    std::vector<double> pred_c0((size_t)C, 0.0);
-    for (int r = 1; r < C; r++)
-      if (need[r]) {  // the predecessor's last model as it stands before this round
-        pred_idx[r].assign(run[r - 1].last_idx.begin(), run[r - 1].last_idx.begin() + run[r - 1].last_len);
-        pred_val[r].assign(run[r - 1].last_val.begin(), run[r - 1].last_val.begin() + run[r - 1].last_len);
-        pred_c0[r] = run[r - 1].last_coef0;
       }
-    auto stitch_job = [&](int r) {
-      if (r >= C || !need[r] || have[(size_t)r]) return;
-      bessx_session *c = k->ctx[r];
-      ChunkRun &q = run[r], &t = st[r];
-      t.shape(q.lo, q.hi, width, s->p_full);
-      t.bind(&t.res);
-      t.chain = bessx_path_chain();
-      t.chain.init_idx = pred_idx[r].data();
-      t.chain.init_val = pred_val[r].data();
-      t.chain.init_len = (int)pred_idx[r].size();
-      t.chain.init_coef0 = pred_c0[r];
-      t.chain.keep_caches = 1;
-      t.chain.stop_support = q.support.data();
-      t.chain.stop_beta = q.beta.data();
-      t.chain.stop_rows = q.hi - q.lo;
-      t.chain.stop_row_len = width;
-      t.chain.stop_rtol = 1e-9;
-      t.chain.last_idx = t.last_idx.data();
-      t.chain.last_val = t.last_val.data();
-      t.chain.last_cap = width;
-      t.rc = hipSetDevice(s->device) == hipSuccess ? context_begin(c) : fail(BESSX_ERR_HIP, "hipSetDevice");
-      c->timing = s->timing;
-      if (t.rc == 0)
-        t.rc = sequential_path(c, seq + q.lo, std::min(q.hi - q.lo, budget_of(r)), &lambda, 1, ic_type, 0, &t.res, &t.chain);
-      if (t.rc == 0 && hipStreamSynchronize(c->st) != hipSuccess) t.rc = fail(BESSX_ERR_HIP, "chunk chain: stream");
-      if (t.rc) t.err = g_err;
-      t.fits = c->n_fits;
-      sp_leave(c);
-      kchains_leave(k, t.rc != 0);
-    };
-    int active = 0;
-    for (int r = 1; r < C; r++) active += (need[r] && !have[(size_t)r]) ? 1 : 0;
-    if (active > 0) {
-      if (int rc = writer_map_in_step()) return rc;
-      kchains_round(k, active, staged);
-      {
-        std::vector<bessx_session *> who;
-        for (int r = 1; r < C; r++)
-          if (need[r] && !have[(size_t)r]) who.push_back(k->ctx[r]);
+      if (!who.empty()) {
+        if (int rc = writer_map_in_step()) return rc;
+        kchains_round(k, (int)who.size(), staged);
         sp_round(k, who);
+        auto job = [&](int r) {
+          if (r < C && todo[(size_t)r]) stitch_job(r, st[(size_t)r]);
+        };
+        if (!k->pool.run(job, s->wait_deadline_s)) return fail(BESSX_ERR_HIP, "chunk chains: a host thread did not come back");
       }
-      if (!k->pool.run(stitch_job, s->wait_deadline_s)) return fail(BESSX_ERR_HIP, "chunk chains: a host thread did not come back");
-    }
-    bool any = false;
-    for (int r = 1; r < C; r++) {
-      changed[r] = 0;
-      if (!need[r]) continue;
-      ChunkRun &q = run[r], &t = st[r];
-      if (t.rc) return fail(t.rc, "chunk chain (stitch): " + t.err);
-      const int m = std::min(t.res.n_candidates, q.hi - q.lo);
-      for (int i = 0; i < m; i++) {  // what was walked before the merge point is replaced
-        q.T0[i] = t.T0[i];
-        q.iters[i] = t.iters[i];
-        q.lam[i] = t.lam[i];
-        q.loss[i] = t.loss[i];
-        q.ic[i] = t.ic[i];
-        q.coef0[i] = t.coef0[i];
-        std::copy(t.support.begin() + (size_t)i * width, t.support.begin() + (size_t)(i + 1) * width,
-                  q.support.begin() + (size_t)i * width);
-        std::copy(t.beta.begin() + (size_t)i * width, t.beta.begin() + (size_t)(i + 1) * width,
-                  q.beta.begin() + (size_t)i * width);
+      std::vector<StitchRefit> refit((size_t)C);
+      for (int r = 1; r < C; r++) {
+        if (!need[r]) continue;
+        ChunkRun &q = run[r], &t = st[r];
+        if (t.rc) return fail(t.rc, "chunk chain (stitch): " + t.err);
+        const int m = std::min(t.res.n_candidates, q.hi - q.lo);
+        std::copy_n(t.T0.begin(), m, q.T0.begin());  // what was walked before the merge point is replaced
+        std::copy_n(t.iters.begin(), m, q.iters.begin());
+        std::copy_n(t.lam.begin(), m, q.lam.begin());
+        std::copy_n(t.loss.begin(), m, q.loss.begin());
+        std::copy_n(t.ic.begin(), m, q.ic.begin());
+        std::copy_n(t.coef0.begin(), m, q.coef0.begin());
+        std::copy_n(t.support.begin(), (size_t)m * width, q.support.begin());
+        std::copy_n(t.beta.begin(), (size_t)m * width, q.beta.begin());
+        refits += m;
+        refit[(size_t)r] = {m, q.hi - q.lo, t.chain.stopped_at >= 0};
       }
-      refits += m;
-      q.fits += t.fits;
-      if (t.chain.stopped_at < 0 && m < q.hi - q.lo) {
-        // out of budget without meeting the chunk's own chain
-        if (give_up_from < 0 || r < give_up_from) give_up_from = r;
-      } else if (t.chain.stopped_at < 0) {  // the whole (short) chunk was replaced: its last model is a new one
-        changed[r] = 1;
-        any = true;
-        q.last_idx = t.last_idx;
-        q.last_val = t.last_val;
-        q.last_len = t.chain.last_len;
-        q.last_coef0 = t.chain.last_coef0;
-      }
+      const StitchRound d = stitch_round(need, refit);
+      for (int r = 1; r < C; r++)
+        if (d.changed[r]) {  // its last model is a new one
+          run[r].last_idx = st[r].last_idx;
+          run[r].last_val = st[r].last_val;
+          run[r].last_len = st[r].last_len;
+          run[r].last_coef0 = st[r].last_coef0;
+        }
+      give_up_from = d.give_up_from;
+      if (give_up_from >= 0 || !d.any) return 0;
+      if (round > C) return fail(BESSX_ERR_NUMERIC, "chunk chains: the stitching did not settle");
+      need = d.need;
     }
-    if (give_up_from >= 0) {
-      // a chunk behind one whose last model changed in this round was refitted from the old model: unsettled too
-      for (int r = 1; r < give_up_from; r++)
-        if (changed[r] && r + 1 < give_up_from) give_up_from = r + 1;
-      break;
-    }
-    if (!any) break;
-    if (round > C) return fail(BESSX_ERR_NUMERIC, "chunk chains: the stitching did not settle");
-    for (int r = 1; r < C; r++) need[r] = changed[r - 1];
   }
-  if (give_up_from >= 1) {
-    // the rest as ONE chain on the session's own state, from the last settled chunk's last model, on the warm cache
+
+  // after a give-up: the rest as ONE chain on the session's own state, from the last settled chunk's last model, on the
+  // warm cache
+  int give_up_tail() {
+    if (give_up_from < 1) return 0;
     const int f = give_up_from;
     ChunkRun tail;
-    tail.shape(bounds[f], ns, width, s->p_full);
-    tail.bind(&tail.res);
-    tail.chain = bessx_path_chain();
-    tail.chain.init_idx = run[f - 1].last_idx.data();
-    tail.chain.init_val = run[f - 1].last_val.data();
-    tail.chain.init_len = run[f - 1].last_len;
-    tail.chain.init_coef0 = run[f - 1].last_coef0;
-    tail.chain.keep_caches = 1;
-    tail.chain.last_idx = tail.last_idx.data();
-    tail.chain.last_val = tail.last_val.data();
-    tail.chain.last_cap = width;
+    tail.shape(bounds[f], ns, width);
+    tail.link_behind(run[f - 1]);
     kchains_quiesce(s);
     if (int rc = settle_device_chain(s)) return rc;
     for (auto &q : s->cache) q.valid = q.model_only = false;
     s->dev_state_rs = -1;
-    const long long fits_before = s->n_fits;
     if (int rc = sequential_path(s, seq + bounds[f], ns - bounds[f], &lambda, 1, ic_type, 0, &tail.res, &tail.chain)) return rc;
     tail.last_len = tail.chain.last_len;
     tail.last_coef0 = tail.chain.last_coef0;
-    tail.fits = s->n_fits - fits_before;
     run.resize((size_t)f);
     run.push_back(std::move(tail));
     s->kch_giveups++;
     if (s->kpath_chains == 0) s->kch_auto_off = true;
+    return 0;
   }
-  for (bessx_session *c : k->ctx) c->kch_sp_member = false;
-  k->sp.on = false;
-  if (int rc = sp_collect(s, k->sp)) return rc;
-  if (k->sp.rc) return fail(BESSX_ERR_HIP, std::string("shared pass over X: ") + hipGetErrorString((hipError_t)k->sp.rc));
-  const int R = (int)run.size();  // chunks of the result (fewer than C after a give-up)
-  if (k->log_on) {
-    kchains_log(s, "path ends", 0, 0);
-    for (const auto &r : k->log) std::fprintf(stderr, "kchunks %8.3f ms  chain %2d  %-28s %d %d\n", r.ms, r.chain, r.what, r.a, r.b);
-  }
-  s->kch_t[0] += secs(t_begin, t_coarse);
-  s->kch_t[1] += secs(t_coarse, t_chunks);
-  s->kch_t[2] += secs(t_chunks, now());
+
   // ---- the path's result: the candidates in order, the best of them by the criterion (first minimum, :113)
-  res->n_candidates = 0;
-  int best_r = 0, best_i = 0;
-  long long iters_path = 0, fits_all = coarse_fits;
-  for (int r = 0; r < R; r++) {
-    const ChunkRun &q = run[r];
-    fits_all += q.fits;
-    for (int i = 0; i < q.hi - q.lo; i++) {
-      const int g = res->n_candidates++;
-      iters_path += std::min(q.iters[i], s->max_iter);  // (a fit that ran out of iterations reports max_iter + 1)
-      if (q.ic[i] < run[best_r].ic[best_i]) {
-        best_r = r;
-        best_i = i;
-      }
-      if (g >= res->capacity) continue;
-      if (res->cand_T0) res->cand_T0[g] = q.T0[i];
-      if (res->cand_lambda) res->cand_lambda[g] = q.lam[i];
-      if (res->cand_iters) res->cand_iters[g] = q.iters[i];
-      if (res->cand_train_loss) res->cand_train_loss[g] = q.loss[i];
-      if (res->cand_ic) res->cand_ic[g] = q.ic[i];
-      if (res->cand_coef0) res->cand_coef0[g] = q.coef0[i];
-      for (int j = 0; j < res->max_T0; j++) {
-        if (res->cand_support) res->cand_support[(size_t)g * res->max_T0 + j] = j < width ? q.support[(size_t)i * width + j] : -1;
-        if (res->cand_beta) res->cand_beta[(size_t)g * res->max_T0 + j] = j < width ? q.beta[(size_t)i * width + j] : 0.0;
+  void assemble(bessx_path_result *res) {
+    if (k->log_on) {
+      kchains_log(s, "path ends", 0, 0);
+      for (const auto &r : k->log) std::fprintf(stderr, "kchunks %8.3f ms  chain %2d  %-28s %d %d\n", r.ms, r.chain, r.what, r.a, r.b);
+    }
+    s->kch_t[0] += secs(t_begin, t_coarse);
+    s->kch_t[1] += secs(t_coarse, t_chunks);
+    s->kch_t[2] += secs(t_chunks, Clock::now());
+    res->n_candidates = 0;
+    int best_r = 0, best_i = 0;
+    for (size_t r = 0; r < run.size(); r++) {  // (fewer chunks than C after a give-up)
+      const ChunkRun &q = run[r];
+      for (int i = 0; i < q.hi - q.lo; i++) {
+        const int g = res->n_candidates++;
+        iters_path += std::min(q.iters[i], s->max_iter);  // (a fit that ran out of iterations reports max_iter + 1)
+        if (q.ic[i] < run[best_r].ic[best_i]) {
+          best_r = (int)r;
+          best_i = i;
+        }
+        if (g >= res->capacity) continue;
+        if (res->cand_T0) res->cand_T0[g] = q.T0[i];
+        if (res->cand_lambda) res->cand_lambda[g] = q.lam[i];
+        if (res->cand_iters) res->cand_iters[g] = q.iters[i];
+        if (res->cand_train_loss) res->cand_train_loss[g] = q.loss[i];
+        if (res->cand_ic) res->cand_ic[g] = q.ic[i];
+        if (res->cand_coef0) res->cand_coef0[g] = q.coef0[i];
+        for (int j = 0; j < res->max_T0; j++) {
+          if (res->cand_support) res->cand_support[(size_t)g * res->max_T0 + j] = j < width ? q.support[(size_t)i * width + j] : -1;
+          if (res->cand_beta) res->cand_beta[(size_t)g * res->max_T0 + j] = j < width ? q.beta[(size_t)i * width + j] : 0.0;
+        }
       }
     }
-  }
-  {
     const ChunkRun &q = run[best_r];
     if (res->beta) {
       std::fill(res->beta, res->beta + s->p_full, 0.0);
@@ -1296,61 +1243,79 @@ int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lam
     res->best_T0 = q.T0[best_i];
     res->best_iters = q.iters[best_i];
   }
-  for (bessx_session *c : k->ctx) {  // statistics of the contexts belong to the session
-    s->cov_panel_groups += c->cov_panel_groups;
-    s->cov_cg_fallbacks += c->cov_cg_fallbacks;
-    s->cov_tie_rescues += c->cov_tie_rescues;
-    s->dbg_waits += c->dbg_waits;
-    s->dbg_waits_ready += c->dbg_waits_ready;
-    s->dbg_enq_s += c->dbg_enq_s;
-    c->dbg_waits = c->dbg_waits_ready = 0;
-    c->dbg_enq_s = 0.0;
-    s->chain_queued += c->chain_queued;
-    s->chain_hits += c->chain_hits;
-    c->cov_panel_groups = c->cov_cg_fallbacks = c->cov_tie_rescues = 0;
-    c->chain_queued = c->chain_hits = 0;
-    s->n_submodel_steps += c->n_submodel_steps;
-    c->n_submodel_steps = 0;
-    s->k1_seconds += c->k1_seconds;
-    s->k1_bytes += c->k1_bytes;
-    s->k1_launches += c->k1_launches;
-    c->k1_seconds = c->k1_bytes = 0.0;
-    c->k1_launches = 0;
-    for (int w = 0; w < 2; w++) {
-      s->panel_w_seconds[w] += c->panel_w_seconds[w];
-      s->panel_w_launches[w] += c->panel_w_launches[w];
-      c->panel_w_seconds[w] = 0.0;
-      c->panel_w_launches[w] = 0;
+
+  // the session as the path leaves it.  Fits and get_A calls as the single chain counts them; the work really done
+  // (coarse chain, replaced candidates) is in bessx_session_counter 14-16
+  void session_state(bessx_path_chain *link) {
+    s->n_fits = ns;
+    s->n_iters = iters_path;
+    s->kch_paths++;
+    s->kch_last_chains = C;
+    s->kch_refits += refits;
+    // the session's own device state is the coarse chain's last fit, not the path's last candidate
+    for (auto &q : s->cache) q.valid = q.model_only = false;
+    s->dev_state_rs = -1;
+    const ChunkRun &q = run.back();
+    if (link) {  // the model the link's successor starts from
+      link->last_len = q.last_len;
+      link->last_coef0 = q.last_coef0;
+      for (int i = 0; i < q.last_len && i < link->last_cap; i++) {
+        if (link->last_idx) link->last_idx[i] = q.last_idx[i];
+        if (link->last_val) link->last_val[i] = q.last_val[i];
+      }
     }
-  }
-  // fits and get_A calls as the single chain counts them; the work really done (coarse chain, replaced candidates) is in
-  // bessx_session_counter 14-16
-  (void)fits_all;
-  s->n_fits = ns;
-  s->n_iters = iters_path;
-  s->kch_paths++;
-  s->kch_last_chains = C;
-  s->kch_refits += refits;
-  // the session's own device state is the coarse chain's last fit, not the path's last candidate
-  for (auto &q : s->cache) q.valid = q.model_only = false;
-  s->dev_state_rs = -1;
-  if (link) {  // the model the link's successor starts from
-    const ChunkRun &q = run[R - 1];
-    link->last_len = q.last_len;
-    link->last_coef0 = q.last_coef0;
-    for (int i = 0; i < q.last_len && i < link->last_cap; i++) {
-      if (link->last_idx) link->last_idx[i] = q.last_idx[i];
-      if (link->last_val) link->last_val[i] = q.last_val[i];
-    }
-  }
-  // Algorithm state as the path leaves it: the last candidate's model (normalised scale)
-  {
-    const ChunkRun &q = run[R - 1];
+    // Algorithm state as the path leaves it: the last candidate's model (normalised scale)
     s->beta.idx.assign(q.last_idx.begin(), q.last_idx.begin() + q.last_len);
     s->beta.val.assign(q.last_val.begin(), q.last_val.begin() + q.last_len);
     s->coef0 = q.last_coef0;
   }
+};
+
+// statistics of a chain context belong to the session
+void fold_context_statistics(bessx_session *s, bessx_session *c) {
+  auto take = [](auto &to, auto &from) { to += from, from = 0; };
+  take(s->cov_panel_groups, c->cov_panel_groups);
+  take(s->cov_cg_fallbacks, c->cov_cg_fallbacks);
+  take(s->cov_tie_rescues, c->cov_tie_rescues);
+  take(s->dbg_waits, c->dbg_waits);
+  take(s->dbg_waits_ready, c->dbg_waits_ready);
+  take(s->dbg_enq_s, c->dbg_enq_s);
+  take(s->chain_queued, c->chain_queued);
+  take(s->chain_hits, c->chain_hits);
+  take(s->n_submodel_steps, c->n_submodel_steps);
+  take(s->k1_seconds, c->k1_seconds);
+  take(s->k1_bytes, c->k1_bytes);
+  take(s->k1_launches, c->k1_launches);
+  for (int w = 0; w < 2; w++) {
+    take(s->panel_w_seconds[w], c->panel_w_seconds[w]);
+    take(s->panel_w_launches[w], c->panel_w_launches[w]);
+  }
+}
+
+}  // namespace
+
+int sequential_path_chunked(bessx_session *s, const int *seq, int ns, double lambda, int ic_type,
+                            bessx_path_result *res, bessx_path_chain *link) {
+  const int C = chains_for(s, ns, link != nullptr, link && link->init_len > 0 && link->keep_caches);
+  HIPX(hipSetDevice(s->device));
+  KChains *k = s->kch;
+  if (!k || (int)k->ctx.size() < C || k->pool.broken)
+    return fail(BESSX_ERR_HIP, "chunk chains: not prepared (kchunks_prepare)");
+  const int width = res->max_T0 > 0 ? res->max_T0 : seq[ns - 1];
+  ChunkPath d{s, k, seq, ns, lambda, ic_type, C, width, s->model_type == 1 && s->cov_mode};
+  d.plan();
+  d.fill_stream();
+  if (int rc = d.coarse_chain(link)) return rc;
+  std::optional<SharedPassScope> scope;  // opened by chunk_round: from there EVERY way out closes the shared-pass round
+  if (int rc = d.chunk_round(scope)) return rc;
+  if (int rc = d.stitch_rounds()) return rc;
+  if (int rc = d.give_up_tail()) return rc;
+  if (int rc = scope->close()) return rc;
+  d.assemble(res);
+  for (bessx_session *c : k->ctx) fold_context_statistics(s, c);
+  d.session_state(link);
   return 0;
 }
 
 }  // namespace bessx
+

@@ -327,7 +327,9 @@ def test_failed_allocation_during_set_cv(gpu, probe, alloc_fail, monkeypatch):
 @pytest.mark.parametrize("form", ["covariance", "streaming"])
 def test_failed_allocation_during_first_chunked_path(gpu, probe, alloc_fail, form):
     """The first chunked path of a session creates the chain contexts, the host threads' rendezvous and the buffers of
-    the merged launches / shared passes: the call either fails cleanly or falls back (fewer mechanisms, same path)."""
+    the merged launches / shared passes: the call either fails cleanly or falls back (fewer mechanisms, same path).  After
+    a call that failed, the same session walks the same path again: nothing of the failed call (members of a shared-pass
+    round, launch counters, a half-made context) is left for it to trip over."""
     X, y, _, _ = synth.make_lm(1200, 300, 8, seed=10)
     kw, seq = (dict(score_mode=1) if form == "streaming" else {}), np.arange(1, 21)
     with gpu.Session(X, y, **kw) as s:
@@ -349,6 +351,13 @@ def test_failed_allocation_during_first_chunked_path(gpu, probe, alloc_fail, for
             fired = requests(probe) - before >= N
             if err is not None:
                 assert fired and err and gpu.last_error(), "N = %d" % N
+                # the SAME session, the hook removed: the failed call left nothing behind that its next path trips over
+                paths = s.counters()["kpath_chunked_paths"]
+                again = s.sequential_path(seq, ic_type=3)
+                assert np.array_equal(again["cand_support"], want["cand_support"]), "N = %d, same session" % N
+                assert np.allclose(again["cand_ic"], want["cand_ic"], rtol=1e-9), "N = %d, same session" % N
+                # (as chunk chains again, or -- contexts not to be had -- the same path as one chain)
+                assert s.counters()["kpath_chunked_paths"] in (paths, paths + 1), "N = %d, same session" % N
             else:
                 assert np.array_equal(got["cand_support"], want["cand_support"]), "N = %d" % N
                 assert np.allclose(got["cand_ic"], want["cand_ic"], rtol=1e-9), "N = %d" % N
