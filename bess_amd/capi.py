@@ -41,6 +41,7 @@ SYMBOLS = [
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
+    "bessx_cox_brier_device", "bessx_cox_brier_workspace", "bessx_op_cox_brier_bench",
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
     "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
     "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
@@ -106,6 +107,14 @@ class CoxSurvivalInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("B", _D), ("hg", _D), ("T", _i), ("kind", _i), ("out_row_stride", _ll),
                 ("out_col_stride", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class CoxBrierInput(ctypes.Structure):
+    """bessx_cox_brier_input: R Cox models, X in GPU memory, the baseline cumulative hazards at T times (R x T,
+    model-major), the times, and the rows' time / IPCW weights / case weights in host memory; strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("R", _i), ("hg", _D), ("times", _D), ("T", _i), ("time", _D),
+                ("row_a", _D), ("time_b", _D), ("weight", _D), ("stream", _vp)]
 
 
 class InfoInput(ctypes.Structure):
@@ -344,6 +353,10 @@ def lib():
         L.bessx_cox_baseline_device.argtypes = [ctypes.POINTER(CoxBaselineInput), _I, _D, _D]
         L.bessx_cox_survival_device.argtypes = [ctypes.POINTER(CoxSurvivalInput), _vp]
         L.bessx_op_cox_surv_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
+        L.bessx_cox_brier_device.argtypes = [ctypes.POINTER(CoxBrierInput), _D, _D]
+        L.bessx_cox_brier_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), ctypes.POINTER(_ll),
+                                                _I]
+        L.bessx_op_cox_brier_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _D]
         L.bessx_info_device.argtypes = [ctypes.POINTER(InfoInput), _D, _D]
         L.bessx_info_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
         L.bessx_op_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D]
@@ -3029,6 +3042,268 @@ def op_cox_surv_bench(x, cols, T=100, kind="survival", out_col_major=False, repe
     _check(lib().bessx_op_cox_surv_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                          _ip(cols), cols.size, int(T), SURV_KINDS[kind], int(bool(out_col_major)),
                                          repeats, _dp(ms)))
+    return tuple(float(v) for v in ms)
+
+
+def _km_steps(time, status, w, order=None):
+    """The distinct times u (ascending) with, in fp64: cens_u / ev_u = the weight of the rows censored / with an event at u,
+    after_u = the weight of the rows with a later time.  Sums in time order (np.cumsum).  order: the stable argsort of
+    time, where the caller has it."""
+    if order is None:
+        order = np.argsort(time, kind="stable")
+    t, d, w = time[order], status[order], w[order]
+    new = np.ones(t.size, dtype=bool)
+    new[1:] = t[1:] != t[:-1]
+    starts = np.nonzero(new)[0]
+    ev = np.add.reduceat(w * d, starts)
+    cens = np.add.reduceat(w * (1.0 - d), starts)
+    tail = np.concatenate([np.cumsum(w[::-1])[::-1], [0.0]])  # tail[k]: the weight from position k on
+    return t[starts], cens, ev, tail[np.append(starts[1:], t.size)]
+
+
+def _km_vectors(time, status, weight):
+    time, status = _f64(time).reshape(-1), _f64(status).reshape(-1)
+    n = time.size
+    if n < 1 or status.size != n:
+        raise ValueError("time and status must hold the same number (>= 1) of values")
+    w = np.ones(n) if weight is None else _f64(weight).reshape(-1)
+    if w.size != n:
+        raise ValueError("time.size should be equal to weight.size")
+    if np.isnan(time).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(status, (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    if not (w >= 0.0).all():
+        raise ValueError("weight should be non-negative")
+    return time, status, w
+
+
+def censoring_km(time, status, weight=None):
+    """The weighted Kaplan-Meier estimate G of the censoring distribution as a right-continuous step function: (times,
+    G), the distinct times of the rows, ascending, and G at them; G = 1 before the first.  An event at a time leaves the
+    risk set before a censoring at the same time: with d_u the weight of the rows censored at u and Y_u the weight of the
+    rows with a later time plus d_u, G(t) = prod over u <= t of (1 - d_u / Y_u), each factor formed as (Y_u - d_u) / Y_u
+    from the sum it is, without the subtraction.  Host arrays, fp64."""
+    return _censoring_km(*_km_vectors(time, status, weight))
+
+
+def _censoring_km(time, status, w, order=None):
+    u, cens, _, after = _km_steps(time, status, w, order)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = np.where(cens > 0.0, after / (after + cens), 1.0)
+    return u, np.cumprod(f)
+
+
+def _step_at(u, G, t, left=False):
+    """G(t) (left: G(t-)) of the right-continuous step function (u, G) that is 1 before u[0]."""
+    idx = np.searchsorted(u, t, side="left" if left else "right")
+    return np.concatenate([[1.0], G])[idx]
+
+
+def ipcw_weights(time, status, times, weight=None, censoring="km"):
+    """(row_a (n,), time_b (T,)) of the IPCW Brier score at the requested times.  censoring="km": a_i = status_i /
+    G(time_i-) (0 where weight_i = 0 or status_i = 0) and b_j = 1 / G(times_j) with G = censoring_km of the same rows; a
+    time with G(times_j) = 0 is a ValueError that names the largest admissible time.  censoring=None: a = status, b = 1
+    (without censoring: the mean squared error of S against 1{time > t}).  censoring=(row_a, time_b): the caller's
+    arrays, finite and >= 0, for example from a training set's G."""
+    return _ipcw_weights(*_km_vectors(time, status, weight), times, censoring)
+
+
+def _ipcw_weights(time, status, w, times, censoring, order=None):
+    times = _f64(times).reshape(-1)
+    if np.isnan(times).any():
+        raise ValueError("There is NAN value in times")
+    if censoring is None:
+        return status.copy(), np.ones(times.size)
+    if isinstance(censoring, str):
+        if censoring != "km":
+            raise ValueError("censoring must be 'km', None or a pair (row_a, time_b), got %r" % (censoring,))
+        u, G = _censoring_km(time, status, w, order)
+        Gt = _step_at(u, G, times)
+        if (Gt <= 0.0).any():
+            raise ValueError("the censoring estimate G reaches 0 at the last time %r: the largest admissible time is %r"
+                             % (float(u[-1]), float(np.nextafter(u[-1], -np.inf))))
+        a = np.where((status != 0.0) & (w > 0.0), 1.0, 0.0)
+        a[a > 0.0] /= _step_at(u, G, time[a > 0.0], left=True)
+        return a, 1.0 / Gt
+    try:
+        row_a, time_b = censoring
+        row_a, time_b = _f64(row_a).reshape(-1), _f64(time_b).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("censoring must be 'km', None or a pair (row_a, time_b), got %r" % (censoring,)) from None
+    if row_a.size != time.size or time_b.size != times.size:
+        raise ValueError("censoring=(row_a, time_b) must hold n = %d and T = %d values, got %d and %d"
+                         % (time.size, times.size, row_a.size, time_b.size))
+    for what, v in (("row_a", row_a), ("time_b", time_b)):
+        if not (np.isfinite(v) & (v >= 0.0)).all():
+            raise ValueError("censoring: %s must be finite and non-negative" % what)
+    return row_a, time_b
+
+
+def _increasing(times):
+    return times.size >= 2 and bool((np.diff(times) > 0.0).all())
+
+
+def integrated_brier(times, bs):
+    """The integrated Brier score: the trapezoid rule over the strictly increasing times (T >= 2), divided by
+    times[-1] - times[0].  bs: (T,) or (T, R); returns a float or (R,)."""
+    times, bs = _f64(times).reshape(-1), np.asarray(bs, dtype=np.float64)
+    if times.size < 2:
+        raise ValueError("the integrated Brier score needs at least 2 times, got %d" % times.size)
+    if np.isnan(times).any():
+        raise ValueError("There is NAN value in times")
+    if not _increasing(times):
+        raise ValueError("the integrated Brier score needs strictly increasing times")
+    if bs.shape[0] != times.size or bs.ndim not in (1, 2):
+        raise ValueError("bs must have shape (T,) or (T, R) with T = %d, got %s" % (times.size, bs.shape))
+    dt = np.diff(times)
+    area = np.sum((0.5 * dt).reshape((-1,) + (1,) * (bs.ndim - 1)) * (bs[1:] + bs[:-1]), axis=0)
+    return area / (times[-1] - times[0])
+
+
+def brier_null(time, status, w, times, row_a, time_b, order=None):
+    """(BS_null (T,), sum_w): the weighted Kaplan-Meier survival S^ of the rows put through the Brier formula,
+    BS_null[j] = (S^(t_j)^2 sum_{time_i <= t_j} w_i a_i + (1 - S^(t_j))^2 b_j sum_{time_i > t_j} w_i) / W.  Host, fp64."""
+    if order is None:
+        order = np.argsort(time, kind="stable")
+    u, cens, ev, after = _km_steps(time, status, w, order)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = np.where(ev > 0.0, (after + cens) / (after + cens + ev), 1.0)
+    S = _step_at(u, np.cumprod(f), times)
+    ts = time[order]
+    idx = np.searchsorted(ts, times, side="right")  # rows with time <= t_j
+    cum_wa = np.concatenate([[0.0], np.cumsum((w * row_a)[order])])
+    tail_w = np.concatenate([np.cumsum(w[order][::-1])[::-1], [0.0]])
+    W = float(np.sum(w))
+    return (S * S * cum_wa[idx] + (1.0 - S) ** 2 * time_b * tail_w[idx]) / W, W
+
+
+def _brier_result(bs, times, time, status, w, row_a, time_b, order=None):
+    """The dict of cox_brier_device / bess_base.brier_survival from bs (T, R): the null model, IPA and the integrals (NaN
+    where the times are not at least 2 and strictly increasing)."""
+    null, W = brier_null(time, status, w, times, row_a, time_b, order)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ipa = np.where(null[:, None] > 0.0, 1.0 - bs / null[:, None], np.nan)
+    if _increasing(times):
+        ibs, ibs_null = integrated_brier(times, bs), float(integrated_brier(times, null))
+    else:
+        ibs, ibs_null = np.full(bs.shape[1], np.nan), float("nan")
+    return {"brier": bs, "null": null, "ipa": ipa, "ibs": ibs, "ibs_null": ibs_null, "row_a": row_a, "time_b": time_b,
+            "sum_w": W}
+
+
+def _brier_grid(hg, times, R):
+    """(hg float64 (T, R), times float64 (T,)), checked."""
+    if np.ndim(times) > 1:
+        raise ValueError("times must be 1-D")
+    times = _f64(times).reshape(-1)
+    T = times.size
+    if T < 1:
+        raise ValueError("times is empty: no score to compute")
+    if np.isnan(times).any():
+        raise ValueError("There is NAN value in times")
+    hg = np.asarray(hg, dtype=np.float64)
+    if hg.ndim == 1 and R == 1:
+        hg = hg.reshape(-1, 1)
+    if hg.shape != (T, R):
+        raise ValueError("hg must have shape (T, R) = (%d, %d), got %s" % (T, R, hg.shape))
+    if not (hg >= 0.0).all():
+        raise ValueError("hg should be non-negative")
+    return hg, times
+
+
+def cox_brier_workspace(n, T, R):
+    """(doubles of device memory, rows per slab, slabs, row groups per workgroup) of a cox_brier_device call on n rows, T
+    times and R models (bessx_cox_brier_workspace; needs no device).  Nothing in it is n x T."""
+    d, rows, slabs, groups = _ll(0), _ll(0), _ll(0), _i(0)
+    _check(lib().bessx_cox_brier_workspace(int(n), int(T), int(R), ctypes.byref(d), ctypes.byref(rows),
+                                           ctypes.byref(slabs), ctypes.byref(groups)))
+    return int(d.value), int(rows.value), int(slabs.value), int(groups.value)
+
+
+def cox_brier_device(x, cols, B, hg, times, time, status, weight=None, censoring="km", stream=0):
+    """The time-dependent Brier score of R Cox models under inverse-probability-of-censoring weights on a device matrix x
+    (n x p: float64 or float32, any non-negative strides), read once where it lies, the support's columns only
+    (bessx_cox_brier_device): with eta = x[:, cols] @ B (no intercept), e = exp(clip(eta, -30, 30)), z = hg[j, r] e_ir,
+    S = exp(-z) and q = -expm1(-z),
+        BS[j, r] = (1 / W) sum_i w_i (a_i S^2 if time_i <= times_j else b_j q^2),      W = sum_i w_i,
+    in one fused reduction that never stores an n x T element.  hg: (T, R) (or (T,) for one model), the baseline
+    cumulative hazard of every model at the times (baseline_at on what cox_baseline_device returned); time, status (0 or
+    1), weight (None = ones, else >= 0): n values each, host or device arrays (device arrays are copied to the host).
+    (a, b) = ipcw_weights(time, status, times, weight, censoring).  Returns {"brier": (T, R), "null": (T,) the Kaplan-Meier
+    survival of the same rows put through the same formula, "ipa": (T, R) = 1 - brier / null (NaN where null is 0),
+    "ibs": (R,) and "ibs_null": integrated_brier over the times (NaN unless they are at least 2 and strictly increasing),
+    "row_a", "time_b", "sum_w"}.  Every sum has a fixed order: the same call gives the same bits."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    B = np.asarray(B, dtype=np.float64)
+    R = B.shape[1] if B.ndim == 2 else 1
+    cols, B, _ = _predict_model(dx, cols, B, np.zeros(R))
+    hg, times = _brier_grid(hg, times, R)
+    if not (isinstance(censoring, (str, tuple, list)) or censoring is None):
+        raise ValueError("censoring must be 'km', None or a pair (row_a, time_b), got %r" % (censoring,))
+    if isinstance(censoring, str) and censoring != "km":
+        raise ValueError("censoring must be 'km', None or a pair (row_a, time_b), got %r" % (censoring,))
+
+    class _Fields:
+        pass
+
+    host = _cox_data(_Fields(), time, status, weight, n, stream)
+    w = host.get("weight")
+    if w is not None and not (w >= 0.0).all():
+        raise ValueError("weight should be non-negative")
+    wv = np.ones(n) if w is None else w
+    if not float(np.sum(wv)) > 0.0:
+        raise ValueError("the weights sum to 0")
+    order = np.argsort(host["time"], kind="stable")  # (once: the weights and the null model both walk the rows in it)
+    row_a, time_b = _ipcw_weights(host["time"], host["status"], wv, times, censoring, order)
+    row_a, time_b = np.ascontiguousarray(row_a), np.ascontiguousarray(time_b)
+    hg_mt = np.ascontiguousarray(hg.T)  # model-major
+    a = CoxBrierInput()
+    _set_x(a, dx)
+    a.cols, a.m, a.B, a.R = _ip(cols), cols.size, _dp(B), R
+    a.hg, a.times, a.T = _dp(hg_mt), _dp(times), times.size
+    a.time, a.row_a, a.time_b, a.weight = _dp(host["time"]), _dp(row_a), _dp(time_b), _dp(w)
+    a.stream = int(stream) if stream else None
+    bs, sum_w = np.zeros((times.size, R)), _d(0)
+    _check(lib().bessx_cox_brier_device(ctypes.byref(a), _dp(bs), ctypes.byref(sum_w)))
+    out = _brier_result(bs, times, host["time"], host["status"], wv, row_a, time_b, order)
+    out["sum_w"] = sum_w.value
+    return out
+
+
+def cox_brier_candidates(result, x_train, time_train, status_train, x_val, time_val, status_val, times, weight_train=None,
+                         weight_val=None, censoring="km", stream=0):
+    """The train / validation split for the curves: for every candidate of a path, the Breslow baseline on the training
+    rows (one cox_baseline_device call per candidate: that entry point takes one model), then ONE cox_brier_device call
+    over the union of the supports on the validation rows.  times: at least 2, strictly increasing.  Returns (ibs (R,),
+    best) with best the lowest index among the smallest integrated Brier scores (a NaN never wins)."""
+    cols, B, _ = candidate_models(result)
+    times = _f64(times).reshape(-1)
+    if not _increasing(times):
+        raise ValueError("the integrated Brier score needs at least 2 strictly increasing times")
+    hg = np.zeros((times.size, B.shape[1]))
+    for r in range(B.shape[1]):
+        used = B[:, r] != 0.0
+        base = cox_baseline_device(x_train, cols[used], B[used, r], time_train, status_train, weight=weight_train,
+                                   stream=stream)
+        hg[:, r] = baseline_at(base["times"], base["cumhaz"], times)
+    ibs = cox_brier_device(x_val, cols, B, hg, times, time_val, status_val, weight=weight_val, censoring=censoring,
+                           stream=stream)["ibs"]
+    return ibs, int(np.argmin(np.where(np.isnan(ibs), np.inf, ibs)))
+
+
+def op_cox_brier_bench(x, cols, R=1, T=100, repeats=20):
+    """Milliseconds per launch of the kernels behind cox_brier_device on the device matrix x for the support cols, R
+    models and T times, device events: (predictor pass that stores exp(clip(eta)) as R x n, the reduction kernel
+    k_cxb_terms over n * T * R elements, the addition of its slabs)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    if int(T) < 1 or int(R) < 1:
+        raise ValueError("T and R must be at least 1")
+    ms = np.zeros(3)
+    _check(lib().bessx_op_cox_brier_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                          _ip(cols), cols.size, int(R), int(T), repeats, _dp(ms)))
     return tuple(float(v) for v in ms)
 
 

@@ -1873,6 +1873,174 @@ int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------
+// IPCW Brier score of R Cox models at T times on a caller's device matrix (include/bessx.h section 2p)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the device side of one problem: buffers of `sc`, uploads queued on st (the host arrays must outlive them)
+struct BrierDev {
+  int *cols = nullptr;
+  double *B = nullptr, *zero = nullptr, *ex = nullptr, *time = nullptr, *w = nullptr, *wa = nullptr, *hg = nullptr,
+         *tg = nullptr, *b = nullptr, *part = nullptr, *bs = nullptr;
+};
+
+// w, wa: n host values each (w = ones without weights, wa = w * row_a)
+int cox_brier_stage(Owner &sc, const int *cols, int m, const double *B, int R, int n, int T, const double *time,
+                    const double *w, const double *wa, const double *hg, const double *tg, const double *b, hipStream_t st,
+                    BrierDev *d) {
+  const size_t N = (size_t)n, RT = (size_t)R * (size_t)T;
+  long long rows, slabs;
+  cox_brier_split(n, &rows, &slabs);
+  HIPX(sc.alloc(&d->B, (size_t)m * R + (size_t)R));
+  HIPX(sc.alloc(&d->cols, (size_t)m));
+  d->zero = d->B + (size_t)m * R;
+  HIPX(hipMemsetAsync(d->zero, 0, (size_t)R * sizeof(double), st));
+  if (m > 0) {
+    HIPX(hipMemcpyAsync(d->cols, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(d->B, B, (size_t)m * R * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  HIPX(sc.alloc(&d->time, 3 * N));  // time, w, wa
+  d->w = d->time + N;
+  d->wa = d->w + N;
+  HIPX(hipMemcpyAsync(d->time, time, N * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->w, w, N * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->wa, wa, N * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(sc.alloc(&d->hg, 2 * RT + 2 * (size_t)T));  // hg, the result, t, b
+  d->bs = d->hg + RT;
+  d->tg = d->bs + RT;
+  d->b = d->tg + T;
+  HIPX(hipMemcpyAsync(d->hg, hg, RT * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->tg, tg, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->b, b, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(sc.alloc(&d->ex, N * (size_t)R));
+  HIPX(sc.alloc(&d->part, (size_t)slabs * RT));
+  return 0;
+}
+
+int cox_brier_run(Owner &sc, std::vector<double> &h, const std::vector<double> &w, const std::vector<double> &wa, double W,
+                  const bessx_cox_brier_input *in, double *bs, hipStream_t st) {
+  const int n = in->n, T = in->T, R = in->R, f32 = in->x_dtype == BESSX_F32;
+  BrierDev d;
+  if (int rc = cox_brier_stage(sc, in->cols, in->m, in->B, R, n, T, in->time, w.data(), wa.data(), in->hg, in->times,
+                               in->time_b, st, &d))
+    return rc;
+  HIPX(launch_cox_brier_ex(in->x, f32, in->x_row_stride, in->x_col_stride, n, d.cols, in->m, d.B, d.zero, R, d.ex, st));
+  HIPX(launch_cox_brier(d.ex, d.time, d.w, d.wa, d.hg, d.tg, d.b, n, T, R, W, d.part, d.bs, 0, st));
+  h.resize((size_t)R * (size_t)T);
+  HIPX(hipMemcpyAsync(h.data(), d.bs, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  std::copy(h.begin(), h.end(), bs);
+  return 0;
+}
+
+int cox_brier_check_sizes(const std::string &w, int R, int T) {
+  if (R > 65535) return fail(BESSX_ERR_ARG, w + ": R must be at most 65535");
+  if (T < 1) return fail(BESSX_ERR_ARG, w + ": T must be at least 1");
+  if (T > COX_BRIER_T_MAX) return fail(BESSX_ERR_ARG, w + ": T must be at most " + std::to_string(COX_BRIER_T_MAX));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_brier_workspace(int n, int T, int R, long long *doubles, long long *rows_per_slab, long long *slabs,
+                              int *row_groups) {
+  const std::string w("cox_brier_workspace");
+  if (!doubles || !rows_per_slab || !slabs || !row_groups) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (n < 1 || R < 1) return fail(BESSX_ERR_ARG, w + ": n and R must be at least 1");
+  if (int rc = cox_brier_check_sizes(w, R, T)) return rc;
+  *doubles = cox_brier_workspace(n, T, R);
+  cox_brier_split(n, rows_per_slab, slabs);
+  *row_groups = cox_brier_row_groups(T);
+  return BESSX_OK;
+}
+
+int bessx_cox_brier_device(const bessx_cox_brier_input *in, double *bs, double *sum_w) {
+  const std::string w("cox_brier_device");
+  if (!in || !bs || !sum_w) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_check("cox_brier_device", c, false, false)) return rc;
+  if (int rc = cox_brier_check_sizes(w, in->R, in->T)) return rc;
+  if (!in->hg || !in->times || !in->time || !in->row_a || !in->time_b) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const int n = in->n, T = in->T;
+  for (int j = 0; j < T; j++) {
+    if (std::isnan(in->times[j])) return fail(BESSX_ERR_ARG, w + ": times holds a NaN");
+    if (!(in->time_b[j] >= 0.0) || !std::isfinite(in->time_b[j]))
+      return fail(BESSX_ERR_ARG, w + ": time_b must be non-negative and finite");
+  }
+  for (size_t q = 0; q < (size_t)in->R * (size_t)T; q++)
+    if (!(in->hg[q] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": hg must be non-negative");
+  std::vector<double> wv((size_t)n), wa((size_t)n);
+  double W = 0.0;
+  for (int i = 0; i < n; i++) {
+    if (std::isnan(in->time[i])) return fail(BESSX_ERR_ARG, w + ": time holds a NaN");
+    if (!(in->row_a[i] >= 0.0) || !std::isfinite(in->row_a[i]))
+      return fail(BESSX_ERR_ARG, w + ": row_a must be non-negative and finite");
+    const double wi = in->weight ? in->weight[i] : 1.0;
+    if (!(wi >= 0.0)) return fail(BESSX_ERR_ARG, w + ": weight must be non-negative");
+    wv[(size_t)i] = wi;
+    wa[(size_t)i] = wi * in->row_a[i];
+    W += wi;
+  }
+  if (!(W > 0.0) || !std::isfinite(W)) return fail(BESSX_ERR_ARG, w + ": the weights must have a positive, finite sum");
+  int dev = -1;
+  if (int rc = cox_check_device("cox_brier_device", c, &dev)) return rc;
+  const int rc = dev_call(dev, c.stream, [&](DevCall &dc) { return cox_brier_run(dc.sc, dc.h, wv, wa, W, in, bs, dc.st); });
+  if (!rc) *sum_w = W;
+  return rc;
+}
+
+int bessx_op_cox_brier_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                             const int *cols, int m, int R, int T, int repeats, double *stage_ms) {
+  const std::string w("op_cox_brier_bench");
+  if (repeats < 1 || !stage_ms) return fail(BESSX_ERR_ARG, w + ": bad arguments");
+  if (!x) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = predict_check_model("op_cox_brier_bench", n, p, cols, m, R, BESSX_LINK_IDENTITY)) return rc;
+  if (int rc = cox_brier_check_sizes(w, R, T)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_brier_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m * R), time((size_t)n), wv((size_t)n, 1.0), wa((size_t)n), hg((size_t)R * T), tg((size_t)T),
+      b((size_t)T);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int i = 0; i < n; i++) {  // distinct times in an order that is not the rows'
+    time[(size_t)i] = (double)(((long long)i * 7919) % n) + (double)i / (2.0 * n);
+    wa[(size_t)i] = (double)(i % 2);
+  }
+  for (int j = 0; j < T; j++) {
+    tg[(size_t)j] = (j + 0.5) * (double)n / T;
+    b[(size_t)j] = 1.0 + (double)j / T;
+    for (int r = 0; r < R; r++) hg[(size_t)r * T + j] = (j + 1.0) / T * (1.0 + (double)r / R);
+  }
+  Owner sc;
+  BrierDev d;
+  if (int rc = cox_brier_stage(sc, cols, m, B.data(), R, n, T, time.data(), wv.data(), wa.data(), hg.data(), tg.data(),
+                               b.data(), nullptr, &d))
+    return rc;
+  HIPX(hipDeviceSynchronize());
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
+  const int f32 = dtype == BESSX_F32;
+  for (int stage = 0; stage < 3; stage++) {
+    float ms = 0.f;
+    if (int rc = bt.run(repeats, &ms, [&]() -> int {
+          if (stage == 0)
+            HIPX(launch_cox_brier_ex(x, f32, row_stride, col_stride, n, d.cols, m, d.B, d.zero, R, d.ex, nullptr));
+          else
+            HIPX(launch_cox_brier(d.ex, d.time, d.w, d.wa, d.hg, d.tg, d.b, n, T, R, (double)n, d.part, d.bs, stage, nullptr));
+          return 0;
+        }))
+      return rc;
+    stage_ms[stage] = ms / repeats;
+  }
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
 // expected information and score of one model on a caller's device matrix (include/bessx.h section 2g)
 // ----------------------------------------------------------------------------------------------
 namespace {

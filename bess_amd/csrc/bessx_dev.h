@@ -112,6 +112,21 @@ hipError_t launch_cox_surv_ex(const void *src, int f32, long long rs, long long 
                               const double *B, const double *zero, double *ex, hipStream_t st);
 hipError_t launch_cox_surv_curves(const double *ex, const double *hg, long long n, int T, int kind, double *out,
                                   long long ors, long long ocs, hipStream_t st);
+// IPCW Brier score of R Cox models at T times (bessx_k_coxbrier.hip).  _ex: e[r * n + i] = exp(clamp(eta(i, r), +-30)) in
+// ROW order (src, cols, B (m x R) as in launch_predict; zero: R doubles of 0.0).  launch_cox_brier: bs[j * R + r] = (1 / W)
+// sum_i (time[i] <= tg[j] ? wa[i] exp(-z)^2 : b[j] w[i] expm1(-z)^2), z = hg[r * T + j] * e[r * n + i]; part: slabs * R * T
+// doubles of the split (a function of n alone); only = 1 / 2 launches the term kernel / the addition of the slabs alone.
+// _row_groups: the row groups whose sums a workgroup adds, a function of T alone.  _workspace: the doubles of device
+// memory of a bessx_cox_brier_device call.  Everything else is device memory.
+constexpr int COX_BRIER_T_MAX = 1 << 20;
+void cox_brier_split(long long n, long long *rows_per_slab, long long *slabs);
+int cox_brier_row_groups(int T);
+long long cox_brier_workspace(long long n, int T, int R);
+hipError_t launch_cox_brier_ex(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                               const double *B, const double *zero, int R, double *ex, hipStream_t st);
+hipError_t launch_cox_brier(const double *e, const double *time, const double *w, const double *wa, const double *hg,
+                            const double *tg, const double *b, long long n, int T, int R, double W, double *part,
+                            double *bs, int only, hipStream_t st);
 // expected information and score of one model (bessx_k_info.hip): with eta as in launch_predict (R = 1), v_i / g_i the
 // working and score weights of the link and z_i = (1, x(i, cols[0]), ...), info = sum_i v_i z_i z_i^T ((m + 1) x (m + 1),
 // leading dimension ld, both triangles, mirrors of each other) and score = sum_i g_i z_i (m + 1); res: launch_eval's

@@ -1,6 +1,6 @@
 #ifndef BESSX_DEVCALL_H
 #define BESSX_DEVCALL_H
-// bessx_devcall.h -- what the entry points that take a caller's X in GPU memory share (include/bessx.h sections 2c to 2o,
+// bessx_devcall.h -- what the entry points that take a caller's X in GPU memory share (include/bessx.h sections 2c to 2p,
 // in bessx_abi.cpp): a view of the call's arguments with its checks, the scope one call runs in,
 // the copy of staged results to the caller's host memory, and the timing of the single-kernel benches.
 #include "bessx_host.h"
@@ -85,6 +85,10 @@ inline CoxCall cox_call(const bessx_cox_baseline_input *in) {  // (Breslow's est
 inline CoxCall cox_call(const bessx_cox_survival_input *in) {
   return CoxCall{in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,   in->p, in->cols, in->m,
                  in->B, 1,           nullptr,          nullptr,          nullptr, 1,     static_cast<hipStream_t>(in->stream)};
+}
+inline CoxCall cox_call(const bessx_cox_brier_input *in) {  // (no status: row_a and time_b carry what it decides)
+  return CoxCall{in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,   in->p,      in->cols, in->m,
+                 in->B, in->R,       in->time,         nullptr,          in->weight, 1,       static_cast<hipStream_t>(in->stream)};
 }
 
 // ---- the checks that need no device: they report under the entry point's name ------------------------------------------

@@ -56,6 +56,10 @@ class bess_base:
     right-continuous step function that is 0 before the first event.  For an X in GPU memory both read the support's
     columns in place (capi.cox_baseline_device / capi.cox_survival_device) and the curves are a tensor on X's device that
     is written once; a NumPy X is served in fp64 NumPy.  fit() does not call fit_baseline.
+    brier_survival(X, y, times, weight=None, censoring="km") says how good those curves are on rows the model may not
+    have seen: the time-dependent Brier score under inverse-probability-of-censoring weights, the Kaplan-Meier null
+    model's, IPA = 1 - brier / null and the integrated scores.  For an X in GPU memory one fused reduction
+    (capi.cox_brier_device) forms every term in registers: no curve is stored.
     inference(X, y, weight=None) is the coefficient table of the fitted model on these rows (Lm, Logistic, Poisson; None
     for Cox; a 2-D beta raises): coef (intercept first), se, z, p_value (two-sided normal), cov, score, dispersion, dof,
     cond, positive_definite and cols, from the unpenalised expected information sum_i v_i z_i z_i^T of the selected
@@ -1529,6 +1533,62 @@ class bess_base:
         a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))
         z = np.exp(a)[:, None] * hg[None, :]
         return z if kind == "cumhaz" else np.exp(-z)
+
+    # ---- Cox: how good the curves are -------------------------------------------------------------------------------
+    @staticmethod
+    def _brier_host(eta, hg, times, time, w, row_a, time_b):
+        """BS (T, R) in fp64 NumPy with the definitions of capi.cox_brier_device: eta (n, R), hg (T, R), the rest
+        vectors.  One model at a time: no temporary beyond n x T."""
+        T, R = hg.shape
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))
+        left = time[:, None] <= times[None, :]
+        wa, W = w * row_a, np.sum(w)
+        bs = np.empty((T, R))
+        for r in range(R):
+            nz = -(np.exp(a[:, r])[:, None] * hg[None, :, r])
+            s, q = np.exp(np.where(left, nz, 0.0)), np.expm1(np.where(left, 0.0, nz))  # (one of the two is used)
+            sa = np.sum(np.where(left, wa[:, None] * (s * s), 0.0), axis=0)
+            sq = np.sum(np.where(left, 0.0, w[:, None] * (q * q)), axis=0)
+            bs[:, r] = (sa + time_b * sq) / W
+        return bs
+
+    def brier_survival(self, X, y, times, weight=None, censoring="km"):
+        """Cox only, after fit_baseline(): the time-dependent Brier score of the fitted model's curves S(t | x) on the rows
+        X, y (which it may not have seen) under inverse-probability-of-censoring weights, at the times given.  y = (time,
+        status) as in fit, weight n values >= 0 or None, censoring "km" (Kaplan-Meier weights from these rows), None or
+        a pair (row_a, time_b): capi.ipcw_weights.  Returns the dict of capi.cox_brier_device for the one model: "brier",
+        "null", "ipa" (T,), "ibs", "ibs_null" (floats; NaN unless the times are at least 2 and strictly increasing),
+        "row_a", "time_b", "sum_w".  An X in GPU memory is read once, in place, on torch's current stream, by a fused
+        reduction that stores no curve; a NumPy X is served in fp64 NumPy."""
+        if self.model_type_int != 4:
+            raise ValueError("brier_survival is for the Cox classes, this is a %s model" % self.model_type)
+        on_device, n = self._survival_x(X)
+        if getattr(self, "baseline_times_", None) is None:
+            raise ValueError("brier_survival needs the baseline hazard: call fit_baseline(X, y) first")
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        if not (w >= 0.0).all():
+            raise ValueError("weight should be non-negative")
+        if not float(np.sum(w)) > 0.0:
+            raise ValueError("the weights sum to 0")
+        if np.ndim(times) > 1:
+            raise ValueError("times must be 1-D")
+        hg = capi.baseline_at(self.baseline_times_, self.baseline_cumhaz_, times).reshape(-1, 1)
+        hg, times = capi._brier_grid(hg, times, 1)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.cox_brier_device(X, cols, beta[cols], hg, times, time, status,
+                                        weight=None if weight is None else w, censoring=censoring,
+                                        stream=_current_stream(X))
+        else:
+            row_a, time_b = capi.ipcw_weights(time, status, times, w, censoring)
+            eta = self._support_eta(X, cols, beta).reshape(-1, 1)
+            got = capi._brier_result(self._brier_host(eta, hg, times, time, w, row_a, time_b), times, time, status, w,
+                                     row_a, time_b)
+        out = dict(got)
+        out["brier"], out["ipa"] = got["brier"][:, 0], got["ipa"][:, 0]
+        out["ibs"] = float(np.asarray(got["ibs"]).reshape(-1)[0])
+        return out
 
 
 def _make(name, algorithm_type, model_type):

@@ -1098,6 +1098,54 @@ int bessx_cox_groupscore_workspace(int n, int p, int m, int n_event_rows, const 
                                    const int *groups, int n_tested, int candidate_block, long long *doubles,
                                    long long *block_doubles, long long *rows_per_slab, int *slabs, int *n_blocks,
                                    int *block_first, int *band, int *depth);
+/* ---------------------------------------------------------------------------------------
+ * 2p. The time-dependent Brier score of R Cox models under inverse-probability-of-censoring weights (Graf et al. 1999)
+ *     on an X already in GPU memory (bessx_k_coxbrier.hip): how good the curves of section 2f are, without storing one.
+ *     Stateless like sections 2c to 2o.  x, n, p, cols, m, B (m x R, HOST memory), R, stream: section 2e; no intercept;
+ *     eta(i, r) = sum_k x(i, cols[k]) * B[k * R + r], e(i, r) = exp(clamp(eta(i, r), -30, 30)).  hg: R x T doubles in HOST
+ *     memory, MODEL-major (hg[r * T + j] = the baseline cumulative hazard of model r at times[j], >= 0: the caller does the
+ *     step-function lookup); times: T >= 1 doubles (any order; no NaN); time (n), row_a (n, >= 0, finite), time_b (T, >= 0,
+ *     finite) and weight (n, >= 0, or NULL = ones) in HOST memory.  With z = hg[r * T + j] * e(i, r):
+ *         term(i, j, r) = row_a[i] * exp(-z)^2              when time[i] <= times[j]   (inclusive)
+ *                       = time_b[j] * (-expm1(-z))^2        otherwise
+ *         bs[j * R + r] = (1 / W) sum_i w_i term(i, j, r),  W = *sum_w = sum_i w_i (added on the host in row order)
+ *     One transcendental per element; 1 - S is never formed by a rounded subtraction.  row_a and time_b are plain arrays:
+ *     the entry point does not know how they were made (Kaplan-Meier weights of the censoring distribution, ones, or a
+ *     training set's).  Every term is non-negative.  hg = 0 gives exactly (1 / W) sum over time[i] <= times[j] of w_i
+ *     row_a[i].  A NaN in a support column makes the scores of exactly the models that use the column NaN.
+ *     Steps: the predictor pass of section 2e's loops writes e as R x n in row order; one reduction kernel over (row slabs
+ *     of 1024) x models forms every term in registers -- a slab's e, time, w and w * row_a are read once per workgroup, the
+ *     lanes lie along the times -- and writes one partial per (slab, model, time); a second kernel adds the slabs in
+ *     ascending order and divides by W.  No n x T element is stored; no floating-point atomics; the grids depend on (n, T,
+ *     R) alone: the same call gives the same bits.
+ *     bessx_cox_brier_workspace needs no device: *doubles of device memory in all (3 n + R n + slabs R T + 2 R T + 2 T), the
+ *     row split, and *row_groups = the sums of row groups a workgroup adds for T times (a function of T alone).
+ *     R <= 65535, T <= 2^20, n <= 2^31 - 1.  Argument errors (BESSX_ERR_ARG: the messages of section 2e for x / cols /
+ *     strides / dtype; a null pointer; T < 1; a NaN in times or time; a negative or NaN hg / weight; a negative or
+ *     non-finite row_a / time_b; weights that sum to 0) are found before any device call; without a GPU a call with valid
+ *     arguments returns BESSX_ERR_HIP.  Scratch memory is released before the call returns.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  int R;
+  const double *hg;
+  const double *times;
+  int T;
+  const double *time;
+  const double *row_a;
+  const double *time_b;
+  const double *weight;
+  void *stream;
+} bessx_cox_brier_input;
+int bessx_cox_brier_device(const bessx_cox_brier_input *in, double *bs, double *sum_w);
+int bessx_cox_brier_workspace(int n, int T, int R, long long *doubles, long long *rows_per_slab, long long *slabs,
+                              int *row_groups);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1560,6 +1608,11 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
                                   const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
                                   int n_tested, int candidate_block, int sorted, int repeats, double *stage_ms,
                                   double *bytes);
+/* The kernels of section 2p timed the same way for R models and T times, from a B, time, weights and an hg of the
+ * library's own (distinct times, T ascending times across their range): stage_ms[0] the predictor pass that stores e
+ * (R x n, row order), [1] the reduction kernel k_cxb_terms (n * T * R elements), [2] the addition of its slabs. */
+int bessx_op_cox_brier_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                             const int *cols, int m, int R, int T, int repeats, double *stage_ms);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
