@@ -42,6 +42,7 @@ SYMBOLS = [
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
     "bessx_cox_brier_device", "bessx_cox_brier_workspace", "bessx_op_cox_brier_bench",
+    "bessx_cox_auc_device", "bessx_cox_auc_workspace", "bessx_auc_device", "bessx_op_pairauc_bench",
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
     "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
     "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
@@ -115,6 +116,20 @@ class CoxBrierInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("B", _D), ("R", _i), ("hg", _D), ("times", _D), ("T", _i), ("time", _D),
                 ("row_a", _D), ("time_b", _D), ("weight", _D), ("stream", _vp)]
+
+
+class CoxAucInput(ctypes.Structure):
+    """bessx_cox_auc_input: R Cox models, X in GPU memory, T non-decreasing times, and the rows' time / status / IPCW
+    weights / case weights in host memory, the truncation time of Uno's C (NaN = none); strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("R", _i), ("times", _D), ("T", _i), ("time", _D), ("status", _D),
+                ("row_a", _D), ("weight", _D), ("tau", _d), ("want_uno", _i), ("stream", _vp)]
+
+
+class AucInput(ctypes.Structure):
+    """bessx_auc_input: R logistic models, X in GPU memory, y (shared by the models) and the weights in host memory."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("R", _i), ("y", _D), ("weight", _D), ("stream", _vp)]
 
 
 class InfoInput(ctypes.Structure):
@@ -357,6 +372,10 @@ def lib():
         L.bessx_cox_brier_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), ctypes.POINTER(_ll),
                                                 _I]
         L.bessx_op_cox_brier_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _D]
+        L.bessx_cox_auc_device.argtypes = [ctypes.POINTER(CoxAucInput), _D, _D, _D, _D, _D, _D]
+        L.bessx_cox_auc_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), ctypes.POINTER(_ll)]
+        L.bessx_auc_device.argtypes = [ctypes.POINTER(AucInput), _D, _D, _D, _D]
+        L.bessx_op_pairauc_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _D, _D]
         L.bessx_info_device.argtypes = [ctypes.POINTER(InfoInput), _D, _D]
         L.bessx_info_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
         L.bessx_op_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D]
@@ -3161,15 +3180,21 @@ def integrated_brier(times, bs):
     return area / (times[-1] - times[0])
 
 
+def _km_survival(time, status, w, order=None):
+    """The weighted Kaplan-Meier survival of the rows as a right-continuous step function (u, S): the distinct times,
+    ascending, and S at them; S = 1 before the first.  Each factor is (Y_u - ev_u) / Y_u formed from the sums it is."""
+    u, cens, ev, after = _km_steps(time, status, w, order)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = np.where(ev > 0.0, (after + cens) / (after + cens + ev), 1.0)
+    return u, np.cumprod(f)
+
+
 def brier_null(time, status, w, times, row_a, time_b, order=None):
     """(BS_null (T,), sum_w): the weighted Kaplan-Meier survival S^ of the rows put through the Brier formula,
     BS_null[j] = (S^(t_j)^2 sum_{time_i <= t_j} w_i a_i + (1 - S^(t_j))^2 b_j sum_{time_i > t_j} w_i) / W.  Host, fp64."""
     if order is None:
         order = np.argsort(time, kind="stable")
-    u, cens, ev, after = _km_steps(time, status, w, order)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        f = np.where(ev > 0.0, (after + cens) / (after + cens + ev), 1.0)
-    S = _step_at(u, np.cumprod(f), times)
+    S = _step_at(*_km_survival(time, status, w, order), times)
     ts = time[order]
     idx = np.searchsorted(ts, times, side="right")  # rows with time <= t_j
     cum_wa = np.concatenate([[0.0], np.cumsum((w * row_a)[order])])
@@ -3305,6 +3330,325 @@ def op_cox_brier_bench(x, cols, R=1, T=100, repeats=20):
     _check(lib().bessx_op_cox_brier_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                           _ip(cols), cols.size, int(R), int(T), repeats, _dp(ms)))
     return tuple(float(v) for v in ms)
+
+
+PAIRAUC_T_MAX = 1024  # the most times of cox_auc_device (PAIRAUC_T_MAX of bessx_dev.h)
+
+
+def cox_auc_workspace(n, T, R):
+    """(an upper bound of the doubles of device memory, positions per tile, an upper bound of the tiles) of a
+    cox_auc_device call on n rows, T times and R models (bessx_cox_auc_workspace; needs no device).  Nothing in it is
+    n x T or n x n."""
+    d, rows, tiles = _ll(0), _ll(0), _ll(0)
+    _check(lib().bessx_cox_auc_workspace(int(n), int(T), int(R), ctypes.byref(d), ctypes.byref(rows),
+                                         ctypes.byref(tiles)))
+    return int(d.value), int(rows.value), int(tiles.value)
+
+
+def _auc_times(times):
+    """(times float64 (T,), the stable argsort of them), checked; None = no times."""
+    if times is None:
+        times = np.zeros(0)
+    if np.ndim(times) > 1:
+        raise ValueError("times must be 1-D")
+    times = _f64(times).reshape(-1)
+    if np.isnan(times).any():
+        raise ValueError("There is NAN value in times")
+    if times.size > PAIRAUC_T_MAX:
+        raise ValueError("at most %d times per call, got %d" % (PAIRAUC_T_MAX, times.size))
+    return times, np.argsort(times, kind="stable")
+
+
+def _auc_row_a(time, status, w, censoring, order=None):
+    """row_a (n,) of the AUC / Uno's C: censoring="km": status_i / G(time_i-) from these rows (ipcw_weights without the
+    check of G at requested times: none is needed here); None: status; n values: the caller's; a pair (row_a, time_b) as
+    the Brier score takes it: its row_a."""
+    if censoring is None or isinstance(censoring, str):
+        return _ipcw_weights(time, status, w, np.zeros(0), censoring, order)[0]
+    bad = "censoring must be 'km', None, row_a (n values) or a pair (row_a, time_b), got %r" % (censoring,)
+    if isinstance(censoring, (tuple, list)) and len(censoring) == 2 and np.ndim(censoring[0]) >= 1:
+        censoring = censoring[0]
+    try:
+        row_a = _f64(censoring).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(bad) from None
+    if row_a.size != time.size:
+        raise ValueError("censoring: row_a must hold n = %d values, got %d" % (time.size, row_a.size))
+    if not (np.isfinite(row_a) & (row_a >= 0.0)).all():
+        raise ValueError("censoring: row_a must be finite and non-negative")
+    return row_a
+
+
+def _auc_tau(tau):
+    """tau of Uno's C as a float (NaN = no truncation), checked."""
+    if tau is None:
+        return float("nan")
+    tau = float(tau)
+    if np.isnan(tau):
+        raise ValueError("tau must not be NaN (None = no truncation)")
+    return tau
+
+
+def _pair_sums_host(eta, time, w, cw, times):
+    """(greater, equal) (T, R) of the cumulative/dynamic AUC in fp64 NumPy: eta (n, R); cases time_i <= t_j carry cw_i,
+    controls time_l > t_j carry w_l.  Per model one stable sort of eta, then per time one cumulative sum of the controls'
+    weights in that order: the weight strictly below a row is the running sum at the start of its group of equal eta,
+    the weight level with it the group's sum.  Sums of non-negative terms only, no subtraction; no n x T temporary."""
+    n, R = eta.shape
+    T = times.size
+    g, e = np.zeros((T, R)), np.zeros((T, R))
+    for r in range(R):
+        oe = np.argsort(eta[:, r], kind="stable")
+        es = eta[oe, r]
+        new = np.ones(n, dtype=bool)
+        new[1:] = es[1:] != es[:-1]
+        starts = np.nonzero(new)[0]
+        gid = np.cumsum(new) - 1
+        ts, ws, cs = time[oe], w[oe], cw[oe]
+        for j in range(T):
+            case = ts <= times[j]
+            v = np.where(case, 0.0, ws)
+            below = np.concatenate([[0.0], np.cumsum(v)])[starts][gid]
+            level = np.add.reduceat(v, starts)[gid]
+            u = np.where(case, cs, 0.0)
+            g[j, r], e[j, r] = np.sum(u * below), np.sum(u * level)
+    return g, e
+
+
+def _uno_sums_host(eta, time, w, cw2, order, block=512):
+    """(concordant, tied (R,), comparable) of Uno's C in fp64 NumPy: the pairs status_k = 1 (cw2_k > 0 carries it),
+    time_k < time_l, weight cw2_k w_l.  O(n^2 R) comparisons in blocks of `block` case rows against all rows: this is
+    the route without a GPU, meant for modest n."""
+    n, R = eta.shape
+    ts, ws, c2 = time[order], w[order], cw2[order]
+    tail = np.concatenate([np.cumsum(ws[::-1])[::-1], [0.0]])
+    comparable = float(np.sum(c2 * tail[np.searchsorted(ts, ts, side="right")]))
+    conc, tied = np.zeros(R), np.zeros(R)
+    rows = np.nonzero(c2 > 0.0)[0]
+    for r in range(R):
+        es = eta[order, r]
+        sc = st = 0.0
+        for b0 in range(0, rows.size, block):
+            k = rows[b0:b0 + block]
+            later = ts[None, :] > ts[k, None]
+            sc += float(np.sum(c2[k] * ((later & (es[k, None] > es[None, :])) @ ws)))
+            st += float(np.sum(c2[k] * ((later & (es[k, None] == es[None, :])) @ ws)))
+        conc[r], tied[r] = sc, st
+    return conc, tied, comparable
+
+
+def _case_control_sums(time, w, cw, times, order):
+    """(cases (T,), controls (T,)): sum of cw over time <= t_j and of w over time > t_j, running sums in time order."""
+    ts = time[order]
+    idx = np.searchsorted(ts, times, side="right")
+    return (np.concatenate([[0.0], np.cumsum(cw[order])])[idx],
+            np.concatenate([np.cumsum(w[order][::-1])[::-1], [0.0]])[idx])
+
+
+def _cox_auc_result(greater, equal, cases, controls, perm, times, time, status, w, row_a, uno, order=None):
+    """The dict of cox_auc_device / bess_base.auc_survival from the sums at the SORTED times (rows j of greater, equal,
+    cases, controls belong to times[perm[j]]) and uno = (concordant, tied, comparable): the quotients, the Kaplan-Meier
+    drops and their mean, everything returned in the caller's order of times."""
+    T, R = greater.shape
+    with np.errstate(invalid="ignore", divide="ignore"):
+        den = cases * controls
+        auc = np.where(den[:, None] > 0.0, (greater + 0.5 * equal) / den[:, None], np.nan)
+    S = _step_at(*_km_survival(time, status, w, order), times[perm])
+    drop = np.concatenate([[1.0], S])[:T] - S
+    used = drop > 0.0
+    if used.any():
+        with np.errstate(invalid="ignore"):
+            mean = np.sum(auc[used] * drop[used, None], axis=0) / np.sum(drop[used])
+    else:
+        mean = np.full(R, np.nan)
+    back = np.empty(T, dtype=np.int64)
+    back[perm] = np.arange(T)
+    conc, tied, comp = uno
+    comp = float(comp)
+    return {"auc": auc[back], "greater": greater[back], "equal": equal[back], "cases": cases[back],
+            "controls": controls[back], "km_drop": drop[back], "mean_auc": mean,
+            "uno_c": (conc + 0.5 * tied) / comp if comp > 0.0 else np.full(R, np.nan), "uno_concordant": conc,
+            "uno_tied": tied, "uno_comparable": comp, "row_a": row_a}
+
+
+def _cox_auc_host(eta, times, time, status, w, censoring, tau):
+    """cox_auc_device in fp64 NumPy from the linear predictors eta (n, R): bess_base.auc_survival for a NumPy X."""
+    times, perm = _auc_times(times)
+    tau = _auc_tau(tau)
+    order = np.argsort(time, kind="stable")
+    row_a = _auc_row_a(time, status, w, censoring, order)
+    cw = w * row_a
+    cw2 = np.where((status != 0.0) & ~(time >= tau), cw * row_a, 0.0)
+    ts = times[perm]
+    greater, equal = _pair_sums_host(eta, time, w, cw, ts)
+    cases, controls = _case_control_sums(time, w, cw, ts, order)
+    uno = _uno_sums_host(eta, time, w, cw2, order)
+    return _cox_auc_result(greater, equal, cases, controls, perm, times, time, status, w, row_a, uno, order)
+
+
+def cox_auc_device(x, cols, B, times, time, status, weight=None, censoring="km", tau=None, stream=0):
+    """The censoring-robust rank measures of R Cox models on a device matrix x (n x p: float64 or float32, any
+    non-negative strides), read once where it lies, the support's columns only (bessx_cox_auc_device).  With eta =
+    x[:, cols] @ B (no intercept), w the weights (None = ones) and a = row_a, the inverse-probability-of-censoring
+    weights of the rows (censoring="km": status_i / G(time_i-) with G = censoring_km of these rows; None: status; n
+    values, or the pair (row_a, time_b) the Brier score takes: the caller's):
+        cumulative/dynamic AUC at every t_j of times (any order, repeats allowed, at most 1024; None or empty: none):
+            cases time_i <= t_j carry w_i a_i, controls time_l > t_j carry w_l,
+            greater[j, r] = sum over cases and controls of w_i a_i w_l 1(eta_ir > eta_lr), equal[j, r]: 1(eta_ir = eta_lr),
+            auc = (greater + equal / 2) / (cases * controls), NaN where there is no case or no control;
+        mean_auc[r] = sum_j auc[j, r] d_j / sum_j d_j over the times in ascending order, d_j = S^(t_(j-1)) - S^(t_j) the
+            drop of the weighted Kaplan-Meier survival of these rows (S^ = 1 before the first time), over the times with
+            d_j > 0; NaN if one of those auc is NaN or no d_j is positive;
+        Uno's C truncated at tau (None = not truncated): the pairs status_i = 1, time_i < time_l (strictly),
+            time_i < tau carry w_i a_i^2 w_l; uno_c = (uno_concordant + uno_tied / 2) / uno_comparable, NaN without a pair.
+    time, status (0 or 1), weight (>= 0): n values each, host or device arrays (device arrays are copied to the host).
+    Returns {"auc", "greater", "equal": (T, R); "cases", "controls", "km_drop": (T,); "mean_auc", "uno_c",
+    "uno_concordant", "uno_tied": (R,); "uno_comparable": float; "row_a": (n,)}, the time axis in the caller's order.
+    One tiled pair kernel counts all of it in fp64 with no atomics and every sum in a fixed order: the same call gives the
+    same bits; only T x R numbers cross the bus, nothing n x T is stored.  The work is O(n^2 R) comparisons."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    B = np.asarray(B, dtype=np.float64)
+    R = B.shape[1] if B.ndim == 2 else 1
+    cols, B, _ = _predict_model(dx, cols, B, np.zeros(R))
+    times, perm = _auc_times(times)
+    tau = _auc_tau(tau)
+    if isinstance(censoring, str) and censoring != "km":
+        raise ValueError("censoring must be 'km', None, row_a (n values) or a pair (row_a, time_b), got %r" % (censoring,))
+    a = CoxAucInput()
+    _set_x(a, dx)
+    a.cols, a.m, a.B, a.R = _ip(cols), cols.size, _dp(B), R
+    host = _cox_data(a, time, status, weight, n, stream)  # (alive until the call has returned)
+    w = host.get("weight")
+    if w is not None and not (w >= 0.0).all():
+        raise ValueError("weight should be non-negative")
+    wv = np.ones(n) if w is None else w
+    order = np.argsort(host["time"], kind="stable")
+    row_a = np.ascontiguousarray(_auc_row_a(host["time"], host["status"], wv, censoring, order))
+    ts = np.ascontiguousarray(times[perm])
+    T = ts.size
+    a.times, a.T, a.row_a, a.tau, a.want_uno = _dp(ts), T, _dp(row_a), tau, 1
+    a.stream = int(stream) if stream else None
+    greater, equal, cases, controls = np.zeros((T, R)), np.zeros((T, R)), np.zeros(T), np.zeros(T)
+    uno, comp = np.zeros((R, 3)), _d(0)
+    _check(lib().bessx_cox_auc_device(ctypes.byref(a), _dp(greater), _dp(equal), _dp(cases), _dp(controls), _dp(uno),
+                                      ctypes.byref(comp)))
+    return _cox_auc_result(greater, equal, cases, controls, perm, times, host["time"], host["status"], wv, row_a,
+                           (np.ascontiguousarray(uno[:, 0]), np.ascontiguousarray(uno[:, 1]), comp.value), order)
+
+
+def _auc_y(y, n):
+    """y of the ROC AUC as n float64 host values shared by the models, checked."""
+    if np.ndim(y) > 1 and not (np.ndim(y) == 2 and np.shape(y)[1] == 1):
+        raise ValueError("y must hold one value per row, shared by the models, got shape %s" % (np.shape(y),))
+    y = _f64(y).reshape(-1)
+    if y.size != n:
+        raise ValueError("X.shape(0) should be equal to y.shape(0): %d rows, y has %d values" % (n, y.size))
+    if np.isnan(y).any():
+        raise ValueError("There is NAN value in y")
+    return y
+
+
+def _auc_weight(weight, n):
+    if weight is None:
+        return None
+    w = _f64(weight).reshape(-1)
+    if w.size != n:
+        raise ValueError("X.shape(0) should be equal to weight.size")
+    if not (np.isfinite(w) & (w >= 0.0)).all():
+        raise ValueError("weight should be non-negative")
+    return w
+
+
+def _auc_result(greater, equal, pos, neg):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        auc = (greater + 0.5 * equal) / (pos * neg) if pos * neg > 0.0 else np.full(greater.shape, np.nan)
+    return {"auc": auc, "greater": greater, "equal": equal, "pos_weight": float(pos), "neg_weight": float(neg)}
+
+
+def _auc_host(eta, y, weight):
+    """auc_device in fp64 NumPy from the linear predictors eta (n, R): bess_base.auc for a NumPy X."""
+    n = eta.shape[0]
+    y, w = _auc_y(y, n), _auc_weight(weight, n)
+    w = np.ones(n) if w is None else w
+    cls = np.where(y > 0.5, 0.0, 1.0)  # (the classes as times: the one cut lies at 0)
+    cut = np.zeros(1)
+    greater, equal = _pair_sums_host(eta, cls, w, w, cut)
+    pos, neg = _case_control_sums(cls, w, w, cut, np.argsort(cls, kind="stable"))
+    return _auc_result(greater[0], equal[0], pos[0], neg[0])
+
+
+def auc_device(x, cols, B, y, weight=None, stream=0):
+    """The ROC AUC of R logistic models on a device matrix x (n x p: float64 or float32, any non-negative strides), read
+    once where it lies, the support's columns only (bessx_auc_device): with eta = x[:, cols] @ B (the intercept moves no
+    rank and is not taken), cases y_i > 0.5 and controls y_l <= 0.5 (y: n values shared by the models, a host or device
+    array; an (n, R) y is a ValueError), w the weights (None = ones, else >= 0):
+        greater[r] = sum over cases and controls of w_i w_l 1(eta_ir > eta_lr), equal[r]: 1(eta_ir = eta_lr),
+        auc = (greater + equal / 2) / (pos_weight * neg_weight), NaN when a class is empty.
+    Returns {"auc", "greater", "equal": (R,); "pos_weight", "neg_weight": floats}.  The kernels of cox_auc_device with
+    the rows cut once, between the classes: fp64, no atomics, the same call gives the same bits."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    B = np.asarray(B, dtype=np.float64)
+    R = B.shape[1] if B.ndim == 2 else 1
+    cols, B, _ = _predict_model(dx, cols, B, np.zeros(R))
+    if is_device_array(y):
+        shape = _DeviceArray(y, "y").shape
+        if len(shape) > 1 and not (len(shape) == 2 and shape[1] == 1):
+            raise ValueError("y must hold one value per row, shared by the models, got shape %s" % (shape,))
+        y = device_to_host(y, stream)
+    if is_device_array(weight):
+        weight = device_to_host(weight, stream)
+    y, w = np.ascontiguousarray(_auc_y(y, n)), _auc_weight(weight, n)
+    a = AucInput()
+    _set_x(a, dx)
+    a.cols, a.m, a.B, a.R, a.y, a.weight = _ip(cols), cols.size, _dp(B), R, _dp(y), _dp(w)
+    a.stream = int(stream) if stream else None
+    greater, equal, pos, neg = np.zeros(R), np.zeros(R), _d(0), _d(0)
+    _check(lib().bessx_auc_device(ctypes.byref(a), _dp(greater), _dp(equal), ctypes.byref(pos), ctypes.byref(neg)))
+    return _auc_result(greater, equal, pos.value, neg.value)
+
+
+def _best_score(scores):
+    """The lowest index of the largest score; a NaN never wins."""
+    return int(np.argmax(np.where(np.isnan(scores), -np.inf, scores)))
+
+
+def cox_auc_candidates(result, x, time, status, times=None, weight=None, censoring="km", tau=None, by="uno_c", stream=0):
+    """The validation split by discrimination: Uno's C (by="uno_c") or the mean cumulative/dynamic AUC over `times`
+    (by="mean_auc") of every candidate of a path on held-out rows x, time, status, in ONE cox_auc_device call over the
+    union of the candidates' supports (their coef0 is ignored; no training-set baseline is needed).  Returns (scores (R,),
+    best) with best the lowest index of the largest score (a NaN never wins)."""
+    if by not in ("uno_c", "mean_auc"):
+        raise ValueError("by must be 'uno_c' or 'mean_auc', got %r" % (by,))
+    cols, B, _ = candidate_models(result)
+    scores = cox_auc_device(x, cols, B, times, time, status, weight=weight, censoring=censoring, tau=tau,
+                            stream=stream)[by]
+    return scores, _best_score(scores)
+
+
+def auc_candidates(result, x, y, weight=None, stream=0):
+    """The validation split of a logistic path by ROC AUC: every candidate on held-out rows x, y in ONE auc_device call
+    over the union of the candidates' supports (coef0 is taken from the path and ignored: it moves no rank).  Returns
+    (auc (R,), best) with best the lowest index of the largest AUC (a NaN never wins)."""
+    cols, B, _coef0 = candidate_models(result)
+    scores = auc_device(x, cols, B, y, weight=weight, stream=stream)["auc"]
+    return scores, _best_score(scores)
+
+
+def op_pairauc_bench(x, cols, R=1, T=100, repeats=5):
+    """Milliseconds per launch of the kernels behind cox_auc_device / auc_device on the device matrix x for the support
+    cols, R models and T cuts, device events, and the pairs the AUC pair kernel compares per launch: ((predictor pass
+    that stores eta in position order, the pair kernel in AUC mode, its two finish kernels, the pair kernel in Uno
+    mode), pairs)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    if int(T) < 1 or int(R) < 1:
+        raise ValueError("T and R must be at least 1")
+    ms, pairs = np.zeros(4), _d(0)
+    _check(lib().bessx_op_pairauc_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                        _ip(cols), cols.size, int(R), int(T), repeats, _dp(ms), ctypes.byref(pairs)))
+    return tuple(float(v) for v in ms), float(pairs.value)
 
 
 def op_chol_bench(m, repeats=200):

@@ -2041,6 +2041,319 @@ int bessx_op_cox_brier_bench(const void *x, int dtype, long long row_stride, lon
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------
+// weighted pair counts on a caller's device matrix: AUC(t) and Uno's C of R Cox models (include/bessx.h section 2q), the
+// ROC AUC of R logistic models (section 2r)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the host side: the order of the rows, the tiles between the cuts, the weights in position order, and the sums that
+// need no pair (all fp64, in position order)
+struct PairPlan {
+  std::vector<int> pos, first, kg, tstart, tseg, tnext, last, from;
+  std::vector<double> cw, lw, cw2, cases, controls;
+  double comparable = 0.0, pairs = 0.0;  // pairs: (k, l) the AUC mode compares, per model
+  int NT = 0, S = 1;
+};
+
+// times: T non-decreasing values; row_a, weight: null = status, ones; tau: NaN = no truncation
+void pair_plan(const double *time, const double *status, const double *row_a, const double *weight, int n,
+               const double *times, int T, double tau, PairPlan *o) {
+  const size_t N = (size_t)n;
+  std::vector<int> idx(N);
+  std::iota(idx.begin(), idx.end(), 0);
+  std::stable_sort(idx.begin(), idx.end(), [time](int a, int b) { return time[a] < time[b]; });
+  o->pos.resize(N);
+  o->first.resize(N);
+  o->kg.resize(N);
+  o->cw.resize(N);
+  o->lw.resize(N);
+  o->cw2.resize(N);
+  std::vector<double> ts(N);
+  for (int k = 0; k < n; k++) {
+    const int i = idx[(size_t)k];
+    const double w = weight ? weight[i] : 1.0, a = row_a ? row_a[i] : status[i];
+    const bool ev = status[i] != 0.0;
+    ts[(size_t)k] = time[i];
+    o->pos[(size_t)i] = k;
+    o->first[(size_t)k] = (k > 0 && ts[(size_t)k - 1] == time[i]) ? o->first[(size_t)k - 1] : k;
+    o->kg[(size_t)k] = ev ? o->first[(size_t)k] : INT_MAX;
+    o->cw[(size_t)k] = w * a;
+    o->lw[(size_t)k] = w;
+    o->cw2[(size_t)k] = (ev && !(time[i] >= tau)) ? (w * a) * a : 0.0;
+  }
+  // the segments: bnd[J] = rows with time <= times[J - 1]
+  const int S = T + 1;
+  std::vector<int> bnd((size_t)S + 1);
+  bnd[0] = 0;
+  for (int j = 0; j < T; j++) bnd[(size_t)j + 1] = (int)(std::upper_bound(ts.begin(), ts.end(), times[j]) - ts.begin());
+  bnd[(size_t)S] = n;
+  o->S = S;
+  o->tstart.clear();
+  o->tseg.clear();
+  o->last.assign((size_t)S, -1);
+  o->from.assign((size_t)S, 0);
+  for (int s = 0; s < S; s++) {
+    for (int p = bnd[(size_t)s]; p < bnd[(size_t)s + 1]; p += PAIRAUC_TILE) {
+      o->tstart.push_back(p);
+      o->tseg.push_back(s);
+    }
+    if (s < T) {  // entry j = s of k_pa_cut: the tiles of the segments <= j against the segments from j + 1 on
+      o->last[(size_t)s] = (int)o->tseg.size() - 1;
+      o->from[(size_t)s] = s + 1;
+    }
+  }
+  o->NT = (int)o->tseg.size();
+  o->tstart.push_back(n);
+  o->last[(size_t)T] = o->NT - 1;  // entry T: everything (Uno's C)
+  o->tnext.resize((size_t)o->NT);
+  for (int t = o->NT - 1, nx = o->NT; t >= 0; t--) {
+    if (t < o->NT - 1 && o->tseg[(size_t)t + 1] != o->tseg[(size_t)t]) nx = t + 1;
+    o->tnext[(size_t)t] = nx;
+  }
+  // the sums without a pair
+  std::vector<double> pc(N + 1), sl(N + 1);
+  pc[0] = 0.0;
+  for (size_t k = 0; k < N; k++) pc[k + 1] = pc[k] + o->cw[k];
+  sl[N] = 0.0;
+  for (size_t k = N; k-- > 0;) sl[k] = sl[k + 1] + o->lw[k];
+  o->cases.resize((size_t)T);
+  o->controls.resize((size_t)T);
+  for (int j = 0; j < T; j++) {
+    o->cases[(size_t)j] = pc[(size_t)bnd[(size_t)j + 1]];
+    o->controls[(size_t)j] = sl[(size_t)bnd[(size_t)j + 1]];
+  }
+  o->comparable = 0.0;
+  for (int k = n - 1, end = n; k >= 0; k--) {  // end: first position with a later time than position k
+    if (k < n - 1 && o->first[(size_t)k + 1] != o->first[(size_t)k]) end = k + 1;
+    o->comparable += o->cw2[(size_t)k] * sl[(size_t)end];
+  }
+  o->pairs = 0.0;
+  for (int t = 0; t < o->NT; t++)
+    o->pairs += (double)(o->tstart[(size_t)t + 1] - o->tstart[(size_t)t]) *
+                (double)(n - (o->tnext[(size_t)t] < o->NT ? o->tstart[(size_t)o->tnext[(size_t)t]] : n));
+}
+
+// the device side of one problem: buffers of `sc`, uploads queued on st (the vectors of the plan must outlive them)
+struct PairDev {
+  int *cols = nullptr, *pos = nullptr, *first = nullptr, *kg = nullptr, *tstart = nullptr, *tseg = nullptr,
+      *tnext = nullptr, *last = nullptr, *from = nullptr;
+  double *B = nullptr, *zero = nullptr, *cw = nullptr, *lw = nullptr, *cw2 = nullptr, *eta = nullptr, *part = nullptr,
+         *og = nullptr, *oe = nullptr;
+};
+
+template <class V>
+int pair_upload(Owner &sc, V **dst, const std::vector<V> &src, hipStream_t st) {
+  HIPX(sc.alloc(dst, src.size()));
+  HIPX(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+int pairauc_stage(Owner &sc, const PairPlan &o, const int *cols, int m, const double *B, int R, int n, int uno,
+                  hipStream_t st, PairDev *d) {
+  HIPX(sc.alloc(&d->B, (size_t)m * R + (size_t)R));
+  HIPX(sc.alloc(&d->cols, (size_t)m));
+  d->zero = d->B + (size_t)m * R;
+  HIPX(hipMemsetAsync(d->zero, 0, (size_t)R * sizeof(double), st));
+  if (m > 0) {
+    HIPX(hipMemcpyAsync(d->cols, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(d->B, B, (size_t)m * R * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  if (int rc = pair_upload(sc, &d->pos, o.pos, st)) return rc;
+  if (int rc = pair_upload(sc, &d->tstart, o.tstart, st)) return rc;
+  if (int rc = pair_upload(sc, &d->tseg, o.tseg, st)) return rc;
+  if (int rc = pair_upload(sc, &d->tnext, o.tnext, st)) return rc;
+  if (int rc = pair_upload(sc, &d->last, o.last, st)) return rc;
+  if (int rc = pair_upload(sc, &d->from, o.from, st)) return rc;
+  if (int rc = pair_upload(sc, &d->cw, o.cw, st)) return rc;
+  if (int rc = pair_upload(sc, &d->lw, o.lw, st)) return rc;
+  if (uno) {
+    if (int rc = pair_upload(sc, &d->first, o.first, st)) return rc;
+    if (int rc = pair_upload(sc, &d->kg, o.kg, st)) return rc;
+    if (int rc = pair_upload(sc, &d->cw2, o.cw2, st)) return rc;
+  }
+  HIPX(sc.alloc(&d->eta, (size_t)n * R));
+  HIPX(sc.alloc(&d->part, 2 * (size_t)R * (size_t)o.NT * (size_t)o.S));
+  HIPX(sc.alloc(&d->og, 2 * (size_t)o.S * R));
+  d->oe = d->og + (size_t)o.S * R;
+  return 0;
+}
+
+// res: (T + 1) * R greater then (T + 1) * R equal, entry T of each = Uno's sums (when uno)
+int pairauc_run(Owner &sc, std::vector<double> &h, const PairPlan &o, const bessx_cox_auc_input *in, hipStream_t st) {
+  const int n = in->n, T = in->T, R = in->R, f32 = in->x_dtype == BESSX_F32, uno = in->want_uno != 0;
+  PairDev d;
+  if (int rc = pairauc_stage(sc, o, in->cols, in->m, in->B, R, n, uno, st, &d)) return rc;
+  HIPX(launch_pairauc_eta(in->x, f32, in->x_row_stride, in->x_col_stride, n, d.cols, in->m, d.B, d.zero, R, d.pos, d.eta,
+                          st));
+  if (T > 0)
+    HIPX(launch_pairauc(d.eta, d.cw, d.lw, nullptr, nullptr, d.tstart, d.tseg, d.tnext, n, o.NT, o.S, R, 0, d.last, d.from,
+                        T, d.part, d.og, d.oe, 0, st));
+  if (uno)  // (the partials are free again: the stream has finished with them)
+    HIPX(launch_pairauc(d.eta, d.cw2, d.lw, d.kg, d.first, d.tstart, d.tseg, d.tnext, n, o.NT, o.S, R, 1, d.last + T,
+                        d.from + T, 1, d.part, d.og + (size_t)T * R, d.oe + (size_t)T * R, 0, st));
+  h.assign(2 * (size_t)o.S * R, 0.0);
+  HIPX(hipMemcpyAsync(h.data(), d.og, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  return 0;
+}
+
+int pairauc_check_sizes(const std::string &w, int R, int T) {
+  if (R > 65535) return fail(BESSX_ERR_ARG, w + ": R must be at most 65535");
+  if (T < 0) return fail(BESSX_ERR_ARG, w + ": T must not be negative");
+  if (T > PAIRAUC_T_MAX) return fail(BESSX_ERR_ARG, w + ": T must be at most " + std::to_string(PAIRAUC_T_MAX));
+  return 0;
+}
+
+inline CoxCall cox_call(const bessx_cox_auc_input *in) {
+  return CoxCall{in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,      in->p, in->cols, in->m,
+                 in->B, in->R,       in->time,         in->status,       in->weight, 1,     static_cast<hipStream_t>(in->stream)};
+}
+
+// the checks and the call of sections 2q and 2r; res as pairauc_run leaves it
+int pairauc_call(const char *who, const bessx_cox_auc_input *in, PairPlan *o, std::vector<double> *res) {
+  const std::string w(who);
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_check(who, c, false)) return rc;
+  if (int rc = pairauc_check_sizes(w, in->R, in->T)) return rc;
+  if (in->T > 0 && !in->times) return fail(BESSX_ERR_ARG, w + ": null argument");
+  for (int j = 0; j < in->T; j++) {
+    if (std::isnan(in->times[j])) return fail(BESSX_ERR_ARG, w + ": times holds a NaN");
+    if (j > 0 && in->times[j] < in->times[j - 1]) return fail(BESSX_ERR_ARG, w + ": times must not decrease");
+  }
+  for (int i = 0; i < in->n; i++) {
+    if (in->row_a && (!(in->row_a[i] >= 0.0) || !std::isfinite(in->row_a[i])))
+      return fail(BESSX_ERR_ARG, w + ": row_a must be non-negative and finite");
+    if (in->weight && (!(in->weight[i] >= 0.0) || !std::isfinite(in->weight[i])))
+      return fail(BESSX_ERR_ARG, w + ": weight must be non-negative and finite");
+  }
+  int dev = -1;
+  if (int rc = cox_check_device(who, c, &dev)) return rc;
+  pair_plan(in->time, in->status, in->row_a, in->weight, in->n, in->times, in->T, in->tau, o);
+  return dev_call(dev, c.stream, [&](DevCall &dc) {
+    if (int rc = pairauc_run(dc.sc, dc.h, *o, in, dc.st)) return rc;
+    *res = dc.h;
+    return 0;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_auc_workspace(int n, int T, int R, long long *doubles, long long *tile_rows, long long *tiles_max) {
+  const std::string w("cox_auc_workspace");
+  if (!doubles || !tile_rows || !tiles_max) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (n < 1 || R < 1) return fail(BESSX_ERR_ARG, w + ": n and R must be at least 1");
+  if (int rc = pairauc_check_sizes(w, R, T)) return rc;
+  *doubles = pairauc_workspace(n, T, R);
+  *tile_rows = PAIRAUC_TILE;
+  *tiles_max = pairauc_tiles_max(n, T);
+  return BESSX_OK;
+}
+
+int bessx_cox_auc_device(const bessx_cox_auc_input *in, double *greater, double *equal, double *cases, double *controls,
+                         double *uno, double *uno_comparable) {
+  const std::string w("cox_auc_device");
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->T > 0 && (!greater || !equal || !cases || !controls)) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->want_uno && (!uno || !uno_comparable)) return fail(BESSX_ERR_ARG, w + ": want_uno needs uno and uno_comparable");
+  PairPlan o;
+  std::vector<double> res;
+  if (int rc = pairauc_call("cox_auc_device", in, &o, &res)) return rc;
+  const size_t T = (size_t)in->T, R = (size_t)in->R, SR = (T + 1) * R;
+  std::copy(res.begin(), res.begin() + (long long)(T * R), greater);
+  std::copy(res.begin() + (long long)SR, res.begin() + (long long)(SR + T * R), equal);
+  std::copy(o.cases.begin(), o.cases.end(), cases);
+  std::copy(o.controls.begin(), o.controls.end(), controls);
+  if (in->want_uno) {
+    for (size_t r = 0; r < R; r++) {
+      uno[3 * r] = res[T * R + r];
+      uno[3 * r + 1] = res[SR + T * R + r];
+      uno[3 * r + 2] = o.comparable;
+    }
+    *uno_comparable = o.comparable;
+  }
+  return BESSX_OK;
+}
+
+int bessx_auc_device(const bessx_auc_input *in, double *greater, double *equal, double *pos_weight, double *neg_weight) {
+  const std::string w("auc_device");
+  if (!in || !greater || !equal || !pos_weight || !neg_weight) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->n < 1 || in->p < 1) return fail(BESSX_ERR_ARG, w + ": empty matrix");
+  if (!in->y) return fail(BESSX_ERR_ARG, w + ": null argument");
+  // the classes as times: a case leaves at 0, a control at 1, and the one cut lies at 0
+  std::vector<double> cls((size_t)in->n), ones((size_t)in->n, 1.0);
+  for (int i = 0; i < in->n; i++) {
+    if (std::isnan(in->y[i])) return fail(BESSX_ERR_ARG, w + ": y holds a NaN");
+    cls[(size_t)i] = in->y[i] > 0.5 ? 0.0 : 1.0;
+  }
+  const double cut = 0.0;
+  const bessx_cox_auc_input c{in->x,      in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,      in->p,
+                              in->cols,   in->m,       in->B,            in->R,            &cut,       1,
+                              cls.data(), ones.data(), nullptr,          in->weight,       std::nan(""), 0,
+                              in->stream};
+  PairPlan o;
+  std::vector<double> res;
+  if (int rc = pairauc_call("auc_device", &c, &o, &res)) return rc;
+  const size_t R = (size_t)in->R;
+  std::copy(res.begin(), res.begin() + (long long)R, greater);
+  std::copy(res.begin() + 2 * (long long)R, res.begin() + 3 * (long long)R, equal);
+  *pos_weight = o.cases[0];
+  *neg_weight = o.controls[0];
+  return BESSX_OK;
+}
+
+int bessx_op_pairauc_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                           const int *cols, int m, int R, int T, int repeats, double *stage_ms, double *pairs) {
+  const std::string w("op_pairauc_bench");
+  if (repeats < 1 || !stage_ms || !pairs) return fail(BESSX_ERR_ARG, w + ": bad arguments");
+  if (!x) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = predict_check_model("op_pairauc_bench", n, p, cols, m, R, BESSX_LINK_IDENTITY)) return rc;
+  if (int rc = pairauc_check_sizes(w, R, T)) return rc;
+  if (T < 1) return fail(BESSX_ERR_ARG, w + ": T must be at least 1");
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_pairauc_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m * R), time((size_t)n), status((size_t)n), tg((size_t)T);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int i = 0; i < n; i++) {  // distinct times in an order that is not the rows'
+    time[(size_t)i] = (double)(((long long)i * 7919) % n) + (double)i / (2.0 * n);
+    status[(size_t)i] = (double)(i % 2);
+  }
+  for (int j = 0; j < T; j++) tg[(size_t)j] = (j + 0.5) * (double)n / T;
+  PairPlan o;
+  pair_plan(time.data(), status.data(), nullptr, nullptr, n, tg.data(), T, std::nan(""), &o);
+  Owner sc;
+  PairDev d;
+  if (int rc = pairauc_stage(sc, o, cols, m, B.data(), R, n, 1, nullptr, &d)) return rc;
+  HIPX(hipDeviceSynchronize());
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
+  const int f32 = dtype == BESSX_F32;
+  for (int stage = 0; stage < 4; stage++) {
+    float ms = 0.f;
+    if (int rc = bt.run(repeats, &ms, [&]() -> int {
+          if (stage == 0)
+            HIPX(launch_pairauc_eta(x, f32, row_stride, col_stride, n, d.cols, m, d.B, d.zero, R, d.pos, d.eta, nullptr));
+          else if (stage < 3)
+            HIPX(launch_pairauc(d.eta, d.cw, d.lw, nullptr, nullptr, d.tstart, d.tseg, d.tnext, n, o.NT, o.S, R, 0, d.last,
+                                d.from, T, d.part, d.og, d.oe, stage, nullptr));
+          else
+            HIPX(launch_pairauc(d.eta, d.cw2, d.lw, d.kg, d.first, d.tstart, d.tseg, d.tnext, n, o.NT, o.S, R, 1,
+                                d.last + T, d.from + T, 1, d.part, d.og + (size_t)T * R, d.oe + (size_t)T * R, 1, nullptr));
+          return 0;
+        }))
+      return rc;
+    stage_ms[stage] = ms / repeats;
+  }
+  *pairs = o.pairs * R;
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
 // expected information and score of one model on a caller's device matrix (include/bessx.h section 2g)
 // ----------------------------------------------------------------------------------------------
 namespace {

@@ -127,6 +127,24 @@ hipError_t launch_cox_brier_ex(const void *src, int f32, long long rs, long long
 hipError_t launch_cox_brier(const double *e, const double *time, const double *w, const double *wa, const double *hg,
                             const double *tg, const double *b, long long n, int T, int R, double W, double *part,
                             double *bs, int only, hipStream_t st);
+// weighted pair counts of R models (bessx_k_pairauc.hip): AUC(t), Uno's C, ROC AUC.  _eta: eta[r * n + pos[i]] =
+// eta(i, r) (src, cols, B (m x R) as in launch_predict; zero: R doubles of 0.0).  launch_pairauc: the positions are cut
+// into NT tiles of 1 .. PAIRAUC_TILE consecutive positions (tstart: NT + 1 ints, tstart[NT] = n; tseg[tile] < S: its
+// segment, ascending; tnext[tile]: the first tile of a later segment, NT where there is none); the pair kernel writes
+// part[((r * NT + kt) * S + b) * 2 + {0, 1}] = sum over k in tile kt, l in segment b of cw[k] lw[l] 1(eta_k > eta_l) /
+// 1(eta_k = eta_l) for the segments after the tile's own (uno: from the tile's own on, and only where first[l] > kg[k]);
+// the finish adds the tiles in order and writes og / oe[q * R + r] = sum_{kt <= last[q]} sum_{b >= from[q]} part (Q
+// entries; last[q] < 0 gives 0).  part: 2 R NT S doubles; only = 1 / 2 launches the pair kernel / the finish alone.
+// _tiles_max, _workspace: upper bounds of NT and of the doubles of device memory of a call.  Everything else is device memory.
+constexpr int PAIRAUC_TILE = 1024, PAIRAUC_T_MAX = 1024;
+long long pairauc_tiles_max(long long n, int T);
+long long pairauc_workspace(long long n, int T, int R);
+hipError_t launch_pairauc_eta(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                              const double *B, const double *zero, int R, const int *pos, double *eta, hipStream_t st);
+hipError_t launch_pairauc(const double *eta, const double *cw, const double *lw, const int *kg, const int *first,
+                          const int *tstart, const int *tseg, const int *tnext, long long n, int NT, int S, int R, int uno,
+                          const int *last, const int *from, int Q, double *part, double *og, double *oe, int only,
+                          hipStream_t st);
 // expected information and score of one model (bessx_k_info.hip): with eta as in launch_predict (R = 1), v_i / g_i the
 // working and score weights of the link and z_i = (1, x(i, cols[0]), ...), info = sum_i v_i z_i z_i^T ((m + 1) x (m + 1),
 // leading dimension ld, both triangles, mirrors of each other) and score = sum_i g_i z_i (m + 1); res: launch_eval's

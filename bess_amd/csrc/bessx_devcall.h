@@ -1,6 +1,6 @@
 #ifndef BESSX_DEVCALL_H
 #define BESSX_DEVCALL_H
-// bessx_devcall.h -- what the entry points that take a caller's X in GPU memory share (include/bessx.h sections 2c to 2p,
+// bessx_devcall.h -- what the entry points that take a caller's X in GPU memory share (include/bessx.h sections 2c to 2r,
 // in bessx_abi.cpp): a view of the call's arguments with its checks, the scope one call runs in,
 // the copy of staged results to the caller's host memory, and the timing of the single-kernel benches.
 #include "bessx_host.h"

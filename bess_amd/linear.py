@@ -60,6 +60,10 @@ class bess_base:
     have seen: the time-dependent Brier score under inverse-probability-of-censoring weights, the Kaplan-Meier null
     model's, IPA = 1 - brier / null and the integrated scores.  For an X in GPU memory one fused reduction
     (capi.cox_brier_device) forms every term in registers: no curve is stored.
+    auc_survival(X, y, times=None, weight=None, censoring="km", tau=None) (Cox) and auc(X, y, weight=None) (Logistic) say
+    how well the model ranks such rows: the cumulative/dynamic AUC(t) with its Kaplan-Meier-weighted mean and Uno's C,
+    and the ROC AUC.  For an X in GPU memory one tiled kernel counts the weighted pairs (capi.cox_auc_device /
+    capi.auc_device); any other model type raises a ValueError that names it.
     inference(X, y, weight=None) is the coefficient table of the fitted model on these rows (Lm, Logistic, Poisson; None
     for Cox; a 2-D beta raises): coef (intercept first), se, z, p_value (two-sided normal), cov, score, dispersion, dof,
     cond, positive_definite and cols, from the unpenalised expected information sum_i v_i z_i z_i^T of the selected
@@ -1589,6 +1593,54 @@ class bess_base:
         out["brier"], out["ipa"] = got["brier"][:, 0], got["ipa"][:, 0]
         out["ibs"] = float(np.asarray(got["ibs"]).reshape(-1)[0])
         return out
+
+    # ---- discrimination: AUC(t) and Uno's C (Cox), ROC AUC (Logistic) ------------------------------------------------
+    def auc_survival(self, X, y, times=None, weight=None, censoring="km", tau=None):
+        """Cox only: how well the fitted model ranks rows it may not have seen, robust to the censoring pattern: the
+        cumulative/dynamic AUC at the times given (any order; None: none), its mean weighted by the drops of the rows'
+        Kaplan-Meier survival, and Uno's C truncated at tau (None: not truncated).  y = (time, status) as in fit, weight n
+        values >= 0 or None, censoring "km" (Kaplan-Meier weights from these rows), None, row_a (n values) or the pair
+        (row_a, time_b) of brier_survival.  Returns the dict of capi.cox_auc_device for the one model: "auc", "greater",
+        "equal", "cases", "controls", "km_drop" (T,), "mean_auc", "uno_c", "uno_concordant", "uno_tied",
+        "uno_comparable" (floats), "row_a".  An X in GPU memory is read once, in place, on torch's current stream, by a
+        tiled pair kernel; a NumPy X is served in fp64 NumPy (a sort, then running sums per time; Uno's C by blocks of
+        pairs)."""
+        if self.model_type_int != 4:
+            raise ValueError("auc_survival is for the Cox classes, this is a %s model" % self.model_type)
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        if not (w >= 0.0).all():
+            raise ValueError("weight should be non-negative")
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.cox_auc_device(X, cols, beta[cols], times, time, status, weight=None if weight is None else w,
+                                      censoring=censoring, tau=tau, stream=_current_stream(X))
+        else:
+            got = capi._cox_auc_host(self._support_eta(X, cols, beta).reshape(-1, 1), times, time, status, w, censoring,
+                                     tau)
+        out = dict(got)
+        for k in ("auc", "greater", "equal"):
+            out[k] = got[k][:, 0]
+        for k in ("mean_auc", "uno_c", "uno_concordant", "uno_tied"):
+            out[k] = float(np.asarray(got[k]).reshape(-1)[0])
+        return out
+
+    def auc(self, X, y, weight=None):
+        """Logistic only: the ROC AUC of the fitted model on rows it may not have seen -- the weighted share of (case,
+        control) pairs that the linear predictor orders correctly, ties counting half; cases are y > 0.5.  weight: n
+        values >= 0 or None.  Returns {"auc", "greater", "equal", "pos_weight", "neg_weight"} as floats (auc is NaN when
+        a class is empty): capi.auc_device.  An X in GPU memory is read once, in place, on torch's current stream; a
+        NumPy X is served in fp64 NumPy (a sort and a running sum)."""
+        if self.model_type_int != 2:
+            raise ValueError("auc is for the Logistic classes, this is a %s model" % self.model_type)
+        on_device, n = self._survival_x(X)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if on_device:
+            got = capi.auc_device(X, cols, beta[cols], y, weight=weight, stream=_current_stream(X))
+        else:
+            got = capi._auc_host(self._support_eta(X, cols, beta).reshape(-1, 1), y, weight)
+        return {k: float(np.asarray(v).reshape(-1)[0]) for k, v in got.items()}
 
 
 def _make(name, algorithm_type, model_type):

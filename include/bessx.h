@@ -1146,6 +1146,82 @@ typedef struct {
 int bessx_cox_brier_device(const bessx_cox_brier_input *in, double *bs, double *sum_w);
 int bessx_cox_brier_workspace(int n, int T, int R, long long *doubles, long long *rows_per_slab, long long *slabs,
                               int *row_groups);
+/* ---------------------------------------------------------------------------------------
+ * 2q. The censoring-robust rank measures of R Cox models on an X already in GPU memory (bessx_k_pairauc.hip): the
+ *     numerators of the cumulative/dynamic AUC(t) at T times (Uno et al. 2007; Hung and Chiang 2010) and of Uno's C
+ *     (Uno et al. 2011), as weighted counts of ordered pairs of rows.  Stateless like sections 2c to 2p.  x, n, p, cols,
+ *     m, B (m x R, HOST memory), R, stream: section 2e; no intercept; eta(i, r) = sum_k x(i, cols[k]) * B[k * R + r].
+ *     times: T >= 0 doubles in HOST memory, NON-DECREASING (repeats allowed; no NaN); time, status (0 or 1), row_a
+ *     (>= 0, finite: status_i / G(time_i-) for an inverse-probability-of-censoring estimate G, or status itself) and
+ *     weight (>= 0, finite, or NULL = ones): n doubles each in HOST memory.  With w_i the weights:
+ *         greater[j * R + r] = sum over time_i <= times[j] < time_l of w_i row_a[i] w_l 1(eta_ir > eta_lr)
+ *         equal  [j * R + r] = the same with 1(eta_ir = eta_lr)
+ *         cases[j] = sum_{time_i <= times[j]} w_i row_a[i],      controls[j] = sum_{time_l > times[j]} w_l
+ *     and, when want_uno is not 0 (tau: the truncation time; NaN = none),
+ *         uno[3 r], uno[3 r + 1] = sum over status_i = 1, time_i < time_l (strictly), time_i < tau of
+ *                                  w_i row_a[i]^2 w_l 1(eta_ir > eta_lr) / 1(eta_ir = eta_lr)
+ *         uno[3 r + 2] = *uno_comparable = the same sum without the indicator (the same for every model).
+ *     AUC(t_j) = (greater + equal / 2) / (cases * controls) and C = (uno[0] + uno[1] / 2) / uno[2] are the caller's: half
+ *     credit for ties in eta is never applied here.  Any of greater / equal / cases / controls may be NULL when T = 0.
+ *     Steps: the host sorts the rows by time (stable) and cuts the positions at the T cuts into tiles of at most 1024
+ *     that straddle no cut; the predictor pass of section 2e's loops writes eta as R x n in that order; one kernel over
+ *     (tiles x models) keeps a tile's eta in registers, streams the later tiles through LDS and adds w_l 1(.) into fp64
+ *     accumulators per row, which it reduces in a fixed order into a slot of its own per (model, tile, segment of l); a
+ *     second adds the tiles in order and a third the segments on the far side of every cut.  No atomics of any kind, no
+ *     n x T and no n x n array; the grids depend on (n, the cuts, R) alone: the same call gives the same bits.  Work is
+ *     O(n^2 R) comparisons (twice that with want_uno and T > 0).
+ *     bessx_cox_auc_workspace needs no device: *doubles = an upper bound of the device memory of a call in doubles
+ *     (R n + 3 n + 2 R tiles_max (T + 1) + 2 R (T + 1), plus the int tables), *tile_rows = 1024, *tiles_max = ceil(n /
+ *     1024) + T.  R <= 65535, T <= 1024, n <= 2^31 - 1.  Argument errors (BESSX_ERR_ARG: the messages of section 2e for
+ *     x / cols / strides / dtype; a null pointer; T < 0 or T > 1024; times that decrease or hold a NaN; a NaN in time; a
+ *     status that is not 0 or 1; a negative or non-finite row_a / weight) are found before any device call; without a GPU
+ *     a call with valid arguments returns BESSX_ERR_HIP.  Scratch memory is released before the call returns.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  int R;
+  const double *times;
+  int T;
+  const double *time;
+  const double *status;
+  const double *row_a;
+  const double *weight;
+  double tau;
+  int want_uno;
+  void *stream;
+} bessx_cox_auc_input;
+int bessx_cox_auc_device(const bessx_cox_auc_input *in, double *greater, double *equal, double *cases, double *controls,
+                         double *uno, double *uno_comparable);
+int bessx_cox_auc_workspace(int n, int T, int R, long long *doubles, long long *tile_rows, long long *tiles_max);
+/* ---------------------------------------------------------------------------------------
+ * 2r. The numerators of the ROC AUC of R logistic models on an X already in GPU memory: section 2q's kernels with the
+ *     rows cut once, between the classes.  y: n doubles in HOST memory, shared by the models (no NaN); a row is a case
+ *     when y_i > 0.5 and a control otherwise.  weight: n doubles >= 0, finite, or NULL = ones.
+ *         greater[r] = sum over cases i, controls l of w_i w_l 1(eta_ir > eta_lr),   equal[r]: 1(eta_ir = eta_lr)
+ *         *pos_weight = sum of w over the cases,   *neg_weight = sum of w over the controls
+ *     AUC = (greater + equal / 2) / (pos_weight * neg_weight) is the caller's.  The intercept moves no rank and is not
+ *     taken.  Limits, errors and determinism as in section 2q (T = 1).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  int R;
+  const double *y;
+  const double *weight;
+  void *stream;
+} bessx_auc_input;
+int bessx_auc_device(const bessx_auc_input *in, double *greater, double *equal, double *pos_weight, double *neg_weight);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1613,6 +1689,12 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
  * (R x n, row order), [1] the reduction kernel k_cxb_terms (n * T * R elements), [2] the addition of its slabs. */
 int bessx_op_cox_brier_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                              const int *cols, int m, int R, int T, int repeats, double *stage_ms);
+/* The kernels of sections 2q and 2r timed the same way for R models and T >= 1 cuts, from a B, times, a status and
+ * weights of the library's own (distinct times, T ascending cuts across their range): stage_ms[0] the predictor pass
+ * that stores eta (R x n, position order), [1] the pair kernel k_pa_pairs in AUC mode, [2] its two finish kernels, [3]
+ * the pair kernel in Uno mode; *pairs = the pairs (k, l) stage 1 compares per launch, all models together. */
+int bessx_op_pairauc_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                           const int *cols, int m, int R, int T, int repeats, double *stage_ms, double *pairs);
 
 /* ---------------------------------------------------------------------------------------
  * 5. A communicator for hosts without torch.distributed (round 6): the ONE collective the sharded paths need -- an
