@@ -32,7 +32,8 @@ SYMBOLS = [
     "bessx_session_set_fill_hook", "bessx_session_set_kpath_chains",
     "bessx_session_marginal_scores", "bessx_session_cov_prefill_begin", "bessx_session_cov_prefill_compute",
     "bessx_session_cov_prefill_export", "bessx_session_cov_prefill_import", "bessx_session_cov_prefill_end",
-    "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
+    "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_session_cov_cache_columns",
+    "bessx_session_cv_fill_geometry", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
     "bessx_op_cox_state", "bessx_op_cox_score", "bessx_op_cox_score_multi", "bessx_op_glm_gh", "bessx_op_glm_irls", "bessx_op_glm_irls_geometry",
     "bessx_op_group_scores", "bessx_op_group_lsq",
@@ -320,6 +321,8 @@ def lib():
         L.bessx_session_cov_prefill_begin.argtypes = [_vp, _I, _i]
         L.bessx_session_cov_prefill_extend.argtypes = [_vp, _I, _i]
         L.bessx_session_cov_state.argtypes = [_vp, _D, _I]
+        L.bessx_session_cov_cache_columns.argtypes = [_vp, _i, _I, _i, _D, _I]
+        L.bessx_session_cv_fill_geometry.argtypes = [_vp, _I]
         L.bessx_session_cov_prefill_compute.argtypes = [_vp, _i, _i]
         L.bessx_session_cov_prefill_export.argtypes = [_vp, _i, _i, _vp, _i]
         L.bessx_session_cov_prefill_import.argtypes = [_vp, _i, _i, _vp, _i]
@@ -945,6 +948,23 @@ class Session:
         bd, so = np.zeros(self.p_kept), np.zeros(self.p_kept, dtype=np.int32)
         _check(lib().bessx_session_cov_state(self._h, _dp(bd), _ip(so)))
         return bd, so
+
+    def cov_cache_columns(self, row_set, cols):
+        """(G, cached): the Gram columns row set `row_set` (0 = all rows, k + 1 = training rows of fold k) holds cached
+        for `cols`, p x len(cols), and which of them it holds (bool); columns of G that are not cached are NaN.
+        Read-only (bessx_session_cov_cache_columns)."""
+        c = _i32(cols)
+        out = np.full((c.size, self.p_kept), np.nan)
+        hit = np.zeros(c.size, dtype=np.int32)
+        _check(lib().bessx_session_cov_cache_columns(self._h, int(row_set), _ip(c), c.size, _dp(out), _ip(hit)))
+        return out.T.copy(), hit.astype(bool)
+
+    def cv_fill_geometry(self):
+        """How the CV row sets' Gram fills run (bessx_session_cv_fill_geometry): shared fills or masked ones, and the
+        geometry of the fold-major copy (0 unless shared)."""
+        g = np.zeros(4, dtype=np.int32)
+        _check(lib().bessx_session_cv_fill_geometry(self._h, _ip(g)))
+        return {"shared": bool(g[0]), "cvp_nsl": int(g[1]), "cvp_rps": int(g[2]), "copy_rows": int(g[3])}
 
     def cov_prefill_compute(self, g0, ngroups):
         _check(lib().bessx_session_cov_prefill_compute(self._h, int(g0), int(ngroups)))

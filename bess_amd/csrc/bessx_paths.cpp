@@ -939,6 +939,45 @@ int bessx_session_cov_state(bessx_session *s, double *bd, int *slot_of) {
   return BESSX_OK;
 }
 
+// Diagnostic, read-only: the cached Gram columns of ONE row set (0 = all rows, k + 1 = the training rows of fold k), on
+// sessions with and without folds.  The fold contexts of the side-by-side chains borrow the session's caches
+// (fold_ctx_create copies the cov vector: the pointers are the owner's), so the owner's caches are what every fit of
+// the row set reads, wherever it ran; their streams are waited for as well.  Nothing is allocated, queued or written.
+int bessx_session_cov_cache_columns(bessx_session *s, int row_set, const int *cols, int ncols, double *dst, int *cached) {
+  if (!s) return fail(BESSX_ERR_ARG, "null session");
+  if (!s->cov_mode || s->model_type != 1 || s->cov.empty())
+    return fail(BESSX_ERR_UNSUPPORTED, "cov_cache_columns: the session does not run the covariance form of the LM score pass");
+  if (row_set < 0 || row_set >= (int)s->cov.size() || ncols < 0 || (ncols > 0 && (!cols || !dst || !cached)))
+    return fail(BESSX_ERR_ARG, "cov_cache_columns: bad row set or arguments");
+  for (int i = 0; i < ncols; i++)
+    if (cols[i] < 0 || cols[i] >= s->p) return fail(BESSX_ERR_ARG, "cov_cache_columns: column out of range");
+  HIPX(hipSetDevice(s->device));
+  HIPX(hipStreamSynchronize(s->st));
+  for (bessx_session *c : s->fold_ctx) HIPX(hipStreamSynchronize(c->st));
+  const bessx_session::CovCache &cv = s->cov[(size_t)row_set];
+  std::vector<int> slot((size_t)s->p);
+  HIPX(hipMemcpy(slot.data(), cv.slot_of, slot.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < ncols; i++) {
+    const int sl = slot[(size_t)cols[i]];
+    cached[i] = sl >= 0 && sl < s->cov_C ? 1 : 0;
+    if (cached[i])
+      HIPX(hipMemcpy(dst + (size_t)i * s->p, cv.G + (size_t)sl * s->p, (size_t)s->p * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return BESSX_OK;
+}
+
+// How the folds' Gram fills run: out[0] = 1 shared fills (one pass over the fold-major copy serves every row set), 0
+// masked per-row-set fills (no folds, another form of the score pass, the test hook, or the copy was refused);
+// out[1] = slabs per fold, out[2] = rows per slab, out[3] = rows of the fold-major copy (all 0 without shared fills).
+int bessx_session_cv_fill_geometry(const bessx_session *s, int *out) {
+  if (!s || !out) return fail(BESSX_ERR_ARG, "null argument");
+  out[0] = s->cv_shared ? 1 : 0;
+  out[1] = s->cv_shared ? s->cvp_nsl : 0;
+  out[2] = s->cv_shared ? s->cvp_rps : 0;
+  out[3] = s->cv_shared ? (int)s->ldp : 0;
+  return BESSX_OK;
+}
+
 int bessx_session_cov_prefill_compute(bessx_session *s, int g0, int ngroups) {
   if (int rc = prefill_ready(s)) return rc;
   if (g0 < 0 || ngroups < 0 || (g0 + ngroups) * COV_R > s->prefill_cols) return fail(BESSX_ERR_ARG, "cov_prefill: group range");

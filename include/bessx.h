@@ -1458,6 +1458,18 @@ int bessx_session_cov_prefill_compute(bessx_session *s, int g0, int ngroups);
 int bessx_session_cov_prefill_export(bessx_session *s, int g0, int ngroups, double *dst, int dst_on_device);
 int bessx_session_cov_prefill_import(bessx_session *s, int g0, int ngroups, const double *src, int src_on_device);
 int bessx_session_cov_prefill_end(bessx_session *s);
+/* Diagnostic, read-only: the Gram columns X^T diag(m_r) x_c that row set r (0 = all rows, k + 1 = the training rows of
+ * fold k) holds cached right now, on sessions with and without CV folds, whichever way the folds' caches are filled.
+ * cached[i] = 1 if cols[i] is in THAT row set's cache (its own slot map: row set 0's where the folds share their fills);
+ * then dst[i * p .. (i + 1) * p) is the column, all p entries, as bessx_session_cov_prefill_export lays a block out.
+ * The entries of dst for uncached columns are left as they are.  Waits for the session's streams; changes no state and
+ * queues nothing.  BESSX_ERR_UNSUPPORTED outside the covariance form of the LM score pass, BESSX_ERR_ARG for a row set
+ * the session does not have or a column outside 0 .. p-1. */
+int bessx_session_cov_cache_columns(bessx_session *s, int row_set, const int *cols, int ncols, double *dst, int *cached);
+/* How the Gram fills of the CV row sets run.  out[0]: 1 = shared (one unmasked pass over a fold-major copy of X, every
+ * fold padded to whole row slabs, serves all K + 1 row sets), 0 = one masked pass per row set (also: no folds).
+ * out[1]: row slabs per fold, out[2]: rows per slab, out[3]: rows of the copy = K * out[1] * out[2]; 0 unless shared. */
+int bessx_session_cv_fill_geometry(const bessx_session *s, int *out /* 4 */);
 
 /* How many chunk chains bessx_session_sequential_path may run side by side (bessx_kchunks.cpp):
  * 0 = automatic, 1 = one chain, 2..8 = that many where the path qualifies.  The initial value is BESSX_KPATH_CHAINS (else

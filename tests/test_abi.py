@@ -62,3 +62,6 @@ def test_argument_validation_needs_no_gpu():
     pb = capi.Problem()
     pb.n, pb.p = 0, 3
     assert lib.bessx_session_create(ctypes.byref(h), ctypes.byref(pb)) == 1
+    geo = (ctypes.c_int * 4)()
+    assert lib.bessx_session_cov_cache_columns(None, 0, None, 0, None, None) == 1
+    assert lib.bessx_session_cv_fill_geometry(None, geo) == 1

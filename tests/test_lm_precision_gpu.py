@@ -10,9 +10,11 @@ runs (k_col_normalize: one workgroup per column, independent of the row padding;
 x_norm are bitwise op_normalize's).
 
 What is not reachable through the ABI, and therefore not covered: the scores of a streaming session (cov_state serves the
-covariance form only; marginal_scores is compared in both modes); Gram columns of a CV row set (the prefill export serves
-row set 0 of sessions without folds only -- masked Gram columns are covered through the fold fits of (a)); the hand-over at
-CGB_MAX_K from bessx_cgbig.hip to the blocked Cholesky is listed in LARGE_T0 and runs in its own test.
+covariance form only; marginal_scores is compared in both modes).  Gram columns of a CV row set are not compared HERE (the
+prefill export serves row set 0 of sessions without folds only): tests/test_cv_gram_gpu.py holds every row set's cached
+columns -- shared fills, masked fills, the refused fold-major copy, more than one slab per fold -- to the same bound through
+bessx_session_cov_cache_columns.  The hand-over at CGB_MAX_K from bessx_cgbig.hip to the blocked Cholesky is listed in
+LARGE_T0 and runs in its own test.
 Also not covered: the score VALUES of the fused launches.  cov_state is compared after traced fits (the trace names the
 model the last scores were formed from), and tracing switches the fused selection + solve launch (k_sel_cgr) off, so (c)
 sees k_cov_d followed by the unfused selection; the fused launches are held to the coefficient and loss bounds of (a)
