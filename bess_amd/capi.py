@@ -42,6 +42,8 @@ SYMBOLS = [
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
+    "bessx_cox_hazard_var_device", "bessx_cox_hazard_var_workspace", "bessx_cox_band_device", "bessx_cox_band_workspace",
+    "bessx_op_cox_band_bench",
     "bessx_cox_brier_device", "bessx_cox_brier_workspace", "bessx_op_cox_brier_bench",
     "bessx_cox_auc_device", "bessx_cox_auc_workspace", "bessx_auc_device", "bessx_op_pairauc_bench",
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
@@ -109,6 +111,24 @@ class CoxSurvivalInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("B", _D), ("hg", _D), ("T", _i), ("kind", _i), ("out_row_stride", _ll),
                 ("out_col_stride", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class CoxHazardVarInput(ctypes.Structure):
+    """bessx_cox_hazard_var_input: one Cox model, X in GPU memory, time / status / weight and the T grid times in host
+    memory."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
+                ("times", _D), ("T", _i), ("stream", _vp)]
+
+
+class CoxBandInput(ctypes.Structure):
+    """bessx_cox_band_input: one Cox model, X in GPU memory, cumhaz / var0 / drift at T times and the factor of the
+    inverse information in host memory, what is wanted and how out is laid out; strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("cumhaz", _D), ("var0", _D), ("drift", _D), ("drift_ld", _ll),
+                ("T", _i), ("factor", _D), ("factor_ld", _ll), ("kind", _i), ("conf_type", _i), ("z_c", _d),
+                ("what", ctypes.c_uint), ("out_slab_stride", _ll), ("out_row_stride", _ll), ("out_col_stride", _ll),
+                ("out_on_device", _i), ("stream", _vp)]
 
 
 class CoxBrierInput(ctypes.Structure):
@@ -371,6 +391,11 @@ def lib():
         L.bessx_cox_baseline_device.argtypes = [ctypes.POINTER(CoxBaselineInput), _I, _D, _D]
         L.bessx_cox_survival_device.argtypes = [ctypes.POINTER(CoxSurvivalInput), _vp]
         L.bessx_op_cox_surv_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
+        L.bessx_cox_hazard_var_device.argtypes = [ctypes.POINTER(CoxHazardVarInput), _D, _D, _D, _ll, _D]
+        L.bessx_cox_hazard_var_workspace.argtypes = [_i, _i, _i, _i, ctypes.POINTER(_ll)]
+        L.bessx_cox_band_device.argtypes = [ctypes.POINTER(CoxBandInput), _vp]
+        L.bessx_cox_band_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, ctypes.c_uint, _i, ctypes.POINTER(_ll), _I]
+        L.bessx_op_cox_band_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, ctypes.c_uint, _i, _D]
         L.bessx_cox_brier_device.argtypes = [ctypes.POINTER(CoxBrierInput), _D, _D]
         L.bessx_cox_brier_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), ctypes.POINTER(_ll),
                                                 _I]
@@ -3065,6 +3090,202 @@ def cox_survival_device(x, cols, B, base_times, base_cumhaz, times=None, kind="s
     a.stream = int(stream) if stream else None
     _check(lib().bessx_cox_survival_device(ctypes.byref(a), ptr))
     return result
+
+
+BAND_CONF = {"plain": 0, "log": 1, "log-log": 2}  # BESSX_BAND_PLAIN / _LOG / _LOGLOG
+BAND_WHAT = ("estimate", "se", "lower", "upper")  # bits 1, 2, 4, 8 (BESSX_BAND_*), the order of the slabs
+
+
+def normal_quantile(level):
+    """z with P(|N(0, 1)| <= z) = level, on the host: the root of erfc(z / sqrt 2) = 1 - level by bisection on math.erfc
+    (erfc is decreasing; the interval is halved until it holds no further double).  level must lie in (0, 1)."""
+    import math
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must lie in (0, 1), got %r" % (level,))
+    target, r2 = 1.0 - level, math.sqrt(2.0)
+    lo, hi = 0.0, 40.0  # erfc(0) = 1 > target >= 2^-53 > erfc(40 / sqrt 2)
+    while True:
+        mid = 0.5 * (lo + hi)
+        if not lo < mid < hi:
+            # the neighbouring doubles lo, hi bracket the root: the one whose erfc is nearer the target
+            return lo if abs(math.erfc(lo / r2) - target) <= abs(math.erfc(hi / r2) - target) else hi
+        if math.erfc(mid / r2) > target:
+            lo = mid
+        else:
+            hi = mid
+
+
+def _band_mask(what):
+    """(bit mask, names in slab order) of an iterable of output names (or one name)."""
+    if isinstance(what, str):
+        what = (what,)
+    what = tuple(what)
+    for k in what:
+        if k not in BAND_WHAT:
+            raise ValueError("what must be drawn from %s, got %r" % (list(BAND_WHAT), k))
+    if not what:
+        raise ValueError("what is empty: nothing to compute")
+    names = [k for k in BAND_WHAT if k in what]
+    return sum(1 << BAND_WHAT.index(k) for k in names), names
+
+
+def _band_kind(kind, conf_type):
+    if kind not in SURV_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(SURV_KINDS), kind))
+    if conf_type not in BAND_CONF:
+        raise ValueError("conf_type must be one of %s, got %r" % (sorted(BAND_CONF), conf_type))
+    if kind == "cumhaz" and conf_type == "log-log":
+        raise ValueError("conf_type 'log-log' is defined for kind='survival', not for the cumulative hazard")
+
+
+def _band_inputs(m, cumhaz, var0, drift, factor):
+    """cumhaz (T,), var0 (T,), drift (T, m), factor (m, m) as contiguous float64 host arrays, checked."""
+    cumhaz, var0 = _f64(cumhaz).reshape(-1), _f64(var0).reshape(-1)
+    T = cumhaz.size
+    if T < 1:
+        raise ValueError("cumhaz is empty: no curve to compute")
+    if var0.size != T:
+        raise ValueError("cumhaz and var0 must have the same size, got %d and %d" % (T, var0.size))
+    for what, v in (("cumhaz", cumhaz), ("var0", var0)):
+        if not (np.isfinite(v).all() and (v >= 0.0).all()):
+            raise ValueError("%s should be finite and non-negative" % what)
+    drift = _f64(drift if drift is not None else np.zeros((T, 0)))
+    if drift.shape != (T, m):
+        raise ValueError("drift must have shape (%d, %d), got %s" % (T, m, drift.shape))
+    if not np.isfinite(drift).all():
+        raise ValueError("drift should be finite")
+    factor = _f64(factor if factor is not None else np.zeros((0, 0)))
+    if factor.shape != (m, m):
+        raise ValueError("factor must have shape (%d, %d), got %s" % (m, m, factor.shape))
+    if not np.isfinite(np.tril(factor)).all():
+        raise ValueError("the lower triangle of factor should be finite (is the information positive definite?)")
+    return cumhaz, var0, drift, factor
+
+
+def cox_baseline_variance_device(x, cols, beta, time, status, times, weight=None, ties="breslow", stream=0):
+    """What the variance of the curves of ONE Cox model needs from the rows it was fitted to, x a device matrix (n x p:
+    float64 or float32, any non-negative strides) read where it lies (bessx_cox_hazard_var_device).  With the quantities
+    of cox_information_device (positions k in time order, r(k), e, wd = w * status, S0_k, u_k = S1_k / S0_k) and K(t) the
+    positions with time <= t, for every grid time t:
+        cumhaz = sum_K wd_k / S0_k,     var0 = sum_K wd_k / S0_k^2,     drift = sum_K (wd_k / S0_k) u_k     (m values)
+    times: T >= 1 values in any order, repeats allowed, a NaN is a ValueError; a time before the first gives exact zeros.
+    weight: None = ones, else >= 0.  Returns {"times" (T,), "cumhaz" (T,), "var0" (T,), "drift" (T, m), "n_events"},
+    NumPy arrays.  Under ties="breslow" cumhaz is baseline_at(cox_baseline_device(...), times) bit for bit.  Additions
+    only, in a fixed order: the same call gives the same bits.  len(cols) + 1 <= 1024."""
+    a = CoxHazardVarInput()
+    n, p, cols, B, host = _cox_call(a, "cox_baseline_variance_device", x, cols, beta, time, status, weight, ties, stream)
+    if weight is not None and not (host["weight"] >= 0.0).all():
+        raise ValueError("weight should be non-negative")
+    if np.ndim(times) > 1:
+        raise ValueError("times must be 1-D")
+    tg = _f64(times).reshape(-1)
+    if tg.size < 1:
+        raise ValueError("times is empty: no curve to compute")
+    if np.isnan(tg).any():
+        raise ValueError("There is NAN value in times")
+    m, T = cols.size, tg.size
+    a.times, a.T = _dp(tg), T
+    cumhaz, var0, drift, ne = np.zeros(T), np.zeros(T), np.zeros((T, m)), _d(0)
+    _check(lib().bessx_cox_hazard_var_device(ctypes.byref(a), _dp(cumhaz), _dp(var0), _dp(drift), max(m, 1),
+                                             ctypes.byref(ne)))
+    return {"times": tg.copy(), "cumhaz": cumhaz, "var0": var0, "drift": drift, "n_events": ne.value}
+
+
+def cox_band_workspace(n, m, T, what=("estimate", "lower", "upper"), dtype=np.float64, row_stride=None, col_stride=1,
+                       out_on_device=True):
+    """(doubles of scratch memory, grid times per workgroup of the matrix-core kernel) of a cox_survival_band_device call
+    on an n-row matrix of the given element type and strides (row_stride=None: dense row-major needs no number here,
+    any value > 1 stands for it) with a support of m columns, T times and the outputs `what`
+    (bessx_cox_band_workspace; no device is needed)."""
+    mask, _ = _band_mask(what)
+    nd, tc = _ll(0), _i(0)
+    rs = 2 if row_stride is None else int(row_stride)
+    _check(lib().bessx_cox_band_workspace(0 if np.dtype(dtype) == np.float64 else 1, rs, int(col_stride), int(n), int(m),
+                                          int(T), mask, int(bool(out_on_device)), ctypes.byref(nd), ctypes.byref(tc)))
+    return nd.value, tc.value
+
+
+def cox_survival_band_device(x, cols, beta, cumhaz, var0, drift, factor, kind="survival", conf_type="log-log", level=0.95,
+                             what=("estimate", "lower", "upper"), out=None, stream=0):
+    """Curves of one Cox model with their standard errors and pointwise confidence bounds for the rows of a device
+    matrix x (n x p: float64 or float32, any non-negative strides), read where it lies, the support's columns only
+    (bessx_cox_band_device; Tsiatis 1981, survival::survfit's numbers for a Breslow baseline).  cumhaz, var0 (T,) and
+    drift (T, m) are cox_baseline_variance_device's; factor (m, m) is info_factor's R for cox_information_device's info
+    (inv(info) = R^T R).  With z = x[i, cols], e = exp(clip(z @ beta, -30, 30)), L = cumhaz * e, t = R z, p = R drift and
+    z_c = normal_quantile(level):
+        V = var0 + |p - cumhaz t|^2,   se_L = e sqrt(V),   r = z_c sqrt(V) / cumhaz
+        kind="cumhaz":    estimate L, se se_L; plain: max(L - z_c se_L, 0), L + z_c se_L; log: L exp(-r), L exp(r)
+        kind="survival":  estimate S = exp(-L), se S se_L; plain: S -+ z_c se clipped to [0, 1]; log: exp(-(L + z_c se_L)),
+                          exp(-max(L - z_c se_L, 0)); log-log: exp(-L exp(r)), exp(-L exp(-r))
+    Where cumhaz is 0 the se is 0 and the bounds are the estimate.  estimate has cox_survival_device's bits for the same
+    baseline values.  what: a subset of ("estimate", "se", "lower", "upper").  Returns a dict from name to an (n, T) view
+    of one (K, n, T) array, K = len(what), slabs in that order: out when given (a float64 device array of shape
+    (K, n, T), any strides), else a torch tensor on x's device when x is a torch tensor (torch is looked up, never
+    imported) and a NumPy array for any other device object.  The sum of squares is formed directly on the fp64 matrix
+    cores' output, never by the expansion that cancels for columns that are not centred; no (n, m) or (n, T) temporary
+    is made.  len(cols) + 1 <= 1024, T <= 65535.  stream: raw handle of the stream x was produced on."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    _band_kind(kind, conf_type)
+    mask, names = _band_mask(what)
+    zc = normal_quantile(level)
+    if np.ndim(beta) > 1:
+        raise ValueError("beta must be 1-D: cox_survival_band_device takes one model per call")
+    cols, B = _cox_model(dx, cols, np.asarray(beta, dtype=np.float64).reshape(-1))
+    if not np.isfinite(B).all():
+        raise ValueError("beta must be finite")
+    m = cols.size
+    cumhaz, var0, drift, factor = _band_inputs(m, cumhaz, var0, drift, factor)
+    T, K = cumhaz.size, len(names)
+    if out is not None:
+        if not is_device_array(out):
+            raise ValueError("out must be a device array")
+        cai = out.__cuda_array_interface__
+        shape = tuple(int(v) for v in cai["shape"])
+        if cai["typestr"] != "<f8":
+            raise ValueError("out: a device array of float64 is needed (typestr '<f8')")
+        if shape != (K, n, T):
+            raise ValueError("out must have shape %s, got %s" % ((K, n, T), shape))
+        st = cai.get("strides")
+        st = (n * T, T, 1) if st is None else tuple(int(v) // 8 for v in st)
+        if any(int(v) < 0 or int(v) % 8 for v in (cai.get("strides") or ())):
+            raise ValueError("out: byte strides must be non-negative multiples of 8")
+        ptr, on_device, result = int(cai["data"][0]), 1, out
+    else:
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(x, torch.Tensor):
+            result = torch.empty((K, n, T), dtype=torch.float64, device=x.device)
+            ptr, on_device = int(result.data_ptr()), 1
+        else:
+            result = np.empty((K, n, T))
+            ptr, on_device = int(result.ctypes.data), 0
+        st = (n * T, T, 1)
+    a = CoxBandInput()
+    _set_x(a, dx)
+    a.cols, a.m, a.beta = _ip(cols), m, _dp(B)
+    a.cumhaz, a.var0, a.drift, a.drift_ld, a.T = _dp(cumhaz), _dp(var0), _dp(drift), max(m, 1), T
+    a.factor, a.factor_ld = _dp(factor), max(m, 1)
+    a.kind, a.conf_type, a.z_c, a.what = SURV_KINDS[kind], BAND_CONF[conf_type], zc, mask
+    a.out_slab_stride, a.out_row_stride, a.out_col_stride, a.out_on_device = st[0], st[1], st[2], on_device
+    a.stream = int(stream) if stream else None
+    _check(lib().bessx_cox_band_device(ctypes.byref(a), ptr))
+    return {k: result[s] for s, k in enumerate(names)}
+
+
+def op_cox_band_bench(x, cols, T=100, what=("estimate", "lower", "upper"), repeats=20):
+    """Milliseconds per launch of the two device steps of cox_survival_band_device on the device matrix x for the support
+    cols, device events: (predictor pass that stores exp(clip(eta)) in row order, k_cbd_band writing the K = len(what)
+    row-major (n, T) slabs with the survival / log-log epilogue)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    mask, _ = _band_mask(what)
+    if int(T) < 1:
+        raise ValueError("T must be at least 1")
+    ms = np.zeros(2)
+    _check(lib().bessx_op_cox_band_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, int(T), mask, repeats, _dp(ms)))
+    return tuple(float(v) for v in ms)
 
 
 def op_cox_surv_bench(x, cols, T=100, kind="survival", out_col_major=False, repeats=20):

@@ -5062,3 +5062,353 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
+// standard errors and confidence bands of the curves of one Cox model on a caller's device matrix (include/bessx.h
+// section 2s)
+// ----------------------------------------------------------------------------------------------
+static_assert((int)BESSX_BAND_PLAIN == 0 && (int)BESSX_BAND_LOG == 1 && (int)BESSX_BAND_LOGLOG == 2,
+              "conf codes of launch_cox_band");
+
+namespace {
+
+constexpr unsigned kBandAll = BESSX_BAND_ESTIMATE | BESSX_BAND_SE | BESSX_BAND_LOWER | BESSX_BAND_UPPER;
+constexpr int kBandTMax = 65535;
+
+inline CoxCall cox_call(const bessx_cox_band_input *in) {
+  return CoxCall{in->x,    in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,   in->p, in->cols, in->m,
+                 in->beta, 1,           nullptr,          nullptr,          nullptr, 1,     static_cast<hipStream_t>(in->stream)};
+}
+
+// doubles of device scratch of one bessx_cox_hazard_var_device call
+long long cox_hazvar_doubles(long long n, int m, long long J, int T) {
+  const long long nb = (n + 1023) / 1024;
+  // eta / H, e -> S0, the scans' totals, B; var0's increment, the totals of the two forward scans, the gathered result
+  long long d = 2 * n + cox_eval_workspace(n, 1) + 1 + (long long)m + 1 + n + cox_surv_workspace(n) + (long long)T * (m + 2);
+  if (m == 0 || J == 0) return d;
+  // e, W and its totals, U, A and its totals, dh
+  return d + n + (long long)m * n + nb * m + cox_info_ldu(J) * m + cox_diag_lda(n) * m + nb * m + n;
+}
+
+// idx[j]: where the prefix arrays are read for times[j] -- the last position with time <= times[j] behind which nothing is
+// added any more: the end of the last tie group (ties = 0: the last position) that holds an event, -1 when no event has
+// time <= times[j].  Under ties = 1 these are the positions section 2f's baseline reads, so cumhaz has its bits.  (o.first
+// holds r(k): cox_event_groups sees single positions under ties = 0.)
+void cox_hazvar_index(const CoxOrder &o, const double *time, int n, const double *times, int T, std::vector<int> *idx) {
+  std::vector<double> gt;
+  std::vector<int> ends;
+  cox_event_groups(o, time, n, &gt, &ends);
+  idx->resize((size_t)T);
+  for (int j = 0; j < T; j++) {
+    const size_t g = (size_t)(std::upper_bound(gt.begin(), gt.end(), times[j]) - gt.begin());
+    (*idx)[(size_t)j] = g > 0 ? ends[g - 1] : -1;
+  }
+}
+
+int cox_hazvar_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const std::vector<int> &idx, std::vector<double> &h,
+                   const bessx_cox_hazard_var_input *in, double *cumhaz, double *var0, double *drift, long long ld,
+                   hipStream_t st) {
+  const int n = in->n, m = in->m, T = in->T, f32 = in->x_dtype == BESSX_F32, ties = in->ties;
+  const size_t N = (size_t)n, nb = (size_t)((n + 1023) / 1024), W = (size_t)m + 2;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  const bool means = m > 0;  // (the caller has seen to it that an event exists)
+  CoxDev d;  // (d.first holds r(k); d.ex holds S0 and d.eta holds H once they have been formed)
+  if (int rc = cox_eval_stage(sc, o, in->cols, m, in->beta, 1, n, 1, 0, st, &d)) return rc;
+  int *lastk = nullptr, *rowof = nullptr, *jptr = nullptr, *idx_d = nullptr;
+  double *hs = nullptr, *v0 = nullptr, *res = nullptr, *e = nullptr, *Wd = nullptr, *scr = nullptr, *U = nullptr,
+         *A = nullptr, *dh = nullptr, *scrA = nullptr;
+  HIPX(sc.alloc(&hs, (size_t)cox_surv_workspace(n)));
+  HIPX(sc.alloc(&v0, N));
+  HIPX(sc.alloc(&res, (size_t)T * W));
+  HIPX(sc.alloc(&idx_d, (size_t)T));
+  HIPX(hipMemcpyAsync(idx_d, idx.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, st));
+  if (ties) {
+    HIPX(sc.alloc(&lastk, N));
+    HIPX(hipMemcpyAsync(lastk, x.lastk.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  const long long ldU = cox_info_ldu(x.J), ldA = cox_diag_lda(n);
+  if (means) {
+    HIPX(sc.alloc(&rowof, N));
+    HIPX(hipMemcpyAsync(rowof, x.rowof.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&jptr, N + 1));
+    HIPX(hipMemcpyAsync(jptr, x.jptr.data(), (N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&e, N));
+    HIPX(sc.alloc(&Wd, (size_t)m * N));
+    HIPX(sc.alloc(&scr, nb * (size_t)m));
+    HIPX(sc.alloc(&U, (size_t)ldU * (size_t)m));
+    HIPX(sc.alloc(&A, (size_t)ldA * (size_t)m));
+    HIPX(sc.alloc(&dh, N));
+    HIPX(sc.alloc(&scrA, nb * (size_t)m));
+  }
+  // sections 2e / 2f / 2h / 2j's launchers as they are
+  HIPX(launch_cox_eval_eta(in->x, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
+  if (means) HIPX(hipMemcpyAsync(e, d.ex, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPX(launch_cox_eval_suffix(d.ex, n, 1, d.work, st));
+  if (means) HIPX(launch_cox_info_gather(in->x, f32, rs, cs, n, d.cols, m, rowof, e, Wd, st));
+  HIPX(launch_cox_baseline(d.ex, d.wd, d.first, n, nullptr, 0, d.eta, hs, nullptr, st));  // (eta's n doubles hold H)
+  HIPX(launch_cox_band_dh2(d.wd, d.ex, d.first, ties ? lastk : nullptr, n, v0, st));
+  HIPX(launch_cox_prefix_scan(v0, n, hs, st));
+  if (means) {
+    HIPX(launch_cox_info_means(Wd, d.ex, jptr, n, m, x.J, scr, U, ldU, st));
+    HIPX(launch_cox_diag_accum(U, ldU, jptr, d.wd, d.ex, d.first, ties ? lastk : nullptr, n, m, dh, scrA, A, ldA, st));
+  }
+  HIPX(launch_cox_band_gather(d.eta, v0, A, ldA, idx_d, T, m, res, st));
+  h.resize((size_t)T * W);
+  HIPX(hipMemcpyAsync(h.data(), res, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  for (int j = 0; j < T; j++) {
+    const double *r = h.data() + (size_t)j * W;
+    cumhaz[j] = r[0];
+    var0[j] = r[1];
+    std::copy(r + 2, r + W, drift + (long long)j * ld);
+  }
+  return 0;
+}
+
+// everything about a band call that needs no device; slab[w]: the slab of out that takes output w, or -1
+int cox_band_check_args(const std::string &w, const CoxCall &c, const bessx_cox_band_input *in, const double *out, int *slab) {
+  if (!out) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_check(w.c_str(), c, true, false)) return rc;
+  if (int rc = check_m_max(w, in->m)) return rc;
+  const int T = in->T, m = in->m;
+  if (T < 1 || !in->cumhaz || !in->var0) return fail(BESSX_ERR_ARG, w + ": cumhaz and var0 need T >= 1 values");
+  if (T > kBandTMax) return fail(BESSX_ERR_UNSUPPORTED, w + ": T must be at most " + std::to_string(kBandTMax));
+  for (int j = 0; j < T; j++) {
+    if (!(in->cumhaz[j] >= 0.0) || !std::isfinite(in->cumhaz[j]))
+      return fail(BESSX_ERR_ARG, w + ": cumhaz must be finite and non-negative");
+    if (!(in->var0[j] >= 0.0) || !std::isfinite(in->var0[j]))
+      return fail(BESSX_ERR_ARG, w + ": var0 must be finite and non-negative");
+  }
+  if (m > 0) {
+    if (!in->drift || !in->factor) return fail(BESSX_ERR_ARG, w + ": null argument (drift, factor)");
+    if (in->drift_ld < m) return fail(BESSX_ERR_ARG, w + ": drift_ld must be at least m");
+    if (in->factor_ld < m) return fail(BESSX_ERR_ARG, w + ": factor_ld must be at least m");
+    for (long long j = 0; j < T; j++)
+      for (long long k = 0; k < m; k++)
+        if (!std::isfinite(in->drift[j * in->drift_ld + k])) return fail(BESSX_ERR_ARG, w + ": drift must be finite");
+    for (long long j = 0; j < m; j++)
+      for (long long k = 0; k <= j; k++)
+        if (!std::isfinite(in->factor[j * in->factor_ld + k]))
+          return fail(BESSX_ERR_ARG, w + ": the lower triangle of the factor must be finite");
+  }
+  if (in->kind != BESSX_SURV_SURVIVAL && in->kind != BESSX_SURV_CUMHAZ)
+    return fail(BESSX_ERR_ARG, w + ": kind must be BESSX_SURV_SURVIVAL or BESSX_SURV_CUMHAZ");
+  if (in->conf_type != BESSX_BAND_PLAIN && in->conf_type != BESSX_BAND_LOG && in->conf_type != BESSX_BAND_LOGLOG)
+    return fail(BESSX_ERR_ARG, w + ": conf_type must be BESSX_BAND_PLAIN, _LOG or _LOGLOG");
+  if (in->kind == BESSX_SURV_CUMHAZ && in->conf_type == BESSX_BAND_LOGLOG)
+    return fail(BESSX_ERR_ARG, w + ": log-log bands are defined for the survival function, not for the cumulative hazard");
+  if (in->what == 0 || (in->what & ~kBandAll))
+    return fail(BESSX_ERR_ARG, w + ": what must be a non-empty set of BESSX_BAND_* bits");
+  if (!(in->z_c >= 0.0) || !std::isfinite(in->z_c)) return fail(BESSX_ERR_ARG, w + ": z_c must be finite and non-negative");
+  if (in->out_slab_stride < 0 || in->out_row_stride < 0 || in->out_col_stride < 0)
+    return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  int K = 0;
+  for (int q = 0; q < 4; q++) slab[q] = (in->what >> q) & 1u ? K++ : -1;
+  if ((in->n > 1 && in->out_row_stride == 0) || (T > 1 && in->out_col_stride == 0) || (K > 1 && in->out_slab_stride == 0))
+    return fail(BESSX_ERR_ARG, w + ": out: a zero stride along an axis longer than 1");
+  return 0;
+}
+
+int cox_band_run(Owner &sc, std::vector<double> &pk, std::vector<double> &tmp, const bessx_cox_band_input *in,
+                 const int *slab, double *out, hipStream_t st) {
+  const int n = in->n, m = in->m, T = in->T, f32 = in->x_dtype == BESSX_F32;
+  const size_t ldP = 16 * (((size_t)m + 15) / 16), nP = (size_t)T * ldP, nR = m > 0 ? (size_t)cox_diag_pack_doubles(m, 1) : 0;
+  int K = 0;
+  for (int q = 0; q < 4; q++) K += slab[q] >= 0;
+  // one upload: cumhaz, var0, the rows p_j = R drift_j (zeros behind entry m), the packed factor
+  pk.assign(2 * (size_t)T + nP + nR, 0.0);
+  std::copy(in->cumhaz, in->cumhaz + T, pk.begin());
+  std::copy(in->var0, in->var0 + T, pk.begin() + T);
+  double *P = pk.data() + 2 * (size_t)T;
+  for (long long j = 0; j < T; j++) {
+    const double *dj = in->drift + j * in->drift_ld;
+    for (long long a = 0; a < m; a++) {
+      const double *Ra = in->factor + a * in->factor_ld;
+      double s = 0.0;
+      for (long long k = 0; k <= a; k++) s += Ra[k] * dj[k];
+      P[(size_t)j * ldP + (size_t)a] = s;
+    }
+  }
+  if (m > 0) cox_diag_pack(in->factor, in->factor_ld, m, 1, P + nP);
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *zero_d = nullptr, *ex = nullptr, *up = nullptr, *stage = nullptr;
+  if (int rc = predict_upload_model(sc, in->cols, m, in->beta, &kCoxZero, 1, st, &cols_d, &B_d, &zero_d)) return rc;
+  HIPX(sc.alloc(&ex, (size_t)n));
+  HIPX(sc.alloc(&up, pk.size()));
+  HIPX(hipMemcpyAsync(up, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPX(launch_cox_surv_ex(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, B_d, zero_d, ex, st));
+  const double *hz = up, *v0 = up + T, *Pd = up + 2 * (size_t)T, *pkd = Pd + nP;
+  if (in->out_on_device) {
+    HIPX(launch_cox_band(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, pkd, Pd, (long long)ldP, hz, v0, ex,
+                         T, in->kind, in->conf_type, in->z_c, slab, out, in->out_slab_stride, in->out_row_stride,
+                         in->out_col_stride, st));
+    HIPX(hipStreamSynchronize(st));
+    return 0;
+  }
+  const size_t one = (size_t)n * (size_t)T, cnt = one * (size_t)K;
+  HIPX(sc.alloc(&stage, cnt));
+  HIPX(launch_cox_band(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, m, pkd, Pd, (long long)ldP, hz, v0, ex, T,
+                       in->kind, in->conf_type, in->z_c, slab, stage, (long long)one, T, 1, st));
+  tmp.resize(cnt);
+  HIPX(hipMemcpyAsync(tmp.data(), stage, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  for (long long s = 0; s < K; s++)
+    for (long long i = 0; i < n; i++)
+      for (long long j = 0; j < T; j++)
+        out[s * in->out_slab_stride + i * in->out_row_stride + j * in->out_col_stride] = tmp[(size_t)s * one + i * T + j];
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_hazard_var_workspace(int n, int m, int n_event_rows, int T, long long *doubles) {
+  if (!doubles) return fail(BESSX_ERR_ARG, "cox_hazard_var_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_hazard_var_workspace: empty matrix");
+  if (n_event_rows < 0 || n_event_rows > n)
+    return fail(BESSX_ERR_ARG, "cox_hazard_var_workspace: n_event_rows must lie in [0, n]");
+  if (T < 1) return fail(BESSX_ERR_ARG, "cox_hazard_var_workspace: T must be at least 1");
+  if (int rc = check_m_max("cox_hazard_var_workspace", m)) return rc;
+  *doubles = n_event_rows > 0 ? cox_hazvar_doubles(n, m, n_event_rows, T) : 0;
+  return BESSX_OK;
+}
+
+int bessx_cox_hazard_var_device(const bessx_cox_hazard_var_input *in, double *cumhaz, double *var0, double *drift,
+                                long long drift_ld, double *n_events) {
+  const std::string w("cox_hazard_var_device");
+  if (!in || !cumhaz || !var0 || !n_events) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const CoxCall c = cox_call(in);
+  int events = 0;
+  if (int rc = cox_check("cox_hazard_var_device", c, true, true, &events)) return rc;
+  if (int rc = check_m_max(w, in->m)) return rc;
+  if (in->weight)
+    for (int i = 0; i < in->n; i++)
+      if (!(in->weight[i] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": weight must be non-negative");
+  if (in->T < 1 || !in->times) return fail(BESSX_ERR_ARG, w + ": times needs T >= 1 values");
+  for (int j = 0; j < in->T; j++)
+    if (std::isnan(in->times[j])) return fail(BESSX_ERR_ARG, w + ": times holds a NaN");
+  if (in->m > 0 && !drift) return fail(BESSX_ERR_ARG, w + ": null argument (drift)");
+  if (drift_ld < (long long)in->m) return fail(BESSX_ERR_ARG, w + ": drift_ld must be at least m");
+  int dev = -1;
+  if (int rc = cox_check_device("cox_hazard_var_device", c, &dev)) return rc;
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  CoxInfoOrder x;
+  cox_info_order(&o, in->n, in->m, in->ties, &x);
+  std::vector<int> idx;
+  cox_hazvar_index(o, in->time, in->n, in->times, in->T, &idx);
+  int rc = 0;
+  if (events > 0) {
+    rc = dev_call(dev, c.stream, [&](DevCall &dc) {
+      return cox_hazvar_run(dc.sc, o, x, idx, dc.h, in, cumhaz, var0, drift, drift_ld, dc.st);
+    });
+  } else {  // every row censored: no increment anywhere
+    for (int j = 0; j < in->T; j++) {
+      cumhaz[j] = var0[j] = 0.0;
+      if (in->m > 0) std::fill(drift + (long long)j * drift_ld, drift + (long long)j * drift_ld + in->m, 0.0);
+    }
+  }
+  if (!rc) *n_events = x.n_events;
+  return rc;
+}
+
+int bessx_cox_band_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int T, unsigned what,
+                             int out_on_device, long long *doubles, int *time_chunk) {
+  const std::string w("cox_band_workspace");
+  if (!doubles || !time_chunk) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (x_dtype != BESSX_F64 && x_dtype != BESSX_F32) return fail(BESSX_ERR_ARG, w + ": x: dtype must be BESSX_F64 or BESSX_F32");
+  if (x_row_stride < 0 || x_col_stride < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, w + ": empty matrix");
+  if (T < 1) return fail(BESSX_ERR_ARG, w + ": T must be at least 1");
+  if (T > kBandTMax) return fail(BESSX_ERR_UNSUPPORTED, w + ": T must be at most " + std::to_string(kBandTMax));
+  if (what == 0 || (what & ~kBandAll)) return fail(BESSX_ERR_ARG, w + ": what must be a non-empty set of BESSX_BAND_* bits");
+  if (int rc = check_m_max(w, m)) return rc;
+  int K = 0;
+  for (int q = 0; q < 4; q++) K += (what >> q) & 1u;
+  const long long ldP = 16 * (((long long)m + 15) / 16);
+  *doubles = (long long)m + 1 + n + 2LL * T + (long long)T * ldP + (m > 0 ? cox_diag_pack_doubles(m, 1) : 0) +
+             (out_on_device ? 0 : (long long)K * n * T);
+  *time_chunk = cox_band_time_chunk(x_dtype == BESSX_F32, x_row_stride, x_col_stride, nullptr);  // (an aligned base)
+  return BESSX_OK;
+}
+
+int bessx_cox_band_device(const bessx_cox_band_input *in, double *out) {
+  const std::string w("cox_band_device");
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const CoxCall c = cox_call(in);
+  int slab[4];
+  if (int rc = cox_band_check_args(w, c, in, out, slab)) return rc;
+  int dev = -1;
+  if (int rc = cox_check_device("cox_band_device", c, &dev)) return rc;
+  if (in->out_on_device)
+    for (int q = 0; q < 4; q++)
+      if (slab[q] >= 0)
+        if (int rc = check_on_device("cox_band_device", "out", out + (long long)slab[q] * in->out_slab_stride, BESSX_F64,
+                                     in->out_row_stride, in->out_col_stride, in->n, in->T, dev))
+          return rc;
+  return dev_call(dev, c.stream, [&](DevCall &dc) { return cox_band_run(dc.sc, dc.pk, dc.h, in, slab, out, dc.st); });
+}
+
+int bessx_op_cox_band_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int T, unsigned what, int repeats, double *stage_ms) {
+  const std::string w("op_cox_band_bench");
+  if (repeats < 1 || !stage_ms || T < 1 || T > kBandTMax || what == 0 || (what & ~kBandAll))
+    return fail(BESSX_ERR_ARG, w + ": bad arguments");
+  if (!x) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = check_x_model(w, x, dtype, row_stride >= 0 && col_stride >= 0, n, p, cols, m, &kCoxZero, 1,
+                             BESSX_LINK_IDENTITY, false))
+    return rc;  // (beta is the library's own)
+  if (int rc = check_m_max(w, m)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_band_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  // a model, a factor and T-sized inputs of the library's own: R = 0.2 I + a small lower triangle, drift = cumhaz * 0.1
+  const size_t M = (size_t)m, ldP = 16 * ((M + 15) / 16), nP = (size_t)T * ldP, nR = m > 0 ? (size_t)cox_diag_pack_doubles(m, 1) : 0;
+  std::vector<double> B(M), R(M * M, 0.0), up(2 * (size_t)T + nP + nR, 0.0);
+  for (size_t q = 0; q < M; q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (size_t j = 0; j < M; j++)
+    for (size_t k = 0; k <= j; k++) R[j * M + k] = j == k ? 0.2 : ((j + 3 * k) % 5 - 2.0) / (16.0 * (double)M);
+  for (int j = 0; j < T; j++) {
+    const double H = (j + 1.0) / T;
+    up[(size_t)j] = H;
+    up[(size_t)T + (size_t)j] = H * H / 50.0;
+    for (size_t a = 0; a < M; a++) {
+      double s = 0.0;
+      for (size_t k = 0; k <= a; k++) s += R[a * M + k] * (0.1 * H);
+      up[2 * (size_t)T + (size_t)j * ldP + a] = s;
+    }
+  }
+  if (m > 0) cox_diag_pack(R.data(), m, m, 1, up.data() + 2 * (size_t)T + nP);
+  Owner sc;
+  int *cols_d = nullptr, slab[4], K = 0;
+  for (int q = 0; q < 4; q++) slab[q] = (what >> q) & 1u ? K++ : -1;
+  double *B_d = nullptr, *zero_d = nullptr, *ex = nullptr, *upd = nullptr, *out = nullptr;
+  if (int rc = predict_upload_model(sc, cols, m, B.data(), &kCoxZero, 1, nullptr, &cols_d, &B_d, &zero_d)) return rc;
+  HIPX(sc.alloc(&ex, (size_t)n));
+  HIPX(sc.alloc(&upd, up.size()));
+  HIPX(sc.alloc(&out, (size_t)K * (size_t)n * (size_t)T));
+  HIPX(hipMemcpy(upd, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  const int f32 = dtype == BESSX_F32;
+  BenchTimer bt;
+  if (int rc = bt.init(sc)) return rc;
+  for (int stage = 0; stage < 2; stage++) {
+    float ms = 0.f;
+    const int rc = bt.run(repeats, &ms, [&]() -> int {
+      if (stage == 0)
+        HIPX(launch_cox_surv_ex(x, f32, row_stride, col_stride, n, cols_d, m, B_d, zero_d, ex, nullptr));
+      else
+        HIPX(launch_cox_band(x, f32, row_stride, col_stride, n, cols_d, m, upd + 2 * (size_t)T + nP, upd + 2 * (size_t)T,
+                             (long long)ldP, upd, upd + T, ex, T, BESSX_SURV_SURVIVAL, BESSX_BAND_LOGLOG, 1.96, slab, out,
+                             (long long)n * T, T, 1, nullptr));
+      return 0;
+    });
+    if (rc) return rc;
+    stage_ms[stage] = ms / repeats;
+  }
+  return BESSX_OK;
+}
+
+}  // extern "C"

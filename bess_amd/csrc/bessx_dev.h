@@ -108,6 +108,7 @@ hipError_t launch_cox_eval_pairs(const double *eta, const int *kg, const int *fi
 long long cox_surv_workspace(long long n);
 hipError_t launch_cox_baseline(const double *S, const double *wd, const int *first, long long n, const int *ends, int J,
                                double *h, double *scr, double *hout, hipStream_t st);
+hipError_t launch_cox_prefix_scan(double *h, long long n, double *scr, hipStream_t st);  // (_baseline's scan alone)
 hipError_t launch_cox_surv_ex(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
                               const double *B, const double *zero, double *ex, hipStream_t st);
 hipError_t launch_cox_surv_curves(const double *ex, const double *hg, long long n, int T, int kind, double *out,
@@ -270,6 +271,22 @@ hipError_t launch_cox_diag_perm(const double *L, long long ldL, long long n, int
 hipError_t launch_cox_diag_schoenfeld(const void *src, int f32, long long rs, long long cs, const int *cols, int m,
                                       const int *evrow, int J, const double *U, long long ldU, double *out,
                                       long long ldo, hipStream_t st);
+// standard errors and bands of the curves of one Cox model (bessx_k_coxband.hip).  _dh2: dv[p] = sum_{k : r(k) = p} wd_k /
+// S0(p)^2 (arguments of launch_cox_diag_accum).  _gather: out[tau * (m + 2) + (0, 1, 2 + j)] = (H, V0, A(j, .)) at position
+// idx[tau], zeros for idx[tau] < 0 (A null: no drift).  launch_cox_band: the n x Tn results from pk = cox_diag_pack(R, tri),
+// P (Tn rows p_tau = R drift_tau of ldP = 16 ceil(m / 16) doubles, zeros behind entry m), hz = cumhaz, v0 = var0, ex of
+// launch_cox_surv_ex; slab[w] for w = estimate, se, lower, upper: the slab of out that takes it or negative; conf: 0 plain,
+// 1 log, 2 log-log.  _time_chunk: grid times per workgroup for a source of this shape.  Device memory.
+int cox_band_time_chunk(int f32, long long rs, long long cs, const void *src);
+int cox_band_sum_depth(int m);
+hipError_t launch_cox_band_dh2(const double *wd, const double *S0, const int *first, const int *lastk, long long n,
+                               double *dv, hipStream_t st);
+hipError_t launch_cox_band_gather(const double *H, const double *V0, const double *A, long long ldA, const int *idx,
+                                  int Tn, int m, double *out, hipStream_t st);
+hipError_t launch_cox_band(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                           const double *pk, const double *P, long long ldP, const double *hz, const double *v0,
+                           const double *ex, int Tn, int kind, int conf, double zc, const int *slab, double *out,
+                           long long oss, long long ors, long long ocs, hipStream_t st);
 // score tests of candidate columns against one Cox model (bessx_k_coxaddscore.hip), on top of the arrays of
 // bessx_k_coxinfo.hip and bessx_k_coxdiag.hip.  _pack: the panel (v_i, v_i x_i - e_pos(i) A_pos(i), g_i, zeros) in
 // launch_addscore_pack's layout for the same m (launch_addscore_blocks takes it as it is: column 0 is v, where section

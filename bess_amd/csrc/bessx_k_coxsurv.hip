@@ -173,6 +173,18 @@ hipError_t launch_cox_baseline(const double *S, const double *wd, const int *fir
   return hipSuccess;
 }
 
+// the forward scan of launch_cox_baseline alone, for another increment (bessx_k_coxband.hip): h becomes its prefix sums in
+// place; scr: cox_surv_workspace(n) doubles
+hipError_t launch_cox_prefix_scan(double *h, long long n, double *scr, hipStream_t st) {
+  if (!h || !scr || n < 1 || n > 0x7fffffffLL) return hipErrorInvalidValue;
+  const unsigned nb = (unsigned)((n + CXS_B - 1) / CXS_B);
+  hipLaunchKernelGGL(k_cxs_scan_tot, dim3(nb), dim3(CXS_T), 0, st, h, n, scr);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_cxs_scan_apply, dim3(nb), dim3(CXS_T), 0, st, h, n, scr);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 // curves, stage one: ex[i] = exp(clamp(eta_i, +-30)) in row order; src, cols, B as in launch_predict with R = 1; zero:
 // one device double holding 0.0
 hipError_t launch_cox_surv_ex(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,

@@ -1538,6 +1538,151 @@ class bess_base:
         z = np.exp(a)[:, None] * hg[None, :]
         return z if kind == "cumhaz" else np.exp(-z)
 
+    # ---- Cox: standard errors and confidence bands of the curves -----------------------------------------------------
+    @staticmethod
+    def _hazard_var_host(Xs, beta, time, status, w, ties, times):
+        """(cumhaz (T,), var0 (T,), drift (T, m)) in fp64 NumPy with the definitions of
+        capi.cox_baseline_variance_device, by the same decomposition (running sums): Xs (n, m) the support's columns,
+        beta (m,), time, status, w (n,) in row order, times (T,)."""
+        n, m = Xs.shape
+        eta = np.zeros(n)
+        for c in range(m):  # (column by column: a row's sum does not depend on where the row lies)
+            eta += Xs[:, c] * beta[c]
+        order = np.argsort(time, kind="stable")
+        x, eta, t, d = Xs[order], eta[order], time[order], status[order]
+        wd = w[order] * d
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))  # (comparisons: a NaN stays a NaN)
+        e = np.exp(a)
+        r = first if ties == "breslow" else np.arange(n)
+        S0 = np.cumsum(e[::-1])[::-1][r]
+        h = wd / S0
+        H, V0 = np.cumsum(h), np.cumsum(wd / (S0 * S0))
+        u = np.cumsum((e[:, None] * x)[::-1], axis=0)[::-1][r] / S0[:, None]
+        A = np.cumsum(np.where((d != 0)[:, None], h[:, None] * u, 0.0), axis=0)
+        idx = np.searchsorted(t, times, side="right") - 1
+        at = lambda z: np.where((idx >= 0).reshape((-1,) + (1,) * (z.ndim - 1)), z[np.maximum(idx, 0)], 0.0)
+        return at(H), at(V0), at(A)
+
+    @staticmethod
+    def _bands_host(Xs, beta, cumhaz, var0, drift, R, kind, conf_type, zc, names):
+        """capi.cox_survival_band_device's numbers in fp64 NumPy with the same definitions: Xs (n, m) the support's
+        columns; returns {name: (n, T)}.  The sum of squares is formed directly, one support column at a time."""
+        n, m = Xs.shape
+        eta = np.zeros(n)
+        for c in range(m):
+            eta += Xs[:, c] * beta[c]
+        e = np.exp(np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta)))[:, None]
+        H = cumhaz[None, :]
+        V = np.zeros((n, cumhaz.size))
+        for j in range(m):
+            tj, pj = np.zeros(n), np.zeros(cumhaz.size)
+            for k in range(j + 1):
+                tj = tj + R[j, k] * Xs[:, k]
+                pj = pj + R[j, k] * drift[:, k]
+            dj = pj[None, :] - H * tj[:, None]
+            V = V + dj * dj
+        V = V + var0[None, :]
+        floor0 = lambda z: np.where(z < 0.0, 0.0, z)  # (comparisons: a NaN stays a NaN)
+        ceil1 = lambda z: np.where(z > 1.0, 1.0, z)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            L = H * e
+            sq = np.sqrt(V)
+            seL = e * sq
+            wv = zc * seL
+            r = (zc * sq) / H
+            if kind == "cumhaz":
+                est, se = L, seL
+                lo, hi = (floor0(L - wv), L + wv) if conf_type == "plain" else (L * np.exp(-r), L * np.exp(r))
+            else:
+                est = np.exp(-L)
+                se = est * seL
+                if conf_type == "plain":
+                    lo, hi = floor0(est - zc * se), ceil1(est + zc * se)
+                elif conf_type == "log":
+                    lo, hi = np.exp(-(L + wv)), np.exp(-floor0(L - wv))
+                else:
+                    lo, hi = np.exp(-(L * np.exp(r))), np.exp(-(L * np.exp(-r)))
+        zero = np.broadcast_to(H == 0.0, est.shape)  # before the first event: no 0 / 0, the bounds are the estimate
+        se, lo, hi = np.where(zero, L, se), np.where(zero, est, lo), np.where(zero, est, hi)
+        return {k: v for k, v in (("estimate", est), ("se", se), ("lower", lo), ("upper", hi)) if k in names}
+
+    def fit_survival_bands(self, X, y, times, weight=None, ties="breslow"):
+        """Cox only, after fit(): what the standard errors and confidence bands of the fitted model's curves need from
+        the rows X, y (the rows it was fitted to), y = (time, status) as in fit, weight n values >= 0 or None, at the
+        grid `times` (any order, repeats allowed).  Runs the observed information (capi.cox_information_device), its
+        factor (capi.info_factor) and capi.cox_baseline_variance_device, sets band_times_, band_cumhaz_, band_var0_ (T,),
+        band_drift_ (T, m), band_factor_ (m, m), band_cols_ and returns self.  Raises ValueError when the information is
+        not positive definite (collinear support columns, or too few events for the support).  An X in GPU memory is
+        read in place on torch's current stream; a NumPy X is served in fp64 NumPy with the same definitions.  fit(),
+        fit_baseline() and predict_survival() do not depend on this."""
+        if self.model_type_int != 4:
+            raise ValueError("fit_survival_bands is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        if not (w >= 0.0).all():
+            raise ValueError("weight should be non-negative")
+        if np.ndim(times) > 1:
+            raise ValueError("times must be 1-D")
+        tg = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        if tg.size < 1:
+            raise ValueError("times is empty: no curve to compute")
+        if np.isnan(tg).any():
+            raise ValueError("There is NAN value in times")
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        m = cols.size
+        wt = None if weight is None else w
+        if on_device:
+            st = _current_stream(X)
+            info = capi.cox_information_device(X, cols, beta[cols], time, status, weight=wt, ties=ties, stream=st)["info"]
+        else:
+            Xs = np.asarray(X, dtype=np.float64)[:, cols]
+            info = self._cox_information_host(Xs, beta[cols], time, status, w, ties)["info"]
+        R, pd = capi.info_factor(info) if m > 0 else (np.zeros((0, 0)), True)
+        if not pd:
+            raise ValueError("fit_survival_bands: the observed information of the fitted model on these rows is not "
+                             "positive definite (collinear support columns, or too few events): no standard errors")
+        if on_device:
+            got = capi.cox_baseline_variance_device(X, cols, beta[cols], time, status, tg, weight=wt, ties=ties, stream=st)
+            cumhaz, var0, drift = got["cumhaz"], got["var0"], got["drift"]
+        else:
+            cumhaz, var0, drift = self._hazard_var_host(Xs, beta[cols], time, status, w, ties, tg)
+        self.band_times_, self.band_cumhaz_, self.band_var0_, self.band_drift_ = tg.copy(), cumhaz, var0, drift
+        self.band_factor_, self.band_cols_ = R, cols
+        return self
+
+    def predict_survival_bands(self, X, kind="survival", conf_type="log-log", level=0.95,
+                               what=("estimate", "lower", "upper")):
+        """Cox only, after fit_survival_bands(): the curves of the rows of X at band_times_ with their standard errors
+        and pointwise confidence bounds.  kind "survival" or "cumhaz"; conf_type "plain", "log" or "log-log" (survival
+        only); level in (0, 1); what a subset of ("estimate", "se", "lower", "upper").  Returns a dict from name to an
+        (n, T) array (definitions: capi.cox_survival_band_device): views of one tensor on X's device for an X in GPU
+        memory, read in place on torch's current stream, NumPy for a NumPy X."""
+        if self.model_type_int != 4:
+            raise ValueError("predict_survival_bands is for the Cox classes, this is a %s model" % self.model_type)
+        on_device, n = self._survival_x(X)
+        capi._band_kind(kind, conf_type)
+        _, names = capi._band_mask(what)
+        zc = capi.normal_quantile(level)
+        if getattr(self, "band_times_", None) is None:
+            raise ValueError("predict_survival_bands needs the variance terms: call fit_survival_bands(X, y, times) first")
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        if not np.array_equal(cols, self.band_cols_):
+            raise ValueError("the support has changed since fit_survival_bands: call it again")
+        if on_device:
+            return capi.cox_survival_band_device(X, cols, beta[cols], self.band_cumhaz_, self.band_var0_, self.band_drift_,
+                                                 self.band_factor_, kind=kind, conf_type=conf_type, level=level,
+                                                 what=names, stream=_current_stream(X))
+        Xs = np.asarray(X, dtype=np.float64)[:, cols]
+        return self._bands_host(Xs, beta[cols], self.band_cumhaz_, self.band_var0_, self.band_drift_, self.band_factor_,
+                                kind, conf_type, zc, names)
+
     # ---- Cox: how good the curves are -------------------------------------------------------------------------------
     @staticmethod
     def _brier_host(eta, hg, times, time, w, row_a, time_b):

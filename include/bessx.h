@@ -1222,6 +1222,103 @@ typedef struct {
   void *stream;
 } bessx_auc_input;
 int bessx_auc_device(const bessx_auc_input *in, double *greater, double *equal, double *pos_weight, double *neg_weight);
+/* ---------------------------------------------------------------------------------------
+ * 2s. Standard errors and pointwise confidence bands of the cumulative hazard and survival curves of ONE Cox model on an X
+ *     already in GPU memory (bessx_k_coxband.hip; Tsiatis 1981, what survival::survfit returns with a Breslow baseline).
+ *     Stateless like sections 2c to 2r.  Notation of section 2h: positions k in the stable ascending order of time, r(k),
+ *     e = exp(clamp(eta, -30, 30)), wd = w * status, S0_k, u_k = S1_k / S0_k; ties as there.
+ *
+ *     bessx_cox_hazard_var_device: on the rows the model was fitted to (x, n, p, cols, m, beta, time, status, weight, ties,
+ *     stream: section 2h; every weight >= 0) and T >= 1 grid times in HOST memory (any order, repeats allowed, a NaN is
+ *     BESSX_ERR_ARG), with K(tau) the positions of time <= tau:
+ *         cumhaz[j]          = sum_{k in K} wd_k / S0_k
+ *         var0[j]            = sum_{k in K} wd_k / S0_k^2
+ *         drift[j * ld + c]  = sum_{k in K} (wd_k / S0_k) u_k[c]            (T x m, drift_ld >= m)
+ *     in HOST memory, *n_events = sum of wd.  A grid time before the first time gives exact zeros.  The predictor pass,
+ *     S0, the hazard scan (section 2f's launcher: under ties = 1 cumhaz is section 2f's baseline at the grid times, bit
+ *     for bit), the gather of W, the means U and the accumulated means (section 2j) are the existing launches as they
+ *     are.  New: var0's increment (section 2j's dh with S0 squared, same tie handling), its scan in section 2f's form, and
+ *     one gather kernel that reads the three prefix arrays at the last position with time <= tau behind which nothing
+ *     is added (the end of the last tie group that holds an event; the host finds it from its sorted times): T (m + 2)
+ *     numbers cross the bus.  Additions only, one fixed order: the same call gives the same bits.  m = 0: drift
+ *     has no columns and nothing of x beyond section 2h's reads is read.  m + 1 <= 1024 (BESSX_ERR_UNSUPPORTED beyond).
+ *     Scratch (bessx_cox_hazard_var_workspace): about (m + 4) n doubles with an event, plus J m for J event rows.
+ *
+ *     bessx_cox_band_device: for ANY rows x (n x p as in section 2c, read in place, the support's columns only), with
+ *     z = x(i, cols), e_i as above, Lambda = cumhaz[j] * e_i, factor = R (m x m lower triangular, HOST memory, element
+ *     (j, k) at [j * factor_ld + k], inverse(info) = R^T R for section 2h's info; its strict upper triangle is never read),
+ *     t = R z and p_j = R drift[j]:
+ *         V(i, j)   = var0[j] + sum_c (p_j[c] - cumhaz[j] * t_c)^2      (= var0 + q^T inverse(info) q, q = drift - z cumhaz)
+ *         se_L      = e_i * sqrt(V),    w = z_c * se_L,    r = z_c * sqrt(V) / cumhaz[j]
+ *         kind _CUMHAZ:    estimate Lambda, se = se_L;  _PLAIN: max(Lambda - w, 0), Lambda + w;  _LOG: Lambda exp(-r),
+ *                          Lambda exp(r);  _LOGLOG: BESSX_ERR_ARG
+ *         kind _SURVIVAL:  estimate S = exp(-Lambda), se = S se_L;  _PLAIN: max(S - z_c se, 0), min(S + z_c se, 1);  _LOG:
+ *                          exp(-(Lambda + w)), exp(-max(Lambda - w, 0));  _LOGLOG: exp(-Lambda exp(r)), exp(-Lambda exp(-r))
+ *     Where cumhaz[j] == 0 (decided by that comparison, never 0 / 0) se is 0 and both bounds are the estimate.  estimate is
+ *     section 2f's expression from section 2f's predictor pass: the same bits for the same hg.  The sum of squares is formed
+ *     directly (additions of non-negative terms: its expansion cancels for columns that are not centred).  The host forms
+ *     p_j in fp64 plain loops in a fixed order; the device forms t in 16 x 16 tiles on the fp64 matrix cores from x in place
+ *     (section 2i's operand layout and access shapes, only the k-steps at or below a tile's diagonal) and, as each tile
+ *     completes, adds the squares per (row, time) for a chunk of times (*time_chunk of the workspace call: 16 for element
+ *     loads, 8 / 4 for 16-byte loads of fp64 / fp32); tiles in ascending order, then the 16 lanes of a DPP row, then var0.
+ *     No n x m or n x T intermediate, no floating-point atomics: V(i, .) depends on row i's values and the T-sized inputs
+ *     alone, whatever the layout, the row's position or n.  m = 0: V = var0 and the matrix-core kernel is not launched.
+ *     what: a non-empty set of BESSX_BAND_ESTIMATE / _SE / _LOWER / _UPPER; out holds K = |what| slabs in that order,
+ *     element (i, j) of slab s at [s * out_slab_stride + i * out_row_stride + j * out_col_stride], device memory of x's
+ *     device when out_on_device != 0 (every slab checked as in section 2c), else host memory staged through a device
+ *     buffer.  z_c >= 0 finite (the normal quantile of the level).  A NaN in a support column of row i reaches the outputs
+ *     of row i and nothing else.  Argument errors (BESSX_ERR_ARG: those of section 2f for x / cols / beta / out; a
+ *     non-finite or negative cumhaz / var0, a non-finite drift or factor, an unknown kind / conf_type / what, _LOGLOG with
+ *     _CUMHAZ) are found before any device call.  m + 1 <= 1024, T <= 65535 (BESSX_ERR_UNSUPPORTED beyond).  Out of scope:
+ *     Efron ties, strata, bands simultaneous over time, robust-covariance bands, more than one model per call.
+ * ------------------------------------------------------------------------------------- */
+enum { BESSX_BAND_PLAIN = 0, BESSX_BAND_LOG = 1, BESSX_BAND_LOGLOG = 2 };
+enum { BESSX_BAND_ESTIMATE = 1, BESSX_BAND_SE = 2, BESSX_BAND_LOWER = 4, BESSX_BAND_UPPER = 8 };
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  const double *times;
+  int T;
+  void *stream;
+} bessx_cox_hazard_var_input;
+int bessx_cox_hazard_var_device(const bessx_cox_hazard_var_input *in, double *cumhaz, double *var0, double *drift,
+                                long long drift_ld, double *n_events);
+int bessx_cox_hazard_var_workspace(int n, int m, int n_event_rows, int T, long long *doubles);
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *cumhaz;
+  const double *var0;
+  const double *drift;
+  long long drift_ld;
+  int T;
+  const double *factor;
+  long long factor_ld;
+  int kind;
+  int conf_type;
+  double z_c;
+  unsigned what;
+  long long out_slab_stride, out_row_stride, out_col_stride;
+  int out_on_device;
+  void *stream;
+} bessx_cox_band_input;
+int bessx_cox_band_device(const bessx_cox_band_input *in, double *out);
+int bessx_cox_band_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int T, unsigned what,
+                             int out_on_device, long long *doubles, int *time_chunk);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1696,6 +1793,11 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
                                   const int *cols, int m, const int *group_starts, int n_groups, const int *groups,
                                   int n_tested, int candidate_block, int sorted, int repeats, double *stage_ms,
                                   double *bytes);
+/* The kernels of section 2s' band call timed the same way for an n x T result of the outputs `what` (K row-major slabs), from
+ * a model, a factor and T-sized inputs of the library's own: stage_ms[0] the predictor pass that stores exp(clip(eta)),
+ * stage_ms[1] k_cbd_band (k_cbd_band0 for m = 0) with the survival / log-log epilogue. */
+int bessx_op_cox_band_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int T, unsigned what, int repeats, double *stage_ms);
 /* The kernels of section 2p timed the same way for R models and T times, from a B, time, weights and an hg of the
  * library's own (distinct times, T ascending times across their range): stage_ms[0] the predictor pass that stores e
  * (R x n, row order), [1] the reduction kernel k_cxb_terms (n * T * R elements), [2] the addition of its slabs. */
