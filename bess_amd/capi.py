@@ -48,6 +48,7 @@ SYMBOLS = [
     "bessx_cox_auc_device", "bessx_cox_auc_workspace", "bessx_auc_device", "bessx_op_pairauc_bench",
     "bessx_info_device", "bessx_info_workspace", "bessx_op_info_bench",
     "bessx_cox_info_device", "bessx_cox_info_workspace", "bessx_op_cox_info_bench",
+    "bessx_cox_zph_device", "bessx_cox_zph_workspace", "bessx_op_cox_zph_bench",
     "bessx_diag_device", "bessx_diag_workspace", "bessx_op_diag_bench",
     "bessx_cox_diag_device", "bessx_cox_diag_workspace", "bessx_op_cox_diag_bench",
     "bessx_meat_device", "bessx_sandwich_device", "bessx_sandwich_workspace", "bessx_op_sandwich_bench",
@@ -178,6 +179,15 @@ class CoxInfoInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
                 ("info", _vp), ("info_ld", _ll), ("score", _vp), ("out_on_device", _i), ("stream", _vp)]
+
+
+class CoxZphInput(ctypes.Structure):
+    """bessx_cox_zph_input: bessx_cox_info_input's model and data, the time transform gt in host memory, and where the
+    three weighted information matrices and the two score vectors go."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("beta", _D), ("time", _D), ("status", _D), ("weight", _D), ("ties", _i),
+                ("gt", _D), ("info0", _vp), ("info1", _vp), ("info2", _vp), ("info_ld", _ll), ("score0", _vp),
+                ("score1", _vp), ("out_on_device", _i), ("stream", _vp)]
 
 
 class CoxDiagInput(ctypes.Structure):
@@ -410,6 +420,9 @@ def lib():
         L.bessx_cox_info_device.argtypes = [ctypes.POINTER(CoxInfoInput), _D, _D, _D]
         L.bessx_cox_info_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
         L.bessx_op_cox_info_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _D, _D]
+        L.bessx_cox_zph_device.argtypes = [ctypes.POINTER(CoxZphInput), _D, _D]
+        L.bessx_cox_zph_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_ll), ctypes.POINTER(_ll), _I]
+        L.bessx_op_cox_zph_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D]
         L.bessx_diag_device.argtypes = [ctypes.POINTER(DiagInput)]
         L.bessx_diag_workspace.argtypes = [_i, _i, ctypes.c_uint, ctypes.POINTER(_ll)]
         L.bessx_op_diag_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _D, _D, _D]
@@ -2670,6 +2683,172 @@ def op_cox_info_bench(x, cols, ties="order", repeats=20):
     _check(lib().bessx_op_cox_info_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
                                          _ip(cols), cols.size, TIES[ties], repeats, _dp(ms), ctypes.byref(nbytes)))
     return tuple(float(v) for v in ms), nbytes.value
+
+
+def cox_zph_workspace(n, m, n_event_rows):
+    """(doubles of scratch memory, (rows per slab, slabs) of the sweep over x, (rows per slab, slabs) of the sweep over the
+    risk-set means) of a cox_zph_device call, as cox_info_workspace states them for cox_information_device
+    (bessx_cox_zph_workspace; no device is needed).  The two sweeps carry three weights each over the same row splits."""
+    nd, rps, sl = _ll(0), (_ll * 2)(), (_i * 2)()
+    _check(lib().bessx_cox_zph_workspace(int(n), int(m), int(n_event_rows), ctypes.byref(nd), rps, sl))
+    return nd.value, (int(rps[0]), int(sl[0])), (int(rps[1]), int(sl[1]))
+
+
+def cox_zph_device(x, cols, beta, time, status, gt, weight=None, ties="order", stream=0):
+    """The ingredients of the proportional-hazards score test (Grambsch and Therneau, the exact form of survival::cox.zph)
+    of ONE Cox model on a device matrix x, read where it lies (bessx_cox_zph_device).  Model, data and definitions are
+    cox_information_device's; gt: the time transform per row (n values, host or device array; zph_transform makes it),
+    read at the rows with status 1 only, finite there, already centred.  With Var_k(x) the weighted covariance of the
+    support's columns over the risk set of event k and u_k their mean there, for q = 0, 1, 2
+        info_q  = sum_k wd_k gt_k^q Var_k(x)          (m, m), both triangles exact mirrors
+        score_q = sum_k wd_k gt_k^q (x_k - u_k)       (m,)   (q = 1: the gt-weighted sum of the Schoenfeld residuals)
+    Returns {"info0", "info1", "info2", "score0", "score1", "loglik", "n_events"}; info0, score0 and loglik are
+    cox_information_device's info, score and loglik bit for bit.  cox_zph_table turns them into the test.  The three
+    matrices come from ONE sweep of the matrix-core Gram over x's support carrying three row weights, and one over the
+    risk-set means; every sum has a fixed order (the same call gives the same bits); a NaN inside the support view
+    propagates.  len(cols) + 1 <= 1024; cols may be empty (the matrices are (0, 0), loglik the null model's)."""
+    a = CoxZphInput()
+    n, p, cols, B, host = _cox_call(a, "cox_zph_device", x, cols, beta, time, status, weight, ties, stream)
+    _survival_vector(gt, n, "gt", check_only=True)
+    g = _survival_vector(gt, n, "gt", stream)
+    if not np.isfinite(g[host["status"] != 0.0]).all():
+        raise ValueError("gt must be finite at every row with status 1")
+    m = cols.size
+    out = {k: np.empty((m, m)) for k in ("info0", "info1", "info2")}
+    out.update({k: np.empty(m) for k in ("score0", "score1")})
+    a.gt, a.info_ld, a.out_on_device = _dp(g), m, 0
+    for k, v in out.items():
+        setattr(a, k, v.ctypes.data)
+    ll, ne = _d(0), _d(0)
+    _check(lib().bessx_cox_zph_device(ctypes.byref(a), ctypes.byref(ll), ctypes.byref(ne)))
+    out.update(loglik=ll.value, n_events=ne.value)
+    return out
+
+
+def op_cox_zph_bench(x, cols, repeats=20):
+    """(fused_ms (repeats,), separate_ms (repeats,)): single timings by device events, alternating, after one warm-up of
+    each, of cox_zph_device's three-weight Gram sweep over the device matrix x for the support cols (with its finish)
+    and of three back-to-back one-weight sweeps of information_device on the same data."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    fused, sep = np.zeros(repeats), np.zeros(repeats)
+    _check(lib().bessx_op_cox_zph_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                        _ip(cols), cols.size, repeats, _dp(fused), _dp(sep)))
+    return fused, sep
+
+
+ZPH_TRANSFORMS = ("km", "rank", "identity", "log")
+
+
+def zph_transform(time, status, weight=None, transform="km"):
+    """(gt (n,), centre): the time transform g(t) of the proportional-hazards test at every row's time, centred, on the
+    host in fp64.  transform: "identity" (t), "log" (log t; a non-positive time at a row with status 1 is a ValueError),
+    "rank" (the mid-rank of t among the times of the rows with status 1: those below it plus half of those equal to it,
+    plus one half), "km" (1 - S(t-), S the weighted Kaplan-Meier estimate of all rows, taken just before t -- what
+    survival::cox.zph uses by default), an array of n values, or a callable applied to the times.  centre = the mean of g
+    over the rows with status 1 weighted by wd = weight * status, summed in np.longdouble and rounded once (0 without
+    such a row); gt = g - centre.  time, status, weight: n values each, host or device arrays (None = ones)."""
+    n = _DeviceArray(time, "time").size if is_device_array(time) else np.size(time)
+    time = _survival_vector(time, n, "time")
+    status = _survival_vector(status, n, "status")
+    w = np.ones(n) if weight is None else _survival_vector(weight, n, "weight")
+    if np.isnan(time).any():
+        raise ValueError("There is NAN value in time")
+    if not np.isin(status, (0.0, 1.0)).all():
+        raise ValueError("status should be 0 or 1")
+    ev = status != 0.0
+    if callable(transform):
+        g = _f64(transform(time)).reshape(-1)
+        if g.size != n:
+            raise ValueError("transform must return n = %d values, got %d" % (n, g.size))
+    elif not isinstance(transform, str):
+        g = _survival_vector(transform, n, "transform").copy()
+    elif transform == "identity":
+        g = time.copy()
+    elif transform == "log":
+        if (time[ev] <= 0.0).any():
+            raise ValueError('transform="log" needs positive times at the rows with status 1')
+        with np.errstate(invalid="ignore", divide="ignore"):
+            g = np.log(time)
+    elif transform == "rank":
+        te = np.sort(time[ev])
+        g = 0.5 * (np.searchsorted(te, time, side="left") + np.searchsorted(te, time, side="right") + 1.0)
+    elif transform == "km":
+        u, S = _km_survival(time, status, w)
+        Sl = np.concatenate([[1.0], S])  # (S just before u[i] is S at u[i - 1], and 1 before the first time)
+        g = 1.0 - Sl[np.searchsorted(u, time, side="left")]
+    else:
+        raise ValueError("transform must be one of %s, an array of n values or a callable, got %r"
+                         % (list(ZPH_TRANSFORMS), transform))
+    if not np.isfinite(g[ev]).all():
+        raise ValueError("the transform must be finite at every row with status 1")
+    wd = (w * status)[ev].astype(np.longdouble)
+    sw = wd.sum()
+    centre = float((wd * g[ev].astype(np.longdouble)).sum() / sw) if sw > 0 else 0.0
+    return g - centre, centre
+
+
+def _scaled_factor(A):
+    """(inverse(A), cond of the scaled matrix, positive definite) by _wald's scaled Cholesky factorisation and tests."""
+    M = A.shape[0]
+    dg = np.diag(A)
+    if not (np.isfinite(A).all() and (dg > 0).all()):
+        return None, float("nan"), False
+    d = 1.0 / np.sqrt(dg)
+    S = A * d[:, None] * d[None, :]
+    S = 0.5 * (S + S.T)
+    ev = np.linalg.eigvalsh(S)
+    if not (ev[0] > M * np.finfo(np.float64).eps * ev[-1]):
+        return None, float("inf") if ev[0] <= 0 else float(ev[-1] / ev[0]), False
+    try:
+        Lc = np.linalg.cholesky(S)
+    except np.linalg.LinAlgError:
+        return None, float(ev[-1] / ev[0]), False
+    Li = np.linalg.solve(Lc, np.eye(M))
+    return (Li.T @ Li) * d[:, None] * d[None, :], float(ev[-1] / ev[0]), True
+
+
+def cox_zph_table(got, centre=None):
+    """The proportional-hazards test from cox_zph_device's dict (or the host route's), on the host in fp64 NumPy with
+    the scaled Cholesky factorisations of wald_table: D = info2 - info1 inverse(info0) info1, the information about
+    theta in beta(t) = beta + theta g(t) at theta = 0 with beta profiled out (score0 is taken as 0: the model is at its
+    optimum).  Returns {"chisq": score1_j^2 / D_jj (m,), "p_value": chi2_sf(chisq, 1), "global_chisq": score1^T
+    inverse(D) score1, "global_df": m, "global_p_value", "slope_var": diag(inverse(D)), "cond": the 2-norm condition
+    number of the scaled D, "cond_info": that of the scaled info0, "positive_definite", "score0", "score1", "n_events",
+    "gt_centre": centre}.  When info0 or D is not positive definite by wald_table's tests -- no event, every event with
+    one value of g (D = 0 up to rounding: a diagonal entry of D not above sqrt(eps) times info2's counts as 0), duplicated
+    columns -- the statistics are NaN and positive_definite is False: data decide
+    that, so nothing is raised.  An empty model gives empty arrays, a global statistic of 0 and positive_definite True."""
+    I0, I1, I2 = (np.array(got[k], dtype=np.float64) for k in ("info0", "info1", "info2"))
+    s0, s1 = (np.asarray(got[k], dtype=np.float64).reshape(-1) for k in ("score0", "score1"))
+    m = s1.size
+    if I0.shape != (m, m) or I1.shape != (m, m) or I2.shape != (m, m) or s0.shape != (m,):
+        raise ValueError("info0, info1, info2 must be (%d, %d) and score0, score1 (%d,)" % (m, m, m))
+    nan_v = np.full(m, np.nan)
+    out = {"chisq": nan_v, "p_value": nan_v.copy(), "global_chisq": float("nan"), "global_df": m,
+           "global_p_value": float("nan"), "slope_var": nan_v.copy(), "cond": float("nan"), "cond_info": float("nan"),
+           "positive_definite": False, "score0": s0, "score1": s1, "n_events": float(got.get("n_events", float("nan"))),
+           "gt_centre": centre}
+    if m == 0:
+        out.update(global_chisq=0.0, global_p_value=1.0, positive_definite=True)
+        return out
+    C0, out["cond_info"], ok = _scaled_factor(I0)
+    if not ok or not (np.isfinite(I1).all() and np.isfinite(I2).all() and np.isfinite(s1).all()):
+        return out
+    D = I2 - I1 @ C0 @ I1
+    D = 0.5 * (D + D.T)
+    # (D is a difference of matrices that are differences themselves: a diagonal entry that keeps less than sqrt(eps) of
+    # info2's has lost half its digits and counts as 0, whatever its sign -- one event time, or one value of g)
+    if not (np.diag(D) > np.sqrt(np.finfo(np.float64).eps) * np.abs(np.diag(I2))).all():
+        return out
+    Dinv, out["cond"], ok = _scaled_factor(D)
+    if not ok:
+        return out
+    chisq = s1 * s1 / np.diag(D)
+    gl = float(s1 @ Dinv @ s1)
+    out.update(chisq=chisq, p_value=np.array([chi2_sf(v, 1) for v in chisq]), global_chisq=gl,
+               global_p_value=chi2_sf(gl, m), slope_var=np.diag(Dinv).copy(), positive_definite=True)
+    return out
 
 
 def cox_addscore_workspace(n, m, n_event_rows, q, candidate_block=0):

@@ -2915,6 +2915,221 @@ int bessx_op_cox_info_bench(const void *x, int dtype, long long row_stride, long
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------
+// the proportional-hazards test of one Cox model on a caller's device matrix (include/bessx.h section 2t)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// doubles of device scratch of one call: section 2h's buffers (its v, g, partials and results stay unused), then gp, the
+// three H^q, v^q and a^q, the partials and results of the three-weight sweeps and the event weights
+long long cox_zph_doubles(long long n, int m, long long J) {
+  long long d = cox_info_doubles(n, m, J);
+  if (m == 0) return d;
+  const long long M = (long long)m + 1;
+  d += n + 3 * n + 6 * n + cox_zph_gram_workspace(n, m) + 6 * (M * M + M) + 3 * (long long)m * m + 2 * m;
+  if (J > 0) d += 3 * J + cox_zph_gram_workspace(J, m);
+  return d;
+}
+
+// everything about the call that needs no device
+int cox_zph_check_args(const char *who, const CoxCall &c, const bessx_cox_zph_input *in, const double *loglik,
+                       const double *n_events) {
+  const std::string w(who);
+  if (!loglik || !n_events || !in->gt) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (int rc = cox_check(who, c, true, true)) return rc;
+  if (c.m > 0 && (!in->info0 || !in->info1 || !in->info2 || !in->score0 || !in->score1))
+    return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (in->info_ld < (long long)c.m) return fail(BESSX_ERR_ARG, w + ": info_ld must be at least m");
+  for (int i = 0; i < c.n; i++)
+    if (c.status[i] != 0.0 && !std::isfinite(in->gt[i]))
+      return fail(BESSX_ERR_ARG, w + ": gt must be finite at every row with status 1");
+  return check_m_max(w, c.m);
+}
+
+// gp: gt in position order with an exact 0 at the positions without an event; cJ: c^q_j = wd g^q of the J event rows in
+// position order, q = 0, 1, 2, J values each -- the products the kernels form ((wd * g) * g)
+void cox_zph_order(const CoxOrder &o, const CoxInfoOrder &x, const double *gt, int n, std::vector<double> *gp,
+                   std::vector<double> *cJ) {
+  const size_t J = (size_t)x.J;
+  gp->assign((size_t)n, 0.0);
+  cJ->resize(3 * J);
+  size_t j = 0;
+  for (int k = 0; k < n; k++)
+    if (o.kg[(size_t)k] != INT_MAX) {
+      const double g = gt[x.rowof[(size_t)k]], c0 = o.wd[(size_t)k], c1 = c0 * g;
+      (*gp)[(size_t)k] = g;
+      (*cJ)[j] = c0;
+      (*cJ)[J + j] = c1;
+      (*cJ)[2 * J + j] = c1 * g;
+      j++;
+    }
+}
+
+int cox_zph_run(Owner &sc, const CoxOrder &o, const CoxInfoOrder &x, const std::vector<double> &gp,
+                const std::vector<double> &cJ, std::vector<double> &h, const bessx_cox_zph_input *in, double *loglik,
+                hipStream_t st) {
+  const int n = in->n, m = in->m, f32 = in->x_dtype == BESSX_F32, ties = in->ties;
+  const long long rs = in->x_row_stride, cs = in->x_col_stride;
+  const size_t N = (size_t)n, M = (size_t)m + 1, mm = (size_t)m * (size_t)m, gs = M * M + M, nout = 3 * mm + 2 * (size_t)m;
+  CoxInfoDev c;
+  if (int rc = cox_info_stage(sc, o, x, in->cols, m, in->beta, n, ties, st, &c)) return rc;
+  const CoxDev &d = c.d;
+  HIPX(hipMemsetAsync(c.res, 0, 2 * sizeof(double), st));
+  // the predictor, e, S0 and the likelihood: section 2h's launches (the same bits)
+  HIPX(launch_cox_eval_eta(in->x, f32, rs, cs, n, d.cols, m, d.B, d.zero, 1, d.pos, d.eta, d.ex, st));
+  if (m > 0) HIPX(hipMemcpyAsync(c.e, d.ex, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPX(launch_cox_eval_loglik(d.eta, d.ex, d.wd, ties ? d.first : nullptr, n, 1, d.work, c.res, st));
+  const bool staged = m > 0 && !in->out_on_device;
+  double *stage = nullptr;
+  if (m > 0) {
+    double *gp_d = nullptr, *H = nullptr, *va = nullptr, *part = nullptr, *G = nullptr;
+    HIPX(sc.alloc(&gp_d, N));
+    HIPX(hipMemcpyAsync(gp_d, gp.data(), N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(sc.alloc(&H, 3 * N));
+    HIPX(sc.alloc(&va, 6 * N));
+    HIPX(sc.alloc(&part, (size_t)cox_zph_gram_workspace(n, m)));
+    HIPX(sc.alloc(&G, 6 * gs));
+    double *v = va, *a = va + 3 * N, *G1 = G, *G2 = G + 3 * gs;
+    HIPX(launch_cox_info_gather(in->x, f32, rs, cs, n, d.cols, m, c.rowof, c.e, c.W, st));
+    HIPX(launch_cox_zph_hazard(d.wd, gp_d, d.ex, d.first, n, H, H + N, H + 2 * N, st));
+    for (int q = 0; q < 3; q++) HIPX(launch_cox_prefix_scan(H + (size_t)q * N, n, c.hs, st));
+    HIPX(launch_cox_zph_vg(c.e, H, n, ties ? c.lastk : nullptr, d.wd, gp_d, d.pos, n, v, a, n, st));
+    HIPX(launch_cox_zph_gram(in->x, f32, rs, cs, n, d.cols, m, v, a, n, part, G1, (long long)gs, st));
+    if (c.J > 0) {
+      const size_t J = (size_t)c.J;
+      double *cJ_d = nullptr, *part2 = nullptr;
+      HIPX(sc.alloc(&cJ_d, 3 * J));
+      HIPX(hipMemcpyAsync(cJ_d, cJ.data(), 3 * J * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPX(sc.alloc(&part2, (size_t)cox_zph_gram_workspace(c.J, m)));
+      HIPX(launch_cox_info_means(c.W, d.ex, c.jptr, n, m, c.J, c.scr, c.U, c.ldU, st));
+      HIPX(launch_cox_zph_gram(c.U, 0, 1, c.ldU, c.J, c.iota, m, cJ_d, cJ_d, c.J, part2, G2, (long long)gs, st));
+    }
+    double *i0 = in->info0, *i1 = in->info1, *i2 = in->info2, *s0 = in->score0, *s1 = in->score1;
+    long long ld = in->info_ld;
+    if (staged) {
+      HIPX(sc.alloc(&stage, nout));
+      i0 = stage, i1 = stage + mm, i2 = stage + 2 * mm, s0 = stage + 3 * mm, s1 = s0 + m;
+      ld = m;
+    }
+    HIPX(launch_cox_zph_finish(G1, c.J > 0 ? G2 : nullptr, (long long)gs, m, i0, i1, i2, ld, s0, s1, st));
+  }
+  h.resize(1 + (staged ? nout : 0));
+  HIPX(hipMemcpyAsync(h.data(), c.res, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (staged) HIPX(hipMemcpyAsync(h.data() + 1, stage, nout * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  *loglik = h[0];
+  if (staged) {
+    const double *r = h.data() + 1;
+    copy_out(r, (size_t)m, (size_t)m, in->info0, in->info_ld);
+    copy_out(r + mm, (size_t)m, (size_t)m, in->info1, in->info_ld);
+    copy_out(r + 2 * mm, (size_t)m, (size_t)m, in->info2, in->info_ld);
+    copy_out(r + 3 * mm, (size_t)m, 1, in->score0, 0);
+    copy_out(r + 3 * mm + (size_t)m, (size_t)m, 1, in->score1, 0);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_zph_workspace(int n, int m, int n_event_rows, long long *doubles, long long *rows_per_slab, int *slabs) {
+  if (!doubles || !rows_per_slab || !slabs) return fail(BESSX_ERR_ARG, "cox_zph_workspace: null argument");
+  if (n < 1 || m < 0) return fail(BESSX_ERR_ARG, "cox_zph_workspace: empty matrix");
+  if (n_event_rows < 0 || n_event_rows > n)
+    return fail(BESSX_ERR_ARG, "cox_zph_workspace: n_event_rows must lie in [0, n]");
+  if (int rc = check_m_max("cox_zph_workspace", m)) return rc;
+  *doubles = cox_zph_doubles(n, m, n_event_rows);
+  rows_per_slab[0] = rows_per_slab[1] = 0;
+  slabs[0] = slabs[1] = 0;
+  if (m > 0) {
+    info_split(n, m, &rows_per_slab[0], &slabs[0]);
+    if (n_event_rows > 0) info_split(n_event_rows, m, &rows_per_slab[1], &slabs[1]);
+  }
+  return BESSX_OK;
+}
+
+int bessx_cox_zph_device(const bessx_cox_zph_input *in, double *loglik, double *n_events) {
+  if (!in) return fail(BESSX_ERR_ARG, "cox_zph_device: null argument");
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_zph_check_args("cox_zph_device", c, in, loglik, n_events)) return rc;
+  int dev = -1;
+  if (int rc = cox_check_device("cox_zph_device", c, &dev)) return rc;
+  if (in->out_on_device && in->m > 0) {
+    const char *names[3] = {"info0", "info1", "info2"};
+    double *const infos[3] = {in->info0, in->info1, in->info2};
+    for (int q = 0; q < 3; q++)
+      if (int rc = check_on_device("cox_zph_device", names[q], infos[q], BESSX_F64, in->info_ld, 1, in->m, in->m, dev))
+        return rc;
+    if (int rc = check_on_device("cox_zph_device", "score0", in->score0, BESSX_F64, 1, 0, in->m, 1, dev)) return rc;
+    if (int rc = check_on_device("cox_zph_device", "score1", in->score1, BESSX_F64, 1, 0, in->m, 1, dev)) return rc;
+  }
+  CoxOrder o;
+  cox_order(in->time, in->status, in->weight, in->n, &o);
+  CoxInfoOrder x;
+  cox_info_order(&o, in->n, in->m, in->ties, &x);
+  std::vector<double> gp, cJ;
+  cox_zph_order(o, x, in->gt, in->n, &gp, &cJ);
+  const int rc = dev_call(dev, c.stream,
+                          [&](DevCall &dc) { return cox_zph_run(dc.sc, o, x, gp, cJ, dc.h, in, loglik, dc.st); });
+  if (!rc) *n_events = x.n_events;
+  return rc;
+}
+
+int bessx_op_cox_zph_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                           const int *cols, int m, int repeats, double *fused_ms, double *separate_ms) {
+  if (!x || repeats < 1 || !fused_ms || !separate_ms || m < 1) return fail(BESSX_ERR_ARG, "op_cox_zph_bench: bad arguments");
+  if (int rc = predict_check_model("op_cox_zph_bench", n, p, cols, m, 1, BESSX_LINK_IDENTITY)) return rc;
+  if (int rc = check_m_max("op_cox_zph_bench", m)) return rc;
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_zph_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  Owner sc;
+  const size_t N = (size_t)n, M = (size_t)m + 1, gs = M * M + M;
+  std::vector<double> v(3 * N), g(3 * N);
+  for (size_t q = 0; q < 3; q++)
+    for (size_t i = 0; i < N; i++) {
+      v[q * N + i] = 0.25 * (double)(q + 1);
+      g[q * N + i] = ((i + q) % 2) ? -0.5 : 0.5;
+    }
+  int *cols_d = nullptr;
+  double *v_d = nullptr, *g_d = nullptr, *part = nullptr, *out = nullptr;
+  HIPX(sc.alloc(&cols_d, (size_t)m));
+  HIPX(sc.alloc(&v_d, v.size()));
+  HIPX(sc.alloc(&g_d, g.size()));
+  HIPX(sc.alloc(&part, (size_t)cox_zph_gram_workspace(n, m)));
+  HIPX(sc.alloc(&out, 3 * gs));
+  HIPX(hipMemcpy(cols_d, cols, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(v_d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(g_d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  const int f32 = dtype == BESSX_F32;
+  for (int i = -1; i < repeats; i++)  // (i = -1: the warm-up of both routes)
+    for (int route = 0; route < 2; route++) {
+      HIPX(hipEventRecord(e0, nullptr));
+      if (route == 0) {
+        HIPX(launch_cox_zph_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d, g_d, n, part, out, (long long)gs,
+                                 nullptr));
+      } else {
+        for (size_t q = 0; q < 3; q++)
+          HIPX(launch_info_gram(x, f32, row_stride, col_stride, n, cols_d, m, v_d + q * N, g_d + q * N, part,
+                                out + q * gs, (long long)M, out + q * gs + M * M, nullptr));
+      }
+      HIPX(hipEventRecord(e1, nullptr));
+      HIPX(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPX(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 0) (route == 0 ? fused_ms : separate_ms)[i] = (double)ms;
+    }
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
 // residuals, dfbeta and case influence of one Cox model on a caller's device matrix (include/bessx.h section 2j)
 // ----------------------------------------------------------------------------------------------
 namespace {

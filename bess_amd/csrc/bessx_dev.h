@@ -243,6 +243,25 @@ hipError_t launch_cox_info_vg(const double *e, const double *H, const int *lastk
                               long long n, double *v, double *g, hipStream_t st);
 hipError_t launch_cox_info_finish(const double *G1, const double *G2, const double *U1, int m, double *info, long long ld,
                                   double *score, double *res, hipStream_t st);
+// the proportional-hazards score test of one Cox model (bessx_k_coxzph.hip), on top of the arrays of bessx_k_coxinfo.hip.
+// gp: the time transform in position order, an exact 0 where status is 0.  _hazard: h^q[k] = wd[k] gp[k]^q / S[first[k]],
+// q = 0, 1, 2 (their forward scans are launch_cox_prefix_scan).  _vg: v^q_i = e[pos[i]] * H^q[lastk[pos[i]]] and a^q_i =
+// wd gp^q - v^q_i in ROW order, weight q at + q * vs (H^q at + q * hs; lastk null: the identity).  _gram: launch_info_gram
+// for the three weight pairs (vw + q * ws, gw + q * ws) in ONE sweep, each weight's results bit for bit launch_info_gram's
+// with that weight alone: G + q * gs holds the (m + 1) x (m + 1) matrix (leading dimension m + 1), then the m + 1 score
+// values; part: cox_zph_gram_workspace(n, m) doubles.  _finish: info_q = G1^q - G2^q without the intercept entry (G2
+// null: no event), score0, score1.  Device memory.
+long long cox_zph_gram_workspace(long long n, int m);
+hipError_t launch_cox_zph_hazard(const double *wd, const double *gp, const double *S, const int *first, long long n,
+                                 double *h0, double *h1, double *h2, hipStream_t st);
+hipError_t launch_cox_zph_vg(const double *e, const double *H, long long hs, const int *lastk, const double *wd,
+                             const double *gp, const int *pos, long long n, double *v, double *a, long long vs,
+                             hipStream_t st);
+hipError_t launch_cox_zph_gram(const void *src, int f32, long long rs, long long cs, long long n, const int *cols, int m,
+                               const double *vw, const double *gw, long long ws, double *part, double *G, long long gs,
+                               hipStream_t st);
+hipError_t launch_cox_zph_finish(const double *G1, const double *G2, long long gs, int m, double *info0, double *info1,
+                                 double *info2, long long ld, double *score0, double *score1, hipStream_t st);
 // residuals and case influence of one Cox model (bessx_k_coxdiag.hip), on top of the arrays of bessx_k_coxinfo.hip.
 // _accum: A(c, l) = sum_{p <= l} dh_p U(jptr[p], c), m x n position-major with leading dimension ldA = cox_diag_lda(n)
 // (dh: n doubles, scr: ceil(n / 1024) * m doubles; U null: no event, A = 0).  _form: L(c, k) = g[rowof[k]] x(rowof[k],

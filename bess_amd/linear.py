@@ -1100,6 +1100,102 @@ class bess_base:
         out.update(cols=cols, loglik=float(got["loglik"]), residual_sum=float(got["residual_sum"]))
         return out
 
+    # ---- Cox: the test of proportional hazards -----------------------------------------------------------------------
+    @staticmethod
+    def _cox_zph_host(Xs, beta, time, status, w, gt, ties):
+        """cox_zph_device's quantities in fp64 NumPy, by the same decomposition as _cox_information_host with the event
+        weights wd g^q, q = 0, 1, 2: Xs (n, m) the support's columns, gt (n,) the centred time transform (read at the
+        rows with status 1), the other arguments in row order."""
+        n, m = Xs.shape
+        eta = np.zeros(n)
+        for c in range(m):  # (column by column: a row's sum does not depend on where the row lies)
+            eta += Xs[:, c] * beta[c]
+        order = np.argsort(time, kind="stable")
+        x, eta, t, d = Xs[order], eta[order], time[order], status[order]
+        wd = w[order] * d
+        g = np.where(d != 0, gt[order], 0.0)
+        new = np.ones(n, dtype=bool)
+        new[1:] = t[1:] != t[:-1]
+        starts = np.nonzero(new)[0]
+        first = np.maximum.accumulate(np.where(new, np.arange(n), 0))
+        last = np.append(starts[1:] - 1, n - 1)[np.cumsum(new) - 1]
+        a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))  # (comparisons: a NaN stays a NaN)
+        e = np.exp(a)
+        r = first if ties == "breslow" else np.arange(n)
+        S0 = np.cumsum(e[::-1])[::-1][r]
+        out = {"loglik": float(np.sum(wd * (a - np.log(S0)))), "n_events": float(np.sum(wd))}
+        ev = d != 0
+        U = np.cumsum((e[:, None] * x)[::-1], axis=0)[::-1][r[ev]] / S0[ev][:, None]
+        c = wd
+        for q in range(3):
+            H = np.cumsum(c / S0)
+            if ties == "breslow":
+                H = H[last]
+            v = e * H
+            info = x.T @ (v[:, None] * x) - U.T @ (c[ev][:, None] * U)
+            out["info%d" % q] = np.tril(info) + np.tril(info, -1).T
+            if q < 2:
+                out["score%d" % q] = x.T @ (c - v)
+            c = c * g
+        return out
+
+    def proportional_hazards_test(self, X, y, weight=None, ties="order", transform="km", residuals=False):
+        """Cox only: the test of the proportional-hazards assumption of the fitted model on the rows (X, y) -- the score
+        test of theta_j = 0 in beta_j(t) = beta_j + theta_j g(t) for every selected column and of all of them together
+        (Grambsch and Therneau 1994, in the exact form survival::cox.zph has used since 3.0: the information matrices
+        weighted by g and g^2 are computed, not approximated by a constant variance).  y: (n, 2) time and status as in
+        fit; weight: n values or None; ties: "order" or "breslow"; transform: "km" (the default), "rank", "identity",
+        "log", an array of n values or a callable (capi.zph_transform; g is centred at its event-weighted mean).
+        Returns capi.cox_zph_table's dict (chisq, p_value per column on 1 degree of freedom, global_chisq, global_df,
+        global_p_value, slope_var, cond, cond_info, positive_definite, score0, score1, n_events) plus cols, the selected
+        columns in the order of chisq, transform, gt_centre and loglik.  A small p_value says that the column's effect
+        drifts with g(t).  The model is taken to be at its optimum (score0, returned, is treated as 0); selection is not
+        corrected for.  An X in GPU memory is read in place on torch's current stream by capi.cox_zph_device, the
+        support's columns only (y and weight may be device arrays: n values each are copied to the host); a NumPy X is
+        served in fp64 NumPy with the same decomposition.
+        residuals=True adds "time" (the J event times in time order) and "scaled_schoenfeld" (J, m): r_j inv(info0) *
+        n_events + beta, the points survival::cox.zph plots against g(t), r the Schoenfeld residuals of
+        diagnostics_survival (capi.cox_diagnostics_device(kinds=("schoenfeld",)) for an X in GPU memory, where the
+        product is a matrix product on the device and the result lies there); NaN where info0 is not positive definite."""
+        if self.model_type_int != 4:
+            raise ValueError("proportional_hazards_test is for the Cox classes, this is a %s model" % self.model_type)
+        if ties not in capi.TIES:
+            self._survival_x(X)
+            raise ValueError("ties must be one of %s, got %r" % (sorted(capi.TIES), ties))
+        on_device, n, time, status, w, weight = self._survival_data(X, y, weight)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        cols = np.nonzero(beta)[0]
+        m = cols.size
+        wt = None if weight is None else w
+        gt, centre = capi.zph_transform(time, status, wt, transform)
+        if on_device:
+            st = _current_stream(X)
+            got = capi.cox_zph_device(X, cols, beta[cols], time, status, gt, weight=wt, ties=ties, stream=st)
+        else:
+            Xs = np.asarray(X, dtype=np.float64)[:, cols]
+            got = self._cox_zph_host(Xs, beta[cols], time, status, w, gt, ties)
+        out = capi.cox_zph_table(got, centre)
+        out.update(cols=cols, transform=transform if isinstance(transform, str) else "user", loglik=float(got["loglik"]))
+        if residuals:
+            C = capi._scaled_factor(np.array(got["info0"], dtype=np.float64))[0] if m > 0 else np.zeros((0, 0))
+            if C is None:
+                C = np.full((m, m), np.nan)
+            C = C * float(got["n_events"])
+            if on_device:
+                d = capi.cox_diagnostics_device(X, cols, beta[cols], time, status, weight=wt, ties=ties,
+                                                kinds=("schoenfeld",), stream=st)
+                r = d["schoenfeld"]
+                if capi.is_device_array(r):
+                    import torch
+                    ss = r @ torch.as_tensor(C, device=r.device) + torch.as_tensor(beta[cols], device=r.device)
+                else:
+                    ss = np.asarray(r) @ C + beta[cols]
+            else:
+                d = self._cox_diagnostics_host(Xs, beta[cols], time, status, w, ties, None, None, ("schoenfeld",))
+                ss = d["schoenfeld"] @ C + beta[cols]
+            out.update(time=np.asarray(d["event_times"]), scaled_schoenfeld=ss)
+        return out
+
     # ---- Cox: score tests of the columns left out ----------------------------------------------------------------------
     @staticmethod
     def _cox_score_terms(X, cols, beta, time, status, w, ties):

@@ -1319,6 +1319,63 @@ typedef struct {
 int bessx_cox_band_device(const bessx_cox_band_input *in, double *out);
 int bessx_cox_band_workspace(int x_dtype, long long x_row_stride, long long x_col_stride, int n, int m, int T, unsigned what,
                              int out_on_device, long long *doubles, int *time_chunk);
+/* ---------------------------------------------------------------------------------------
+ * 2t. The test of the proportional-hazards assumption of ONE Cox model on an X already in GPU memory
+ *     (bessx_k_coxzph.hip; Grambsch and Therneau 1994 in the exact form survival::cox.zph has used since 3.0, not the
+ *     constant-variance approximation).  Stateless like sections 2c to 2s.  x, n, p, cols, m, beta, time, status, weight,
+ *     ties, stream: exactly as in section 2h (the vectors in HOST memory); positions, r(k), e, wd, S0, u_k: sections 2e and
+ *     2h.  gt: the time transform per row, n doubles in HOST memory, read at the rows with status = 1 only (finite there:
+ *     else BESSX_ERR_ARG) and already centred by the caller; g_k its value at position k.  For q = 0, 1, 2
+ *         h^q_k = wd_k g_k^q / S0(k),   H^q_l = sum_{k : r(k) <= l} h^q_k,   v^q_l = e_l H^q_l,   a^q_l = wd_l g_l^q - v^q_l
+ *         info_q  = G1^q - G2^q,   G1^q = sum_l v^q_l x_l x_l^T,   G2^q = sum_{k : status_k = 1} wd_k g_k^q u_k u_k^T
+ *         score_q = sum_l a^q_l x_l        ( = sum_k wd_k g_k^q (x_k - u_k): for q = 1 the g-weighted sum of the Schoenfeld
+ *                                            residuals of section 2j )
+ *     with wd_k g_k^2 formed as (wd_k g_k) g_k.  info_q = sum_k wd_k g_k^q Var_k(x), the information weighted by g^q.
+ *     info0, score0 and loglik are section 2h's info, score and loglik BIT FOR BIT, and where gt is 1 at every event so
+ *     are info1, info2 and score1.  The score test of theta = 0 in beta(t) = beta + theta g(t) follows on the host
+ *     (score0 taken as 0): D = info2 - info1 inverse(info0) info1, global = score1^T inverse(D) score1 on m degrees of
+ *     freedom, and per column score1_j^2 / D_jj on one.  g may be negative: the q = 1 sums are not sums of non-negative
+ *     terms, and info_q is a DIFFERENCE as in section 2h.
+ *     The predictor pass, the S0 scan, the gather of e x and the means u_k are section 2h's launches, unchanged.  The
+ *     three H^q are three runs of section 2f's forward scan.  G1^q for q = 0, 1, 2 is ONE sweep of the matrix-core Gram
+ *     over x in place that carries the three weight pairs (the loads and the unweighted operand are shared; each weight
+ *     has its own accumulators and gets the bits section 2g's sweep gives with that weight alone), G2^q a second such
+ *     sweep over the J x m matrix of the u_k.  No floating-point atomics; block and slab counts depend on (n, m, J)
+ *     alone: the same call gives the same bits.
+ *     info0, info1, info2: m x m each, entry (j, k) at [j * info_ld + k], info_ld >= m shared by the three, both triangles
+ *     written as bit-identical mirrors; score0, score1: m values each.  They are device memory of x's device when
+ *     out_on_device != 0 (checked as in section 2c), else host memory; loglik and n_events (= sum_k wd_k) are host
+ *     memory.  m = 0 is valid: nothing of x is read, the outputs are untouched and loglik is the null model's.  Without an
+ *     event row the matrices and vectors are exact zeros.  m + 1 <= 1024: a larger m is BESSX_ERR_UNSUPPORTED, with every
+ *     other argument error (BESSX_ERR_ARG, the messages of sections 2e / 2h) found before any device call.  A NaN INSIDE
+ *     the support view is no error and propagates; nothing outside the view is read.  Scratch memory (section 2h's plus
+ *     10 n + 3 J doubles and the partials of the two three-weight sweeps: about (m + 15) n + J m doubles plus partials,
+ *     bessx_cox_zph_workspace states it) is released before the call returns: counters 38 / 39 are back at their
+ *     earlier values.
+ *     bessx_cox_zph_workspace needs no device: the doubles of scratch memory and the row splits of the two sweeps as in
+ *     bessx_cox_info_workspace (rows_per_slab[0], slabs[0] over n rows, [1] over J rows; 0, 0 for a sweep not launched).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *beta;
+  const double *time;
+  const double *status;
+  const double *weight;
+  int ties;
+  const double *gt;
+  double *info0, *info1, *info2;
+  long long info_ld;
+  double *score0, *score1;
+  int out_on_device;
+  void *stream;
+} bessx_cox_zph_input;
+int bessx_cox_zph_device(const bessx_cox_zph_input *in, double *loglik, double *n_events);
+int bessx_cox_zph_workspace(int n, int m, int n_event_rows, long long *doubles, long long *rows_per_slab, int *slabs);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1798,6 +1855,11 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
  * stage_ms[1] k_cbd_band (k_cbd_band0 for m = 0) with the survival / log-log epilogue. */
 int bessx_op_cox_band_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int T, unsigned what, int repeats, double *stage_ms);
+/* Section 2t's sweep over x for three row-weight pairs of the library's own, device events with one warm-up, `repeats`
+ * single timings each way, alternating: fused_ms[i] one launch of the three-weight sweep with its finish, separate_ms[i]
+ * three back-to-back launches of section 2g's one-weight sweep with its finish on the same data. */
+int bessx_op_cox_zph_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                           const int *cols, int m, int repeats, double *fused_ms, double *separate_ms);
 /* The kernels of section 2p timed the same way for R models and T times, from a B, time, weights and an hg of the
  * library's own (distinct times, T ascending times across their range): stage_ms[0] the predictor pass that stores e
  * (R x n, row order), [1] the reduction kernel k_cxb_terms (n * T * R elements), [2] the addition of its slabs. */
