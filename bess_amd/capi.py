@@ -33,6 +33,7 @@ SYMBOLS = [
     "bessx_session_marginal_scores", "bessx_session_cov_prefill_begin", "bessx_session_cov_prefill_compute",
     "bessx_session_cov_prefill_export", "bessx_session_cov_prefill_import", "bessx_session_cov_prefill_end",
     "bessx_session_cov_prefill_extend", "bessx_session_cov_state", "bessx_session_cov_cache_columns",
+    "bessx_session_score_state",
     "bessx_session_cv_fill_geometry", "bessx_op_xtv", "bessx_op_topk", "bessx_op_gram",
     "bessx_op_chol_solve", "bessx_op_topk_bench", "bessx_op_chol_bench", "bessx_op_normalize", "bessx_op_stream_copy_gbps", "bessx_op_xtv_bench", "bessx_op_cox_score_bench",
     "bessx_op_cox_state", "bessx_op_cox_score", "bessx_op_cox_score_multi", "bessx_op_glm_gh", "bessx_op_glm_irls", "bessx_op_glm_irls_geometry",
@@ -352,6 +353,7 @@ def lib():
         L.bessx_session_cov_prefill_extend.argtypes = [_vp, _I, _i]
         L.bessx_session_cov_state.argtypes = [_vp, _D, _I]
         L.bessx_session_cov_cache_columns.argtypes = [_vp, _i, _I, _i, _D, _I]
+        L.bessx_session_score_state.argtypes = [_vp, _i, _I, _D, _I, _D, _D, _vp, _D, _D, _D, _D]
         L.bessx_session_cv_fill_geometry.argtypes = [_vp, _I]
         L.bessx_session_cov_prefill_compute.argtypes = [_vp, _i, _i]
         L.bessx_session_cov_prefill_export.argtypes = [_vp, _i, _i, _vp, _i]
@@ -996,6 +998,35 @@ class Session:
         hit = np.zeros(c.size, dtype=np.int32)
         _check(lib().bessx_session_cov_cache_columns(self._h, int(row_set), _ip(c), c.size, _dp(out), _ip(hit)))
         return out.T.copy(), hit.astype(bool)
+
+    SCORE_STATE_HEAD = ("done", "l", "T0", "k_cur", "d_fresh", "info", "cov_miss", "fast_same", "serial", "row_set",
+                        "bmm_owner", "score_mode", "U", "nrb", "n", "p", "sums_are_d", "known", "has_inA", "ahead")
+
+    def score_state(self, ctx=-1):
+        """The score state in device memory, read-only (bessx_session_score_state): the control block's fields and the
+        host's record of the fit it describes (SCORE_STATE_HEAD, "lambda"), the model (A_cur, b_cur, beta_dense, inA), the
+        scores bd, the sums they were formed from ("d": p values in the covariance form; "part": nrb x p row-block
+        partials and "r": the residual the pass read, in the streaming form) and cov_bmm as (min inside, max outside,
+        column of that max) per block of 32 columns.  ctx >= 0: fold context ctx of the side-by-side CV chains."""
+        p, n = self.p_kept, self.n
+        head, lam = np.zeros(len(self.SCORE_STATE_HEAD), dtype=np.int32), _d(0)
+        _check(lib().bessx_session_score_state(self._h, int(ctx), _ip(head), ctypes.byref(lam), None, None, None, None,
+                                               None, None, None, None))
+        st = {k: int(v) for k, v in zip(self.SCORE_STATE_HEAD, head)}
+        A, b, beta, bd = np.zeros(p, dtype=np.int32), np.zeros(p), np.zeros(p), np.zeros(p)
+        inA, r = np.zeros(p, dtype=np.uint8), np.zeros(n)
+        sums = np.zeros((1 if st["sums_are_d"] else st["nrb"]) * p)
+        nb = (p + 31) // 32
+        bmm = np.zeros(3 * nb)
+        _check(lib().bessx_session_score_state(self._h, int(ctx), _ip(head), ctypes.byref(lam), _ip(A), _dp(b), _dp(beta),
+                                               inA.ctypes.data_as(_vp), _dp(bd), _dp(sums), _dp(r), _dp(bmm)))
+        st = {k: int(v) for k, v in zip(self.SCORE_STATE_HEAD, head)}
+        k = max(0, min(st["k_cur"], p))
+        st.update({"lambda": lam.value, "A_cur": A[:k].copy(), "b_cur": b[:k].copy(), "beta_dense": beta,
+                   "inA": inA.astype(bool), "bd": bd, "r": r,
+                   "bmm_min": bmm[0:2 * nb:2].copy(), "bmm_max": bmm[1:2 * nb:2].copy(), "bmm_arg": bmm[2 * nb:].copy()})
+        st["d" if st["sums_are_d"] else "part"] = sums if st["sums_are_d"] else sums.reshape(st["nrb"], p)
+        return st
 
     def cv_fill_geometry(self):
         """How the CV row sets' Gram fills run (bessx_session_cv_fill_geometry): shared fills or masked ones, and the

@@ -133,6 +133,8 @@ int fold_fits_side_by_side(bessx_session *s, double *out, const std::vector<int>
     q.scores_ok = q.use_cache && cc.lambda == lambda;
     q.grow1 = q.scores_ok && cc.T0 + 1 == T0;
     c->dev_state_rs = rs;
+    c->dev_state_lambda = lambda;
+    c->dev_state_serial = q.serial;
     if (!q.use_cache && q.k_init > 0) {
       SBS(open_fit(q));  // (fit_begin leaves the initial support in A_cur)
       q.todo = NONE;

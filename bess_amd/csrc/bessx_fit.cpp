@@ -1422,6 +1422,8 @@ int algorithm_fit(bessx_session *s) {
                          s->beta_dense, s->p, s->hist, s->st, s->inA, my_serial);
   }
   s->dev_state_rs = rs;
+  s->dev_state_lambda = lambda;
+  s->dev_state_serial = my_serial;
   if (e == hipSuccess && !use_cache && !cov) {
     if (!glm)
       e = launch_resid_lm(s->X, s->ld, s->n, s->y, s->mask[rs], s->ctrl, 0, s->A_cur, s->b_cur, s->r_rs[rs], s->sse,

@@ -292,6 +292,8 @@ struct bessx_session {
   bool geig_on = true;  // (test hook group_eig=0: diagonalise at every iteration, round 3's form)
   int cox_state_rs = -1;
   int dev_state_rs = -1;                // row set of the fit whose final coefficients sit in A_cur/b_cur/beta_dense
+  double dev_state_lambda = 0.0;        // ... the lambda of that fit and the serial number it was queued under (what
+  int dev_state_serial = 0;             // bessx_session_score_state reports next to the control block; never read by a fit)
   CoxBufs cox = {};                     // Cox work space (model_type 4 only)
   int *idcols = nullptr;
   struct RsCache {

@@ -939,6 +939,57 @@ int bessx_session_cov_state(bessx_session *s, double *bd, int *slot_of) {
   return BESSX_OK;
 }
 
+// Diagnostic, read-only: the control block of the fit the device ran last, the host's record of which fit that was, and
+// the model, scores and score-pass sums in device memory -- both forms of the LM score pass, singleton groups.  Like
+// bessx_session_cov_cache_columns it waits for the streams and copies: nothing is allocated or queued, and ahead,
+// cache[], dev_state_rs and bmm_owner stay as they are (a chain queued ahead is neither consumed nor broken).
+int bessx_session_score_state(bessx_session *s, int ctx, int *head, double *lambda, int *A_cur, double *b_cur,
+                              double *beta_dense, unsigned char *inA, double *bd, double *sums, double *r, double *cov_bmm) {
+  if (!s) return fail(BESSX_ERR_ARG, "null session");
+  if (s->model_type != 1 || s->grouped)
+    return fail(BESSX_ERR_UNSUPPORTED, "score_state: LM sessions with singleton groups only");
+  if (!head || !lambda) return fail(BESSX_ERR_ARG, "score_state: head and lambda are required");
+  if (ctx >= (int)s->fold_ctx.size()) return fail(BESSX_ERR_ARG, "score_state: the session has no such fold context");
+  HIPX(hipSetDevice(s->device));
+  HIPX(hipStreamSynchronize(s->st));
+  for (bessx_session *c : s->fold_ctx) HIPX(hipStreamSynchronize(c->st));
+  const bessx_session *c = ctx >= 0 ? s->fold_ctx[(size_t)ctx] : s;
+  FitCtrl hc;
+  HIPX(hipMemcpy(&hc, c->ctrl, sizeof(FitCtrl), hipMemcpyDeviceToHost));
+  // which fit the block describes: the one queued last by a call, or the one chained ahead of the next call
+  const bessx_session::Ahead &ah = c->ahead;
+  const bool is_ahead = ah.serial > 0 && hc.serial == ah.serial && hc.serial != c->dev_state_serial;
+  const int rs = is_ahead ? ah.rs : c->dev_state_rs;
+  const bool known = rs >= 0 && rs < (int)c->part_rs.size() && (is_ahead || c->parent || hc.serial == c->dev_state_serial);
+  // (a covariance-form session runs a fit whose level does not fit the Gram column cache in the streaming form)
+  const bool cov_layout = c->cov_mode && (is_ahead || !known || c->cache[(size_t)rs].cov_layout);
+  const int p = c->p, k = std::max(0, std::min(hc.k_cur, c->cap));
+  const int vals[BESSX_SCORE_STATE_HEAD] = {hc.done, hc.l, hc.T0, hc.k_cur, hc.d_fresh, hc.info, hc.cov_miss, hc.fast_same,
+                                            hc.serial, rs, c->bmm_owner, c->cov_mode ? 2 : 1, c->U, c->nrb, c->n, p,
+                                            cov_layout ? 1 : 0, known ? 1 : 0, c->inA ? 1 : 0, is_ahead ? 1 : 0};
+  std::copy(vals, vals + BESSX_SCORE_STATE_HEAD, head);
+  *lambda = is_ahead ? ah.lambda : c->dev_state_lambda;
+  if (A_cur && k) HIPX(hipMemcpy(A_cur, c->A_cur, (size_t)k * sizeof(int), hipMemcpyDeviceToHost));
+  if (b_cur && k) HIPX(hipMemcpy(b_cur, c->b_cur, (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+  if (beta_dense) HIPX(hipMemcpy(beta_dense, c->beta_dense, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+  if (inA) {
+    if (c->inA) HIPX(hipMemcpy(inA, c->inA, (size_t)p, hipMemcpyDeviceToHost));
+    else std::fill(inA, inA + p, (unsigned char)0);
+  }
+  if (bd) HIPX(hipMemcpy(bd, c->bd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+  const int rs_buf = known ? rs : 0;
+  if (sums)
+    HIPX(hipMemcpy(sums, c->part_rs[(size_t)rs_buf], (size_t)(cov_layout ? 1 : c->nrb) * p * sizeof(double),
+                   hipMemcpyDeviceToHost));
+  if (r) HIPX(hipMemcpy(r, c->r_rs[(size_t)rs_buf], (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost));
+  if (cov_bmm) {
+    const size_t nb = (size_t)3 * ((p + 31) / 32);
+    if (c->cov_bmm) HIPX(hipMemcpy(cov_bmm, c->cov_bmm, nb * sizeof(double), hipMemcpyDeviceToHost));
+    else std::fill(cov_bmm, cov_bmm + nb, 0.0);
+  }
+  return BESSX_OK;
+}
+
 // Diagnostic, read-only: the cached Gram columns of ONE row set (0 = all rows, k + 1 = the training rows of fold k), on
 // sessions with and without folds.  The fold contexts of the side-by-side chains borrow the session's caches
 // (fold_ctx_create copies the cov vector: the pointers are the owner's), so the owner's caches are what every fit of

@@ -1620,6 +1620,28 @@ int bessx_session_cov_prefill_end(bessx_session *s);
  * queues nothing.  BESSX_ERR_UNSUPPORTED outside the covariance form of the LM score pass, BESSX_ERR_ARG for a row set
  * the session does not have or a column outside 0 .. p-1. */
 int bessx_session_cov_cache_columns(bessx_session *s, int row_set, const int *cols, int ncols, double *dst, int *cached);
+/* Diagnostic, read-only: the score state in device memory.  LM sessions with singleton groups, both forms of the score
+ * pass; BESSX_ERR_UNSUPPORTED otherwise.  ctx < 0: the session's own state; ctx >= 0: fold context ctx of the
+ * side-by-side CV chains (BESSX_ERR_ARG where the session has none).  Waits for the session's and the fold contexts'
+ * streams and copies; allocates nothing, queues nothing and changes no host bookkeeping, so a fit chained ahead on the
+ * device stays as it is.  head[BESSX_SCORE_STATE_HEAD]:
+ *    0..8  the control block: done, l, T0, k_cur, d_fresh, info, cov_miss, fast_same, serial
+ *    9     row set of the fit that block describes (0 = all rows, k + 1 = training rows of fold k; -1: not recorded)
+ *   10     row set of the score kernel that wrote cov_bmm last (-1: bd was re-scored since, or never)
+ *   11..15 score_mode (1 streaming, 2 covariance), U, nrb (row blocks of 128 U rows of the streaming pass), n, p
+ *   16     layout of `sums`: 1 = d itself, p doubles (covariance form); 0 = the nrb x p row-block partials, row block
+ *          after row block, as the streaming pass leaves them
+ *   17     1 if the host has a record of the fit the block describes (then head[9] and *lambda are that fit's)
+ *   18     1 if the session keeps membership flags (inA; covariance form), else inA is returned as zeros
+ *   19     1 if the block describes a fit chained ahead on the device that no call has asked for yet
+ * *lambda: the ridge parameter of that fit.  A_cur, b_cur: the first k_cur entries are written (buffers of p entries
+ * always suffice); beta_dense, inA, bd: p entries; sums: p or nrb * p doubles (head[16]); r: the n residuals m o (y - X b)
+ * the streaming pass read; cov_bmm: 3 * ceil(p / 32) doubles -- per block of 32 columns the smallest score inside the
+ * active set (DBL_MAX if none) and the largest outside it (-1 if none), interleaved, then the lowest column attaining
+ * each maximum (2147483647 if none).  Every array pointer may be NULL. */
+#define BESSX_SCORE_STATE_HEAD 20
+int bessx_session_score_state(bessx_session *s, int ctx, int *head, double *lambda, int *A_cur, double *b_cur,
+                              double *beta_dense, unsigned char *inA, double *bd, double *sums, double *r, double *cov_bmm);
 /* How the Gram fills of the CV row sets run.  out[0]: 1 = shared (one unmasked pass over a fold-major copy of X, every
  * fold padded to whole row slabs, serves all K + 1 row sets), 0 = one masked pass per row set (also: no folds).
  * out[1]: row slabs per fold, out[2]: rows per slab, out[3]: rows of the copy = K * out[1] * out[2]; 0 unless shared. */

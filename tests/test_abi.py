@@ -65,3 +65,6 @@ def test_argument_validation_needs_no_gpu():
     geo = (ctypes.c_int * 4)()
     assert lib.bessx_session_cov_cache_columns(None, 0, None, 0, None, None) == 1
     assert lib.bessx_session_cv_fill_geometry(None, geo) == 1
+    assert lib.bessx_session_score_state(None, -1, None, None, None, None, None, None, None, None, None, None) == 1
+    assert len(capi.Session.SCORE_STATE_HEAD) == 20  # BESSX_SCORE_STATE_HEAD of include/bessx.h
+    assert "#define BESSX_SCORE_STATE_HEAD 20" in open(os.path.join(ROOT, "include", "bessx.h")).read()

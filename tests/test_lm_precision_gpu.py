@@ -9,17 +9,21 @@ so their reference reads the fp64 columns the library itself holds: the output o
 runs (k_col_normalize: one workgroup per column, independent of the row padding; (e) checks that a session's x_mean /
 x_norm are bitwise op_normalize's).
 
-What is not reachable through the ABI, and therefore not covered: the scores of a streaming session (cov_state serves the
-covariance form only; marginal_scores is compared in both modes).  Gram columns of a CV row set are not compared HERE (the
+Covered elsewhere: the score VALUES beyond what (c) sees here.  cov_state serves the covariance form only, and (c) reads it
+after TRACED fits (the trace names the model the last scores were formed from); tracing switches the fused selection +
+solve launch (k_sel_cgr), the chained start, the lambda-only re-score and the arg-max start off.  tests/test_score_state_gpu.py
+reads the whole score state through bessx_session_score_state -- control block, A_cur / b_cur, bd, the sums bd was formed
+from, the per-block extremes of k_cov_d -- and holds to xprec.scores: the scores of STREAMING sessions after fits (with the
+residual and k_xtv's row-block partial sums, at every U and at nrb % 4 != 0), the scores of UNTRACED covariance-form fits on
+the default launches and bitwise under fuse_sel=0 / fuse=0 / chain=0, and the scores that are kept instead of recomputed
+(chained paths, row-set switches).  Gram columns of a CV row set are not compared HERE (the
 prefill export serves row set 0 of sessions without folds only): tests/test_cv_gram_gpu.py holds every row set's cached
 columns -- shared fills, masked fills, the refused fold-major copy, more than one slab per fold -- to the same bound through
 bessx_session_cov_cache_columns.  The hand-over at CGB_MAX_K from bessx_cgbig.hip to the blocked Cholesky is listed in
 LARGE_T0 and runs in its own test.
-Also not covered: the score VALUES of the fused launches.  cov_state is compared after traced fits (the trace names the
-model the last scores were formed from), and tracing switches the fused selection + solve launch (k_sel_cgr) off, so (c)
-sees k_cov_d followed by the unfused selection; the fused launches are held to the coefficient and loss bounds of (a)
-only.  marginal_scores is host arithmetic on x_j.y and x_j.x_j read back from the device: it covers the kernels that
-form those sums, not k_score / k_cov_d.
+Here the fused launches are held to the coefficient and loss bounds of (a); their score values are in that file too.
+marginal_scores is host arithmetic on x_j.y and x_j.x_j read back from the device: it covers the kernels that form those
+sums, not k_score / k_cov_d.
 
 Measured maxima (MI355X, 2026-10-16, on top of commit 9b20946):
   restricted fits, |b - b*| / bound, all routes                      0.011   (collinear, lam = 0.3; benign designs 0.0025;
