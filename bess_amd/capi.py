@@ -43,6 +43,7 @@ SYMBOLS = [
     "bessx_op_ingest_bench", "bessx_predict_device", "bessx_op_predict_bench", "bessx_eval_device", "bessx_op_eval_bench",
     "bessx_eval_cox_device", "bessx_op_cox_eval_bench",
     "bessx_cox_baseline_device", "bessx_cox_survival_device", "bessx_op_cox_surv_bench",
+    "bessx_cox_survtime_device", "bessx_cox_survtime_workspace", "bessx_op_cox_rmst_bench",
     "bessx_cox_hazard_var_device", "bessx_cox_hazard_var_workspace", "bessx_cox_band_device", "bessx_cox_band_workspace",
     "bessx_op_cox_band_bench",
     "bessx_cox_brier_device", "bessx_cox_brier_workspace", "bessx_op_cox_brier_bench",
@@ -113,6 +114,17 @@ class CoxSurvivalInput(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
                 ("cols", _I), ("m", _i), ("B", _D), ("hg", _D), ("T", _i), ("kind", _i), ("out_row_stride", _ll),
                 ("out_col_stride", _ll), ("out_on_device", _i), ("stream", _vp)]
+
+
+class CoxSurvtimeInput(ctypes.Structure):
+    """bessx_cox_survtime_input: one Cox model, X in GPU memory; the segments and cuts of the RMST part and the baseline
+    and levels of the quantile part in host memory (either part absent: count 0, pointers NULL); how the two outputs are
+    laid out, strides in elements."""
+    _fields_ = [("x", _vp), ("x_dtype", _i), ("x_row_stride", _ll), ("x_col_stride", _ll), ("n", _i), ("p", _i),
+                ("cols", _I), ("m", _i), ("B", _D), ("hs", _D), ("wd", _D), ("K", _i), ("cut", _I), ("T", _i),
+                ("hz", _D), ("ut", _D), ("J", _i), ("c", _D), ("Q", _i), ("rmst_row_stride", _ll),
+                ("rmst_col_stride", _ll), ("quant_row_stride", _ll), ("quant_col_stride", _ll), ("out_on_device", _i),
+                ("stream", _vp)]
 
 
 class CoxHazardVarInput(ctypes.Structure):
@@ -403,7 +415,10 @@ def lib():
         L.bessx_cox_baseline_device.argtypes = [ctypes.POINTER(CoxBaselineInput), _I, _D, _D]
         L.bessx_cox_survival_device.argtypes = [ctypes.POINTER(CoxSurvivalInput), _vp]
         L.bessx_op_cox_surv_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _D]
-        L.bessx_cox_hazard_var_device.argtypes = [ctypes.POINTER(CoxHazardVarInput), _D, _D, _D, _ll, _D]
+        L.bessx_cox_survtime_device.argtypes = [ctypes.POINTER(CoxSurvtimeInput), _vp, _vp]
+        L.bessx_cox_survtime_workspace.argtypes = [_i, _I, _i, _I, _I, ctypes.POINTER(_ll), ctypes.POINTER(_ll)]
+        L.bessx_op_cox_rmst_bench.argtypes = [_vp, _i, _ll, _ll, _i, _i, _I, _i, _i, _i, _i, _i, _i, _D]
+        L.bessx_cox_hazard_var_device.argtypes =[ctypes.POINTER(CoxHazardVarInput), _D, _D, _D, _ll, _D]
         L.bessx_cox_hazard_var_workspace.argtypes = [_i, _i, _i, _i, ctypes.POINTER(_ll)]
         L.bessx_cox_band_device.argtypes = [ctypes.POINTER(CoxBandInput), _vp]
         L.bessx_cox_band_workspace.argtypes = [_i, _ll, _ll, _i, _i, _i, ctypes.c_uint, _i, ctypes.POINTER(_ll), _I]
@@ -3300,6 +3315,182 @@ def cox_survival_device(x, cols, B, base_times, base_cumhaz, times=None, kind="s
     a.stream = int(stream) if stream else None
     _check(lib().bessx_cox_survival_device(ctypes.byref(a), ptr))
     return result
+
+
+def rmst_segments(base_times, base_cumhaz, tau):
+    """The step function S(t | x) = exp(-H0(t) e) cut into the segments that the restricted mean survival time
+    RMST(tau) = integral_0^tau S(t | x) dt sums over, on the host: (hs, wd, cut) with
+        RMST_i(tau[j]) = sum over k < cut[j] of wd[k] * exp(-(hs[k] * e_i)).
+    The breakpoints are 0, every base time below max(tau) and every tau, merged in ascending order; segment k spans
+    [a_k, b_k) with hs[k] = baseline_at(base_times, base_cumhaz, a_k) and wd[k] = b_k - a_k in fp64 (segments of zero
+    width are dropped), and cut[j] is the number of segments that end at or before tau[j].  base_times ascending and
+    non-negative (what cox_baseline_device returned); tau 1-D with at least one value, finite and >= 0, in any order,
+    repeats allowed.  The curve keeps its last value beyond the last base time; tau = 0 gives cut = 0 (an RMST of exactly
+    0.0); a baseline without an event gives the segments of hazard 0 (an RMST of exactly tau).  A NaN or negative or
+    infinite tau, or a negative base time, is a ValueError.  Returns (hs float64 (K,), wd float64 (K,), cut int32 (T,))."""
+    base_times, base_cumhaz = _f64(base_times).reshape(-1), _f64(base_cumhaz).reshape(-1)
+    if base_times.size != base_cumhaz.size:
+        raise ValueError("base_times and base_cumhaz must have the same size, got %d and %d"
+                         % (base_times.size, base_cumhaz.size))
+    tau = np.asarray(tau, dtype=np.float64)
+    if tau.ndim != 1 or tau.size < 1:
+        raise ValueError("tau must be 1-D with at least one value, got shape %s" % (tau.shape,))
+    if np.isnan(tau).any():
+        raise ValueError("There is NAN value in tau")
+    if not (np.isfinite(tau) & (tau >= 0.0)).all():
+        raise ValueError("tau should be finite and non-negative")
+    if np.isnan(base_times).any():
+        raise ValueError("There is NAN value in base_times")
+    if (base_times < 0.0).any():
+        raise ValueError("base_times should be non-negative")
+    pts = np.unique(np.concatenate([[0.0], base_times[base_times < tau.max()], tau]))  # ascending and distinct
+    hs = np.ascontiguousarray(baseline_at(base_times, base_cumhaz, pts[:-1]))
+    wd = np.ascontiguousarray(pts[1:] - pts[:-1])
+    return hs, wd, np.searchsorted(pts, tau).astype(np.int32)
+
+
+def survival_levels(q):
+    """The cumulative-hazard levels c = -log1p(-q) of the q-quantiles of the survival time (S(t) <= 1 - q exactly when
+    H(t) >= c), in fp64; q 0-D or 1-D with every value in (0, 1), else a ValueError."""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or q.size < 1:
+        raise ValueError("q must be a number or 1-D with at least one value, got shape %s" % (q.shape,))
+    if not ((q > 0.0) & (q < 1.0)).all():
+        raise ValueError("q should lie strictly between 0 and 1")
+    return -np.log1p(-q)
+
+
+def _hazard_levels(q, hazard_levels):
+    """The (Q,) levels c > 0 of a quantile request given as q or as hazard_levels (one of the two)."""
+    if q is not None and hazard_levels is not None:
+        raise ValueError("give q or hazard_levels, not both")
+    if q is not None:
+        return np.ascontiguousarray(survival_levels(q))
+    c = np.atleast_1d(np.asarray(hazard_levels, dtype=np.float64))
+    if c.ndim != 1 or c.size < 1:
+        raise ValueError("hazard_levels must be a number or 1-D with at least one value, got shape %s" % (c.shape,))
+    if not (c > 0.0).all():
+        raise ValueError("hazard_levels should be positive")
+    return np.ascontiguousarray(c)
+
+
+def _quantile_baseline(base_times, base_cumhaz):
+    """(ut, hz) of a quantile request, checked: the same size, no NaN, hz non-negative and non-decreasing."""
+    ut, hz = _f64(base_times).reshape(-1), _f64(base_cumhaz).reshape(-1)
+    if ut.size != hz.size:
+        raise ValueError("base_times and base_cumhaz must have the same size, got %d and %d" % (ut.size, hz.size))
+    if np.isnan(ut).any():
+        raise ValueError("There is NAN value in base_times")
+    if not (hz >= 0.0).all():
+        raise ValueError("base_cumhaz should be non-negative")
+    if (np.diff(hz) < 0.0).any():
+        raise ValueError("base_cumhaz should be non-decreasing")
+    return ut, hz
+
+
+def _survtime_out(out, what, x, n, T):
+    """(result, ptr, row stride, column stride, on_device) of an (n, T) output of cox_survival_times_device: out as in
+    cox_survival_device."""
+    if out is not None:
+        if not is_device_array(out):
+            raise ValueError("%s must be a device array" % what)
+        do = _DeviceArray(out, what)
+        if do.item != 8:
+            raise ValueError("%s: a device array of float64 is needed (typestr '<f8')" % what)
+        if do.shape != (n, T):
+            raise ValueError("%s must have shape %s, got %s" % (what, (n, T), do.shape))
+        return out, do.ptr, do.strides[0], do.strides[1], 1
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(x, torch.Tensor):
+        result = torch.empty((n, T), dtype=torch.float64, device=x.device)
+        return result, int(result.data_ptr()), T, 1, 1
+    result = np.empty((n, T))
+    return result, int(result.ctypes.data), T, 1, 0
+
+
+def cox_survtime_workspace(n, cut):
+    """What the RMST part of cox_survival_times_device needs for n rows and the cuts of rmst_segments
+    (bessx_cox_survtime_workspace; no device): {"slab": the segments of a piece at most, "pieces", "rows_per_chunk",
+    "doubles": the doubles of device scratch with device outputs}."""
+    cut = _i32(np.asarray(cut).reshape(-1))
+    slab, pieces, rows, doubles = _i(0), _i(0), _ll(0), _ll(0)
+    _check(lib().bessx_cox_survtime_workspace(int(n), _ip(cut), cut.size, ctypes.byref(slab), ctypes.byref(pieces),
+                                              ctypes.byref(rows), ctypes.byref(doubles)))
+    return {"slab": slab.value, "pieces": pieces.value, "rows_per_chunk": rows.value, "doubles": doubles.value}
+
+
+def cox_survival_times_device(x, cols, B, base_times, base_cumhaz, tau=None, q=None, hazard_levels=None, out_rmst=None,
+                              out_quantile=None, stream=0):
+    """One number per row and horizon / level from one Cox model, for the rows of a device matrix x (n x p: float64 or
+    float32, any non-negative strides) read once where it lies, the support's columns only
+    (bessx_cox_survtime_device).  No curve is stored.  With eta = x[:, cols] @ B, e = exp(clip(eta, -30, 30)), H0 the step
+    function of baseline_at(base_times, base_cumhaz, .) and S(t | x_i) = exp(-(H0(t) * e_i)):
+        tau (T,):  "rmst" (n, T), the restricted mean survival times integral_0^tau[j] S(t | x_i) dt, the finite sum
+                   over the segments of rmst_segments(base_times, base_cumhaz, tau) (tau finite and >= 0, any order,
+                   repeats allowed; tau = 0 gives exactly 0.0), in fp64 by additions only in a fixed order: the bits of a
+                   row depend neither on n nor on where the row lies, and along ascending tau a row never decreases;
+        q (Q,) in (0, 1), or hazard_levels (Q,) > 0 (one of the two):  "quantile" (n, Q), the first base time at which
+                   base_cumhaz * e_i (one fp64 product) reaches the level c = -log1p(-q), that is at which
+                   S(t | x_i) <= 1 - q; +inf when the curve never gets there (a baseline without an event included);
+                   q = 0.5 is the median survival time.  (survival::survfit averages two times where S equals 1 - q
+                   exactly; this does not.)
+    At least one of tau, q and hazard_levels must be given; only the requested keys are returned.  A NaN in a support
+    column of row i gives NaN in every output of row i and nowhere else.  base_times, base_cumhaz: what
+    cox_baseline_device returned.  out_rmst / out_quantile: float64 device arrays of shape (n, T) / (n, Q) to write into,
+    any strides; without them the results are torch tensors on x's device when x is a torch tensor (torch is looked up,
+    never imported) and NumPy arrays for any other device object.  stream: raw handle of the stream x was produced on;
+    the results are complete when the call returns."""
+    dx = _DeviceArray(x, "x", 2)
+    n, p = dx.shape
+    cols, B = _cox_model(dx, cols, B)
+    want_q = q is not None or hazard_levels is not None
+    if tau is None and not want_q:
+        raise ValueError("nothing to compute: give tau, q or hazard_levels")
+    parts = {}
+    if tau is not None:
+        hs, wd, cut = rmst_segments(base_times, base_cumhaz, tau)
+        if not (hs >= 0.0).all():
+            raise ValueError("base_cumhaz should be non-negative")
+        parts["rmst"] = (hs, wd, cut) + _survtime_out(out_rmst, "out_rmst", x, n, cut.size)
+    elif out_rmst is not None:
+        raise ValueError("out_rmst goes with tau")
+    if want_q:
+        c = _hazard_levels(q, hazard_levels)
+        ut, hz = _quantile_baseline(base_times, base_cumhaz)
+        parts["quantile"] = (hz, ut, c) + _survtime_out(out_quantile, "out_quantile", x, n, c.size)
+    elif out_quantile is not None:
+        raise ValueError("out_quantile goes with q or hazard_levels")
+    # one call serves both parts (one predictor pass) unless one result is device memory and the other a host array
+    groups = [list(parts)] if len({v[-1] for v in parts.values()}) == 1 else [[k] for k in parts]
+    for names in groups:
+        a = CoxSurvtimeInput()
+        _set_x(a, dx)
+        a.cols, a.m, a.B = _ip(cols), cols.size, _dp(B)
+        a.stream = int(stream) if stream else None
+        rm_ptr = qu_ptr = None
+        if "rmst" in names:
+            hs, wd, cut, _, rm_ptr, a.rmst_row_stride, a.rmst_col_stride, a.out_on_device = parts["rmst"]
+            a.hs, a.wd, a.K, a.cut, a.T = _dp(hs), _dp(wd), hs.size, _ip(cut), cut.size
+        if "quantile" in names:
+            hz, ut, c, _, qu_ptr, a.quant_row_stride, a.quant_col_stride, a.out_on_device = parts["quantile"]
+            a.hz, a.ut, a.J, a.c, a.Q = _dp(hz), _dp(ut), hz.size, _dp(c), c.size
+        _check(lib().bessx_cox_survtime_device(ctypes.byref(a), rm_ptr, qu_ptr))
+    return {k: v[3] for k, v in parts.items()}
+
+
+def op_cox_rmst_bench(x, cols, K=1000, T=100, J=1000, Q=5, repeats=20):
+    """Milliseconds per launch of the device steps of cox_survival_times_device on the device matrix x for the support
+    cols, device events, for K segments, T horizons, J base times and Q levels of the library's own: (predictor pass that
+    stores exp(clip(eta)) in row order, k_cxr_partial over every chunk of rows, k_cxr_finish over every chunk,
+    k_cxr_quantile)."""
+    dx = _DeviceArray(x, "x", 2)
+    cols, _, _ = _predict_model(dx, cols)
+    if min(int(K), int(T), int(J), int(Q)) < 1:
+        raise ValueError("K, T, J and Q must be at least 1")
+    ms = np.zeros(4)
+    _check(lib().bessx_op_cox_rmst_bench(dx.ptr, dx.dtype, dx.strides[0], dx.strides[1], dx.shape[0], dx.shape[1],
+                                         _ip(cols), cols.size, int(K), int(T), int(J), int(Q), repeats, _dp(ms)))
+    return tuple(float(v) for v in ms)
 
 
 BAND_CONF = {"plain": 0, "log": 1, "log-log": 2}  # BESSX_BAND_PLAIN / _LOG / _LOGLOG

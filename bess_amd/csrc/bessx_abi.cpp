@@ -1873,6 +1873,273 @@ int bessx_op_cox_surv_bench(const void *x, int dtype, long long row_stride, long
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------
+// Restricted mean and quantile survival times on a caller's device matrix (include/bessx.h section 2u)
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+// the host side of the RMST part: the pieces of the used segments, and the columns sorted by the pieces in front of them
+struct RmstPlan {
+  int Kc = 0, NP = 0;  // segments below the largest cut; pieces
+  std::vector<int> pstart, colq, colj;
+};
+
+void rmst_plan(const int *cut, int T, RmstPlan *pl) {
+  pl->Kc = T > 0 ? *std::max_element(cut, cut + T) : 0;
+  pl->pstart.assign((size_t)(pl->Kc / cox_rmst_slab() + T + 1), 0);
+  std::vector<int> q((size_t)T);
+  pl->NP = T > 0 ? cox_rmst_pieces(cut, T, pl->pstart.data(), q.data()) : 0;
+  pl->colj.resize((size_t)T);
+  std::iota(pl->colj.begin(), pl->colj.end(), 0);
+  std::stable_sort(pl->colj.begin(), pl->colj.end(), [&](int a, int b) { return q[(size_t)a] < q[(size_t)b]; });
+  pl->colq.resize((size_t)T);
+  for (int s = 0; s < T; s++) pl->colq[(size_t)s] = q[(size_t)pl->colj[(size_t)s]];
+}
+
+// its device side: buffers of `sc`, uploads queued on st (the plan and hs / wd must outlive them)
+struct RmstDev {
+  double *hs = nullptr, *wd = nullptr, *part = nullptr;
+  int *pstart = nullptr, *colq = nullptr, *colj = nullptr;
+  long long rows = 0;  // rows per launch pair
+};
+
+int rmst_stage(Owner &sc, const RmstPlan &pl, const double *hs, const double *wd, int T, long long n, hipStream_t st,
+               RmstDev *d) {
+  const size_t Kc = (size_t)pl.Kc, NP = (size_t)pl.NP;
+  d->rows = cox_rmst_chunk_rows(n, pl.NP);
+  HIPX(sc.alloc(&d->hs, 2 * Kc));
+  d->wd = d->hs + Kc;
+  HIPX(sc.alloc(&d->pstart, NP + 1 + 2 * (size_t)T));
+  d->colq = d->pstart + NP + 1;
+  d->colj = d->colq + T;
+  HIPX(sc.alloc(&d->part, NP * (size_t)d->rows));
+  if (Kc > 0) {
+    HIPX(hipMemcpyAsync(d->hs, hs, Kc * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(d->wd, wd, Kc * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  HIPX(hipMemcpyAsync(d->pstart, pl.pstart.data(), (NP + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->colq, pl.colq.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d->colj, pl.colj.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// the launch pairs of every chunk of rows, in order on st (the partials of a chunk are read before the next overwrites
+// them); only = 1 / 2: the partial / the finish kernels alone
+int rmst_launch(const RmstPlan &pl, const RmstDev &d, const double *ex, long long n, int T, double *out, long long ors,
+                long long ocs, hipStream_t st, int only = 0) {
+  for (long long row0 = 0; row0 < n; row0 += d.rows) {
+    const long long nr = std::min(d.rows, n - row0);
+    if (pl.NP > 0 && only != 2) HIPX(launch_cox_rmst_partial(ex + row0, nr, d.hs, d.wd, d.pstart, pl.NP, d.part, st));
+    if (only != 1)
+      HIPX(launch_cox_rmst_finish(ex + row0, d.part, nr, pl.NP, d.colq, d.colj, T, out + row0 * ors, ors, ocs, st));
+  }
+  return 0;
+}
+
+// an n x T row-major staged result to the caller's host memory at its strides (tmp: the call's host vector)
+int survtime_to_host(std::vector<double> &tmp, const double *stage, long long n, long long T, double *out, long long ors,
+                     long long ocs, hipStream_t st) {
+  const size_t cnt = (size_t)n * (size_t)T;
+  const bool dense = (T == 1 || ocs == 1) && (n == 1 || ors == T);
+  double *h = out;
+  if (!dense) {
+    tmp.resize(cnt);
+    h = tmp.data();
+  }
+  HIPX(hipMemcpyAsync(h, stage, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  if (!dense)
+    for (long long i = 0; i < n; i++)
+      for (long long j = 0; j < T; j++) out[i * ors + j * ocs] = h[i * T + j];
+  return 0;
+}
+
+int cox_survtime_run(DevCall &dc, const bessx_cox_survtime_input *in, const RmstPlan &pl, double *rmst, double *quant) {
+  Owner &sc = dc.sc;
+  hipStream_t st = dc.st;
+  const int n = in->n, T = in->T, Q = in->Q, J = in->J, f32 = in->x_dtype == BESSX_F32;
+  const bool dev_out = in->out_on_device != 0;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *zero_d = nullptr, *ex = nullptr, *rm = rmst, *qu = quant;
+  if (int rc = predict_upload_model(sc, in->cols, in->m, in->B, &kCoxZero, 1, st, &cols_d, &B_d, &zero_d)) return rc;
+  HIPX(sc.alloc(&ex, (size_t)n));
+  HIPX(launch_cox_surv_ex(in->x, f32, in->x_row_stride, in->x_col_stride, n, cols_d, in->m, B_d, zero_d, ex, st));
+  if (T > 0) {
+    RmstDev d;
+    if (int rc = rmst_stage(sc, pl, in->hs, in->wd, T, n, st, &d)) return rc;
+    if (!dev_out) HIPX(sc.alloc(&rm, (size_t)n * (size_t)T));
+    if (int rc = rmst_launch(pl, d, ex, n, T, rm, dev_out ? in->rmst_row_stride : T, dev_out ? in->rmst_col_stride : 1, st))
+      return rc;
+  }
+  if (Q > 0) {
+    double *hz_d = nullptr, *c_d = nullptr;
+    HIPX(sc.alloc(&hz_d, 2 * (size_t)J));
+    HIPX(sc.alloc(&c_d, (size_t)Q));
+    if (J > 0) {
+      HIPX(hipMemcpyAsync(hz_d, in->hz, (size_t)J * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPX(hipMemcpyAsync(hz_d + J, in->ut, (size_t)J * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIPX(hipMemcpyAsync(c_d, in->c, (size_t)Q * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!dev_out) HIPX(sc.alloc(&qu, (size_t)n * (size_t)Q));
+    HIPX(launch_cox_quantile(ex, n, J > 0 ? hz_d : nullptr, J > 0 ? hz_d + J : nullptr, J, c_d, Q, qu,
+                             dev_out ? in->quant_row_stride : Q, dev_out ? in->quant_col_stride : 1, st));
+  }
+  if (dev_out) {
+    HIPX(hipStreamSynchronize(st));
+    return 0;
+  }
+  if (T > 0)
+    if (int rc = survtime_to_host(dc.h, rm, n, T, rmst, in->rmst_row_stride, in->rmst_col_stride, st)) return rc;
+  if (Q > 0)
+    if (int rc = survtime_to_host(dc.h, qu, n, Q, quant, in->quant_row_stride, in->quant_col_stride, st)) return rc;
+  return 0;
+}
+
+int survtime_check_strides(const std::string &w, const char *what, int n, int cols, long long rs, long long cs) {
+  if (rs < 0 || cs < 0) return fail(BESSX_ERR_ARG, w + ": strides must be non-negative");
+  if ((n > 1 && rs == 0) || (cols > 1 && cs == 0))
+    return fail(BESSX_ERR_ARG, w + ": " + what + ": a zero stride along an axis longer than 1");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bessx_cox_survtime_device(const bessx_cox_survtime_input *in, double *rmst, double *quant) {
+  const std::string w("cox_survtime_device");
+  if (!in) return fail(BESSX_ERR_ARG, w + ": null argument");
+  const CoxCall c = cox_call(in);
+  if (int rc = cox_check("cox_survtime_device", c, false, false)) return rc;
+  const int T = in->T, Q = in->Q, K = in->K, J = in->J;
+  if (T < 0 || Q < 0 || K < 0 || J < 0) return fail(BESSX_ERR_ARG, w + ": T, Q, K and J must be non-negative");
+  if (T == 0 && Q == 0) return fail(BESSX_ERR_ARG, w + ": nothing to compute (T = 0 and Q = 0)");
+  if ((T > 0) != (rmst != nullptr)) return fail(BESSX_ERR_ARG, w + ": rmst goes with T >= 1, and is NULL with T = 0");
+  if ((Q > 0) != (quant != nullptr)) return fail(BESSX_ERR_ARG, w + ": quant goes with Q >= 1, and is NULL with Q = 0");
+  if (T > 0) {
+    if (!in->cut || (K > 0 && (!in->hs || !in->wd))) return fail(BESSX_ERR_ARG, w + ": null argument (hs, wd or cut)");
+    for (int k = 0; k < K; k++) {
+      if (!(in->hs[k] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": hs must be non-negative");
+      if (!(in->wd[k] > 0.0)) return fail(BESSX_ERR_ARG, w + ": wd must be positive");
+    }
+    for (int j = 0; j < T; j++)
+      if (in->cut[j] < 0 || in->cut[j] > K) return fail(BESSX_ERR_ARG, w + ": cut must lie in [0, K]");
+    if (int rc = survtime_check_strides(w, "rmst", in->n, T, in->rmst_row_stride, in->rmst_col_stride)) return rc;
+  }
+  if (Q > 0) {
+    if (!in->c || (J > 0 && (!in->hz || !in->ut))) return fail(BESSX_ERR_ARG, w + ": null argument (hz, ut or c)");
+    for (int g = 0; g < J; g++) {
+      if (!(in->hz[g] >= 0.0)) return fail(BESSX_ERR_ARG, w + ": hz must be non-negative");
+      if (g > 0 && in->hz[g] < in->hz[g - 1]) return fail(BESSX_ERR_ARG, w + ": hz must be non-decreasing");
+      if (std::isnan(in->ut[g])) return fail(BESSX_ERR_ARG, w + ": ut holds a NaN");
+    }
+    for (int j = 0; j < Q; j++)
+      if (!(in->c[j] > 0.0)) return fail(BESSX_ERR_ARG, w + ": c must be positive");
+    if (int rc = survtime_check_strides(w, "quant", in->n, Q, in->quant_row_stride, in->quant_col_stride)) return rc;
+  }
+  int dev = -1;
+  if (int rc = cox_check_device("cox_survtime_device", c, &dev)) return rc;
+  if (in->out_on_device) {
+    if (T > 0)
+      if (int rc = check_on_device("cox_survtime_device", "rmst", rmst, BESSX_F64, in->rmst_row_stride,
+                                   in->rmst_col_stride, in->n, T, dev))
+        return rc;
+    if (Q > 0)
+      if (int rc = check_on_device("cox_survtime_device", "quant", quant, BESSX_F64, in->quant_row_stride,
+                                   in->quant_col_stride, in->n, Q, dev))
+        return rc;
+  }
+  RmstPlan pl;  // (declared before dev_call: the uploads of the call read it)
+  rmst_plan(in->cut, T, &pl);
+  return dev_call(dev, c.stream, [&](DevCall &dc) { return cox_survtime_run(dc, in, pl, rmst, quant); });
+}
+
+int bessx_cox_survtime_workspace(int n, const int *cut, int T, int *slab, int *pieces, long long *rows_per_chunk,
+                                 long long *doubles) {
+  const std::string w("cox_survtime_workspace");
+  if (!slab || !pieces || !rows_per_chunk || !doubles || (T > 0 && !cut)) return fail(BESSX_ERR_ARG, w + ": null argument");
+  if (n < 1 || T < 0) return fail(BESSX_ERR_ARG, w + ": n must be at least 1 and T non-negative");
+  for (int j = 0; j < T; j++)
+    if (cut[j] < 0) return fail(BESSX_ERR_ARG, w + ": cut must be non-negative");
+  RmstPlan pl;
+  rmst_plan(cut, T, &pl);
+  *slab = cox_rmst_slab();
+  *pieces = pl.NP;
+  *rows_per_chunk = T > 0 ? cox_rmst_chunk_rows(n, pl.NP) : 0;
+  *doubles = n;
+  if (T > 0) *doubles += 2LL * pl.Kc + (long long)pl.NP * *rows_per_chunk + (pl.NP + 1 + 2LL * T + 1) / 2;
+  return BESSX_OK;
+}
+
+int bessx_op_cox_rmst_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int K, int T, int J, int Q, int repeats, double *stage_ms) {
+  if (repeats < 1 || !stage_ms || K < 1 || T < 1 || J < 1 || Q < 1)
+    return fail(BESSX_ERR_ARG, "op_cox_rmst_bench: bad arguments");
+  if (!x) return fail(BESSX_ERR_ARG, "op_cox_rmst_bench: null argument");
+  if (int rc = check_x_model("op_cox_rmst_bench", x, dtype, row_stride >= 0 && col_stride >= 0, n, p, cols, m, &kCoxZero, 1,
+                             BESSX_LINK_IDENTITY, false))
+    return rc;  // (B is the library's own)
+  if (int rc = need_device()) return rc;
+  int dev = -1;
+  if (int rc = check_device_matrix("op_cox_rmst_bench: x", x, dtype, row_stride, col_stride, n, p, &dev)) return rc;
+  HIPX(hipSetDevice(dev));
+  std::vector<double> B((size_t)m), hs((size_t)K), wd((size_t)K), hzut(2 * (size_t)J), lev((size_t)Q);
+  std::vector<int> cut((size_t)T);
+  for (size_t q = 0; q < B.size(); q++) B[q] = ((q % 7) - 3.0) / 64.0;
+  for (int k = 0; k < K; k++) {  // a cumulative hazard that reaches 3 over a span of 1
+    hs[(size_t)k] = 3.0 * k / K;
+    wd[(size_t)k] = 1.0 / K;
+  }
+  for (int j = 0; j < T; j++) cut[(size_t)j] = (int)((long long)K * (j + 1) / T);
+  for (int g = 0; g < J; g++) {
+    hzut[(size_t)g] = 3.0 * (g + 1) / J;
+    hzut[(size_t)J + g] = g + 1.0;
+  }
+  for (int j = 0; j < Q; j++) lev[(size_t)j] = -std::log1p(-(j + 1.0) / (Q + 1.0));
+  RmstPlan pl;
+  rmst_plan(cut.data(), T, &pl);
+  Owner sc;
+  int *cols_d = nullptr;
+  double *B_d = nullptr, *zero_d = nullptr, *ex = nullptr, *hz_d = nullptr, *c_d = nullptr, *rm = nullptr, *qu = nullptr;
+  if (int rc = predict_upload_model(sc, cols, m, B.data(), &kCoxZero, 1, nullptr, &cols_d, &B_d, &zero_d)) return rc;
+  RmstDev d;
+  if (int rc = rmst_stage(sc, pl, hs.data(), wd.data(), T, n, nullptr, &d)) return rc;
+  HIPX(sc.alloc(&ex, (size_t)n));
+  HIPX(sc.alloc(&hz_d, 2 * (size_t)J));
+  HIPX(sc.alloc(&c_d, (size_t)Q));
+  HIPX(sc.alloc(&rm, (size_t)n * (size_t)T));
+  HIPX(sc.alloc(&qu, (size_t)n * (size_t)Q));
+  HIPX(hipMemcpy(hz_d, hzut.data(), 2 * (size_t)J * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipMemcpy(c_d, lev.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice));
+  HIPX(hipDeviceSynchronize());
+  const int f32 = dtype == BESSX_F32;
+  hipEvent_t e0, e1;
+  HIPX(sc.event(&e0));
+  HIPX(sc.event(&e1));
+  for (int stage = 0; stage < 4; stage++) {
+    float total = 0.f;
+    for (int i = -1; i < repeats; i++) {  // (i = -1: the warm-up)
+      HIPX(hipEventRecord(e0, nullptr));
+      if (stage == 0) {
+        HIPX(launch_cox_surv_ex(x, f32, row_stride, col_stride, n, cols_d, m, B_d, zero_d, ex, nullptr));
+      } else if (stage == 3) {
+        HIPX(launch_cox_quantile(ex, n, hz_d, hz_d + J, J, c_d, Q, qu, Q, 1, nullptr));
+      } else if (int rc = rmst_launch(pl, d, ex, n, T, rm, T, 1, nullptr, stage)) {
+        return rc;
+      }
+      HIPX(hipEventRecord(e1, nullptr));
+      HIPX(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPX(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 0) total += ms;
+    }
+    stage_ms[stage] = total / repeats;
+  }
+  return BESSX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------
 // IPCW Brier score of R Cox models at T times on a caller's device matrix (include/bessx.h section 2p)
 // ----------------------------------------------------------------------------------------------
 namespace {

@@ -113,6 +113,23 @@ hipError_t launch_cox_surv_ex(const void *src, int f32, long long rs, long long 
                               const double *B, const double *zero, double *ex, hipStream_t st);
 hipError_t launch_cox_surv_curves(const double *ex, const double *hg, long long n, int T, int kind, double *out,
                                   long long ors, long long ocs, hipStream_t st);
+// Restricted mean and quantile survival times of one Cox model (bessx_k_coxrmst.hip), from the ex of launch_cox_surv_ex.
+// cox_rmst_pieces (host): the pieces of the segments below the largest of the T cuts -- they end at every distinct cut
+// and after every cox_rmst_slab() segments -- pstart[0 .. NP] (room for max(cut) / cox_rmst_slab() + T + 1 values) and
+// qcut[j] = the pieces in front of cut[j]; returns NP.  cox_rmst_chunk_rows: the rows one launch pair takes, so that its
+// NP * rows doubles of partials stay bounded.  _partial: part[p * nr + i] = sum over the segments k of piece p, ascending,
+// of wd[k] * exp(-(hs[k] * ex[i])) by fused multiply-add; _finish: out[i * ors + colj[s] * ocs] = the sum of the first
+// colq[s] partials of row i (colq ascending, T entries).  _quantile: out[i * ors + j * ocs] = ut[first g with
+// hz[g] * ex[i] >= c[j]], +inf without one, NaN for a NaN ex[i].  Everything but cut / pstart / qcut is device memory.
+int cox_rmst_slab();
+int cox_rmst_pieces(const int *cut, int T, int *pstart, int *qcut);
+long long cox_rmst_chunk_rows(long long n, int NP);
+hipError_t launch_cox_rmst_partial(const double *ex, long long nr, const double *hs, const double *wd, const int *pstart,
+                                   int NP, double *part, hipStream_t st);
+hipError_t launch_cox_rmst_finish(const double *ex, const double *part, long long nr, int NP, const int *colq,
+                                  const int *colj, int T, double *out, long long ors, long long ocs, hipStream_t st);
+hipError_t launch_cox_quantile(const double *ex, long long n, const double *hz, const double *ut, int J, const double *c,
+                               int Q, double *out, long long ors, long long ocs, hipStream_t st);
 // IPCW Brier score of R Cox models at T times (bessx_k_coxbrier.hip).  _ex: e[r * n + i] = exp(clamp(eta(i, r), +-30)) in
 // ROW order (src, cols, B (m x R) as in launch_predict; zero: R doubles of 0.0).  launch_cox_brier: bs[j * R + r] = (1 / W)
 // sum_i (time[i] <= tg[j] ? wa[i] exp(-z)^2 : b[j] w[i] expm1(-z)^2), z = hg[r * T + j] * e[r * n + i]; part: slabs * R * T

@@ -86,6 +86,10 @@ inline CoxCall cox_call(const bessx_cox_survival_input *in) {
   return CoxCall{in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,   in->p, in->cols, in->m,
                  in->B, 1,           nullptr,          nullptr,          nullptr, 1,     static_cast<hipStream_t>(in->stream)};
 }
+inline CoxCall cox_call(const bessx_cox_survtime_input *in) {
+  return CoxCall{in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,   in->p, in->cols, in->m,
+                 in->B, 1,           nullptr,          nullptr,          nullptr, 1,     static_cast<hipStream_t>(in->stream)};
+}
 inline CoxCall cox_call(const bessx_cox_brier_input *in) {  // (no status: row_a and time_b carry what it decides)
   return CoxCall{in->x, in->x_dtype, in->x_row_stride, in->x_col_stride, in->n,   in->p,      in->cols, in->m,
                  in->B, in->R,       in->time,         nullptr,          in->weight, 1,       static_cast<hipStream_t>(in->stream)};

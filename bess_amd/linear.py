@@ -56,6 +56,10 @@ class bess_base:
     right-continuous step function that is 0 before the first event.  For an X in GPU memory both read the support's
     columns in place (capi.cox_baseline_device / capi.cox_survival_device) and the curves are a tensor on X's device that
     is written once; a NumPy X is served in fp64 NumPy.  fit() does not call fit_baseline.
+    predict_rmst(X, tau) and predict_quantile(X, q=0.5) give one number per row from those curves without storing them:
+    the restricted mean survival time to each horizon tau (the integral of the step function S(t | x) over [0, tau]) and
+    the q-quantile of the survival time (q = 0.5: the median; +inf where the curve stays above 1 - q).  For an X in GPU
+    memory both are capi.cox_survival_times_device: one predictor pass, a sum over the steps, a binary search.
     brier_survival(X, y, times, weight=None, censoring="km") says how good those curves are on rows the model may not
     have seen: the time-dependent Brier score under inverse-probability-of-censoring weights, the Kaplan-Meier null
     model's, IPA = 1 - brier / null and the integrated scores.  For an X in GPU memory one fused reduction
@@ -1633,6 +1637,80 @@ class bess_base:
         a = np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta))
         z = np.exp(a)[:, None] * hg[None, :]
         return z if kind == "cumhaz" else np.exp(-z)
+
+    # ---- Cox: restricted mean and quantile survival times ------------------------------------------------------------
+    _SURVTIME_BLOCK = 1 << 23  # elements of the largest temporary of the NumPy routes: 64 MB of float64
+
+    def _survtime_model(self, X, who):
+        """(on_device, n, cols, beta) for predict_rmst / predict_quantile, with their checks."""
+        if self.model_type_int != 4:
+            raise ValueError("%s is for the Cox classes, this is a %s model" % (who, self.model_type))
+        on_device, n = self._survival_x(X)
+        if getattr(self, "baseline_times_", None) is None:
+            raise ValueError("%s needs the baseline hazard: call fit_baseline(X, y) first" % who)
+        beta = np.asarray(self.beta, dtype=np.float64).reshape(-1)
+        return on_device, n, np.nonzero(beta)[0], beta
+
+    def _support_e(self, X, cols, beta):
+        eta = self._support_eta(X, cols, beta)
+        return np.exp(np.where(eta > 30.0, 30.0, np.where(eta < -30.0, -30.0, eta)))  # (a NaN stays a NaN)
+
+    def predict_rmst(self, X, tau):
+        """Cox only, after fit_baseline(): the restricted mean survival times RMST_i(tau_j) = integral_0^tau_j S(t | x_i) dt
+        of the curves of predict_survival, S a step function and the integral therefore a finite sum over the segments of
+        capi.rmst_segments (tau finite and >= 0, any order, repeats allowed; tau = 0 gives 0.0, a baseline without an
+        event gives tau).  Returns (n, T), or (n,) for a tau that is a single number.  No curve is stored: an X in GPU
+        memory is read once on torch's current stream by capi.cox_survival_times_device and gives a tensor on X's device;
+        a NumPy X is served in fp64 NumPy with the same definitions, the segments summed in blocks."""
+        on_device, n, cols, beta = self._survtime_model(X, "predict_rmst")
+        single = np.ndim(tau) == 0
+        tau = np.atleast_1d(np.asarray(tau, dtype=np.float64))
+        if on_device:
+            out = capi.cox_survival_times_device(X, cols, beta[cols], self.baseline_times_, self.baseline_cumhaz_, tau=tau,
+                                                 stream=_current_stream(X))["rmst"]
+            return out[:, 0] if single else out
+        hs, wd, cut = capi.rmst_segments(self.baseline_times_, self.baseline_cumhaz_, tau)
+        if not (hs >= 0.0).all():
+            raise ValueError("base_cumhaz should be non-negative")
+        e = self._support_e(X, cols, beta)
+        out = np.empty((n, cut.size))
+        acc = np.where(np.isnan(e), e, 0.0)  # one running sum per row over the segments in ascending order
+        block = max(1, self._SURVTIME_BLOCK // max(n, 1))
+        k = 0
+        for j in np.argsort(cut, kind="stable"):
+            while k < cut[j]:
+                kk = min(int(cut[j]), k + block)
+                acc = acc + np.exp(-(e[:, None] * hs[None, k:kk])) @ wd[k:kk]
+                k = kk
+            out[:, j] = acc
+        return out[:, 0] if single else out
+
+    def predict_quantile(self, X, q=0.5):
+        """Cox only, after fit_baseline(): the q-quantiles of the survival time of every row, the first baseline time at
+        which S(t | x_i) <= 1 - q, found as the first time at which baseline_cumhaz_ * exp(clip(eta_i)) (one fp64 product)
+        reaches -log1p(-q); +inf where the curve never gets there.  q = 0.5 is the median survival time.  q in (0, 1), a
+        number (the result is (n,)) or 1-D (the result is (n, Q)).  survival::survfit averages two times where S equals
+        1 - q exactly; this does not.  An X in GPU memory is read once on torch's current stream by
+        capi.cox_survival_times_device and gives a tensor on X's device; a NumPy X is served in fp64 NumPy."""
+        on_device, n, cols, beta = self._survtime_model(X, "predict_quantile")
+        single = np.ndim(q) == 0
+        c = capi.survival_levels(q)
+        if on_device:
+            out = capi.cox_survival_times_device(X, cols, beta[cols], self.baseline_times_, self.baseline_cumhaz_,
+                                                 hazard_levels=c, stream=_current_stream(X))["quantile"]
+            return out[:, 0] if single else out
+        ut, hz = capi._quantile_baseline(self.baseline_times_, self.baseline_cumhaz_)
+        e = self._support_e(X, cols, beta)
+        out = np.full((n, c.size), np.inf)
+        rows = max(1, self._SURVTIME_BLOCK // max(hz.size, 1))
+        for i0 in range(0, n if hz.size else 0, rows):
+            z = e[i0:i0 + rows, None] * hz[None, :]
+            for j in range(c.size):
+                hit = z >= c[j]
+                g = hit.argmax(axis=1)  # (hz non-decreasing and e > 0: the first True)
+                out[i0:i0 + rows, j] = np.where(hit[np.arange(g.size), g], ut[g], np.inf)
+        out[np.isnan(e)] = np.nan
+        return out[:, 0] if single else out
 
     # ---- Cox: standard errors and confidence bands of the curves -----------------------------------------------------
     @staticmethod

@@ -1376,6 +1376,84 @@ typedef struct {
 } bessx_cox_zph_input;
 int bessx_cox_zph_device(const bessx_cox_zph_input *in, double *loglik, double *n_events);
 int bessx_cox_zph_workspace(int n, int m, int n_event_rows, long long *doubles, long long *rows_per_slab, int *slabs);
+/* ---------------------------------------------------------------------------------------
+ * 2u. Restricted mean survival times (RMST) and quantile survival times of ONE Cox model on an X already in GPU memory
+ *     (bessx_k_coxrmst.hip): one number per row and horizon / level, and no curve is stored.  Stateless like sections 2c
+ *     to 2t.  x, dtype, strides, n, p, cols, m, B, stream: exactly as in section 2f; e_i = exp(clamp(eta_i, -30, 30)) is
+ *     that section's predictor pass, unchanged, and ONE such pass serves both parts.  S(t | x_i) = exp(-(H0(t) * e_i)),
+ *     every value of it the element bessx_cox_survival_device would write.
+ *
+ *     RMST.  S is a step function, so RMST_i(tau) = integral_0^tau S(t | x_i) dt is a finite sum, and as in section 2f
+ *     the caller does the step-function lookup: hs, wd (K values each, HOST memory) are the baseline cumulative hazard
+ *     on, and the width of, the K segments between consecutive breakpoints (0, the baseline's times, the horizons), and
+ *     cut (T values, HOST memory) the number of segments in front of each horizon:
+ *         rmst(i, j) = sum_{k < cut[j]} wd[k] * exp(-(hs[k] * e_i))
+ *     K >= 0 (K = 0: hs and wd may be NULL), 0 <= cut[j] <= K in any order, repeats allowed; cut[j] = 0 gives exactly 0.0.
+ *     Each term is formed as fma(wd[k], exp(-(hs[k] * e_i)), acc): one rounding per term.  The segments below the largest
+ *     cut are split into pieces that end at every distinct cut and after every 256 segments; a piece is summed in
+ *     ascending order from 0, and a row's pieces are added in ascending order from 0: ADDITIONS ONLY in fp64, in an order
+ *     fixed by (K, cut) alone, every term entering once, no floating-point atomics.  Given e_i, the bits of a row depend
+ *     neither on n, nor on the row's position, nor on the layout or dtype of x, nor on a repeat of the call; two horizons
+ *     with the same cut get the same bits, and along ascending cuts a row never decreases.  e_i is section 2f's: its
+ *     predictor pass adds the support's products in one order for a row-contiguous x (x_col_stride = 1) and in another
+ *     for every other layout, so equal widened values give equal bits within each of the two kinds of layout, for either
+ *     dtype, and across them where m <= 1.
+ *
+ *     Quantiles.  hz, ut (J >= 0 values each, HOST memory): the baseline's cumulative hazards (non-negative and
+ *     non-decreasing) and its times; c (Q levels > 0, HOST memory).  With g* = min{ g : fl(hz[g] * e_i) >= c[j] } -- the
+ *     product one fp64 multiplication, compared as it stands, found by one binary search per (i, j) over hz in device
+ *     memory (multiplication by e_i > 0 is monotone) --
+ *         quant(i, j) = ut[g*],     +inf when there is no such g (J = 0 included).
+ *     For the q-quantile of the survival time the caller passes c = -log1p(-q): quant is then the first baseline time at
+ *     which S(t | x_i) <= 1 - q.  (survival::survfit averages two times where S equals 1 - q exactly; this does not.)
+ *
+ *     Either part may be absent (T = 0 with rmst NULL; Q = 0 with quant NULL); both absent is BESSX_ERR_ARG.  rmst holds
+ *     element (i, j) at [i * rmst_row_stride + j * rmst_col_stride], quant at [i * quant_row_stride + j *
+ *     quant_col_stride], and both are handled exactly as out is in section 2f: out_on_device != 0: device memory of x's
+ *     device, checked as there; otherwise host memory, staged through a device buffer of the library's own.
+ *     A NaN in a support column of row i gives NaN in every output of row i (a horizon with cut 0 included) and nowhere
+ *     else; columns outside the support are not read; x is never written.
+ *     BESSX_ERR_ARG with text, found before any device call, besides those of section 2f for x / cols / B: a NaN or
+ *     negative hs; a wd that is NaN or not positive; a cut outside [0, K]; an hz that decreases, is negative or NaN; a c
+ *     that is NaN or not positive; a NaN in ut; a negative stride, or a zero stride along an axis longer than 1; a
+ *     negative count or a NULL array with a positive count.  Without a GPU a call with valid arguments returns
+ *     BESSX_ERR_HIP.
+ *     Scratch memory: n doubles of e; the K' = max(cut) used segments twice, the pieces' starts and 2 T column entries;
+ *     the partials, NP * rows doubles with NP <= K' / 256 + T the number of pieces and rows = min(n, max(512, 2^24 / NP
+ *     rounded down to a multiple of 512)) the rows taken at a time (at most 2^24 doubles = 128 MiB while NP <= 2^15);
+ *     2 J + Q doubles for the quantiles; n * T and n * Q more for host outputs.  There is no n x K and no n x T
+ *     temporary.  All of it is released before the call returns: counters 38 / 39 are back at their earlier values.
+ *     Measured on an MI355X: n = 200 000, m = 150, K = 139 806, T = 1, Q = 5, fp64 row-major: 27.0 ms
+ *     per call to device outputs, of which the partial kernel 17.8 ms (1 572 G terms/s, bound by the fp64 exp).
+ *     bessx_cox_survtime_workspace needs no device: *slab = 256, and for the given cuts *pieces = NP, *rows_per_chunk and
+ *     *doubles = the doubles of device scratch of a call with device outputs (the quantile part's not included).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const void *x;
+  int x_dtype;
+  long long x_row_stride, x_col_stride;
+  int n, p;
+  const int *cols;
+  int m;
+  const double *B;
+  const double *hs;
+  const double *wd;
+  int K;
+  const int *cut;
+  int T;
+  const double *hz;
+  const double *ut;
+  int J;
+  const double *c;
+  int Q;
+  long long rmst_row_stride, rmst_col_stride;
+  long long quant_row_stride, quant_col_stride;
+  int out_on_device;
+  void *stream;
+} bessx_cox_survtime_input;
+int bessx_cox_survtime_device(const bessx_cox_survtime_input *in, double *rmst, double *quant);
+int bessx_cox_survtime_workspace(int n, const int *cut, int T, int *slab, int *pieces, long long *rows_per_chunk,
+                                 long long *doubles);
 /* screening_A of src/screening.cpp:68: original column of every kept column (ascending).  Returns the number of
  * kept columns (= p when the session was created without screening, map = identity); writes min(count, cap). */
 int bessx_session_get_screening(const bessx_session *s, int *columns, int cap);
@@ -1877,6 +1955,12 @@ int bessx_op_cox_groupscore_bench(const void *x, int dtype, long long row_stride
  * stage_ms[1] k_cbd_band (k_cbd_band0 for m = 0) with the survival / log-log epilogue. */
 int bessx_op_cox_band_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
                             const int *cols, int m, int T, unsigned what, int repeats, double *stage_ms);
+/* The kernels of section 2u timed the same way for K segments, T horizons (cuts spread evenly over the segments), J
+ * baseline times and Q levels, from a B, segments, a baseline and levels of the library's own; the outputs are row-major
+ * device buffers: stage_ms[0] the predictor pass that stores e, [1] k_cxr_partial over every chunk of rows (n * K terms),
+ * [2] k_cxr_finish over every chunk, [3] k_cxr_quantile (n * Q searches). */
+int bessx_op_cox_rmst_bench(const void *x, int dtype, long long row_stride, long long col_stride, int n, int p,
+                            const int *cols, int m, int K, int T, int J, int Q, int repeats, double *stage_ms);
 /* Section 2t's sweep over x for three row-weight pairs of the library's own, device events with one warm-up, `repeats`
  * single timings each way, alternating: fused_ms[i] one launch of the three-weight sweep with its finish, separate_ms[i]
  * three back-to-back launches of section 2g's one-weight sweep with its finish on the same data. */
